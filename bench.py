@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — the grpnet hot path on MI355X, one JSON line per run.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}] [--dump-outputs DIR] [--full]
 
 ``--config`` selects the BASELINE.json workload (default 2, the one the headline metric is quoted on):
 
@@ -10,11 +10,18 @@
   4  binomial lasso (IRLS) on a 2-bit SNP design 500k x 50k (25 % ones, 5 % twos, 10 % missing)      step = one path
   5  ``cv_grpnet`` with 8 folds on the config-2 data                                                 step = one CV (8 fold paths)
 
-The design is resident in HBM when the timed region starts.  Every line carries ``roofline`` (the dominant kernel, timed live
-with HIP events on the stream it runs on, inside the timed steps), ``roofline_path`` (algorithmic matrix bytes
-of the whole path / wall time), the solver's counters, and — rank 0, N = 1 — ``cpu_baseline``: the CPU oracle (``oracle/``, a
-restatement of the reference algorithm with the reference's OpenMP flags; kind "port") on a bounded sample of the same
-workload, on the box's host cores.
+A plain run sets up, runs W untimed and exactly K timed steps, and prints one line: ``value`` (paths/s of the timed steps),
+``ms_per_step`` (wall milliseconds of one timed step), ``roofline`` (the dominant of the kernels timed live with HIP events on
+the stream they run on, inside the timed steps), ``roofline_path`` (algorithmic matrix bytes of the whole path /
+wall time) and the solver's counters.  The design is resident in HBM when the timed region starts.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step returned to its caller as ``DIR/<name>.npy``
+(see ``dump_outputs``); the inputs are generated from fixed seeds, so two builds can be compared output for output.
+
+``--full`` adds everything that takes runs of its own: one extra untimed step with per-launch events on the panel step kernel
+(``roofline_panel_step``), and — rank 0, N = 1 — ``cpu_baseline``: the CPU oracle (``oracle/``, a restatement of the
+reference algorithm with the reference's OpenMP flags; kind "port") on a bounded sample of the same workload, on the box's
+host cores; on the default line also the legs listed below.
 
 Multi-GPU (``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...``, one rank per GPU over RCCL):
   * configs 2-4: every rank holds a replica of the design and solves its own paths; rank r trains on the complement of CV
@@ -22,9 +29,9 @@ Multi-GPU (``python -m torch.distributed.run --nproc-per-node N bench.py --gpus 
     end.  Per-GPU work is fixed: ``"scaling": "weak"``; ``value`` = paths of all ranks / max-over-ranks wall.
   * config 5: ONE 8-fold CV whose folds are sharded over the ranks (fold k on rank k % N, one all_gather of the loss
     table): total work is fixed, ``"scaling": "strong"``.
-  * the default line (config 2) additionally carries the legs ``"cfg3"``, ``"f32"`` (config 2 in single precision) and
-    ``"cfg4"`` — the same measurement as ``--config 3 / 4`` with fewer steps, each with its own roofline objects — unless
-    ``--no-extra-legs`` is given (profiling runs); at N = 1 also ``"standardized_snp_view"`` (a Gaussian path on config 4's
+  * with ``--full``, the default line (config 2) additionally carries the legs ``"cfg3"``, ``"f32"`` (config 2 in single
+    precision) and ``"cfg4"`` — the same measurement as ``--config 3 / 4`` with fewer steps, each with its own roofline
+    objects — unless ``--no-extra-legs`` is given (profiling runs); at N = 1 also ``"standardized_snp_view"`` (a Gaussian path on config 4's
     2-bit design under the lazy standardized view: 6.25 GB resident instead of a 200 GB copy) and ``"sparse_resident"`` (a
     1M x 100k sparse design with 1e8 stored entries kept sparse: 745 GiB as dense f64), ROUNDS.md 9.9, and
   * ``"cv_config5"``: the same sharded CV timed right after the headline
@@ -215,10 +222,11 @@ def gathered_fold_counts(ctx, n_folds):
     return per_rank
 
 
-def measure(ctx, cfg, *, n, p, gs, alpha, dtype, L, steps, warmup, n_folds=8, cv_leg=False, data=None):
+def measure(ctx, cfg, *, n, p, gs, alpha, dtype, L, steps, warmup, n_folds=8, cv_leg=False, panel_leg=False, data=None):
     """One workload: builds (or re-uses) the resident design, runs `warmup` untimed and `steps` timed steps, and returns
     (line, keep): `line` = the JSON object of this workload (value, rooflines, counters), `keep` = what the CPU baseline and a
-    following leg on the same data need (design, response, last result)."""
+    following leg on the same data need (design, response, last result).  `cv_leg` / `panel_leg` (--full): the timed CV of the
+    default line and the extra untimed step with per-launch events on the panel step kernel, both after the timed steps."""
     import adelie_amd as ad
 
     torch, dist, world, rank = ctx.torch, ctx.dist, ctx.world, ctx.rank
@@ -305,7 +313,7 @@ def measure(ctx, cfg, *, n, p, gs, alpha, dtype, L, steps, warmup, n_folds=8, cv
 
     # ---- one extra, untimed step with per-launch events on the panel step kernel (second HBM-bound kernel of the path) --
     panel = None
-    if rank == 0 and cfg in (2, 3, 4):
+    if panel_leg and rank == 0 and cfg in (2, 3, 4):
         os.environ["ADELIE_HIP_TIME_PANEL"] = "1"
         stp = ad.grpnet(Xd, glm, **kw)
         del os.environ["ADELIE_HIP_TIME_PANEL"]
@@ -471,6 +479,36 @@ LEG_KEYS = ("value", "unit", "ms_per_step", "steps", "warmup", "dtype", "config"
             "roofline_gram_mfma", "roofline_panel_step", "breakdown_ms_last_path", "final_active", "final_screen")
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(d, cfg, last, npdtype):
+    """``--dump-outputs DIR``: the arrays the last timed step handed its caller, one ``DIR/<name>.npy`` each, in the run's float
+    type (float32 under ``--dtype f32``, float64 otherwise), DUMP_BUDGET_BYTES at most in all.  grpnet (configs 2-4): lmdas,
+    intercepts, devs and the coefficients as a dense (lambdas, p) array ``betas`` -- or, when that would not fit, the columns of
+    a fixed seeded sample (``betas_sample``, their indices in ``betas_sample_columns``).  cv_grpnet (config 5): lmdas, the
+    (folds, lambdas) loss table ``losses``, ``avg_losses`` and ``best_idx``."""
+    ft = np.float32 if npdtype == np.float32 else np.float64
+    size = np.dtype(ft).itemsize
+    if cfg == 5:
+        arrays = {"lmdas": last.lmdas, "losses": last.losses, "avg_losses": last.avg_losses, "best_idx": [last.best_idx]}
+    else:
+        arrays = {"lmdas": last.lmdas, "intercepts": last.intercepts, "devs": last.devs}
+        B = last.betas.tocsc()
+        L, p = B.shape
+        room = DUMP_BUDGET_BYTES - 1024 * 8 - size * sum(np.size(a) for a in arrays.values())   # (npy headers)
+        k = min(p, room // (size * max(L, 1) + size))
+        if k == p:
+            arrays["betas"] = B.toarray()
+        else:
+            cols = np.sort(np.random.default_rng(0).choice(p, k, replace=False))
+            arrays["betas_sample"] = B[:, cols].toarray()
+            arrays["betas_sample_columns"] = cols
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.asarray(a, dtype=ft))
+
+
 def launch_ranks_if_needed(args):
     """``python bench.py --gpus N`` with N > 1 and no launcher around it: start the N ranks ourselves — re-exec under
     ``torch.distributed.run`` (one process per GPU, rendezvous on 127.0.0.1, RCCL) with the same arguments; rank 0 of the
@@ -527,11 +565,18 @@ def main():
                     help="config 3: CPU budget of the tol = 1e-10 comparison of a lambda prefix (0: skip)")
     ap.add_argument("--cfg4-parity-budget-s", type=float, default=200.0,
                     help="config 4: CPU budget of the coarse-path parity sample with non-zero coefficients (0: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the panel-step roofline step, the CPU baselines and, on "
+                         "the default line, the cv_config5 / cfg3 / f32 / cfg4 / ... legs (the --no-* options trim these)")
     args = ap.parse_args()
     launch_ranks_if_needed(args)
     cfg = args.config
     if args.steps is None:
         args.steps = {2: 3, 3: 2, 4: 1, 5: 3}[cfg]
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     n = args.n or (500_000 if cfg == 4 else 100_000)
     p = args.p or (50_000 if cfg == 4 else 10_000)
     gs = args.group_size or (10 if cfg == 3 else 1)
@@ -541,14 +586,16 @@ def main():
     ctx = Ctx()
     default_line = (cfg == 2 and gs == 1 and alpha == 1.0 and args.dtype == "f64" and args.n is None and args.p is None)
     out, keep = measure(ctx, cfg, n=n, p=p, gs=gs, alpha=alpha, dtype=args.dtype, L=L, steps=args.steps, warmup=args.warmup,
-                        n_folds=args.n_folds, cv_leg=(default_line and not args.no_cv_leg))
+                        n_folds=args.n_folds, cv_leg=(args.full and default_line and not args.no_cv_leg), panel_leg=args.full)
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, cfg, keep["last"], keep["npdtype"])
 
-    if ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
+    if args.full and ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg, args, keep, keep["y"].astype(keep["npdtype"]), keep["glm"], keep["kw"],
                                            keep["cv_kw"], keep["npdtype"], keep["last"], keep["Xd"], n, p)
 
     # ---- the other BASELINE.json configurations, as objects of the default line (N = 1: they are single-GPU workloads) -----
-    if default_line and ctx.world == 1 and not args.no_extra_legs:
+    if args.full and default_line and ctx.world == 1 and not args.no_extra_legs:
         def leg(line):
             return {k: line[k] for k in LEG_KEYS if k in line}
 
@@ -569,7 +616,7 @@ def main():
         if "cv_config5" in out:
             out["cv_config5"]["cpu_baseline"] = cpu_leg(5, keep, n, p)
         # config 3 re-uses the resident design of the headline (same X, grouped penalty)
-        line3, keep3 = measure(ctx, 3, n=n, p=p, gs=10, alpha=0.5, dtype="f64", L=L, steps=2, warmup=1,
+        line3, keep3 = measure(ctx, 3, n=n, p=p, gs=10, alpha=0.5, dtype="f64", L=L, steps=2, warmup=1, panel_leg=True,
                                data={k: keep[k] for k in ("X", "y", "Xd", "Xh") if k in keep})
         out["cfg3"] = leg(line3)
         out["cfg3"]["cpu_baseline"] = cpu_leg(3, keep3, n, p)
@@ -586,12 +633,12 @@ def main():
         gc.collect()
         ctx.torch.cuda.empty_cache()
         # the headline workload in single precision (SURVEY.md 8d asks for both arithmetic types)
-        line32, k32 = measure(ctx, 2, n=n, p=p, gs=1, alpha=1.0, dtype="f32", L=L, steps=3, warmup=1)
+        line32, k32 = measure(ctx, 2, n=n, p=p, gs=1, alpha=1.0, dtype="f32", L=L, steps=3, warmup=1, panel_leg=True)
         out["f32"] = leg(line32)
         del k32, line32
         gc.collect()
         ctx.torch.cuda.empty_cache()
-        line4, k4 = measure(ctx, 4, n=500_000, p=50_000, gs=1, alpha=1.0, dtype="f64", L=L, steps=2, warmup=1)
+        line4, k4 = measure(ctx, 4, n=500_000, p=50_000, gs=1, alpha=1.0, dtype="f64", L=L, steps=2, warmup=1, panel_leg=True)
         out["cfg4"] = leg(line4)
         out["cfg4"]["cpu_baseline"] = cpu_leg(4, k4, 500_000, 50_000)
         # two designs whose dense f64 form does not fit (or barely fits) in HBM, as further objects of the default line

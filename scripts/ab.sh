@@ -14,7 +14,7 @@ while getopts "c:r:s:w:x:" o; do
 done
 shift $((OPTIND - 1))
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-B="python bench.py --no-cpu-baseline --no-cv-leg --no-extra-legs --config $CFG --steps $STEPS --warmup $WARM $EXTRA"
+B="python bench.py --full --no-cpu-baseline --no-cv-leg --no-extra-legs --config $CFG --steps $STEPS --warmup $WARM $EXTRA"
 for ((i = 0; i < ROUNDS; ++i)); do
   for arm in "$@"; do
     env $arm $B 2>gpurun_out/ab_last.err | ARM="$arm" python -c "

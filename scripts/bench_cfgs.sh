@@ -1,8 +1,8 @@
 #!/bin/bash
 # other BASELINE.json configs at scale (not the headline line): group size 10 / alpha 0.5, f32, 8-fold CV on one GPU
 set -x
-python bench.py --steps 1 --warmup 1 --no-cpu-baseline --group-size 10 --alpha 0.5 2>&1 | tail -1 | cut -c1-1500
-python bench.py --steps 1 --warmup 1 --no-cpu-baseline --dtype f32 2>&1 | tail -1 | cut -c1-1200
+python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --group-size 10 --alpha 0.5 2>&1 | tail -1 | cut -c1-1500
+python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --dtype f32 2>&1 | tail -1 | cut -c1-1200
 python - <<'PY'
 import sys, time, numpy as np, torch
 sys.path.insert(0, '.')

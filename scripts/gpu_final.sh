@@ -1,15 +1,23 @@
-# End-of-round artefacts: full -m gpu suite, the default bench line, one bench line per config (with CPU baselines and the
-# parity fields), rocprof summaries (kernel trace + PMC passes per config, constrained path, sparse path).
+# End-of-round artefacts: full -m gpu suite, the default bench line, one bench line per config (--full: with CPU baselines and
+# the parity fields), rocprof summaries (kernel trace + PMC passes per config, constrained path).  Stops at the first failing
+# step.  Results go to $OUT (default out/).  Usage: [OUT=dir] bash scripts/gpu_final.sh <tag>
 TAG=${1:-r05}
-mkdir -p gpurun_out
-timeout 1800 python -m pytest tests -m gpu -q > gpurun_out/${TAG}_gpu_pytest.log 2>&1; echo "pytest rc=$?" | tee -a gpurun_out/${TAG}_gpu_pytest.log
-tail -3 gpurun_out/${TAG}_gpu_pytest.log
-timeout 1200 python bench.py > gpurun_out/${TAG}_default_line.json 2> gpurun_out/${TAG}_default_line.err; echo "default line rc=$?"
-cut -c1-200 gpurun_out/${TAG}_default_line.json
+export OUT=${OUT:-out}
+mkdir -p $OUT
+timeout -k 10 1800 python -m pytest tests -m gpu -q > $OUT/${TAG}_gpu_pytest.log 2>&1
+rc=$?; echo "pytest rc=$rc" | tee -a $OUT/${TAG}_gpu_pytest.log
+tail -3 $OUT/${TAG}_gpu_pytest.log
+[ $rc -eq 0 ] || exit $rc
+timeout -k 10 1200 python bench.py --full > $OUT/${TAG}_default_line.json 2> $OUT/${TAG}_default_line.err
+rc=$?; echo "default line rc=$rc"
+cut -c1-200 $OUT/${TAG}_default_line.json
+[ $rc -eq 0 ] || exit $rc
 for c in 2 3 5 4; do
-  timeout 1200 python bench.py --config $c > gpurun_out/${TAG}_cfg${c}_bench.json 2> gpurun_out/${TAG}_cfg${c}_bench.err; echo "cfg $c rc=$?"
-  cut -c1-200 gpurun_out/${TAG}_cfg${c}_bench.json
+  timeout -k 10 1200 python bench.py --full --config $c > $OUT/${TAG}_cfg${c}_bench.json 2> $OUT/${TAG}_cfg${c}_bench.err
+  rc=$?; echo "cfg $c rc=$rc"
+  cut -c1-200 $OUT/${TAG}_cfg${c}_bench.json
+  [ $rc -eq 0 ] || exit $rc
 done
-for c in 2 3 5 4; do bash scripts/prof_cmd.sh ${TAG} $c > gpurun_out/prof_${TAG}_cfg$c.log 2>&1; done
-bash scripts/prof_cons.sh ${TAG} > /dev/null 2>&1
-ls gpurun_out | grep ${TAG} | head -40
+for c in 2 3 5 4; do bash scripts/prof_cmd.sh ${TAG} $c > $OUT/prof_${TAG}_cfg$c.log 2>&1 || exit 1; done
+bash scripts/prof_cons.sh ${TAG} > /dev/null 2>&1 || exit 1
+ls $OUT | grep ${TAG} | head -40
