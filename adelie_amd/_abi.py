@@ -16,6 +16,8 @@ COL_MAJOR, ROW_MAJOR = 0, 1
 SCREEN_STRONG, SCREEN_PIVOT = 0, 1
 GLM_GAUSSIAN, GLM_BINOMIAL_LOGIT, GLM_GAUSSIAN_IRLS, GLM_MULTINOMIAL, GLM_POISSON, GLM_BINOMIAL_PROBIT = 0, 1, 2, 3, 4, 5
 GLM_CALLBACK = 6  # a Python subclass of glm.GlmBase64/32, evaluated by host callbacks
+GLM_COX = 7  # glm.cox: evaluated on the device from an adelie_hip_glm_cox handle (ABI 11)
+TIE_BRESLOW, TIE_EFRON = 0, 1
 
 # int poll(void* user, int final, int64_t n_solutions, const adelie_hip_result* live)
 POLL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p)
@@ -134,6 +136,7 @@ class GrpnetArgs(C.Structure):
         ("lmda_aug_ratios", C.POINTER(C.c_double)),
         ("n_lmda_aug", C.c_int64),
         ("lmda_aug_min", C.c_double),
+        ("glm_cox", C.c_void_p),
     ]
 
 
@@ -170,6 +173,7 @@ HIP_SYMBOLS = [
     "design_cmul", "design_ctmul", "design_bmul", "design_btmul", "design_mul", "design_mul_batch", "design_cov",
     "design_sq_mul", "design_sp_tmul",
     "design_create_cov_dense", "design_create_cov_lazy", "design_cov_bmul", "design_cov_mul", "design_cov_to_dense", "gaussian_cov_solve",
+    "glm_cox_create", "glm_cox_destroy", "glm_cox_eval",
     "grpnet_solve", "grpnet_solve_many", "result_destroy", "result_size", "result_copy", "result_scalar", "result_error", "result_sync",
     "bench_sweep",
 ]
@@ -189,7 +193,7 @@ def dtype_code(dtype):
 
 
 # kept equal to ADELIE_HIP_ABI_VERSION in include/adelie_hip.h (tests/test_abi.py compares the two)
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class Backend:
@@ -257,6 +261,9 @@ class Backend:
         sig("design_cov", ci, [vp, i64, i64, vp, vp])
         sig("design_sq_mul", ci, [vp, vp, vp])
         sig("design_sp_tmul", ci, [vp, i64, vp, vp, vp, vp])
+        sig("glm_cox_create", ci, [ci, ci, i64, vp, vp, vp, vp, vp, ci, p(vp)])
+        sig("glm_cox_destroy", ci, [vp])
+        sig("glm_cox_eval", ci, [vp, vp, vp, vp, p(dbl)])
         sig("grpnet_solve", ci, [vp, p(GrpnetArgs), p(vp)])
         sig("grpnet_solve_many", ci, [p(vp), p(p(GrpnetArgs)), C.c_int32, p(vp), DONE_FN, vp])
         sig("gaussian_cov_solve", ci, [vp, p(GrpnetArgs), p(vp)])

@@ -1413,6 +1413,8 @@ int adelie_hip_design_glm_path_losses(adelie_hip_design* d, int glm_kind, int64_
     if (!d || !indptr || !intercepts || !offsets || !y || !weights_a || !weights_b || !out)
         throw make_core_error("null argument.");
     if (L < 0) throw make_core_error("L must be >= 0.");
+    if (glm_kind == ADELIE_HIP_GLM_COX || glm_kind == ADELIE_HIP_GLM_CALLBACK || glm_kind == ADELIE_HIP_GLM_MULTINOMIAL)
+        throw make_core_error("glm_path_losses: elementwise single-response families only.");
     if (L > 0) {
         DTYPE_DISPATCH(d, op_path_losses<T>(d, glm_kind, L, indptr, indices, (const T*)values, (const T*)intercepts,
                                             (const T*)offsets, (const T*)y, (const T*)weights_a, (const T*)weights_b, out),

@@ -113,10 +113,12 @@ __global__ __launch_bounds__(RT) void irls_prepare_kernel(int kind, const T* __r
                                                           T* __restrict__ hess, T* __restrict__ irls_resid,
                                                           T* __restrict__ irls_y, T* sums, int K) {
     T acc[1] = {T(0)};
-    // user-defined GLM (kind CALLBACK): hess and irls_resid arrive filled with glm.hessian() / glm.inv_hessian_gradient()
+    // user-defined GLM (kind CALLBACK): hess and irls_resid arrive filled with glm.hessian() / glm.inv_hessian_gradient();
+    // Cox (kind COX): hess arrives filled by the family's device evaluation (kernels_cox.hip)
     const bool cb = kind == ADELIE_HIP_GLM_CALLBACK;
+    const bool pre = cb || kind == ADELIE_HIP_GLM_COX;
     GRID_STRIDE(i, n) {
-        const T h0 = cb ? hess[i] : glm_hess(kind, y[i], w[i], resid[i], eta[i], K);
+        const T h0 = pre ? hess[i] : glm_hess(kind, y[i], w[i], resid[i], eta[i], K);
         const T h = (h0 > T(0) ? h0 : T(0)) + hmin * T(h0 <= T(0));
         const T z = cb ? irls_resid[i] : resid[i] / h; // inv_hessian_gradient uses the same raised hessian (glm_base.ipp:32-36)
         hess[i] = h;
@@ -153,8 +155,9 @@ __global__ __launch_bounds__(RT) void irls_finish_kernel(int kind, const T* __re
     GRID_STRIDE(i, n) {
         const T e = irls_y[i] + off[i] - irls_resid[i] + shift;
         eta[i] = e;
-        // multinomial: row-coupled, below; a user-defined GLM's gradient is a host callback on the new eta
-        if (kind != ADELIE_HIP_GLM_MULTINOMIAL && kind != ADELIE_HIP_GLM_CALLBACK) resid[i] = glm_grad(kind, y[i], w[i], e);
+        // multinomial: row-coupled, below; a user-defined GLM's gradient is a host callback on the new eta, Cox's a device
+        // evaluation over risk sets (kernels_cox.hip)
+        if (kind != ADELIE_HIP_GLM_MULTINOMIAL && kind != ADELIE_HIP_GLM_CALLBACK && kind != ADELIE_HIP_GLM_COX) resid[i] = glm_grad(kind, y[i], w[i], e);
     }
 }
 
@@ -196,8 +199,9 @@ __global__ __launch_bounds__(RT) void null_step_kernel(int kind, const T* __rest
                                                        const T* __restrict__ cb_hess, const T* __restrict__ cb_z) {
     T acc[2] = {T(0), T(0)};
     const bool cb = kind == ADELIE_HIP_GLM_CALLBACK;
+    const bool pre = cb || kind == ADELIE_HIP_GLM_COX; // (Cox: cb_hess holds the family's Hessian, cb_z is not read)
     GRID_STRIDE(i, n) {
-        const T h0 = cb ? cb_hess[i] : glm_hess(kind, y[i], w[i], resid[i], eta[i], K);
+        const T h0 = pre ? cb_hess[i] : glm_hess(kind, y[i], w[i], resid[i], eta[i], K);
         const T h = (h0 > T(0) ? h0 : T(0)) + hmin * T(h0 <= T(0));
         const T z = cb ? cb_z[i] : resid[i] / h;
         acc[0] += h;

@@ -11,6 +11,7 @@
 // p-vector or the design runs in the kernels of kernels_*.hip on the design's stream.  Per BASIL iteration the
 // host receives: the CD kernel's scalar block, the screen coefficients (<= |S| values) and abs_grad (G values).
 #include "common.hpp"
+#include "cox.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -651,6 +652,31 @@ int adelie_hip_set_config(const char* name, double value) {
     } else if (nm == "pool_trim") DevPool::trim();
     else {
         set_last_error("adelie_core: unknown config name.");
+        return 1;
+    }
+    return 0;
+}
+
+int adelie_hip_glm_cox_create(int device, int dtype, int64_t n, const void* start, const void* stop, const void* status,
+                              const int64_t* strata, const void* weights, int tie_method, adelie_hip_glm_cox** out) {
+    try {
+        if (!out) throw make_core_error("null argument.");
+        *out = cox_create(device, dtype, n, start, stop, status, strata, weights, tie_method);
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return 1;
+    }
+    return 0;
+}
+int adelie_hip_glm_cox_destroy(adelie_hip_glm_cox* h) {
+    cox_destroy(h);
+    return 0;
+}
+int adelie_hip_glm_cox_eval(adelie_hip_glm_cox* h, const void* eta, void* grad, void* hess, double* loss) {
+    try {
+        cox_eval_host(h, eta, grad, hess, loss);
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
         return 1;
     }
     return 0;

@@ -69,6 +69,11 @@
     }
     adelie_hip_glm_callbacks glm_cb{};       // glm_kind == CALLBACK: the user's GlmBase subclass, evaluated on the host
     std::vector<T> cb_eta, cb_grad, cb_hess, cb_z;
+    // glm_kind == COX: the family's device pack (kernels_cox.hip) and this solve's own scratch.  cox_hess_ok: d_hess holds the
+    // family's (unraised) Hessian at d_eta; cox_loss_ok: the scratch's loss slot holds the loss at d_eta.
+    const adelie_hip_glm_cox* cox = nullptr;
+    DevBuf<double> d_cox_scr;
+    bool cox_hess_ok = false, cox_loss_ok = false;
     idx max_gs = 1;
     bool all_scalar = true;
     // ---- dynamic host state ----

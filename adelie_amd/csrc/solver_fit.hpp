@@ -313,6 +313,18 @@
 
     // ---- GlmBase members: device kernels for the built-in families, host callbacks for a user-defined one ----
     bool glm_is_cb() const { return glm_kind == ADELIE_HIP_GLM_CALLBACK; }
+    bool glm_is_cox() const { return glm_kind == ADELIE_HIP_GLM_COX; }
+    // Cox: one evaluation on the device (grad / hess may be null); the loss lands in the scratch's loss slot
+    void cox_eval_dev(const T* eta_dev, T* grad_dev, T* hess_dev, bool want_loss) {
+        cox_eval<T>(cox->pack, eta_dev, grad_dev, hess_dev, want_loss, d_cox_scr.p, st);
+        cox_loss_ok = want_loss && eta_dev == d_eta.p;
+    }
+    T cox_loss_now() {
+        double l;
+        AHIP_CHECK(hipMemcpyAsync(&l, d_cox_scr.p + cox_loss_slot(n), sizeof(double), hipMemcpyDeviceToHost, st));
+        sync();
+        return T(l);
+    }
     void cb_fetch(const T* dev, std::vector<T>& host) {
         host.resize(size_t(n));
         AHIP_CHECK(hipMemcpyAsync(host.data(), dev, size_t(n) * sizeof(T), hipMemcpyDeviceToHost, st));
@@ -323,6 +335,10 @@
     }
     // resid = glm.gradient(eta)
     void glm_gradient_dev(const T* eta_dev, T* r_dev) {
+        if (glm_is_cox()) {
+            cox_eval_dev(eta_dev, r_dev, nullptr, false);
+            return;
+        }
         if (!glm_is_cb()) {
             launch_glm_gradient<T>(glm_kind, d_y.p, d_gw.p, eta_dev, n, r_dev, st, mk());
             return;
@@ -335,6 +351,10 @@
     }
     // glm.loss(eta)
     T glm_loss_dev(const T* eta_dev) {
+        if (glm_is_cox()) { // (after an IRLS iteration the loss at d_eta came with its gradient)
+            if (!(cox_loss_ok && eta_dev == d_eta.p)) cox_eval_dev(eta_dev, nullptr, nullptr, true);
+            return cox_loss_now();
+        }
         if (!glm_is_cb()) {
             launch_glm_loss<T>(glm_kind, d_y.p, d_gw.p, eta_dev, n, d_sums.p, st, mk());
             return device_scalar(d_sums.p);
@@ -375,6 +395,8 @@
             // :336-348
             T sums[4];
             if (glm_is_cb()) glm_hessian_cb(d_eta.p, d_r.p, d_hess.p, d_irls_resid.p);
+            if (glm_is_cox() && !cox_hess_ok) cox_eval_dev(d_eta.p, nullptr, d_hess.p, false); // (first iteration of the path)
+            cox_hess_ok = false; // (raised in place below)
             launch_irls_prepare<T>(glm_kind, d_y.p, d_gw.p, d_eta.p, d_r.p, d_off.p, hmin, n, d_hess.p, d_irls_resid.p,
                                    d_irls_y.p, d_sums.p, st, mk());
             d_sums.download(sums, 1, st);
@@ -490,9 +512,14 @@
             // :439-449
             std::swap(d_eta.p, d_eta_prev.p);
             std::swap(d_r.p, d_resid_prev.p);
+            cox_loss_ok = false;
             launch_irls_finish<T>(glm_kind, d_y.p, d_gw.p, d_irls_y.p, d_off.p, d_irls_resid.p,
                                   intercept ? (beta0 - ym) : T(0), n, d_eta.p, d_r.p, d_sums.p, st, mk());
             if (glm_is_cb()) glm_gradient_dev(d_eta.p, d_r.p);
+            if (glm_is_cox()) { // gradient, the Hessian of the next iteration and the loss (deviance) at the new eta, at once
+                cox_eval_dev(d_eta.p, d_r.p, d_hess.p, true);
+                cox_hess_ok = true;
+            }
             launch_dot_diff<T>(d_r.p, d_resid_prev.p, d_eta.p, d_eta_prev.p, n, d_sums.p, st);
             const T conv = device_scalar(d_sums.p);
             if (std::abs(conv) <= irls_tol) {
@@ -558,10 +585,13 @@
         AHIP_CHECK(hipMemcpyAsync(r.p, d_r.p, n * sizeof(T), hipMemcpyDeviceToDevice, st));
         size_t it = 0;
         const T hmin = T(g_hessian_min);
+        cox_hess_ok = false; // (d_hess serves the null model's iterations below)
+        bool null_hess_ok = false;
         while (1) {
             if (it >= irls_max_iters) throw make_solver_error("Maximum IRLS iterations reached.");
             T sums[2];
             if (glm_is_cb()) glm_hessian_cb(e.p, r.p, d_hess.p, d_irls_y.p);
+            if (glm_is_cox() && !null_hess_ok) cox_eval_dev(e.p, nullptr, d_hess.p, false);
             launch_null_step<T>(glm_kind, d_y.p, d_gw.p, e.p, r.p, d_off.p, hmin, n, d_sums.p, st, mk(), d_hess.p, d_irls_y.p);
             d_sums.download(sums, 2, st);
             sync();
@@ -569,7 +599,12 @@
             std::swap(e.p, e_prev.p);
             launch_set_eta<T>(d_off.p, b0, n, e.p, st);
             std::swap(r.p, r_prev.p);
-            glm_gradient_dev(e.p, r.p);
+            if (glm_is_cox()) { // gradient and the next step's Hessian in one evaluation
+                cox_eval_dev(e.p, r.p, d_hess.p, false);
+                null_hess_ok = true;
+            } else {
+                glm_gradient_dev(e.p, r.p);
+            }
             launch_dot_diff<T>(r.p, r_prev.p, e.p, e_prev.p, n, d_sums.p, st);
             const T conv = device_scalar(d_sums.p);
             if (std::abs(conv) <= irls_tol) {

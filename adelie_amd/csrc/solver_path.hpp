@@ -384,6 +384,13 @@
                 throw make_core_error("glm_cb with gradient, hessian and loss is required for a user-defined GLM.");
             glm_cb = *a->glm_cb;
         }
+        cox = nullptr;
+        if (glm_kind == ADELIE_HIP_GLM_COX) {
+            if (!a->glm_cox) throw make_core_error("glm_cox is required for the Cox family.");
+            if (a->glm_cox->device != X->device) throw make_core_error("glm_cox must live on the design's device.");
+            if (a->glm_cox->dtype != X->dtype) throw make_core_error("glm_cox must have the design's dtype.");
+            cox = a->glm_cox;
+        }
         lmda_max = T(a->lmda_max);
         if (a->lmda_path && a->n_lmda_path > 0) lmda_path.assign((const T*)a->lmda_path, (const T*)a->lmda_path + a->n_lmda_path);
         lmda_aug.clear();
@@ -731,6 +738,11 @@
             beta0 = T(a->beta0); loss_null = T(a->loss_null); loss_full = T(a->loss_full);
             irls_max_iters = size_t(a->irls_max_iters); irls_tol = T(a->irls_tol);
             setup_loss_null = a->setup_loss_null;
+            cox_hess_ok = cox_loss_ok = false;
+            if (cox) {
+                if (cox->pack.n != n) throw make_core_error("glm_cox must have one row per row of X.");
+                d_cox_scr.reserve(cox_scratch_doubles(n));
+            }
             sync();
             device_append_screen();
         }

@@ -1,5 +1,5 @@
 """Synthetic data generators — self-contained restatement of the recipes in reference ``adelie/data.py``:
-``dense`` (``:84-219``) and ``snp_unphased`` (``:222-359``), single-response gaussian / binomial only.
+``dense`` (``:84-219``) and ``snp_unphased`` (``:222-359``), single-response gaussian / binomial / cox only.
 Used by the tests and by ``bench.py``."""
 import numpy as np
 
@@ -7,7 +7,7 @@ from . import glm as _glm
 
 
 def _sample_y(glm, eta, beta, rho, snr):
-    """Reference ``data.py:13-82`` (gaussian and binomial branches)."""
+    """Reference ``data.py:13-82`` (gaussian, binomial and cox branches)."""
     n = eta.shape[0]
     signal_scale = np.sqrt(rho * np.sum(beta) ** 2 + (1 - rho) * np.sum(beta ** 2))
     noise_scale = signal_scale / np.sqrt(snr)
@@ -19,6 +19,15 @@ def _sample_y(glm, eta, beta, rho, snr):
         mu = 1 / (1 + np.exp(-eta / noise_scale))
         y = np.random.binomial(1, mu).astype(eta.dtype)
         return _glm.binomial(y=y)
+    if glm == "cox":
+        # reference data.py:50-63: left-truncated survival times with independent censoring
+        eta = eta.ravel()
+        s = np.round(np.random.exponential(1, n))
+        t = 1 + s + np.round(np.exp(eta / noise_scale + np.random.normal(0, 1, n)))
+        C = 1 + s + np.round(np.exp(np.random.normal(0, 1, n)))
+        d = (t < C).astype(eta.dtype)
+        t = np.minimum(t, C)
+        return _glm.cox(start=s, stop=t, status=d)
     raise NotImplementedError(glm)
 
 

@@ -404,3 +404,270 @@ def binomial(y, *, weights=None, link: str = "logit", dtype=None):
             return binomial(y=y, weights=w, dtype=dtype)
 
     return _binomial()
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Cox proportional hazards (reference ``adelie.glm.cox``, ``glm.py:199-371``; arithmetic ``glm_cox.ipp:356-514, 649-748``)
+#
+# Every quantity lives in one of three orders: the caller's row order, "stop order" (rows sorted by (stratum, stop), stable)
+# and "start order" (sorted by (stratum, start), stable).  Strata occupy the same contiguous segment in both sorted orders.
+# A tie group is a run of equal stop times inside a stratum (stop order).  The scans below are truly segmented: a sum never
+# crosses a stratum (or tie group) boundary, so a small stratum after a large one keeps all its digits.
+
+def _seg_cumsum(x, first):
+    """Inclusive prefix sums of ``x`` restarted wherever ``first`` is True (Hillis-Steele doubling: O(n log L) for segments
+    of length <= L, exact segmentation; the association is a fixed tree)."""
+    x = np.array(x, dtype=np.float64, copy=True)
+    n = x.shape[0]
+    # seg_lo[i]: position of the first element of i's segment
+    seg_lo = np.maximum.accumulate(np.where(first, np.arange(n), 0)) if n else np.zeros(0, dtype=np.int64)
+    pos = np.arange(n)
+    d = 1
+    while d < n:
+        m = pos[d:] - d >= seg_lo[d:]
+        if not m.any():
+            break
+        add = np.where(m, x[:-d], 0.0)
+        x[d:] = x[d:] + add
+        d *= 2
+    return x
+
+
+class _CoxOrders:
+    """The weight-free part of a Cox family: sort orders, tie groups and the search positions of the at-risk sums.  Computed
+    once per (start, stop, strata) and shared by every ``reweight`` of the family."""
+
+    def __init__(self, start, stop, strata):
+        n = stop.shape[0]
+        self.n = n
+        self.n_strata = int(strata.max()) + 1 if n else 0
+        self.to = np.lexsort((stop, strata))           # stop order (stable)
+        self.so = np.lexsort((start, strata))          # start order (stable)
+        st = strata[self.to]
+        self.stratum_sorted = st
+        counts = np.bincount(strata, minlength=self.n_strata)
+        self.outer = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        lo = self.outer[st]                            # segment [lo, hi) of each sorted position
+        hi = self.outer[st + 1]
+        pos = np.arange(n)
+        self.seg_first = pos == lo
+        self.seg_last = pos == hi - 1
+        stop_to = stop[self.to]
+        start_so = start[self.so]
+        gflag = self.seg_first.copy()
+        gflag[1:] |= stop_to[1:] != stop_to[:-1]
+        self.gflag = gflag
+        self.gid = np.cumsum(gflag) - 1
+        gstarts = np.flatnonzero(gflag)
+        gends = np.append(gstarts[1:], n)
+        self.gstarts = gstarts
+        self.gstart = gstarts[self.gid]
+        self.gend = gends[self.gid]
+        # at-risk sums need, per stop position q, the first start position of its stratum with start >= stop_to[q]; the
+        # start-order term needs, per start position, the first stop position of its stratum with stop > start_so[q].
+        # Both are searches on the key (stratum, rank of the time among all start and stop times), monotone in both orders.
+        _, ranks = np.unique(np.concatenate([stop_to, start_so]), return_inverse=True)
+        U = np.int64(ranks.max() + 2 if n else 1)
+        key_to = st.astype(np.int64) * U + ranks[:n]
+        key_so = st.astype(np.int64) * U + ranks[n:]
+        b = np.searchsorted(key_so, key_to, side="left")
+        self.bpos = np.where(b < hi, b, -1)           # -1: no start time in the stratum is >= stop_to[q]
+        ub = np.searchsorted(key_to, key_so, side="right")
+        self.ub_m1 = np.where(ub > lo, ub - 1, -1)     # last stop position with stop <= start_so[q]; -1: none
+
+
+def cox(start, stop, status, *, strata=None, weights=None, tie_method: str = "efron", dtype=None):
+    """Cox family (reference ``adelie.glm.cox``, ``glm.py:199-371``):
+
+    ``loss(eta) = -sum_i w_i d_i eta_i + sum_i wbar_i d_i log(sum_{k in R(t_i)} w_k e^eta_k - sigma_i sum_{k in H(t_i)} w_k e^eta_k)``
+
+    summed over strata, with ``R(u) = {k : s_k < u <= t_k}``, ``H(u)`` the events at ``u`` with non-zero weight, ``wbar`` their
+    average weight and ``sigma`` the Efron scales (zero for Breslow).  The numpy members below serve the Python preamble,
+    ``diagnostic``, ``cv_grpnet``'s fold losses and the tests; inside ``grpnet`` the family is evaluated on the device
+    (``kernels_cox.hip``) from a handle the library builds on first use (``_device_handle``)."""
+    status, dtype = _coerce_dtype(status, dtype)
+    return _cox_make(start, stop, status, strata, weights, tie_method, dtype, None)
+
+
+def _cox_make(start, stop, status, strata, weights, tie_method, dtype, orders):
+    n = status.shape[0] if status.ndim == 1 else -1
+    if status.ndim != 1:
+        raise RuntimeError("y must be 1-dimensional.")
+    start = np.array(start, copy=True, dtype=dtype)
+    stop = np.array(stop, copy=True, dtype=dtype)
+    if strata is None:
+        strata = np.zeros(n, dtype=int)
+    strata = np.array(strata, copy=True, dtype=int)
+    # glm_cox.ipp:600-645
+    if start.shape != (n,):
+        raise RuntimeError("start must be (n,) where status is (n,).")
+    if stop.shape != (n,):
+        raise RuntimeError("stop must be (n,) where status is (n,).")
+    if strata.shape != (n,):
+        raise RuntimeError("strata must be (n,) where status is (n,).")
+    if n and strata.min() < 0:
+        raise RuntimeError("strata must take values in {0, ..., M-1}.")
+    if tie_method not in ("efron", "breslow"):
+        raise RuntimeError("Invalid tie method: " + str(tie_method))
+    if orders is None:
+        orders = _CoxOrders(start, stop, strata)
+
+    class _cox(glm_base, _mixin(dtype)):
+        name = "cox"
+
+        def __init__(self):
+            glm_base.__init__(self, status, weights, dtype)
+            self.status = self.y
+            self.start = start
+            self.stop = stop
+            self.strata = strata
+            self.tie_method = tie_method
+            self.core_kind = _abi.GLM_COX
+            self._orders = orders
+            self._handles = {}
+            self._pack_weights()
+
+        def _pack_weights(self):
+            """The weight-dependent part of the pack (stop order): event indicators with non-zero weight, tie sizes, averaged
+            weights ``wbar`` and the tie-breaking scales (glm_cox.ipp:151-264, 302-354)."""
+            o = self._orders
+            w_to = self.weights.astype(np.float64)[o.to]
+            d_to = self.status.astype(np.float64)[o.to]
+            ind = d_to * (w_to != 0)
+            if o.n:
+                size = np.add.reduceat(ind, o.gstarts)[o.gid] * ind
+                wsum = np.add.reduceat(w_to * ind, o.gstarts)[o.gid] * ind
+            else:
+                size = wsum = np.zeros(0)
+            wbar = np.divide(wsum, size, out=np.zeros_like(wsum), where=size > 0)
+            if self.tie_method == "breslow" or not o.n:
+                scale = np.zeros(o.n)
+            else:
+                cum = np.cumsum(ind)
+                k = cum - ind - (cum - ind)[o.gstart]    # events with non-zero weight before q in its tie group
+                scale = np.divide(k * ind, size, out=np.zeros(o.n), where=size > 0)
+            self._ind, self._size, self._wbar, self._scale = ind, size, wbar, scale
+            self._dw = d_to * wbar
+
+        def _risk_total(self, eta):
+            """z = w exp(eta - c) with c = max eta (row order) and the risk totals of the events (stop order):
+            sum_{k in R(t_q)} z_k - sigma_q sum_{k in H(t_q)} z_k."""
+            o = self._orders
+            eta = np.asarray(eta, dtype=np.float64)
+            c = eta.max()
+            z = self.weights.astype(np.float64) * np.exp(eta - c)
+            z_to, z_so = z[o.to], z[o.so]
+            s_stop = _seg_cumsum(z_to[::-1], o.seg_last[::-1])[::-1]     # sum over stop order from q to the stratum's end
+            s_start = _seg_cumsum(z_so[::-1], o.seg_last[::-1])[::-1]
+            ties = np.add.reduceat(z_to * self._ind, o.gstarts)[o.gid] * self._ind
+            risk = s_stop[o.gstart] - np.where(o.bpos >= 0, s_start[np.maximum(o.bpos, 0)], 0.0)
+            return z, risk - self._scale * ties, c
+
+        def _risk_scaled(self, v, sc):
+            """Row order: sum over the events i with z_row in R(t_i) of v_i, minus the tie term sc_i v_i over the row's own
+            event tie (glm_cox.ipp:439-446): the factor of z (gradient) or z^2 (Hessian)."""
+            o = self._orders
+            P = _seg_cumsum(v, o.seg_first)
+            tie = np.add.reduceat(v * sc * self._ind, o.gstarts)[o.gid] * self._ind
+            acc = np.empty(o.n)
+            acc[o.to] = P[o.gend - 1] - tie
+            acc[o.so] -= np.where(o.ub_m1 >= 0, P[np.maximum(o.ub_m1, 0)], 0.0)
+            return acc
+
+        def _grad_hess(self, eta, want_hess):
+            w = self.weights.astype(np.float64)
+            wd = w * self.status.astype(np.float64)
+            if self._orders.n == 0:
+                return np.zeros(0), np.zeros(0)
+            z, rt, _ = self._risk_total(eta)
+            nz = self._dw != 0
+            v = np.divide(self._dw, rt, out=np.zeros_like(rt), where=nz)
+            grad = wd - z * self._risk_scaled(v, self._scale)
+            if not want_hess:
+                return grad, None
+            v2 = np.divide(v, rt, out=np.zeros_like(rt), where=nz)
+            return grad, wd - grad - z * z * self._risk_scaled(v2, self._scale * (2 - self._scale))
+
+        def gradient(self, eta, grad):
+            grad[...] = self._grad_hess(eta, False)[0]
+
+        def hessian(self, eta, grad, hess):
+            # (recomputed from eta: `grad` is the gradient at eta, as for every family)
+            hess[...] = self._grad_hess(eta, True)[1]
+
+        def loss(self, eta):
+            if self._orders.n == 0:
+                return self.dtype(0)
+            mx = np.finfo(self.dtype).max
+            _, rt, c = self._risk_total(eta)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                lg = np.maximum(np.log(np.maximum(rt, 0)), -mx)
+            wd = self.weights.astype(np.float64) * self.status
+            return -np.sum(wd * (np.asarray(eta, dtype=np.float64) - c)) + np.sum(np.where(self._dw != 0, self._dw * lg, 0.0))
+
+        def loss_full(self):
+            mx = np.finfo(self.dtype).max
+            with np.errstate(divide="ignore", invalid="ignore"):
+                lg = np.maximum(np.log(self._size * self._wbar * (1 - self._scale)), -mx)
+            return self.dtype(np.sum(np.where(self._dw != 0, self._dw * lg, 0.0)))
+
+        def inv_link(self, eta, out):
+            out[...] = np.exp(eta)
+
+        def reweight(self, weights=None):
+            w = self.weights if weights is None else weights
+            return _cox_make(self.start, self.stop, self.status, self.strata, w, self.tie_method, dtype, self._orders)
+
+        def _device_handle(self, device):
+            """``adelie_hip_glm_cox`` of this family on ``device``, created on first use and kept with the family (immutable:
+            every solve that uses it brings its own scratch)."""
+            h = self._handles.get(device)
+            if h is None:
+                h = _CoxHandle(self, device)
+                self._handles[device] = h
+            return h
+
+        def _device_eval(self, eta, device=0, *, grad=True, hess=True, loss=True):
+            """One evaluation of the family on the device (``adelie_hip_glm_cox_eval``): (grad, hess, loss), None where not
+            asked for."""
+            return self._device_handle(device).eval(eta, grad=grad, hess=hess, loss=loss)
+
+    return _cox()
+
+
+class _CoxHandle:
+    """Owner of one ``adelie_hip_glm_cox`` handle."""
+
+    def __init__(self, fam, device):
+        b = _abi.hip_backend()
+        self._b = b
+        self.dtype = fam.dtype
+        self.n = fam.status.shape[0]
+        self.device = device
+        h = _abi.C.c_void_p()
+        start, stop, status, weights = [np.ascontiguousarray(a, dtype=fam.dtype)
+                                        for a in (fam.start, fam.stop, fam.status, fam.weights)]
+        strata = np.ascontiguousarray(fam.strata, dtype=np.int64)
+        tie = _abi.TIE_EFRON if fam.tie_method == "efron" else _abi.TIE_BRESLOW
+        b.check(b.fn("glm_cox_create")(int(device), _abi.dtype_code(fam.dtype), self.n, start.ctypes.data, stop.ctypes.data,
+                                       status.ctypes.data, strata.ctypes.data, weights.ctypes.data, tie, _abi.C.byref(h)))
+        self.h = h
+
+    def eval(self, eta, *, grad=True, hess=True, loss=True):
+        eta = np.ascontiguousarray(eta, dtype=self.dtype)
+        if eta.shape != (self.n,):
+            raise RuntimeError("eta must be (n,).")
+        g = np.empty(self.n, dtype=self.dtype) if grad else None
+        h = np.empty(self.n, dtype=self.dtype) if hess else None
+        lo = _abi.C.c_double(0)
+        self._b.check(self._b.fn("glm_cox_eval")(self.h, eta.ctypes.data, _abi.ptr(g), _abi.ptr(h),
+                                                 _abi.C.byref(lo) if loss else None))
+        return g, h, (lo.value if loss else None)
+
+    def __del__(self):
+        h = getattr(self, "h", None)
+        if h is not None and h.value:
+            try:
+                self._b.fn("glm_cox_destroy")(h)
+            except Exception:  # noqa: BLE001 (interpreter shutdown)
+                pass

@@ -703,6 +703,11 @@ class glm_naive_base(base):
             cbs = self._glm_callbacks(g, len(y))
             keep.append(cbs)
             a.glm_cb = _abi.C.pointer(cbs)
+        elif kind == _abi.GLM_COX:  # the family's device pack, created on the design's device the first time it is needed
+            X = self._X
+            h = g._device_handle(int(X._backend.fn("design_device")(X._handle)))
+            keep.append(h)
+            a.glm_cox = h.h.value
         a.glm_y = y.ctypes.data
         a.glm_weights = w.ctypes.data
         a.offsets = off.ctypes.data

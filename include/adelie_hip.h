@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define ADELIE_HIP_ABI_VERSION 10
+#define ADELIE_HIP_ABI_VERSION 11
 
 enum adelie_hip_dtype { ADELIE_HIP_F32 = 0, ADELIE_HIP_F64 = 1 };
 enum adelie_hip_order { ADELIE_HIP_COL_MAJOR = 0, ADELIE_HIP_ROW_MAJOR = 1 };
@@ -42,6 +42,8 @@ enum adelie_hip_glm_kind {
     ADELIE_HIP_GLM_CALLBACK = 6,        /* a GlmBase subclass written by the user (Python trampoline PyGlmBase, py_glm.cpp:8-92):
                                            StateGlmNaive + IRLS with gradient / hessian / loss evaluated by the host
                                            callbacks of adelie_hip_glm_callbacks on n-vectors, once per IRLS iteration */
+    ADELIE_HIP_GLM_COX = 7,             /* glm.cox (glm_cox.ipp): StateGlmNaive + IRLS, the family evaluated on the device from the
+                                           adelie_hip_glm_cox handle in adelie_hip_grpnet_args::glm_cox (ABI 11) */
     ADELIE_HIP_GLM_MULTINOMIAL = 3      /* glm.multinomial: StateMultiGlmNaive (solver_multiglm_naive.hpp) + IRLS; the design must
                                            be a multi-response view (adelie_hip_design_create_multi).  glm_y is (n, K) row-major,
                                            glm_weights is (n,), offsets / eta / resid are (n, K) row-major (glm_multinomial.ipp) */
@@ -50,6 +52,7 @@ enum adelie_hip_glm_kind {
 /* Opaque handles. */
 typedef struct adelie_hip_design adelie_hip_design; /* device-resident MatrixNaiveBase object */
 typedef struct adelie_hip_result adelie_hip_result; /* solved state snapshot (the `state` copy _solve returns) */
+typedef struct adelie_hip_glm_cox adelie_hip_glm_cox; /* ABI 11: a Cox family's sort orders and weights, resident on one device */
 
 /* ------------------------------------------------------------------------------------------
  * Library
@@ -291,6 +294,20 @@ typedef struct adelie_hip_linear_constraint {
     double         cfg[7];  /* max_iters, tol, nnls_max_iters, nnls_tol, pinball_max_iters, pinball_tol, slack */
 } adelie_hip_linear_constraint;
 
+/* ABI 11.  Cox proportional-hazards family (reference GlmCox{32,64}, glm_cox.hpp / glm_cox.ipp).
+ * create: start, stop, status, weights are (n,) HOST arrays of `dtype`, strata (n,) int64 in {0, ..., M-1} (NULL: one stratum),
+ *   tie_method ADELIE_HIP_TIE_BRESLOW / _EFRON.  The library sorts (stratum, stop) and (stratum, start) (stable), finds the tie
+ *   groups, the search positions of the at-risk sums, the tie sizes, averaged weights and Efron scales on the host, and uploads
+ *   them once to `device`.  The handle is immutable afterwards: every solve / evaluation that uses it brings its own scratch,
+ *   so concurrent solves may share it.  Weights are used as given (glm.cox normalises them).
+ * eval: one evaluation at eta on the handle's device; eta (n,) HOST, grad / hess (n,) HOST outputs of `dtype` (the negative
+ *   gradient and the diagonal Hessian of GlmCox), *loss; any output may be NULL.  Synchronous. */
+enum adelie_hip_tie_method { ADELIE_HIP_TIE_BRESLOW = 0, ADELIE_HIP_TIE_EFRON = 1 };
+int adelie_hip_glm_cox_create(int device, int dtype, int64_t n, const void* start, const void* stop, const void* status,
+                              const int64_t* strata, const void* weights, int tie_method, adelie_hip_glm_cox** out);
+int adelie_hip_glm_cox_destroy(adelie_hip_glm_cox* h);
+int adelie_hip_glm_cox_eval(adelie_hip_glm_cox* h, const void* eta, void* grad, void* hess, double* loss);
+
 typedef struct adelie_hip_grpnet_args {
     /* ---- problem (static) ---- */
     int64_t        G;                 /* number of groups */
@@ -412,6 +429,8 @@ typedef struct adelie_hip_grpnet_args {
     const double*  lmda_aug_ratios;
     int64_t        n_lmda_aug;
     double         lmda_aug_min;
+    /* ABI 11: the family of glm_kind ADELIE_HIP_GLM_COX (required iff that kind; on the design's device).  NULL otherwise. */
+    const adelie_hip_glm_cox* glm_cox;
 } adelie_hip_grpnet_args;
 
 /* Runs the whole path.  `*out` is always set on return code 0 (even when the solve recorded
