@@ -18,7 +18,7 @@
 namespace ahip {
 
 // ---- every environment hook of libadelie_hip.so, in one place ------------------------------------------------------------------
-// Eleven variables.  They are read when a solve starts (Hooks::from_env, one call per solve): the tests force the multi-CU engines
+// Ten variables.  They are read when a solve starts (Hooks::from_env, one call per solve): the tests force the multi-CU engines
 // at sizes the CPU checker finishes in seconds and compare variants between two solves of ONE process, so reading them once at
 // library load would freeze the first test's setting.  None changes results beyond rounding.  (Python side: ADELIE_HIP_LIB picks
 // another build of this library, ADELIE_HIP_SWEEP_BATCH=0 keeps concurrent CV folds from sharing their sweeps.)
@@ -29,7 +29,6 @@ namespace ahip {
 //   ADELIE_HIP_SPECULATE=0        no speculative first active-set pass behind the invariance sweep                  [A/B, bit-identity test]
 //   ADELIE_HIP_IRLS_REUSE=theta   IRLS diagonal-block / Gram reuse threshold (default 0.1, 0 = rebuild per iteration) [documented deviation]
 //   ADELIE_HIP_CONS_HOST=1        box / one-sided constraint objects visited on the host instead of kernels_cons.hip  [A/B, tests]
-//   ADELIE_HIP_GROUP_NEXT_CORR=0  group look-ahead: the next block's correction formed by its own solve              [A/B]
 //   ADELIE_HIP_SPARSE_PANEL=0     IRLS on a design kept sparse on the full-Gram engines instead of the panel engine    [A/B, tests]
 //   ADELIE_HIP_STD_PANEL=0        standardized dense / 2-bit views on their full-Gram engines instead of the panel engines [A/B, tests]
 //   ADELIE_HIP_TIME_PANEL=1       per-launch HIP events around the panel step (bench.py's roofline leg)
@@ -37,17 +36,13 @@ namespace ahip {
 struct Hooks {
     long long cd_block_min_nv = -1; // -1: unset
     int panel_bsz = 0;
-    int sparse_panel = -1;
-    int std_panel = -1;      // ADELIE_HIP_STD_PANEL=0: a standardized dense / 2-bit view stays on its full-Gram engines            [A/B hook]   // ADELIE_HIP_SPARSE_PANEL=0: IRLS on a design kept sparse stays on the full-Gram engines      [A/B hook]
+    int sparse_panel = -1;   // ADELIE_HIP_SPARSE_PANEL=0: IRLS on a design kept sparse stays on the full-Gram engines
+    int std_panel = -1;      // ADELIE_HIP_STD_PANEL=0: a standardized dense / 2-bit view stays on its full-Gram engines
     int lookahead = -1, speculate = -1;
     double irls_reuse = -1;
     bool time_panel = false;
-    int group_next_corr = -1; // ADELIE_HIP_GROUP_NEXT_CORR=0: every group solve forms its own look-ahead correction (A/B)
     bool cons_host = false; // ADELIE_HIP_CONS_HOST=1: box / one-sided objects on several coefficients visited on the host (A/B, tests)
     int trace = 0;
-    int solve_sums = -1;    // ADELIE_HIP_SOLVE_SUMS=0: the sequential panel form keeps its panel_reduce launch per block             [A/B hook]
-    int step_tail = -1;     // ADELIE_HIP_STEP_TAIL=0: 2-bit designs keep the panel_reduce launch behind every sequential step        [A/B hook]
-    int step_means = -1;    // ADELIE_HIP_STEP_MEANS=1: IRLS takes the column means from the panel steps (no mean sweep per iteration)   [A/B hook]
     static Hooks from_env() {
         Hooks h;
         if (const char* e = std::getenv("ADELIE_HIP_CD_BLOCK_MIN_NV")) h.cd_block_min_nv = std::atoll(e);
@@ -60,13 +55,9 @@ struct Hooks {
         if (const char* e = std::getenv("ADELIE_HIP_IRLS_REUSE")) h.irls_reuse = std::max(0.0, std::atof(e));
         h.time_panel = std::getenv("ADELIE_HIP_TIME_PANEL") != nullptr;
         if (const char* e = std::getenv("ADELIE_HIP_CONS_HOST")) h.cons_host = std::atoi(e) != 0;
-        if (const char* e = std::getenv("ADELIE_HIP_GROUP_NEXT_CORR")) h.group_next_corr = std::atoi(e) != 0;
         if (const char* e = std::getenv("ADELIE_HIP_SPARSE_PANEL")) h.sparse_panel = std::atoi(e) != 0;
         if (const char* e = std::getenv("ADELIE_HIP_STD_PANEL")) h.std_panel = std::atoi(e) != 0;
         if (const char* e = std::getenv("ADELIE_HIP_TRACE")) h.trace = std::max(1, std::atoi(e));
-        if (const char* e = std::getenv("ADELIE_HIP_SOLVE_SUMS")) h.solve_sums = std::atoi(e) != 0;
-        if (const char* e = std::getenv("ADELIE_HIP_STEP_MEANS")) h.step_means = std::atoi(e) != 0;
-        if (const char* e = std::getenv("ADELIE_HIP_STEP_TAIL")) h.step_tail = std::atoi(e) != 0;
         return h;
     }
 };

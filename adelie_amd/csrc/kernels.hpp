@@ -201,12 +201,9 @@ void set_small_gram_workgroups(int wgs); // kernels_gram.hip: spread of the next
 template <class T>
 void launch_syrk_batch(const DenseView<T>& X, const T* w, const int32_t* cols_base, const SyrkBatch& b, const T* xm_by_col,
                        bool center, T* C_base, int64_t ldc, T* work, hipStream_t s);
-// xm_build != nullptr (blocks of 33-64 columns on a 2-bit design, syrk_batch_snp_brings_means): the build computes the weighted
-// means of its own columns on the side, leaves them in xm_build (by design column) and centres with THEM instead of xm_by_col
 template <class T>
 void launch_syrk_batch_snp(const SnpView& X, const T* impute, const T* w, const int32_t* cols_base, const SyrkBatch& b,
-                           const T* xm_by_col, bool center, T* C_base, int64_t ldc, T* work, hipStream_t s, T* xm_build = nullptr);
-bool syrk_batch_snp_brings_means(const SyrkBatch& b);
+                           const T* xm_by_col, bool center, T* C_base, int64_t ldc, T* work, hipStream_t s);
 template <class T>
 void launch_syrk(const DenseView<T>& X, const T* w, const int32_t* cols, int32_t M, const T* xm_by_col, bool center, T* C,
                    int64_t ldc, T* work, hipStream_t s);
@@ -494,19 +491,14 @@ int cd_block_size();
 template <class T> void launch_cd_block_pass(const CdBlkParams<T>& p, hipStream_t s);
 // ---- panel form (kernels_cd_panel.hip): residual-based block passes ------------------------------------------------
 // step: r -= sum_{m < *nz_dev} dlt[m] X[:, dcol[m]]; then part[c][slice] = X[slice, cols[c]] . (w*r)[slice] for c < nb.
-// Returns the number of row slices.  `part` holds panel_part_elems(n) elements.  `slice_major`: part[slice * 128 + c] instead,
-// the layout the stand-alone solve sums itself (CdBlkParams::part with part_ld == 0: no panel_reduce launch in between).
+// Returns the number of row slices.  `part` holds panel_part_elems(n) elements.
 template <class T>
 int launch_panel_step(const DenseView<T>& X, const T* w, T* r, const int32_t* dcol, const T* dlt, const int32_t* nz_dev,
-                      const int32_t* cols, int nb, T* part, hipStream_t s, bool slice_major = false);
+                      const int32_t* cols, int nb, T* part, hipStream_t s);
 // `tail` (2-bit designs, the one-word-per-lane kernel only; *tailed says whether it was used): the step sums its own partials
 // -- the last eight workgroups to finish take eight columns each once every workgroup's partials are out -- and leaves the
 // block's gradient in tail->g (what panel_reduce would: - rsum[0] * xm[cols[c]] applied): no reduce launch behind the step.
 // `counter` counts finished workgroups monotonically over the launches of one solver; `base` = its value before this launch.
-// Means mode (xm_col != nullptr; IRLS with an intercept): phase (B) also accumulates sum_i x_ic w_i, the CURRENT weighted mean of
-// every column it reads; the tail centres the gradient with it and leaves it where the solve and later steps look (by design
-// column in xm_col, by screen value in sxm[list ? list[pos0 + c] : pos0 + c]) -- no sweep over the screen columns per IRLS
-// iteration for the means.
 template <class T>
 struct StepTail {
     int32_t* counter;
@@ -514,16 +506,10 @@ struct StepTail {
     T* g;
     const T* rsum;
     const T* xm; // by design column, or nullptr (no intercept term)
-    T* xm_col;           // means mode: out, by design column
-    T* sxm;              // means mode: out, by screen value
-    const int32_t* list; // the pass's visiting list (nullptr: screen order)
-    int32_t pos0;        // list position of the block's first coordinate
 };
-// whether launch_panel_step_snp would take the kernel that can run a StepTail on this design
-bool panel_step_snp_has_tail(const SnpView& X);
 template <class T>
 int launch_panel_step_snp(const SnpView& X, const T* impute, const T* w, T* r, const int32_t* dcol, const T* dlt,
-                          const int32_t* nz_dev, const int32_t* cols, int nb, T* part, hipStream_t s, bool slice_major = false,
+                          const int32_t* nz_dev, const int32_t* cols, int nb, T* part, hipStream_t s,
                           const StepTail<T>* tail = nullptr, bool* tailed = nullptr);
 int64_t panel_part_elems(int64_t n);
 // Opening of a look-ahead pass whose block-0 gradient already exists: g[c] = grad[cols[c]] (c < nb) out of the full gradient

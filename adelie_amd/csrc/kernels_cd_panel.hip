@@ -9,7 +9,7 @@
 //                        (B) partial gradients of the next block on the same slice,
 //                            part[c][slice] = X[slice, col_c] . (w*r)[slice]   (cmul of pin_naive:84-86)
 //                        r is read and written once per block; the block's columns are read once for (B) and, if they
-//                        changed, once more for (A) of the following step (second read served by the 256 MB MALL).
+//                        changed, once more for (A) of the following step (from HBM again: DESIGN.md §4).
 //   panel_reduce_kernel  sums the slice partials in a fixed order and applies the intercept term  - resid_sum * xbar_c.
 //   blk_solve_kernel     (kernels_cd_block.hip, NAIVE variant, ONE workgroup) runs the block's visits in order against
 //                        the B x B block  D = X_B^T W X_B - xbar xbar^T  (computed once per block and weight vector by
@@ -18,7 +18,6 @@
 // Compared with keeping the full |S| x |S| Gram matrix current, the MFMA work drops from n|S|^2/2 to 128 n |S| MACs and
 // nothing has to be recomputed per IRLS iteration except the blocks that are actually visited.  The iterates are the
 // Gauss-Seidel sequence of the reference in exact arithmetic.
-#include <cstdlib>
 #include "kernels.hpp"
 #include "accessors.hpp"
 #include "wavered.hpp"
@@ -33,8 +32,8 @@ constexpr int PB = 128;
 constexpr int PT = 256;
 
 // Raw (undecoded) row-slice loads: VEC consecutive rows of one column per lane.  Dense: the values themselves, with
-// temporal (cache-allocating) loads because the block's columns are read again by the next step.  SNP: the byte
-// holding the four 2-bit calls, decoded at use (keeps 16 loads in flight within the register budget).
+// non-temporal (streaming) loads in both phases, since the second read of a block's columns comes from HBM as well.  SNP:
+// the byte holding the four 2-bit calls, decoded at use (keeps 16 loads in flight within the register budget).
 template <class T, int VEC>
 struct RawDense { Pack<T, VEC> v; };
 struct RawSnp { unsigned byte; };
@@ -42,15 +41,7 @@ struct RawSnp { unsigned byte; };
 // `full` == false (only in the ragged last slice): lanes whose rows lie beyond n read from row 0 instead (a valid
 // address) and every out-of-range element is zeroed by a select — no branches, so the loads of a batch stay in flight
 // together (a branchy tail path made the one ragged workgroup the slowest of the launch by ~10 us).
-// Load policy of the two phases (dense designs).  Phase (B) is the FIRST read of a block's columns, phase (A) of the step two
-// launches later the SECOND and last one: 1 = non-temporal (streaming) load, 0 = plain (allocating) load.
-#ifndef AHIP_PANEL_NT_A
-#define AHIP_PANEL_NT_A 1
-#endif
-#ifndef AHIP_PANEL_NT_B
-#define AHIP_PANEL_NT_B 1
-#endif
-template <class T, int VEC, bool NTL = true>
+template <class T, int VEC>
 __device__ __forceinline__ RawDense<T, VEC> praw(const DenseAcc<T>& X, int64_t j, int64_t i, int64_t n, bool full) {
     RawDense<T, VEC> r;
     const T* col = X.colptr(j);
@@ -62,15 +53,13 @@ __device__ __forceinline__ RawDense<T, VEC> praw(const DenseAcc<T>& X, int64_t j
         static_assert(VEC == VecOf<T>::N, "dense vector width");
         // vector path requires ld % VEC == 0, so a lane starting below n may read up to VEC-1 pad elements: in bounds
         const int64_t ii = (full || i < n) ? i : 0;
-        V x;
-        if constexpr (NTL) x = __builtin_nontemporal_load(reinterpret_cast<const V*>(col + ii));
-        else x = *reinterpret_cast<const V*>(col + ii);
+        const V x = __builtin_nontemporal_load(reinterpret_cast<const V*>(col + ii));
 #pragma unroll
         for (int e = 0; e < VEC; ++e) r.v.v[e] = (full || i + e < n) ? x[e] : T(0);
     }
     return r;
 }
-template <class T, int VEC, bool NTL = true>
+template <class T, int VEC>
 __device__ __forceinline__ RawSnp praw(const SnpAcc<T>& X, int64_t j, int64_t i, int64_t n, bool full) {
     static_assert(VEC == 4 || VEC == 16, "one byte (4 calls) or one 32-bit word (16 calls) per lane");
     RawSnp r;
@@ -130,7 +119,7 @@ __device__ __forceinline__ void panel_step_body(const Acc& X, int64_t n, const T
 #pragma unroll
         for (int u = 0; u < UB; ++u) jb[u] = cols[min(wv + 4 * u, nb - 1)];
 #pragma unroll
-        for (int u = 0; u < UB; ++u) xb[u] = praw<T, VEC, AHIP_PANEL_NT_B != 0>(X, jb[u], i, n, full);
+        for (int u = 0; u < UB; ++u) xb[u] = praw<T, VEC>(X, jb[u], i, n, full);
     }
 
     // ---- (A) residual slice -= X[slice, changed columns] * del ---------------------------------------------------------
@@ -149,7 +138,7 @@ __device__ __forceinline__ void panel_step_body(const Acc& X, int64_t n, const T
                 cf[u] = m < nz ? dlt[min(m, nz - 1)] : T(0);
             }
 #pragma unroll
-            for (int u = 0; u < U; ++u) xa[u] = praw<T, VEC, AHIP_PANEL_NT_A != 0>(X, ja[u], i, n, full);
+            for (int u = 0; u < U; ++u) xa[u] = praw<T, VEC>(X, ja[u], i, n, full);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const Pack<T, VEC> xx = pdecode<T, VEC>(X, xa[u], ja[u], i, n);
@@ -189,7 +178,7 @@ __device__ __forceinline__ void panel_step_body(const Acc& X, int64_t n, const T
 #pragma unroll
             for (int u = 0; u < UB; ++u) jb[u] = cols[min(c0 + 4 * u, nb - 1)];
 #pragma unroll
-            for (int u = 0; u < UB; ++u) xb[u] = praw<T, VEC, AHIP_PANEL_NT_B != 0>(X, jb[u], i, n, full);
+            for (int u = 0; u < UB; ++u) xb[u] = praw<T, VEC>(X, jb[u], i, n, full);
         }
         T pu[UB];
 #pragma unroll
@@ -275,12 +264,12 @@ __device__ __forceinline__ void snp16_decode(unsigned word, T imp, int64_t i, in
     }
 }
 
-template <class T, bool FULL, bool MEANS>
+template <class T, bool FULL>
 __device__ __forceinline__ void panel_step_snp16_body(const SnpAcc<T>& X, int64_t n, const T* __restrict__ w, T* __restrict__ r,
                                                       const int32_t* __restrict__ dcol, const T* __restrict__ dlt, int nz,
                                                       const int32_t* __restrict__ cols, int nb, T* __restrict__ part,
-                                                      int64_t part_ld, T (*red)[S16_RS], T* wrs, T* wsl, T* psum, T* psum2,
-                                                      const T* ptab, int t, int64_t slice) {
+                                                      int64_t part_ld, T (*red)[S16_RS], T* wrs, T* psum, const T* ptab, int t,
+                                                      int64_t slice) {
     constexpr int U = 16;
     const int lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -366,7 +355,6 @@ __device__ __forceinline__ void panel_step_snp16_body(const SnpAcc<T>& X, int64_
             if (ok) r[q0 + k] = rr;
         }
         wrs[q] = ok ? wq[k] * rr : T(0);
-        if constexpr (MEANS) wsl[q] = ok ? wq[k] : T(0);
     }
     if (nb <= 0) return;
     __syncthreads();
@@ -374,11 +362,6 @@ __device__ __forceinline__ void panel_step_snp16_body(const SnpAcc<T>& X, int64_
     T wr[16];
 #pragma unroll
     for (int e = 0; e < 16; ++e) wr[e] = wrs[e * 64 + lane];
-    T wl[16];
-    if constexpr (MEANS) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) wl[e] = wsl[e * 64 + lane];
-    }
     for (int c0 = wv; c0 < nb; c0 += 4 * U) {
         if (c0 != wv) {
 #pragma unroll
@@ -386,49 +369,23 @@ __device__ __forceinline__ void panel_step_snp16_body(const SnpAcc<T>& X, int64_
 #pragma unroll
             for (int u = 0; u < U; ++u) xb[u] = word(jb[u]);
         }
-        if constexpr (!MEANS) {
-            T pu[U];
+        T pu[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                T xx[16];
-                snp16_decode<T, FULL>(xb[u], X.impute[jb[u]], i, n, xx);
-                T sacc = T(0);
+        for (int u = 0; u < U; ++u) {
+            T xx[16];
+            snp16_decode<T, FULL>(xb[u], X.impute[jb[u]], i, n, xx);
+            T sacc = T(0);
 #pragma unroll
-                for (int e = 0; e < 16; ++e) sacc = fma(xx[e], wr[e], sacc);
-                pu[u] = sacc;
-            }
-            const T tot = reduce16(pu, lane);
-            if (lane < U && c0 + 4 * lane < nb) psum[c0 + 4 * lane] = tot;
-        } else {
-            // eight columns at a time: their gradient sums and their weighted sums (the column means under the CURRENT weights,
-            // from the same decoded calls) share one sixteen-value butterfly -- lanes 0-7 end with the former, 8-15 the latter
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                T pv[16];
-#pragma unroll
-                for (int u8 = 0; u8 < 8; ++u8) {
-                    const int u = 8 * h + u8;
-                    T xx[16];
-                    snp16_decode<T, FULL>(xb[u], X.impute[jb[u]], i, n, xx);
-                    T sacc = T(0), macc = T(0);
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        sacc = fma(xx[e], wr[e], sacc);
-                        macc = fma(xx[e], wl[e], macc);
-                    }
-                    pv[u8] = sacc;
-                    pv[8 + u8] = macc;
-                }
-                const T tot = reduce16(pv, lane);
-                const int c = c0 + 4 * (8 * h + (lane & 7));
-                if (lane < 16 && c < nb) (lane < 8 ? psum : psum2)[c] = tot;
-            }
+            for (int e = 0; e < 16; ++e) sacc = fma(xx[e], wr[e], sacc);
+            pu[u] = sacc;
         }
+        const T tot = reduce16(pu, lane);
+        if (lane < U && c0 + 4 * lane < nb) psum[c0 + 4 * lane] = tot;
     }
     (void)part; (void)part_ld;
 }
 
-template <class T, bool MEANS>
+template <class T>
 __global__ __launch_bounds__(256 * S16_NSUB) void panel_step_snp16_kernel(SnpAcc<T> X, int64_t n, const T* __restrict__ w,
                                                                           T* __restrict__ r, const int32_t* __restrict__ dcol,
                                                                           const T* __restrict__ dlt,
@@ -438,8 +395,6 @@ __global__ __launch_bounds__(256 * S16_NSUB) void panel_step_snp16_kernel(SnpAcc
     __shared__ T red[S16_NSUB][4][S16_RS];
     __shared__ T wrs[S16_NSUB][S16_RS];
     __shared__ T psum[S16_NSUB][PB];
-    __shared__ T wsl[MEANS ? S16_NSUB : 1][MEANS ? S16_RS : 1]; // means mode: the slice's weights
-    __shared__ T psum2[S16_NSUB][PB];                           // means mode: the columns' weighted sums
     __shared__ T ptab[64 * 16]; // pair tables of phase (A): [batch of 64 columns][wave][pair of the wave's columns][16]
     const int nz = nz_dev[0];
     const int sub = threadIdx.x >> 8, t = threadIdx.x & 255;
@@ -461,17 +416,15 @@ __global__ __launch_bounds__(256 * S16_NSUB) void panel_step_snp16_kernel(SnpAcc
             ptab[q * 16 + e] = va + vb;
         }
     }
-    constexpr bool means = MEANS; // (the launcher picks the instantiation: tail.xm_col != nullptr; implies a tail)
     if ((int64_t(blockIdx.x) + 1) * S16_NSUB * S16_RS <= n)
-        panel_step_snp16_body<T, true, MEANS>(X, n, w, r, dcol, dlt, nz, cols, nb, part, part_ld, red[sub], wrs[sub], wsl[MEANS ? sub : 0],
-                                              psum[sub], psum2[sub], ptab, t, slice);
+        panel_step_snp16_body<T, true>(X, n, w, r, dcol, dlt, nz, cols, nb, part, part_ld, red[sub], wrs[sub], psum[sub], ptab, t,
+                                       slice);
     else
-        panel_step_snp16_body<T, false, MEANS>(X, n, w, r, dcol, dlt, nz, cols, nb, part, part_ld, red[sub], wrs[sub], wsl[MEANS ? sub : 0],
-                                               psum[sub], psum2[sub], ptab, t, slice);
+        panel_step_snp16_body<T, false>(X, n, w, r, dcol, dlt, nz, cols, nb, part, part_ld, red[sub], wrs[sub], psum[sub], ptab, t,
+                                        slice);
     if (nb <= 0) return; // (uniform)
     __syncthreads();
     const bool do_tail = tail.counter != nullptr; // (then part_ld > 0: column-major partials)
-    T* part2 = part + int64_t(PB) * part_ld;      // means mode: the weighted column sums, same layout behind the gradients'
     if (int(threadIdx.x) < nb) { // one partial per column and workgroup: the two slices in a fixed order
         const int c = threadIdx.x;
         const T tot = psum[0][c] + psum[1][c];
@@ -479,9 +432,6 @@ __global__ __launch_bounds__(256 * S16_NSUB) void panel_step_snp16_kernel(SnpAcc
         // tail: device-coherent (written through) -- workgroups of this launch on other XCDs read it
         if (do_tail) __hip_atomic_store(dst, tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else *dst = tot;
-        if (means)
-            __hip_atomic_store(part2 + int64_t(c) * part_ld + blockIdx.x, psum2[0][c] + psum2[1][c], __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
     }
     if (!do_tail) return;
     // ---- tail: the LAST EIGHT workgroups to get here sum the partials, eight columns per workgroup and round ----------------
@@ -515,28 +465,9 @@ __global__ __launch_bounds__(256 * S16_NSUB) void panel_step_snp16_kernel(SnpAcc
             for (int u = 0; u < 4; ++u) sacc += v[u];
         }
         sacc = wave_sum64(sacc);
-        T macc = T(0);
-        if (means) {
-            const T* pm = part2 + int64_t(c) * part_ld;
-            for (int k0 = lane; k0 < nwg; k0 += 4 * 64) {
-                T v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    v[u] = (k0 + 64 * u < nwg) ? __hip_atomic_load(pm + k0 + 64 * u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : T(0);
-#pragma unroll
-                for (int u = 0; u < 4; ++u) macc += v[u];
-            }
-            macc = wave_sum64(macc);
-        }
         if (lane == 0) {
             T g = sacc;
-            if (means) {
-                g -= tail.rsum[0] * macc;
-                tail.xm_col[cols[c]] = macc;
-                tail.sxm[tail.list ? tail.list[tail.pos0 + c] : tail.pos0 + c] = macc;
-            } else if (tail.xm) {
-                g -= tail.rsum[0] * tail.xm[cols[c]];
-            }
+            if (tail.xm) g -= tail.rsum[0] * tail.xm[cols[c]];
             tail.g[c] = g;
         }
     }
@@ -682,12 +613,11 @@ __global__ void gather_i32_kernel(const int32_t* __restrict__ src, const int32_t
 
 template <class T, class Acc, int VEC>
 int step_launch(const Acc& acc, int64_t n, const T* w, T* r, const int32_t* dcol, const T* dlt, const int32_t* nz_dev,
-                const int32_t* cols, int nb, T* part, bool slice_major, hipStream_t s) {
+                const int32_t* cols, int nb, T* part, hipStream_t s) {
     constexpr int RS = 64 * VEC;
     const int64_t ns = (n + RS - 1) / RS;
-    // slice_major: part[slice * 128 + c] for a solve that sums the partials itself (blk_solve_la_body), else part[c * ns + slice]
     hipLaunchKernelGGL((panel_step_kernel<T, Acc, VEC>), dim3((unsigned)ns), dim3(PT), 0, s, acc, n, w, r, dcol, dlt,
-                       nz_dev, cols, nb, part, slice_major ? int64_t(0) : ns);
+                       nz_dev, cols, nb, part, ns);
     return int(ns);
 }
 
@@ -878,49 +808,37 @@ int64_t panel_part_elems(int64_t n) { return int64_t(PB) * ((n + 63) / 64) + 16;
 
 template <class T>
 int launch_panel_step(const DenseView<T>& X, const T* w, T* r, const int32_t* dcol, const T* dlt, const int32_t* nz_dev,
-                      const int32_t* cols, int nb, T* part, hipStream_t s, bool slice_major) {
+                      const int32_t* cols, int nb, T* part, hipStream_t s) {
     DenseAcc<T> acc{X.X, X.ld};
     constexpr int V = VecOf<T>::N;
     const bool vecok = (X.ld % V == 0) && ((reinterpret_cast<uintptr_t>(X.X) % 16) == 0);
-    if (vecok) return step_launch<T, DenseAcc<T>, V>(acc, X.n, w, r, dcol, dlt, nz_dev, cols, nb, part, slice_major, s);
-    return step_launch<T, DenseAcc<T>, 1>(acc, X.n, w, r, dcol, dlt, nz_dev, cols, nb, part, slice_major, s);
+    if (vecok) return step_launch<T, DenseAcc<T>, V>(acc, X.n, w, r, dcol, dlt, nz_dev, cols, nb, part, s);
+    return step_launch<T, DenseAcc<T>, 1>(acc, X.n, w, r, dcol, dlt, nz_dev, cols, nb, part, s);
 }
-namespace {
-inline bool snp16_old_form() {
-    static const bool v = std::getenv("ADELIE_HIP_SNP16_OLD") != nullptr; // (A/B of the round-6 kernel)
-    return v;
-}
-inline bool snp16_shape_ok(const SnpView& X) { return X.n >= 16384 && X.ldb % 4 == 0 && (reinterpret_cast<uintptr_t>(X.bits) % 4) == 0; }
-} // namespace
-bool panel_step_snp_has_tail(const SnpView& X) { return snp16_shape_ok(X) && !snp16_old_form(); }
 
 template <class T>
 int launch_panel_step_snp(const SnpView& X, const T* impute, const T* w, T* r, const int32_t* dcol, const T* dlt,
-                          const int32_t* nz_dev, const int32_t* cols, int nb, T* part, hipStream_t s, bool slice_major,
-                          const StepTail<T>* tail, bool* tailed) {
+                          const int32_t* nz_dev, const int32_t* cols, int nb, T* part, hipStream_t s, const StepTail<T>* tail,
+                          bool* tailed) {
     SnpAcc<T> acc{X.bits, X.ldb, impute};
     if (tailed) *tailed = false;
     // 16 calls (one 32-bit word) per lane and column instead of 4 (one byte): a quarter of the workgroups, four times the
     // bytes per load instruction - the byte form is bound by the number of workgroups and load instructions, not by bytes.
-    if (snp16_shape_ok(X)) {
+    if (X.n >= 16384 && X.ldb % 4 == 0 && (reinterpret_cast<uintptr_t>(X.bits) % 4) == 0) {
         // (nb > 128: the opening step of a look-ahead pass prepares two blocks at once; the generic body has no per-block tables)
-        if (snp16_old_form() || nb > PB) return step_launch<T, SnpAcc<T>, 16>(acc, X.n, w, r, dcol, dlt, nz_dev, cols, nb, part, slice_major, s);
+        if (nb > PB) return step_launch<T, SnpAcc<T>, 16>(acc, X.n, w, r, dcol, dlt, nz_dev, cols, nb, part, s);
         constexpr int64_t RW = int64_t(S16_RS) * S16_NSUB;
         const int64_t nwg = (X.n + RW - 1) / RW;
         StepTail<T> tl{};
-        if (tail && nb > 0 && !slice_major) {
+        if (tail && nb > 0) {
             tl = *tail;
             if (tailed) *tailed = true;
         }
-        if (tl.xm_col != nullptr)
-            hipLaunchKernelGGL((panel_step_snp16_kernel<T, true>), dim3((unsigned)nwg), dim3(256 * S16_NSUB), 0, s, acc, X.n, w, r,
-                               dcol, dlt, nz_dev, cols, nb, part, nwg, tl);
-        else
-            hipLaunchKernelGGL((panel_step_snp16_kernel<T, false>), dim3((unsigned)nwg), dim3(256 * S16_NSUB), 0, s, acc, X.n, w, r,
-                               dcol, dlt, nz_dev, cols, nb, part, slice_major ? int64_t(0) : nwg, tl);
+        hipLaunchKernelGGL((panel_step_snp16_kernel<T>), dim3((unsigned)nwg), dim3(256 * S16_NSUB), 0, s, acc, X.n, w, r, dcol, dlt,
+                           nz_dev, cols, nb, part, nwg, tl);
         return int(nwg);
     }
-    return step_launch<T, SnpAcc<T>, 4>(acc, X.n, w, r, dcol, dlt, nz_dev, cols, nb, part, slice_major, s);
+    return step_launch<T, SnpAcc<T>, 4>(acc, X.n, w, r, dcol, dlt, nz_dev, cols, nb, part, s);
 }
 template <class T>
 void launch_panel_reduce(const T* part, int nslices, int nb, const int32_t* cols, const T* rsum_dev, const T* xm_by_col,
@@ -950,10 +868,10 @@ void launch_gather_i32(const int32_t* src, const int32_t* idx, int cnt, int32_t*
 
 #define INST(T)                                                                                                        \
     template int launch_panel_step<T>(const DenseView<T>&, const T*, T*, const int32_t*, const T*, const int32_t*,     \
-                                      const int32_t*, int, T*, hipStream_t, bool);                                     \
+                                      const int32_t*, int, T*, hipStream_t);                                           \
     template int launch_panel_step_snp<T>(const SnpView&, const T*, const T*, T*, const int32_t*, const T*,            \
-                                          const int32_t*, const int32_t*, int, T*, hipStream_t, bool,                  \
-                                          const StepTail<T>*, bool*);                                                  \
+                                          const int32_t*, const int32_t*, int, T*, hipStream_t, const StepTail<T>*,    \
+                                          bool*);                                                                      \
     template void launch_panel_reduce<T>(const T*, int, int, const int32_t*, const T*, const T*, T*, hipStream_t);     \
     template void launch_panel_reduce_ld<T>(const T*, int64_t, int, int, const int32_t*, const T*, const T*, T*,       \
                                             hipStream_t);                                                              \

@@ -32,7 +32,7 @@ namespace {
 constexpr int MT = 256;  // threads of the sweep kernel
 // Features per sweep block.  The K vectors are re-read (from L2) once per block: with 4 features a K = 8 sweep pulls twice as
 // many bytes of v through L2 as it streams of X from HBM and ends up bound by L2 (1.73 ms = 4.6 TB/s at 100k x 10k f64); with
-// 8 the two are equal.  (ADELIE_HIP_MULTI_SWEEP_MCB=4 selects the old shape for an A/B run.)
+// 8 the two are equal.
 constexpr int MCB_MAX = 8;
 constexpr int MAXB = 128; // entries of a panel block (== cd_block_size())
 

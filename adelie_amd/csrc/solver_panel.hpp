@@ -385,12 +385,7 @@
             Stopwatch sw_enq;
             sw_enq.start();
             // the step of block 0 goes out before the builds are enqueued (it does not depend on them; see record_pass_e0)
-            // The stand-alone solve sums the slice partials itself (blk_solve_la_body, second round trip of its prologue): no
-            // panel_reduce launch between step and solve.  Config 4: 54.8 k blocks per path x (reduce 4.85 us + a boundary).
-            // Not with constraints (their solve kernel has the plain prologue), views and compressed columns (their gradient
-            // is corrected / written by other launches), the multi-response view (its own partial layout).
             bool step_tailed_of[2] = {false, false};
-            const bool solve_sums = plain_solve_sums && !cons_on && !multi() && !std_generic() && !sparse() && D->std_center == nullptr;
             auto step_of = [&](int j) {
                 const int nb = std::min(B, count - j * B);
                 const int32_t* cols = cols_all + size_t(j) * B;
@@ -398,8 +393,7 @@
                 if (time_panel) t_step.begin(st);
                 const int nsl = panel_step(cur_w, r_dev, ps < 0 ? d_dcolblk.p : d_la_dcol.p + size_t(ps) * SL,
                                            ps < 0 ? d_dlt.p : d_la_dlt.p + size_t(ps) * SL,
-                                           ps < 0 ? &d_blk.p->nz : d_la_nz.p + ps, cols, nb, solve_sums,
-                                           step_tail && !solve_sums && !multi() && !sparse(), xm_c, bp.list, j * B);
+                                           ps < 0 ? &d_blk.p->nz : d_la_nz.p + ps, cols, nb, !multi() && !sparse(), xm_c);
                 if (time_panel) t_step.end(st);
                 step_tailed_of[j & 1] = step_tailed;
                 return nsl;
@@ -448,12 +442,7 @@
                 const int nsl = (j == 0) ? nsl0 : step_of(j);
                 pending_slot = -1;
                 cnt.n_panel_cols += nb;
-                if (solve_sums) {
-                    bp.part = d_part.p; bp.part_ld = 0; bp.part_n = nsl;
-                    bp.part_rsum = xm_c ? &d_blk.p->resid_sum : nullptr; // (the residual sum the step's residual belongs to)
-                } else if (!step_tailed_of[j & 1]) { // (else the step's last workgroups left the gradient in d_gblk)
-                    panel_reduce(nsl, nb, cols, xm_c, d_gblk.p);
-                }
+                if (!step_tailed_of[j & 1]) panel_reduce(nsl, nb, cols, xm_c, d_gblk.p); // (else the step left the gradient in d_gblk)
                 bp.Dptr = Dptr;
                 if (h_report && j == nblk - 1) {
                     bp.report_j = j;
@@ -566,7 +555,6 @@
     PassTables ptab_scr, ptab_act;
     DevBuf<int32_t> d_blk_g0_act, d_gdesc_act;
     DevBuf<T> d_la_corr;                      // look-ahead corrections left by the previous solve (CdGrpBlkParams::corr_out), by block parity
-    bool group_next_corr = true;              // A/B: ADELIE_HIP_GROUP_NEXT_CORR=0
     bool pass_tables_cached = true;           // A/B hook ADELIE_HIP_PASS_TABLES=0
     std::vector<int32_t> part_host;
     int build_partition(const idx* list, idx count) { // returns nblk; fills part_host with nblk+1 list positions
@@ -1072,7 +1060,7 @@
             int prev_ld = 0; // partials of block j left behind by the previous fused launch (fr_grp), see run_panel_passes
             // the correction of block j + 1 formed by the idle waves of solve j (CdGrpBlkParams::Cnext): fused launches of the
             // rotated single-response form
-            const bool next_corr = group_next_corr && bp.rot && !multi();
+            const bool next_corr = bp.rot && !multi();
             if (next_corr) d_la_corr.reserve(size_t(2) * SL);
             bool prev_made_corr = false;
             for (int j = 0; j < nblk; ++j) {

@@ -447,20 +447,16 @@
             if (i < 0 || i >= G) throw make_core_error("screen_set contains an out-of-range group index.");
 
         AHIP_CHECK(hipSetDevice(X->device));
-        hooks = Hooks::from_env(); // (common.hpp: the library's seven environment hooks)
+        hooks = Hooks::from_env(); // (common.hpp: the library's environment hooks)
         if (hooks.cd_block_min_nv >= 0) cd_block_min_nv = hooks.cd_block_min_nv;
         time_panel = hooks.time_panel;
         // two build streams under IRLS (config 4: 8.2 -> 7.2 s; three or four are no better), one under fixed weights (the
         // few builds of a Gaussian path only add contention for the look-ahead launches: 3.13 vs 3.08 paths/s)
         n_side = is_glm() ? 2 : 1;
         if (hooks.lookahead >= 0) lookahead = hooks.lookahead != 0;
-        if (hooks.group_next_corr >= 0) group_next_corr = hooks.group_next_corr != 0;
         fuse_reduce = !multi() && fused_partials() <= 200;
         if (hooks.speculate >= 0) spec_enabled = hooks.speculate != 0;
         if (hooks.irls_reuse >= 0) irls_reuse = hooks.irls_reuse;
-        if (hooks.solve_sums >= 0) plain_solve_sums = hooks.solve_sums != 0;
-        if (hooks.step_tail >= 0) step_tail = hooks.step_tail != 0;
-        if (hooks.step_means >= 0) step_means_opt = hooks.step_means != 0;
         panel_bsz = hooks.panel_bsz;
         if (cov_mode) { // base state of the covariance method: no intercept, adev_tol = ddev_tol = 0 (state_gaussian_cov.hpp:118)
             engine_panel = false; // the panel engines work on the residual; the Gram engines on C = A[S, S] and its gradient

@@ -46,22 +46,8 @@
     DevBuf<int32_t> d_tail_ctr;
     int32_t tail_base = 0;
     bool step_tailed = false;
-    // Means mode (step_means_now; IRLS on a 2-bit design with an intercept): the step also produces the CURRENT weighted means of
-    // the block's columns and leaves them in d_irls_xm (by column) and d_sxm (by screen value: `list` / `pos0` locate the block)
-    // before the block's solve reads them -- glm_fit then runs no mean sweep over the screen columns per IRLS iteration.
-    // Measured on config 4 (profiles/r06_cfg4_ab.txt): parity, 2.91-2.94 s with it against 2.90-2.95 s without -- the mean sweeps it
-    // removes (0.15 s of the main stream) the step gives back (cd 2.43 against 2.29 s: phase (B)'s second accumulation, butterfly
-    // and tail sum, 2.5 us per step); the builds take the means of their own columns inside the MFMA kernel at no cost (with a
-    // sweep per build batch instead it was 3.03-3.06 against 2.98-3.00 s).  Off; hook ADELIE_HIP_STEP_MEANS=1.
-    bool step_means_opt = false;
-    bool step_means_now = false;  // (set per IRLS iteration by glm_fit)
-    bool step_means_possible() const {
-        return step_means_opt && step_tail && !plain_solve_sums && is_glm() && intercept && all_scalar && !multi() && !sparse() &&
-               !dense() && D->std_center == nullptr && !cov_mode && panel_step_snp_has_tail(D->snp());
-    }
     int panel_step(const T* w, T* r, const int32_t* dcol, const T* dlt, const int32_t* nz_dev, const int32_t* cols, int nb,
-                   bool slice_major = false, bool want_tail = false, const T* tail_xm = nullptr, const int32_t* list = nullptr,
-                   int pos0 = 0) {
+                   bool want_tail = false, const T* tail_xm = nullptr) {
         step_tailed = false;
         if (multi()) return launch_multi_panel_step<T>(D->multi<T>(), w, r, dcol, dlt, nz_dev, cols, nb, d_part.p, st);
         const T* kappa = nullptr;
@@ -84,9 +70,9 @@
                                        &d_blk.p->resid_sum, intercept ? cur_xm : nullptr, st);
             return 0;
         }
-        if (dense()) return launch_panel_step<T>(D->dense<T>(), w, r, dcol, dlt, nz_dev, cols, nb, d_part.p, st, slice_major);
+        if (dense()) return launch_panel_step<T>(D->dense<T>(), w, r, dcol, dlt, nz_dev, cols, nb, d_part.p, st);
         StepTail<T> tl{};
-        const bool tail_ok = want_tail && !stdv && nb > 0 && !slice_major;
+        const bool tail_ok = want_tail && !stdv && nb > 0;
         if (tail_ok) {
             if (!d_tail_ctr.p) { // (monotone over the launches of this solver; zeroed once)
                 d_tail_ctr.reserve(4);
@@ -94,13 +80,9 @@
                 tail_base = 0;
             }
             tl.counter = d_tail_ctr.p; tl.base = tail_base; tl.g = d_gblk.p; tl.rsum = &d_blk.p->resid_sum; tl.xm = tail_xm;
-            if (step_means_now) {
-                tl.xm_col = d_irls_xm.p; tl.sxm = d_sxm.p; tl.list = list; tl.pos0 = pos0;
-            }
         }
-        if (step_means_now && nb > 0 && !tail_ok) throw make_core_error("means mode without a step tail (internal error).");
         const int nsl = launch_panel_step_snp<T>(D->snp(), static_cast<const T*>(D->impute), w, r, dcol, dlt, nz_dev, cols, nb,
-                                                 d_part.p, st, slice_major, tail_ok ? &tl : nullptr, &step_tailed);
+                                                 d_part.p, st, tail_ok ? &tl : nullptr, &step_tailed);
         if (step_tailed) {
             tail_base += nsl;
             if (tail_base > (int32_t(1) << 30)) { // (far from overflow: start over behind everything enqueued so far)
@@ -133,7 +115,7 @@
     }
     // `sb.count` diagonal blocks in one launch (non-multi designs): block y = columns cols_base[sb.off[y] ...], into
     // D0 + sb.dst[y] (ld = B)
-    void gram_block_batch(const T* w, const int32_t* cols_base, const SyrkBatch& sb, const T* xm, T* D0, int side, T* xm_build = nullptr) {
+    void gram_block_batch(const T* w, const int32_t* cols_base, const SyrkBatch& sb, const T* xm, T* D0, int side) {
         const int B = cd_block_size();
         hipStream_t gs = side == 0 ? st : (side >= 2 ? st_x[side - 2] : st2);
         if (sparse()) { // compressed columns: one thread per pair of columns merges the two row lists (kernels_sparse.hip)
@@ -150,8 +132,7 @@
         t_gram.begin(gs);
         const bool stdv = std_generic(); // raw X' W X of the base design, then the view's corrections (kernels_sparse.hip)
         if (dense()) launch_syrk_batch<T>(D->dense<T>(), w, cols_base, sb, xm, intercept && !stdv, D0, B, work, gs);
-        else launch_syrk_batch_snp<T>(D->snp(), static_cast<const T*>(D->impute), w, cols_base, sb, xm, intercept && !stdv, D0, B, work, gs,
-                                      stdv ? nullptr : xm_build);
+        else launch_syrk_batch_snp<T>(D->snp(), static_cast<const T*>(D->impute), w, cols_base, sb, xm, intercept && !stdv, D0, B, work, gs);
         if (stdv) std_block_fix(w, cols_base, sb, xm, D0, side, gs);
         t_gram.end(gs);
         for (int y = 0; y < sb.count; ++y) {
