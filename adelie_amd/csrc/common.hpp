@@ -18,7 +18,7 @@
 namespace ahip {
 
 // ---- every environment hook of libadelie_hip.so, in one place ------------------------------------------------------------------
-// Ten variables.  They are read when a solve starts (Hooks::from_env, one call per solve): the tests force the multi-CU engines
+// Eleven variables.  They are read when a solve starts (Hooks::from_env, one call per solve): the tests force the multi-CU engines
 // at sizes the CPU checker finishes in seconds and compare variants between two solves of ONE process, so reading them once at
 // library load would freeze the first test's setting.  None changes results beyond rounding.  (Python side: ADELIE_HIP_LIB picks
 // another build of this library, ADELIE_HIP_SWEEP_BATCH=0 keeps concurrent CV folds from sharing their sweeps.)
@@ -31,6 +31,9 @@ namespace ahip {
 //   ADELIE_HIP_CONS_HOST=1        box / one-sided constraint objects visited on the host instead of kernels_cons.hip  [A/B, tests]
 //   ADELIE_HIP_SPARSE_PANEL=0     IRLS on a design kept sparse on the full-Gram engines instead of the panel engine    [A/B, tests]
 //   ADELIE_HIP_STD_PANEL=0        standardized dense / 2-bit views on their full-Gram engines instead of the panel engines [A/B, tests]
+//   ADELIE_HIP_FACTOR_SWEEP=0|1   full sweeps of a one-hot / interaction design read off Z (kernels_factor.hip) or off the
+//                                 expanded matrix like any dense design (default: kFactorSweepDefault below; the matrix
+//                                 operations read it at the call)                                                     [A/B, tests]
 //   ADELIE_HIP_TIME_PANEL=1       per-launch HIP events around the panel step (bench.py's roofline leg)
 //   ADELIE_HIP_TRACE=1|2          1: per-pass trace on stderr; 2: + enqueue / allocation / build timings
 struct Hooks {
@@ -39,6 +42,7 @@ struct Hooks {
     int sparse_panel = -1;   // ADELIE_HIP_SPARSE_PANEL=0: IRLS on a design kept sparse stays on the full-Gram engines
     int std_panel = -1;      // ADELIE_HIP_STD_PANEL=0: a standardized dense / 2-bit view stays on its full-Gram engines
     int lookahead = -1, speculate = -1;
+    int factor_sweep = -1;   // ADELIE_HIP_FACTOR_SWEEP (-1: unset)
     double irls_reuse = -1;
     bool time_panel = false;
     bool cons_host = false; // ADELIE_HIP_CONS_HOST=1: box / one-sided objects on several coefficients visited on the host (A/B, tests)
@@ -58,9 +62,18 @@ struct Hooks {
         if (const char* e = std::getenv("ADELIE_HIP_SPARSE_PANEL")) h.sparse_panel = std::atoi(e) != 0;
         if (const char* e = std::getenv("ADELIE_HIP_STD_PANEL")) h.std_panel = std::atoi(e) != 0;
         if (const char* e = std::getenv("ADELIE_HIP_TRACE")) h.trace = std::max(1, std::atoi(e));
+        h.factor_sweep = factor_sweep_env();
         return h;
     }
+    static int factor_sweep_env() {
+        const char* e = std::getenv("ADELIE_HIP_FACTOR_SWEEP");
+        return e ? int(std::atoi(e) != 0) : -1;
+    }
 };
+// Whether the full sweeps of a factor design take the structured kernel when ADELIE_HIP_FACTOR_SWEEP is unset: only once it is
+// measured at least as fast as the dense sweep on both shapes of scripts/bench_factor.py (profiles/factor_sweep.txt).
+constexpr bool kFactorSweepDefault = false;
+inline bool factor_sweep_on(int hook) { return hook < 0 ? kFactorSweepDefault : hook != 0; }
 
 
 // util/exceptions.hpp:8-55 — same prefixes so that the Python layer's error-vs-warning split keeps working
@@ -457,6 +470,15 @@ struct adelie_hip_design {
     int64_t mK = 0, nb = 0, pb = 0;
     int micpt = 0;
     void* ones = nullptr; // nb ones (owned)
+    // factor design (adelie_hip_design_create_one_hot / _interaction): X above is the expanded matrix; next to it a column-major
+    // copy of the d columns of Z and the per-block descriptors that the structured full sweep reads (kernels_factor.hip).  Owned
+    // unless alias; f_outer (host) = the blocks' first columns and P.
+    void* fz = nullptr;
+    int64_t fz_ld = 0;
+    ahip::FactorBlock* fblk = nullptr;
+    ahip::FactorChunk* fchunk = nullptr;
+    int64_t f_nchunk = 0;
+    std::vector<int64_t> f_outer;
     // Sweep batching across solvers that run concurrently on one resident matrix (cv_grpnet folds on alias handles): the
     // batcher object lives with the design the aliases were made from (solver.hip::SweepBatcher, created on first use).
     adelie_hip_design* batch_owner = nullptr; // nullptr: this design itself
@@ -471,6 +493,10 @@ struct adelie_hip_design {
         return ahip::CscView<T>{cptr, cidx, static_cast<const T*>(cval), rptr, rcol, static_cast<const T*>(rval), n, p, nnz,
                                 bptr, sp_nb, sp_rb, static_cast<const T*>(std_center), static_cast<const T*>(std_iscale),
                                 tptr, trow, static_cast<const T*>(tval), sp_nt, sp_th};
+    }
+    bool factor() const { return fblk != nullptr; }
+    template <class T> ahip::FactorView<T> factor_view() const {
+        return ahip::FactorView<T>{static_cast<const T*>(fz), n, fz_ld, p, fblk, fchunk, f_nchunk};
     }
     template <class T> ahip::MultiView<T> multi() const {
         return ahip::MultiView<T>{static_cast<const T*>(X), nb, pb, ld, static_cast<const T*>(ones), int32_t(mK), int32_t(micpt),

@@ -1,6 +1,7 @@
 // design.hip — C ABI: library info, design-matrix handles and the MatrixNaiveBase operations.
 // (include/adelie_hip.h documents which reference method each entry point replaces.)
 #include <atomic>
+#include <cstdio>
 #include "common.hpp"
 
 #include <mutex>
@@ -164,7 +165,10 @@ void op_sweep(adelie_hip_design* d, int64_t c0, int64_t ncols, const T* v, const
         AHIP_CHECK(hipMemcpyAsync(dw, w, n * sizeof(T), hipMemcpyHostToDevice, s));
         launch_vmul<T>(dv, dw, dv, n, s);
     }
-    if (d->kind == 0)
+    if (d->kind == 0 && d->factor() && c0 == 0 && ncols == d->p && !square && factor_sweep_on(Hooks::factor_sweep_env()))
+        launch_sweep_factor<T>(d->factor_view<T>(), dv, dout, nullptr, nullptr,
+                               scratch<T>(d->s_misc, size_t(factor_sweep_work_elems(n, d->p, d->f_nchunk))), s);
+    else if (d->kind == 0)
         launch_sweep<T>(d->dense<T>(), dv, dout, c0, ncols, nullptr, nullptr, nullptr, square, work, s);
     else if (d->kind == 3)
         launch_sweep_csc<T>(d->csc<T>(), dv, dout, c0, ncols, nullptr, nullptr, nullptr, square,
@@ -509,6 +513,89 @@ U read_as(const uint8_t* p) {
     U v;
     std::memcpy(&v, p, sizeof(U));
     return v;
+}
+
+
+// ---- factor designs: one-hot / pairwise interactions of a resident table Z ---------------------------------------------------
+std::string gib(double bytes) {
+    char buf[64];
+    std::snprintf(buf, sizeof buf, "%.2f GiB", bytes / double(int64_t(1) << 30));
+    return buf;
+}
+
+// `blocks` describe the expanded design (col0 / ncols still unset); fills them in, allocates the expanded matrix, the copy of Z
+// and the tables on Z's device, and runs the expansion kernel.  `what`: "one_hot" / "interaction" for the messages.
+template <class T>
+void create_factor_t(adelie_hip_design* Z, std::vector<FactorBlock>& blocks, const char* what, adelie_hip_design** out) {
+    constexpr int64_t kAlign = 32;
+    const int64_t n = Z->n, dz = Z->p;
+    std::vector<int64_t> outer(blocks.size() + 1, 0);
+    const double max_cols = double((int64_t(1) << 31) - 64);
+    for (size_t b = 0; b < blocks.size(); ++b) {
+        const double sz = double(blocks[b].l0) * double(blocks[b].l1) - double(blocks[b].shift);
+        if (double(outer[b]) + sz > max_cols)
+            throw make_core_error(std::string(what) + "(): the expanded design has more columns than the solver's 32-bit column "
+                                  "indices address (" + gib((double(outer[b]) + sz) * double(n) * sizeof(T)) + " of values at least).");
+        outer[b + 1] = outer[b] + int64_t(sz);
+    }
+    const int64_t P = outer.back();
+    std::vector<FactorChunk> chunks;
+    for (size_t b = 0; b < blocks.size(); ++b) {
+        blocks[b].col0 = int32_t(outer[b]);
+        blocks[b].ncols = int32_t(outer[b + 1] - outer[b]);
+        for (int32_t t0 = 0; t0 < blocks[b].ncols; t0 += kFactorChunk)
+            chunks.push_back(FactorChunk{int32_t(b), t0, std::min<int32_t>(kFactorChunk, blocks[b].ncols - t0), 0});
+    }
+    adelie_hip_design* d = new_design(n, P, Z->dtype, Z->device);
+    try {
+        const int64_t ld = ((n + kAlign - 1) / kAlign) * kAlign;
+        hipStream_t s = d->stream;
+        T* X = nullptr;
+        if (hipMalloc(reinterpret_cast<void**>(&X), size_t(ld) * size_t(P) * sizeof(T)) != hipSuccess) {
+            (void)hipGetLastError();
+            throw make_core_error(std::string(what) + "(): could not allocate the expanded design (" + std::to_string(n) + " x " +
+                                  std::to_string(P) + ", " + gib(double(ld) * double(P) * sizeof(T)) + ") on the device.");
+        }
+        d->X = X;
+        d->ld = ld;
+        d->owned = true;
+        d->kind = 0;
+        T* fz = nullptr;
+        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fz), size_t(ld) * size_t(dz) * sizeof(T)));
+        d->fz = fz;
+        d->fz_ld = ld;
+        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->fblk), blocks.size() * sizeof(FactorBlock)));
+        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->fchunk), chunks.size() * sizeof(FactorChunk)));
+        d->f_nchunk = int64_t(chunks.size());
+        d->f_outer = outer;
+        AHIP_CHECK(hipMemcpyAsync(d->fblk, blocks.data(), blocks.size() * sizeof(FactorBlock), hipMemcpyHostToDevice, s));
+        AHIP_CHECK(hipMemcpyAsync(d->fchunk, chunks.data(), chunks.size() * sizeof(FactorChunk), hipMemcpyHostToDevice, s));
+        // zero the padding rows (vector loads past n never see NaN payloads), then copy Z and expand
+        AHIP_CHECK(hipMemsetAsync(fz, 0, size_t(ld) * size_t(dz) * sizeof(T), s));
+        if (ld > n) AHIP_CHECK(hipMemset2DAsync(X + n, size_t(ld) * sizeof(T), 0, size_t(ld - n) * sizeof(T), size_t(P), s));
+        AHIP_CHECK(hipStreamSynchronize(Z->stream)); // (Z's own creation may still be in flight on its stream)
+        launch_derive_dense<T>(Z->dense<T>(), n, dz, nullptr, nullptr, nullptr, nullptr, fz, ld, s);
+        launch_factor_expand<T>(d->factor_view<T>(), X, ld, s);
+        AHIP_CHECK(hipStreamSynchronize(s)); // (the host tables above go out of scope)
+    } catch (...) {
+        adelie_hip_design_destroy(d);
+        throw;
+    }
+    *out = d;
+}
+
+void check_factor_source(const adelie_hip_design* Z, const int64_t* levels, const void* out, const char* what) {
+    if (!Z || !levels || !out) throw make_core_error("null argument.");
+    if (Z->kind != 0 || Z->cov || Z->std_center)
+        throw make_core_error(std::string(what) + "(): mat must be a resident dense naive design (not an SNP, sparse, view or "
+                              "covariance handle).");
+    for (int64_t j = 0; j < Z->p; ++j)
+        if (levels[j] > int64_t(0x7fffffff)) throw make_core_error(std::string(what) + "(): levels must fit in int32.");
+}
+// basis size and "discrete" flag of feature j
+inline int32_t factor_basis(const int64_t* levels, int64_t j, bool& disc) {
+    disc = levels[j] > 0;
+    return disc ? int32_t(levels[j]) : 2;
 }
 
 } // namespace
@@ -1163,6 +1250,8 @@ int adelie_hip_design_alias(adelie_hip_design* src, adelie_hip_design** out) {
     d->bptr = src->bptr; d->sp_nb = src->sp_nb; d->sp_rb = src->sp_rb;
     d->tptr = src->tptr; d->trow = src->trow; d->tval = src->tval; d->sp_nt = src->sp_nt; d->sp_th = src->sp_th;
     d->std_center = src->std_center; d->std_iscale = src->std_iscale; // (not owned: std_owned stays false)
+    d->fz = src->fz; d->fz_ld = src->fz_ld; d->fblk = src->fblk; d->fchunk = src->fchunk; d->f_nchunk = src->f_nchunk;
+    d->f_outer = src->f_outer; // (a factor design's alias keeps the structure: CV folds sweep the same way)
     d->alias = true;
     d->batch_owner = src->batch_owner ? src->batch_owner : src;
     *out = d;
@@ -1288,6 +1377,50 @@ int adelie_hip_design_create_concat(adelie_hip_design* const* srcs, int64_t k, i
     ABI_CATCH
 }
 
+int adelie_hip_design_create_one_hot(adelie_hip_design* Z, const int64_t* levels, adelie_hip_design** out) {
+    ABI_TRY
+    check_factor_source(Z, levels, out, "one_hot");
+    set_device(Z);
+    std::vector<FactorBlock> blocks(static_cast<size_t>(Z->p));
+    for (int64_t j = 0; j < Z->p; ++j) {
+        bool disc;
+        const int32_t l = factor_basis(levels, j, disc);
+        // continuous: [z] = the basis [1, z] without its constant column; discrete: [z == 0, ..., z == l - 1]
+        blocks[size_t(j)] = FactorBlock{0, 0, int32_t(j), int32_t(j), l, 1, disc ? 0 : 1, (disc ? 1 : 0) | 4};
+    }
+    DTYPE_DISPATCH(Z, create_factor_t<T>(Z, blocks, "one_hot", out), create_factor_t<T>(Z, blocks, "one_hot", out))
+    ABI_CATCH
+}
+
+int adelie_hip_design_create_interaction(adelie_hip_design* Z, const int64_t* pairs, int64_t n_pairs, const int64_t* levels,
+                                         adelie_hip_design** out) {
+    ABI_TRY
+    check_factor_source(Z, levels, out, "interaction");
+    if (!pairs || n_pairs <= 0) throw make_core_error("interaction(): pairs must be non-empty.");
+    set_device(Z);
+    std::vector<FactorBlock> blocks(static_cast<size_t>(n_pairs));
+    for (int64_t k = 0; k < n_pairs; ++k) {
+        const int64_t i0 = pairs[2 * k], i1 = pairs[2 * k + 1];
+        if (i0 < 0 || i0 >= Z->p || i1 < 0 || i1 >= Z->p || i0 == i1)
+            throw make_core_error("interaction(): every pair must name two different columns of mat.");
+        bool d0, d1;
+        const int32_t l0 = factor_basis(levels, i0, d0), l1 = factor_basis(levels, i1, d1);
+        blocks[size_t(k)] = FactorBlock{0, 0, int32_t(i0), int32_t(i1), l0, l1, (!d0 && !d1) ? 1 : 0, (d0 ? 1 : 0) | (d1 ? 2 : 0)};
+    }
+    DTYPE_DISPATCH(Z, create_factor_t<T>(Z, blocks, "interaction", out), create_factor_t<T>(Z, blocks, "interaction", out))
+    ABI_CATCH
+}
+
+int64_t adelie_hip_design_factor_groups(const adelie_hip_design* d, int64_t* groups, int64_t* group_sizes, int64_t cap) {
+    if (!d || d->f_outer.empty()) return -1;
+    const int64_t G = int64_t(d->f_outer.size()) - 1;
+    for (int64_t g = 0; g < G && g < cap; ++g) {
+        if (groups) groups[g] = d->f_outer[size_t(g)];
+        if (group_sizes) group_sizes[g] = d->f_outer[size_t(g) + 1] - d->f_outer[size_t(g)];
+    }
+    return G;
+}
+
 int adelie_hip_design_impute(adelie_hip_design* d, double* out) {
     ABI_TRY
     no_view(d);
@@ -1319,6 +1452,7 @@ int adelie_hip_design_destroy(adelie_hip_design* d) {
         (void)hipFree(d->rptr); (void)hipFree(d->rcol); (void)hipFree(d->rval);
         (void)hipFree(d->bptr);
         (void)hipFree(d->tptr); (void)hipFree(d->trow); (void)hipFree(d->tval);
+        (void)hipFree(d->fz); (void)hipFree(d->fblk); (void)hipFree(d->fchunk);
     }
     if (d->std_owned) { (void)hipFree(d->std_center); (void)hipFree(d->std_iscale); }
     if (d->ones) (void)hipFree(d->ones);

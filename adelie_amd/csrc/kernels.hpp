@@ -706,4 +706,38 @@ void launch_bed_transcode(const uint8_t* bed, int64_t n, int64_t p, int64_t stri
                           hipStream_t s);
 template <class T> void launch_snp_impute(const uint8_t* bits, int64_t n, int64_t p, int64_t ldb, T* impute, hipStream_t s);
 
+// ---- factor designs (kernels_factor.hip): one-hot / pairwise-interaction expansions of a table Z --------------------------
+// A block is the outer product A * B of two small bases over one or two columns of Z, A's columns running fastest
+// (matrix_naive_interaction.ipp:78-200, matrix_naive_one_hot.ipp).  The basis of a continuous column is [1, z] (l = 2), of a
+// discrete one [z == 0, ..., z == l - 1]; a one-hot block has no B (l1 = 1, B = [1]).  Column t of the block is the
+// product's column g = t + shift, k0 = g % l0, k1 = g / l0; `shift` = 1 drops the constant column of two continuous bases
+// and of the one-hot block of a continuous column.
+constexpr int kFactorChunk = 16; // columns of one block a workgroup of the sweep / the expansion owns
+struct FactorBlock {
+    int32_t col0, ncols; // first column in the expanded design, number of columns
+    int32_t i0, i1;      // columns of Z (i1 = i0 when B is absent)
+    int32_t l0, l1;      // sizes of the two bases (continuous: 2; absent B: 1)
+    int32_t shift;
+    int32_t flags;       // bit 0: A discrete, bit 1: B discrete, bit 2: B absent
+};
+struct FactorChunk {
+    int32_t blk, t0, cnt, pad; // columns [t0, t0 + cnt) of block blk, cnt <= kFactorChunk
+};
+template <class T>
+struct FactorView {
+    const T* Z;         // column-major copy of the d columns of Z, leading dimension ldz
+    int64_t n, ldz, p;  // rows, leading dimension of Z, columns of the expanded design
+    const FactorBlock* blk;
+    const FactorChunk* chunk;
+    int64_t nchunk;
+};
+// X (column-major, leading dimension ld, rows >= n untouched) = the expanded design
+template <class T> void launch_factor_expand(const FactorView<T>& F, T* X, int64_t ld, hipStream_t s);
+// The full sweep out[c] = sum_i X[i, c] v[i] - (sub_vec ? sub_scale[0] * sub_vec[c] : 0) over all p columns, read off Z
+// and v alone; fixed summation order (row-slice partials in `work`, factor_sweep_work_elems(n, p, nchunk) elements).
+int64_t factor_sweep_work_elems(int64_t n, int64_t p, int64_t nchunk);
+template <class T>
+void launch_sweep_factor(const FactorView<T>& F, const T* v, T* out, const T* sub_scale, const T* sub_vec, T* work,
+                         hipStream_t s);
+
 } // namespace ahip

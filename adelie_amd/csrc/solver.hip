@@ -189,7 +189,7 @@ struct Counters {
     int64_t n_basil_iters = 0, n_sweeps = 0, n_cd_visits_screen = 0, n_cd_visits_active = 0, n_updates = 0,
             n_irls_iters = 0, n_new_screen_cols = 0, n_cd_passes_screen = 0, n_cd_passes_active = 0,
             n_gram_col_reads = 0, n_resid_col_reads = 0, n_panel_blocks = 0, n_panel_grams = 0, n_panel_cols = 0,
-            n_irls_screen_cols = 0, n_sweeps_shared = 0, n_update_cols = 0;
+            n_irls_screen_cols = 0, n_sweeps_shared = 0, n_update_cols = 0, n_sweeps_factor = 0;
     double gram_flops = 0;
 };
 
@@ -560,6 +560,7 @@ struct Result : ResultBase {
             case ADELIE_HIP_S_N_HOST_SCREENS: return double(s.n_host_screens);
             case ADELIE_HIP_S_N_HOST_CONS_VISITS: return double(s.n_host_cons_visits);
             case ADELIE_HIP_S_N_DEV_CONS_VISITS: return double(s.n_dev_cons_visits_final);
+            case ADELIE_HIP_S_N_SWEEPS_FACTOR: return double(s.cnt.n_sweeps_factor);
             default:
                 if (which >= 900 && which < 908) return double(s.cd_dbg[which - 900]);
                 if (which >= 910 && which < 918) return 1e3 * s.t_host[which - 910];
@@ -776,11 +777,15 @@ int adelie_hip_bench_sweep(adelie_hip_design* d, int64_t reps, double* ms_per_la
             DevBuf<T> v, out, xm, work, sc;
             v.reserve(d->n); out.reserve(d->p); xm.reserve(d->p); sc.reserve(1);
             work.reserve(size_t(d->kind == 3 ? sweep_work_elems_csc(d->sp_parts(), d->p) : sweep_work_elems(d->n, d->p)));
+            // a one-hot / interaction design: the structured sweep unless ADELIE_HIP_FACTOR_SWEEP says otherwise (read here)
+            const bool structured = d->kind == 0 && d->factor() && !d->std_center && factor_sweep_on(Hooks::factor_sweep_env());
+            if (structured) work.reserve(size_t(factor_sweep_work_elems(d->n, d->p, d->f_nchunk)));
             launch_fill<T>(v.p, T(1) / T(d->n), d->n, s);
             launch_fill<T>(xm.p, T(0.5), d->p, s);
             launch_fill<T>(sc.p, T(0.25), 1, s);
             auto once = [&]() {
-                if (d->kind == 0) launch_sweep<T>(d->dense<T>(), v.p, out.p, 0, d->p, nullptr, sc.p, xm.p, false, work.p, s);
+                if (structured) launch_sweep_factor<T>(d->factor_view<T>(), v.p, out.p, sc.p, xm.p, work.p, s);
+                else if (d->kind == 0) launch_sweep<T>(d->dense<T>(), v.p, out.p, 0, d->p, nullptr, sc.p, xm.p, false, work.p, s);
                 else if (d->kind == 3) launch_sweep_csc<T>(d->csc<T>(), v.p, out.p, 0, d->p, nullptr, sc.p, xm.p, false, work.p, s);
                 else launch_sweep_snp<T>(d->snp(), static_cast<const T*>(d->impute), v.p, out.p, 0, d->p, nullptr, sc.p, xm.p, false, work.p, s);
             };

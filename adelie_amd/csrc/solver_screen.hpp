@@ -32,6 +32,13 @@
             ++cnt.n_sweeps_shared;
             return;
         }
+        if (dense() && D->factor() && !cols && ncols == p && !square && factor_sweep_on(hooks.factor_sweep)) {
+            // a one-hot / interaction design: the full sweep reads Z and v instead of the expanded matrix (kernels_factor.hip)
+            launch_sweep_factor<T>(D->factor_view<T>(), v, out, sub_scale, sub_vec,
+                                   d_work_sweep.reserve(size_t(factor_sweep_work_elems(n, p, D->f_nchunk))), st);
+            ++cnt.n_sweeps_factor;
+            return;
+        }
         if (sparse()) { // one wavefront per column over its stored entries (kernels_sparse.hip)
             launch_sweep_csc<T>(D->csc<T>(), v, out, 0, ncols, cols, sub_scale, sub_vec, square,
                                 d_work_sweep.reserve(size_t(sweep_work_elems_csc(D->sp_parts(), ncols))), st);

@@ -767,6 +767,151 @@ def dense(mat, *, method: str = "naive", copy: bool = False, n_threads: int = 1,
     return _wrap(backend, handle, dtype.type, n_threads, kind="dense")
 
 
+# ---- designs built from a table of features: one_hot / interaction -------------------------------------------------------
+def _interaction_pairs(intr_map, d):
+    """The valid and unique pairs of an ``intr_map`` over ``d`` columns, exactly as the reference builds them
+    (``matrix.py:876-904``): keys sorted, ``None`` meaning every column, values sorted and made unique, self-pairs and both
+    orderings of a pair already seen dropped.  Returns an ``(n_pairs, 2)`` int array.  Needs no device."""
+    if len(intr_map) <= 0:
+        raise ValueError("intr_map must be non-empty.")
+    arange_d = np.arange(d)
+    keys = np.sort(list(intr_map.keys()))
+    pairs_seen = set()
+    pairs = []
+    for key in keys:
+        key = int(key)
+        if (key < 0) or (key >= d):
+            warnings.warn(f"key not in range [0,{d}): {key}.")
+        value_lst = intr_map[key]
+        value_lst = arange_d if value_lst is None else np.sort(np.unique(value_lst))
+        for val in value_lst:
+            val = int(val)
+            if ((key, val) in pairs_seen) or ((val, key) in pairs_seen) or (key == val):
+                continue
+            if (val < 0) or (val >= d):
+                warnings.warn(f"value not in range [0,{d}): {val}.")
+            pairs.append((key, val))
+            pairs_seen.add((key, val))
+    if len(pairs) <= 0:
+        raise ValueError("No valid pairs exist. There must be at least one valid pair.")
+    return np.array(pairs, dtype=int)
+
+
+def _factor_outer(levels, pairs=None):
+    """Block offsets of a one-hot (``pairs is None``) or interaction design: ``outer[b]`` is the first column of block ``b``
+    and ``outer[-1]`` the number of columns, so ``groups = outer[:-1]`` and ``group_sizes = diff(outer)``.  A one-hot block
+    has 1 column for a continuous feature and ``L`` for a discrete one; the block of a pair has ``l0 * l1 - both_cont``
+    columns with continuous counted as 2 (``init_outer``, ``matrix_naive_interaction.ipp:10-26``).  Needs no device."""
+    levels = np.asarray(levels).astype(np.int64)
+    if pairs is None:
+        sizes = np.where(levels <= 0, 1, levels)
+    else:
+        pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        l0, l1 = levels[pairs[:, 0]], levels[pairs[:, 1]]
+        both_cont = ((l0 <= 0) & (l1 <= 0)).astype(np.int64)
+        sizes = np.where(l0 <= 0, 2, l0) * np.where(l1 <= 0, 2, l1) - both_cont
+    return np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]).astype(np.int64)
+
+
+class _FactorMatrix(_NativeMatrix):
+    """A one-hot / interaction design: an ordinary resident dense design (every method of :class:`_NativeMatrix`) that also
+    carries the reference's read-only ``groups`` / ``group_sizes`` and ``_levels`` (``_pairs`` for interactions)."""
+
+    @property
+    def groups(self):
+        return self._groups
+
+    @property
+    def group_sizes(self):
+        return self._group_sizes
+
+
+def _factor_design(ctor, mat, levels, pairs, n_threads, device):
+    if n_threads < 1:
+        raise RuntimeError("adelie_core: n_threads must be >= 1.")
+    if isinstance(mat, _NativeMatrix):
+        if (getattr(mat, "_kind", None) != "dense" or isinstance(mat, (_MultiView, _StdView))):
+            raise RuntimeError("adelie_amd: mat must be an (n, d) array or a resident dense design.")
+        Z = mat
+    else:
+        Z = dense(mat, method="naive", n_threads=n_threads, device=device)
+    d = Z.cols()
+    levels = np.zeros(d, dtype=int) if levels is None else np.array(levels, copy=True).astype(int)
+    if levels.shape != (d,):
+        raise RuntimeError("adelie_core: levels must be (d,) where mat is (n, d).")
+    if pairs is not None and (pairs.min() < 0 or pairs.max() >= d):
+        raise RuntimeError("adelie_core: intr_map names a column outside [0, d).")
+    outer = _factor_outer(levels, pairs)
+    itemsize = np.dtype(Z.dtype).itemsize
+    if outer[-1] >= 2 ** 31 - 64:
+        raise RuntimeError(f"adelie_amd: the expanded design would have {int(outer[-1])} columns "
+                           f"({Z.rows() * float(outer[-1]) * itemsize / 2 ** 30:.2f} GiB of values): more than the solver's "
+                           "32-bit column indices address.")
+    backend = Z._backend
+    lv = np.ascontiguousarray(levels, dtype=np.int64)
+    handle = _abi.C.c_void_p()
+    if pairs is None:
+        backend.check(backend.fn(ctor)(Z._handle, lv.ctypes.data, handle))
+    else:
+        pr = np.ascontiguousarray(pairs, dtype=np.int64)
+        backend.check(backend.fn(ctor)(Z._handle, pr.ctypes.data, pr.shape[0], lv.ctypes.data, handle))
+    mixin = MatrixNaiveBase64 if np.dtype(Z.dtype) == np.float64 else MatrixNaiveBase32
+
+    class _factor(_FactorMatrix, mixin):
+        pass
+
+    _factor.dtype = mixin.dtype
+    obj = _factor()
+    obj._init_native(backend, handle, n_threads)
+    obj._keep = None  # (the device copy of Z is the design's own: nothing of `mat` is referenced)
+    obj._kind = "dense"
+    G = len(outer) - 1
+    groups, sizes = np.empty(G, dtype=np.int64), np.empty(G, dtype=np.int64)
+    if backend.fn("design_factor_groups")(handle, groups.ctypes.data, sizes.ctypes.data, G) != G or not (
+            np.array_equal(groups, outer[:-1]) and np.array_equal(sizes, np.diff(outer))):
+        raise RuntimeError("adelie_amd: the native block layout disagrees with the host's.")
+    obj._groups, obj._group_sizes = groups.astype(int), sizes.astype(int)
+    obj._groups.setflags(write=False)
+    obj._group_sizes.setflags(write=False)
+    obj._levels = levels
+    if pairs is not None:
+        obj._pairs = pairs
+    return obj
+
+
+def one_hot(mat, levels=None, *, copy: bool = False, n_threads: int = 1, device: int = 0):
+    """One-hot encoding of the discrete columns of ``mat`` (reference ``adelie.matrix.one_hot``, ``matrix.py:1073-1186``,
+    ``matrix_naive_one_hot.ipp``): in the order of the columns ``j`` of the ``(n, d)`` table, ``[Z_j]`` where
+    ``levels[j] <= 0`` (continuous) and ``[Z_j == 0, ..., Z_j == L - 1]`` where ``levels[j] = L > 0``.  A value outside
+    ``{0..L-1}`` gives a zero row in its block.  ``levels=None``: every column continuous.
+
+    ``mat`` is anything :func:`dense` takes (an ndarray -- a C-ordered one warns as there --, a resident torch tensor) or a
+    resident dense design.  Only the ``n x d`` table crosses to the device; the ``n x P`` design is expanded there by one
+    kernel and lives in HBM next to a copy of the table, ``(n*P + n*d)`` values.  The result is an ordinary dense design (it
+    works under ``grpnet``, ``cv_grpnet``, ``standardize``, ``subset``, ``concatenate``, ``kronecker_eye`` ...) with the
+    reference's ``groups`` / ``group_sizes`` / ``_levels``; with ``ADELIE_HIP_FACTOR_SWEEP=1`` its full gradient sweeps are formed
+    from the table instead of the expanded matrix.  ``copy`` and ``n_threads`` are accepted for parity."""
+    return _factor_design("design_create_one_hot", mat, levels, None, n_threads, device)
+
+
+def interaction(mat, intr_map, levels=None, *, copy: bool = False, n_threads: int = 1, device: int = 0):
+    """Pairwise interaction terms of the columns of ``mat`` (reference ``adelie.matrix.interaction``, ``matrix.py:721-914``,
+    ``matrix_naive_interaction.ipp``).  ``intr_map`` maps a column to the columns it is paired with (``None``: all); the valid
+    and unique pairs are registered as the reference does.  The block of the pair ``(i, j)`` is ``A * B`` with ``A``'s columns
+    running fastest, ``A`` / ``B`` being ``[1, Z_.]`` for a continuous column and ``[Z_. == 0, ...]`` for a discrete one; two
+    continuous columns give ``[Z_i, Z_j, Z_i Z_j]``.  See :func:`one_hot` for the inputs, the memory and the returned object
+    (which also carries ``_pairs``)."""
+    if isinstance(mat, _NativeMatrix):
+        d = mat.cols()
+    else:
+        shape = tuple(mat.shape)
+        if len(shape) != 2:
+            raise RuntimeError("mat must be 2-dimensional.")
+        d = shape[1]
+    pairs = _interaction_pairs(intr_map, d)
+    return _factor_design("design_create_interaction", mat, levels, pairs, n_threads, device)
+
+
 # matrix.sparse(resident="auto"): kept sparse below this density or above this dense size, expanded to a dense design otherwise
 _SPARSE_AUTO_DENSITY = 0.02
 _SPARSE_AUTO_DENSE_BYTES = 32 << 30

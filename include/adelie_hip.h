@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define ADELIE_HIP_ABI_VERSION 11
+#define ADELIE_HIP_ABI_VERSION 12
 
 enum adelie_hip_dtype { ADELIE_HIP_F32 = 0, ADELIE_HIP_F64 = 1 };
 enum adelie_hip_order { ADELIE_HIP_COL_MAJOR = 0, ADELIE_HIP_ROW_MAJOR = 1 };
@@ -171,6 +171,29 @@ int adelie_hip_design_create_concat(adelie_hip_design* const* srcs, int64_t k, i
  * for all K responses (a 2-bit base stays 2-bit: its calls are decoded once per column for all K).  The matrix-op entry
  * points (cmul ... sp_tmul) are not offered on the view: the Python layer reaches them through `base`. */
 int adelie_hip_design_create_multi(adelie_hip_design* base, int64_t K, int intercept, adelie_hip_design** out);
+/* ABI 12.  Replaces MatrixNaiveOneHotDense{32,64}{C,F} (adelie/matrix.py:1073-1186, matrix_naive_one_hot.ipp): the design
+ * whose blocks, in the order of the d columns of Z, are [Z_j] for a continuous column (levels[j] <= 0) and
+ * [Z_j == 0, ..., Z_j == L - 1] for a discrete one (levels[j] = L > 0).  A value outside {0..L-1} gives a zero row in its
+ * block, as the reference's `==` does.  `Z` is a resident dense naive design (SNP, sparse, view and covariance handles are
+ * refused); `levels` has Z's column count.  The result is an ordinary dense column-major design, filled on the device from the
+ * resident Z by one kernel (the reference generates the columns inside every operation; here n * P values live in HBM and
+ * every kernel of the library runs on them), plus what the structured full sweep needs: an owned copy of Z's d columns and a
+ * per-block descriptor table (first column, the two columns of Z, the two basis sizes, the case).  It does not reference `Z`.
+ * adelie_hip_design_alias hands the copy and the table on (not owned); slices, derived designs, concatenations and
+ * multi-response views of the result are plain dense designs. */
+int adelie_hip_design_create_one_hot(adelie_hip_design* Z, const int64_t* levels, adelie_hip_design** out);
+/* ABI 12.  Replaces MatrixNaiveInteractionDense{32,64}{C,F} (adelie/matrix.py:721-914, matrix_naive_interaction.ipp): for every
+ * row (i, j) of `pairs` ((n_pairs, 2) row-major, i != j, the valid and unique pairs that matrix.py:876-904 builds from intr_map)
+ * the block A * B with A's columns running fastest, A / B = [1, Z_.] for a continuous column and [Z_. == 0, ...] for a
+ * discrete one, without the constant column when both are continuous ([Z_i, Z_j, Z_i Z_j]): l0 * l1 - both_cont columns with
+ * continuous counted as 2 (init_outer, matrix_naive_interaction.ipp:10-26).  Entries are 0, 1, a value of Z or one product of
+ * two values of Z in the design's dtype.  Same kind of result and the same handle rules as adelie_hip_design_create_one_hot. */
+int adelie_hip_design_create_interaction(adelie_hip_design* Z, const int64_t* pairs, int64_t n_pairs, const int64_t* levels,
+                                         adelie_hip_design** out);
+/* The reference's read-only `groups` / `group_sizes` of the two classes above (outer[:-1] and diff(outer),
+ * matrix_naive_one_hot.hpp / matrix_naive_interaction.hpp): copies min(G, cap) entries into each non-NULL array and returns the
+ * number of blocks G, or -1 when `d` was not made by one of the two constructors (or is not an alias of such a design). */
+int64_t adelie_hip_design_factor_groups(const adelie_hip_design* d, int64_t* groups, int64_t* group_sizes, int64_t cap);
 /* Copies the (p,) impute vector of an SNP design (as double). */
 int adelie_hip_design_impute(adelie_hip_design* d, double* out);
 int adelie_hip_design_destroy(adelie_hip_design* d);
@@ -532,6 +555,8 @@ enum adelie_hip_scalar {
     ADELIE_HIP_S_N_HOST_SCREENS,     /* ... and by the host routine (first iteration, host constraint objects, G > 2^18) */
     ADELIE_HIP_S_N_HOST_CONS_VISITS, /* ABI 7: visits of constrained groups made on the host through the callbacks ... */
     ADELIE_HIP_S_N_DEV_CONS_VISITS,  /* ... and by the device kernel (box / one-sided objects, kernels_cons.hip) */
+    ADELIE_HIP_S_N_SWEEPS_FACTOR,    /* ABI 12: full-gradient sweeps of a one-hot / interaction design answered by the structured
+                                        kernel (kernels_factor.hip: read off Z, not off the expanded matrix) */
     /* HIP-event time (ms) of the device phases on the design's stream, summed over the solve, and launch counts */
     ADELIE_HIP_S_T_SWEEP_MS = 80, ADELIE_HIP_S_T_GRAM_MS, ADELIE_HIP_S_T_CD_MS, ADELIE_HIP_S_T_AXPY_MS,
     ADELIE_HIP_S_N_SWEEP_LAUNCHES, ADELIE_HIP_S_N_GRAM_LAUNCHES, ADELIE_HIP_S_T_HOST_SCREEN_MS,
@@ -551,6 +576,7 @@ const char* adelie_hip_result_error(const adelie_hip_result* r);
  * Kernel-level timing hook used by bench.py (HIP events on the design's own stream):
  * runs `reps` launches of the dominant kernel (the full gradient sweep grad = X^T(w*r) - rs*X_means
  * with fused per-group abs_grad) on resident buffers and returns the mean milliseconds per launch.
+ * On a one-hot / interaction design it times the route ADELIE_HIP_FACTOR_SWEEP selects (read at the call).
  * ------------------------------------------------------------------------------------------ */
 int adelie_hip_bench_sweep(adelie_hip_design* d, int64_t reps, double* ms_per_launch);
 
