@@ -140,6 +140,19 @@ class GrpnetArgs(C.Structure):
     ]
 
 
+class CssArgs(C.Structure):
+    """``adelie_hip_css_args`` (ABI 13)."""
+
+    _fields_ = [("subset_size", C.c_int64), ("subset", C.c_void_p), ("n_subset", C.c_int64), ("method", C.c_int32),
+                ("loss", C.c_int32), ("max_iters", C.c_int64), ("n_threads", C.c_int32), ("_pad0", C.c_int32)]
+
+
+CSS_METHODS = dict(greedy=0, swapping=1)
+CSS_LOSSES = dict(least_squares=0, subset_factor=1, min_det=2)
+# enum adelie_hip_css_vec / adelie_hip_css_scalar
+CSS_V = dict(subset=0, S_resid=1, S_resid_diag=2, L_T=3)
+CSS_S = dict(n_updates=0, n_swaps=1, n_attempts=2, early_exit=3, total_time=4)
+
 # enum adelie_hip_vec / adelie_hip_scalar
 V = dict(
     intercepts=0, devs=1, lmdas=2, lmda_path=3, screen_beta=4, grad=5, abs_grad=6, resid=7, eta=8,
@@ -177,6 +190,7 @@ HIP_SYMBOLS = [
     "glm_cox_create", "glm_cox_destroy", "glm_cox_eval",
     "grpnet_solve", "grpnet_solve_many", "result_destroy", "result_size", "result_copy", "result_scalar", "result_error", "result_sync",
     "bench_sweep",
+    "css_cov_solve", "css_result_destroy", "css_result_size", "css_result_copy", "css_result_scalar", "css_result_error",
 ]
 
 
@@ -194,7 +208,7 @@ def dtype_code(dtype):
 
 
 # kept equal to ADELIE_HIP_ABI_VERSION in include/adelie_hip.h (tests/test_abi.py compares the two)
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class Backend:
@@ -283,6 +297,12 @@ class Backend:
         sig("result_error", C.c_char_p, [vp])
         sig("result_sync", ci, [vp])
         sig("bench_sweep", ci, [vp, i64, p(dbl)])
+        sig("css_cov_solve", ci, [vp, p(CssArgs), p(vp)])
+        sig("css_result_destroy", ci, [vp])
+        sig("css_result_size", i64, [vp, ci])
+        sig("css_result_copy", ci, [vp, ci, vp, i64])
+        sig("css_result_scalar", dbl, [vp, ci])
+        sig("css_result_error", C.c_char_p, [vp])
 
     def check(self, rc):
         if rc != 0:

@@ -469,3 +469,41 @@ def gaussian_cov(
     if check_state:
         state.check(method="assert")
     return state.solve(progress_bar=progress_bar, exit_cond=exit_cond)
+
+
+def css_cov(
+    S, subset_size: int = None, *, subset: np.ndarray = None, method: str = "swapping", loss: str = "least_squares",
+    max_iters: int = int(1e3), n_threads: int = 1,
+):
+    """Column subset selection via the covariance method on an MI355X (reference ``adelie.solver.css_cov``,
+    ``adelie/solver.py:1274-1427``; arguments, defaults and the greedy-then-swapping chaining are the reference's).
+
+    Minimises ``loss(S, T)`` over index sets ``T`` of size ``subset_size``: ``"least_squares"`` (trace of the residual
+    covariance), ``"subset_factor"`` (``log|S_T|`` plus the log of the residual variances) or ``"min_det"`` (``|S_T|``).
+    ``method="greedy"`` grows ``T`` from the empty set; ``method="swapping"`` starts from ``subset`` (or from the greedy
+    solution when ``subset`` is ``None``) and swaps members while that strictly improves the loss.
+
+    ``S`` is a symmetric positive semi-definite ``(p, p)`` ``float32`` / ``float64`` ndarray in either memory order, or a
+    covariance matrix already resident in HBM: ``matrix.dense(S, method="cov")``, ``matrix.lazy_cov(X)`` (the Gram matrix of a
+    resident design, e.g. a 2-bit SNP design) or ``matrix.block_diag(..., method="cov")``.  It is never modified.  Every
+    rank-one update of the ``(p, p)`` residual covariance and the scores of all columns are one streaming pass on the device."""
+    if method not in ("greedy", "swapping"):
+        raise ValueError("method must be one of 'greedy' or 'swapping'.")
+    if loss not in ("least_squares", "subset_factor", "min_det"):
+        raise ValueError("loss must be one of 'least_squares', 'subset_factor' or 'min_det'.")
+    if (method == "greedy" or subset is None) and not isinstance(subset_size, (int, np.integer)):
+        raise ValueError("subset_size must be an integer for the greedy method.")
+    if method == "greedy":
+        subset = np.empty(0, dtype=int)
+    elif subset is None:
+        greedy = _state.css_cov(S=S, subset_size=subset_size, subset=np.empty(0, dtype=int), method="greedy", loss=loss,
+                                max_iters=max_iters, n_threads=n_threads)
+        if isinstance(S, np.ndarray):  # (checked by the constructor above) one upload serves both searches
+            S = greedy.S = matrix.dense(S, method="cov", n_threads=n_threads)
+        subset = greedy.solve().subset
+    if method == "swapping":
+        subset = np.array(subset, dtype=int)
+        subset_size = subset.size
+    state = _state.css_cov(S=S, subset_size=subset_size, subset=subset, method=method, loss=loss, max_iters=max_iters,
+                           n_threads=n_threads)
+    return state.solve()

@@ -1210,3 +1210,113 @@ def gaussian_cov(
     if len(s.grad) != p:
         raise RuntimeError("adelie_core: grad must be (p,) where A is (p, p).")
     return s
+
+
+class css_cov:
+    """Column-subset-selection state on a resident covariance matrix (reference ``adelie.state.css_cov``,
+    ``state.py:3436-3536``; ``StateCSSCov``, ``state_css_cov.ipp``).  ``S`` is a square ndarray (wrapped with
+    ``matrix.dense(S, method="cov")`` when the solve starts) or a resident covariance matrix of ``adelie_amd.matrix``; it is
+    never modified.  The constructor repeats the reference's checks before any device work; ``solve()`` returns a new solved
+    state whose ``S_resid`` stays on the device until it is first read."""
+
+    def __init__(self, S, subset_size, subset, method, loss, max_iters, n_threads):
+        if isinstance(S, np.ndarray):
+            if S.ndim != 2 or S.shape[0] != S.shape[1]:
+                raise RuntimeError("adelie_core: S must be (p, p).")
+            _abi.dtype_code(S.dtype)
+            p = S.shape[1]
+        elif isinstance(S, (_matrix.MatrixCovBase64, _matrix.MatrixCovBase32)):
+            p = S.cols()
+        else:
+            raise ValueError("S must be an instance of MatrixCovBase32, MatrixCovBase64, or np.ndarray.")
+        if method not in _abi.CSS_METHODS:
+            raise ValueError("method must be one of 'greedy' or 'swapping'.")
+        if loss not in _abi.CSS_LOSSES:
+            raise ValueError("loss must be one of 'least_squares', 'subset_factor' or 'min_det'.")
+        subset = np.array(subset, dtype=np.int64).reshape(-1)
+        subset_size = int(subset_size)
+        # state_css_cov.ipp:15-57
+        if subset_size < 0 or subset_size > p:
+            raise RuntimeError("adelie_core: subset_size must be <= p.")
+        if method == "swapping" and subset_size != subset.size:
+            raise RuntimeError("adelie_core: subset must be (subset_size,) if method is \"swapping\".")
+        if method == "swapping" and subset.size and (subset.min() < 0 or subset.max() >= p):
+            raise RuntimeError("adelie_core: subset must be in the range [0, p).")
+        if method == "greedy" and subset.size:
+            raise RuntimeError("adelie_core: subset must be empty if method is \"greedy\".")
+        if n_threads < 1:
+            raise RuntimeError("adelie_core: n_threads must be >= 1.")
+        self.S, self._p = S, p
+        self.subset_size, self.subset, self.method, self.loss = subset_size, subset, method, loss
+        self.max_iters, self.n_threads = int(max_iters), int(n_threads)
+        self.error, self.total_time = "", 0.0
+        self.n_updates = self.n_swaps = self.n_attempts = 0
+        self.early_exit = False
+        self._result = None
+
+    def __del__(self):
+        r, self._result = getattr(self, "_result", None), None
+        if r is not None:
+            try:
+                self._backend.fn("css_result_destroy")(r)
+            except Exception:
+                pass
+
+    def _vec(self, name, dtype):
+        b, r, which = self._backend, self._result, _abi.CSS_V[name]
+        n = b.fn("css_result_size")(r, which)
+        out = np.empty(max(n, 0), dtype=dtype)
+        if n > 0:
+            b.check(b.fn("css_result_copy")(r, which, out.ctypes.data, n))
+        return out
+
+    def solve(self):
+        """Runs the search on the device and returns the solved state (this one is left untouched).  Failures inside the solve
+        are logged and stored in ``error``, as ``state.base.solve`` does."""
+        S = self.S
+        if isinstance(S, np.ndarray):
+            S = _matrix.dense(S, method="cov", n_threads=self.n_threads)
+        backend = S._backend
+        args = _abi.CssArgs(subset_size=self.subset_size, subset=_abi.ptr(self.subset) if self.subset.size else None,
+                            n_subset=self.subset.size, method=_abi.CSS_METHODS[self.method], loss=_abi.CSS_LOSSES[self.loss],
+                            max_iters=self.max_iters, n_threads=self.n_threads)
+        handle = _abi.C.c_void_p()
+        backend.check(backend.fn("css_cov_solve")(S._handle, _abi.C.byref(args), handle))
+        out = css_cov(self.S, self.subset_size, self.subset, self.method, self.loss, self.max_iters, self.n_threads)
+        out._backend, out._result, out._S_dev, out._dtype = backend, handle, S, np.dtype(S.dtype)
+        out.subset = out._vec("subset", np.int64)
+        k = out.subset.size
+        L_T = out._vec("L_T", np.float64)  # empty for greedy and when swapping returned at once (k <= 0 or k >= p)
+        out.L_T = np.asfortranarray(L_T.reshape((k, k), order="F") if L_T.size else np.empty((0, 0)), dtype=out._dtype)
+        scalar = backend.fn("css_result_scalar")
+        out.n_updates, out.n_swaps, out.n_attempts = (int(scalar(handle, _abi.CSS_S[n]))
+                                                      for n in ("n_updates", "n_swaps", "n_attempts"))
+        out.early_exit = bool(scalar(handle, _abi.CSS_S["early_exit"]))
+        out.total_time = float(scalar(handle, _abi.CSS_S["total_time"]))
+        msg = backend.fn("css_result_error")(handle)
+        out.error = msg.decode() if msg else ""
+        if out.error != "":
+            if out.error.startswith("adelie_core solver: "):
+                logger.error(RuntimeError(out.error))
+            else:
+                logger.warning(RuntimeError(out.error))
+        return out
+
+    @property
+    def S_resid_diag(self):
+        """``(p,)`` diagonal of ``S_resid`` (already on the host: the solve downloads it with its last synchronisation)."""
+        if self._result is None:
+            raise RuntimeError("the state has not been solved.")
+        return self._vec("S_resid_diag", self._dtype)
+
+    @property
+    def S_resid(self):
+        """``(p, p)`` residual covariance with respect to ``subset``, fetched from the device on first access.  Both triangles
+        are filled (the reference defines the lower one).  Empty when swapping returned at once (``k <= 0`` or ``k >= p``), as
+        in the reference."""
+        if self._result is None:
+            raise RuntimeError("the state has not been solved.")
+        if getattr(self, "_S_resid", None) is None:
+            v = self._vec("S_resid", self._dtype)
+            self._S_resid = v.reshape((self._p, self._p), order="F") if v.size else np.empty((0, 0), dtype=self._dtype, order="F")
+        return self._S_resid

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define ADELIE_HIP_ABI_VERSION 12
+#define ADELIE_HIP_ABI_VERSION 13
 
 enum adelie_hip_dtype { ADELIE_HIP_F32 = 0, ADELIE_HIP_F64 = 1 };
 enum adelie_hip_order { ADELIE_HIP_COL_MAJOR = 0, ADELIE_HIP_ROW_MAJOR = 1 };
@@ -53,6 +53,7 @@ enum adelie_hip_glm_kind {
 typedef struct adelie_hip_design adelie_hip_design; /* device-resident MatrixNaiveBase object */
 typedef struct adelie_hip_result adelie_hip_result; /* solved state snapshot (the `state` copy _solve returns) */
 typedef struct adelie_hip_glm_cox adelie_hip_glm_cox; /* ABI 11: a Cox family's sort orders and weights, resident on one device */
+typedef struct adelie_hip_css_result adelie_hip_css_result; /* ABI 13: a solved column-subset-selection state */
 
 /* ------------------------------------------------------------------------------------------
  * Library
@@ -571,6 +572,52 @@ int64_t     adelie_hip_result_size(const adelie_hip_result* r, int which);
 int         adelie_hip_result_copy(const adelie_hip_result* r, int which, void* out, int64_t cap);
 double      adelie_hip_result_scalar(const adelie_hip_result* r, int which);
 const char* adelie_hip_result_error(const adelie_hip_result* r);
+
+/* ------------------------------------------------------------------------------------------
+ * ABI 13.  Column subset selection on a resident covariance matrix
+ *   == adelie.solver.css_cov / StateCSSCov{32,64}(...).solve()   (state_css_cov.ipp:8-67, solver_css_cov.hpp:164-537)
+ * `A` is a covariance-method handle (adelie_hip_design_create_cov_dense / _cov_lazy), assumed symmetric and never modified.
+ * The solve keeps one (p, p) residual covariance in HBM (both triangles, so that every access is a contiguous column) and
+ * streams it once per rank-one update with the loss's per-column score fused into the pass (kernels_css.hip).  Greedy runs
+ * without a host synchronisation inside its loop; swapping makes one small device -> host read per attempt (a record of
+ * scalars and k + 1 entries of A) and keeps its k x k Cholesky algebra on the host in double.  The args carry the
+ * constructor arguments of the reference's state; its checks (state_css_cov.ipp:15-57) fail the call, errors raised inside
+ * the solve ("Initial subset are not linearly independent columns.", "Maximum swapping cycles reached!") are recorded in the
+ * result's error string.  Results are bit-reproducible run to run.
+ * ------------------------------------------------------------------------------------------ */
+enum adelie_hip_css_method { ADELIE_HIP_CSS_GREEDY = 0, ADELIE_HIP_CSS_SWAPPING = 1 };
+enum adelie_hip_css_loss { ADELIE_HIP_CSS_LEAST_SQUARES = 0, ADELIE_HIP_CSS_SUBSET_FACTOR = 1, ADELIE_HIP_CSS_MIN_DET = 2 };
+typedef struct adelie_hip_css_args {
+    int64_t        subset_size;
+    const int64_t* subset;      /* (n_subset,) the initial subset of swapping; greedy: n_subset = 0 */
+    int64_t        n_subset;
+    int32_t        method;      /* adelie_hip_css_method */
+    int32_t        loss;        /* adelie_hip_css_loss */
+    int64_t        max_iters;   /* swapping: cycles over the subset */
+    int32_t        n_threads;   /* accepted for API parity (>= 1) */
+    int32_t        _pad0;
+} adelie_hip_css_args;
+int adelie_hip_css_cov_solve(adelie_hip_design* A, const adelie_hip_css_args* args, adelie_hip_css_result** out);
+int adelie_hip_css_result_destroy(adelie_hip_css_result* r);
+enum adelie_hip_css_vec {
+    ADELIE_HIP_CSS_SUBSET = 0,       /* (k,) int64, in selection order (swapping: positional) */
+    ADELIE_HIP_CSS_S_RESID = 1,      /* (p, p) column-major values of the design's dtype, fetched from the device by the copy;
+                                        size 0 when swapping returned at once (k <= 0 or k >= p) */
+    ADELIE_HIP_CSS_S_RESID_DIAG = 2, /* (p,) its diagonal, design's dtype (already on the host) */
+    ADELIE_HIP_CSS_L_T = 3           /* (k, k) column-major double: lower Cholesky factor of A[T, T], T in the rotated order */
+};
+enum adelie_hip_css_scalar {
+    ADELIE_HIP_CSS_N_UPDATES = 0,    /* rank-one passes over the matrix */
+    ADELIE_HIP_CSS_N_SWAPS,
+    ADELIE_HIP_CSS_N_ATTEMPTS,       /* swapping attempts (= host round trips inside the loop) */
+    ADELIE_HIP_CSS_EARLY_EXIT,       /* the score routine's early-exit flag at the last attempt */
+    ADELIE_HIP_CSS_TOTAL_TIME        /* seconds */
+};
+int64_t     adelie_hip_css_result_size(const adelie_hip_css_result* r, int which);
+/* Copies min(size, cap) elements in the element type named above. */
+int         adelie_hip_css_result_copy(const adelie_hip_css_result* r, int which, void* out, int64_t cap);
+double      adelie_hip_css_result_scalar(const adelie_hip_css_result* r, int which);
+const char* adelie_hip_css_result_error(const adelie_hip_css_result* r);
 
 /* ------------------------------------------------------------------------------------------
  * Kernel-level timing hook used by bench.py (HIP events on the design's own stream):
