@@ -153,6 +153,25 @@ CSS_LOSSES = dict(least_squares=0, subset_factor=1, min_det=2)
 CSS_V = dict(subset=0, S_resid=1, S_resid_diag=2, L_T=3)
 CSS_S = dict(n_updates=0, n_swaps=1, n_attempts=2, early_exit=3, total_time=4)
 
+class BvlsArgs(C.Structure):
+    """``adelie_hip_bvls_args`` (ABI 14)."""
+
+    _fields_ = [("X_vars", C.c_void_p), ("lower", C.c_void_p), ("upper", C.c_void_p), ("weights", C.c_void_p),
+                ("beta", C.c_void_p), ("resid", C.c_void_p), ("grad", C.c_void_p),
+                ("n_X_vars", C.c_int64), ("n_lower", C.c_int64), ("n_upper", C.c_int64), ("n_weights", C.c_int64),
+                ("n_beta", C.c_int64), ("n_resid", C.c_int64), ("n_grad", C.c_int64),
+                ("screen_set", C.c_void_p), ("screen_set_size", C.c_int64),
+                ("active_set", C.c_void_p), ("active_set_size", C.c_int64),
+                ("n_active_set", C.c_int64), ("n_is_active", C.c_int64),
+                ("y_var", C.c_double), ("loss", C.c_double), ("kappa", C.c_int64), ("max_iters", C.c_int64),
+                ("tol", C.c_double)]
+
+
+# enum adelie_hip_bvls_vec / adelie_hip_bvls_scalar
+BVLS_V = dict(beta=0, resid=1, grad=2, screen_set=3, active_set=4, is_screen=5, is_active=6)
+BVLS_S = dict(loss=0, iters=1, n_kkt=2, screen_set_size=3, active_set_size=4, total_time=5, t_sweep_ms=6, t_gram_ms=7,
+              t_fit_ms=8, n_changed=9)
+
 # enum adelie_hip_vec / adelie_hip_scalar
 V = dict(
     intercepts=0, devs=1, lmdas=2, lmda_path=3, screen_beta=4, grad=5, abs_grad=6, resid=7, eta=8,
@@ -191,6 +210,7 @@ HIP_SYMBOLS = [
     "grpnet_solve", "grpnet_solve_many", "result_destroy", "result_size", "result_copy", "result_scalar", "result_error", "result_sync",
     "bench_sweep",
     "css_cov_solve", "css_result_destroy", "css_result_size", "css_result_copy", "css_result_scalar", "css_result_error",
+    "bvls_solve", "bvls_result_destroy", "bvls_result_size", "bvls_result_copy", "bvls_result_scalar", "bvls_result_error",
 ]
 
 
@@ -208,7 +228,7 @@ def dtype_code(dtype):
 
 
 # kept equal to ADELIE_HIP_ABI_VERSION in include/adelie_hip.h (tests/test_abi.py compares the two)
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class Backend:
@@ -303,6 +323,12 @@ class Backend:
         sig("css_result_copy", ci, [vp, ci, vp, i64])
         sig("css_result_scalar", dbl, [vp, ci])
         sig("css_result_error", C.c_char_p, [vp])
+        sig("bvls_solve", ci, [vp, p(BvlsArgs), p(vp)])
+        sig("bvls_result_destroy", ci, [vp])
+        sig("bvls_result_size", i64, [vp, ci])
+        sig("bvls_result_copy", ci, [vp, ci, vp, i64])
+        sig("bvls_result_scalar", dbl, [vp, ci])
+        sig("bvls_result_error", C.c_char_p, [vp])
 
     def check(self, rc):
         if rc != 0:

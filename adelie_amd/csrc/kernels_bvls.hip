@@ -1,0 +1,781 @@
+// kernels_bvls.hip — bounded-variable least squares on a resident dense design (adelie.solver.bvls: solver_bvls.hpp,
+// state_bvls.ipp).  Kernels, the host driver and the C-ABI entry points of adelie_hip_bvls_solve.
+//
+// The reference visits one coordinate at a time and pays two n-length passes per visit (cmul for the gradient, ctmul for the
+// residual).  Here the gradient g_a = x_a^T W r of EVERY screen coordinate is kept current through the resident Gram matrix
+// G = X_S^T W X_S (ns x ns, uncentred, both triangles): a visit that changes beta_k by `del` does g_a -= G[a, k] * del for all
+// a (one contiguous Gram column), and a visit that changes nothing touches no memory but a few broadcast reads.  One workgroup
+// runs a whole fit() — screen passes, active-set passes, prune — without leaving the compute unit; the residual is caught up
+// once per fit from the compact list of changes (launch_axpy_cols), and the Gram-updated gradients are thrown away at every KKT
+// round: the screen members' g is re-read from the fresh full gradient X^T (w * r).
+//
+// Visiting order, predicates (`<=`, `==`), counters and exits are the reference's.  Two things are fixed where the reference
+// leaves them open or does them differently without a visible effect:
+//   * kkt_screen sorts the violations with std::sort, which leaves the order of equal violations unspecified (and carries the
+//     previous round's order into the next sort).  Here the indices are sorted with std::stable_sort from 0..p-1 every round,
+//     so ties go to the lower index.
+//   * add_active appends a coordinate at the visit that changes it; here a screen pass raises a flag at that visit and the
+//     flagged non-members are appended, in screen order, at the end of the pass.  A screen pass visits in screen order, so the
+//     list is the same; it is complete before the pass's max-iterations exit is taken.
+//
+// Synchronisation inside the fit kernel.  Every thread evaluates the scalar update of a visit redundantly from broadcast
+// reads, so no shuffle or reduction sits on the visit chain and all control flow is uniform.  g and beta are double-buffered:
+// a changed visit reads buffer `cur`, writes ALL of g and beta to the other buffer and ends with the one barrier of the visit —
+// a slow wavefront still reading g[k] / beta[k] of buffer `cur` cannot see the fast ones' stores.  Unchanged visits have no
+// barrier and no store.  No atomics anywhere: reruns are bit-identical, and the LDS and the global-memory storage of the
+// per-coordinate arrays run the same code and give the same bits.
+#include <cmath>
+#include <limits>
+#include <numeric>
+
+#include "common.hpp"
+
+namespace ahip {
+void set_last_error(const std::string& s); // design.hip
+
+double g_bvls_gram_limit_mb = 16384.0; // adelie_hip_set_config("bvls_gram_limit_mb", x)
+int64_t g_bvls_lds_max_ns = 0;         // adelie_hip_set_config("bvls_lds_max_ns", x): 0 = automatic
+
+namespace {
+
+constexpr int kBvlsThreads = 1024;
+enum { BVLS_OK = 0, BVLS_MAX_ITERS = 1 };
+
+// what a fit and the host exchange; `loss`, `iters` and `n_active` are read on entry and written on exit
+struct BvlsRec {
+    double loss;
+    int64_t iters;
+    int64_t n_visits_changed; // visits that changed a coefficient (this fit)
+    int32_t status;
+    int32_t n_active;
+    int32_t n_changed;        // coordinates whose beta differs from its value at entry (= length of the compact list)
+    int32_t pad;
+};
+
+// bytes of per-coordinate state: g x 2, beta x 2, lower, upper, vars; active list, membership flag, touched flag
+template <class T>
+constexpr size_t bvls_state_bytes(int64_t ns) {
+    return size_t(ns) * (7 * sizeof(T) + 3 * sizeof(int32_t)) + 64;
+}
+
+template <class T>
+struct BvlsFitArgs {
+    const T* G;          // (ns, ns) column-major, leading dimension ld
+    int64_t ld;
+    int32_t ns;
+    const int32_t* cols; // screen members' columns, screen order
+    const T* lower_s;    // screen order
+    const T* upper_s;
+    const T* vars_s;
+    const T* g_s;        // gradient at entry
+    T* beta_s;           // in: beta at entry; out: beta at exit
+    int32_t* act;        // in / out: active set as positions in the screen set
+    T* beta_full;        // (p,) out: beta_full[cols[a]] = beta at exit
+    int32_t* dcol;       // out: compact list for launch_axpy_cols
+    T* dlt;
+    int32_t* cnt_dev;
+    BvlsRec* rec;
+    char* scratch;       // global storage of the per-coordinate state (the non-LDS form)
+    int64_t max_iters;
+    T tol_yvar;          // tol * y_var
+};
+
+// Appends to a list the positions k = src(i), i in [0, count_in) ascending, for which keep(i, k) holds, through emit(slot, k);
+// returns the number appended (the same value in every thread).  The slots are handed out in ascending i: per trip a ballot
+// gives the rank inside a wavefront and the wavefronts' counts go through `wcnt` (LDS, 16 ints).
+template <class Src, class Keep, class Emit>
+__device__ __forceinline__ int bvls_compact(int count_in, int* wcnt, Src src, Keep keep, Emit emit) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = (blockDim.x + 63) >> 6;
+    int total = 0;
+    for (int base = 0; base < count_in; base += blockDim.x) {
+        const int i = base + tid;
+        int k = 0;
+        bool f = false;
+        if (i < count_in) {
+            k = src(i);
+            f = keep(i, k);
+        }
+        const unsigned long long m = __ballot(f);
+        const int within = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wcnt[wave] = __popcll(m);
+        __syncthreads();
+        int off = 0, tot = 0;
+        for (int w = 0; w < nw; ++w) {
+            const int c = wcnt[w];
+            off += w < wave ? c : 0;
+            tot += c;
+        }
+        if (f) emit(total + off + within, k);
+        total += tot;
+        __syncthreads();
+    }
+    return total;
+}
+
+template <class T, bool LDS>
+__global__ __launch_bounds__(kBvlsThreads) void bvls_fit_kernel(BvlsFitArgs<T> A) {
+    extern __shared__ __attribute__((aligned(16))) char bvls_sm[];
+    __shared__ int wcnt[kBvlsThreads / 64];
+    const int tid = threadIdx.x, bd = blockDim.x, ns = A.ns;
+    // no __restrict__ on the state: the same arrays are read and written across barriers
+    char* base = LDS ? bvls_sm : A.scratch;
+    T* g0 = reinterpret_cast<T*>(base);
+    T* g1 = g0 + ns;
+    T* b0 = g1 + ns;
+    T* b1 = b0 + ns;
+    T* lo = b1 + ns;
+    T* up = lo + ns;
+    T* var = up + ns;
+    int32_t* act = reinterpret_cast<int32_t*>(var + ns);
+    int32_t* isact = act + ns;
+    int32_t* touched = isact + ns;
+
+    int nact = A.rec->n_active;
+    for (int a = tid; a < ns; a += bd) {
+        g0[a] = A.g_s[a];
+        b0[a] = A.beta_s[a];
+        lo[a] = A.lower_s[a];
+        up[a] = A.upper_s[a];
+        var[a] = A.vars_s[a];
+        isact[a] = 0;
+        touched[a] = 0;
+    }
+    __syncthreads();
+    for (int i = tid; i < nact; i += bd) {
+        const int k = A.act[i];
+        act[i] = k;
+        isact[k] = 1;
+    }
+    __syncthreads();
+
+    T loss = T(A.rec->loss);
+    int64_t iters = A.rec->iters;
+    int64_t nvis = 0;
+    const int64_t max_iters = A.max_iters;
+    const T tol_yvar = A.tol_yvar;
+    int cur = 0, status = BVLS_OK;
+    T convg = T(0);
+
+    // coordinate_descent's body for position k (solver_bvls.hpp:44-60); SCREEN: raise the touched flag (add_active)
+    auto visit = [&](int k, bool screen) {
+#pragma clang fp contract(off)
+        const T* gc = cur ? g1 : g0;
+        const T* bc = cur ? b1 : b0;
+        const T vk = var[k], lk = lo[k], uk = up[k], gk = gc[k], bk = bc[k];
+        const T step = (vk <= T(0)) ? T(0) : (gk / vk);
+        const T cand = bk + step;
+        const T hi = (cand < lk) ? lk : cand; // std::max(cand, lk)
+        const T bn = (uk < hi) ? uk : hi;     // std::min(hi, uk)
+        if (bn == bk) return;
+        const T del = bn - bk;
+        const T sds = vk * del * del;
+        convg = (convg < sds) ? sds : convg;
+        loss -= del * gk - T(0.5) * sds;
+        T* gn = cur ? g0 : g1;
+        T* bx = cur ? b0 : b1;
+        const T* Gk = A.G + int64_t(k) * A.ld;
+        for (int a = tid; a < ns; a += bd) {
+            gn[a] = gc[a] - Gk[a] * del;
+            bx[a] = a == k ? bn : bc[a];
+        }
+        if (screen && tid == 0) touched[k] = 1;
+        ++nvis;
+        cur ^= 1;
+        __syncthreads();
+    };
+    auto prune = [&]() { // in place: a kept member moves to a slot at or before its own
+        const T* bc = cur ? b1 : b0;
+        nact = bvls_compact(
+            nact, wcnt, [&](int i) { return act[i]; },
+            [&](int, int k) {
+                const T b = bc[k];
+                const bool drop = b <= lo[k] || b >= up[k];
+                if (drop) isact[k] = 0;
+                return !drop;
+            },
+            [&](int slot, int k) { act[slot] = k; });
+    };
+
+    while (true) { // fit(): solver_bvls.hpp:175-214
+        ++iters;
+        convg = T(0);
+        for (int k = 0; k < ns; ++k) visit(k, true);
+        {   // the pass's add_active calls, in screen order
+            const int base_n = nact;
+            nact += bvls_compact(
+                ns, wcnt, [&](int i) { return i; }, [&](int, int k) { return touched[k] != 0 && isact[k] == 0; },
+                [&](int slot, int k) { act[base_n + slot] = k; });
+            for (int a = tid; a < ns; a += bd) {
+                if (touched[a]) isact[a] = 1;
+                touched[a] = 0;
+            }
+            __syncthreads();
+        }
+        if (iters >= max_iters) {
+            status = BVLS_MAX_ITERS;
+            break;
+        }
+        if (convg <= tol_yvar) {
+            prune();
+            break;
+        }
+        bool stop = false;
+        while (true) { // solve_active(): solver_bvls.hpp:91-111
+            ++iters;
+            convg = T(0);
+            for (int i = 0; i < nact; ++i) visit(act[i], false);
+            if (iters >= max_iters) {
+                status = BVLS_MAX_ITERS;
+                stop = true;
+                break;
+            }
+            if (convg <= tol_yvar) break;
+        }
+        if (stop) break;
+        prune();
+    }
+
+    // exit: the compact (column, change) list, beta, the active set, the report
+    const T* bc = cur ? b1 : b0;
+    const int nchg = bvls_compact(
+        ns, wcnt, [&](int i) { return i; }, [&](int, int k) { return bc[k] != A.beta_s[k]; },
+        [&](int slot, int k) {
+            A.dcol[slot] = A.cols[k];
+            A.dlt[slot] = bc[k] - A.beta_s[k];
+        });
+    // (bvls_compact ends with a barrier: every read of beta at entry is done)
+    for (int a = tid; a < ns; a += bd) {
+        const T b = bc[a];
+        A.beta_s[a] = b;
+        A.beta_full[A.cols[a]] = b;
+    }
+    for (int i = tid; i < nact; i += bd) A.act[i] = act[i];
+    if (tid == 0) {
+        A.rec->loss = double(loss);
+        A.rec->iters = iters;
+        A.rec->n_visits_changed = nvis;
+        A.rec->status = status;
+        A.rec->n_active = nact;
+        A.rec->n_changed = nchg;
+        A.cnt_dev[0] = nchg;
+    }
+}
+
+// viols_j = max(grad_j, 0) [beta_j < upper_j] - min(grad_j, 0) [beta_j > lower_j]   (solver_bvls.hpp:266-271); grad is kept
+template <class T>
+__global__ __launch_bounds__(256) void bvls_viols_kernel(const T* __restrict__ grad, const T* __restrict__ beta,
+                                                         const T* __restrict__ lower, const T* __restrict__ upper, int64_t p,
+                                                         T* __restrict__ viols) {
+    const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (j >= p) return;
+    const T g = grad[j], b = beta[j];
+    const T gp = g > T(0) ? g : T(0), gm = g < T(0) ? g : T(0);
+    viols[j] = gp * T(b < upper[j] ? 1 : 0) - gm * T(b > lower[j] ? 1 : 0);
+}
+
+// screen-order copies for the fit kernel: g of every member from `src` (the full gradient: src[cols[a]], or a sweep of the screen
+// columns: src[a]); bounds, variances and beta of the members from position a0 on
+template <class T>
+__global__ __launch_bounds__(256) void bvls_gather_kernel(const int32_t* __restrict__ cols, int32_t ns, int32_t a0,
+                                                          const T* __restrict__ src, int by_col, const T* __restrict__ lower,
+                                                          const T* __restrict__ upper, const T* __restrict__ vars,
+                                                          const T* __restrict__ beta, T* __restrict__ g_s,
+                                                          T* __restrict__ lower_s, T* __restrict__ upper_s,
+                                                          T* __restrict__ vars_s, T* __restrict__ beta_s) {
+    const int32_t a = int32_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (a >= ns) return;
+    const int64_t j = cols[a];
+    g_s[a] = by_col ? src[j] : src[a];
+    if (a >= a0) {
+        lower_s[a] = lower[j];
+        upper_s[a] = upper[j];
+        vars_s[a] = vars[j];
+        beta_s[a] = beta[j];
+    }
+}
+
+unsigned blocks_for(int64_t n, int per) { return unsigned((n + per - 1) / per); }
+
+} // namespace
+} // namespace ahip
+
+using namespace ahip;
+
+struct adelie_hip_bvls_result {
+    int dtype = ADELIE_HIP_F64, device = 0;
+    int64_t n = 0, p = 0;
+    std::vector<char> beta, resid, grad; // of dtype
+    std::vector<int64_t> screen_set, active_set;
+    std::vector<uint8_t> is_screen, is_active;
+    double loss = 0;
+    int64_t iters = 0, n_kkt = 0, n_changed = 0;
+    double total_time = 0, t_sweep_ms = 0, t_gram_ms = 0, t_fit_ms = 0;
+    std::string error;
+};
+
+namespace {
+
+struct Pinned {
+    void* p = nullptr;
+    size_t bytes = 0;
+    explicit Pinned(size_t n) : bytes((n + 4095) / 4096 * 4096) {
+        p = HostPool::take(bytes, hipHostMallocDefault);
+        if (!p) throw core_error("adelie_hip: hipHostMalloc failed");
+    }
+    ~Pinned() { HostPool::give(p, bytes, hipHostMallocDefault); }
+};
+
+// HIP-event time of the three device phases; collected after a stream synchronisation
+struct PhaseTimer {
+    struct Span { hipEvent_t a, b; int cat; };
+    std::vector<Span> open;
+    std::vector<hipEvent_t> idle;
+    double ms[3] = {0, 0, 0};
+    hipEvent_t get() {
+        if (!idle.empty()) {
+            hipEvent_t e = idle.back();
+            idle.pop_back();
+            return e;
+        }
+        hipEvent_t e;
+        AHIP_CHECK(hipEventCreate(&e));
+        return e;
+    }
+    void begin(int cat, hipStream_t s) {
+        Span sp{get(), get(), cat};
+        AHIP_CHECK(hipEventRecord(sp.a, s));
+        open.push_back(sp);
+    }
+    void end(hipStream_t s) { AHIP_CHECK(hipEventRecord(open.back().b, s)); }
+    void collect() { // (the stream is idle)
+        for (const Span& sp : open) {
+            float t = 0;
+            if (hipEventElapsedTime(&t, sp.a, sp.b) == hipSuccess) ms[sp.cat] += double(t);
+            else (void)hipGetLastError();
+            idle.push_back(sp.a);
+            idle.push_back(sp.b);
+        }
+        open.clear();
+    }
+    ~PhaseTimer() {
+        for (const Span& sp : open) idle.push_back(sp.a), idle.push_back(sp.b);
+        for (hipEvent_t e : idle) (void)hipEventDestroy(e);
+    }
+};
+enum { PH_SWEEP = 0, PH_GRAM = 1, PH_FIT = 2 };
+
+template <class T>
+struct BvlsSolver {
+    adelie_hip_design* X;
+    adelie_hip_bvls_result* res;
+    const adelie_hip_bvls_args* a;
+    int64_t n, p;
+    hipStream_t s;
+    DenseView<T> Xv;
+    DeferredFrees deferred;
+    PhaseTimer timer;
+
+    // full vectors
+    DevBuf<T> d_w, d_r, d_v, d_grad, d_viols, d_beta, d_lower, d_upper, d_vars;
+    // screen order
+    DevBuf<int32_t> d_cols, d_act, d_dcol, d_cnt;
+    DevBuf<T> d_g, d_lower_s, d_upper_s, d_vars_s, d_beta_s, d_dlt, d_sweep_out;
+    DevBuf<T> d_G, d_work_sweep, d_work_gram;
+    DevBuf<char> d_scratch;
+    DevBuf<BvlsRec> d_rec;
+    int64_t ld = 0;
+    size_t cap_s = 0; // capacity of the screen-order buffers
+
+    std::vector<int64_t> screen_set, active_pos;
+    std::vector<uint8_t> is_screen;
+    std::vector<int32_t> h_cols;
+    std::vector<T> h_viols;
+    bool have_viols = false;
+    int64_t ns = 0;
+    int lds_limit = 0;
+    bool attr_done[2] = {false, false};
+
+    T loss;
+    int64_t iters = 0, n_kkt = 0, nact = 0;
+
+    BvlsSolver(adelie_hip_design* X_, const adelie_hip_bvls_args* a_, adelie_hip_bvls_result* r) : X(X_), res(r), a(a_) {
+        n = X->n;
+        p = X->p;
+        s = X->stream;
+        Xv = X->dense<T>();
+        loss = T(a->loss);
+    }
+
+    // grow the screen-order buffers to hold `want` members, keeping the first `keep`
+    void reserve_screen(int64_t want, int64_t keep) {
+        if (size_t(want) <= cap_s) return;
+        size_t c = std::max<size_t>(size_t(want), cap_s + cap_s / 2);
+        c = std::min<size_t>(std::max<size_t>(c, 64), size_t(p));
+        c = std::max<size_t>(c, size_t(want));
+        d_cols.grow(c, size_t(keep), s);
+        d_act.grow(c, size_t(keep), s);
+        d_lower_s.grow(c, size_t(keep), s);
+        d_upper_s.grow(c, size_t(keep), s);
+        d_vars_s.grow(c, size_t(keep), s);
+        d_beta_s.grow(c, size_t(keep), s);
+        d_g.reserve(c), d_dcol.reserve(c), d_dlt.reserve(c), d_sweep_out.reserve(c);
+        cap_s = c;
+    }
+    // the Gram matrix for ns_new members: false when it would pass the limit
+    bool reserve_gram(int64_t ns_new, int64_t ns_old) {
+        if (double(ns_new) * double(ns_new) * double(sizeof(T)) > g_bvls_gram_limit_mb * 1048576.0) return false;
+        if (ns_new <= ld) return true;
+        int64_t nl = std::max<int64_t>(std::max<int64_t>(ns_new, ld + ld / 2), 64);
+        nl = std::min<int64_t>(nl, std::max<int64_t>(p, ns_new));
+        if (double(nl) * double(nl) * double(sizeof(T)) > g_bvls_gram_limit_mb * 1048576.0) nl = ns_new;
+        DevBuf<T> ng;
+        ng.reserve(size_t(nl) * size_t(nl));
+        if (ns_old > 0)
+            AHIP_CHECK(hipMemcpy2DAsync(ng.p, size_t(nl) * sizeof(T), d_G.p, size_t(ld) * sizeof(T), size_t(ns_old) * sizeof(T),
+                                        size_t(ns_old), hipMemcpyDeviceToDevice, s));
+        std::swap(ng.p, d_G.p);
+        std::swap(ng.cap, d_G.cap);
+        ng.release(); // (kept until the end of the solve: DeferredFrees)
+        ld = nl;
+        return true;
+    }
+    void vmul_sweep(const int32_t* cols, int64_t ncols, T* out) {
+        timer.begin(PH_SWEEP, s);
+        launch_vmul<T>(d_w.p, d_r.p, d_v.p, n, s);
+        T* work = d_work_sweep.reserve(size_t(sweep_work_elems(n, ncols)));
+        launch_sweep<T>(Xv, d_v.p, out, 0, ncols, cols, nullptr, nullptr, false, work, s);
+        timer.end(s);
+    }
+    // rows and columns [ns_old, ns_new) of G
+    void extend_gram(int64_t ns_old, int64_t ns_new) {
+        const int64_t N = ns_new - ns_old;
+        if (N <= 0) return;
+        T* work = d_work_gram.reserve(size_t(gram_work_elems(n, ns_new, N)));
+        timer.begin(PH_GRAM, s);
+        launch_gram<T>(Xv, d_w.p, d_cols.p, int32_t(ns_new), 0, d_cols.p + ns_old, int32_t(N), int32_t(ns_old), nullptr, false,
+                       d_G.p, ld, work, s);
+        timer.end(s);
+    }
+    void gather(int64_t a0, const T* src, bool by_col) {
+        hipLaunchKernelGGL((bvls_gather_kernel<T>), dim3(blocks_for(ns, 256)), dim3(256), 0, s, d_cols.p, int32_t(ns), int32_t(a0),
+                           src, by_col ? 1 : 0, d_lower.p, d_upper.p, d_vars.p, d_beta.p, d_g.p, d_lower_s.p, d_upper_s.p,
+                           d_vars_s.p, d_beta_s.p);
+    }
+
+    template <bool LDS>
+    void launch_fit(const BvlsFitArgs<T>& fa, unsigned threads, size_t lds) {
+        if (LDS && !attr_done[1]) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bvls_fit_kernel<T, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit);
+            (void)hipGetLastError();
+            attr_done[1] = true;
+        }
+        hipLaunchKernelGGL((bvls_fit_kernel<T, LDS>), dim3(1), dim3(threads), LDS ? lds : 0, s, fa);
+    }
+    void fit(BvlsRec* h_rec) {
+        BvlsFitArgs<T> fa;
+        fa.G = d_G.p, fa.ld = ld, fa.ns = int32_t(ns), fa.cols = d_cols.p;
+        fa.lower_s = d_lower_s.p, fa.upper_s = d_upper_s.p, fa.vars_s = d_vars_s.p, fa.g_s = d_g.p, fa.beta_s = d_beta_s.p;
+        fa.act = d_act.p, fa.beta_full = d_beta.p, fa.dcol = d_dcol.p, fa.dlt = d_dlt.p, fa.cnt_dev = d_cnt.p, fa.rec = d_rec.p;
+        fa.max_iters = a->max_iters;
+        fa.tol_yvar = T(a->tol) * T(a->y_var);
+        const size_t bytes = bvls_state_bytes<T>(ns);
+        // the static LDS of the kernel (the wavefront counts) comes out of the same budget
+        const bool lds = bytes + 256 <= size_t(lds_limit) && (g_bvls_lds_max_ns <= 0 || ns <= g_bvls_lds_max_ns);
+        fa.scratch = lds ? nullptr : d_scratch.reserve(bytes);
+        const unsigned threads = unsigned(std::min<int64_t>(kBvlsThreads, std::max<int64_t>(64, (ns + 63) / 64 * 64)));
+        h_rec->loss = double(loss), h_rec->iters = iters, h_rec->n_visits_changed = 0, h_rec->status = 0;
+        h_rec->n_active = int32_t(nact), h_rec->n_changed = 0, h_rec->pad = 0;
+        AHIP_CHECK(hipMemcpyAsync(d_rec.p, h_rec, sizeof(BvlsRec), hipMemcpyHostToDevice, s));
+        timer.begin(PH_FIT, s);
+        if (lds) launch_fit<true>(fa, threads, bytes);
+        else launch_fit<false>(fa, threads, 0);
+        timer.end(s);
+        // r -= X * delta
+        launch_axpy_cols<T>(Xv, d_dcol.p, d_dlt.p, d_cnt.p, 0, T(-1), d_r.p, s);
+        AHIP_CHECK(hipMemcpyAsync(h_rec, d_rec.p, sizeof(BvlsRec), hipMemcpyDeviceToHost, s));
+        AHIP_CHECK(hipStreamSynchronize(s));
+        AHIP_CHECK(hipGetLastError());
+        timer.collect();
+        loss = T(h_rec->loss);
+        iters = h_rec->iters;
+        nact = h_rec->n_active;
+        res->n_changed += h_rec->n_visits_changed;
+    }
+
+    void finish() {
+        AHIP_CHECK(hipStreamSynchronize(s));
+        timer.collect();
+        const size_t es = sizeof(T);
+        res->beta.resize(size_t(p) * es), res->resid.resize(size_t(n) * es), res->grad.resize(size_t(p) * es);
+        if (p) AHIP_CHECK(hipMemcpyAsync(res->beta.data(), d_beta.p, size_t(p) * es, hipMemcpyDeviceToHost, s));
+        if (n) AHIP_CHECK(hipMemcpyAsync(res->resid.data(), d_r.p, size_t(n) * es, hipMemcpyDeviceToHost, s));
+        std::vector<int32_t> hact(static_cast<size_t>(nact));
+        if (nact) AHIP_CHECK(hipMemcpyAsync(hact.data(), d_act.p, size_t(nact) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        AHIP_CHECK(hipStreamSynchronize(s));
+        AHIP_CHECK(hipGetLastError());
+        if (have_viols) std::memcpy(res->grad.data(), h_viols.data(), size_t(p) * es);
+        else if (p) std::memcpy(res->grad.data(), a->grad, size_t(p) * es);
+        res->screen_set = screen_set;
+        res->is_screen = is_screen;
+        res->active_set.resize(size_t(nact));
+        res->is_active.assign(size_t(p), 0);
+        for (int64_t i = 0; i < nact; ++i) {
+            const int64_t j = screen_set[size_t(hact[size_t(i)])];
+            res->active_set[size_t(i)] = j;
+            res->is_active[size_t(j)] = 1;
+        }
+        res->loss = double(loss);
+        res->iters = iters;
+        res->n_kkt = n_kkt;
+        res->t_sweep_ms = timer.ms[PH_SWEEP], res->t_gram_ms = timer.ms[PH_GRAM], res->t_fit_ms = timer.ms[PH_FIT];
+    }
+
+    void run() {
+        DeferredFrees::Scope scope(&deferred);
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, X->device) != hipSuccess || v <= 0) {
+            (void)hipGetLastError();
+            v = 65536;
+        }
+        lds_limit = v;
+        d_w.reserve(size_t(n)), d_r.reserve(size_t(n)), d_v.reserve(size_t(n));
+        d_grad.reserve(size_t(p)), d_viols.reserve(size_t(p)), d_beta.reserve(size_t(p));
+        d_lower.reserve(size_t(p)), d_upper.reserve(size_t(p)), d_vars.reserve(size_t(p));
+        d_cnt.reserve(4), d_rec.reserve(1);
+        d_w.upload(static_cast<const T*>(a->weights), size_t(n), s);
+        d_r.upload(static_cast<const T*>(a->resid), size_t(n), s);
+        d_beta.upload(static_cast<const T*>(a->beta), size_t(p), s);
+        d_lower.upload(static_cast<const T*>(a->lower), size_t(p), s);
+        d_upper.upload(static_cast<const T*>(a->upper), size_t(p), s);
+        d_vars.upload(static_cast<const T*>(a->X_vars), size_t(p), s);
+        h_viols.resize(size_t(p));
+        is_screen.assign(size_t(p), 0);
+        Pinned pin(sizeof(BvlsRec));
+        BvlsRec* h_rec = static_cast<BvlsRec*>(pin.p);
+
+        // the caller's screen and active sets (a warm start)
+        std::vector<int64_t> pos_of;
+        if (a->screen_set_size > 0) pos_of.assign(size_t(p), -1);
+        for (int64_t i = 0; i < a->screen_set_size; ++i) {
+            const int64_t j = a->screen_set[i];
+            screen_set.push_back(j);
+            is_screen[size_t(j)] = 1;
+            pos_of[size_t(j)] = i;
+        }
+        ns = int64_t(screen_set.size());
+        nact = a->active_set_size;
+        if (ns > 0) {
+            reserve_screen(ns, 0);
+            h_cols.assign(screen_set.begin(), screen_set.end());
+            d_cols.upload(h_cols.data(), size_t(ns), s);
+            std::vector<int32_t> hact(static_cast<size_t>(nact));
+            for (int64_t i = 0; i < nact; ++i) hact[size_t(i)] = int32_t(pos_of[size_t(a->active_set[i])]);
+            if (nact) d_act.upload(hact.data(), size_t(nact), s);
+            AHIP_CHECK(hipStreamSynchronize(s)); // (hact / h_cols are read by the copies)
+            if (!reserve_gram(ns, 0)) return gram_limit_error(ns);
+            extend_gram(0, ns);
+            vmul_sweep(d_cols.p, ns, d_sweep_out.p);
+            gather(0, d_sweep_out.p, false);
+            AHIP_CHECK(hipStreamSynchronize(s)); // (hact / h_cols are read by the copies)
+        }
+
+        while (true) { // solve(): solver_bvls.hpp:329-347
+            const T loss_prev = loss;
+            if (ns > 0) {
+                fit(h_rec);
+                if (h_rec->status == BVLS_MAX_ITERS) {
+                    res->error = "adelie_core solver: bvls: max iterations reached!";
+                    return finish();
+                }
+            } else { // an empty screen pass
+                ++iters;
+                if (iters >= a->max_iters) {
+                    res->error = "adelie_core solver: bvls: max iterations reached!";
+                    return finish();
+                }
+            }
+            if (n_kkt > 0 && double(std::abs(loss - loss_prev)) < 1e-6 * double(std::abs(T(a->y_var)))) return finish();
+            // kkt_screen(): :229-304
+            ++n_kkt;
+            vmul_sweep(nullptr, p, d_grad.p);
+            hipLaunchKernelGGL((bvls_viols_kernel<T>), dim3(blocks_for(p, 256)), dim3(256), 0, s, d_grad.p, d_beta.p, d_lower.p,
+                               d_upper.p, p, d_viols.p);
+            AHIP_CHECK(hipMemcpyAsync(h_viols.data(), d_viols.p, size_t(p) * sizeof(T), hipMemcpyDeviceToHost, s));
+            AHIP_CHECK(hipStreamSynchronize(s));
+            AHIP_CHECK(hipGetLastError());
+            timer.collect();
+            have_viols = true;
+            std::vector<int64_t> order(static_cast<size_t>(p));
+            std::iota(order.begin(), order.end(), int64_t(0));
+            std::stable_sort(order.begin(), order.end(),
+                             [&](int64_t i, int64_t j) { return h_viols[size_t(i)] > h_viols[size_t(j)]; });
+            std::vector<int64_t> added;
+            bool kkt_passed = true;
+            for (int64_t t = 0; t < p; ++t) {
+                const int64_t k = order[size_t(t)];
+                if (is_screen[size_t(k)] || h_viols[size_t(k)] <= T(0)) continue;
+                kkt_passed = false;
+                if (int64_t(added.size()) >= a->kappa) break;
+                added.push_back(k);
+            }
+            if (kkt_passed) return finish();
+            const int64_t ns_old = ns, ns_new = ns + int64_t(added.size());
+            if (!reserve_gram(ns_new, ns_old)) return gram_limit_error(ns_new);
+            reserve_screen(ns_new, ns_old);
+            for (int64_t k : added) {
+                screen_set.push_back(k);
+                is_screen[size_t(k)] = 1;
+            }
+            h_cols.assign(added.begin(), added.end());
+            d_cols.upload(h_cols.data(), h_cols.size(), s, size_t(ns_old));
+            ns = ns_new;
+            extend_gram(ns_old, ns_new);
+            gather(ns_old, d_grad.p, true);
+            AHIP_CHECK(hipStreamSynchronize(s)); // (h_cols is read by the copy)
+        }
+    }
+    void gram_limit_error(int64_t ns_want) {
+        res->error = "adelie_core solver: bvls: screen set of " + std::to_string(ns_want) +
+                     " coordinates exceeds the device Gram limit";
+        finish();
+    }
+};
+
+template <class T>
+void bvls_run(adelie_hip_design* X, const adelie_hip_bvls_args* a, adelie_hip_bvls_result* res) {
+    BvlsSolver<T> sv(X, a, res);
+    try {
+        sv.run();
+    } catch (...) {
+        (void)hipStreamSynchronize(X->stream); // the buffers are parked by the destructors
+        throw;
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+int adelie_hip_bvls_solve(adelie_hip_design* X, const adelie_hip_bvls_args* a, adelie_hip_bvls_result** out) {
+    adelie_hip_bvls_result* res = nullptr;
+    try {
+        if (!X || !a || !out) throw make_core_error("null argument.");
+        if (X->kind != 0 || X->cov || X->std_center)
+            throw make_core_error("bvls: X must be a plain dense design on this route.");
+        const int64_t n = X->n, p = X->p;
+        // state_bvls.ipp:15-74
+        if (a->n_X_vars != p) throw make_solver_error("X_vars must be (p,) where X is (n, p). ");
+        if (a->n_lower != p) throw make_solver_error("lower must be (p,) where X is (n, p). ");
+        if (a->n_upper != p) throw make_solver_error("upper must be (p,) where X is (n, p). ");
+        if (a->n_weights != n) throw make_solver_error("weights must be (n,) where X is (n, p). ");
+        if (a->kappa <= 0) throw make_solver_error("kappa must be > 0. ");
+        if (a->tol < 0) throw make_solver_error("tol must be >= 0.");
+        if (a->active_set_size > p) throw make_solver_error("active_set_size must be <= p where X is (n, p). ");
+        if (a->n_active_set != p) throw make_solver_error("active_set must be (p,) where X is (n, p). ");
+        if (a->n_is_active != p) throw make_solver_error("is_active must be (p,) where X is (n, p). ");
+        if (a->n_beta != p) throw make_solver_error("beta must be (p,) where X is (p, n). ");
+        if (a->n_resid != n) throw make_solver_error("resid must be (n,) where X is (n, p). ");
+        if (a->n_grad != p) throw make_solver_error("grad must be (p,) where X is (n, p). ");
+        if (p >= (int64_t(1) << 31)) throw make_core_error("bvls: p must be below 2^31.");
+        if (n <= 0 || p <= 0) throw make_core_error("bvls: X must not be empty.");
+        if ((p && (!a->X_vars || !a->lower || !a->upper || !a->beta || !a->grad)) || (n && (!a->weights || !a->resid)))
+            throw make_core_error("null argument.");
+        if (a->screen_set_size < 0 || a->screen_set_size > p || a->active_set_size < 0 ||
+            (a->screen_set_size && !a->screen_set) || (a->active_set_size && !a->active_set))
+            throw make_core_error("bvls: screen_set_size must be in [0, p].");
+        {   // distinct members in range; the active set inside the screen set (what the solver itself maintains)
+            std::vector<uint8_t> seen(size_t(p), 0);
+            for (int64_t i = 0; i < a->screen_set_size; ++i) {
+                const int64_t j = a->screen_set[i];
+                if (j < 0 || j >= p || seen[size_t(j)]) throw make_core_error("bvls: screen_set must hold distinct indices in [0, p).");
+                seen[size_t(j)] = 1;
+            }
+            for (int64_t i = 0; i < a->active_set_size; ++i) {
+                const int64_t j = a->active_set[i];
+                if (j < 0 || j >= p || seen[size_t(j)] != 1)
+                    throw make_core_error("bvls: active_set must hold distinct members of screen_set.");
+                seen[size_t(j)] = 2;
+            }
+        }
+        AHIP_CHECK(hipSetDevice(X->device));
+        res = new adelie_hip_bvls_result;
+        res->dtype = X->dtype;
+        res->device = X->device;
+        res->n = n;
+        res->p = p;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (X->dtype == ADELIE_HIP_F64) bvls_run<double>(X, a, res);
+        else bvls_run<float>(X, a, res);
+        res->total_time = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        *out = res;
+    } catch (const std::exception& e) {
+        delete res;
+        set_last_error(e.what());
+        return 1;
+    }
+    return 0;
+}
+
+int adelie_hip_bvls_result_destroy(adelie_hip_bvls_result* r) {
+    delete r;
+    return 0;
+}
+
+int64_t adelie_hip_bvls_result_size(const adelie_hip_bvls_result* r, int which) {
+    if (!r) return -1;
+    switch (which) {
+        case ADELIE_HIP_BVLS_BETA:
+        case ADELIE_HIP_BVLS_GRAD:
+        case ADELIE_HIP_BVLS_IS_SCREEN:
+        case ADELIE_HIP_BVLS_IS_ACTIVE: return r->p;
+        case ADELIE_HIP_BVLS_RESID: return r->n;
+        case ADELIE_HIP_BVLS_SCREEN_SET: return int64_t(r->screen_set.size());
+        case ADELIE_HIP_BVLS_ACTIVE_SET: return int64_t(r->active_set.size());
+    }
+    return -1;
+}
+
+int adelie_hip_bvls_result_copy(const adelie_hip_bvls_result* r, int which, void* out, int64_t cap) {
+    try {
+        const int64_t size = adelie_hip_bvls_result_size(r, which);
+        if (size < 0 || !out) throw make_core_error("unknown result vector.");
+        const size_t m = size_t(std::min(size, cap));
+        const size_t es = r->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
+        if (!m) return 0;
+        switch (which) {
+            case ADELIE_HIP_BVLS_BETA: std::memcpy(out, r->beta.data(), m * es); break;
+            case ADELIE_HIP_BVLS_RESID: std::memcpy(out, r->resid.data(), m * es); break;
+            case ADELIE_HIP_BVLS_GRAD: std::memcpy(out, r->grad.data(), m * es); break;
+            case ADELIE_HIP_BVLS_SCREEN_SET: std::memcpy(out, r->screen_set.data(), m * sizeof(int64_t)); break;
+            case ADELIE_HIP_BVLS_ACTIVE_SET: std::memcpy(out, r->active_set.data(), m * sizeof(int64_t)); break;
+            case ADELIE_HIP_BVLS_IS_SCREEN: std::memcpy(out, r->is_screen.data(), m); break;
+            case ADELIE_HIP_BVLS_IS_ACTIVE: std::memcpy(out, r->is_active.data(), m); break;
+        }
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return 1;
+    }
+    return 0;
+}
+
+double adelie_hip_bvls_result_scalar(const adelie_hip_bvls_result* r, int which) {
+    if (!r) return 0;
+    switch (which) {
+        case ADELIE_HIP_BVLS_LOSS: return r->loss;
+        case ADELIE_HIP_BVLS_ITERS: return double(r->iters);
+        case ADELIE_HIP_BVLS_N_KKT: return double(r->n_kkt);
+        case ADELIE_HIP_BVLS_SCREEN_SET_SIZE: return double(r->screen_set.size());
+        case ADELIE_HIP_BVLS_ACTIVE_SET_SIZE: return double(r->active_set.size());
+        case ADELIE_HIP_BVLS_TOTAL_TIME: return r->total_time;
+        case ADELIE_HIP_BVLS_T_SWEEP_MS: return r->t_sweep_ms;
+        case ADELIE_HIP_BVLS_T_GRAM_MS: return r->t_gram_ms;
+        case ADELIE_HIP_BVLS_T_FIT_MS: return r->t_fit_ms;
+        case ADELIE_HIP_BVLS_N_CHANGED: return double(r->n_changed);
+    }
+    return 0;
+}
+
+const char* adelie_hip_bvls_result_error(const adelie_hip_bvls_result* r) { return r ? r->error.c_str() : ""; }
+
+} // extern "C"

@@ -640,6 +640,11 @@ void adelie_hip_internal_batch_stats(void* b, double* out) {
     out[2] = sb->timer.ms;
 }
 
+namespace ahip {
+extern double g_bvls_gram_limit_mb; // kernels_bvls.hip
+extern int64_t g_bvls_lds_max_ns;
+} // namespace ahip
+
 extern "C" {
 
 int adelie_hip_set_config(const char* name, double value) {
@@ -651,6 +656,8 @@ int adelie_hip_set_config(const char* name, double value) {
         DevPool::limit_bytes() = value > 0 ? size_t(value) << 20 : 0;
         if (value <= 0) DevPool::trim();
     } else if (nm == "pool_trim") DevPool::trim();
+    else if (nm == "bvls_gram_limit_mb") ahip::g_bvls_gram_limit_mb = value > 0 ? value : 16384.0;
+    else if (nm == "bvls_lds_max_ns") ahip::g_bvls_lds_max_ns = value > 0 ? int64_t(value) : 0;
     else {
         set_last_error("adelie_core: unknown config name.");
         return 1;

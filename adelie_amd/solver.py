@@ -23,8 +23,11 @@ from typing import Callable
 
 import numpy as np
 
+from scipy.sparse import csr_matrix
+
 from . import matrix
 from . import state as _state
+from .configs import Configs
 
 # What a warm start hands over, per state kind (attribute names of a solved state == constructor keywords).
 _SCREEN_FIELDS = ("lmda", "lmda_max", "screen_set", "screen_beta", "screen_is_active", "active_set_size", "active_set")
@@ -506,4 +509,58 @@ def css_cov(
         subset_size = subset.size
     state = _state.css_cov(S=S, subset_size=subset_size, subset=subset, method=method, loss=loss, max_iters=max_iters,
                            n_threads=n_threads)
+    return state.solve()
+
+
+def bvls(
+    X, y: np.ndarray, lower: np.ndarray, upper: np.ndarray, *, weights: np.ndarray = None, kappa: int = None,
+    max_iters: int = int(1e5), tol: float = 1e-7, n_threads: int = 1, warm_start=None,
+):
+    """Bounded-variable least squares on an MI355X (reference ``adelie.solver.bvls``, ``adelie/solver.py:961-1116``; arguments,
+    defaults and the returned state are the reference's):
+
+        minimise ``1/2 ||y - X beta||_W^2`` subject to ``lower <= beta <= upper``.
+
+    ``weights`` defaults to ``1/n``, ``kappa`` (violators admitted to the screen set per KKT round) to ``min(n, p)``; bounds
+    are clipped to ``+-Configs.max_solver_value``; without a ``warm_start`` the start is the vertex of the box nearest the
+    origin, with one it reuses the state's ``beta`` / ``active_set`` / ``is_active``.
+
+    ``X`` goes through ``matrix.as_design``.  A plain dense design is solved by the reference's coordinate descent run by one
+    workgroup on the device: the gradients of all screen coordinates are kept current through the resident Gram matrix of
+    the screen set, so a visit costs one Gram column instead of two passes over the ``n`` rows.  Other designs (SNP, kept
+    sparse, standardized and multi-response views) take the same loop in Python over their ``cmul`` / ``ctmul`` / ``mul``:
+    slow, and meant for coverage rather than speed (``state.bvls``)."""
+    X = matrix.as_design(X, n_threads=n_threads)
+    dtype = np.dtype(X.dtype)
+    n, p = X.shape
+    if weights is None:
+        weights = np.full(n, 1 / n)
+    if kappa is None:
+        kappa = min(n, p)
+    weights = np.asarray(weights)
+    y = np.asarray(y)
+    y_var = np.sum(y ** 2 * weights)
+    X_vars = np.zeros(p, dtype)
+    X.sq_mul(weights, X_vars)
+    cap = Configs.max_solver_value
+    lower = np.maximum(lower, -cap)
+    upper = np.minimum(upper, cap)
+    if warm_start is None:
+        beta = np.where(np.abs(lower) < np.abs(upper), lower, upper)
+        active_set, active_set_size, is_active = np.empty(p, dtype=int), 0, np.zeros(p, dtype=bool)
+    else:
+        beta = warm_start.beta
+        active_set, active_set_size, is_active = warm_start.active_set, warm_start.active_set_size, warm_start.is_active
+    Xb = np.zeros(n, dtype)
+    nz = np.flatnonzero(beta)
+    if nz.size:
+        out = np.empty((1, n), dtype)
+        X.sp_tmul(csr_matrix((np.asarray(beta, dtype)[nz], (np.zeros(nz.size, dtype=int), nz)), shape=(1, p)), out)
+        Xb = out[0]
+    resid = y - Xb
+    loss = 0.5 * np.sum(resid ** 2 * weights)
+    state = _state.bvls(
+        X=X, y_var=y_var, X_vars=X_vars, lower=lower, upper=upper, weights=weights, kappa=kappa, max_iters=max_iters, tol=tol,
+        screen_set_size=active_set_size, screen_set=active_set, is_screen=is_active, active_set_size=active_set_size,
+        active_set=active_set, is_active=is_active, beta=beta, resid=resid, grad=np.empty(p, dtype=dtype), loss=loss)
     return state.solve()

@@ -1320,3 +1320,252 @@ class css_cov:
             v = self._vec("S_resid", self._dtype)
             self._S_resid = v.reshape((self._p, self._p), order="F") if v.size else np.empty((0, 0), dtype=self._dtype, order="F")
         return self._S_resid
+
+
+def _bvls_native(X):
+    """Whether ``X`` is a plain dense design, i.e. what ``adelie_hip_bvls_solve`` accepts."""
+    return (isinstance(X, _matrix._NativeMatrix) and getattr(X, "_kind", None) == "dense"
+            and not isinstance(X, (_matrix._MultiView, _matrix._StdView)))
+
+
+class bvls:
+    """Bounded-variable least squares state (reference ``adelie.state.bvls``, ``state.py:3124-3275``; ``StateBVLS``,
+    ``state_bvls.ipp``): ``min 1/2 ||y - X beta||_W^2`` subject to ``lower <= beta <= upper``.  Constructor arguments and
+    attributes are the reference's, plus ``iters``, ``n_kkt``, ``error`` and ``total_time``.  The constructor repeats the
+    reference's checks; ``solve()`` returns a new solved state and leaves this one untouched.
+
+    A plain dense design (an ndarray, ``matrix.dense``, the expanded one-hot / interaction designs, contiguous slices,
+    materialised copies) is solved on the device by ``adelie_hip_bvls_solve``.  Every other design (SNP, kept sparse,
+    standardized views, multi-response views) takes the same loop written in Python over the matrix's own ``cmul`` /
+    ``ctmul`` / ``mul``, which is what the reference does through its matrix interface: two device calls per visit.  That
+    route is slow and exists for coverage, not for speed."""
+
+    def __init__(self, X, y_var, X_vars, lower, upper, weights, kappa, max_iters, tol, screen_set_size, screen_set,
+                 is_screen, active_set_size, active_set, is_active, beta, resid, grad, loss):
+        X = _matrix.as_design(X)
+        dtype = np.dtype(X.dtype)
+        _abi.dtype_code(dtype)
+        n, p = X.rows(), X.cols()
+        self.X, self._dtype = X, dtype
+        self.y_var = float(y_var)
+        self.X_vars = np.ascontiguousarray(X_vars, dtype=dtype)
+        with np.errstate(over="ignore"):  # (bounds of +-max_solver_value are infinite in float32)
+            self.lower = np.ascontiguousarray(lower, dtype=dtype)
+            self.upper = np.ascontiguousarray(upper, dtype=dtype)
+        self.weights = np.ascontiguousarray(weights, dtype=dtype)
+        self.kappa, self.max_iters, self.tol = int(kappa), int(max_iters), float(tol)
+        self.screen_set_size = int(screen_set_size)
+        self.screen_set = np.array(screen_set, copy=True, dtype=np.int64)
+        self.is_screen = np.array(is_screen, copy=True, dtype=bool)
+        self.active_set_size = int(active_set_size)
+        self.active_set = np.array(active_set, copy=True, dtype=np.int64)
+        self.is_active = np.array(is_active, copy=True, dtype=bool)
+        self.beta = np.array(beta, copy=True, dtype=dtype)
+        self.resid = np.array(resid, copy=True, dtype=dtype)
+        self.grad = np.array(grad, copy=True, dtype=dtype)
+        self.loss = float(loss)
+        self.iters = self.n_kkt = 0
+        self.error, self.total_time = "", 0.0
+        # state_bvls.ipp:15-74
+        pre = "adelie_core solver: "
+        for name, arr, want, tail in (
+                ("X_vars", self.X_vars, p, "(p,) where X is (n, p). "), ("lower", self.lower, p, "(p,) where X is (n, p). "),
+                ("upper", self.upper, p, "(p,) where X is (n, p). "), ("weights", self.weights, n, "(n,) where X is (n, p). ")):
+            if arr.ndim != 1 or arr.size != want:
+                raise RuntimeError(f"{pre}{name} must be {tail}")
+        if self.kappa <= 0:
+            raise RuntimeError(pre + "kappa must be > 0. ")
+        if self.tol < 0:
+            raise RuntimeError(pre + "tol must be >= 0.")
+        if self.active_set_size > p:
+            raise RuntimeError(pre + "active_set_size must be <= p where X is (n, p). ")
+        for name, arr, want, tail in (
+                ("active_set", self.active_set, p, "(p,) where X is (n, p). "), ("is_active", self.is_active, p, "(p,) where X is (n, p). "),
+                ("beta", self.beta, p, "(p,) where X is (p, n). "), ("resid", self.resid, n, "(n,) where X is (n, p). "),
+                ("grad", self.grad, p, "(p,) where X is (n, p). ")):
+            if arr.ndim != 1 or arr.size != want:
+                raise RuntimeError(f"{pre}{name} must be {tail}")
+
+    def _spawn(self):
+        return bvls(X=self.X, y_var=self.y_var, X_vars=self.X_vars, lower=self.lower, upper=self.upper, weights=self.weights,
+                    kappa=self.kappa, max_iters=self.max_iters, tol=self.tol, screen_set_size=self.screen_set_size,
+                    screen_set=self.screen_set, is_screen=self.is_screen, active_set_size=self.active_set_size,
+                    active_set=self.active_set, is_active=self.is_active, beta=self.beta, resid=self.resid, grad=self.grad,
+                    loss=self.loss)
+
+    def _fill_sets(self, screen, active):
+        p = self.X.cols()
+        for name, members in (("screen", screen), ("active", active)):
+            buf = np.array(getattr(self, name + "_set"), copy=True, dtype=np.int64)
+            if buf.size < len(members):
+                buf = np.resize(buf, p)
+            buf[:len(members)] = members
+            flags = np.zeros(p, dtype=bool)
+            flags[np.asarray(members, dtype=np.int64)] = True
+            setattr(self, name + "_set", buf)
+            setattr(self, name + "_set_size", len(members))
+            setattr(self, "is_" + name, flags)
+
+    def solve(self):
+        """Solves on the device (or, for designs the native route does not take, through the matrix interface) and returns
+        the solved state.  Failures inside the solve are logged and stored in ``error``, as ``state.base.solve`` does."""
+        import time
+
+        out = self._spawn()
+        if _bvls_native(self.X):
+            out._solve_native()
+        else:
+            t0 = time.perf_counter()
+            try:
+                out._solve_generic()
+            except _BvlsError as e:
+                out.error = str(e)
+            out.total_time = time.perf_counter() - t0
+        if out.error != "":
+            if out.error.startswith("adelie_core solver: "):
+                logger.error(RuntimeError(out.error))
+            else:
+                logger.warning(RuntimeError(out.error))
+        return out
+
+    def _solve_native(self):
+        X, dtype = self.X, self._dtype
+        b = X._backend
+        p = X.cols()
+        screen = np.ascontiguousarray(self.screen_set[:self.screen_set_size], dtype=np.int64)
+        active = np.ascontiguousarray(self.active_set[:self.active_set_size], dtype=np.int64)
+        args = _abi.BvlsArgs(
+            X_vars=_abi.ptr(self.X_vars), lower=_abi.ptr(self.lower), upper=_abi.ptr(self.upper), weights=_abi.ptr(self.weights),
+            beta=_abi.ptr(self.beta), resid=_abi.ptr(self.resid), grad=_abi.ptr(self.grad),
+            n_X_vars=self.X_vars.size, n_lower=self.lower.size, n_upper=self.upper.size, n_weights=self.weights.size,
+            n_beta=self.beta.size, n_resid=self.resid.size, n_grad=self.grad.size,
+            screen_set=_abi.ptr(screen) if screen.size else None, screen_set_size=screen.size,
+            active_set=_abi.ptr(active) if active.size else None, active_set_size=active.size,
+            n_active_set=self.active_set.size, n_is_active=self.is_active.size,
+            y_var=self.y_var, loss=self.loss, kappa=self.kappa, max_iters=self.max_iters, tol=self.tol)
+        handle = _abi.C.c_void_p()
+        b.check(b.fn("bvls_solve")(X._handle, _abi.C.byref(args), handle))
+        try:
+            def vec(name, dt):
+                which = _abi.BVLS_V[name]
+                m = b.fn("bvls_result_size")(handle, which)
+                o = np.empty(max(m, 0), dtype=dt)
+                if m > 0:
+                    b.check(b.fn("bvls_result_copy")(handle, which, o.ctypes.data, m))
+                return o
+
+            scalar = b.fn("bvls_result_scalar")
+            self.beta, self.resid, self.grad = vec("beta", dtype), vec("resid", dtype), vec("grad", dtype)
+            self._fill_sets(vec("screen_set", np.int64), vec("active_set", np.int64))
+            assert np.array_equal(self.is_screen, vec("is_screen", np.uint8).astype(bool))
+            assert np.array_equal(self.is_active, vec("is_active", np.uint8).astype(bool))
+            self.loss = float(scalar(handle, _abi.BVLS_S["loss"]))
+            self.iters = int(scalar(handle, _abi.BVLS_S["iters"]))
+            self.n_kkt = int(scalar(handle, _abi.BVLS_S["n_kkt"]))
+            self.total_time = float(scalar(handle, _abi.BVLS_S["total_time"]))
+            # device-phase times of the solve (scripts/bench_bvls.py)
+            self.benchmark = {k: float(scalar(handle, _abi.BVLS_S[k])) for k in ("t_sweep_ms", "t_gram_ms", "t_fit_ms", "n_changed")}
+            msg = b.fn("bvls_result_error")(handle)
+            self.error = msg.decode() if msg else ""
+        finally:
+            b.fn("bvls_result_destroy")(handle)
+
+    def _solve_generic(self):
+        """solver_bvls.hpp:22-348 over ``X.cmul`` / ``X.ctmul`` / ``X.mul``, arithmetic in the design's dtype."""
+        X, dt = self.X, self._dtype.type
+        p = X.cols()
+        lower, upper, w, X_vars = self.lower, self.upper, self.weights, self.X_vars
+        beta, resid = self.beta, self.resid
+        screen = [int(k) for k in self.screen_set[:self.screen_set_size]]
+        active = [int(k) for k in self.active_set[:self.active_set_size]]
+        is_screen = np.array(self.is_screen, copy=True)
+        is_active = np.array(self.is_active, copy=True)
+        y_var, tol = dt(self.y_var), dt(self.tol)
+        loss = dt(self.loss)
+        half = dt(0.5)
+
+        def publish():
+            self.loss = float(loss)
+            self._fill_sets(screen, active)
+
+        def descend(members, add):
+            nonlocal loss
+            convg = dt(0)
+            for k in members:
+                vk, lk, uk = X_vars[k], lower[k], upper[k]
+                gk = dt(X.cmul(k, resid, w))
+                bk = beta[k]
+                step = dt(0) if vk <= 0 else gk / vk
+                bn = min(max(bk + step, lk), uk)
+                if bn == bk:
+                    continue
+                beta[k] = bn
+                d = bn - bk
+                sds = vk * d * d
+                convg = max(convg, sds)
+                loss = loss - (d * gk - half * sds)
+                X.ctmul(k, -d, resid)
+                if add and not is_active[k]:
+                    active.append(k)
+                    is_active[k] = True
+            return convg
+
+        def prune():
+            keep = [k for k in active if not (beta[k] <= lower[k] or beta[k] >= upper[k])]
+            for k in active:
+                is_active[k] = False
+            for k in keep:
+                is_active[k] = True
+            active[:] = keep
+
+        def step_iters():
+            self.iters += 1
+            return self.iters >= self.max_iters
+
+        def fit():
+            while True:
+                hit = step_iters()
+                convg = descend(list(screen), True)
+                if hit:
+                    publish()
+                    raise _BvlsError("adelie_core solver: bvls: max iterations reached!")
+                if convg <= tol * y_var:
+                    prune()
+                    return
+                while True:
+                    hit = step_iters()
+                    convg = descend(list(active), False)
+                    if hit:
+                        publish()
+                        raise _BvlsError("adelie_core solver: bvls: max iterations reached!")
+                    if convg <= tol * y_var:
+                        break
+                prune()
+
+        while True:
+            loss_prev = loss
+            fit()
+            if self.n_kkt > 0 and float(abs(loss - loss_prev)) < 1e-6 * float(abs(y_var)):
+                break
+            self.n_kkt += 1
+            grad = np.empty(p, dtype=self._dtype)
+            X.mul(resid, w, grad)
+            viols = np.maximum(grad, 0) * (beta < upper) - np.minimum(grad, 0) * (beta > lower)
+            self.grad = viols.astype(self._dtype)
+            order = np.argsort(-self.grad, kind="stable")  # ties to the lower index (the reference leaves them open)
+            n_old, passed = len(screen), True
+            for k in order:
+                if is_screen[k] or not self.grad[k] > 0:
+                    continue
+                passed = False
+                if len(screen) >= n_old + self.kappa:
+                    break
+                screen.append(int(k))
+                is_screen[k] = True
+            if passed:
+                break
+        publish()
+
+
+class _BvlsError(RuntimeError):
+    pass

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define ADELIE_HIP_ABI_VERSION 13
+#define ADELIE_HIP_ABI_VERSION 14
 
 enum adelie_hip_dtype { ADELIE_HIP_F32 = 0, ADELIE_HIP_F64 = 1 };
 enum adelie_hip_order { ADELIE_HIP_COL_MAJOR = 0, ADELIE_HIP_ROW_MAJOR = 1 };
@@ -54,6 +54,7 @@ typedef struct adelie_hip_design adelie_hip_design; /* device-resident MatrixNai
 typedef struct adelie_hip_result adelie_hip_result; /* solved state snapshot (the `state` copy _solve returns) */
 typedef struct adelie_hip_glm_cox adelie_hip_glm_cox; /* ABI 11: a Cox family's sort orders and weights, resident on one device */
 typedef struct adelie_hip_css_result adelie_hip_css_result; /* ABI 13: a solved column-subset-selection state */
+typedef struct adelie_hip_bvls_result adelie_hip_bvls_result; /* ABI 14: a solved bounded-variable least squares state */
 
 /* ------------------------------------------------------------------------------------------
  * Library
@@ -70,7 +71,10 @@ int         adelie_hip_device_count(void);
  * then accumulated in another (fixed) order than the ordinary sweep's, i.e. they differ from it in the last bits.
  * Device memory: the working buffers of a finished solve are parked in a process-wide cache and handed to the next solve
  * instead of going through hipFree / hipMalloc; "pool_limit_mb" (default 6144; 0 = no caching) bounds what stays parked,
- * "pool_trim" (any value) returns the parked blocks to the driver. */
+ * "pool_trim" (any value) returns the parked blocks to the driver.
+ * adelie_hip_bvls_solve (ABI 14): "bvls_gram_limit_mb" (default 16384) bounds the screen Gram matrix of a solve;
+ * "bvls_lds_max_ns" (default 0 = as many as the device's LDS holds) keeps the fit kernel's per-coordinate state in global
+ * memory for screen sets larger than the value (test hook: both forms give the same bits). */
 int         adelie_hip_set_config(const char* name, double value);
 
 /* ------------------------------------------------------------------------------------------
@@ -618,6 +622,67 @@ int64_t     adelie_hip_css_result_size(const adelie_hip_css_result* r, int which
 int         adelie_hip_css_result_copy(const adelie_hip_css_result* r, int which, void* out, int64_t cap);
 double      adelie_hip_css_result_scalar(const adelie_hip_css_result* r, int which);
 const char* adelie_hip_css_result_error(const adelie_hip_css_result* r);
+
+/* ------------------------------------------------------------------------------------------
+ * ABI 14.  Bounded-variable least squares   min 1/2 ||y - X beta||_W^2  s.t.  lower <= beta <= upper
+ *   == adelie.solver.bvls / StateBVLS{32,64}(...).solve()   (state_bvls.ipp:8-84, solver_bvls.hpp:22-348)
+ * `X` is a plain dense handle (kind dense, no standardized view, not a covariance handle).  The reference's coordinate descent
+ * with its visiting order, predicates and counters; a visit reads the coordinate's gradient from a vector that is kept current
+ * through the resident screen Gram matrix X_S^T W X_S instead of two passes over n rows, one workgroup runs a whole fit(), and
+ * the residual is caught up once per fit (kernels_bvls.hip).  All vectors are host pointers of the design's dtype; the args
+ * carry the constructor arguments of the reference's state with their lengths; its checks (state_bvls.ipp:15-74) fail the call.
+ * Errors raised inside the solve ("bvls: max iterations reached!", the Gram limit) are recorded in the result's error string
+ * and the result carries the state reached.  Ties between equal violations go to the lower index (the reference's std::sort
+ * leaves them unspecified).  Results are bit-reproducible run to run.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct adelie_hip_bvls_args {
+    const void*    X_vars;      /* (n_X_vars,) */
+    const void*    lower;       /* (n_lower,) */
+    const void*    upper;       /* (n_upper,) */
+    const void*    weights;     /* (n_weights,) */
+    const void*    beta;        /* (n_beta,) */
+    const void*    resid;       /* (n_resid,) */
+    const void*    grad;        /* (n_grad,) returned unchanged when no KKT round runs */
+    int64_t        n_X_vars, n_lower, n_upper, n_weights, n_beta, n_resid, n_grad;
+    const int64_t* screen_set;  /* the first screen_set_size entries are read */
+    int64_t        screen_set_size;
+    const int64_t* active_set;  /* (n_active_set,) buffer, the first active_set_size entries are read */
+    int64_t        active_set_size;
+    int64_t        n_active_set, n_is_active; /* buffer lengths of the caller's state (checked against p) */
+    double         y_var;
+    double         loss;
+    int64_t        kappa;
+    int64_t        max_iters;
+    double         tol;
+} adelie_hip_bvls_args;
+int adelie_hip_bvls_solve(adelie_hip_design* X, const adelie_hip_bvls_args* args, adelie_hip_bvls_result** out);
+int adelie_hip_bvls_result_destroy(adelie_hip_bvls_result* r);
+enum adelie_hip_bvls_vec {
+    ADELIE_HIP_BVLS_BETA = 0,        /* (p,) design's dtype */
+    ADELIE_HIP_BVLS_RESID = 1,       /* (n,) design's dtype */
+    ADELIE_HIP_BVLS_GRAD = 2,        /* (p,) design's dtype: the violations of the last KKT round */
+    ADELIE_HIP_BVLS_SCREEN_SET = 3,  /* (screen_set_size,) int64, in order */
+    ADELIE_HIP_BVLS_ACTIVE_SET = 4,  /* (active_set_size,) int64, in order */
+    ADELIE_HIP_BVLS_IS_SCREEN = 5,   /* (p,) uint8 */
+    ADELIE_HIP_BVLS_IS_ACTIVE = 6    /* (p,) uint8 */
+};
+enum adelie_hip_bvls_scalar {
+    ADELIE_HIP_BVLS_LOSS = 0,
+    ADELIE_HIP_BVLS_ITERS,
+    ADELIE_HIP_BVLS_N_KKT,
+    ADELIE_HIP_BVLS_SCREEN_SET_SIZE,
+    ADELIE_HIP_BVLS_ACTIVE_SET_SIZE,
+    ADELIE_HIP_BVLS_TOTAL_TIME,      /* seconds */
+    ADELIE_HIP_BVLS_T_SWEEP_MS,      /* HIP-event time of the full and screen sweeps (with their w * r products) */
+    ADELIE_HIP_BVLS_T_GRAM_MS,       /* ... of the Gram builds */
+    ADELIE_HIP_BVLS_T_FIT_MS,        /* ... of the fit kernel */
+    ADELIE_HIP_BVLS_N_CHANGED        /* visits that changed a coefficient, over all fits */
+};
+int64_t     adelie_hip_bvls_result_size(const adelie_hip_bvls_result* r, int which);
+/* Copies min(size, cap) elements in the element type named above. */
+int         adelie_hip_bvls_result_copy(const adelie_hip_bvls_result* r, int which, void* out, int64_t cap);
+double      adelie_hip_bvls_result_scalar(const adelie_hip_bvls_result* r, int which);
+const char* adelie_hip_bvls_result_error(const adelie_hip_bvls_result* r);
 
 /* ------------------------------------------------------------------------------------------
  * Kernel-level timing hook used by bench.py (HIP events on the design's own stream):
