@@ -43,48 +43,17 @@ __device__ __forceinline__ int blk_index(const CdBlkParams<T>& p, int pos) {
     return p.list ? p.list[pos] : pos;
 }
 
-// `tid` in [0, 256): the calling workgroup's first 256 threads; smem_raw holds blk_solve_lds<T>() bytes, 16-byte aligned.
-// Sum of the slice partials of the block's columns (CdBlkParams::part) by the first 1024 / `nthreads` threads of the fused
-// workgroup: 8 threads per column, each over every 8th slice, combined through LDS in a fixed order.  gsum[c] (LDS, BLK
-// values) is complete after the next workgroup barrier.
-template <class T>
-__device__ __forceinline__ void blk_part_sum(const CdBlkParams<T>& p, int nb, T* gsum8 /* [8][BLK] in LDS */, int wtid) {
-    const int c = wtid & (BLK - 1), k0 = wtid >> 7; // wtid in [0, 1024)
-    T acc = T(0);
-    if (p.part_ld == 0) {
-        // slice-major partials part[k * BLK + c]: the 128 threads of a row read 1 KB contiguously; every thread issues its
-        // loads in batches of eight before it sums them (fixed order k0, k0 + 8, ...)
-        const T* pc = p.part + c;
-        int k = k0;
-        for (; k + 56 < p.part_n; k += 64) {
-            T v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = pc[int64_t(k + 8 * u) * BLK];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc += v[u];
-        }
-        for (; k < p.part_n; k += 8) acc += pc[int64_t(k) * BLK];
-        if (c >= nb) acc = T(0);
-    } else if (c < nb) {
-        const T* pc = p.part + int64_t(c) * p.part_ld;
-        int k = k0;
-        for (; k + 24 < p.part_n; k += 32) {
-            const T v0 = pc[k], v1 = pc[k + 8], v2 = pc[k + 16], v3 = pc[k + 24];
-            acc += v0; acc += v1; acc += v2; acc += v3;
-        }
-        for (; k < p.part_n; k += 8) acc += pc[k];
-    }
-    gsum8[k0 * BLK + c] = acc;
-}
-
+// `tid` in [0, 256): the calling workgroup's 256 threads; smem_raw holds blk_solve_lds<T>() bytes, 16-byte aligned.
 // CONS: one-coefficient box constraints lo_i <= beta_i <= hi_i (CdBlkParams::clo / chi / cmu; ConstraintBox::solve_1d,
 // constraint_box.ipp:51-96, and ConstraintOneSided, constraint_one_sided.ipp:12-49, whose solution is the box form with one
 // side at infinity).  The minimiser of the one-dimensional problem over an interval is the unconstrained one clipped to it,
 // so a visit only gains a min/max; the multiplier  mu = mu_+ - mu_-  of every visited coordinate is computed after the loop,
 // lane-parallel, from the gradient its visit saw — the same quantities the reference's solve_1d leaves in the object.
-template <class T, bool NAIVE, bool CONS = false>
-__device__ __forceinline__ void blk_solve_body(const CdBlkParams<T>& p, int j, char* smem_raw, int tid,
-                                               const T* corr = nullptr, int ncorr = 0, const T* gsum8 = nullptr) {
+// Two forms: CONS = false is the full-Gram engine's solve (gradient p.g, block p.Dbuf, changes out by screen value);
+// CONS = true the panel engine's solve under constraints (residual-based: gradient p.gblk, block p.Dptr, changes out by design
+// column, pass report).  The panel engine's unconstrained solve is blk_solve_la_body below.
+template <class T, bool CONS>
+__device__ __forceinline__ void blk_solve_body(const CdBlkParams<T>& p, int j, char* smem_raw, int tid) {
     T* D = reinterpret_cast<T*>(smem_raw);   // BLK*BLK
     T* gB = D + BLK * BLK;
     T* bB = gB + BLK;
@@ -108,7 +77,7 @@ __device__ __forceinline__ void blk_solve_body(const CdBlkParams<T>& p, int j, c
             const T A = p.vars[idx], pk = p.spen[idx];
             const T den = A + p.l2 * (p.spen2 ? p.spen2[idx] : pk); // (penalty_l2, ABI 8)
             idxB[i] = idx;
-            gB[i] = NAIVE ? ((p.part && gsum8) ? T(0) : p.gblk[i]) : p.g[idx];
+            gB[i] = CONS ? p.gblk[i] : p.g[idx];
             bB[i] = p.beta[idx];
             AB[i] = A;
             l1B[i] = p.l1 * pk;
@@ -121,30 +90,10 @@ __device__ __forceinline__ void blk_solve_body(const CdBlkParams<T>& p, int j, c
         }
         dB[i] = 0;
     }
-    // look-ahead correction, see CdBlkParams.  `corr` != nullptr: helper threads of the fused kernel compute it meanwhile
-    // (blk_corr_helper below: ncorr partial sums per coordinate in LDS, complete at the barrier below)
-    if (NAIVE && p.Cprev != nullptr && corr == nullptr && tid < nb) {
-        const int nzp = p.pnz[0];
-        const T* Cp = p.Cprev + tid;
-        T acc = T(0);
-        int m = 0;
-        for (; m + 8 <= nzp; m += 8) {
-            T c[8], d[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                c[u] = Cp[size_t(p.ppos[m + u]) * BLK];
-                d[u] = p.pdlt[m + u];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc = fma(c[u], d[u], acc);
-        }
-        for (; m < nzp; ++m) acc = fma(Cp[size_t(p.ppos[m]) * BLK], p.pdlt[m], acc);
-        gB[tid] -= acc;
-    }
     {
         using V = typename CbVec<T>::type;
         constexpr int VEC = CbVec<T>::N;
-        const V* src = reinterpret_cast<const V*>(NAIVE ? p.Dptr : p.Dbuf + size_t(j & 1) * BLK * BLK);
+        const V* src = reinterpret_cast<const V*>(CONS ? p.Dptr : p.Dbuf + size_t(j & 1) * BLK * BLK);
         V* dst = reinterpret_cast<V*>(D);
         // 8 loads in flight per lane: the 128 KB block arrives in ~4 round trips instead of 32
         const int NE = nb * BLK / VEC; // columns [0, nb) of the slot
@@ -177,25 +126,6 @@ __device__ __forceinline__ void blk_solve_body(const CdBlkParams<T>& p, int j, c
     // is done lane-parallel afterwards (same quantities; the sums are wave reductions instead of running sums).
     static_assert(BLK == 128, "two coordinates per lane");
     T g0 = gB[lane], g1 = gB[lane + 64];
-    if (NAIVE && gsum8 != nullptr && p.part != nullptr) { // gradient from the slice partials (fixed order), intercept term
-        T s0 = T(0), s1 = T(0);
-        for (int q = 0; q < 8; ++q) {
-            s0 += gsum8[q * BLK + lane];
-            s1 += gsum8[q * BLK + lane + 64];
-        }
-        const T rs = p.part_rsum ? p.part_rsum[0] : T(0);
-        g0 = (lane < nb) ? s0 - rs * xmB[lane] : T(0);
-        g1 = (lane + 64 < nb) ? s1 - rs * xmB[lane + 64] : T(0);
-    }
-    if (NAIVE && corr != nullptr && p.Cprev != nullptr) {
-        T c0 = T(0), c1 = T(0);
-        for (int q = 0; q < ncorr; ++q) { // fixed order
-            c0 += corr[q * BLK + lane];
-            c1 += corr[q * BLK + lane + 64];
-        }
-        g0 -= c0;
-        g1 -= c1;
-    }
     const T b0 = bB[lane], b1 = bB[lane + 64];
     const T A0 = AB[lane], A1 = AB[lane + 64];
     const T L0 = l1B[lane], L1 = l1B[lane + 64];
@@ -303,7 +233,6 @@ __device__ __forceinline__ void blk_solve_body(const CdBlkParams<T>& p, int j, c
     // net changes of the block (a coordinate is visited once per pass, so delta = new - old)
     bB[lane] = nb0; bB[lane + 64] = nb1;
     dB[lane] = nb0 - b0; dB[lane + 64] = nb1 - b1;
-    if (NAIVE && p.dd != nullptr) { p.dd[lane] = nb0 - b0; p.dd[lane + 64] = nb1 - b1; }
     // ---- write back the block: beta, and the compacted non-zero changes for the update kernel ---------------------------
     int nz = 0;
     for (int i0 = 0; i0 < BLK; i0 += 64) {
@@ -314,9 +243,8 @@ __device__ __forceinline__ void blk_solve_body(const CdBlkParams<T>& p, int j, c
         const unsigned long long m = __ballot(ch);
         const int pos = nz + __popcll(m & ((1ull << lane) - 1ull));
         if (ch) {
-            if (NAIVE) {
+            if (CONS) {
                 p.dcol[pos] = p.vcol[idxB[i]];
-                if (p.dpos) p.dpos[pos] = i;
             } else {
                 p.didx[pos] = idxB[i];
             }
@@ -332,11 +260,7 @@ __device__ __forceinline__ void blk_solve_body(const CdBlkParams<T>& p, int j, c
         st->status = status;
         st->n_updates = n_upd;
         st->nz = nz;
-        if (NAIVE && p.nz_out) {
-            p.nz_out[0] = nz;
-            p.rsum_out[0] = rsum;
-        }
-        if (NAIVE && p.host_st && j == p.report_j) {
+        if (CONS && p.host_st && j == p.report_j) {
             CdBlkState<T> out;
             out.rsq = rsq; out.resid_sum = rsum; out.cm = cm; out.n_updates = n_upd;
             out.active_size = asz; out.status = status; out.nz = nz; out._pad = 0;
@@ -351,7 +275,7 @@ __device__ __forceinline__ void blk_solve_body(const CdBlkParams<T>& p, int j, c
 // Solve of block j inside the fused look-ahead launch, for ALL 1024 threads of workgroup 0 (lasso, no constraints).
 // Same visits and bookkeeping as blk_solve_body; what differs is the prologue.  While the other workgroups of the launch
 // stream 190 MB, a dependent global round trip of this workgroup takes 3-5 us (it queues behind the step's loads), and
-// blk_solve_body + blk_corr_helper make four to five of them in a row (indices -> constants, the diagonal block in four
+// blk_solve_body's prologue makes four to five of them in a row (indices -> constants, the diagonal block in four
 // batches, change positions -> cross-block columns in three): the solve, not the step, set the length of the launch.  Here
 // every load of the prologue is independent of the others and issued up front by all sixteen waves:
 //   * the diagonal block, 128 KB, one batch of 16-byte loads per thread;
@@ -700,43 +624,7 @@ __device__ __forceinline__ void blk_solve_la_body(const CdBlkParams<T>& p, int j
     }
 }
 
-// Helper threads of the fused kernel (htid in [0, BLK * NCORR)): partial sums of  Cprev[:, ppos[m]] * pdlt[m]  over the
-// m-range of part htid / BLK for coordinate htid % BLK, into corr[part * BLK + coordinate].  Ends with the workgroup barrier
-// that pairs with the one inside blk_solve_body.
-constexpr int NCORR = 6;
-template <class T>
-__device__ __forceinline__ void blk_corr_helper(const CdBlkParams<T>& p, T* corr, int htid) {
-    const int row = htid & (BLK - 1), part = htid / BLK;
-    T acc = T(0);
-    if (p.Cprev != nullptr) {
-        const int nzp = p.pnz[0];
-        const int per = (nzp + NCORR - 1) / NCORR;
-        const int m0 = part * per, m1 = min(nzp, m0 + per);
-        const T* Cp = p.Cprev + row;
-        int m = m0;
-        for (; m + 8 <= m1; m += 8) {
-            T c[8], d[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                c[u] = Cp[size_t(p.ppos[m + u]) * BLK];
-                d[u] = p.pdlt[m + u];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc = fma(c[u], d[u], acc);
-        }
-        for (; m < m1; ++m) acc = fma(Cp[size_t(p.ppos[m]) * BLK], p.pdlt[m], acc);
-    }
-    corr[part * BLK + row] = acc;
-    __syncthreads();
-}
-
-// LDS of the solve (+ the helper partials of the fused kernel)
-template <class T>
-__host__ __device__ constexpr size_t blk_solve_lds_fused() {
-    return size_t(BLK) * BLK * sizeof(T) + size_t(BLK) * 8 * sizeof(T) + size_t(BLK) * 2 * sizeof(int32_t) + 16 +
-           size_t(NCORR) * BLK * sizeof(T) + size_t(8) * BLK * sizeof(T);
-}
-
+// LDS of blk_solve_body
 template <class T>
 __host__ __device__ constexpr size_t blk_solve_lds() {
     return size_t(BLK) * BLK * sizeof(T) + size_t(BLK) * 8 * sizeof(T) + size_t(BLK) * 2 * sizeof(int32_t) + 16;

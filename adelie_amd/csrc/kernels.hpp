@@ -197,7 +197,6 @@ void set_strip_lds(bool on);                // f64: fragments through the wave-p
 template <class T>
 void launch_strip_batch(const DenseView<T>& X, const T* w, const int32_t* cols_base, const StripBatch& b, const T* xm_by_col,
                         bool center, T* D_base, T* X_base, int64_t ldc, T* work, hipStream_t s);
-void set_small_gram_workgroups(int wgs); // kernels_gram.hip: spread of the next small builds launched by this host thread
 template <class T>
 void launch_syrk_batch(const DenseView<T>& X, const T* w, const int32_t* cols_base, const SyrkBatch& b, const T* xm_by_col,
                        bool center, T* C_base, int64_t ldc, T* work, hipStream_t s);
@@ -341,7 +340,7 @@ struct CdBlkParams {
     // the next one reads the previous block's through pdd and forms the correction as Cprev * pdd without index loads
     const T* pdd;
     T* dd;
-    // one-coefficient constraints (blk_solve_body<.., CONS = true>): bounds per screen value (-inf / +inf where there is none)
+    // one-coefficient constraints (blk_solve_body<T, true>): bounds per screen value (-inf / +inf where there is none)
     // and, out, the multiplier mu_+ - mu_- of every constrained coordinate the block visited
     const T* clo;
     const T* chi;
@@ -421,19 +420,19 @@ struct CdGrpBlkParams {
     int32_t* dpos;
     int32_t* nz_out;
     T* rsum_out;
-    // rot != 0 (panel variant only): Dptr holds the block in the eigen-coordinates of its groups, R^T D R with
-    // R = blockdiag(V_g) (launch_grp_block_rotate, applied once per build): the sequential loop then works on rotated
+    // rot: 1 on every panel (residual-based) launch, 0 on the full-Gram engine's.  Panel launches: Dptr holds the block in the
+    // eigen-coordinates of its groups, R^T D R with R = blockdiag(V_g) (launch_grp_block_rotate, applied once per build): the sequential loop then works on rotated
     // gradients / coefficients throughout and the per-visit rotations of pin_naive:123-157 happen once per block and value,
     // lane-parallel, in the prologue and the epilogue of the solve
     int32_t rot;
-    // rot != 0: per-block layout descriptors of the pass (launch_grp_layout, GDESC_* below: the value / group tables that
+    // panel launches: per-block layout descriptors of the pass (launch_grp_layout, GDESC_* below: the value / group tables that
     // block_layout would otherwise derive through a chain of dependent global loads in every solve's prologue), and the
     // look-ahead correction in dense form: dd (out) / pdd (previous block's, in) = change of every value of the block by
     // block-local position (0 where unchanged or beyond the block), so that the correction is Cprev * pdd with no index loads
     const int32_t* desc;
     const T* pdd;
     T* dd;
-    // fused look-ahead launch, rot != 0: the block's gradient is still in the slice partials the previous launch's step left
+    // fused look-ahead launch: the block's gradient is still in the slice partials the previous launch's step left
     // (slice-major, part[k * 128 + c], k < part_n) and the solve sums them itself in the second round trip of its prologue,
     // in a fixed order, then applies the intercept term  - part_rsum[0] * xbar  (as CdBlkParams::part)
     const T* part;
@@ -451,7 +450,7 @@ struct CdGrpBlkParams {
     const T* clo;
     const T* chi;
     T* cmu;
-    // Fused look-ahead launch, rot != 0: the look-ahead correction of the NEXT block is formed by THIS solve's otherwise idle
+    // Fused look-ahead launch: the look-ahead correction of the NEXT block is formed by THIS solve's otherwise idle
     // waves — they fetch the cross block Cnext = C_{j+1,j} while the visiting wave runs, multiply it with this block's dense
     // changes when those exist and leave the 128 sums in corr_out; the next solve then reads corr_in (1 KB) instead of pulling
     // 128 KB of cross block through its own CU at the head of its prologue.  Same products, same order of summation.

@@ -42,17 +42,17 @@ __global__ void blk_gather_kernel(CdBlkParams<T> p, int j) {
     gather_block(p, j, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
-template <class T, bool NAIVE>
+template <class T>
 __global__ __launch_bounds__(256) void blk_solve_kernel(CdBlkParams<T> p, int j) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    blk_solve_body<T, NAIVE>(p, j, smem_raw, threadIdx.x);
+    blk_solve_body<T, false>(p, j, smem_raw, threadIdx.x);
 }
 
 // the panel solve with one-coefficient box constraints (CdBlkParams::clo / chi / cmu)
 template <class T>
 __global__ __launch_bounds__(256) void blk_solve_cons_kernel(CdBlkParams<T> p, int j) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    blk_solve_body<T, true, true>(p, j, smem_raw, threadIdx.x);
+    blk_solve_body<T, true>(p, j, smem_raw, threadIdx.x);
 }
 
 template <class T>
@@ -136,28 +136,20 @@ void launch_cd_block_pass(const CdBlkParams<T>& p, hipStream_t s) {
     static bool attr_done = false;
     const size_t lds = blk_solve_lds<T>();
     if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk_solve_kernel<double, false>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk_solve_kernel<double>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, int(blk_solve_lds<double>()));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk_solve_kernel<float, false>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk_solve_kernel<float>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, int(blk_solve_lds<float>()));
         attr_done = true;
     }
     for (int j = 0; j < nblk; ++j) {
-        hipLaunchKernelGGL((blk_solve_kernel<T, false>), dim3(1), dim3(256), lds, s, p, j);
+        hipLaunchKernelGGL((blk_solve_kernel<T>), dim3(1), dim3(256), lds, s, p, j);
         hipLaunchKernelGGL((blk_update_kernel<T>), dim3(ug), dim3(256), 0, s, p, j);
     }
 }
 
 template <class T>
 void launch_cd_panel_solve(const CdBlkParams<T>& p, int j, hipStream_t s) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk_solve_kernel<double, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(blk_solve_lds<double>()));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk_solve_kernel<float, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(blk_solve_lds<float>()));
-        attr_done = true;
-    }
     if (p.clo != nullptr) {
         static bool cons_attr_done = false;
         if (!cons_attr_done) {
@@ -170,19 +162,15 @@ void launch_cd_panel_solve(const CdBlkParams<T>& p, int j, hipStream_t s) {
         hipLaunchKernelGGL((blk_solve_cons_kernel<T>), dim3(1), dim3(256), blk_solve_lds<T>(), s, p, j);
         return;
     }
-    {
-        static bool la_attr_done = false;
-        if (!la_attr_done) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk_solve_la_kernel<double>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, int(blk_solve_lds_la<double>()));
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk_solve_la_kernel<float>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, int(blk_solve_lds_la<float>()));
-            la_attr_done = true;
-        }
-        hipLaunchKernelGGL((blk_solve_la_kernel<T>), dim3(1), dim3(1024), blk_solve_lds_la<T>(), s, p, j);
-        return;
+    static bool la_attr_done = false;
+    if (!la_attr_done) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk_solve_la_kernel<double>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(blk_solve_lds_la<double>()));
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blk_solve_la_kernel<float>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(blk_solve_lds_la<float>()));
+        la_attr_done = true;
     }
-    hipLaunchKernelGGL((blk_solve_kernel<T, true>), dim3(1), dim3(256), blk_solve_lds<T>(), s, p, j);
+    hipLaunchKernelGGL((blk_solve_la_kernel<T>), dim3(1), dim3(1024), blk_solve_lds_la<T>(), s, p, j);
 }
 
 template <class T>

@@ -11,9 +11,9 @@
 //                        r is read and written once per block; the block's columns are read once for (B) and, if they
 //                        changed, once more for (A) of the following step (from HBM again: DESIGN.md §4).
 //   panel_reduce_kernel  sums the slice partials in a fixed order and applies the intercept term  - resid_sum * xbar_c.
-//   blk_solve_kernel     (kernels_cd_block.hip, NAIVE variant, ONE workgroup) runs the block's visits in order against
-//                        the B x B block  D = X_B^T W X_B - xbar xbar^T  (computed once per block and weight vector by
-//                        the MFMA Gram kernel and cached), which carries the within-block coupling exactly.
+//   blk_solve_la_kernel  (kernels_cd_block.hip, ONE workgroup, or workgroup 0 of the fused launch below; blk_solve_cons_kernel
+//                        under constraints) runs the block's visits in order against the B x B block  D = X_B^T W X_B - xbar xbar^T
+//                        (built once per block and weight vector by the MFMA Gram kernel and cached): the within-block coupling, exactly.
 //
 // Compared with keeping the full |S| x |S| Gram matrix current, the MFMA work drops from n|S|^2/2 to 128 n |S| MACs and
 // nothing has to be recomputed per IRLS iteration except the blocks that are actually visited.  The iterates are the

@@ -26,11 +26,9 @@ namespace {
 constexpr int BM = 128, KT = 32, LDK = KT + 2, GT = 256;
 
 // Workgroups a SMALL build (one diagonal block / one cross block / a batch of diagonal blocks) is spread over.  512 = one
-// full round of two resident workgroups per CU, the fastest for the build itself.  The panel engine lowers it for builds
-// that run on the side stream next to the look-ahead launches of a Gaussian pass (set_small_gram_workgroups): those launches
-// need ~200 whole CUs, and a build that occupies every CU makes each of them wait.  Per host thread: set right before the
-// launches it is meant for.
-thread_local int t_small_gram_wgs = 512;
+// full round of two resident workgroups per CU, the fastest for the build itself.  (Confining side-stream builds to fewer
+// workgroups was measured slower: 56 -> 2.69, 112 -> 2.99 vs 3.17 paths/s unconfined; the chain waits for the slower builds.)
+constexpr int kSmallGramWgs = 512;
 
 // Block tile BM x BN = 128 x {64,128}; 4 waves: 2x2 of 64x64 (BN=128) or 4x1 of 32x64 (BN=64).
 // WNX = 4 (BN = 128): the four waves side by side, each 128 rows x 32 columns (8 x 2 MFMA tiles) — the "row strip" form of
@@ -628,7 +626,7 @@ void syrk_launch(Acc acc, bool vecok, const T* w, const int32_t* cols, int32_t M
 
 inline void syrk_batch_shape(int64_t n, int count, int& nsplit, int64_t& kchunk) {
     // about one full round of 2 resident workgroups per CU over all the blocks of the batch (count = 1: the single-block shape)
-    int64_t want = (int64_t(t_small_gram_wgs) + count - 1) / count;
+    int64_t want = (int64_t(kSmallGramWgs) + count - 1) / count;
     const int64_t max_split = (n + KT * 8 - 1) / (KT * 8);
     if (want > max_split) want = max_split;
     if (want < 1) want = 1;
@@ -677,7 +675,7 @@ inline GramShape gram_shape(int64_t n, int64_t M, int64_t N) {
     // Many tiles: ~3072 blocks so that the last partial round over the 256 CUs x 2 resident blocks costs little.  A single
     // diagonal block of the panel engine: one full round (512 blocks) - more K-splits only add partial-tile traffic
     // (128 KB written and re-read per split; measured -18 % at n = 500k).
-    const int64_t target = tiles <= 4 ? int64_t(t_small_gram_wgs) : 3072;
+    const int64_t target = tiles <= 4 ? int64_t(kSmallGramWgs) : 3072;
     int64_t want = (target + tiles - 1) / tiles;
     const int64_t max_split = (n + KT * 8 - 1) / (KT * 8);
     if (want > max_split) want = max_split;
@@ -722,15 +720,10 @@ void gram_launch(Acc acc, bool vecok, const T* w, const int32_t* mcols, int32_t 
 
 } // namespace
 
-void set_small_gram_workgroups(int wgs) { t_small_gram_wgs = wgs < 1 ? 512 : wgs; }
-
 int64_t gram_batch_work_elems(int64_t n, int count) {
-    const int keep = t_small_gram_wgs;
-    t_small_gram_wgs = 512; // the buffer is sized for the widest spread
     int ns;
     int64_t kc;
     syrk_batch_shape(n, count, ns, kc);
-    t_small_gram_wgs = keep;
     return int64_t(count) * ns * BM * 128;
 }
 
@@ -769,10 +762,7 @@ void launch_gram_batch_snp(const SnpView& X, const T* impute, const T* w, const 
 int64_t syrk_batch_work_elems(int64_t n, int count) {
     int nsplit;
     int64_t kchunk;
-    const int keep = t_small_gram_wgs;
-    t_small_gram_wgs = 512; // the buffer is sized for the widest spread
     syrk_batch_shape(n, count, nsplit, kchunk);
-    t_small_gram_wgs = keep;
     return int64_t(nsplit) * count * 128 * 128;
 }
 template <class T>
@@ -845,10 +835,7 @@ void launch_gram_multi(const MultiView<T>& X, const T* w, const int32_t* mcols, 
 
 int64_t gram_work_elems(int64_t n, int64_t M, int64_t N) {
     if (M <= 0 || N <= 0) return 0;
-    const int keep = t_small_gram_wgs;
-    t_small_gram_wgs = 512; // the buffer is sized for the widest spread
     const GramShape g = gram_shape(n, M, N);
-    t_small_gram_wgs = keep;
     return int64_t(g.nsplit) * g.Mt * BM * g.Npad;
 }
 

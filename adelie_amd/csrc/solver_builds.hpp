@@ -156,14 +156,13 @@
     // enqueued there up front and the MFMA work overlaps the HBM-bound steps / single-wave solves of the main chain, which
     // waits on a per-block event right before the block's solve.
     hipStream_t st2 = nullptr;
-    // further build streams (ADELIE_HIP_SIDE_STREAMS = 1..4 in total): under IRLS every block is rebuilt per iteration and the
+    // further build streams (n_side = 1..4 streams in total): under IRLS every block is rebuilt per iteration and the
     // chain waits for the builds; one build kernel (512 workgroups, 2 per CU) leaves the MFMA pipes half idle, two or three in
     // flight fill them
     static constexpr int kMaxExtra = 3;
     hipStream_t st_x[kMaxExtra] = {nullptr, nullptr, nullptr};
     DevBuf<T> d_work_x[kMaxExtra];
     int n_side = 1;
-    bool side_grams = true;
     DevBuf<T> d_work_gram2;
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
@@ -191,7 +190,7 @@
         }
         return pre_pool[pre_used++];
     }
-    // `rot_list` != nullptr or `rot_screen`: group passes with CdGrpBlkParams::rot — every block built here is rotated into the
+    // `rot_on` (group panel passes, whose solves work in eigen-coordinates): every block built here is rotated into the
     // eigen-coordinates of its groups right behind its build (same stream), over the pass's visiting list.
     const idx* rot_list = nullptr;
     bool rot_on = false;
@@ -222,7 +221,7 @@
             }
         }
         bool first = true;
-        const bool side = side_grams && st2 != nullptr;
+        const bool side = st2 != nullptr;
         if (side && pass_e0_valid) { // the pass recorded "inputs final" on the main stream before its first step went out
             AHIP_CHECK(hipStreamWaitEvent(st2, pass_e0, 0));
             for (int k = 0; k < kMaxExtra; ++k)
@@ -240,7 +239,7 @@
                 first = false;
             }
         };
-        // Stale blocks of the same tile class go out in batches of up to `batch_blocks` per launch (see syrk_batch_kernel);
+        // Stale blocks of the same tile class go out in batches of up to kBatchBlocks per launch (see syrk_batch_kernel);
         // the chain waits for a block through the event of its batch.  The first batch of a pass is kept small so that the
         // chain can start early.
         stale.clear();
@@ -249,11 +248,12 @@
             else if (tab_ver[j] != w_version) ++n_blocks_reused;
         }
         auto cls = [](int nb) { return nb <= 32 ? 32 : (nb <= 64 ? 64 : 128); };
+        constexpr int kBatchBlocks = 8; // diagonal blocks per build launch
         size_t i = 0;
         bool first_batch = true;
         while (i < stale.size()) {
             const int j0 = stale[i];
-            size_t cap = multi() ? 1 : size_t(first_batch ? std::min(batch_blocks, 4) : batch_blocks);
+            size_t cap = multi() ? 1 : size_t(first_batch ? std::min(kBatchBlocks, 4) : kBatchBlocks);
             first_batch = false;
             SyrkBatch sb{};
             const int32_t* cols_base = cols_of(j0);
@@ -270,9 +270,6 @@
             sb.count = int32_t(k - i);
             const int sidx = pick_side();
             open_side();
-            // Gaussian look-ahead passes: a build whose block the chain reaches late in the pass is confined to few CUs, so
-            // that the fused launches (whole-CU workgroups) running meanwhile never wait for one (see set_small_gram_workgroups)
-            set_small_gram_workgroups((side && side_wgs > 0 && !is_glm() && j0 >= side_wgs_from) ? side_wgs : 512);
             if (multi()) gram_block(cur_w, cols_of(j0), nb_of(j0), cur_xm, pool + size_t(j0) * SL * SL, sidx);
             else gram_block_batch(cur_w, cols_base, sb, cur_xm, pool + size_t(j0) * SL * SL, sidx);
             if (vb_vars && !multi()) // IRLS, groups of one: the variances of a block's coordinates are its diagonal (vars_from_blocks)
@@ -285,7 +282,6 @@
                 e = prebuild ? next_pre_event() : next_event();
                 AHIP_CHECK(hipEventRecord(e, sidx >= 2 ? st_x[sidx - 2] : st2));
             }
-            set_small_gram_workgroups(512);
             for (size_t t = i; t < k; ++t) {
                 const int j = stale[t];
                 (prebuild ? pre_ev : blk_ev)[size_t(j)] = e;
@@ -304,7 +300,7 @@
     bool pass_e0_valid = false;
     void record_pass_e0() {
         pass_e0_valid = false;
-        if (!(side_grams && st2 != nullptr)) return;
+        if (!st2) return;
         if (!pass_e0) AHIP_CHECK(hipEventCreateWithFlags(&pass_e0, hipEventDisableTiming));
         AHIP_CHECK(hipEventRecord(pass_e0, st));
         pass_e0_valid = true;
@@ -341,15 +337,13 @@
         while (v > 1 && acc + ver_drift[size_t(v)] <= budget) { acc += ver_drift[size_t(v)]; --v; }
         min_usable_version = v;
     }
-    bool prebuild_enabled = true; // A/B hook ADELIE_HIP_PREBUILD=0
     // look-ahead passes: the solve of a fused launch sums the previous launch's slice partials itself (second round trip of
     // blk_solve_la_body's prologue) instead of a panel_reduce launch between every two fused launches.  Round 2 measured this
     // slower (3.08 vs 3.20 paths/s) with the solve's old prologue; with the one-round-trip prologue the fused launch grows by
-    // 1 us and the reduce launch + its boundary go away: 290.3 -> 285.9 ms (f32: 178.1 -> 174.6).  Hook ADELIE_HIP_FUSE_REDUCE=0.
+    // 1 us and the reduce launch + its boundary go away: 290.3 -> 285.9 ms (f32: 178.1 -> 174.6).
     // Only while a column has at most 200 partials (n <= 102 400 rows in f64): beyond, one workgroup summing them is slower
     // than the reduce launch.
-    bool fuse_reduce_opt = true;
-    bool fuse_reduce = false;     // (set per solve from fuse_reduce_opt and the partial count)
+    bool fuse_reduce = false;     // (set per solve from the partial count)
     int fused_partials() const {  // partials per column a fused launch leaves (kernels_cd_panel.hip::fused_launch)
         int vec = 4;
         if (dense()) {
@@ -362,13 +356,8 @@
     }
     DevBuf<T> d_part2;
     size_t part2_half = 0;
-    int side_wgs = 0;             // >0: confine side-stream builds of Gaussian look-ahead passes to this many workgroups (hook ADELIE_HIP_SIDE_WGS; measured: 56 -> 2.69, 112 -> 2.99 vs 3.17 paths/s unconfined: the chain waits for the slower builds)
-    int side_wgs_from = 4;        // ... for blocks the chain reaches at this position of the pass or later (ADELIE_HIP_SIDE_WGS_FROM)
     std::vector<int> stale;
-    int batch_blocks = 8; // diagonal blocks per build launch (tuning hook ADELIE_HIP_BATCH_BLOCKS, 1..16)
-    int cross_batch = 8;  // cross blocks per build launch (hook ADELIE_HIP_CROSS_BATCH, 1 = one gram launch per block)
     std::vector<int> stale_x;
-    bool cross_incremental = true; // A/B hook ADELIE_HIP_CROSS_INCR=0: a cross block that gained rows is rebuilt whole
     int x_rows_new[GramBatch::MAX] = {};
     // host-mapped end-of-pass report (state + sequence number), see CdBlkParams::host_st
     struct PassReport { CdBlkState<T> st; int32_t seq; int32_t pad[15]; };
@@ -407,14 +396,12 @@
     // instead of their sum.  (Solves on a second stream with event dependencies were measured first: ~35 us per
     // cross-queue hop, slower than no look-ahead at all.)
     bool lookahead = true;      // A/B hook ADELIE_HIP_LOOKAHEAD
-    int la_min_blocks = 3;      // passes with fewer blocks run in the plain form (hook ADELIE_HIP_LOOKAHEAD_MIN_BLOCKS)
+    static constexpr int kLaMinBlocks = 3; // passes with fewer blocks run in the plain form
     DevBuf<T> d_Xpool, d_la_dlt, d_la_g, d_la_rsum, d_la_dd;
     DevBuf<int32_t> d_gdesc; // layout descriptors of the current group pass (launch_grp_layout)
     DevBuf<int32_t> d_la_dcol, d_la_dpos, d_la_nz;
     DevBuf<int32_t> d_tail_counter; // CdGrpBlkParams::tail_counter
     DevBuf<int32_t> d_zero_i32; // one int32 that stays 0 ("no changes to apply" for the step of a pass's first fused launch)
-    bool la_fused_open = true;  // look-ahead passes open with (step: pending changes + block 0) -> fused (solve 0 || block 1) instead of
-                                // (step: blocks 0 and 1) -> reduce -> solve 0; hook ADELIE_HIP_LA_FUSED_OPEN=0
     struct XKey { int32_t nb_prev = 0, nb = 0; uint64_t ver = 0; };
     std::vector<XKey> xscr_key, xact_key;
     std::vector<hipEvent_t> x_ev;
@@ -425,8 +412,9 @@
     void build_stale_cross(int nblk, std::vector<XKey>& tab, T* xpool, NbOf nb_of, ColsOf cols_of) {
         const int SL = cd_block_size();
         x_ev.assign(size_t(nblk), nullptr);
-        bool first = !(pass_e0_valid && side_grams && st2 != nullptr); // (the diagonal-block builder made st2 wait for pass_e0)
-        if (!multi() && cross_batch > 1) {
+        bool first = !(pass_e0_valid && st2 != nullptr); // (the diagonal-block builder made st2 wait for pass_e0)
+        if (!multi()) {
+            constexpr int kCrossBatch = 8; // cross blocks per build launch
             // several stale cross blocks per launch (gram_batch_kernel): their K-splits share one round over the chip, so the
             // split-K partials written and re-read per block shrink with the batch (134 MB for a block built alone)
             std::vector<int>& sx = stale_x;
@@ -435,11 +423,11 @@
                 const XKey& k = tab[size_t(j)];
                 if (!(k.nb_prev == nb_of(j - 1) && k.nb == nb_of(j) && k.ver == w_version)) sx.push_back(j);
             }
-            const bool side = side_grams && st2 != nullptr;
+            const bool side = st2 != nullptr;
             hipStream_t gs = side ? st2 : st;
             const int32_t* cols_base = cols_of(0);
             for (size_t i = 0; i < sx.size();) {
-                const size_t k = std::min(sx.size(), i + size_t(i == 0 ? std::min(cross_batch, 4) : cross_batch));
+                const size_t k = std::min(sx.size(), i + size_t(i == 0 ? std::min(kCrossBatch, 4) : kCrossBatch));
                 if (side && first) {
                     hipEvent_t e0 = next_event();
                     AHIP_CHECK(hipEventRecord(e0, st));
@@ -454,7 +442,7 @@
                     // version against the same (full) previous block stay valid when the block gains members: only the rows
                     // of the newcomers are computed (the batch kernel skips the 16-row tiles beyond them)
                     const XKey& key = tab[size_t(j)];
-                    const int have = (cross_incremental && key.ver == w_version && key.nb_prev == nb_of(j - 1) &&
+                    const int have = (key.ver == w_version && key.nb_prev == nb_of(j - 1) &&
                                       key.nb > 0 && key.nb < nb_of(j)) ? key.nb : 0;
                     gb.moff[t - i] = int32_t(cols_of(j) - cols_base) + have;
                     gb.m[t - i] = nb_of(j) - have;
@@ -488,11 +476,14 @@
             }
             return;
         }
+        // multi-response view: Gram of the two blocks' distinct features, expanded to view columns (zero between different
+        // responses); look-ahead only runs under uniform weights (Gaussian), so one Gram serves all responses
+        const MultiView<T> mv = D->multi<T>();
         for (int j = 1; j < nblk; ++j) {
             const int nbp = nb_of(j - 1), nb = nb_of(j);
             XKey& k = tab[size_t(j)];
             if (k.nb_prev == nbp && k.nb == nb && k.ver == w_version) continue;
-            const bool side = side_grams && st2 != nullptr;
+            const bool side = st2 != nullptr;
             hipStream_t gs = side ? st2 : st;
             if (side && first) {
                 hipEvent_t e0 = next_event();
@@ -500,42 +491,29 @@
                 AHIP_CHECK(hipStreamWaitEvent(st2, e0, 0));
                 first = false;
             }
-            T* work = (side ? d_work_gram2 : d_work_gram)
-                          .reserve(size_t(std::max<int64_t>(gram_work_elems(n, SL, SL), syrk_work_elems(n, 128))));
             T* Cx = xpool + size_t(j) * SL * SL;
-            set_small_gram_workgroups((side && side_wgs > 0 && !is_glm() && j >= side_wgs_from) ? side_wgs : 512);
             t_gram.begin(gs);
-            if (multi()) {
-                // Gram of the two blocks' distinct features, expanded to view columns (zero between different responses);
-                // look-ahead only runs under uniform weights (Gaussian), so one Gram serves all responses
-                const MultiView<T> mv = D->multi<T>();
-                auto distinct = [&](const int32_t* hc, int cntv) {
-                    multi_seen.clear();
-                    for (int a = 0; a < cntv; ++a) {
-                        const int32_t u = hc[a] / mv.K;
-                        if (std::find(multi_seen.begin(), multi_seen.end(), u) == multi_seen.end()) multi_seen.push_back(u);
-                    }
-                    return int(multi_seen.size());
-                };
-                const int nu = distinct(host_cols(cols_of(j)), nb), nup = distinct(host_cols(cols_of(j - 1)), nbp);
-                DevBuf<int32_t>& ml = side ? d_mlist2 : d_mlist;
-                DevBuf<T>& mc = side ? d_mC2 : d_mC;
-                ml.reserve(size_t(6 * SL));
-                mc.reserve(size_t(SL) * SL);
-                launch_multi_block_lists(cols_of(j), nb, mv.K, ml.p, ml.p + SL, ml.p + 2 * SL, gs);
-                launch_multi_block_lists(cols_of(j - 1), nbp, mv.K, ml.p + 3 * SL, ml.p + 4 * SL, ml.p + 5 * SL, gs);
-                T* mwork = (side ? d_work_gram2 : d_work_gram)
-                               .reserve(size_t(std::max<int64_t>(gram_work_elems(mv.nb, SL, SL), syrk_work_elems(mv.nb, 128))));
-                launch_gram_multi<T>(mv, cur_w, ml.p, nu, ml.p + 3 * SL, nup, mc.p, SL, mwork, gs);
-                launch_multi_expand_cross<T>(mc.p, SL, ml.p + SL, ml.p + 2 * SL, nb, ml.p + 4 * SL, ml.p + 5 * SL, nbp, Cx, SL, gs);
-                cnt.gram_flops += 2.0 * double(mv.nb) * double(nu) * double(nup);
-            } else if (dense())
-                launch_gram<T>(D->dense<T>(), cur_w, cols_of(j), nb, 0, cols_of(j - 1), nbp, 0, cur_xm, intercept, Cx, SL, work, gs);
-            else
-                launch_gram_snp<T>(D->snp(), static_cast<const T*>(D->impute), cur_w, cols_of(j), nb, 0, cols_of(j - 1), nbp, 0,
-                                   cur_xm, intercept, Cx, SL, work, gs);
+            auto distinct = [&](const int32_t* hc, int cntv) {
+                multi_seen.clear();
+                for (int a = 0; a < cntv; ++a) {
+                    const int32_t u = hc[a] / mv.K;
+                    if (std::find(multi_seen.begin(), multi_seen.end(), u) == multi_seen.end()) multi_seen.push_back(u);
+                }
+                return int(multi_seen.size());
+            };
+            const int nu = distinct(host_cols(cols_of(j)), nb), nup = distinct(host_cols(cols_of(j - 1)), nbp);
+            DevBuf<int32_t>& ml = side ? d_mlist2 : d_mlist;
+            DevBuf<T>& mc = side ? d_mC2 : d_mC;
+            ml.reserve(size_t(6 * SL));
+            mc.reserve(size_t(SL) * SL);
+            launch_multi_block_lists(cols_of(j), nb, mv.K, ml.p, ml.p + SL, ml.p + 2 * SL, gs);
+            launch_multi_block_lists(cols_of(j - 1), nbp, mv.K, ml.p + 3 * SL, ml.p + 4 * SL, ml.p + 5 * SL, gs);
+            T* mwork = (side ? d_work_gram2 : d_work_gram)
+                           .reserve(size_t(std::max<int64_t>(gram_work_elems(mv.nb, SL, SL), syrk_work_elems(mv.nb, 128))));
+            launch_gram_multi<T>(mv, cur_w, ml.p, nu, ml.p + 3 * SL, nup, mc.p, SL, mwork, gs);
+            launch_multi_expand_cross<T>(mc.p, SL, ml.p + SL, ml.p + 2 * SL, nb, ml.p + 4 * SL, ml.p + 5 * SL, nbp, Cx, SL, gs);
             t_gram.end(gs);
-            set_small_gram_workgroups(512);
+            cnt.gram_flops += 2.0 * double(mv.nb) * double(nu) * double(nup);
             cnt.gram_flops += 2.0 * double(n) * double(nb) * double(nbp);
             cnt.n_gram_col_reads += nb + nbp;
             if (side) {
@@ -554,9 +532,6 @@
     // tiles) plus a staged cross build whose cost does not shrink with the row count: 71 us against 282 us for 16 new
     // members of a full block pair at n = 100k (scripts/ubench/strip.hip).  Runs before build_stale_blocks /
     // build_stale_cross, which then find these blocks fresh; blocks with more new members stay with them.
-    // Hook ADELIE_HIP_STRIP_BUILDS=0.
-    bool strip_builds = true;
-    int strip_max_m = 128;
     std::vector<hipEvent_t> strip_pool, strip_ev;
     std::vector<int> strip_built; // blocks the last build_stale_strips call built
     size_t strip_used = 0;
@@ -569,8 +544,8 @@
         }
         return strip_pool[strip_used++];
     }
-    bool strips_apply() const { return strip_builds && dense() && !is_glm() && D->std_center == nullptr; }
-    // `rot_dst` != nullptr (group passes with CdGrpBlkParams::rot): `pool` holds the blocks in the design's own coordinates
+    bool strips_apply() const { return dense() && !is_glm() && D->std_center == nullptr; }
+    // `rot_dst` != nullptr (group panel passes): `pool` holds the blocks in the design's own coordinates
     // (d_Draw: what the strips extend), and every block a strip touched is rotated into the eigen-coordinates of its groups
     // right behind it on the same stream, out of place into rot_dst (the pool the solves read), over the visiting list `rlist`.
     DevBuf<T> d_Draw;
@@ -583,7 +558,7 @@
         strip_built.clear();
         if (!strips_apply()) return;
         const int SL = cd_block_size();
-        const bool side = !force_main && side_grams && st2 != nullptr;
+        const bool side = !force_main && st2 != nullptr;
         hipStream_t gs = side ? st2 : st;
         bool first = true;
         const int32_t* cols_base = cols_of(0);
@@ -652,7 +627,8 @@
             // one of the two only: a strip over that block's columns alone; both: from the smaller of the two row counts
             const int have = (need_d && need_x) ? std::min(have_d, have_x) : (need_d ? have_d : have_x);
             const int m = nb - have;
-            if (m <= 0 || m > strip_max_m) continue; // (left to the staged builders)
+            constexpr int kStripMaxM = 128;
+            if (m <= 0 || m > kStripMaxM) continue; // (left to the staged builders)
             const int64_t off1 = cols_of(j) - cols_base, off0 = want_x ? cols_of(j - 1) - cols_base : 0;
             if (off1 < 0 || off1 > (int64_t(1) << 30)) continue;
             // more than 64 new members: two strips of the same launch.  A strip only needs the columns of its block up to
@@ -690,16 +666,15 @@
     }
     std::vector<int32_t> dscr_nb, dact_nb;      // cached block: number of members it was built for
     std::vector<uint64_t> dscr_ver, dact_ver;   // ... and the weight version
-    bool group_panel = true;    // groups (q > 1) on the panel engine too (A/B hook ADELIE_HIP_GROUP_PANEL=0: full-Gram block engine)
     bool panel_mode() const {
-        return engine_panel && nv >= cd_block_min_nv && (all_scalar || (group_panel && max_gs <= idx(cd_block_size())));
+        return engine_panel && nv >= cd_block_min_nv && (all_scalar || max_gs <= idx(cd_block_size()));
     }
     DevBuf<T> d_work_sweep, d_work_gram;
     bool grad_valid = false; // d_grad == X^T W r - rsum*xbar for the current r
     // In stream order, d_grad holds the full Gaussian gradient of the CURRENT d_r (an invariance sweep was enqueued and nothing
     // touched the residual since): the first look-ahead pass of the next fit takes block 0's gradient from it instead of
-    // streaming the block's columns (open_from_grad, consumed by run_panel_passes).  Hook ADELIE_HIP_OPEN_FROM_GRAD=0.
-    bool grad_fresh = false, open_from_grad = false, open_from_grad_opt = true, spec_used_grad = false;
+    // streaming the block's columns (open_from_grad, consumed by run_panel_passes).
+    bool grad_fresh = false, open_from_grad = false, spec_used_grad = false;
     // glm device vectors
     DevBuf<T> d_y, d_gw, d_off, d_eta, d_hess, d_irls_y, d_irls_resid, d_eta_prev, d_resid_prev, d_sums, d_ones;
     // host mirrors of per-screen arrays used to append

@@ -63,7 +63,7 @@
         Stopwatch sw;
         sw.start();
         bool small_fit = false; // the whole pin solve ran in the single-workgroup kernel (its scalars are in d_sc)
-        open_from_grad = grad_fresh && open_from_grad_opt && !is_glm() && !cov_mode && r_dev == d_r.p && !resume && !std_generic();
+        open_from_grad = grad_fresh && !is_glm() && !cov_mode && r_dev == d_r.p && !resume && !std_generic();
         grad_fresh = false; // (whatever engine runs, the residual moves)
         if (!(nv > 0 && panel_mode() && !all_scalar)) join_uv(); // (only the group panel passes know which of them need it)
         if (nv > 0 && panel_mode()) {
@@ -74,7 +74,7 @@
             else run_group_panel_passes(cp, sc, r_dev);
             // Gaussian: the residual is final and current on the device -> enqueue the invariance sweep of this lambda now,
             // so that it runs while the host does the post-fit bookkeeping below (otherwise the GPU idles ~0.2 ms per lambda)
-            if (!is_glm() && sc.status == CD_OK && r_dev == d_r.p && prelaunch_sweep && inv_wanted) {
+            if (!is_glm() && sc.status == CD_OK && r_dev == d_r.p && inv_wanted) {
                 launch_vmul<T>(d_w.p, d_r.p, d_v.p, n, st);
                 t_sweep.begin(st);
                 sweep(d_v.p, d_grad.p, nullptr, p, &d_blk.p->resid_sum, intercept ? d_xm.p : nullptr);
@@ -142,7 +142,7 @@
         }
         // small screen sets (single-workgroup kernel): the invariance sweep of this lambda goes out right behind the residual
         // update as well, ahead of the downloads and the host bookkeeping below (the panel engines did this above)
-        if (small_fit && !is_glm() && !cov_mode && prelaunch_sweep && inv_wanted && sc.status == CD_OK && r_dev == d_r.p &&
+        if (small_fit && !is_glm() && !cov_mode && inv_wanted && sc.status == CD_OK && r_dev == d_r.p &&
             !multi()) {
             launch_vmul<T>(d_w.p, d_r.p, d_v.p, n, st);
             t_sweep.begin(st);
@@ -188,7 +188,7 @@
             sc2.resid_sum = sc.resid_sum;
             sc2.active_size = sc.active_size;
             spec_mode = 1;
-            open_from_grad = grad_fresh && open_from_grad_opt; // (the sweep of this lambda went out just above, on the residual the pass starts from)
+            open_from_grad = grad_fresh; // (the sweep of this lambda went out just above, on the residual the pass starts from)
             spec_used_grad = grad_fresh;
             grad_fresh = false;
             {

@@ -19,13 +19,7 @@
         d_Dbuf.reserve(size_t(2) * B * B);
         d_dlt.reserve(B);
         d_didx.reserve(B);
-        CdBlkState<T> bs{};
-        bs.rsq = sc.rsq;
-        bs.resid_sum = sc.resid_sum;
-        bs.cm = 0;
-        bs.n_updates = 0;
-        bs.active_size = sc.active_size;
-        bs.status = CD_OK;
+        CdBlkState<T> bs = initial_pass_state(sc);
         d_blk.upload(&bs, 1, st);
         CdBlkParams<T> bp{};
         bp.nv = cp.nv; bp.C = cp.C; bp.ldc = cp.ldc; bp.vars = cp.vars; bp.xmean = cp.xmean; bp.spen = cp.spen; bp.spen2 = cp.spen2;
@@ -34,7 +28,6 @@
         bp.max_active_size = cp.max_active_size;
         bp.Dbuf = d_Dbuf.p; bp.dlt = d_dlt.p; bp.didx = d_didx.p; bp.st = d_blk.p;
         bp.bsz = B;
-        int64_t iters = 0;
         int status = CD_OK;
         int asz = sc.active_size;
         auto pass = [&](const int32_t* list, int count, bool mark) -> T {
@@ -58,31 +51,10 @@
             asz = bs.active_size;
             return bs.cm;
         };
-        while (status == CD_OK) {
-            while (status == CD_OK) { // solve_active, pin_naive:173-215
-                ++iters;
-                ++sc.n_passes_active;
-                sc.n_visits_active += asz;
-                const T cm = pass(cp.active_set, asz, false);
-                if (status != CD_OK) break;
-                if (cm < cp.tol) break;
-                if (iters >= cp.max_iters) { status = CD_MAX_CDS; break; }
-            }
-            if (status != CD_OK) break;
-            ++iters;
-            ++sc.n_passes_screen;
-            sc.n_visits_screen += cp.nv;
-            const T cm = pass(nullptr, cp.nv, true);
-            if (status != CD_OK) break;
-            if (cm < cp.tol) break;
-            if (iters >= cp.max_iters) { status = CD_MAX_CDS; break; }
-        }
-        sc.rsq = bs.rsq;
-        sc.resid_sum = bs.resid_sum;
-        sc.iters = iters;
-        sc.n_updates = bs.n_updates;
-        sc.active_size = asz;
-        sc.status = status;
+        const int64_t iters = run_pass_loop(cp, sc, cp.nv, status, asz, [&](bool screen_pass) {
+            return screen_pass ? pass(nullptr, cp.nv, true) : pass(cp.active_set, asz, false);
+        });
+        store_pass_scalars(sc, bs, iters, status, asz);
         // (column, delta) list of the residual update + the device copy of resid_sum for the sweep epilogue
         launch_cd_compact<T>(cp.beta, r_stale ? d_beta_ref.p : cp.beta0, cp.vcol, cp.nv, cp.dcols, cp.dvals, &cp.sc->n_delta, st);
         AHIP_CHECK(hipMemcpyAsync(&sc.n_delta, &cp.sc->n_delta, sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -113,8 +85,8 @@
             }
             panel_maxblk = maxblk;
         }
-        if (side_grams && !st2) st2 = StreamPool::take();
-        for (int k = 0; side_grams && k < std::min(n_side - 1, kMaxExtra); ++k)
+        if (!st2) st2 = StreamPool::take();
+        for (int k = 0; k < std::min(n_side - 1, kMaxExtra); ++k)
             if (!st_x[k]) st_x[k] = StreamPool::take();
         if (use_report && !h_report) {
             void* hp = HostPool::take(sizeof(PassReport), hipHostMallocMapped);
@@ -150,6 +122,119 @@
         sync();
     }
 
+    // ---- what the pass drivers of this file share ----
+    // state a fit's passes start from / the scalars they hand back
+    static CdBlkState<T> initial_pass_state(const CdScalars<T>& sc) {
+        CdBlkState<T> bs{};
+        bs.rsq = sc.rsq;
+        bs.resid_sum = sc.resid_sum;
+        bs.active_size = sc.active_size;
+        bs.status = CD_OK;
+        return bs;
+    }
+    static void store_pass_scalars(CdScalars<T>& sc, const CdBlkState<T>& bs, int64_t iters, int status, int asz) {
+        sc.rsq = bs.rsq;
+        sc.resid_sum = bs.resid_sum;
+        sc.iters = iters;
+        sc.n_updates = bs.n_updates;
+        sc.active_size = asz;
+        sc.status = status;
+    }
+    // The pass structure of a pin solve (pin_naive:317-357): solve_active until convergence, one screen pass, repeat.
+    // `pass(screen_pass)` runs one pass, leaves its outcome in `status` / `asz` and returns its convergence measure;
+    // `screen_visits`: what a screen pass adds to the visit count.  Returns the number of passes.
+    template <class Pass>
+    int64_t run_pass_loop(const CdParams<T>& cp, CdScalars<T>& sc, int64_t screen_visits, int& status, const int& asz, Pass pass) {
+        int64_t iters = 0;
+        while (status == CD_OK) {
+            while (status == CD_OK) { // solve_active, pin_naive:173-215
+                ++iters;
+                ++sc.n_passes_active;
+                sc.n_visits_active += asz;
+                const T cm = pass(false);
+                if (status != CD_OK) break;
+                if (cm < cp.tol) break;
+                if (iters >= cp.max_iters) { status = CD_MAX_CDS; break; }
+            }
+            if (status != CD_OK) break;
+            ++iters;
+            ++sc.n_passes_screen;
+            sc.n_visits_screen += screen_visits;
+            const T cm = pass(true);
+            if (status != CD_OK) break;
+            if (cm < cp.tol) break;
+            if (iters >= cp.max_iters) { status = CD_MAX_CDS; break; }
+        }
+        return iters;
+    }
+    // The changes of the last solved block that the residual does not contain yet: those of look-ahead slot `ps`, or
+    // (ps < 0) the ones a plain solve left.
+    struct PendingChanges { const int32_t* dcol; const T* dlt; const int32_t* nz; };
+    PendingChanges pending_changes(int ps) const {
+        const size_t SL = size_t(cd_block_size());
+        if (ps < 0) return {d_dcolblk.p, d_dlt.p, &d_blk.p->nz};
+        return {d_la_dcol.p + size_t(ps) * SL, d_la_dlt.p + size_t(ps) * SL, d_la_nz.p + ps};
+    }
+    // buffers of the look-ahead form: the cross-block tables, the two slots of per-block vectors, the slice partials
+    void reserve_lookahead(size_t maxblk, int mode) {
+        const int SL = cd_block_size();
+        if (xscr_key.size() != maxblk) {
+            d_Xpool.reserve(size_t(2) * maxblk * SL * SL);
+            xscr_key.assign(maxblk, XKey{});
+            xact_key.assign(maxblk, XKey{});
+        }
+        d_la_dlt.reserve(size_t(2) * SL); d_la_g.reserve(size_t(2) * SL); d_la_rsum.reserve(2); d_la_dd.reserve(size_t(2) * SL);
+        d_la_dcol.reserve(size_t(2) * SL); d_la_dpos.reserve(size_t(2) * SL); d_la_nz.reserve(2);
+        d_part.reserve(size_t(2 * panel_part_elems(n) + 2048));
+        part2_half = size_t(panel_part_elems(n));
+        d_part2.reserve(2 * part2_half);
+        if (mode != 2) pending_slot = -1; // (mode 2: the pass in flight leaves its last block's changes pending)
+    }
+    // block j of a look-ahead pass: the solve writes slot j & 1 and reads the previous block's changes from the other slot
+    template <class BP>
+    void wire_lookahead_slots(BP& bp, int slot) {
+        const size_t SL = size_t(cd_block_size());
+        const int pslot = slot ^ 1;
+        bp.pdlt = d_la_dlt.p + size_t(pslot) * SL;
+        bp.ppos = d_la_dpos.p + size_t(pslot) * SL;
+        bp.pnz = d_la_nz.p + pslot;
+        bp.dlt = d_la_dlt.p + size_t(slot) * SL;
+        bp.dcol = d_la_dcol.p + size_t(slot) * SL;
+        bp.dpos = d_la_dpos.p + size_t(slot) * SL;
+        bp.nz_out = d_la_nz.p + slot;
+        bp.rsum_out = d_la_rsum.p + slot;
+        bp.pdd = d_la_dd.p + size_t(pslot) * SL;
+        bp.dd = d_la_dd.p + size_t(slot) * SL;
+    }
+    // the solve of a pass's last block publishes the pass state (wait_pass_state)
+    template <class BP>
+    void set_pass_report(BP& bp, int j, int nblk) {
+        if (h_report && j == nblk - 1) {
+            bp.report_j = j;
+            bp.report_seq = ++report_seq;
+        } else {
+            bp.report_j = -1;
+        }
+    }
+    // End of a panel fit: the last block's changes go into the residual, which is then current; the scalars go back to the
+    // caller; a failed fit is undone, r += X_S (beta - beta0)  (solver_gaussian_naive.hpp:286-290,326-329 restore the saved residual).
+    void finish_panel_passes(const CdParams<T>& cp, CdScalars<T>& sc, const CdBlkState<T>& bs, int64_t iters, int status, int asz,
+                             bool la, T* r_dev) {
+        t_cd.begin(st);
+        const bool from_slot = la && pending_slot >= 0;
+        const PendingChanges pc = pending_changes(from_slot ? pending_slot : -1);
+        panel_step(cur_w, r_dev, pc.dcol, pc.dlt, pc.nz, d_vcol.p, 0);
+        if (from_slot) pending_slot = -1;
+        t_cd.end(st);
+        store_pass_scalars(sc, bs, iters, status, asz);
+        sc.n_delta = 0;
+        if (status != CD_OK) {
+            launch_cd_compact<T>(cp.beta, cp.beta0, cp.vcol, cp.nv, cp.dcols, cp.dvals, &cp.sc->n_delta, st);
+            axpy_cols(cp.dcols, cp.dvals, &cp.sc->n_delta, 0, T(1), r_dev);
+            sync();
+        }
+    }
+
     // Residual-based block passes (kernels_cd_panel.hip).  Per block: panel step (apply the previous block's changes to the
     // residual, partial gradients of this block) -> reduce -> one-workgroup solve against the cached diagonal block.
     // The residual is current when this returns (no end-of-fit update), also on failure (changes are undone).
@@ -163,12 +248,7 @@
         const int SL = cd_block_size(); // D slot: SL x SL, leading dimension SL
         const size_t maxblk = size_t((p + B - 1) / B + 1);
         panel_setup(maxblk);
-        CdBlkState<T> bs{};
-        bs.rsq = sc.rsq;
-        bs.resid_sum = sc.resid_sum;
-        bs.active_size = sc.active_size;
-        bs.status = CD_OK;
-        bs.nz = 0;
+        CdBlkState<T> bs = initial_pass_state(sc);
         const int mode = spec_mode; // 1: enqueue one (speculative) active pass and return; 2: that pass is already in flight
         if (mode != 2) d_blk.upload(&bs, 1, st);
         bool first_open = open_from_grad && mode != 2 && !cons_on; // block 0 of the first pass: gradient from the sweep
@@ -185,7 +265,6 @@
         bp.host_st = rep_st_dev; bp.host_seq = rep_seq_dev; bp.report_j = -1; bp.report_seq = 0;
         const T* xm_c = intercept ? cur_xm : nullptr;
         const bool trace = hooks.trace >= 1;
-        int64_t iters = 0;
         int status = CD_OK;
         int asz = sc.active_size;
         // blocks prebuilt by a fit that ended before its screen pass (error paths): let them finish before anything reuses
@@ -194,27 +273,17 @@
             if (e) AHIP_CHECK(hipStreamWaitEvent(st, e, 0));
         pre_ev.clear();
         pre_used = 0;
-        const bool prebuild_screen = is_glm() && prebuild_enabled;
+        const bool prebuild_screen = is_glm();
         bool screen_prebuilt = false;
         // look-ahead only under fixed weights: the cross blocks are built once per block pair and re-used for the rest of the
         // path; under IRLS they would double the MFMA work of every iteration
         const bool la = lookahead && !is_glm() && B == SL && !std_generic() && !sparse();
         if (la) {
-            if (xscr_key.size() != maxblk) {
-                d_Xpool.reserve(size_t(2) * maxblk * SL * SL);
-                xscr_key.assign(maxblk, XKey{});
-                xact_key.assign(maxblk, XKey{});
-            }
-            d_la_dlt.reserve(size_t(2) * SL); d_la_g.reserve(size_t(2) * SL); d_la_rsum.reserve(2); d_la_dd.reserve(size_t(2) * SL);
-            d_la_dcol.reserve(size_t(2) * SL); d_la_dpos.reserve(size_t(2) * SL); d_la_nz.reserve(2);
+            reserve_lookahead(maxblk, mode);
             if (!d_zero_i32.p) {
                 d_zero_i32.reserve(1);
                 AHIP_CHECK(hipMemsetAsync(d_zero_i32.p, 0, sizeof(int32_t), st));
             }
-            d_part.reserve(size_t(2 * panel_part_elems(n) + 2048));
-            part2_half = size_t(panel_part_elems(n));
-            d_part2.reserve(2 * part2_half);
-            if (mode != 2) pending_slot = -1; // (mode 2: the pass in flight leaves its last block's changes pending)
         }
         bool no_wait = false;
         auto pass_la = [&](bool screen_pass) -> T {
@@ -248,7 +317,7 @@
             // Fused opening (fuse_reduce): the first launch is a fused launch WITHOUT a solve (j = -1) that prepares block 0
             // only and leaves slice partials; block 0 is then solved by a regular fused launch whose step applies nothing and
             // prepares block 1 — one launch, one boundary and 93 MB of the first step less per pass than step + reduce + solve.
-            const bool fr_open = fuse_reduce && la_fused_open;
+            const bool fr_open = fuse_reduce;
             int prev_ld = 0;         // partials of block j left behind by the previous fused launch (0: none, gblk is ready)
             const bool from_grad = fr_open && first_pass && pending_slot < 0;
             if (from_grad) {
@@ -257,30 +326,26 @@
                 launch_la_open_from_grad<T>(d_grad.p, cols_all, nb_of(0), d_la_g.p, xm_c ? &d_blk.p->resid_sum : nullptr,
                                             d_la_rsum.p, st);
             } else if (fr_open) {
-                const int ps = pending_slot;
+                const PendingChanges pc = pending_changes(pending_slot);
                 CdBlkParams<T> op = bp;
                 op.report_j = -1;
                 op.rsum_out = d_la_rsum.p;                                 // both slots <- resid_sum at the start of the pass
                 op.part_rsum = xm_c ? &d_blk.p->resid_sum : nullptr;
-                const int32_t* dc = ps < 0 ? d_dcolblk.p : d_la_dcol.p + size_t(ps) * SL;
-                const T* dl = ps < 0 ? d_dlt.p : d_la_dlt.p + size_t(ps) * SL;
-                const int32_t* nzp = ps < 0 ? &d_blk.p->nz : d_la_nz.p + ps;
                 T* part_out = d_part2.p + part2_half; // parity of "launch -1"
                 if (time_panel) t_step.begin(st);
                 if (dense())
-                    prev_ld = launch_panel_fused<T>(op, -1, D->dense<T>(), cur_w, r_dev, dc, dl, nzp, cols_all, nb_of(0), part_out, true, st);
+                    prev_ld = launch_panel_fused<T>(op, -1, D->dense<T>(), cur_w, r_dev, pc.dcol, pc.dlt, pc.nz, cols_all, nb_of(0), part_out, true,
+                                                    st);
                 else
-                    prev_ld = launch_panel_fused_snp<T>(op, -1, D->snp(), static_cast<const T*>(D->impute), cur_w, r_dev, dc, dl, nzp,
-                                                        cols_all, nb_of(0), part_out, true, st);
+                    prev_ld = launch_panel_fused_snp<T>(op, -1, D->snp(), static_cast<const T*>(D->impute), cur_w, r_dev, pc.dcol, pc.dlt,
+                                                        pc.nz, cols_all, nb_of(0), part_out, true, st);
                 if (time_panel) t_step.end(st);
                 cnt.n_panel_cols += nb_of(0);
             } else {
                 const int nb01 = nb_of(0) + (nblk > 1 ? nb_of(1) : 0);
-                const int ps = pending_slot;
+                const PendingChanges pc = pending_changes(pending_slot);
                 if (time_panel) t_step.begin(st);
-                const int nsl = panel_step(cur_w, r_dev, ps < 0 ? d_dcolblk.p : d_la_dcol.p + size_t(ps) * SL,
-                                           ps < 0 ? d_dlt.p : d_la_dlt.p + size_t(ps) * SL,
-                                           ps < 0 ? &d_blk.p->nz : d_la_nz.p + ps, cols_all, nb01);
+                const int nsl = panel_step(cur_w, r_dev, pc.dcol, pc.dlt, pc.nz, cols_all, nb01);
                 if (time_panel) t_step.end(st);
                 launch_panel_reduce<T>(d_part.p, nsl, nb01, cols_all, &d_blk.p->resid_sum, xm_c, d_la_g.p, st);
                 cnt.n_panel_cols += nb01;
@@ -303,22 +368,8 @@
                 prev_ld = 0;
                 bp.Dptr = pool + size_t(j) * SL * SL;
                 bp.Cprev = j > 0 ? xpool + size_t(j) * SL * SL : nullptr;
-                bp.pdlt = d_la_dlt.p + size_t(pslot) * SL;
-                bp.ppos = d_la_dpos.p + size_t(pslot) * SL;
-                bp.pnz = d_la_nz.p + pslot;
-                bp.dlt = d_la_dlt.p + size_t(slot) * SL;
-                bp.dcol = d_la_dcol.p + size_t(slot) * SL;
-                bp.dpos = d_la_dpos.p + size_t(slot) * SL;
-                bp.nz_out = d_la_nz.p + slot;
-                bp.rsum_out = d_la_rsum.p + slot;
-                bp.pdd = d_la_dd.p + size_t(pslot) * SL;
-                bp.dd = d_la_dd.p + size_t(slot) * SL;
-                if (h_report && j == nblk - 1) {
-                    bp.report_j = j;
-                    bp.report_seq = ++report_seq;
-                } else {
-                    bp.report_j = -1;
-                }
+                wire_lookahead_slots(bp, slot);
+                set_pass_report(bp, j, nblk);
                 if (blk_ev[size_t(j)]) AHIP_CHECK(hipStreamWaitEvent(st, blk_ev[size_t(j)], 0));
                 if (x_ev[size_t(j)]) AHIP_CHECK(hipStreamWaitEvent(st, x_ev[size_t(j)], 0));
                 if (j == 0 && !fr_open) { // nothing to overlap with: the step above already prepared block 1
@@ -389,11 +440,9 @@
             auto step_of = [&](int j) {
                 const int nb = std::min(B, count - j * B);
                 const int32_t* cols = cols_all + size_t(j) * B;
-                const int ps = (j == 0) ? pending_slot : -1;
+                const PendingChanges pc = pending_changes(j == 0 ? pending_slot : -1);
                 if (time_panel) t_step.begin(st);
-                const int nsl = panel_step(cur_w, r_dev, ps < 0 ? d_dcolblk.p : d_la_dcol.p + size_t(ps) * SL,
-                                           ps < 0 ? d_dlt.p : d_la_dlt.p + size_t(ps) * SL,
-                                           ps < 0 ? &d_blk.p->nz : d_la_nz.p + ps, cols, nb, !multi() && !sparse(), xm_c);
+                const int nsl = panel_step(cur_w, r_dev, pc.dcol, pc.dlt, pc.nz, cols, nb, !multi() && !sparse(), xm_c);
                 if (time_panel) t_step.end(st);
                 step_tailed_of[j & 1] = step_tailed;
                 return nsl;
@@ -419,7 +468,7 @@
             vb_vars = nullptr;
             merge_strip_events(false);
             pass_e0_valid = false;
-            if (!screen_pass && prebuild_screen && !screen_prebuilt && side_grams && st2) {
+            if (!screen_pass && prebuild_screen && !screen_prebuilt && st2) {
                 // IRLS: every screen-order block is stale as well (new weights) and the screen pass follows the active-set
                 // passes of this fit: enqueue those builds now, behind the ones this pass waits for, so that they run while
                 // the active-set passes iterate
@@ -444,12 +493,7 @@
                 cnt.n_panel_cols += nb;
                 if (!step_tailed_of[j & 1]) panel_reduce(nsl, nb, cols, xm_c, d_gblk.p); // (else the step left the gradient in d_gblk)
                 bp.Dptr = Dptr;
-                if (h_report && j == nblk - 1) {
-                    bp.report_j = j;
-                    bp.report_seq = ++report_seq;
-                } else {
-                    bp.report_j = -1;
-                }
+                set_pass_report(bp, j, nblk);
                 if (blk_ev[size_t(j)]) AHIP_CHECK(hipStreamWaitEvent(st, blk_ev[size_t(j)], 0));
                 launch_cd_panel_solve<T>(bp, j, st);
             }
@@ -487,62 +531,22 @@
                 return bs.cm;
             }
             const int count = screen_pass ? cp.nv : asz;
-            return (la && (count + B - 1) / B >= la_min_blocks) ? pass_la(screen_pass) : pass_plain(screen_pass);
+            return (la && (count + B - 1) / B >= kLaMinBlocks) ? pass_la(screen_pass) : pass_plain(screen_pass);
         };
         if (mode == 1) {
             spec_enqueued = false;
             if (asz > 0 && !is_glm()) {
                 const int64_t cols0 = cnt.n_panel_cols;
                 no_wait = true;
-                if (la && (asz + B - 1) / B >= la_min_blocks) pass_la(false);
+                if (la && (asz + B - 1) / B >= kLaMinBlocks) pass_la(false);
                 else pass_plain(false);
                 spec_cols = cnt.n_panel_cols - cols0;
                 spec_enqueued = true;
             }
             return;
         }
-        while (status == CD_OK) {
-            while (status == CD_OK) { // solve_active, pin_naive:173-215
-                ++iters;
-                ++sc.n_passes_active;
-                sc.n_visits_active += asz;
-                const T cm = pass(false);
-                if (status != CD_OK) break;
-                if (cm < cp.tol) break;
-                if (iters >= cp.max_iters) { status = CD_MAX_CDS; break; }
-            }
-            if (status != CD_OK) break;
-            ++iters;
-            ++sc.n_passes_screen;
-            sc.n_visits_screen += cp.nv;
-            const T cm = pass(true);
-            if (status != CD_OK) break;
-            if (cm < cp.tol) break;
-            if (iters >= cp.max_iters) { status = CD_MAX_CDS; break; }
-        }
-        // flush the last block's changes into the residual
-        t_cd.begin(st);
-        if (la && pending_slot >= 0) {
-            panel_step(cur_w, r_dev, d_la_dcol.p + size_t(pending_slot) * SL, d_la_dlt.p + size_t(pending_slot) * SL,
-                       d_la_nz.p + pending_slot, d_vcol.p, 0);
-            pending_slot = -1;
-        } else {
-            panel_step(cur_w, r_dev, d_dcolblk.p, d_dlt.p, &d_blk.p->nz, d_vcol.p, 0);
-        }
-        t_cd.end(st);
-        sc.rsq = bs.rsq;
-        sc.resid_sum = bs.resid_sum;
-        sc.iters = iters;
-        sc.n_updates = bs.n_updates;
-        sc.active_size = asz;
-        sc.status = status;
-        sc.n_delta = 0;
-        if (status != CD_OK) {
-            // undo: r += X_S (beta - beta0)   (solver_gaussian_naive.hpp:286-290,326-329 restore the saved residual)
-            launch_cd_compact<T>(cp.beta, cp.beta0, cp.vcol, cp.nv, cp.dcols, cp.dvals, &cp.sc->n_delta, st);
-            axpy_cols(cp.dcols, cp.dvals, &cp.sc->n_delta, 0, T(1), r_dev);
-            sync();
-        }
+        const int64_t iters = run_pass_loop(cp, sc, cp.nv, status, asz, pass);
+        finish_panel_passes(cp, sc, bs, iters, status, asz, la, r_dev);
     }
 
     // Same for problems with groups: blocks of consecutive groups (<= 128 values), partition built on the host.
@@ -555,7 +559,6 @@
     PassTables ptab_scr, ptab_act;
     DevBuf<int32_t> d_blk_g0_act, d_gdesc_act;
     DevBuf<T> d_la_corr;                      // look-ahead corrections left by the previous solve (CdGrpBlkParams::corr_out), by block parity
-    bool pass_tables_cached = true;           // A/B hook ADELIE_HIP_PASS_TABLES=0
     std::vector<int32_t> part_host;
     int build_partition(const idx* list, idx count) { // returns nblk; fills part_host with nblk+1 list positions
         const int B = cd_block_size();
@@ -582,11 +585,7 @@
         d_Dbuf.reserve(size_t(2) * B * B);
         d_dlt.reserve(B);
         d_didx.reserve(B);
-        CdBlkState<T> bs{};
-        bs.rsq = sc.rsq;
-        bs.resid_sum = sc.resid_sum;
-        bs.active_size = sc.active_size;
-        bs.status = CD_OK;
+        CdBlkState<T> bs = initial_pass_state(sc);
         d_blk.upload(&bs, 1, st);
         CdGrpBlkParams<T> bp{};
         bp.nv = cp.nv; bp.C = cp.C; bp.ldc = cp.ldc; bp.vars = cp.vars; bp.xmean = cp.xmean; bp.beta = cp.beta; bp.g = cp.g;
@@ -597,7 +596,6 @@
         bp.V = cp.V; bp.voff = cp.voff; bp.spen = cp.spen; bp.sbegin = cp.sbegin; bp.ssize = cp.ssize;
         bp.Dbuf = d_Dbuf.p; bp.dlt = d_dlt.p; bp.didx = d_didx.p; bp.st = d_blk.p;
         if (cons_on) { bp.clo = d_clo.p; bp.chi = d_chi.p; bp.cmu = d_cmu.p; } // one-coefficient closed forms (grp_clip_1d)
-        int64_t iters = 0;
         int status = CD_OK;
         int asz = sc.active_size;
         std::vector<idx> act_host(active_set.begin(), active_set.begin() + asz); // host mirror of the active list
@@ -641,31 +639,8 @@
             asz = bs.active_size;
             return bs.cm;
         };
-        while (status == CD_OK) {
-            while (status == CD_OK) { // solve_active, pin_naive:173-215
-                ++iters;
-                ++sc.n_passes_active;
-                sc.n_visits_active += asz;
-                const T cm = pass(false);
-                if (status != CD_OK) break;
-                if (cm < cp.tol) break;
-                if (iters >= cp.max_iters) { status = CD_MAX_CDS; break; }
-            }
-            if (status != CD_OK) break;
-            ++iters;
-            ++sc.n_passes_screen;
-            sc.n_visits_screen += cp.ns;
-            const T cm = pass(true);
-            if (status != CD_OK) break;
-            if (cm < cp.tol) break;
-            if (iters >= cp.max_iters) { status = CD_MAX_CDS; break; }
-        }
-        sc.rsq = bs.rsq;
-        sc.resid_sum = bs.resid_sum;
-        sc.iters = iters;
-        sc.n_updates = bs.n_updates;
-        sc.active_size = asz;
-        sc.status = status;
+        const int64_t iters = run_pass_loop(cp, sc, cp.ns, status, asz, pass);
+        store_pass_scalars(sc, bs, iters, status, asz);
         launch_cd_compact<T>(cp.beta, cp.beta0, cp.vcol, cp.nv, cp.dcols, cp.dvals, &cp.sc->n_delta, st);
         AHIP_CHECK(hipMemcpyAsync(&sc.n_delta, &cp.sc->n_delta, sizeof(int32_t), hipMemcpyDeviceToHost, st));
         sync();
@@ -881,12 +856,7 @@
         const int SL = cd_block_size();
         panel_setup(group_maxblk());
         const size_t maxblk = panel_maxblk;
-        CdBlkState<T> bs{};
-        bs.rsq = sc.rsq;
-        bs.resid_sum = sc.resid_sum;
-        bs.active_size = sc.active_size;
-        bs.status = CD_OK;
-        bs.nz = 0;
+        CdBlkState<T> bs = initial_pass_state(sc);
         const int mode = spec_mode; // see run_panel_passes
         if (mode != 2) d_blk.upload(&bs, 1, st);
         bool first_open = open_from_grad && mode != 2 && !cons_on && !multi(); // see run_panel_passes
@@ -901,7 +871,7 @@
         bp.dlt = d_dlt.p; bp.st = d_blk.p;
         bp.gblk = d_gblk.p; bp.vcol = cp.vcol; bp.dcol = d_dcolblk.p;
         bp.host_st = rep_st_dev; bp.host_seq = rep_seq_dev; bp.report_j = -1; bp.report_seq = 0;
-        bp.rot = group_rot ? 1 : 0;
+        bp.rot = 1; // the solves work in the eigen-coordinates of the block's groups (grp_solve_body_rot)
         if (cons_on) { bp.clo = d_clo.p; bp.chi = d_chi.p; bp.cmu = d_cmu.p; }
         struct RotGuard { // builds of this fit are rotated behind their launch (build_stale_blocks); off again on any exit
             Solver* s;
@@ -912,27 +882,13 @@
         bp.dbg = d_grp_dbg.p;
 #endif
         const T* xm_c = intercept ? cur_xm : nullptr;
-        int64_t iters = 0;
         int status = CD_OK;
         int asz = sc.active_size;
         std::vector<idx> act_host(active_set.begin(), active_set.begin() + asz); // host mirror of the active list
         std::vector<int32_t>& acols = h_actcols;
         // look-ahead form (see run_panel_passes); not on the multi-response view, whose step is a different kernel
         const bool la = lookahead && !is_glm() && (!multi() || multi_w_uniform) && !std_generic() && !sparse();
-        if (la) {
-            if (xscr_key.size() != maxblk) {
-                d_Xpool.reserve(size_t(2) * maxblk * SL * SL);
-                xscr_key.assign(maxblk, XKey{});
-                xact_key.assign(maxblk, XKey{});
-            }
-            d_la_dlt.reserve(size_t(2) * SL); d_la_g.reserve(size_t(2) * SL); d_la_rsum.reserve(2); d_la_dd.reserve(size_t(2) * SL);
-            d_la_dcol.reserve(size_t(2) * SL); d_la_dpos.reserve(size_t(2) * SL); d_la_nz.reserve(2);
-            d_la_dd.reserve(size_t(2) * SL);
-            d_part.reserve(size_t(2 * panel_part_elems(n) + 2048));
-            part2_half = size_t(panel_part_elems(n));
-            d_part2.reserve(2 * part2_half);
-            if (mode != 2) pending_slot = -1;
-        }
+        if (la) reserve_lookahead(maxblk, mode);
         // (The group solve summing the slice partials itself, as the lasso solve does, was measured slower — config 3: 722.7 ms
         // with, 654.1 ms without: a group launch is bound by its solve — and removed in round 4.)
         // The LAST STEP WORKGROUP of a fused launch sums them instead: it finishes ~9 us before the solve does, and summing
@@ -959,16 +915,22 @@
         if (tail_ok) d_part2.reserve(2 * size_t(panel_part_elems(n)));
         bool no_wait = false;
         d_gdesc.reserve(maxblk * size_t(GDESC_STRIDE));
-        auto pass_la = [&](bool screen_pass) -> T {
-            const bool first_pass = first_open;
-            first_open = false;
-            const idx count = screen_pass ? idx(cp.ns) : idx(asz);
-            if (count <= 0) return T(0);
+        // Opening of a pass over `count` entries of its visiting list: the partition into blocks, and - unless the list is the
+        // one the tables were made for (PassTables) - its upload, the design columns of the active values in visiting order and
+        // the layout descriptors of the blocks.
+        struct OpenedPass {
+            int nblk;
+            const int32_t* cols_all;
+            std::vector<int32_t>& tab_nb;
+            std::vector<uint64_t>& tab_ver;
+            T* pool;
+        };
+        auto open_pass = [&](bool screen_pass, idx count) -> OpenedPass {
             const int nblk = build_partition_values(screen_pass ? nullptr : act_host.data(), count);
             PassTables& ptab = screen_pass ? ptab_scr : ptab_act;
             DevBuf<int32_t>& g0buf = screen_pass ? d_blk_g0 : d_blk_g0_act;
             DevBuf<int32_t>& descbuf = screen_pass ? d_gdesc : d_gdesc_act;
-            const bool tables_hit = pass_tables_cached && ptab.count == int64_t(count) && ptab.nblk == nblk && g0buf.p && descbuf.p;
+            const bool tables_hit = ptab.count == int64_t(count) && ptab.nblk == nblk && g0buf.p && descbuf.p;
             if (!tables_hit) {
                 g0buf.reserve(std::max<size_t>(part_host.size(), maxblk + 2));
                 g0buf.upload(part_host.data(), part_host.size(), st);
@@ -988,18 +950,38 @@
             auto& tab_nb = screen_pass ? dscr_nb : dact_nb;
             auto& tab_ver = screen_pass ? dscr_ver : dact_ver;
             T* pool = d_Dpool.p + (screen_pass ? size_t(0) : maxblk * SL * SL);
-            T* xpool = d_Xpool.p + (screen_pass ? size_t(0) : maxblk * SL * SL);
             bp.blk_g0 = g0buf.p;
             bp.list = screen_pass ? nullptr : cp.active_set;
             bp.nblk = nblk;
             bp.mark = screen_pass ? 1 : 0;
             descbuf.reserve(maxblk * size_t(GDESC_STRIDE));
             bp.desc = descbuf.p;
-            if (bp.rot && !tables_hit) launch_grp_layout<T>(bp, nblk, descbuf.p, st);
+            if (!tables_hit) launch_grp_layout<T>(bp, nblk, descbuf.p, st);
             ptab.count = int64_t(count);
             ptab.nblk = nblk;
+            return OpenedPass{nblk, cols_all, tab_nb, tab_ver, pool};
+        };
+        // Close of a pass whose state is in `bs`: picks up the groups a screen pass activated (host mirror of the active list)
+        auto take_pass_state = [&]() -> T {
+            status = bs.status;
+            if (bs.active_size > asz) {
+                std::vector<int32_t> fresh(size_t(bs.active_size - asz));
+                d_actset.download(fresh.data(), fresh.size(), st, asz);
+                sync();
+                for (int32_t v : fresh) act_host.push_back(v);
+            }
+            asz = bs.active_size;
+            return bs.cm;
+        };
+        auto pass_la = [&](bool screen_pass) -> T {
+            const bool first_pass = first_open;
+            first_open = false;
+            const idx count = screen_pass ? idx(cp.ns) : idx(asz);
+            if (count <= 0) return T(0);
+            const OpenedPass pt = open_pass(screen_pass, count);
+            T* xpool = d_Xpool.p + (screen_pass ? size_t(0) : maxblk * SL * SL);
             auto nb_of = [&](int j) { return int(gp_vbeg[size_t(j) + 1] - gp_vbeg[j]); };
-            auto cols_of = [&](int j) { return cols_all + gp_vbeg[j]; };
+            auto cols_of = [&](int j) { return pt.cols_all + gp_vbeg[j]; };
             record_pass_e0();
             t_cd.begin(st);
             // first step of the pass: pending changes of the previous pass's last block; blocks 0 and 1 prepared.  Enqueued
@@ -1007,13 +989,13 @@
             // Fused opening (tail reduce available): a fused launch without a solve (j = -1) applies the pending changes and
             // prepares block 0 (its last step workgroup leaves the gradient); block 0 is then solved by a regular fused
             // launch whose step applies nothing and prepares block 1 - instead of step + two reduces + a stand-alone solve.
-            const bool fr_open = tail_ok && la_fused_open && dense();
+            const bool fr_open = tail_ok && dense();
             if (fr_open && first_pass && pending_slot < 0) {
                 // (as in run_panel_passes: block 0's gradient out of the sweep's result, no opening launch)
-                launch_la_open_from_grad<T>(d_grad.p, cols_all, nb_of(0), d_la_g.p, xm_c ? &d_blk.p->resid_sum : nullptr,
+                launch_la_open_from_grad<T>(d_grad.p, pt.cols_all, nb_of(0), d_la_g.p, xm_c ? &d_blk.p->resid_sum : nullptr,
                                             d_la_rsum.p, st);
             } else if (fr_open) {
-                const int ps = pending_slot;
+                const PendingChanges pc = pending_changes(pending_slot);
                 CdGrpBlkParams<T> op = bp;
                 op.report_j = -1;
                 op.rsum_out = d_la_rsum.p;
@@ -1023,66 +1005,54 @@
                 op.tail_rsum = &d_blk.p->resid_sum;
                 op.tail_xm = xm_c;
                 if (time_panel) t_step.begin(st);
-                launch_panel_fused_grp<T>(op, -1, D->dense<T>(), cur_w, r_dev, ps < 0 ? d_dcolblk.p : d_la_dcol.p + size_t(ps) * SL,
-                                          ps < 0 ? d_dlt.p : d_la_dlt.p + size_t(ps) * SL, ps < 0 ? &d_blk.p->nz : d_la_nz.p + ps,
-                                          cols_all, nb_of(0), d_part2.p, true, st);
+                launch_panel_fused_grp<T>(op, -1, D->dense<T>(), cur_w, r_dev, pc.dcol, pc.dlt, pc.nz, pt.cols_all, nb_of(0), d_part2.p, true,
+                                          st);
                 if (time_panel) t_step.end(st);
                 cnt.n_panel_cols += nb_of(0);
             } else {
-                const int nv0 = nb_of(0), nv1 = nblk > 1 ? nb_of(1) : 0;
-                const int ps = pending_slot;
+                const int nv0 = nb_of(0), nv1 = pt.nblk > 1 ? nb_of(1) : 0;
+                const PendingChanges pc = pending_changes(pending_slot);
                 if (time_panel) t_step.begin(st);
-                const int nsl = panel_step(cur_w, r_dev, ps < 0 ? d_dcolblk.p : d_la_dcol.p + size_t(ps) * SL,
-                                           ps < 0 ? d_dlt.p : d_la_dlt.p + size_t(ps) * SL,
-                                           ps < 0 ? &d_blk.p->nz : d_la_nz.p + ps, cols_all, nv0 + nv1);
+                const int nsl = panel_step(cur_w, r_dev, pc.dcol, pc.dlt, pc.nz, pt.cols_all, nv0 + nv1);
                 if (time_panel) t_step.end(st);
-                launch_panel_reduce<T>(d_part.p, nsl, nv0, cols_all, &d_blk.p->resid_sum, xm_c, d_la_g.p, st);
+                launch_panel_reduce<T>(d_part.p, nsl, nv0, pt.cols_all, &d_blk.p->resid_sum, xm_c, d_la_g.p, st);
                 if (nv1 > 0)
-                    launch_panel_reduce<T>(d_part.p + size_t(nv0) * size_t(nsl), nsl, nv1, cols_all + nv0, &d_blk.p->resid_sum,
+                    launch_panel_reduce<T>(d_part.p + size_t(nv0) * size_t(nsl), nsl, nv1, pt.cols_all + nv0, &d_blk.p->resid_sum,
                                            xm_c, d_la_g.p + SL, st);
                 cnt.n_panel_cols += nv0 + nv1;
             }
             if (strips_apply() && !multi()) {
-                T* raw = group_rot ? d_Draw.reserve(size_t(2) * maxblk * SL * SL) + (screen_pass ? size_t(0) : maxblk * SL * SL) : pool;
-                build_stale_strips(nblk, tab_nb, tab_ver, screen_pass ? &xscr_key : &xact_key, raw, xpool, nb_of, cols_of,
-                                   group_rot ? pool : nullptr, screen_pass ? nullptr : act_host.data());
+                T* raw = d_Draw.reserve(size_t(2) * maxblk * SL * SL) + (screen_pass ? size_t(0) : maxblk * SL * SL);
+                build_stale_strips(pt.nblk, pt.tab_nb, pt.tab_ver, screen_pass ? &xscr_key : &xact_key, raw, xpool, nb_of, cols_of,
+                                   pt.pool, screen_pass ? nullptr : act_host.data());
             } else {
                 strip_ev.clear();
             }
-            rot_on = group_rot;
+            rot_on = true;
             rot_list = screen_pass ? nullptr : act_host.data();
-            build_stale_blocks(nblk, tab_nb, tab_ver, pool, nb_of, cols_of);
+            build_stale_blocks(pt.nblk, pt.tab_nb, pt.tab_ver, pt.pool, nb_of, cols_of);
             rot_on = false;
-            build_stale_cross(nblk, screen_pass ? xscr_key : xact_key, xpool, nb_of, cols_of);
+            build_stale_cross(pt.nblk, screen_pass ? xscr_key : xact_key, xpool, nb_of, cols_of);
             merge_strip_events(true);
             pass_e0_valid = false;
             if (screen_pass) join_uv(); // the new screen groups' blocks / variances / eigenbases (update_vars_panel_groups)
             int prev_ld = 0; // partials of block j left behind by the previous fused launch (fr_grp), see run_panel_passes
             // the correction of block j + 1 formed by the idle waves of solve j (CdGrpBlkParams::Cnext): fused launches of the
             // rotated single-response form
-            const bool next_corr = bp.rot && !multi();
+            const bool next_corr = !multi();
             if (next_corr) d_la_corr.reserve(size_t(2) * SL);
             bool prev_made_corr = false;
-            for (int j = 0; j < nblk; ++j) {
+            for (int j = 0; j < pt.nblk; ++j) {
                 const int slot = j & 1, pslot = slot ^ 1;
                 bp.gblk = d_la_g.p + size_t(slot) * SL;
-                bp.Dptr = pool + size_t(j) * SL * SL;
+                bp.Dptr = pt.pool + size_t(j) * SL * SL;
                 bp.Cprev = j > 0 ? xpool + size_t(j) * SL * SL : nullptr;
                 bp.corr_in = (prev_made_corr && j > 0) ? d_la_corr.p + size_t(pslot) * SL : nullptr;
                 const bool fused_j = !(j == 0 && !fr_open);
-                bp.Cnext = (next_corr && fused_j && j + 1 < nblk) ? xpool + size_t(j + 1) * SL * SL : nullptr;
+                bp.Cnext = (next_corr && fused_j && j + 1 < pt.nblk) ? xpool + size_t(j + 1) * SL * SL : nullptr;
                 bp.corr_out = d_la_corr.p ? d_la_corr.p + size_t(slot) * SL : nullptr;
                 prev_made_corr = bp.Cnext != nullptr;
-                bp.pdlt = d_la_dlt.p + size_t(pslot) * SL;
-                bp.ppos = d_la_dpos.p + size_t(pslot) * SL;
-                bp.pnz = d_la_nz.p + pslot;
-                bp.dlt = d_la_dlt.p + size_t(slot) * SL;
-                bp.dcol = d_la_dcol.p + size_t(slot) * SL;
-                bp.dpos = d_la_dpos.p + size_t(slot) * SL;
-                bp.nz_out = d_la_nz.p + slot;
-                bp.rsum_out = d_la_rsum.p + slot;
-                bp.pdd = d_la_dd.p + size_t(pslot) * SL;
-                bp.dd = d_la_dd.p + size_t(slot) * SL;
+                wire_lookahead_slots(bp, slot);
                 bp.part = nullptr;
                 bp.part_n = prev_ld;
                 bp.part_rsum = xm_c ? d_la_rsum.p + slot : nullptr;
@@ -1092,12 +1062,7 @@
                 bp.tail_g = d_la_g.p + size_t(pslot) * SL;
                 bp.tail_rsum = d_la_rsum.p + pslot;
                 bp.tail_xm = xm_c;
-                if (h_report && j == nblk - 1) {
-                    bp.report_j = j;
-                    bp.report_seq = ++report_seq;
-                } else {
-                    bp.report_j = -1;
-                }
+                set_pass_report(bp, j, pt.nblk);
                 if (blk_ev[size_t(j)]) AHIP_CHECK(hipStreamWaitEvent(st, blk_ev[size_t(j)], 0));
                 if (x_ev[size_t(j)]) AHIP_CHECK(hipStreamWaitEvent(st, x_ev[size_t(j)], 0));
                 if (bp.Cnext) { // the next cross block is read by THIS launch: whatever builds or extends it (strips record into either list)
@@ -1108,8 +1073,8 @@
                     launch_cd_group_panel_solve<T>(bp, 0, st);
                     continue;
                 }
-                const int nbn = (j + 1 < nblk) ? nb_of(j + 1) : 0;
-                const int32_t* cols_n = cols_all + gp_vbeg[size_t(j) + 1];
+                const int nbn = (j + 1 < pt.nblk) ? nb_of(j + 1) : 0;
+                const int32_t* cols_n = pt.cols_all + gp_vbeg[size_t(j) + 1];
                 const int32_t* nz_apply = (j == 0) ? d_zero_i32.p : d_la_nz.p + pslot; // (j = 0 of a fused opening: nothing to apply)
                 int ld;
                 if (time_panel) t_step.begin(st);
@@ -1136,21 +1101,13 @@
                     cnt.n_panel_cols += nbn;
                 }
             }
-            pending_slot = (nblk - 1) & 1;
+            pending_slot = (pt.nblk - 1) & 1;
             t_cd.end(st);
             AHIP_CHECK(hipGetLastError());
-            cnt.n_panel_blocks += nblk;
-            if (no_wait) { spec_blocks = nblk; return T(0); }
+            cnt.n_panel_blocks += pt.nblk;
+            if (no_wait) { spec_blocks = pt.nblk; return T(0); }
             wait_pass_state(bs);
-            status = bs.status;
-            if (bs.active_size > asz) {
-                std::vector<int32_t> fresh(size_t(bs.active_size - asz));
-                d_actset.download(fresh.data(), fresh.size(), st, asz);
-                sync();
-                for (int32_t v : fresh) act_host.push_back(v);
-            }
-            asz = bs.active_size;
-            return bs.cm;
+            return take_pass_state();
         };
         CdBlkState<T> host_bs{};
         bool last_on_host = false;
@@ -1159,67 +1116,33 @@
             const idx count = screen_pass ? idx(cp.ns) : idx(asz);
             if (count <= 0) return T(0);
             last_on_host = false;
-            const int nblk = build_partition_values(screen_pass ? nullptr : act_host.data(), count);
-            PassTables& ptab = screen_pass ? ptab_scr : ptab_act;
-            DevBuf<int32_t>& g0buf = screen_pass ? d_blk_g0 : d_blk_g0_act;
-            DevBuf<int32_t>& descbuf = screen_pass ? d_gdesc : d_gdesc_act;
-            const bool tables_hit = pass_tables_cached && ptab.count == int64_t(count) && ptab.nblk == nblk && g0buf.p && descbuf.p;
-            if (!tables_hit) {
-                g0buf.reserve(std::max<size_t>(part_host.size(), maxblk + 2));
-                g0buf.upload(part_host.data(), part_host.size(), st);
-            }
-            const int32_t* cols_all = d_vcol.p;
-            if (!screen_pass) { // design columns of the active values in visiting order
-                if (!tables_hit) {
-                    acols.clear();
-                    for (idx pos = 0; pos < count; ++pos) {
-                        const idx g = screen_set[act_host[pos]];
-                        for (idx t = 0; t < group_sizes[g]; ++t) acols.push_back(int32_t(groups[g] + t));
-                    }
-                    d_actcols.upload(acols.data(), acols.size(), st);
-                }
-                cols_all = d_actcols.p;
-            }
-            auto& tab_nb = screen_pass ? dscr_nb : dact_nb;
-            auto& tab_ver = screen_pass ? dscr_ver : dact_ver;
-            T* pool = d_Dpool.p + (screen_pass ? size_t(0) : maxblk * SL * SL);
-            bp.blk_g0 = g0buf.p;
-            bp.list = screen_pass ? nullptr : cp.active_set;
-            bp.nblk = nblk;
-            bp.mark = screen_pass ? 1 : 0;
-            descbuf.reserve(maxblk * size_t(GDESC_STRIDE));
-            bp.desc = descbuf.p;
             bp.pdd = nullptr; bp.dd = nullptr;
-            if (bp.rot && !tables_hit) launch_grp_layout<T>(bp, nblk, descbuf.p, st);
-            ptab.count = int64_t(count);
-            ptab.nblk = nblk;
+            const OpenedPass pt = open_pass(screen_pass, count);
             if (strips_apply()) {
-                T* raw = group_rot ? d_Draw.reserve(size_t(2) * maxblk * SL * SL) + (screen_pass ? size_t(0) : maxblk * SL * SL) : pool;
-                build_stale_strips(nblk, tab_nb, tab_ver, nullptr, raw, static_cast<T*>(nullptr),
+                T* raw = d_Draw.reserve(size_t(2) * maxblk * SL * SL) + (screen_pass ? size_t(0) : maxblk * SL * SL);
+                build_stale_strips(pt.nblk, pt.tab_nb, pt.tab_ver, nullptr, raw, static_cast<T*>(nullptr),
                                    [&](int j) { return int(gp_vbeg[size_t(j) + 1] - gp_vbeg[j]); },
-                                   [&](int j) { return cols_all + gp_vbeg[j]; }, group_rot ? pool : nullptr,
+                                   [&](int j) { return pt.cols_all + gp_vbeg[j]; }, pt.pool,
                                    screen_pass ? nullptr : act_host.data());
             } else {
                 strip_ev.clear();
             }
-            rot_on = group_rot;
+            rot_on = true;
             rot_list = screen_pass ? nullptr : act_host.data();
-            build_stale_blocks(nblk, tab_nb, tab_ver, pool, [&](int j) { return int(gp_vbeg[size_t(j) + 1] - gp_vbeg[j]); },
-                               [&](int j) { return cols_all + gp_vbeg[j]; });
+            build_stale_blocks(pt.nblk, pt.tab_nb, pt.tab_ver, pt.pool, [&](int j) { return int(gp_vbeg[size_t(j) + 1] - gp_vbeg[j]); },
+                               [&](int j) { return pt.cols_all + gp_vbeg[j]; });
             merge_strip_events(false);
             if (screen_pass) join_uv();
             t_cd.begin(st);
             bp.gblk = d_gblk.p; bp.dlt = d_dlt.p; bp.dcol = d_dcolblk.p;
             bp.Cprev = nullptr; bp.dpos = nullptr; bp.nz_out = nullptr; bp.rsum_out = nullptr;
-            for (int j = 0; j < nblk; ++j) {
+            for (int j = 0; j < pt.nblk; ++j) {
                 const int nval = gp_vbeg[size_t(j) + 1] - gp_vbeg[j];
-                const int32_t* cols = cols_all + gp_vbeg[j];
-                T* Dptr = pool + size_t(j) * SL * SL;
-                const int ps = (j == 0) ? pending_slot : -1;
+                const int32_t* cols = pt.cols_all + gp_vbeg[j];
+                T* Dptr = pt.pool + size_t(j) * SL * SL;
+                const PendingChanges pc = pending_changes(j == 0 ? pending_slot : -1);
                 if (time_panel) t_step.begin(st);
-                const int nsl = panel_step(cur_w, r_dev, ps < 0 ? d_dcolblk.p : d_la_dcol.p + size_t(ps) * SL,
-                                           ps < 0 ? d_dlt.p : d_la_dlt.p + size_t(ps) * SL,
-                                           ps < 0 ? &d_blk.p->nz : d_la_nz.p + ps, cols, nval);
+                const int nsl = panel_step(cur_w, r_dev, pc.dcol, pc.dlt, pc.nz, cols, nval);
                 if (time_panel) t_step.end(st);
                 pending_slot = -1;
                 cnt.n_panel_cols += nval;
@@ -1229,41 +1152,28 @@
                     if (part_host[size_t(j) + 1] - part_host[size_t(j)] == 1 && host_cons(screen_set[ss0])) {
                         if (blk_ev[size_t(j)]) AHIP_CHECK(hipStreamWaitEvent(st, blk_ev[size_t(j)], 0)); // (its eigenbasis)
                         if (on_device(screen_set[ss0])) { // one launch, the pass report included when it is the last block
-                            dev_group_visit(cp, ss0, screen_pass, j == 0, false, j == nblk - 1);
+                            dev_group_visit(cp, ss0, screen_pass, j == 0, false, j == pt.nblk - 1);
                             last_on_host = false;
                             continue;
                         }
                         host_bs = host_group_visit(cp, ss0, screen_pass, j == 0);
-                        last_on_host = (j == nblk - 1);
+                        last_on_host = (j == pt.nblk - 1);
                         continue;
                     }
                     last_on_host = false;
                 }
                 bp.Dptr = Dptr;
-                if (h_report && j == nblk - 1) {
-                    bp.report_j = j;
-                    bp.report_seq = ++report_seq;
-                } else {
-                    bp.report_j = -1;
-                }
+                set_pass_report(bp, j, pt.nblk);
                 if (blk_ev[size_t(j)]) AHIP_CHECK(hipStreamWaitEvent(st, blk_ev[size_t(j)], 0));
                 launch_cd_group_panel_solve<T>(bp, j, st);
             }
             t_cd.end(st);
             AHIP_CHECK(hipGetLastError()); // a failed launch would otherwise only show up as a stalled pass report
-            cnt.n_panel_blocks += nblk;
-            if (no_wait) { spec_blocks = nblk; return T(0); }
+            cnt.n_panel_blocks += pt.nblk;
+            if (no_wait) { spec_blocks = pt.nblk; return T(0); }
             if (last_on_host) bs = host_bs; // (no device solve published a report for this pass)
             else wait_pass_state(bs);
-            status = bs.status;
-            if (bs.active_size > asz) { // pick up the groups activated by this screen pass
-                std::vector<int32_t> fresh(size_t(bs.active_size - asz));
-                d_actset.download(fresh.data(), fresh.size(), st, asz);
-                sync();
-                for (int32_t v : fresh) act_host.push_back(v);
-            }
-            asz = bs.active_size;
-            return bs.cm;
+            return take_pass_state();
         };
         bool resume_first = mode == 2;
         auto pass = [&](bool screen_pass) -> T {
@@ -1277,7 +1187,7 @@
             if (!la) return pass_plain(screen_pass);
             const idx count = screen_pass ? idx(cp.ns) : idx(asz);
             const int nblk = count > 0 ? build_partition(screen_pass ? nullptr : act_host.data(), count) : 0;
-            return nblk >= la_min_blocks ? pass_la(screen_pass) : pass_plain(screen_pass);
+            return nblk >= kLaMinBlocks ? pass_la(screen_pass) : pass_plain(screen_pass);
         };
         if (mode == 1) {
             spec_enqueued = false;
@@ -1290,46 +1200,7 @@
             }
             return;
         }
-        while (status == CD_OK) {
-            while (status == CD_OK) { // solve_active, pin_naive:173-215
-                ++iters;
-                ++sc.n_passes_active;
-                sc.n_visits_active += asz;
-                const T cm = pass(false);
-                if (status != CD_OK) break;
-                if (cm < cp.tol) break;
-                if (iters >= cp.max_iters) { status = CD_MAX_CDS; break; }
-            }
-            if (status != CD_OK) break;
-            ++iters;
-            ++sc.n_passes_screen;
-            sc.n_visits_screen += cp.ns;
-            const T cm = pass(true);
-            if (status != CD_OK) break;
-            if (cm < cp.tol) break;
-            if (iters >= cp.max_iters) { status = CD_MAX_CDS; break; }
-        }
-        // flush the last block's changes into the residual
-        t_cd.begin(st);
-        if (la && pending_slot >= 0) {
-            panel_step(cur_w, r_dev, d_la_dcol.p + size_t(pending_slot) * SL, d_la_dlt.p + size_t(pending_slot) * SL,
-                       d_la_nz.p + pending_slot, d_vcol.p, 0);
-            pending_slot = -1;
-        } else {
-            panel_step(cur_w, r_dev, d_dcolblk.p, d_dlt.p, &d_blk.p->nz, d_vcol.p, 0);
-        }
-        t_cd.end(st);
-        sc.rsq = bs.rsq;
-        sc.resid_sum = bs.resid_sum;
-        sc.iters = iters;
-        sc.n_updates = bs.n_updates;
-        sc.active_size = asz;
-        sc.status = status;
-        sc.n_delta = 0;
-        if (status != CD_OK) { // undo: r += X_S (beta - beta0)
-            launch_cd_compact<T>(cp.beta, cp.beta0, cp.vcol, cp.nv, cp.dcols, cp.dvals, &cp.sc->n_delta, st);
-            axpy_cols(cp.dcols, cp.dvals, &cp.sc->n_delta, 0, T(1), r_dev);
-            sync();
-        }
+        const int64_t iters = run_pass_loop(cp, sc, cp.ns, status, asz, pass);
+        finish_panel_passes(cp, sc, bs, iters, status, asz, la, r_dev);
     }
 

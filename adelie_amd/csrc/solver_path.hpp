@@ -22,7 +22,7 @@
 
     // update_invariance_f: solver_gaussian_naive.hpp:377-393 / solver_glm_naive.hpp:495-503, + update_abs_grad
     bool inv_wanted = true; // set by solve(): the fit about to run is followed by update_invariance at the same lambda
-    bool prelaunch_sweep = true, inv_prelaunched = false;
+    bool inv_prelaunched = false;
     T inv_prelaunched_lm = 0;
     // ---- speculative first active-set pass of the NEXT lambda (Gaussian lasso on the look-ahead panel engine) ----
     // Between the invariance sweep of lambda_k and the first kernel of the fit at lambda_{k+1} the host checks KKT, screens,
@@ -491,7 +491,6 @@
                 throw make_core_error("multi-response groups (group size x K) must not exceed " + std::to_string(cd_block_size()) + " columns.");
             all_scalar = false;
             engine_panel = true;
-            group_panel = true;
             cd_block_min_nv = 0;
         } else if (glm_kind == ADELIE_HIP_GLM_MULTINOMIAL) {
             throw make_core_error("the multinomial family needs a multi-response view as its design.");
@@ -568,10 +567,10 @@
                     }
                     ++nd;
                 }
-                // the clipped coordinate update lives in the panel solve (blk_solve_body<.., CONS>): that engine from the first
+                // the clipped coordinate update lives in the panel solve (blk_solve_body<T, true>): that engine from the first
                 // screened coefficient on, in its sequential form
-                engine_panel = !cov_mode; // (covariance method: the Gram group engine carries clips and host visits,
-                group_panel = true;       //  solver_gaussian_pin_cov.hpp:287-355,723-763)
+                // (covariance method: the Gram group engine carries clips and host visits, solver_gaussian_pin_cov.hpp:287-355,723-763)
+                engine_panel = !cov_mode;
                 if (cov_mode) {
                     if (max_gs > idx(cd_block_size()))
                         throw make_core_error("constraints are not implemented for problems with groups of more than " +

@@ -268,14 +268,13 @@
         cnt.gram_flops += 2.0 * double(n) * double(M) * double(N);
         gram_shapes.emplace_back(M, N);
     }
-    // pinned staging for the small per-lambda copies (common.hpp::Staging; A/B hook ADELIE_HIP_STAGING=0)
+    // pinned staging for the small per-lambda copies (common.hpp::Staging)
     Staging stage;
     DeferredFrees deferred; // installed for the solving thread by run<T>; drained by ~Solver
     double t_sync_total = 0; // host seconds inside sync() (bench: splits the host phases into compute and waiting)
     // update_vars_panel_groups on the side stream (strip builds of the new screen groups' rows, their eigen-decompositions,
     // the rotations): everything a SCREEN pass needs and an active-set pass does not, so the active-set passes of the fit run
-    // meanwhile and the screen pass (or any host read) joins through this event.  Hook ADELIE_HIP_UV_SIDE=0.
-    bool uv_side = true;
+    // meanwhile and the screen pass (or any host read) joins through this event.
     hipEvent_t uv_ev = nullptr, uv_in_ev = nullptr;
     bool uv_pending = false;
     void join_uv() {
@@ -490,7 +489,7 @@
             if (q > 1) any_group = true;
             max_q = std::max(max_q, q);
         }
-        if (any_group && device_eig && max_q <= idx(kEigMaxQ)) {
+        if (any_group && max_q <= idx(kEigMaxQ)) {
             // eigen-decompositions of the new groups' diagonal blocks of C on the device (kernels_eig.hip): no per-group copy
             // to the host and back, no host wait
             eig_desc.clear();
@@ -620,16 +619,15 @@
         while (j0 + 1 < nblk && size_t(part_host[j0 + 1]) <= g_begin) ++j0;
         idx max_q = 1;
         for (idx ss = idx(g_begin); ss < ns; ++ss) max_q = std::max(max_q, group_sizes[screen_set[ss]]);
-        const bool dev_eig = device_eig && max_q <= idx(kEigMaxQ);
+        const bool dev_eig = max_q <= idx(kEigMaxQ);
         std::vector<T> hD(dev_eig ? size_t(0) : size_t(nblk - j0) * SL * SL);
         std::vector<int> rebuilt_blocks;
         // Gaussian dense designs: only the rows of the new groups (strip builds), with the rows of the cross blocks when the
         // look-ahead tables exist, into the unrotated pool; the staged builder below then finds the blocks fresh
         if (!is_glm()) { cur_w = w_dev; cur_xm = xm_dev; } // (Gaussian: the weights / means every pin solve of the path runs under)
         const bool use_strips = strips_apply();
-        const bool raw_split = use_strips && group_rot;
-        T* const rawbase = raw_split ? d_Draw.p : d_Dpool.p;
-        const bool on_side = use_strips && dev_eig && uv_side && side_grams && st2 != nullptr;
+        T* const rawbase = use_strips ? d_Draw.p : d_Dpool.p;
+        const bool on_side = use_strips && dev_eig && st2 != nullptr;
         if (use_strips) {
             // (diagonal rows only here and the cross rows on the side stream in the pass that needs them: measured slower,
             // config 3 634 vs 621 ms — two launches per block instead of one)
@@ -708,9 +706,8 @@
                 es = st2;
             }
             launch_grp_eig<T>(rawbase, d_eig_desc.p, int(eig_desc.size()), int(max_q), d_vars.p, d_V.p, es);
-            if (group_rot)
-                for (int jb : rebuilt_blocks)
-                    rotate_block(nullptr, jb, d_Dpool.p + size_t(jb) * SL * SL, on_side ? 1 : 0, rawbase + size_t(jb) * SL * SL);
+            for (int jb : rebuilt_blocks)
+                rotate_block(nullptr, jb, d_Dpool.p + size_t(jb) * SL * SL, on_side ? 1 : 0, rawbase + size_t(jb) * SL * SL);
             if (on_side) {
                 AHIP_CHECK(hipEventRecord(uv_ev, st2));
                 uv_pending = true;
@@ -752,22 +749,18 @@
         d_vars.upload(vars_host.data(), N, st, pos0);
         d_voff.upload(voff.data(), voff.size(), st, g_begin);
         // the blocks built above, into the eigen-coordinates of their groups (the eigenbases are on the device now)
-        if (group_rot)
-            for (int jb : rebuilt_blocks)
-                rotate_block(nullptr, jb, d_Dpool.p + size_t(jb) * SL * SL, 0, rawbase + size_t(jb) * SL * SL);
+        for (int jb : rebuilt_blocks) rotate_block(nullptr, jb, d_Dpool.p + size_t(jb) * SL * SL, 0, rawbase + size_t(jb) * SL * SL);
         sync(); // the staging vectors go out of scope
         for (idx t = 0; t < N; ++t) screen_vars[pos0 + t] = vars_host[t];
     }
-    // device-side eigen-decompositions of new screen groups (kernels_eig.hip; A/B hook ADELIE_HIP_DEVICE_EIG=0: host Jacobi on
-    // copies of the blocks, as in rounds 1-2).  `host_mirrors_stale`: screen_vars / screen_transforms on the host lag behind
+    // device-side eigen-decompositions of new screen groups (kernels_eig.hip; groups wider than kEigMaxQ: host Jacobi on
+    // copies of the blocks).  `host_mirrors_stale`: screen_vars / screen_transforms on the host lag behind
     // d_vars / d_V until download_invariants refreshes them.
-    bool device_eig = true;
     bool host_mirrors_stale = false;
     std::vector<EigDesc> eig_desc;
     DevBuf<EigDesc> d_eig_desc;
     // D <- R^T D R for block `jb` of the partition in part_host over `list` (nullptr: screen order), on the stream of build
-    // side `side` (0: main).  See CdGrpBlkParams::rot.
-    bool group_rot = true; // A/B hook ADELIE_HIP_GROUP_ROT=0
+    // side `side` (0: main).  See grp_solve_body_rot.
     std::vector<idx> h_voff; // per screen group: offset of its eigenbasis in d_V
     DevBuf<T> d_rot_scratch[2 + kMaxExtra];
     void rotate_block(const idx* list, int jb, T* Dptr, int side, const T* Dsrc = nullptr) {
