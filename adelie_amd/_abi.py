@@ -191,15 +191,17 @@ S = dict(
     n_basil_iters=50, n_sweeps=51, n_cd_visits_screen=52, n_cd_visits_active=53, n_updates=54,
     n_irls_iters=55, n_new_screen_cols=56, n_cd_passes_screen=57, n_cd_passes_active=58,
     n_gram_col_reads=59, n_resid_col_reads=60, gram_flops=61, n_panel_blocks=62, n_panel_grams=63, n_panel_cols=64, n_irls_screen_cols=65, n_speculated=66, n_spec_rollbacks=67, n_sweeps_shared=68, n_update_cols=69, n_device_screens=70, n_host_screens=71, n_host_cons_visits=72, n_dev_cons_visits=73, n_sweeps_factor=74,
+    n_sweeps_filtered=75, n_sweeps_refilled=76, n_filter_exact_cols=77, n_filter_shadow_cols=78,
     t_sweep_ms=80, t_gram_ms=81, t_cd_ms=82, t_axpy_ms=83, n_sweep_launches=84, n_gram_launches=85,
     t_host_screen_ms=86, t_panel_step_ms=87, n_panel_step_launches=88, t_host_screen_wait_ms=89,
+    t_fsweep_ms=90, n_fsweep_launches=91, fsweep_bytes=92,
 )
 
 # every symbol include/adelie_hip.h declares (checked by tests/test_abi.py)
 HIP_SYMBOLS = [
     "abi_version", "last_error", "device_count", "set_config",
     "design_create_dense", "design_create_sparse", "design_create_csc", "design_create_standardized", "design_adopt_dense_dev", "design_create_snp_unphased",
-    "design_create_snp_calldata", "design_create_snp_bed", "design_alias", "design_create_slice", "design_create_multi", "design_create_derived", "design_create_concat", "design_impute", "design_destroy",
+    "design_create_snp_calldata", "design_create_snp_bed", "design_alias", "design_drop_shadow", "design_shadow_stats", "design_create_slice", "design_create_multi", "design_create_derived", "design_create_concat", "design_impute", "design_destroy",
     "design_create_one_hot", "design_create_interaction", "design_factor_groups",
     "design_glm_path_losses", "design_multi_path_losses", "design_batch_stats", "design_rows", "design_cols", "design_dtype",
     "design_device", "design_stream",
@@ -208,7 +210,7 @@ HIP_SYMBOLS = [
     "design_create_cov_dense", "design_create_cov_lazy", "design_cov_bmul", "design_cov_mul", "design_cov_to_dense", "gaussian_cov_solve",
     "glm_cox_create", "glm_cox_destroy", "glm_cox_eval",
     "grpnet_solve", "grpnet_solve_many", "result_destroy", "result_size", "result_copy", "result_scalar", "result_error", "result_sync",
-    "bench_sweep",
+    "bench_sweep", "filter_sweep_test",
     "css_cov_solve", "css_result_destroy", "css_result_size", "css_result_copy", "css_result_scalar", "css_result_error",
     "bvls_solve", "bvls_result_destroy", "bvls_result_size", "bvls_result_copy", "bvls_result_scalar", "bvls_result_error",
 ]
@@ -277,6 +279,8 @@ class Backend:
         sig("design_create_interaction", ci, [vp, vp, i64, vp, p(vp)])
         sig("design_factor_groups", i64, [vp, vp, vp, i64])
         sig("design_alias", ci, [vp, p(vp)])
+        sig("design_drop_shadow", ci, [vp])
+        sig("design_shadow_stats", ci, [vp, p(i64)])
         sig("design_create_slice", ci, [vp, i64, i64, i64, i64, p(vp)])
         sig("design_batch_stats", ci, [vp, p(dbl)])
         sig("design_create_multi", ci, [vp, i64, ci, p(vp)])
@@ -317,6 +321,7 @@ class Backend:
         sig("result_error", C.c_char_p, [vp])
         sig("result_sync", ci, [vp])
         sig("bench_sweep", ci, [vp, i64, p(dbl)])
+        sig("filter_sweep_test", ci, [vp, vp, vp, dbl, vp, vp, i64, vp, vp, i64, vp, dbl, vp, vp, vp])
         sig("css_cov_solve", ci, [vp, p(CssArgs), p(vp)])
         sig("css_result_destroy", ci, [vp])
         sig("css_result_size", i64, [vp, ci])

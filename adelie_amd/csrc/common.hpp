@@ -34,6 +34,8 @@ namespace ahip {
 //   ADELIE_HIP_FACTOR_SWEEP=0|1   full sweeps of a one-hot / interaction design read off Z (kernels_factor.hip) or off the
 //                                 expanded matrix like any dense design (default: kFactorSweepDefault below; the matrix
 //                                 operations read it at the call)                                                     [A/B, tests]
+//   ADELIE_HIP_FILTER_SWEEP=0|1   the invariance sweep of an eligible Gaussian lambda through the float32 shadow of the design
+//                                 (kernels_sweep.hip) or as the full f64 sweep; same results bit for bit             [A/B, tests]
 //   ADELIE_HIP_TIME_PANEL=1       per-launch HIP events around the panel step (bench.py's roofline leg)
 //   ADELIE_HIP_TRACE=1|2          1: per-pass trace on stderr; 2: + enqueue / allocation / build timings
 struct Hooks {
@@ -43,6 +45,7 @@ struct Hooks {
     int std_panel = -1;      // ADELIE_HIP_STD_PANEL=0: a standardized dense / 2-bit view stays on its full-Gram engines
     int lookahead = -1, speculate = -1;
     int factor_sweep = -1;   // ADELIE_HIP_FACTOR_SWEEP (-1: unset)
+    int filter_sweep = -1;   // ADELIE_HIP_FILTER_SWEEP (-1: unset)
     double irls_reuse = -1;
     bool time_panel = false;
     bool cons_host = false; // ADELIE_HIP_CONS_HOST=1: box / one-sided objects on several coefficients visited on the host (A/B, tests)
@@ -63,7 +66,12 @@ struct Hooks {
         if (const char* e = std::getenv("ADELIE_HIP_STD_PANEL")) h.std_panel = std::atoi(e) != 0;
         if (const char* e = std::getenv("ADELIE_HIP_TRACE")) h.trace = std::max(1, std::atoi(e));
         h.factor_sweep = factor_sweep_env();
+        h.filter_sweep = filter_sweep_env();
         return h;
+    }
+    static int filter_sweep_env() {
+        const char* e = std::getenv("ADELIE_HIP_FILTER_SWEEP");
+        return e ? int(std::atoi(e) != 0) : -1;
     }
     static int factor_sweep_env() {
         const char* e = std::getenv("ADELIE_HIP_FACTOR_SWEEP");
@@ -74,6 +82,11 @@ struct Hooks {
 // measured at least as fast as the dense sweep on both shapes of scripts/bench_factor.py (profiles/factor_sweep.txt).
 constexpr bool kFactorSweepDefault = false;
 inline bool factor_sweep_on(int hook) { return hook < 0 ? kFactorSweepDefault : hook != 0; }
+// Whether an eligible Gaussian lambda takes the filtered invariance sweep (float32 shadow, kernels_sweep.hip) when
+// ADELIE_HIP_FILTER_SWEEP is unset.  On: the headline gains 16 ms of 252 ms per path against a parent-to-hook-off spread of
+// 0.3 ms in one interleaved job, with identical outputs (profiles/filter_sweep.txt).
+constexpr bool kFilterSweepDefault = true;
+inline bool filter_sweep_on(int hook) { return hook < 0 ? kFilterSweepDefault : hook != 0; }
 
 
 // util/exceptions.hpp:8-55 — same prefixes so that the Python layer's error-vs-warning split keeps working
@@ -483,6 +496,15 @@ struct adelie_hip_design {
     // batcher object lives with the design the aliases were made from (solver.hip::SweepBatcher, created on first use).
     adelie_hip_design* batch_owner = nullptr; // nullptr: this design itself
     void* batcher = nullptr;
+    // float32 shadow of a dense f64 design for the filtered invariance sweep (kernels_sweep.hip: ShadowView), made on the first
+    // eligible solve.  Like the batcher it lives with the design the aliases were made from, which frees it.
+    float* sh_X = nullptr;
+    int64_t sh_ld = 0;
+    double* sh_err = nullptr; // (p,) ||x_j - xs_j||_2
+    double* sh_nrm = nullptr; // (p,) ||xs_j||_2
+    int sh_state = 0;         // 0: none yet, 1: built, -1: ineligible (an entry float32 cannot hold, memory, a failed staleness check)
+    int64_t sh_n_ineligible = 0, sh_n_builds = 0;
+    std::mutex sh_mu;
     hipStream_t stream = nullptr;
     // scratch for the host-vector matrix ops (value_t typed, grow-only)
     ahip::DevBuf<char> s_n1, s_n2, s_p1, s_work, s_misc, s_idx1, s_idx2;
@@ -503,3 +525,10 @@ struct adelie_hip_design {
                                   bits, ldb, static_cast<const T*>(impute)};
     }
 };
+
+// The shadow of `d` (of the design its aliases were made from), built on d's stream if there is none yet: false when the
+// design has none and cannot have one.  mark_stale: a staleness check failed -- no later solve takes the shadow.
+extern "C" {
+bool adelie_hip_internal_shadow_acquire(adelie_hip_design* d, ahip::ShadowView* out); // design.hip
+void adelie_hip_internal_shadow_mark_stale(adelie_hip_design* d);
+}

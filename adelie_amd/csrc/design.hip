@@ -1232,6 +1232,83 @@ int adelie_hip_design_batch_stats(adelie_hip_design* d, double* out) {
     ABI_CATCH
 }
 
+static adelie_hip_design* shadow_owner(adelie_hip_design* d) { return d->batch_owner ? d->batch_owner : d; }
+static void shadow_free(adelie_hip_design* o) {
+    (void)hipFree(o->sh_X); (void)hipFree(o->sh_err); (void)hipFree(o->sh_nrm);
+    o->sh_X = nullptr; o->sh_err = nullptr; o->sh_nrm = nullptr;
+    o->sh_ld = 0;
+}
+
+bool adelie_hip_internal_shadow_acquire(adelie_hip_design* d, ahip::ShadowView* out) {
+    if (!d || d->kind != 0 || d->dtype != ADELIE_HIP_F64 || d->cov || d->std_center || !d->X || d->n < 1 || d->p < 1) return false;
+    adelie_hip_design* o = shadow_owner(d);
+    if (o->X != d->X || o->ld != d->ld || o->n != d->n || o->p != d->p) return false;
+    std::lock_guard<std::mutex> lk(o->sh_mu);
+    if (o->sh_state == 0) {
+        const int64_t lds = (d->n + 3) / 4 * 4; // 16-byte aligned columns
+        const size_t need = size_t(d->p) * size_t(lds) * sizeof(float) + 2 * size_t(d->p) * sizeof(double);
+        size_t free_b = 0, total_b = 0;
+        AHIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+        const size_t keep = std::max<size_t>(size_t(4) << 30, total_b / 10);
+        bool ok = free_b >= need && free_b - need >= keep;
+        int32_t* bad = nullptr;
+        if (ok) {
+            ok = hipMalloc((void**)&o->sh_X, size_t(d->p) * size_t(lds) * sizeof(float)) == hipSuccess &&
+                 hipMalloc((void**)&o->sh_err, size_t(d->p) * sizeof(double)) == hipSuccess &&
+                 hipMalloc((void**)&o->sh_nrm, size_t(d->p) * sizeof(double)) == hipSuccess &&
+                 hipMalloc((void**)&bad, sizeof(int32_t)) == hipSuccess;
+            if (!ok) (void)hipGetLastError();
+        }
+        if (ok) {
+            int32_t h_bad = 0;
+            // (plain status checks: an error here must not leave the blocks behind with sh_state still 0)
+            ok = hipMemsetAsync(bad, 0, sizeof(int32_t), d->stream) == hipSuccess;
+            if (ok) launch_shadow_build(d->dense<double>(), o->sh_X, lds, o->sh_err, o->sh_nrm, bad, d->stream);
+            ok = ok && hipMemcpyAsync(&h_bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream) == hipSuccess;
+            ok = (hipStreamSynchronize(d->stream) == hipSuccess) && ok;
+            if (!ok) (void)hipGetLastError();
+            ok = ok && h_bad == 0; // an entry beyond FLT_MAX or not finite: no shadow for this design
+            o->sh_ld = lds;
+            ++o->sh_n_builds;
+        }
+        (void)hipFree(bad);
+        if (!ok) {
+            shadow_free(o);
+            ++o->sh_n_ineligible;
+        }
+        o->sh_state = ok ? 1 : -1;
+    }
+    if (o->sh_state != 1) return false;
+    *out = ahip::ShadowView{o->sh_X, d->n, d->p, o->sh_ld, o->sh_err, o->sh_nrm};
+    return true;
+}
+void adelie_hip_internal_shadow_mark_stale(adelie_hip_design* d) {
+    adelie_hip_design* o = shadow_owner(d);
+    std::lock_guard<std::mutex> lk(o->sh_mu);
+    if (o->sh_state == 1) ++o->sh_n_ineligible;
+    o->sh_state = -1; // (the memory stays until drop_shadow / destroy: a solve on an alias may still be reading it)
+}
+
+int adelie_hip_design_drop_shadow(adelie_hip_design* d) {
+    ABI_TRY
+    if (!d) throw make_core_error("null argument.");
+    adelie_hip_design* o = shadow_owner(d);
+    AHIP_CHECK(hipSetDevice(o->device));
+    std::lock_guard<std::mutex> lk(o->sh_mu);
+    AHIP_CHECK(hipDeviceSynchronize());
+    shadow_free(o);
+    o->sh_state = 0;
+    ABI_CATCH
+}
+int adelie_hip_design_shadow_stats(adelie_hip_design* d, int64_t* out) {
+    ABI_TRY
+    if (!d || !out) throw make_core_error("null argument.");
+    adelie_hip_design* o = shadow_owner(d);
+    std::lock_guard<std::mutex> lk(o->sh_mu);
+    out[0] = o->sh_state; out[1] = o->sh_n_builds; out[2] = o->sh_n_ineligible;
+    ABI_CATCH
+}
+
 int adelie_hip_design_alias(adelie_hip_design* src, adelie_hip_design** out) {
     ABI_TRY
     if (!src || !out) throw make_core_error("null argument.");
@@ -1457,6 +1534,7 @@ int adelie_hip_design_destroy(adelie_hip_design* d) {
     if (d->std_owned) { (void)hipFree(d->std_center); (void)hipFree(d->std_iscale); }
     if (d->ones) (void)hipFree(d->ones);
     if (d->batcher) adelie_hip_internal_free_batcher(d->batcher);
+    (void)hipFree(d->sh_X); (void)hipFree(d->sh_err); (void)hipFree(d->sh_nrm);
     delete d;
     if (live_designs().fetch_sub(1) == 1) DevPool::trim();
     return 0;

@@ -61,6 +61,38 @@ template <class T>
 void launch_sweep_snp(const SnpView& X, const T* impute, const T* v, T* out, int64_t c0, int64_t ncols,
                       const int32_t* cols, const T* sub_scale, const T* sub_vec, bool square, T* work, hipStream_t s);
 int64_t sweep_work_elems(int64_t n, int64_t ncols);
+
+// ---- filtered invariance sweep (kernels_sweep.hip): a float32 shadow of a dense f64 design ----------------------------------
+// Xs: the columns rounded to float32 (column-major, ld a multiple of 4); err[j] = ||x_j - xs_j||_2, nrm[j] = ||xs_j||_2 (both
+// rounded up).  |x_j.v - xs_j.v| as the two sweeps compute them differ by at most (err[j] + fp_term() * nrm[j]) * ||v||_2.
+struct ShadowView {
+    const float* X;
+    int64_t n, p, ld;
+    const double* err;
+    const double* nrm;
+    double fp_term() const { return 4.0 * double(n) * 1.1102230246251565e-16; } // 4 n 2^-53: both accumulations' rounding
+};
+// makes the copy and measures err / nrm; *bad |= 1 when an entry is not finite or beyond FLT_MAX
+void launch_shadow_build(const DenseView<double>& X, float* Xs, int64_t lds, double* err, double* nrm, int32_t* bad, hipStream_t s);
+// out = a * b, and sq_part[0 .. filter_norm_parts(n)) = fixed-order partial sums of out^2
+int filter_norm_parts(int64_t n);
+void launch_vmul_sq(const double* a, const double* b, double* out, int64_t n, double* sq_part, hipStream_t s);
+// out[c] = xs_c . v - (sub_vec ? sub_scale[0] * sub_vec[c] : 0) for every column; work: shadow_sweep_work_elems(n, p)
+int64_t shadow_sweep_work_elems(int64_t n, int64_t p);
+void launch_shadow_sweep(const ShadowView& S, const double* v, double* out, const double* sub_scale, const double* sub_vec,
+                         double* work, hipStream_t s);
+// exact sweep of the first min(*count_dev, max_cols) columns of `cols` (count_dev == nullptr: max_cols), out[cols[c]] = the
+// bits launch_sweep over all X.p columns gives that column; guard != nullptr: out holds the shadow's values on entry and
+// *flags |= 2 when a pair differs by more than its bound (vnorm: device, the ||v||_2 of the bound).  work:
+// sweep_list_work_elems(n, p, max_cols)
+int64_t sweep_list_work_elems(int64_t n, int64_t p, int64_t max_cols);
+void launch_sweep_list(const DenseView<double>& X, const double* v, double* out, const int32_t* cols, int64_t max_cols,
+                       const int32_t* count_dev, const double* sub_scale, const double* sub_vec, const ShadowView* guard,
+                       const double* vnorm, int32_t* flags, double* work, hipStream_t s);
+// see filter_classify_kernel
+void launch_filter_classify(const double* grad, const int64_t* groups, const int64_t* group_sizes, int64_t G, const int32_t* slot,
+                            const double* penalty, double tstar, const ShadowView& S, const double* sq_part, int n_part,
+                            const double* sub_scale, int32_t* list, int64_t cap, int32_t* meta_i, double* meta_d, hipStream_t s);
 // sparse design: one wavefront per (column, row block) over its stored entries; `work` holds sweep_work_elems_csc(X.nb, ncols)
 int64_t sweep_work_elems_csc(int nb, int64_t ncols);
 template <class T>

@@ -18,6 +18,7 @@
 #include "kernels.hpp"
 #include "accessors.hpp"
 #include <cstdlib>
+#include <cfloat>
 
 namespace ahip {
 
@@ -950,6 +951,360 @@ void launch_snp_impute(const uint8_t* bits, int64_t n, int64_t p, int64_t ldb, T
 }
 template void launch_snp_impute<double>(const uint8_t*, int64_t, int64_t, int64_t, double*, hipStream_t);
 template void launch_snp_impute<float>(const uint8_t*, int64_t, int64_t, int64_t, float*, hipStream_t);
+
+// ---- filtered invariance sweep: a float32 shadow of a dense f64 design ---------------------------------------------------
+// The per-lambda gradient sweep is consumed almost only through comparisons with thresholds (KKT, the screening rules).  With
+// xs_j = column j rounded to float32 and e_j = ||x_j - xs_j||_2 measured when the copy is made, |x_j.v - xs_j.v| <= e_j ||v||_2:
+// a sweep of the copy (half the bytes) proves most columns to lie below every threshold, and only the others are swept
+// again in f64.  The exact sweeps over a column list (sweep_list_kernel) repeat, per column, the arithmetic of sweep_kernel
+// on the row splits of the FULL design, so their values are the bits the full sweep gives.
+namespace {
+
+constexpr int kShadowCB = 4, kShadowVec = 4;
+
+__global__ __launch_bounds__(kThreads) void shadow_build_kernel(const double* __restrict__ X, int64_t ld, int64_t n,
+                                                                float* __restrict__ Xs, int64_t lds, double* __restrict__ err,
+                                                                double* __restrict__ nrm, int32_t* __restrict__ bad) {
+    const int64_t j = blockIdx.x;
+    const int tid = threadIdx.x;
+    const double* col = X + j * ld;
+    float* dst = Xs + j * lds;
+    double e2 = 0, n2 = 0;
+    bool any_bad = false;
+    for (int64_t i = tid; i < lds; i += kThreads) {
+        float f = 0.f;
+        if (i < n) {
+            const double x = col[i];
+            const bool ok = fabs(x) <= double(FLT_MAX); // (false for NaN and +-inf as well)
+            any_bad = any_bad || !ok;
+            f = ok ? float(x) : 0.f;
+            const double d = x - double(f);
+            e2 = fma(d, d, e2);
+            n2 = fma(double(f), double(f), n2);
+        }
+        dst[i] = f;
+    }
+    __shared__ double red[2][kThreads / 64];
+    const int lane = tid & 63, wv = tid >> 6;
+    e2 = wave_sum(e2);
+    n2 = wave_sum(n2);
+    if (lane == 0) { red[0][wv] = e2; red[1][wv] = n2; }
+    __syncthreads();
+    if (tid == 0) {
+        double a = 0, b = 0;
+        for (int w = 0; w < kThreads / 64; ++w) { a += red[0][w]; b += red[1][w]; }
+        // (rounded up a little: the sums above carry their own rounding error)
+        err[j] = sqrt(a) * (1.0 + 1e-9);
+        nrm[j] = sqrt(b) * (1.0 + 1e-9);
+    }
+    if (any_bad) atomicOr(bad, 1);
+}
+
+// out = a * b and, per workgroup, the sum of squares of its products (fixed grid, fixed order: ||out||_2 is reproducible)
+__global__ __launch_bounds__(kThreads) void vmul_sq_kernel(const double* __restrict__ a, const double* __restrict__ b,
+                                                           double* __restrict__ out, int64_t n, double* __restrict__ part) {
+    double acc = 0;
+    for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += int64_t(gridDim.x) * blockDim.x) {
+        const double x = a[i] * b[i];
+        out[i] = x;
+        acc = fma(x, x, acc);
+    }
+    __shared__ double red[kThreads / 64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    acc = wave_sum(acc);
+    if (lane == 0) red[wv] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0;
+        for (int w = 0; w < kThreads / 64; ++w) s += red[w];
+        part[blockIdx.x] = s;
+    }
+}
+
+// out[c] = sum_i float(Xs[i, c]) * v[i] over all columns, f64 accumulation; row splits and epilogue as sweep_kernel
+__global__ __launch_bounds__(kThreads) void shadow_sweep_kernel(const float* __restrict__ Xs, int64_t ld,
+                                                                const double* __restrict__ v, double* __restrict__ out,
+                                                                int64_t n, int64_t ncols, int64_t rows_per_split, int nsplit,
+                                                                const double* __restrict__ sub_scale,
+                                                                const double* __restrict__ sub_vec) {
+    constexpr int CB = kShadowCB, VEC = kShadowVec;
+    const int tid = threadIdx.x;
+    const int64_t cb = blockIdx.x;
+    const int split = blockIdx.y;
+    const int64_t r0 = int64_t(split) * rows_per_split;
+    const int64_t r1 = min(n, r0 + rows_per_split);
+    const float* cp[CB];
+#pragma unroll
+    for (int k = 0; k < CB; ++k) {
+        int64_t c = cb * CB + k;
+        if (c >= ncols) c = ncols - 1; // duplicate work on the tail panel, discarded below
+        cp[k] = Xs + c * ld;
+    }
+    double acc[CB];
+#pragma unroll
+    for (int k = 0; k < CB; ++k) acc[k] = 0;
+    const int64_t body_end = r0 + ((r1 - r0) / VEC) * VEC;
+#pragma unroll 2
+    for (int64_t i = r0 + int64_t(tid) * VEC; i < body_end; i += int64_t(kThreads) * VEC) {
+        const d2_t v0 = *reinterpret_cast<const d2_t*>(v + i);
+        const d2_t v1 = *reinterpret_cast<const d2_t*>(v + i + 2);
+        f4_t xx[CB];
+#pragma unroll
+        for (int k = 0; k < CB; ++k) xx[k] = __builtin_nontemporal_load(reinterpret_cast<const f4_t*>(cp[k] + i));
+#pragma unroll
+        for (int k = 0; k < CB; ++k) {
+            acc[k] = fma(double(xx[k][0]), v0[0], acc[k]);
+            acc[k] = fma(double(xx[k][1]), v0[1], acc[k]);
+            acc[k] = fma(double(xx[k][2]), v1[0], acc[k]);
+            acc[k] = fma(double(xx[k][3]), v1[1], acc[k]);
+        }
+    }
+    for (int64_t i = body_end + tid; i < r1; i += kThreads) {
+        const double vi = v[i];
+#pragma unroll
+        for (int k = 0; k < CB; ++k) acc[k] = fma(double(cp[k][i]), vi, acc[k]);
+    }
+    __shared__ double red[kThreads / 64][CB];
+    const int lane = tid & 63, wv = tid >> 6;
+#pragma unroll
+    for (int k = 0; k < CB; ++k) {
+        const double s = wave_sum(acc[k]);
+        if (lane == 0) red[wv][k] = s;
+    }
+    __syncthreads();
+    if (tid < CB) {
+        const int64_t c = cb * CB + tid;
+        if (c < ncols) {
+            double s = 0;
+#pragma unroll
+            for (int w = 0; w < kThreads / 64; ++w) s += red[w][tid];
+            if (nsplit == 1) {
+                if (sub_vec) s -= sub_scale[0] * sub_vec[c];
+                out[c] = s;
+            } else {
+                out[int64_t(split) * ncols + c] = s; // partial
+            }
+        }
+    }
+}
+
+// |exact - shadow| <= bound must hold for every column swept both ways: a design modified after the copy was made shows here
+__device__ __forceinline__ void shadow_guard(double exact, double approx, int64_t j, const double* __restrict__ err,
+                                             const double* __restrict__ nrm, double fp_term, const double* __restrict__ vnorm,
+                                             int32_t* __restrict__ flags) {
+    const double bound = (err[j] + fp_term * nrm[j]) * vnorm[0];
+    if (!(fabs(exact - approx) <= bound)) atomicOr(flags, 2);
+}
+
+// One column per workgroup, the first *count_dev (or max_cols) entries of `cols`: per column the loop, the reductions and the
+// epilogue of sweep_kernel (any CB gives a column the same bits) on the row splits the caller took from the full design's
+// shape; the result goes to out[column].  err != nullptr: out[column] holds the shadow's value on entry (shadow_guard).
+template <int VEC>
+__global__ __launch_bounds__(kThreads) void sweep_list_kernel(DenseAcc<double> X, const double* __restrict__ v,
+                                                              double* __restrict__ out, double* __restrict__ part, int64_t n,
+                                                              const int32_t* __restrict__ cols, int64_t max_cols,
+                                                              const int32_t* __restrict__ count_dev, int64_t rows_per_split,
+                                                              int nsplit, const double* __restrict__ sub_scale,
+                                                              const double* __restrict__ sub_vec, const double* __restrict__ err,
+                                                              const double* __restrict__ nrm, double fp_term,
+                                                              const double* __restrict__ vnorm, int32_t* __restrict__ flags) {
+    const int64_t c = blockIdx.x;
+    const int64_t count = count_dev ? min(int64_t(count_dev[0]), max_cols) : max_cols;
+    if (c >= count) return;
+    const int tid = threadIdx.x;
+    const int split = blockIdx.y;
+    const int64_t r0 = int64_t(split) * rows_per_split;
+    const int64_t r1 = min(n, r0 + rows_per_split);
+    const int64_t j = cols[c];
+    const double* cp = X.colptr(j);
+    double acc = 0;
+    const int64_t body_end = r0 + ((r1 - r0) / VEC) * VEC;
+#pragma unroll 8
+    for (int64_t i = r0 + int64_t(tid) * VEC; i < body_end; i += int64_t(kThreads) * VEC) {
+        const Pack<double, VEC> vv = load_vec<double, VEC>(v + i);
+        const Pack<double, VEC> xx = X.template load<VEC>(cp, i, j);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc = fma(xx.v[e], vv.v[e], acc);
+    }
+    for (int64_t i = body_end + tid; i < r1; i += kThreads) acc = fma(X.template load<1>(cp, i, j).v[0], v[i], acc);
+    __shared__ double red[kThreads / 64];
+    const int lane = tid & 63, wv = tid >> 6;
+    const double ws = wave_sum(acc);
+    if (lane == 0) red[wv] = ws;
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0;
+#pragma unroll
+        for (int w = 0; w < kThreads / 64; ++w) s += red[w];
+        if (nsplit == 1) {
+            if (sub_vec) s -= sub_scale[0] * sub_vec[j];
+            if (err) shadow_guard(s, out[j], j, err, nrm, fp_term, vnorm, flags);
+            out[j] = s;
+        } else {
+            part[int64_t(split) * max_cols + c] = s;
+        }
+    }
+}
+__global__ void sweep_list_reduce_kernel(const double* __restrict__ part, double* __restrict__ out,
+                                         const int32_t* __restrict__ cols, int64_t max_cols,
+                                         const int32_t* __restrict__ count_dev, int nsplit, const double* __restrict__ sub_scale,
+                                         const double* __restrict__ sub_vec, const double* __restrict__ err,
+                                         const double* __restrict__ nrm, double fp_term, const double* __restrict__ vnorm,
+                                         int32_t* __restrict__ flags) {
+    const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const int64_t count = count_dev ? min(int64_t(count_dev[0]), max_cols) : max_cols;
+    if (c >= count) return;
+    const int64_t j = cols[c];
+    double s = 0;
+    for (int r = 0; r < nsplit; ++r) s += part[int64_t(r) * max_cols + c];
+    if (sub_vec) s -= sub_scale[0] * sub_vec[j];
+    if (err) shadow_guard(s, out[j], j, err, nrm, fp_term, vnorm, flags);
+    out[j] = s;
+}
+
+// One workgroup.  ||v||_2 from the partial sums of vmul_sq_kernel, then per group outside the screen set (slot < 0) with a
+// positive penalty: approximate norm a of its gradient block and the bound eps on its distance from the exact one; the
+// columns of every group that a + eps cannot place below thr_g = tstar * penalty_g are appended to `list`, in group order.
+// meta_i: [0] columns listed (at most cap), [1] flags (bit 0: more than cap), [2] columns wanted; meta_d: [0] the inflated
+// ||v||_2 the bounds use, [1] a copy of sub_scale[0] (what a later exact sweep of the same residual subtracts).
+constexpr int kClassifyThreads = 1024;
+__global__ __launch_bounds__(kClassifyThreads) void filter_classify_kernel(
+    const double* __restrict__ grad, const int64_t* __restrict__ groups, const int64_t* __restrict__ group_sizes, int64_t G,
+    const int32_t* __restrict__ slot, const double* __restrict__ penalty, double tstar, const double* __restrict__ err,
+    const double* __restrict__ nrm, double fp_term, const double* __restrict__ sq_part, int n_part,
+    const double* __restrict__ sub_scale, int32_t* __restrict__ list, int64_t cap, int32_t* __restrict__ meta_i,
+    double* __restrict__ meta_d) {
+    constexpr int NW = kClassifyThreads / 64;
+    __shared__ double sred[NW];
+    __shared__ int32_t wtot[NW];
+    __shared__ double s_vnorm;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    {
+        double a = 0;
+        for (int i = tid; i < n_part; i += kClassifyThreads) a += sq_part[i];
+        a = wave_sum(a);
+        if (lane == 0) sred[wv] = a;
+        __syncthreads();
+        if (tid == 0) {
+            double s = 0;
+            for (int w = 0; w < NW; ++w) s += sred[w];
+            s_vnorm = sqrt(s) * (1.0 + 1e-6);
+            meta_d[0] = s_vnorm;
+            meta_d[1] = sub_scale ? sub_scale[0] : 0.0;
+        }
+        __syncthreads();
+    }
+    const double vnorm = s_vnorm;
+    int64_t run = 0;
+    for (int64_t g0 = 0; g0 < G; g0 += kClassifyThreads) {
+        const int64_t g = g0 + tid;
+        int32_t mine = 0;
+        int64_t k = 0;
+        if (g < G && slot[g] < 0 && penalty[g] > 0) {
+            k = groups[g];
+            const int64_t sz = group_sizes[g];
+            double a2 = 0, b2 = 0;
+            for (int64_t t = 0; t < sz; ++t) {
+                const double x = grad[k + t], b = err[k + t] + fp_term * nrm[k + t];
+                a2 = fma(x, x, a2);
+                b2 = fma(b, b, b2);
+            }
+            const double reach = (sqrt(a2) + sqrt(b2) * vnorm * (1.0 + 1e-9)) * (1.0 + 1e-9);
+            if (!(reach < tstar * penalty[g])) mine = int32_t(sz);
+        }
+        // exclusive scan of `mine` over the workgroup
+        int32_t inc = mine;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int32_t y = __shfl_up(inc, off, 64);
+            if (lane >= off) inc += y;
+        }
+        if (lane == 63) wtot[wv] = inc;
+        __syncthreads();
+        int32_t before = 0, total = 0;
+        for (int w = 0; w < NW; ++w) {
+            const int32_t t = wtot[w];
+            if (w < wv) before += t;
+            total += t;
+        }
+        const int64_t at = run + before + inc - mine;
+        for (int32_t t = 0; t < mine; ++t)
+            if (at + t < cap) list[at + t] = int32_t(k + t);
+        run += total;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        meta_i[0] = int32_t(run < cap ? run : cap);
+        if (run > cap) atomicOr(meta_i + 1, 1);
+        meta_i[2] = int32_t(run < int64_t(0x7fffffff) ? run : int64_t(0x7fffffff));
+    }
+}
+
+} // namespace
+
+void launch_shadow_build(const DenseView<double>& X, float* Xs, int64_t lds, double* err, double* nrm, int32_t* bad,
+                         hipStream_t s) {
+    if (X.p <= 0) return;
+    hipLaunchKernelGGL(shadow_build_kernel, dim3((unsigned)X.p), dim3(kThreads), 0, s, X.X, X.ld, X.n, Xs, lds, err, nrm, bad);
+}
+int filter_norm_parts(int64_t n) { return int(grid1d(n, kThreads, 1024)); }
+void launch_vmul_sq(const double* a, const double* b, double* out, int64_t n, double* sq_part, hipStream_t s) {
+    hipLaunchKernelGGL(vmul_sq_kernel, dim3(grid1d(n, kThreads, 1024)), dim3(kThreads), 0, s, a, b, out, n, sq_part);
+}
+int64_t shadow_sweep_work_elems(int64_t n, int64_t p) {
+    int64_t blocks_c, rps;
+    int ns;
+    sweep_shape(n, p, kShadowVec, blocks_c, ns, rps);
+    return int64_t(ns) * p + 16;
+}
+void launch_shadow_sweep(const ShadowView& S, const double* v, double* out, const double* sub_scale, const double* sub_vec,
+                         double* work, hipStream_t s) {
+    if (S.p <= 0) return;
+    int64_t blocks_c, rps;
+    int ns;
+    sweep_shape(S.n, S.p, kShadowVec, blocks_c, ns, rps);
+    static_assert(kShadowCB == kSweepCB, "sweep_shape counts panels of kSweepCB columns");
+    hipLaunchKernelGGL(shadow_sweep_kernel, dim3((unsigned)blocks_c, (unsigned)ns), dim3(kThreads), 0, s, S.X, S.ld, v,
+                       ns == 1 ? out : work, S.n, S.p, rps, ns, sub_scale, sub_vec);
+    if (ns > 1)
+        hipLaunchKernelGGL((sweep_reduce_kernel<double>), dim3((unsigned)((S.p + 255) / 256)), dim3(256), 0, s, work, out, S.p,
+                           ns, int64_t(0), (const int32_t*)nullptr, sub_scale, sub_vec);
+}
+int64_t sweep_list_work_elems(int64_t n, int64_t p, int64_t max_cols) {
+    int64_t blocks_c, rps;
+    int ns;
+    sweep_shape(n, p, 1, blocks_c, ns, rps); // VEC=1 gives the largest split count
+    return int64_t(ns) * max_cols + 16;
+}
+void launch_sweep_list(const DenseView<double>& X, const double* v, double* out, const int32_t* cols, int64_t max_cols,
+                       const int32_t* count_dev, const double* sub_scale, const double* sub_vec, const ShadowView* guard,
+                       const double* vnorm, int32_t* flags, double* work, hipStream_t s) {
+    if (max_cols <= 0) return;
+    DenseAcc<double> acc{X.X, X.ld};
+    const bool vec = dense_vec_ok(X) && (reinterpret_cast<uintptr_t>(v) % 16) == 0;
+    int64_t blocks_c, rps;
+    int ns;
+    sweep_shape(X.n, X.p, vec ? VecOf<double>::N : 1, blocks_c, ns, rps); // the FULL design's shape, whatever the list length
+    const double* err = guard ? guard->err : nullptr;
+    const double* nrm = guard ? guard->nrm : nullptr;
+    const double fp = guard ? guard->fp_term() : 0.0;
+    dim3 grid((unsigned)max_cols, (unsigned)ns);
+    if (vec)
+        hipLaunchKernelGGL((sweep_list_kernel<VecOf<double>::N>), grid, dim3(kThreads), 0, s, acc, v, out, work, X.n, cols, max_cols,
+                           count_dev, rps, ns, sub_scale, sub_vec, err, nrm, fp, vnorm, flags);
+    else
+        hipLaunchKernelGGL((sweep_list_kernel<1>), grid, dim3(kThreads), 0, s, acc, v, out, work, X.n, cols, max_cols, count_dev, rps,
+                           ns, sub_scale, sub_vec, err, nrm, fp, vnorm, flags);
+    if (ns > 1)
+        hipLaunchKernelGGL(sweep_list_reduce_kernel, dim3((unsigned)((max_cols + 255) / 256)), dim3(256), 0, s, work, out, cols,
+                           max_cols, count_dev, ns, sub_scale, sub_vec, err, nrm, fp, vnorm, flags);
+}
+void launch_filter_classify(const double* grad, const int64_t* groups, const int64_t* group_sizes, int64_t G, const int32_t* slot,
+                            const double* penalty, double tstar, const ShadowView& S, const double* sq_part, int n_part,
+                            const double* sub_scale, int32_t* list, int64_t cap, int32_t* meta_i, double* meta_d, hipStream_t s) {
+    hipLaunchKernelGGL(filter_classify_kernel, dim3(1), dim3(kClassifyThreads), 0, s, grad, groups, group_sizes, G, slot, penalty,
+                       tstar, S.err, S.nrm, S.fp_term(), sq_part, n_part, sub_scale, list, cap, meta_i, meta_d);
+}
 
 #define INST(T)                                                                                                        \
     template void launch_vmul<T>(const T*, const T*, T*, int64_t, hipStream_t);                                        \

@@ -11,6 +11,7 @@
 // p-vector or the design runs in the kernels of kernels_*.hip on the design's stream.  Per BASIL iteration the
 // host receives: the CD kernel's scalar block, the screen coefficients (<= |S| values) and abs_grad (G values).
 #include "common.hpp"
+#include "filter_host.hpp"
 #include "cox.hpp"
 
 #include <algorithm>
@@ -561,6 +562,13 @@ struct Result : ResultBase {
             case ADELIE_HIP_S_N_HOST_CONS_VISITS: return double(s.n_host_cons_visits);
             case ADELIE_HIP_S_N_DEV_CONS_VISITS: return double(s.n_dev_cons_visits_final);
             case ADELIE_HIP_S_N_SWEEPS_FACTOR: return double(s.cnt.n_sweeps_factor);
+            case ADELIE_HIP_S_N_SWEEPS_FILTERED: return double(s.n_sweeps_filtered);
+            case ADELIE_HIP_S_N_SWEEPS_REFILLED: return double(s.n_sweeps_refilled);
+            case ADELIE_HIP_S_N_FILTER_EXACT_COLS: return double(s.n_filter_exact_cols);
+            case ADELIE_HIP_S_N_FILTER_SHADOW_COLS: return double(s.n_filter_shadow_cols);
+            case ADELIE_HIP_S_T_FSWEEP_MS: return s.t_fsweep.ms;
+            case ADELIE_HIP_S_N_FSWEEP_LAUNCHES: return double(s.t_fsweep.launches);
+            case ADELIE_HIP_S_FSWEEP_BYTES: return s.fsweep_bytes;
             default:
                 if (which >= 900 && which < 908) return double(s.cd_dbg[which - 900]);
                 if (which >= 910 && which < 918) return 1e3 * s.t_host[which - 910];
@@ -813,6 +821,90 @@ int adelie_hip_bench_sweep(adelie_hip_design* d, int64_t reps, double* ms_per_la
         };
         if (d->dtype == ADELIE_HIP_F64) body(double{});
         else body(float{});
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return 1;
+    }
+    return 0;
+}
+
+// One filtered invariance sweep on a dense f64 design, as a solve at one lambda enqueues it: v = w o r, the shadow sweep, the
+// classification against tstar, the exact sweeps of the screen groups' columns, of the groups without a penalty and of the
+// groups listed.  grad (p), exact (p: 1 where the value is the full sweep's), info: [0] columns listed, [1] flags (1: more
+// than the cap of max(1024, p/4) were wanted, 2: a column swept both ways left its bound), [2] 1 if the route ran, 0 if
+// the plain full sweep answered (hook off, no shadow), [3] columns wanted.
+int adelie_hip_filter_sweep_test(adelie_hip_design* d, const double* w, const double* r, double sub_scale, const double* sub_vec,
+                                 const int64_t* screen_groups, int64_t n_screen, const int64_t* groups, const int64_t* group_sizes,
+                                 int64_t G, const double* penalty, double tstar, double* grad, uint8_t* exact, int64_t* info) {
+    try {
+        if (!d || !w || !r || !groups || !group_sizes || !penalty || !grad || !exact || !info || G < 1 || n_screen < 0)
+            throw make_core_error("bad arguments.");
+        if (d->kind != 0 || d->dtype != ADELIE_HIP_F64 || d->cov || d->std_center) throw make_core_error("a dense f64 design is required.");
+        AHIP_CHECK(hipSetDevice(d->device));
+        hipStream_t s = d->stream;
+        const int64_t n = d->n, p = d->p;
+        if (groups[G - 1] + group_sizes[G - 1] != p) throw make_core_error("groups do not cover the columns.");
+        std::vector<int32_t> slot(size_t(G), -1), scols, pen0;
+        for (int64_t k = 0; k < n_screen; ++k) {
+            const int64_t g = screen_groups[k];
+            if (g < 0 || g >= G) throw make_core_error("screen group out of range.");
+            slot[size_t(g)] = int32_t(scols.size());
+            for (int64_t t = 0; t < group_sizes[g]; ++t) scols.push_back(int32_t(groups[g] + t));
+        }
+        for (int64_t g = 0; g < G; ++g)
+            if (!(penalty[g] > 0))
+                for (int64_t t = 0; t < group_sizes[g]; ++t) pen0.push_back(int32_t(groups[g] + t));
+        ShadowView sh{};
+        const bool route = filter_sweep_on(Hooks::filter_sweep_env()) && adelie_hip_internal_shadow_acquire(d, &sh);
+        const int64_t cap = filter_list_cap(p);
+        DevBuf<double> dw, dr, dv, dgrad, dxm, dsc, dpen, dpart, dmetad, work;
+        DevBuf<int64_t> dgroups, dgs;
+        DevBuf<int32_t> dslot, dscols, dpen0, dlist, dmeta;
+        dw.reserve(n); dr.reserve(n); dv.reserve(n); dgrad.reserve(p); dsc.reserve(1); dpen.reserve(G); dgroups.reserve(G);
+        dgs.reserve(G); dslot.reserve(G); dlist.reserve(cap); dmeta.reserve(4); dmetad.reserve(2);
+        const int n_part = filter_norm_parts(n);
+        dpart.reserve(n_part);
+        const int64_t mx = std::max<int64_t>(std::max<int64_t>(cap, int64_t(scols.size())), int64_t(pen0.size()));
+        work.reserve(size_t(std::max(std::max(sweep_list_work_elems(n, p, mx), shadow_sweep_work_elems(n, p)), sweep_work_elems(n, p))));
+        dw.upload(w, n, s); dr.upload(r, n, s); dsc.upload(&sub_scale, 1, s); dpen.upload(penalty, G, s);
+        dgroups.upload(groups, G, s); dgs.upload(group_sizes, G, s); dslot.upload(slot.data(), G, s);
+        if (sub_vec) { dxm.reserve(p); dxm.upload(sub_vec, p, s); }
+        if (!scols.empty()) { dscols.reserve(scols.size()); dscols.upload(scols.data(), scols.size(), s); }
+        if (!pen0.empty()) { dpen0.reserve(pen0.size()); dpen0.upload(pen0.data(), pen0.size(), s); }
+        const double* xm = sub_vec ? dxm.p : nullptr;
+        const DenseView<double> X = d->dense<double>();
+        int32_t meta[4] = {0, 0, 0, 0};
+        std::vector<int32_t> list;
+        if (!route) {
+            launch_vmul<double>(dw.p, dr.p, dv.p, n, s);
+            launch_sweep<double>(X, dv.p, dgrad.p, 0, p, nullptr, dsc.p, xm, false, work.p, s);
+            std::fill(exact, exact + p, uint8_t(1));
+        } else {
+            AHIP_CHECK(hipMemsetAsync(dmeta.p, 0, 4 * sizeof(int32_t), s));
+            launch_vmul_sq(dw.p, dr.p, dv.p, n, dpart.p, s);
+            launch_shadow_sweep(sh, dv.p, dgrad.p, dsc.p, xm, work.p, s);
+            launch_filter_classify(dgrad.p, dgroups.p, dgs.p, G, dslot.p, dpen.p, tstar, sh, dpart.p, n_part, dsc.p, dlist.p, cap,
+                                   dmeta.p, dmetad.p, s);
+            if (!scols.empty())
+                launch_sweep_list(X, dv.p, dgrad.p, dscols.p, int64_t(scols.size()), nullptr, dsc.p, xm, &sh, dmetad.p, dmeta.p + 1, work.p, s);
+            if (!pen0.empty())
+                launch_sweep_list(X, dv.p, dgrad.p, dpen0.p, int64_t(pen0.size()), nullptr, dsc.p, xm, &sh, dmetad.p, dmeta.p + 1, work.p, s);
+            launch_sweep_list(X, dv.p, dgrad.p, dlist.p, cap, dmeta.p, dsc.p, xm, &sh, dmetad.p, dmeta.p + 1, work.p, s);
+            AHIP_CHECK(hipMemcpyAsync(meta, dmeta.p, sizeof(meta), hipMemcpyDeviceToHost, s));
+            AHIP_CHECK(hipStreamSynchronize(s));
+            list.resize(size_t(meta[0]));
+            if (meta[0] > 0) AHIP_CHECK(hipMemcpyAsync(list.data(), dlist.p, size_t(meta[0]) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            std::fill(exact, exact + p, uint8_t(0));
+        }
+        AHIP_CHECK(hipMemcpyAsync(grad, dgrad.p, size_t(p) * sizeof(double), hipMemcpyDeviceToHost, s));
+        AHIP_CHECK(hipStreamSynchronize(s));
+        if (route) {
+            for (int32_t c : scols) exact[c] = 1;
+            for (int32_t c : pen0) exact[c] = 1;
+            for (int32_t c : list) exact[c] = 1;
+            if (meta[1] & 2) adelie_hip_internal_shadow_mark_stale(d);
+        }
+        info[0] = meta[0]; info[1] = meta[1]; info[2] = route ? 1 : 0; info[3] = meta[2];
     } catch (const std::exception& e) {
         set_last_error(e.what());
         return 1;

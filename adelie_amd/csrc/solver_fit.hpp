@@ -75,10 +75,7 @@
             // Gaussian: the residual is final and current on the device -> enqueue the invariance sweep of this lambda now,
             // so that it runs while the host does the post-fit bookkeeping below (otherwise the GPU idles ~0.2 ms per lambda)
             if (!is_glm() && sc.status == CD_OK && r_dev == d_r.p && inv_wanted) {
-                launch_vmul<T>(d_w.p, d_r.p, d_v.p, n, st);
-                t_sweep.begin(st);
-                sweep(d_v.p, d_grad.p, nullptr, p, &d_blk.p->resid_sum, intercept ? d_xm.p : nullptr);
-                t_sweep.end(st);
+                invariance_sweep(lm, int(sc.active_size), &d_blk.p->resid_sum);
                 device_abs_grad(lm, int(sc.active_size));
                 grad_fresh = true;
                 inv_prelaunched = true;
@@ -144,10 +141,7 @@
         // update as well, ahead of the downloads and the host bookkeeping below (the panel engines did this above)
         if (small_fit && !is_glm() && !cov_mode && inv_wanted && sc.status == CD_OK && r_dev == d_r.p &&
             !multi()) {
-            launch_vmul<T>(d_w.p, d_r.p, d_v.p, n, st);
-            t_sweep.begin(st);
-            sweep(d_v.p, d_grad.p, nullptr, p, &d_sc.p->resid_sum, intercept ? d_xm.p : nullptr);
-            t_sweep.end(st);
+            invariance_sweep(lm, int(sc.active_size), &d_sc.p->resid_sum);
             device_abs_grad(lm, int(sc.active_size));
             grad_fresh = true;
             inv_prelaunched = true;

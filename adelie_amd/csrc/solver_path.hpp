@@ -64,6 +64,7 @@
             if (inv_prelaunched_lm == lm) {
                 if (!spec_active) sync(); // (pin_solve waited for the downloads; a full sync would wait for the speculative pass)
                 grad_valid = true;
+                filtered_sweep_arrived();
                 host_cons_abs_grad(lm);
                 return;
             }
@@ -85,15 +86,13 @@
             sweep(d_r.p, d_grad.p, nullptr, p, nullptr, nullptr); // resid already carries the weights
             t_sweep.end(st);
         } else {
-            launch_vmul<T>(d_w.p, d_r.p, d_v.p, n, st);
-            t_sweep.begin(st);
-            sweep(d_v.p, d_grad.p, nullptr, p, &d_sc.p->resid_sum, intercept ? d_xm.p : nullptr);
-            t_sweep.end(st);
+            invariance_sweep(lm, int(active_set_size), &d_sc.p->resid_sum);
             grad_valid = true;
             grad_fresh = true;
         }
         device_abs_grad(lm, int(active_set_size));
         sync();
+        filtered_sweep_arrived();
         host_cons_abs_grad(lm);
     }
 
@@ -243,12 +242,15 @@
                 t_host_screen += benchmark_screen.back();
                 t_host_screen_wait += t_sync_total - sync0;
                 spec_next_lm = (lmda_path_idx + 1 < L) ? lmda_path[lmda_path_idx + 1] : T(0);
+                inv_next_lm = spec_next_lm;
+                solve_active_size = current_active_size;
                 auto fo = fit_f(lmda_curr);
                 spec_next_lm = T(0);
                 benchmark_fit_screen.push_back(fo.t_screen);
                 benchmark_fit_active.push_back(fo.t_active);
                 sw.start();
                 update_invariance(lmda_curr);
+                inv_next_lm = T(0);
                 benchmark_invariance.push_back(sw.elapsed());
                 t_host[4] += benchmark_invariance.back();
                 sw.start();
@@ -281,7 +283,7 @@
         if (hooks.trace >= 2)
             std::fprintf(stderr, "[alloc] hipMalloc/hipFree so far in this process: %ld calls, %.1f ms\n", DevAllocStats::calls(),
                          DevAllocStats::seconds() * 1e3);
-        t_sweep.collect(); t_gram.collect(); t_cd.collect(); t_axpy.collect(); t_step.collect();
+        t_sweep.collect(); t_fsweep.collect(); t_gram.collect(); t_cd.collect(); t_axpy.collect(); t_step.collect();
         if (d_grp_dbg.p) {
             sync();
             d_grp_dbg.download(cd_dbg, 8, st);
@@ -315,6 +317,7 @@
     // host mirrors of the device-resident invariants (grad, resid, eta, screen_beta, screen_X_means, screen_vars); also what
     // adelie_hip_result_sync does for the live state inside a poll callback
     void download_invariants() {
+        ensure_exact_grad();
         spec_rollback();
         d_grad.download(grad.data(), size_t(p), st);
         if (!cov_mode) d_r.download(resid.data(), size_t(n), st);

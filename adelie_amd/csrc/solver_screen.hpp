@@ -341,6 +341,139 @@
         d_absgrad.download(abs_grad.data(), size_t(G), st);
     }
 
+    // ---- the filtered invariance sweep (kernels_sweep.hip: float32 shadow of a dense f64 design) ---------------------------
+    // A Gaussian lambda's full gradient is read exactly only for the screen set; every other group merely has to be placed
+    // below or above the thresholds that kkt() and screen() compare it with.  tstar is the smallest of them: a sweep of the
+    // shadow proves most groups below it, the rest are swept again in f64 (the bits of the full sweep).  Whoever needs every
+    // value exact (screen()'s sort of all G, the state handed back) calls ensure_exact_grad() first.
+    int fs_state = 0;              // 0: not asked yet, 1: the design has a shadow, -1: it has none / the route is off
+    ShadowView fs_shadow{};
+    bool grad_filtered = false;    // d_grad / abs_grad are exact for the screen set and the groups listed on the device only
+    T inv_next_lm = 0;             // set by solve(): the lambda that follows the one being fit if KKT passes (0: none)
+    int solve_active_size = 0;     // the active count of the last accepted lambda (solve()'s current_active_size)
+    int64_t screen_thr_count = 0;  // how many scores lay at or above screen_thr when it was set
+    T fs_lm = 0;
+    DevBuf<int32_t> d_fs_list, d_fs_meta, d_fs_pen0;
+    DevBuf<T> d_fs_part, d_fs_metad, d_fs_work, d_fs_v, d_fs_abs;
+    int64_t fs_pen0_cols = -1;
+    int32_t fs_meta[4] = {0, 0, 0, 0};
+    std::vector<T> fs_abs_host;
+    KTimer t_fsweep;
+    double fsweep_bytes = 0;
+    int64_t n_sweeps_filtered = 0, n_sweeps_refilled = 0, n_filter_exact_cols = 0, n_filter_shadow_cols = 0;
+    int64_t fs_pending_screen_cols = 0;
+    int64_t fs_cap() const { return filter_list_cap(int64_t(p)); }
+
+    // tstar for the sweep at lambda lm, or 0 when this sweep has to be the full one
+    T filter_threshold(T lm, int active_now) {
+        if constexpr (!std::is_same<T, double>::value) return T(0);
+        if (fs_state < 0 || !filter_sweep_on(hooks.filter_sweep)) return T(0);
+        if (!dense() || is_glm() || cov_mode || cons_on || multi() || std_generic() || batcher || D->factor() || has_pen2) return T(0);
+        FilterRule f; // (filter_host.hpp: the rule itself, free of device calls)
+        f.screen_rule = screen_rule == ADELIE_HIP_SCREEN_STRONG ? kFilterRuleStrong
+                        : screen_rule == ADELIE_HIP_SCREEN_PIVOT ? kFilterRulePivot : -1;
+        f.alpha = double(alpha); f.lm = double(lm); f.lm_next = double(inv_next_lm);
+        f.thr_valid = screen_thr_valid; f.screen_thr = double(screen_thr); f.thr_count = screen_thr_count;
+        f.G = int64_t(G); f.screen_size = int64_t(screen_set.size());
+        f.n_new_active = std::max(0, active_now - solve_active_size); // what the next screen() is told
+        f.subset_ratio = double(pivot_subset_ratio); f.subset_min = int64_t(pivot_subset_min); f.slack_ratio = double(pivot_slack_ratio);
+        const T tstar = T(filter_tstar(f));
+        if (!(tstar > 0)) return T(0);
+        if (fs_state == 0) fs_state = adelie_hip_internal_shadow_acquire(D, &fs_shadow) ? 1 : -1;
+        return fs_state == 1 ? tstar : T(0);
+    }
+
+    // v = W o r and the gradient of lambda lm into d_grad, behind whatever is on the stream: filtered when it may be
+    void invariance_sweep(T lm, int active_now, const T* rsum_dev) {
+        const T tstar = filter_threshold(lm, active_now);
+        if (!(tstar > 0)) {
+            launch_vmul<T>(d_w.p, d_r.p, d_v.p, n, st);
+            t_sweep.begin(st);
+            sweep(d_v.p, d_grad.p, nullptr, p, rsum_dev, intercept ? d_xm.p : nullptr);
+            t_sweep.end(st);
+            grad_filtered = false;
+            return;
+        }
+        if constexpr (std::is_same<T, double>::value) {
+            const T* xm = intercept ? d_xm.p : nullptr;
+            const int64_t cap = fs_cap();
+            if (fs_pen0_cols < 0) { // columns of the groups without a penalty: always exact
+                const std::vector<int32_t> c0 = filter_unpenalized_cols(groups, group_sizes, penalty);
+                fs_pen0_cols = int64_t(c0.size());
+                if (!c0.empty()) {
+                    d_fs_pen0.reserve(c0.size());
+                    d_fs_pen0.upload(c0.data(), c0.size(), st);
+                }
+            }
+            const int n_part = filter_norm_parts(n);
+            d_fs_part.reserve(size_t(n_part));
+            d_fs_meta.reserve(4);
+            d_fs_metad.reserve(2);
+            d_fs_list.reserve(size_t(cap));
+            const int64_t wl = sweep_list_work_elems(n, p, std::max<int64_t>(std::max<int64_t>(cap, nv), fs_pen0_cols));
+            d_fs_work.reserve(size_t(std::max<int64_t>(wl, shadow_sweep_work_elems(n, p))));
+            const DenseView<T> X = D->dense<T>();
+            t_fsweep.begin(st);
+            AHIP_CHECK(hipMemsetAsync(d_fs_meta.p, 0, 4 * sizeof(int32_t), st));
+            launch_vmul_sq(d_w.p, d_r.p, d_v.p, n, d_fs_part.p, st);
+            launch_shadow_sweep(fs_shadow, d_v.p, d_grad.p, rsum_dev, xm, d_fs_work.p, st);
+            launch_filter_classify(d_grad.p, d_groups.p, d_gsizes.p, G, d_slot.p, d_penalty.p, tstar, fs_shadow, d_fs_part.p, n_part,
+                                   rsum_dev, d_fs_list.p, cap, d_fs_meta.p, d_fs_metad.p, st);
+            if (nv > 0)
+                launch_sweep_list(X, d_v.p, d_grad.p, d_vcol.p, nv, nullptr, rsum_dev, xm, &fs_shadow, d_fs_metad.p, d_fs_meta.p + 1,
+                                  d_fs_work.p, st);
+            if (fs_pen0_cols > 0)
+                launch_sweep_list(X, d_v.p, d_grad.p, d_fs_pen0.p, fs_pen0_cols, nullptr, rsum_dev, xm, &fs_shadow, d_fs_metad.p,
+                                  d_fs_meta.p + 1, d_fs_work.p, st);
+            launch_sweep_list(X, d_v.p, d_grad.p, d_fs_list.p, cap, d_fs_meta.p, rsum_dev, xm, &fs_shadow, d_fs_metad.p,
+                              d_fs_meta.p + 1, d_fs_work.p, st);
+            t_fsweep.end(st);
+            d_fs_meta.download(fs_meta, 4, st);
+            grad_filtered = true;
+            fs_lm = lm;
+            fs_pending_screen_cols = int64_t(nv) + std::max<int64_t>(fs_pen0_cols, 0);
+            ++n_sweeps_filtered;
+        }
+    }
+
+    // after the host has the downloads of a filtered sweep: its counters, and the full sweep when the list overflowed or a
+    // column swept both ways left its bound (the design was modified after the shadow was made)
+    void filtered_sweep_arrived() {
+        if (!grad_filtered) return;
+        const int64_t exact = fs_pending_screen_cols + fs_meta[0];
+        n_filter_exact_cols += exact;
+        n_filter_shadow_cols += int64_t(p);
+        fsweep_bytes += double(n) * (double(exact) * 8.0 + double(p) * 4.0);
+        const FilterFollowUp fu = filter_follow_up(fs_meta[1]);
+        if (fu.retire) {
+            adelie_hip_internal_shadow_mark_stale(D);
+            fs_state = -1;
+        }
+        if (fu.refill) ensure_exact_grad();
+    }
+
+    // today's full sweep on the residual the filtered sweep saw: every entry of d_grad / grad-derived abs_grad exact again
+    void ensure_exact_grad() {
+        if (!grad_filtered) return;
+        grad_filtered = false;
+        ++n_sweeps_refilled;
+        const T* rsrc = spec_active ? d_r_snap.p : d_r.p;
+        d_fs_v.reserve(size_t(n));
+        d_fs_abs.reserve(size_t(G));
+        launch_vmul<T>(d_w.p, rsrc, d_fs_v.p, n, st);
+        t_sweep.begin(st);
+        sweep(d_fs_v.p, d_grad.p, nullptr, p, d_fs_metad.p + 1, intercept ? d_xm.p : nullptr);
+        t_sweep.end(st);
+        // the groups outside the screen set only: a speculative pass in flight has moved the coefficients of the others, and
+        // theirs were exact already
+        launch_abs_grad<T>(d_grad.p, d_groups.p, d_gsizes.p, G, d_slot.p, d_beta.p, d_penalty.p, (1 - alpha) * fs_lm, d_fs_abs.p, st);
+        fs_abs_host.resize(size_t(G));
+        d_fs_abs.download(fs_abs_host.data(), size_t(G), st);
+        sync();
+        for (idx g = 0; g < G; ++g)
+            if (!is_screen(g)) abs_grad[g] = fs_abs_host[size_t(g)];
+    }
+
     int64_t n_host_screens = 0;
 
     // solver_base.hpp:120-153
@@ -893,6 +1026,7 @@
                     partial = int64_t(keyed.size()) >= need;
                 }
                 if (!partial) {
+                    ensure_exact_grad(); // (every score is read)
                     keyed.resize(size_t(Gi));
                     for (int i = 0; i < Gi; ++i) keyed[size_t(i)] = std::make_pair(score(i), idx(i));
                 }
@@ -906,6 +1040,7 @@
                     const int64_t depth = std::min<int64_t>(2 * need, M);
                     screen_thr = keyed[size_t(M - depth)].first;
                     screen_thr_valid = depth >= need;
+                    screen_thr_count = depth;
                 }
                 std::vector<T> sub(subset_size), mses(subset_size), ind(subset_size);
                 for (int i = 0; i < subset_size; ++i) {

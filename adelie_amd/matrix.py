@@ -165,6 +165,19 @@ class _NativeMatrix:
         self._backend.check(self._backend.fn("design_batch_stats")(self._handle, out))
         return {"launches": int(out[0]), "vectors": int(out[1]), "ms": float(out[2])}
 
+    def drop_shadow(self):
+        """Frees the float32 shadow copy that the filtered invariance sweep of a Gaussian path reads (dense f64 designs; made
+        on the first eligible solve and shared with the aliases).  Call it after modifying the memory of an adopted tensor,
+        with no solve in flight; the next eligible solve makes the copy again."""
+        self._backend.check(self._backend.fn("design_drop_shadow")(self._handle))
+
+    def shadow_stats(self):
+        """``{"state", "builds", "ineligible"}`` of the float32 shadow copy (state 0: none, 1: built, -1: the design cannot
+        have one -- an entry float32 cannot hold, too little free memory, or a failed staleness check)."""
+        out = (_abi.C.c_int64 * 3)()
+        self._backend.check(self._backend.fn("design_shadow_stats")(self._handle, out))
+        return {"state": int(out[0]), "builds": int(out[1]), "ineligible": int(out[2])}
+
     def impute(self):
         """The ``(p,)`` impute values of an SNP design (what a missing call contributes)."""
         out = np.empty(self._cols, dtype=np.float64)
@@ -717,7 +730,9 @@ def dense(mat, *, method: str = "naive", copy: bool = False, n_threads: int = 1,
     ----------
     mat : (n, p) ndarray or torch.Tensor
         float32/float64 matrix.  A numpy array is copied to HBM once.  A CUDA(ROCm) torch tensor is
-        adopted in place (no copy); it must be F- or C-contiguous and is kept alive by the handle.
+        adopted in place (no copy); it must be F- or C-contiguous and is kept alive by the handle.  An adopted tensor must
+        not be modified while the handle lives: a float64 design keeps a float32 copy of itself for the invariance sweeps of
+        Gaussian paths (``drop_shadow()`` after a modification has the copy made again).
     method : str
         Only ``"naive"`` is on the hot path.
     n_threads : int

@@ -201,6 +201,12 @@ int adelie_hip_design_create_interaction(adelie_hip_design* Z, const int64_t* pa
 int64_t adelie_hip_design_factor_groups(const adelie_hip_design* d, int64_t* groups, int64_t* group_sizes, int64_t cap);
 /* Copies the (p,) impute vector of an SNP design (as double). */
 int adelie_hip_design_impute(adelie_hip_design* d, double* out);
+/* The float32 shadow that the filtered invariance sweep reads (made on the first eligible solve, shared with the aliases) is
+ * freed; the next eligible solve makes it again.  To be called after the memory of an adopted tensor was modified, and with
+ * no solve in flight on the design or its aliases.  shadow_stats: out[3] = {state (0 none, 1 built, -1 ineligible), builds,
+ * times found ineligible (an entry float32 cannot hold, memory, a failed staleness check)}. */
+int adelie_hip_design_drop_shadow(adelie_hip_design* d);
+int adelie_hip_design_shadow_stats(adelie_hip_design* d, int64_t* out);
 int adelie_hip_design_destroy(adelie_hip_design* d);
 
 /* cv_grpnet post-processing on the device (adelie/cv.py:296-312, diagnostic.py:30-121): for the L
@@ -562,6 +568,11 @@ enum adelie_hip_scalar {
     ADELIE_HIP_S_N_DEV_CONS_VISITS,  /* ... and by the device kernel (box / one-sided objects, kernels_cons.hip) */
     ADELIE_HIP_S_N_SWEEPS_FACTOR,    /* ABI 12: full-gradient sweeps of a one-hot / interaction design answered by the structured
                                         kernel (kernels_factor.hip: read off Z, not off the expanded matrix) */
+    /* the filtered invariance sweep (float32 shadow of a dense f64 design, ADELIE_HIP_FILTER_SWEEP): */
+    ADELIE_HIP_S_N_SWEEPS_FILTERED,  /* invariance sweeps answered by the shadow sweep + exact sweeps of the columns it left open */
+    ADELIE_HIP_S_N_SWEEPS_REFILLED,  /* ... of which were followed by the full sweep after all (every value had to be exact) */
+    ADELIE_HIP_S_N_FILTER_EXACT_COLS,  /* columns the filtered sweeps read in f64 */
+    ADELIE_HIP_S_N_FILTER_SHADOW_COLS, /* columns the filtered sweeps read from the shadow */
     /* HIP-event time (ms) of the device phases on the design's stream, summed over the solve, and launch counts */
     ADELIE_HIP_S_T_SWEEP_MS = 80, ADELIE_HIP_S_T_GRAM_MS, ADELIE_HIP_S_T_CD_MS, ADELIE_HIP_S_T_AXPY_MS,
     ADELIE_HIP_S_N_SWEEP_LAUNCHES, ADELIE_HIP_S_N_GRAM_LAUNCHES, ADELIE_HIP_S_T_HOST_SCREEN_MS,
@@ -569,7 +580,10 @@ enum adelie_hip_scalar {
     ADELIE_HIP_S_T_PANEL_STEP_MS, ADELIE_HIP_S_N_PANEL_STEP_LAUNCHES,
     /* the part of T_HOST_SCREEN_MS the host spent waiting for the device (stream / event synchronisation) rather than
      * computing the screening rule, the appends and the launches of the new groups' variances */
-    ADELIE_HIP_S_T_HOST_SCREEN_WAIT_MS
+    ADELIE_HIP_S_T_HOST_SCREEN_WAIT_MS,
+    /* the filtered invariance sweeps as a whole (T_SWEEP_MS / N_SWEEP_LAUNCHES count the launches that read the whole f64
+     * design only): time, count, and the design bytes they asked for */
+    ADELIE_HIP_S_T_FSWEEP_MS, ADELIE_HIP_S_N_FSWEEP_LAUNCHES, ADELIE_HIP_S_FSWEEP_BYTES
 };
 int64_t     adelie_hip_result_size(const adelie_hip_result* r, int which);
 /* Copies min(size, cap) elements: value vectors as double, index vectors as int64. */
@@ -691,6 +705,14 @@ const char* adelie_hip_bvls_result_error(const adelie_hip_bvls_result* r);
  * On a one-hot / interaction design it times the route ADELIE_HIP_FACTOR_SWEEP selects (read at the call).
  * ------------------------------------------------------------------------------------------ */
 int adelie_hip_bench_sweep(adelie_hip_design* d, int64_t reps, double* ms_per_launch);
+/* One filtered invariance sweep on a dense f64 design (tests): v = w o r, the float32 shadow sweep, the classification of the
+ * groups outside `screen_groups` against tstar * penalty, the exact f64 sweeps of the columns left open.  grad (p), exact (p
+ * bytes: 1 where the value is bit for bit the full sweep's), info[4] = {columns listed, flags (1: more than max(1024, p/4)
+ * columns were wanted, 2: a column swept both ways left its bound), 1 if the route ran / 0 if the plain full sweep answered
+ * (ADELIE_HIP_FILTER_SWEEP=0, a design without a shadow), columns wanted}. */
+int adelie_hip_filter_sweep_test(adelie_hip_design* d, const double* w, const double* r, double sub_scale, const double* sub_vec,
+                                 const int64_t* screen_groups, int64_t n_screen, const int64_t* groups, const int64_t* group_sizes,
+                                 int64_t G, const double* penalty, double tstar, double* grad, uint8_t* exact, int64_t* info);
 
 #ifdef __cplusplus
 }
