@@ -442,8 +442,17 @@ struct DevBuf {
 struct adelie_hip_design {
     int dtype = ADELIE_HIP_F64;
     int device = 0;
-    int kind = 0; // 0 dense, 1 snp (2-bit), 2 multi-response view of a dense or 2-bit design (adelie_hip_design_create_multi),
-                  // 3 sparse kept sparse (adelie_hip_design_create_csc: CSC + CSR copies of the entries, kernels_sparse.hip)
+    // storage kinds: dense, snp (2-bit), multi-response view of a dense or 2-bit design (adelie_hip_design_create_multi),
+    // sparse kept sparse (adelie_hip_design_create_csc: CSC + CSR copies of the entries, kernels_sparse.hip)
+    enum : int { kDense = 0, kSnp = 1, kMulti = 2, kCsc = 3 };
+    int kind = kDense;
+    bool is_dense() const { return kind == kDense; }
+    bool is_snp() const { return kind == kSnp; }
+    bool is_multi() const { return kind == kMulti; }
+    bool is_csc() const { return kind == kCsc; }
+    // standardized view over a dense or 2-bit design (adelie_hip_design_create_standardized): the base kernels run on the raw
+    // matrix, centring and scaling are applied around them; a view over compressed columns applies them inside its kernels
+    bool is_std_view() const { return std_center != nullptr && kind != kCsc; }
     // covariance-method matrix A (adelie_hip_design_create_cov_dense): a dense (p, p) design with n == p that only
     // adelie_hip_gaussian_cov_solve and the cov_* operations accept; cov == 2: the stored matrix is A^T (row-major input)
     int cov = 0;

@@ -2,7 +2,9 @@
 // (include/adelie_hip.h documents which reference method each entry point replaces.)
 #include <atomic>
 #include <cstdio>
+#include <memory>
 #include "common.hpp"
+#include "design_ops.hpp"
 
 #include <mutex>
 
@@ -123,9 +125,21 @@ adelie_hip_design* new_design(int64_t n, int64_t p, int dtype, int device) {
     return d;
 }
 
+// Owns a design under construction: a create entry point that throws destroys what it has built so far, one that succeeds
+// hands the design over with release().
+struct DesignDeleter {
+    void operator()(adelie_hip_design* d) const { adelie_hip_design_destroy(d); }
+};
+using DesignGuard = std::unique_ptr<adelie_hip_design, DesignDeleter>;
+// a temporary device block, freed on every way out
+struct DevTmp {
+    void* p = nullptr;
+    ~DevTmp() { (void)hipFree(p); }
+};
+
 void create_snp_from_calldata(adelie_hip_design* d, const int8_t* calldata, const double* impute) {
     const int64_t n = d->n, p = d->p;
-    d->kind = 1;
+    d->kind = adelie_hip_design::kSnp;
     d->ldb = (((n + 3) / 4 + 127) / 128) * 128;
     AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bits), size_t(d->ldb) * size_t(p)));
     int8_t* tmp = nullptr;
@@ -159,23 +173,14 @@ void op_sweep(adelie_hip_design* d, int64_t c0, int64_t ncols, const T* v, const
     T* dv = scratch<T>(d->s_n1, n);
     T* dw = scratch<T>(d->s_n2, n);
     T* dout = scratch<T>(d->s_p1, ncols);
-    T* work = scratch<T>(d->s_work, sweep_work_elems(n, ncols));
+    const bool structured = raw_sweep_structured(*d, c0, ncols, nullptr, square, Hooks::factor_sweep_env());
+    T* work = scratch<T>(d->s_work, size_t(raw_sweep_work_elems(*d, ncols, structured)));
     AHIP_CHECK(hipMemcpyAsync(dv, v, n * sizeof(T), hipMemcpyHostToDevice, s));
     if (w) {
         AHIP_CHECK(hipMemcpyAsync(dw, w, n * sizeof(T), hipMemcpyHostToDevice, s));
         launch_vmul<T>(dv, dw, dv, n, s);
     }
-    if (d->kind == 0 && d->factor() && c0 == 0 && ncols == d->p && !square && factor_sweep_on(Hooks::factor_sweep_env()))
-        launch_sweep_factor<T>(d->factor_view<T>(), dv, dout, nullptr, nullptr,
-                               scratch<T>(d->s_misc, size_t(factor_sweep_work_elems(n, d->p, d->f_nchunk))), s);
-    else if (d->kind == 0)
-        launch_sweep<T>(d->dense<T>(), dv, dout, c0, ncols, nullptr, nullptr, nullptr, square, work, s);
-    else if (d->kind == 3)
-        launch_sweep_csc<T>(d->csc<T>(), dv, dout, c0, ncols, nullptr, nullptr, nullptr, square,
-                            scratch<T>(d->s_misc, size_t(sweep_work_elems_csc(d->sp_parts(), ncols))), s);
-    else
-        launch_sweep_snp<T>(d->snp(), static_cast<const T*>(d->impute), dv, dout, c0, ncols, nullptr, nullptr, nullptr,
-                            square, work, s);
+    raw_sweep<T>(*d, dv, dout, c0, ncols, nullptr, nullptr, nullptr, square, structured, work, s);
     AHIP_CHECK(hipMemcpyAsync(out, dout, ncols * sizeof(T), hipMemcpyDeviceToHost, s));
     AHIP_CHECK(hipStreamSynchronize(s));
 }
@@ -188,14 +193,13 @@ void op_mul_batch(adelie_hip_design* d, const T* V, int64_t L, T* out) {
     hipStream_t s = d->stream;
     const int64_t n = d->n, p = d->p;
     constexpr int64_t KB = 8;
-    const bool is_dense = d->kind == 0;
-    if (d->kind == 3) { // sparse: one pass over the stored entries per vector
+    if (d->is_csc()) { // sparse: one pass over the stored entries per vector
         T* dv1 = scratch<T>(d->s_n1, size_t(n));
         T* dout1 = scratch<T>(d->s_p1, size_t(p));
+        T* work1 = scratch<T>(d->s_work, size_t(raw_sweep_work_elems(*d, p, false)));
         for (int64_t l = 0; l < L; ++l) {
             AHIP_CHECK(hipMemcpyAsync(dv1, V + l * n, size_t(n) * sizeof(T), hipMemcpyHostToDevice, s));
-            launch_sweep_csc<T>(d->csc<T>(), dv1, dout1, 0, p, nullptr, nullptr, nullptr, false,
-                                scratch<T>(d->s_misc, size_t(sweep_work_elems_csc(d->sp_parts(), p))), s);
+            raw_sweep<T>(*d, dv1, dout1, 0, p, nullptr, nullptr, nullptr, false, false, work1, s);
             AHIP_CHECK(hipMemcpyAsync(out + l * p, dout1, size_t(p) * sizeof(T), hipMemcpyDeviceToHost, s));
             AHIP_CHECK(hipStreamSynchronize(s));
         }
@@ -206,24 +210,22 @@ void op_mul_batch(adelie_hip_design* d, const T* V, int64_t L, T* out) {
     // one work buffer for both kernels (a lone last vector goes through the single-vector sweep); the K-wide sweep's
     // work size only depends on (n, p, K)
     const MultiView<T> shape{nullptr, n, p, n, nullptr, int32_t(KB), 0};
-    T* work = scratch<T>(d->s_work, std::max<size_t>(size_t(sweep_work_elems(n, p)), size_t(multi_sweep_work_elems<T>(shape))));
+    T* work = scratch<T>(d->s_work, std::max<size_t>(size_t(raw_sweep_work_elems(*d, p, false)), size_t(multi_sweep_work_elems<T>(shape))));
     std::vector<T> hout(size_t(KB) * size_t(p));
     for (int64_t l0 = 0; l0 < L; l0 += KB) {
         const int64_t K = std::min(KB, L - l0);
         AHIP_CHECK(hipMemcpyAsync(dv, V + l0 * n, size_t(K) * size_t(n) * sizeof(T), hipMemcpyHostToDevice, s));
         if (K == 1) {
-            if (is_dense) launch_sweep<T>(d->dense<T>(), dv, dout, 0, p, nullptr, nullptr, nullptr, false, work, s);
-            else launch_sweep_snp<T>(d->snp(), static_cast<const T*>(d->impute), dv, dout, 0, p, nullptr, nullptr, nullptr, false,
-                                     work, s);
+            raw_sweep<T>(*d, dv, dout, 0, p, nullptr, nullptr, nullptr, false, false, work, s);
             AHIP_CHECK(hipMemcpyAsync(out + l0 * p, dout, size_t(p) * sizeof(T), hipMemcpyDeviceToHost, s));
             AHIP_CHECK(hipStreamSynchronize(s));
             continue;
         }
-        if (is_dense) {
+        if (d->is_dense()) {
             const DenseView<T> X = d->dense<T>();
             launch_multi_sweep<T>(MultiView<T>{X.X, n, p, X.ld, nullptr, int32_t(K), 0}, dv, dout, work, s);
         } else {
-            launch_multi_sweep_snp<T>(d->snp(), static_cast<const T*>(d->impute), int(K), dv, dout, work, s);
+            launch_multi_sweep_snp<T>(d->snp(), snp_impute<T>(*d), int(K), dv, dout, work, s);
         }
         AHIP_CHECK(hipMemcpyAsync(hout.data(), dout, size_t(K) * size_t(p) * sizeof(T), hipMemcpyDeviceToHost, s));
         AHIP_CHECK(hipStreamSynchronize(s));
@@ -247,15 +249,12 @@ void op_axpy(adelie_hip_design* d, int64_t j, int64_t q, const T* coef, T* out) 
     AHIP_CHECK(hipMemcpyAsync(dout, out, n * sizeof(T), hipMemcpyHostToDevice, s));
     AHIP_CHECK(hipMemcpyAsync(dcoef, coef, q * sizeof(T), hipMemcpyHostToDevice, s));
     AHIP_CHECK(hipMemcpyAsync(dcols, cols.data(), q * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (d->kind == 0) {
-        launch_axpy_cols<T>(d->dense<T>(), dcols, dcoef, nullptr, int32_t(q), T(1), dout, s);
-    } else if (d->kind == 3) {
-        T* delta = scratch<T>(d->s_misc, size_t(d->p) + 8);
+    T* delta = nullptr;
+    if (d->is_csc()) {
+        delta = scratch<T>(d->s_misc, size_t(d->p) + 8);
         AHIP_CHECK(hipMemsetAsync(delta, 0, (size_t(d->p) + 8) * sizeof(T), s));
-        launch_axpy_cols_csc<T>(d->csc<T>(), dcols, dcoef, nullptr, int32_t(q), T(1), dout, delta, s);
-    } else {
-        launch_axpy_cols_snp<T>(d->snp(), static_cast<const T*>(d->impute), dcols, dcoef, nullptr, int32_t(q), T(1), dout, s);
     }
+    raw_axpy_cols<T>(*d, dcols, dcoef, nullptr, int32_t(q), T(1), dout, delta, s);
     AHIP_CHECK(hipMemcpyAsync(out, dout, n * sizeof(T), hipMemcpyDeviceToHost, s));
     AHIP_CHECK(hipStreamSynchronize(s));
 }
@@ -267,20 +266,14 @@ void op_cov(adelie_hip_design* d, int64_t j, int64_t q, const T* sw, T* out) {
     const int64_t n = d->n;
     T* dw = scratch<T>(d->s_n1, n);
     T* dC = scratch<T>(d->s_p1, q * q);
-    T* work = scratch<T>(d->s_work, d->kind == 3 ? gram_work_elems_csc(n, q, q, d->sp_parts()) : gram_work_elems(n, q, q));
+    T* work = scratch<T>(d->s_work, size_t(raw_gram_work_elems(*d, n, q, q)));
     int32_t* dcols = scratch<int32_t>(d->s_idx1, q);
     std::vector<int32_t> cols(q);
     for (int64_t k = 0; k < q; ++k) cols[k] = int32_t(j + k);
     AHIP_CHECK(hipMemcpyAsync(dw, sw, n * sizeof(T), hipMemcpyHostToDevice, s));
     launch_vmul<T>(dw, dw, dw, n, s); // weights = sqrt_weights^2
     AHIP_CHECK(hipMemcpyAsync(dcols, cols.data(), q * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (d->kind == 0)
-        launch_gram<T>(d->dense<T>(), dw, dcols, int32_t(q), 0, dcols, int32_t(q), 0, nullptr, false, dC, q, work, s);
-    else if (d->kind == 3)
-        launch_gram_csc<T>(d->csc<T>(), dw, dcols, int32_t(q), 0, dcols, int32_t(q), 0, nullptr, false, dC, q, work, s);
-    else
-        launch_gram_snp<T>(d->snp(), static_cast<const T*>(d->impute), dw, dcols, int32_t(q), 0, dcols, int32_t(q), 0,
-                           nullptr, false, dC, q, work, s);
+    raw_gram<T>(*d, dw, dcols, int32_t(q), 0, dcols, int32_t(q), 0, nullptr, false, dC, q, work, s);
     AHIP_CHECK(hipMemcpyAsync(out, dC, q * q * sizeof(T), hipMemcpyDeviceToHost, s));
     AHIP_CHECK(hipStreamSynchronize(s));
 }
@@ -307,21 +300,59 @@ static void cov_lazy_t(adelie_hip_design* X, adelie_hip_design* A) {
     cols.reserve(size_t(p));
     ones.upload(h1.data(), size_t(n), s);
     cols.upload(hc.data(), size_t(p), s);
-    work.reserve(size_t(X->kind == 3 ? gram_work_elems_csc(n, p, std::min<int64_t>(p, PANEL), X->sp_parts())
-                                     : gram_work_elems(n, p, std::min<int64_t>(p, PANEL))));
+    work.reserve(size_t(raw_gram_work_elems(*X, n, p, std::min<int64_t>(p, PANEL))));
     for (int64_t c0 = 0; c0 < p; c0 += PANEL) {
         const int64_t nc = std::min<int64_t>(PANEL, p - c0);
-        if (X->kind == 0)
-            launch_gram<T>(X->dense<T>(), ones.p, cols.p, int32_t(p), 0, cols.p + c0, int32_t(nc), int32_t(c0), nullptr, false, C, ld,
-                           work.p, s);
-        else if (X->kind == 3)
-            launch_gram_csc<T>(X->csc<T>(), ones.p, cols.p, int32_t(p), 0, cols.p + c0, int32_t(nc), int32_t(c0), nullptr, false, C,
-                               ld, work.p, s);
-        else
-            launch_gram_snp<T>(X->snp(), static_cast<const T*>(X->impute), ones.p, cols.p, int32_t(p), 0, cols.p + c0, int32_t(nc),
-                               int32_t(c0), nullptr, false, C, ld, work.p, s);
+        raw_gram<T>(*X, ones.p, cols.p, int32_t(p), 0, cols.p + c0, int32_t(nc), int32_t(c0), nullptr, false, C, ld, work.p, s);
     }
     AHIP_CHECK(hipStreamSynchronize(s));
+}
+
+// The CSR operand of sp_tmul and the loss paths on the device: indptr (rows + 1) in s_idx1, indices in s_idx2, the values at the
+// front of s_p1 with room for `extra` more elements behind them.
+template <class T>
+struct DevCsr {
+    int64_t *ptr, *ind;
+    T* val;
+};
+template <class T>
+DevCsr<T> upload_csr(adelie_hip_design* d, int64_t rows, const int64_t* indptr, const int64_t* indices, const T* values,
+                     size_t extra = 0) {
+    hipStream_t s = d->stream;
+    const int64_t nnz = indptr[rows];
+    DevCsr<T> A{scratch<int64_t>(d->s_idx1, rows + 1), scratch<int64_t>(d->s_idx2, nnz), scratch<T>(d->s_p1, size_t(nnz) + extra)};
+    AHIP_CHECK(hipMemcpyAsync(A.ptr, indptr, (rows + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    if (nnz) {
+        AHIP_CHECK(hipMemcpyAsync(A.ind, indices, nnz * sizeof(int64_t), hipMemcpyHostToDevice, s));
+        AHIP_CHECK(hipMemcpyAsync(A.val, values, nnz * sizeof(T), hipMemcpyHostToDevice, s));
+    }
+    return A;
+}
+// eta = V X^T for the L groups of K consecutive CSR rows each, a panel of at most ~1 GiB of eta (s_misc) at a time:
+// per_panel(l0, lc, eta) follows the sp_tmul of groups [l0, l0 + lc) on the design's stream (the csc form works in s_work).
+template <class T, class F>
+void for_each_eta_panel(adelie_hip_design* d, const DevCsr<T>& A, int64_t L, int64_t K, F&& per_panel) {
+    const int64_t len = d->n * K;
+    const int64_t Lp = std::max<int64_t>(1, (int64_t(1) << 30) / int64_t(len * sizeof(T)));
+    T* eta = scratch<T>(d->s_misc, size_t(std::min(Lp, L)) * len);
+    const int64_t wn = raw_sp_tmul_work_elems(*d);
+    T* work = wn ? scratch<T>(d->s_work, size_t(wn)) : nullptr;
+    for (int64_t l0 = 0; l0 < L; l0 += Lp) {
+        const int64_t lc = std::min(Lp, L - l0);
+        raw_sp_tmul<T>(*d, lc * K, A.ptr + l0 * K, A.ind, A.val, eta, work, d->stream);
+        per_panel(l0, lc, eta);
+    }
+}
+// the (loss under wa, loss under wb) pairs of L fits, left on the device by the loss kernels -> out[0..L) and out[L..2L)
+template <class T>
+void download_loss_pairs(adelie_hip_design* d, const T* dres, int64_t L, double* out) {
+    std::vector<T> res(size_t(2) * L);
+    AHIP_CHECK(hipMemcpyAsync(res.data(), dres, res.size() * sizeof(T), hipMemcpyDeviceToHost, d->stream));
+    AHIP_CHECK(hipStreamSynchronize(d->stream));
+    for (int64_t l = 0; l < L; ++l) {
+        out[l] = double(res[2 * l]);
+        out[L + l] = double(res[2 * l + 1]);
+    }
 }
 
 template <class T>
@@ -329,27 +360,11 @@ void op_sp_tmul(adelie_hip_design* d, int64_t L, const int64_t* indptr, const in
     set_device(d);
     hipStream_t s = d->stream;
     const int64_t n = d->n;
-    const int64_t nnz = indptr[L];
-    int64_t* dptr = scratch<int64_t>(d->s_idx1, L + 1);
-    int64_t* dind = scratch<int64_t>(d->s_idx2, nnz);
-    T* dval = scratch<T>(d->s_p1, nnz);
-    AHIP_CHECK(hipMemcpyAsync(dptr, indptr, (L + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    if (nnz) {
-        AHIP_CHECK(hipMemcpyAsync(dind, indices, nnz * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        AHIP_CHECK(hipMemcpyAsync(dval, values, nnz * sizeof(T), hipMemcpyHostToDevice, s));
-    }
-    // bound the device output panel to ~1 GiB
-    const int64_t Lp = std::max<int64_t>(1, (int64_t(1) << 30) / int64_t(n * sizeof(T)));
-    T* dout = scratch<T>(d->s_misc, size_t(std::min(Lp, L)) * n);
-    for (int64_t l0 = 0; l0 < L; l0 += Lp) {
-        const int64_t lc = std::min(Lp, L - l0);
-        if (d->kind == 0) launch_sp_tmul<T>(d->dense<T>(), lc, dptr + l0, dind, dval, dout, s);
-        else if (d->kind == 3)
-            launch_sp_tmul_csc<T>(d->csc<T>(), lc, dptr + l0, dind, dval, dout, scratch<T>(d->s_work, sp_tmul_work_elems_csc(d->p)), s);
-        else launch_sp_tmul_snp<T>(d->snp(), static_cast<const T*>(d->impute), lc, dptr + l0, dind, dval, dout, s);
-        AHIP_CHECK(hipMemcpyAsync(out + l0 * n, dout, size_t(lc) * n * sizeof(T), hipMemcpyDeviceToHost, s));
+    const DevCsr<T> A = upload_csr<T>(d, L, indptr, indices, values);
+    for_each_eta_panel<T>(d, A, L, 1, [&](int64_t l0, int64_t lc, const T* eta) {
+        AHIP_CHECK(hipMemcpyAsync(out + l0 * n, eta, size_t(lc) * n * sizeof(T), hipMemcpyDeviceToHost, s));
         AHIP_CHECK(hipStreamSynchronize(s));
-    }
+    });
 }
 
 } // namespace
@@ -371,15 +386,7 @@ void op_path_losses(adelie_hip_design* d, int kind, int64_t L, const int64_t* in
     set_device(d);
     hipStream_t s = d->stream;
     const int64_t n = d->n;
-    const int64_t nnz = indptr[L];
-    int64_t* dptr = scratch<int64_t>(d->s_idx1, L + 1);
-    int64_t* dind = scratch<int64_t>(d->s_idx2, nnz);
-    T* dval = scratch<T>(d->s_p1, nnz);
-    AHIP_CHECK(hipMemcpyAsync(dptr, indptr, (L + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    if (nnz) {
-        AHIP_CHECK(hipMemcpyAsync(dind, indices, nnz * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        AHIP_CHECK(hipMemcpyAsync(dval, values, nnz * sizeof(T), hipMemcpyHostToDevice, s));
-    }
+    const DevCsr<T> A = upload_csr<T>(d, L, indptr, indices, values);
     // n-vectors y, wa, wb, offsets and the reduction scratch share one buffer
     const size_t SUMS = 16 + 4 * 256;
     T* vec = scratch<T>(d->s_n1, size_t(4) * n + SUMS + size_t(2) * L);
@@ -388,26 +395,13 @@ void op_path_losses(adelie_hip_design* d, int kind, int64_t L, const int64_t* in
     AHIP_CHECK(hipMemcpyAsync(dwa, wa, n * sizeof(T), hipMemcpyHostToDevice, s));
     AHIP_CHECK(hipMemcpyAsync(dwb, wb, n * sizeof(T), hipMemcpyHostToDevice, s));
     AHIP_CHECK(hipMemcpyAsync(doff, offsets, n * sizeof(T), hipMemcpyHostToDevice, s));
-    const int64_t Lp = std::max<int64_t>(1, (int64_t(1) << 30) / int64_t(n * sizeof(T)));
-    T* dout = scratch<T>(d->s_misc, size_t(std::min(Lp, L)) * n);
-    for (int64_t l0 = 0; l0 < L; l0 += Lp) {
-        const int64_t lc = std::min(Lp, L - l0);
-        if (d->kind == 0) launch_sp_tmul<T>(d->dense<T>(), lc, dptr + l0, dind, dval, dout, s);
-        else if (d->kind == 3)
-            launch_sp_tmul_csc<T>(d->csc<T>(), lc, dptr + l0, dind, dval, dout, scratch<T>(d->s_work, sp_tmul_work_elems_csc(d->p)), s);
-        else launch_sp_tmul_snp<T>(d->snp(), static_cast<const T*>(d->impute), lc, dptr + l0, dind, dval, dout, s);
+    for_each_eta_panel<T>(d, A, L, 1, [&](int64_t l0, int64_t lc, const T* eta) {
         for (int64_t l = 0; l < lc; ++l) {
-            launch_glm_loss2<T>(kind, dy, dwa, dwb, dout + l * n, intercepts[l0 + l], doff, n, sums, s);
+            launch_glm_loss2<T>(kind, dy, dwa, dwb, eta + l * n, intercepts[l0 + l], doff, n, sums, s);
             AHIP_CHECK(hipMemcpyAsync(dres + 2 * (l0 + l), sums, 2 * sizeof(T), hipMemcpyDeviceToDevice, s));
         }
-    }
-    std::vector<T> res(size_t(2) * L);
-    AHIP_CHECK(hipMemcpyAsync(res.data(), dres, res.size() * sizeof(T), hipMemcpyDeviceToHost, s));
-    AHIP_CHECK(hipStreamSynchronize(s));
-    for (int64_t l = 0; l < L; ++l) {
-        out[l] = double(res[2 * l]);
-        out[L + l] = double(res[2 * l + 1]);
-    }
+    });
+    download_loss_pairs<T>(d, dres, L, out);
 }
 
 // The same for multi-response fits on the base design `d`: row l of the CSR is a coefficient vector over the view columns
@@ -448,15 +442,8 @@ void op_multi_path_losses(adelie_hip_design* d, int kind, int K, int64_t L, cons
             ym[size_t(k) * n + i] = y[i * K + k];
             om[size_t(k) * n + i] = offsets[i * K + k];
         }
-    int64_t* dptr = scratch<int64_t>(d->s_idx1, size_t(L) * K + 1);
-    int64_t* dind = scratch<int64_t>(d->s_idx2, nnz);
-    T* dval = scratch<T>(d->s_p1, size_t(nnz) + size_t(L) * K);
-    T* dicpt = dval + nnz;
-    AHIP_CHECK(hipMemcpyAsync(dptr, ptr.data(), ptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    if (nnz) {
-        AHIP_CHECK(hipMemcpyAsync(dind, ind.data(), nnz * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        AHIP_CHECK(hipMemcpyAsync(dval, val.data(), nnz * sizeof(T), hipMemcpyHostToDevice, s));
-    }
+    const DevCsr<T> A = upload_csr<T>(d, L * K, ptr.data(), ind.data(), val.data(), size_t(L) * K); // (+ the intercepts)
+    T* dicpt = A.val + nnz;
     AHIP_CHECK(hipMemcpyAsync(dicpt, intercepts, size_t(L) * K * sizeof(T), hipMemcpyHostToDevice, s));
     const size_t SUMS = 16 + 4 * 256;
     const size_t nK = size_t(n) * K;
@@ -466,35 +453,21 @@ void op_multi_path_losses(adelie_hip_design* d, int kind, int K, int64_t L, cons
     AHIP_CHECK(hipMemcpyAsync(doff, om.data(), nK * sizeof(T), hipMemcpyHostToDevice, s));
     AHIP_CHECK(hipMemcpyAsync(dwa, wa, n * sizeof(T), hipMemcpyHostToDevice, s));
     AHIP_CHECK(hipMemcpyAsync(dwb, wb, n * sizeof(T), hipMemcpyHostToDevice, s));
-    const int64_t Lp = std::max<int64_t>(1, (int64_t(1) << 30) / int64_t(nK * sizeof(T)));
-    T* dout = scratch<T>(d->s_misc, size_t(std::min(Lp, L)) * nK);
-    for (int64_t l0 = 0; l0 < L; l0 += Lp) {
-        const int64_t lc = std::min(Lp, L - l0);
-        if (d->kind == 0) launch_sp_tmul<T>(d->dense<T>(), lc * K, dptr + l0 * K, dind, dval, dout, s);
-        else if (d->kind == 3)
-            launch_sp_tmul_csc<T>(d->csc<T>(), lc * K, dptr + l0 * K, dind, dval, dout, scratch<T>(d->s_work, sp_tmul_work_elems_csc(d->p)), s);
-        else launch_sp_tmul_snp<T>(d->snp(), static_cast<const T*>(d->impute), lc * K, dptr + l0 * K, dind, dval, dout, s);
+    for_each_eta_panel<T>(d, A, L, K, [&](int64_t l0, int64_t lc, const T* eta) {
         for (int64_t l = 0; l < lc; ++l) {
-            launch_multi_loss2<T>(kind, dy, dwa, dwb, dout + size_t(l) * nK, dicpt + (l0 + l) * K, doff, n, K, sums, s);
+            launch_multi_loss2<T>(kind, dy, dwa, dwb, eta + size_t(l) * nK, dicpt + (l0 + l) * K, doff, n, K, sums, s);
             AHIP_CHECK(hipMemcpyAsync(dres + 2 * (l0 + l), sums, 2 * sizeof(T), hipMemcpyDeviceToDevice, s));
         }
-    }
-    std::vector<T> res(size_t(2) * L);
-    AHIP_CHECK(hipMemcpyAsync(res.data(), dres, res.size() * sizeof(T), hipMemcpyDeviceToHost, s));
-    AHIP_CHECK(hipStreamSynchronize(s));
-    for (int64_t l = 0; l < L; ++l) {
-        out[l] = double(res[2 * l]);
-        out[L + l] = double(res[2 * l + 1]);
-    }
+    });
+    download_loss_pairs<T>(d, dres, L, out);
 }
 
-// the multi-response view (kind 2) only serves grpnet_solve; its matrix ops go through the base design
+// the multi-response view only serves grpnet_solve; its matrix ops go through the base design
 void no_view(const adelie_hip_design* d) {
-    if (d && d->std_center && d->kind != 3)
+    if (d && d->is_std_view())
         throw make_core_error("the matrix operations of a standardized view over a dense or SNP design are composed by the caller "
                               "(adelie_amd.matrix); the handle only serves grpnet_solve.");
-    if (d && d->kind == 2)
-        throw make_core_error("this entry point is not offered on a multi-response view; use the base design.");
+    if (d && d->is_multi()) throw multi_view_error();
     if (d && d->cov)
         throw make_core_error("this entry point takes a design matrix, not a covariance matrix (matrix.dense(method=\"cov\")).");
 }
@@ -546,47 +519,43 @@ void create_factor_t(adelie_hip_design* Z, std::vector<FactorBlock>& blocks, con
         for (int32_t t0 = 0; t0 < blocks[b].ncols; t0 += kFactorChunk)
             chunks.push_back(FactorChunk{int32_t(b), t0, std::min<int32_t>(kFactorChunk, blocks[b].ncols - t0), 0});
     }
-    adelie_hip_design* d = new_design(n, P, Z->dtype, Z->device);
-    try {
-        const int64_t ld = ((n + kAlign - 1) / kAlign) * kAlign;
-        hipStream_t s = d->stream;
-        T* X = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&X), size_t(ld) * size_t(P) * sizeof(T)) != hipSuccess) {
-            (void)hipGetLastError();
-            throw make_core_error(std::string(what) + "(): could not allocate the expanded design (" + std::to_string(n) + " x " +
-                                  std::to_string(P) + ", " + gib(double(ld) * double(P) * sizeof(T)) + ") on the device.");
-        }
-        d->X = X;
-        d->ld = ld;
-        d->owned = true;
-        d->kind = 0;
-        T* fz = nullptr;
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fz), size_t(ld) * size_t(dz) * sizeof(T)));
-        d->fz = fz;
-        d->fz_ld = ld;
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->fblk), blocks.size() * sizeof(FactorBlock)));
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->fchunk), chunks.size() * sizeof(FactorChunk)));
-        d->f_nchunk = int64_t(chunks.size());
-        d->f_outer = outer;
-        AHIP_CHECK(hipMemcpyAsync(d->fblk, blocks.data(), blocks.size() * sizeof(FactorBlock), hipMemcpyHostToDevice, s));
-        AHIP_CHECK(hipMemcpyAsync(d->fchunk, chunks.data(), chunks.size() * sizeof(FactorChunk), hipMemcpyHostToDevice, s));
-        // zero the padding rows (vector loads past n never see NaN payloads), then copy Z and expand
-        AHIP_CHECK(hipMemsetAsync(fz, 0, size_t(ld) * size_t(dz) * sizeof(T), s));
-        if (ld > n) AHIP_CHECK(hipMemset2DAsync(X + n, size_t(ld) * sizeof(T), 0, size_t(ld - n) * sizeof(T), size_t(P), s));
-        AHIP_CHECK(hipStreamSynchronize(Z->stream)); // (Z's own creation may still be in flight on its stream)
-        launch_derive_dense<T>(Z->dense<T>(), n, dz, nullptr, nullptr, nullptr, nullptr, fz, ld, s);
-        launch_factor_expand<T>(d->factor_view<T>(), X, ld, s);
-        AHIP_CHECK(hipStreamSynchronize(s)); // (the host tables above go out of scope)
-    } catch (...) {
-        adelie_hip_design_destroy(d);
-        throw;
+    DesignGuard g(new_design(n, P, Z->dtype, Z->device));
+    adelie_hip_design* d = g.get();
+    const int64_t ld = ((n + kAlign - 1) / kAlign) * kAlign;
+    hipStream_t s = d->stream;
+    T* X = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&X), size_t(ld) * size_t(P) * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        throw make_core_error(std::string(what) + "(): could not allocate the expanded design (" + std::to_string(n) + " x " +
+                              std::to_string(P) + ", " + gib(double(ld) * double(P) * sizeof(T)) + ") on the device.");
     }
-    *out = d;
+    d->X = X;
+    d->ld = ld;
+    d->owned = true;
+    d->kind = adelie_hip_design::kDense;
+    T* fz = nullptr;
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fz), size_t(ld) * size_t(dz) * sizeof(T)));
+    d->fz = fz;
+    d->fz_ld = ld;
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->fblk), blocks.size() * sizeof(FactorBlock)));
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->fchunk), chunks.size() * sizeof(FactorChunk)));
+    d->f_nchunk = int64_t(chunks.size());
+    d->f_outer = outer;
+    AHIP_CHECK(hipMemcpyAsync(d->fblk, blocks.data(), blocks.size() * sizeof(FactorBlock), hipMemcpyHostToDevice, s));
+    AHIP_CHECK(hipMemcpyAsync(d->fchunk, chunks.data(), chunks.size() * sizeof(FactorChunk), hipMemcpyHostToDevice, s));
+    // zero the padding rows (vector loads past n never see NaN payloads), then copy Z and expand
+    AHIP_CHECK(hipMemsetAsync(fz, 0, size_t(ld) * size_t(dz) * sizeof(T), s));
+    if (ld > n) AHIP_CHECK(hipMemset2DAsync(X + n, size_t(ld) * sizeof(T), 0, size_t(ld - n) * sizeof(T), size_t(P), s));
+    AHIP_CHECK(hipStreamSynchronize(Z->stream)); // (Z's own creation may still be in flight on its stream)
+    launch_derive_dense<T>(Z->dense<T>(), n, dz, nullptr, nullptr, nullptr, nullptr, fz, ld, s);
+    launch_factor_expand<T>(d->factor_view<T>(), X, ld, s);
+    AHIP_CHECK(hipStreamSynchronize(s)); // (the host tables above go out of scope)
+    *out = g.release();
 }
 
 void check_factor_source(const adelie_hip_design* Z, const int64_t* levels, const void* out, const char* what) {
     if (!Z || !levels || !out) throw make_core_error("null argument.");
-    if (Z->kind != 0 || Z->cov || Z->std_center)
+    if (!Z->is_dense() || Z->cov || Z->std_center)
         throw make_core_error(std::string(what) + "(): mat must be a resident dense naive design (not an SNP, sparse, view or "
                               "covariance handle).");
     for (int64_t j = 0; j < Z->p; ++j)
@@ -608,9 +577,10 @@ inline int32_t factor_basis(const int64_t* levels, int64_t j, bool& disc) {
     }                                  \
     return 0;
 
-#define DTYPE_DISPATCH(d, call64, call32)               \
-    if ((d)->dtype == ADELIE_HIP_F64) { using T = double; (void)sizeof(T); call64; } \
-    else { using T = float; (void)sizeof(T); call32; }
+// runs the statement(s) once with T = the design's value type
+#define DTYPE_DISPATCH(d, ...)                                                            \
+    if ((d)->dtype == ADELIE_HIP_F64) { using T = double; (void)sizeof(T); __VA_ARGS__; } \
+    else { using T = float; (void)sizeof(T); __VA_ARGS__; }
 
 namespace {
 template <class T>
@@ -618,9 +588,9 @@ void derive_t(adelie_hip_design* src, adelie_hip_design* d, const int64_t* rows,
               int64_t ncols, const double* centers, const double* scales) {
     constexpr int64_t kAlign = 32;
     const int64_t nout = d->n, pout = d->p;
-    if (src->kind == 1 && !centers && !scales) { // a subset of a 2-bit design stays 2 bits per call
+    if (src->is_snp() && !centers && !scales) { // a subset of a 2-bit design stays 2 bits per call
         hipStream_t s = d->stream;
-        d->kind = 1;
+        d->kind = adelie_hip_design::kSnp;
         d->ldb = (((nout + 3) / 4 + 127) / 128) * 128;
         AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bits), size_t(d->ldb) * size_t(pout)));
         AHIP_CHECK(hipMalloc(&d->impute, size_t(pout) * sizeof(T)));
@@ -635,7 +605,7 @@ void derive_t(adelie_hip_design* src, adelie_hip_design* d, const int64_t* rows,
         }
         AHIP_CHECK(hipStreamSynchronize(src->stream));
         launch_snp_subset(src->snp(), nout, pout, drows, dcols, d->bits, d->ldb, s);
-        launch_gather_cols<T>(static_cast<const T*>(src->impute), dcols, pout, static_cast<T*>(d->impute), s);
+        launch_gather_cols<T>(snp_impute<T>(*src), dcols, pout, static_cast<T*>(d->impute), s);
         AHIP_CHECK(hipStreamSynchronize(s));
         return;
     }
@@ -645,7 +615,7 @@ void derive_t(adelie_hip_design* src, adelie_hip_design* d, const int64_t* rows,
     d->X = X;
     d->ld = ld;
     d->owned = true;
-    d->kind = 0;
+    d->kind = adelie_hip_design::kDense;
     hipStream_t s = d->stream;
     AHIP_CHECK(hipMemsetAsync(X, 0, size_t(ld) * size_t(pout) * sizeof(T), s));
     int64_t *drows = nullptr, *dcols = nullptr;
@@ -671,9 +641,9 @@ void derive_t(adelie_hip_design* src, adelie_hip_design* d, const int64_t* rows,
     }
     // the source's stream may still be writing it (e.g. its own creation): order after it
     AHIP_CHECK(hipStreamSynchronize(src->stream));
-    if (src->kind == 3) throw make_core_error("derived designs of a sparse design are composed on the host (adelie_amd.matrix).");
-    if (src->kind == 0) launch_derive_dense<T>(src->dense<T>(), nout, pout, drows, dcols, dc, ds, X, ld, s);
-    else launch_derive_dense_snp<T>(src->snp(), static_cast<const T*>(src->impute), nout, pout, drows, dcols, dc, ds, X, ld, s);
+    if (src->is_csc()) throw make_core_error("derived designs of a sparse design are composed on the host (adelie_amd.matrix).");
+    if (src->is_dense()) launch_derive_dense<T>(src->dense<T>(), nout, pout, drows, dcols, dc, ds, X, ld, s);
+    else launch_derive_dense_snp<T>(src->snp(), snp_impute<T>(*src), nout, pout, drows, dcols, dc, ds, X, ld, s);
     AHIP_CHECK(hipStreamSynchronize(s));
 }
 // concatenation of resident designs along the columns (axis 1) or the rows (axis 0): every source is copied (SNP sources
@@ -683,10 +653,10 @@ void concat_t(adelie_hip_design* const* srcs, int64_t k, int axis, adelie_hip_de
     constexpr int64_t kAlign = 32;
     const int64_t nout = d->n, pout = d->p;
     bool all_snp = axis == 1;
-    for (int64_t m = 0; m < k && all_snp; ++m) all_snp = srcs[m]->kind == 1 && !srcs[m]->std_center && srcs[m]->ldb == srcs[0]->ldb;
+    for (int64_t m = 0; m < k && all_snp; ++m) all_snp = srcs[m]->is_snp() && !srcs[m]->std_center && srcs[m]->ldb == srcs[0]->ldb;
     if (all_snp) { // 2-bit designs side by side stay a 2-bit design: their columns are copied as they are
         hipStream_t s = d->stream;
-        d->kind = 1;
+        d->kind = adelie_hip_design::kSnp;
         d->ldb = srcs[0]->ldb;
         AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bits), size_t(d->ldb) * size_t(pout)));
         AHIP_CHECK(hipMalloc(&d->impute, size_t(pout) * sizeof(T)));
@@ -707,7 +677,7 @@ void concat_t(adelie_hip_design* const* srcs, int64_t k, int axis, adelie_hip_de
     d->X = X;
     d->ld = ld;
     d->owned = true;
-    d->kind = 0;
+    d->kind = adelie_hip_design::kDense;
     hipStream_t s = d->stream;
     AHIP_CHECK(hipMemsetAsync(X, 0, size_t(ld) * size_t(pout) * sizeof(T), s));
     int64_t off = 0;
@@ -715,9 +685,9 @@ void concat_t(adelie_hip_design* const* srcs, int64_t k, int axis, adelie_hip_de
         adelie_hip_design* src = srcs[m];
         AHIP_CHECK(hipStreamSynchronize(src->stream));
         T* dst = axis == 1 ? X + off * ld : X + off;
-        if (src->kind == 3) throw make_core_error("concatenations with a sparse design are composed on the host (adelie_amd.matrix).");
-        if (src->kind == 0) launch_derive_dense<T>(src->dense<T>(), src->n, src->p, nullptr, nullptr, nullptr, nullptr, dst, ld, s);
-        else launch_derive_dense_snp<T>(src->snp(), static_cast<const T*>(src->impute), src->n, src->p, nullptr, nullptr,
+        if (src->is_csc()) throw make_core_error("concatenations with a sparse design are composed on the host (adelie_amd.matrix).");
+        if (src->is_dense()) launch_derive_dense<T>(src->dense<T>(), src->n, src->p, nullptr, nullptr, nullptr, nullptr, dst, ld, s);
+        else launch_derive_dense_snp<T>(src->snp(), snp_impute<T>(*src), src->n, src->p, nullptr, nullptr,
                                         nullptr, nullptr, dst, ld, s);
         off += axis == 1 ? src->p : src->n;
     }
@@ -785,15 +755,9 @@ int adelie_hip_design_create_dense(const void* host, int64_t n, int64_t p, int d
                                    adelie_hip_design** out) {
     ABI_TRY
     if (!host || !out) throw make_core_error("null argument.");
-    adelie_hip_design* d = new_design(n, p, dtype, device);
-    try {
-        if (dtype == ADELIE_HIP_F64) create_dense_t<double>(d, host, false, order);
-        else create_dense_t<float>(d, host, false, order);
-    } catch (...) {
-        adelie_hip_design_destroy(d);
-        throw;
-    }
-    *out = d;
+    DesignGuard g(new_design(n, p, dtype, device));
+    DTYPE_DISPATCH(g, create_dense_t<T>(g.get(), host, false, order))
+    *out = g.release();
     ABI_CATCH
 }
 
@@ -803,16 +767,10 @@ int adelie_hip_design_create_cov_dense(const void* host, int64_t p, int dtype, i
     ABI_TRY
     if (!host || !out) throw make_core_error("null argument.");
     if (p <= 0) throw make_core_error("mat must be (p, p).");
-    adelie_hip_design* d = new_design(p, p, dtype, device);
-    try {
-        if (dtype == ADELIE_HIP_F64) create_dense_t<double>(d, host, false, ADELIE_HIP_COL_MAJOR);
-        else create_dense_t<float>(d, host, false, ADELIE_HIP_COL_MAJOR);
-        d->cov = (order == ADELIE_HIP_ROW_MAJOR) ? 2 : 1;
-    } catch (...) {
-        adelie_hip_design_destroy(d);
-        throw;
-    }
-    *out = d;
+    DesignGuard g(new_design(p, p, dtype, device));
+    DTYPE_DISPATCH(g, create_dense_t<T>(g.get(), host, false, ADELIE_HIP_COL_MAJOR))
+    g->cov = (order == ADELIE_HIP_ROW_MAJOR) ? 2 : 1;
+    *out = g.release();
     ABI_CATCH
 }
 
@@ -821,20 +779,14 @@ int adelie_hip_design_create_cov_lazy(adelie_hip_design* X, adelie_hip_design** 
     ABI_TRY
     if (!X || !out) throw make_core_error("null argument.");
     if (X->cov) throw make_core_error("mat must be a naive (n, p) matrix, not a covariance matrix.");
-    if (X->kind != 0 && X->kind != 1) throw make_core_error("lazy_cov takes a dense or SNP design.");
+    if (!X->is_dense() && !X->is_snp()) throw make_core_error("lazy_cov takes a dense or SNP design.");
     if (X->p > (int64_t(1) << 31) - 1) throw make_core_error("too many columns.");
     set_device(X);
     AHIP_CHECK(hipStreamSynchronize(X->stream));
-    adelie_hip_design* d = new_design(X->p, X->p, X->dtype, X->device);
-    try {
-        if (X->dtype == ADELIE_HIP_F64) cov_lazy_t<double>(X, d);
-        else cov_lazy_t<float>(X, d);
-        d->cov = 1;
-    } catch (...) {
-        adelie_hip_design_destroy(d);
-        throw;
-    }
-    *out = d;
+    DesignGuard g(new_design(X->p, X->p, X->dtype, X->device));
+    DTYPE_DISPATCH(X, cov_lazy_t<T>(X, g.get()))
+    g->cov = 1;
+    *out = g.release();
     ABI_CATCH
 }
 
@@ -847,8 +799,7 @@ int adelie_hip_design_cov_bmul(adelie_hip_design* d, const int64_t* subset, int6
         if (subset[k] < 0 || subset[k] >= d->p) throw make_core_error("bmul(): subset index out of range.");
     for (int64_t k = 0; k < ni; ++k)
         if (indices[k] < 0 || indices[k] >= d->p) throw make_core_error("bmul(): index out of range.");
-    DTYPE_DISPATCH(d, op_cov_bmul<double>(d, subset, ns, indices, (const double*)values, ni, (double*)out),
-                   op_cov_bmul<float>(d, subset, ns, indices, (const float*)values, ni, (float*)out))
+    DTYPE_DISPATCH(d, op_cov_bmul<T>(d, subset, ns, indices, (const T*)values, ni, (T*)out))
     ABI_CATCH
 }
 int adelie_hip_design_cov_mul(adelie_hip_design* d, const int64_t* indices, const void* values, int64_t ni, void* out) {
@@ -857,15 +808,14 @@ int adelie_hip_design_cov_mul(adelie_hip_design* d, const int64_t* indices, cons
     if (ni < 0 || ni > d->p) throw make_core_error("mul() is given inconsistent inputs!");
     for (int64_t k = 0; k < ni; ++k)
         if (indices[k] < 0 || indices[k] >= d->p) throw make_core_error("mul(): index out of range.");
-    DTYPE_DISPATCH(d, op_cov_mul<double>(d, indices, (const double*)values, ni, (double*)out),
-                   op_cov_mul<float>(d, indices, (const float*)values, ni, (float*)out))
+    DTYPE_DISPATCH(d, op_cov_mul<T>(d, indices, (const T*)values, ni, (T*)out))
     ABI_CATCH
 }
 int adelie_hip_design_cov_to_dense(adelie_hip_design* d, int64_t i, int64_t q, void* out) {
     ABI_TRY
     need_cov(d);
     if (i < 0 || q < 0 || i + q > d->p) throw make_core_error("to_dense() is given inconsistent inputs!");
-    if (q > 0) { DTYPE_DISPATCH(d, op_cov_to_dense<double>(d, i, q, (double*)out), op_cov_to_dense<float>(d, i, q, (float*)out)) }
+    if (q > 0) { DTYPE_DISPATCH(d, op_cov_to_dense<T>(d, i, q, (T*)out)) }
     ABI_CATCH
 }
 
@@ -881,15 +831,9 @@ int adelie_hip_design_create_sparse(const int64_t* indptr, const int32_t* indice
     if (nnz > 0 && (!indices || !values)) throw make_core_error("null argument.");
     for (int64_t k = 0; k < nnz; ++k)
         if (indices[k] < 0 || indices[k] >= n) throw make_core_error("sparse(): row index out of range.");
-    adelie_hip_design* d = new_design(n, p, dtype, device);
-    try {
-        if (dtype == ADELIE_HIP_F64) create_sparse_t<double>(d, indptr, indices, values);
-        else create_sparse_t<float>(d, indptr, indices, values);
-    } catch (...) {
-        adelie_hip_design_destroy(d);
-        throw;
-    }
-    *out = d;
+    DesignGuard g(new_design(n, p, dtype, device));
+    DTYPE_DISPATCH(g, create_sparse_t<T>(g.get(), indptr, indices, values))
+    *out = g.release();
     ABI_CATCH
 }
 
@@ -945,84 +889,71 @@ int adelie_hip_design_create_csc(const int64_t* indptr, const int32_t* indices, 
         }
         if (sum_r != sum_c) throw make_core_error("sparse(): the two compressed forms must hold the same entries.");
     }
-    adelie_hip_design* d = new_design(n, p, dtype, device);
-    try {
-        d->kind = 3;
-        d->nnz = nnz;
-        const size_t vs = dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
-        const size_t nz1 = size_t(std::max<int64_t>(nnz, 1));
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cptr), size_t(p + 1) * sizeof(int64_t)));
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cidx), nz1 * sizeof(int32_t)));
-        AHIP_CHECK(hipMalloc(&d->cval, nz1 * vs));
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rptr), size_t(n + 1) * sizeof(int64_t)));
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rcol), nz1 * sizeof(int32_t)));
-        AHIP_CHECK(hipMalloc(&d->rval, nz1 * vs));
-        hipStream_t s = d->stream;
-        AHIP_CHECK(hipMemcpyAsync(d->cptr, indptr, size_t(p + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        AHIP_CHECK(hipMemcpyAsync(d->rptr, row_indptr, size_t(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        if (nnz) {
-            AHIP_CHECK(hipMemcpyAsync(d->cidx, indices, size_t(nnz) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            AHIP_CHECK(hipMemcpyAsync(d->cval, values, size_t(nnz) * vs, hipMemcpyHostToDevice, s));
-            AHIP_CHECK(hipMemcpyAsync(d->rcol, row_indices, size_t(nnz) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-            AHIP_CHECK(hipMemcpyAsync(d->rval, row_values, size_t(nnz) * vs, hipMemcpyHostToDevice, s));
-        }
-        csc_block_layout(n, vs, &d->sp_nb, &d->sp_rb);
-        if (d->sp_nb > 1) {
-            AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bptr), size_t(p) * size_t(d->sp_nb + 1) * sizeof(int64_t)));
-            launch_csc_block_ptr(d->cptr, d->cidx, p, d->sp_nb, d->sp_rb, d->bptr, s);
-        }
-        // Tile-major copy for the full sweeps (csc_tile_sweep_kernel): tiles of kCscTileBytes of an n-vector.  Built on the
-        // device from the per-column tile pointers; the tile-major offsets are a prefix sum over (tile, column) on the host.
-        {
-            const int64_t th = kCscTileBytes / int64_t(vs);
-            const int64_t nt = (n + th - 1) / th;
-            // (the tile of v is 128 KB of dynamic LDS — gfx950 has 160 KB per workgroup, the only target of this library; a launch
-            // the device refuses raises in raw_sweep)
-            const bool worth = nt > 1 && nt <= 4096 && nnz >= (int64_t(1) << 16) && nt * (p + 1) * 8 <= (int64_t(1) << 30) &&
-                               nnz / (nt * p) >= 4; // (segments of a few entries at least: below, the pointers outweigh the entries)
-            if (worth) {
-                int64_t* colptr = nullptr;
-                AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&colptr), size_t(p) * size_t(nt + 1) * sizeof(int64_t)));
-                try {
-                    launch_csc_block_ptr(d->cptr, d->cidx, p, int(nt), th, colptr, s);
-                    std::vector<int64_t> cp(size_t(p) * size_t(nt + 1)), tp(size_t(nt) * size_t(p + 1));
-                    AHIP_CHECK(hipMemcpyAsync(cp.data(), colptr, cp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-                    AHIP_CHECK(hipStreamSynchronize(s));
-                    int64_t run = 0;
-                    for (int64_t t = 0; t < nt; ++t) {
-                        int64_t* row = tp.data() + size_t(t) * size_t(p + 1);
-                        for (int64_t c = 0; c < p; ++c) {
-                            row[c] = run;
-                            run += cp[size_t(c) * size_t(nt + 1) + size_t(t) + 1] - cp[size_t(c) * size_t(nt + 1) + size_t(t)];
-                        }
-                        row[p] = run;
-                    }
-                    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->tptr), tp.size() * sizeof(int64_t)));
-                    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->trow), nz1 * sizeof(uint16_t)));
-                    AHIP_CHECK(hipMalloc(&d->tval, nz1 * vs));
-                    AHIP_CHECK(hipMemcpyAsync(d->tptr, tp.data(), tp.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-                    if (dtype == ADELIE_HIP_F64)
-                        launch_csc_tile_scatter<double>(colptr, d->cidx, static_cast<const double*>(d->cval), p, int(nt), th, d->tptr,
-                                                        d->trow, static_cast<double*>(d->tval), s);
-                    else
-                        launch_csc_tile_scatter<float>(colptr, d->cidx, static_cast<const float*>(d->cval), p, int(nt), th, d->tptr,
-                                                       d->trow, static_cast<float*>(d->tval), s);
-                    AHIP_CHECK(hipStreamSynchronize(s));
-                    d->sp_nt = int(nt);
-                    d->sp_th = th;
-                } catch (...) {
-                    (void)hipFree(colptr);
-                    throw;
-                }
-                (void)hipFree(colptr);
-            }
-        }
-        AHIP_CHECK(hipStreamSynchronize(s));
-    } catch (...) {
-        adelie_hip_design_destroy(d);
-        throw;
+    DesignGuard g(new_design(n, p, dtype, device));
+    adelie_hip_design* d = g.get();
+    d->kind = adelie_hip_design::kCsc;
+    d->nnz = nnz;
+    const size_t vs = dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
+    const size_t nz1 = size_t(std::max<int64_t>(nnz, 1));
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cptr), size_t(p + 1) * sizeof(int64_t)));
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cidx), nz1 * sizeof(int32_t)));
+    AHIP_CHECK(hipMalloc(&d->cval, nz1 * vs));
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rptr), size_t(n + 1) * sizeof(int64_t)));
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rcol), nz1 * sizeof(int32_t)));
+    AHIP_CHECK(hipMalloc(&d->rval, nz1 * vs));
+    hipStream_t s = d->stream;
+    AHIP_CHECK(hipMemcpyAsync(d->cptr, indptr, size_t(p + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    AHIP_CHECK(hipMemcpyAsync(d->rptr, row_indptr, size_t(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    if (nnz) {
+        AHIP_CHECK(hipMemcpyAsync(d->cidx, indices, size_t(nnz) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        AHIP_CHECK(hipMemcpyAsync(d->cval, values, size_t(nnz) * vs, hipMemcpyHostToDevice, s));
+        AHIP_CHECK(hipMemcpyAsync(d->rcol, row_indices, size_t(nnz) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        AHIP_CHECK(hipMemcpyAsync(d->rval, row_values, size_t(nnz) * vs, hipMemcpyHostToDevice, s));
     }
-    *out = d;
+    csc_block_layout(n, vs, &d->sp_nb, &d->sp_rb);
+    if (d->sp_nb > 1) {
+        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bptr), size_t(p) * size_t(d->sp_nb + 1) * sizeof(int64_t)));
+        launch_csc_block_ptr(d->cptr, d->cidx, p, d->sp_nb, d->sp_rb, d->bptr, s);
+    }
+    // Tile-major copy for the full sweeps (csc_tile_sweep_kernel): tiles of kCscTileBytes of an n-vector.  Built on the
+    // device from the per-column tile pointers; the tile-major offsets are a prefix sum over (tile, column) on the host.
+    {
+        const int64_t th = kCscTileBytes / int64_t(vs);
+        const int64_t nt = (n + th - 1) / th;
+        // (the tile of v is 128 KB of dynamic LDS — gfx950 has 160 KB per workgroup, the only target of this library; a launch
+        // the device refuses raises in raw_sweep)
+        const bool worth = nt > 1 && nt <= 4096 && nnz >= (int64_t(1) << 16) && nt * (p + 1) * 8 <= (int64_t(1) << 30) &&
+                           nnz / (nt * p) >= 4; // (segments of a few entries at least: below, the pointers outweigh the entries)
+        if (worth) {
+            DevTmp ctmp;
+            AHIP_CHECK(hipMalloc(&ctmp.p, size_t(p) * size_t(nt + 1) * sizeof(int64_t)));
+            int64_t* colptr = static_cast<int64_t*>(ctmp.p);
+            launch_csc_block_ptr(d->cptr, d->cidx, p, int(nt), th, colptr, s);
+            std::vector<int64_t> cp(size_t(p) * size_t(nt + 1)), tp(size_t(nt) * size_t(p + 1));
+            AHIP_CHECK(hipMemcpyAsync(cp.data(), colptr, cp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            AHIP_CHECK(hipStreamSynchronize(s));
+            int64_t run = 0;
+            for (int64_t t = 0; t < nt; ++t) {
+                int64_t* row = tp.data() + size_t(t) * size_t(p + 1);
+                for (int64_t c = 0; c < p; ++c) {
+                    row[c] = run;
+                    run += cp[size_t(c) * size_t(nt + 1) + size_t(t) + 1] - cp[size_t(c) * size_t(nt + 1) + size_t(t)];
+                }
+                row[p] = run;
+            }
+            AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->tptr), tp.size() * sizeof(int64_t)));
+            AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->trow), nz1 * sizeof(uint16_t)));
+            AHIP_CHECK(hipMalloc(&d->tval, nz1 * vs));
+            AHIP_CHECK(hipMemcpyAsync(d->tptr, tp.data(), tp.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            DTYPE_DISPATCH(d, launch_csc_tile_scatter<T>(colptr, d->cidx, static_cast<const T*>(d->cval), p, int(nt), th, d->tptr, d->trow,
+                                                         static_cast<T*>(d->tval), s))
+            AHIP_CHECK(hipStreamSynchronize(s));
+            d->sp_nt = int(nt);
+            d->sp_th = th;
+        }
+    }
+    AHIP_CHECK(hipStreamSynchronize(s));
+    *out = g.release();
     ABI_CATCH
 }
 
@@ -1030,34 +961,30 @@ int adelie_hip_design_create_standardized(adelie_hip_design* src, const double* 
                                           adelie_hip_design** out) {
     ABI_TRY
     if (!src || !centers || !scales || !out) throw make_core_error("null argument.");
-    if (src->kind == 2 || src->cov) no_view(src);
+    if (src->is_multi() || src->cov) no_view(src);
     if (src->std_center) throw make_core_error("the design is a standardized view already.");
     for (int64_t j = 0; j < src->p; ++j)
         if (!(scales[j] != 0.0)) throw make_core_error("scales must be non-zero.");
     adelie_hip_design* d = nullptr;
     if (adelie_hip_design_alias(src, &d)) throw make_core_error(g_last_error);
-    try {
-        const int64_t p = src->p;
-        const size_t vs = src->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
-        AHIP_CHECK(hipMalloc(&d->std_center, size_t(p) * vs));
-        d->std_owned = true;
-        AHIP_CHECK(hipMalloc(&d->std_iscale, size_t(p) * vs));
-        if (src->dtype == ADELIE_HIP_F64) {
-            std::vector<double> is(static_cast<size_t>(p));
-            for (int64_t j = 0; j < p; ++j) is[size_t(j)] = 1.0 / scales[j];
-            AHIP_CHECK(hipMemcpy(d->std_center, centers, size_t(p) * vs, hipMemcpyHostToDevice));
-            AHIP_CHECK(hipMemcpy(d->std_iscale, is.data(), size_t(p) * vs, hipMemcpyHostToDevice));
-        } else {
-            std::vector<float> ce(static_cast<size_t>(p)), is(static_cast<size_t>(p));
-            for (int64_t j = 0; j < p; ++j) { ce[size_t(j)] = float(centers[j]); is[size_t(j)] = float(1.0 / scales[j]); }
-            AHIP_CHECK(hipMemcpy(d->std_center, ce.data(), size_t(p) * vs, hipMemcpyHostToDevice));
-            AHIP_CHECK(hipMemcpy(d->std_iscale, is.data(), size_t(p) * vs, hipMemcpyHostToDevice));
-        }
-    } catch (...) {
-        adelie_hip_design_destroy(d);
-        throw;
+    DesignGuard g(d);
+    const int64_t p = src->p;
+    const size_t vs = src->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
+    AHIP_CHECK(hipMalloc(&d->std_center, size_t(p) * vs));
+    d->std_owned = true;
+    AHIP_CHECK(hipMalloc(&d->std_iscale, size_t(p) * vs));
+    if (src->dtype == ADELIE_HIP_F64) {
+        std::vector<double> is(static_cast<size_t>(p));
+        for (int64_t j = 0; j < p; ++j) is[size_t(j)] = 1.0 / scales[j];
+        AHIP_CHECK(hipMemcpy(d->std_center, centers, size_t(p) * vs, hipMemcpyHostToDevice));
+        AHIP_CHECK(hipMemcpy(d->std_iscale, is.data(), size_t(p) * vs, hipMemcpyHostToDevice));
+    } else {
+        std::vector<float> ce(static_cast<size_t>(p)), is(static_cast<size_t>(p));
+        for (int64_t j = 0; j < p; ++j) { ce[size_t(j)] = float(centers[j]); is[size_t(j)] = float(1.0 / scales[j]); }
+        AHIP_CHECK(hipMemcpy(d->std_center, ce.data(), size_t(p) * vs, hipMemcpyHostToDevice));
+        AHIP_CHECK(hipMemcpy(d->std_iscale, is.data(), size_t(p) * vs, hipMemcpyHostToDevice));
     }
-    *out = d;
+    *out = g.release();
     ABI_CATCH
 }
 
@@ -1065,15 +992,9 @@ int adelie_hip_design_adopt_dense_dev(const void* dev_ptr, int64_t n, int64_t p,
                                       adelie_hip_design** out) {
     ABI_TRY
     if (!dev_ptr || !out) throw make_core_error("null argument.");
-    adelie_hip_design* d = new_design(n, p, dtype, device);
-    try {
-        if (dtype == ADELIE_HIP_F64) create_dense_t<double>(d, dev_ptr, true, order);
-        else create_dense_t<float>(d, dev_ptr, true, order);
-    } catch (...) {
-        adelie_hip_design_destroy(d);
-        throw;
-    }
-    *out = d;
+    DesignGuard g(new_design(n, p, dtype, device));
+    DTYPE_DISPATCH(g, create_dense_t<T>(g.get(), dev_ptr, true, order))
+    *out = g.release();
     ABI_CATCH
 }
 
@@ -1081,14 +1002,9 @@ int adelie_hip_design_create_snp_calldata(const int8_t* calldata, int64_t n, int
                                           int device, adelie_hip_design** out) {
     ABI_TRY
     if (!calldata || !impute || !out) throw make_core_error("null argument.");
-    adelie_hip_design* d = new_design(n, p, dtype, device);
-    try {
-        create_snp_from_calldata(d, calldata, impute);
-    } catch (...) {
-        adelie_hip_design_destroy(d);
-        throw;
-    }
-    *out = d;
+    DesignGuard g(new_design(n, p, dtype, device));
+    create_snp_from_calldata(g.get(), calldata, impute);
+    *out = g.release();
     ABI_CATCH
 }
 
@@ -1143,42 +1059,36 @@ int adelie_hip_design_create_snp_unphased(const void* snpdat, int64_t n_bytes, i
         if (endc > uint64_t(n_bytes) || base < hdr || base > endc || endc - base < 24)
             throw make_core_error("corrupt .snpdat column index.");
     }
-    adelie_hip_design* d = new_design(int64_t(n), int64_t(p), dtype, device);
-    int8_t* tmp = nullptr;
-    try {
-        d->kind = 1;
-        d->ldb = int64_t((((n + 3) / 4 + 127) / 128) * 128);
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bits), size_t(d->ldb) * size_t(p)));
-        // decode -> int8 panel on the host -> 2-bit on the device, a panel of columns at a time
-        const uint64_t panel = std::min<uint64_t>(p, std::max<uint64_t>(1, (uint64_t(1) << 28) / n));
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&tmp), size_t(n) * size_t(panel)));
-        std::vector<int8_t> calls(size_t(n) * size_t(panel));
-        for (uint64_t j0 = 0; j0 < p; j0 += panel) {
-            const uint64_t pc = std::min(panel, p - j0);
-            std::fill(calls.begin(), calls.begin() + size_t(n) * size_t(pc), int8_t(0));
-            for (uint64_t j = j0; j < j0 + pc; ++j)
-                decode_snpdat_column(buf, read_as<uint64_t>(outer_p + 8 * j), read_as<uint64_t>(outer_p + 8 * (j + 1)), n,
-                                     calls.data() + size_t(j - j0) * size_t(n));
-            AHIP_CHECK(hipMemcpyAsync(tmp, calls.data(), size_t(n) * size_t(pc), hipMemcpyHostToDevice, d->stream));
-            launch_pack_snp(tmp, int64_t(n), int64_t(pc), d->bits + int64_t(j0) * d->ldb, d->ldb, d->stream);
-            AHIP_CHECK(hipStreamSynchronize(d->stream));
-        }
-        (void)hipFree(tmp);
-        tmp = nullptr;
-        if (d->dtype == ADELIE_HIP_F64) {
-            AHIP_CHECK(hipMalloc(&d->impute, size_t(p) * sizeof(double)));
-            AHIP_CHECK(hipMemcpy(d->impute, impute.data(), size_t(p) * sizeof(double), hipMemcpyHostToDevice));
-        } else {
-            std::vector<float> f(impute.begin(), impute.end());
-            AHIP_CHECK(hipMalloc(&d->impute, size_t(p) * sizeof(float)));
-            AHIP_CHECK(hipMemcpy(d->impute, f.data(), size_t(p) * sizeof(float), hipMemcpyHostToDevice));
-        }
-    } catch (...) {
-        if (tmp) (void)hipFree(tmp);
-        adelie_hip_design_destroy(d);
-        throw;
+    DesignGuard g(new_design(int64_t(n), int64_t(p), dtype, device));
+    adelie_hip_design* d = g.get();
+    d->kind = adelie_hip_design::kSnp;
+    d->ldb = int64_t((((n + 3) / 4 + 127) / 128) * 128);
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bits), size_t(d->ldb) * size_t(p)));
+    // decode -> int8 panel on the host -> 2-bit on the device, a panel of columns at a time
+    const uint64_t panel = std::min<uint64_t>(p, std::max<uint64_t>(1, (uint64_t(1) << 28) / n));
+    DevTmp tmp;
+    AHIP_CHECK(hipMalloc(&tmp.p, size_t(n) * size_t(panel)));
+    int8_t* dcalls = static_cast<int8_t*>(tmp.p);
+    std::vector<int8_t> calls(size_t(n) * size_t(panel));
+    for (uint64_t j0 = 0; j0 < p; j0 += panel) {
+        const uint64_t pc = std::min(panel, p - j0);
+        std::fill(calls.begin(), calls.begin() + size_t(n) * size_t(pc), int8_t(0));
+        for (uint64_t j = j0; j < j0 + pc; ++j)
+            decode_snpdat_column(buf, read_as<uint64_t>(outer_p + 8 * j), read_as<uint64_t>(outer_p + 8 * (j + 1)), n,
+                                 calls.data() + size_t(j - j0) * size_t(n));
+        AHIP_CHECK(hipMemcpyAsync(dcalls, calls.data(), size_t(n) * size_t(pc), hipMemcpyHostToDevice, d->stream));
+        launch_pack_snp(dcalls, int64_t(n), int64_t(pc), d->bits + int64_t(j0) * d->ldb, d->ldb, d->stream);
+        AHIP_CHECK(hipStreamSynchronize(d->stream));
     }
-    *out = d;
+    if (d->dtype == ADELIE_HIP_F64) {
+        AHIP_CHECK(hipMalloc(&d->impute, size_t(p) * sizeof(double)));
+        AHIP_CHECK(hipMemcpy(d->impute, impute.data(), size_t(p) * sizeof(double), hipMemcpyHostToDevice));
+    } else {
+        std::vector<float> f(impute.begin(), impute.end());
+        AHIP_CHECK(hipMalloc(&d->impute, size_t(p) * sizeof(float)));
+        AHIP_CHECK(hipMemcpy(d->impute, f.data(), size_t(p) * sizeof(float), hipMemcpyHostToDevice));
+    }
+    *out = g.release();
     ABI_CATCH
 }
 
@@ -1192,35 +1102,31 @@ int adelie_hip_design_create_snp_bed(const void* bed, int64_t n_bytes, int64_t n
     if (n_bytes < 3 || buf[0] != 0x6c || buf[1] != 0x1b) throw make_core_error("not a PLINK .bed image (bad magic).");
     if (buf[2] != 0x01) throw make_core_error("only SNP-major .bed files (third byte 0x01) are supported.");
     if (n_bytes < 3 + stride * p) throw make_core_error("truncated .bed image: expected 3 + ceil(n/4)*p bytes.");
-    adelie_hip_design* d = new_design(n, p, dtype, device);
-    try {
-        d->kind = 1;
-        d->ldb = (((n + 3) / 4 + 127) / 128) * 128;
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bits), size_t(d->ldb) * size_t(p)));
-        // stage the records in panels of SNPs to bound the temporary
-        const int64_t panel = std::max<int64_t>(1, (int64_t(1) << 28) / stride);
-        uint8_t* tmp = nullptr;
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&tmp), size_t(stride) * size_t(std::min(panel, p))));
-        for (int64_t j0 = 0; j0 < p; j0 += panel) {
-            const int64_t pc = std::min(panel, p - j0);
-            AHIP_CHECK(hipMemcpyAsync(tmp, buf + 3 + j0 * stride, size_t(stride) * size_t(pc), hipMemcpyDefault, d->stream));
-            launch_bed_transcode(tmp, n, pc, stride, d->bits + j0 * d->ldb, d->ldb, d->stream);
-            AHIP_CHECK(hipStreamSynchronize(d->stream));
-        }
-        (void)hipFree(tmp);
-        if (d->dtype == ADELIE_HIP_F64) {
-            AHIP_CHECK(hipMalloc(&d->impute, size_t(p) * sizeof(double)));
-            launch_snp_impute<double>(d->bits, n, p, d->ldb, static_cast<double*>(d->impute), d->stream);
-        } else {
-            AHIP_CHECK(hipMalloc(&d->impute, size_t(p) * sizeof(float)));
-            launch_snp_impute<float>(d->bits, n, p, d->ldb, static_cast<float*>(d->impute), d->stream);
-        }
+    DesignGuard g(new_design(n, p, dtype, device));
+    adelie_hip_design* d = g.get();
+    d->kind = adelie_hip_design::kSnp;
+    d->ldb = (((n + 3) / 4 + 127) / 128) * 128;
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bits), size_t(d->ldb) * size_t(p)));
+    // stage the records in panels of SNPs to bound the temporary
+    const int64_t panel = std::max<int64_t>(1, (int64_t(1) << 28) / stride);
+    uint8_t* tmp = nullptr;
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&tmp), size_t(stride) * size_t(std::min(panel, p))));
+    for (int64_t j0 = 0; j0 < p; j0 += panel) {
+        const int64_t pc = std::min(panel, p - j0);
+        AHIP_CHECK(hipMemcpyAsync(tmp, buf + 3 + j0 * stride, size_t(stride) * size_t(pc), hipMemcpyDefault, d->stream));
+        launch_bed_transcode(tmp, n, pc, stride, d->bits + j0 * d->ldb, d->ldb, d->stream);
         AHIP_CHECK(hipStreamSynchronize(d->stream));
-    } catch (...) {
-        adelie_hip_design_destroy(d);
-        throw;
     }
-    *out = d;
+    (void)hipFree(tmp);
+    if (d->dtype == ADELIE_HIP_F64) {
+        AHIP_CHECK(hipMalloc(&d->impute, size_t(p) * sizeof(double)));
+        launch_snp_impute<double>(d->bits, n, p, d->ldb, static_cast<double*>(d->impute), d->stream);
+    } else {
+        AHIP_CHECK(hipMalloc(&d->impute, size_t(p) * sizeof(float)));
+        launch_snp_impute<float>(d->bits, n, p, d->ldb, static_cast<float*>(d->impute), d->stream);
+    }
+    AHIP_CHECK(hipStreamSynchronize(d->stream));
+    *out = g.release();
     ABI_CATCH
 }
 
@@ -1240,7 +1146,7 @@ static void shadow_free(adelie_hip_design* o) {
 }
 
 bool adelie_hip_internal_shadow_acquire(adelie_hip_design* d, ahip::ShadowView* out) {
-    if (!d || d->kind != 0 || d->dtype != ADELIE_HIP_F64 || d->cov || d->std_center || !d->X || d->n < 1 || d->p < 1) return false;
+    if (!d || !d->is_dense() || d->dtype != ADELIE_HIP_F64 || d->cov || d->std_center || !d->X || d->n < 1 || d->p < 1) return false;
     adelie_hip_design* o = shadow_owner(d);
     if (o->X != d->X || o->ld != d->ld || o->n != d->n || o->p != d->p) return false;
     std::lock_guard<std::mutex> lk(o->sh_mu);
@@ -1312,8 +1218,9 @@ int adelie_hip_design_shadow_stats(adelie_hip_design* d, int64_t* out) {
 int adelie_hip_design_alias(adelie_hip_design* src, adelie_hip_design** out) {
     ABI_TRY
     if (!src || !out) throw make_core_error("null argument.");
-    if (src->kind == 2 || src->cov) no_view(src);
-    adelie_hip_design* d = new_design(src->n, src->p, src->dtype, src->device); // own stream, own scratch
+    if (src->is_multi() || src->cov) no_view(src);
+    DesignGuard g(new_design(src->n, src->p, src->dtype, src->device)); // own stream, own scratch
+    adelie_hip_design* d = g.get();
     d->kind = src->kind;
     d->X = src->X;
     d->ld = src->ld;
@@ -1331,7 +1238,7 @@ int adelie_hip_design_alias(adelie_hip_design* src, adelie_hip_design** out) {
     d->f_outer = src->f_outer; // (a factor design's alias keeps the structure: CV folds sweep the same way)
     d->alias = true;
     d->batch_owner = src->batch_owner ? src->batch_owner : src;
-    *out = d;
+    *out = g.release();
     ABI_CATCH
 }
 
@@ -1339,18 +1246,19 @@ int adelie_hip_design_create_slice(adelie_hip_design* base, int64_t r0, int64_t 
                                    adelie_hip_design** out) {
     ABI_TRY
     if (!base || !out) throw make_core_error("null argument.");
-    if ((base->kind != 0 && base->kind != 1) || base->cov || base->std_center)
+    if ((!base->is_dense() && !base->is_snp()) || base->cov || base->std_center)
         throw make_core_error("only dense and 2-bit SNP designs are sliced in place.");
     if (r0 < 0 || nr < 1 || c0 < 0 || nc < 1 || r0 + nr > base->n || c0 + nc > base->p)
         throw make_core_error("slice out of range.");
     const int64_t es = base->dtype == ADELIE_HIP_F64 ? 8 : 4;
-    if (base->kind == 1 && (r0 != 0 || nr != base->n)) throw make_core_error("a 2-bit design is sliced by columns only.");
-    if (base->kind == 0 && (r0 * es) % 16 != 0) throw make_core_error("a row slice must start on a 16-byte boundary.");
-    adelie_hip_design* d = new_design(nr, nc, base->dtype, base->device); // own stream, own scratch
+    if (base->is_snp() && (r0 != 0 || nr != base->n)) throw make_core_error("a 2-bit design is sliced by columns only.");
+    if (base->is_dense() && (r0 * es) % 16 != 0) throw make_core_error("a row slice must start on a 16-byte boundary.");
+    DesignGuard g(new_design(nr, nc, base->dtype, base->device)); // own stream, own scratch
+    adelie_hip_design* d = g.get();
     d->kind = base->kind;
     d->owned = false;
     d->alias = true; // never frees what it points into
-    if (base->kind == 0) {
+    if (base->is_dense()) {
         d->X = static_cast<char*>(base->X) + (c0 * base->ld + r0) * es;
         d->ld = base->ld;
     } else {
@@ -1358,21 +1266,22 @@ int adelie_hip_design_create_slice(adelie_hip_design* base, int64_t r0, int64_t 
         d->ldb = base->ldb;
         d->impute = static_cast<char*>(base->impute) + c0 * es;
     }
-    *out = d;
+    *out = g.release();
     ABI_CATCH
 }
 
 int adelie_hip_design_create_multi(adelie_hip_design* base, int64_t K, int intercept, adelie_hip_design** out) {
     ABI_TRY
     if (!base || !out) throw make_core_error("null argument.");
-    if ((base->kind != 0 && base->kind != 1) || base->cov || base->std_center)
+    if ((!base->is_dense() && !base->is_snp()) || base->cov || base->std_center)
         throw make_core_error("the multi-response view needs a dense or 2-bit SNP base design.");
     if (K < 1) throw make_core_error("K must be >= 1.");
     const int64_t icpt = intercept ? 1 : 0;
     if ((base->p + icpt) * K > int64_t(0x7fffffff) || base->n * K > (int64_t(1) << 40))
         throw make_core_error("the multi-response view is too large.");
-    adelie_hip_design* d = new_design(base->n * K, (base->p + icpt) * K, base->dtype, base->device); // own stream + scratch
-    d->kind = 2;
+    DesignGuard g(new_design(base->n * K, (base->p + icpt) * K, base->dtype, base->device)); // own stream + scratch
+    adelie_hip_design* d = g.get();
+    d->kind = adelie_hip_design::kMulti;
     d->X = base->X;
     d->ld = base->ld;
     d->bits = base->bits; // (2-bit base: the K-wide kernels decode the calls themselves, MultiView::bits)
@@ -1389,10 +1298,10 @@ int adelie_hip_design_create_multi(adelie_hip_design* base, int64_t K, int inter
         const int64_t len = ((base->n + 31) / 32) * 32;
         AHIP_CHECK(hipMalloc(&d->ones, size_t(len) * esz));
         AHIP_CHECK(hipMemsetAsync(d->ones, 0, size_t(len) * esz, d->stream));
-        DTYPE_DISPATCH(d, launch_fill<T>((T*)d->ones, T(1), base->n, d->stream), launch_fill<T>((T*)d->ones, T(1), base->n, d->stream))
+        DTYPE_DISPATCH(d, launch_fill<T>((T*)d->ones, T(1), base->n, d->stream))
         AHIP_CHECK(hipStreamSynchronize(d->stream));
     }
-    *out = d;
+    *out = g.release();
     ABI_CATCH
 }
 
@@ -1411,15 +1320,9 @@ int adelie_hip_design_create_derived(adelie_hip_design* src, const int64_t* rows
     if (scales)
         for (int64_t j = 0; j < pout; ++j)
             if (!(scales[j] != 0.0)) throw make_core_error("scales must be non-zero.");
-    adelie_hip_design* d = new_design(nout, pout, src->dtype, src->device);
-    try {
-        DTYPE_DISPATCH(src, derive_t<T>(src, d, rows, n_rows, cols, n_cols, centers, scales),
-                       derive_t<T>(src, d, rows, n_rows, cols, n_cols, centers, scales))
-    } catch (...) {
-        adelie_hip_design_destroy(d);
-        throw;
-    }
-    *out = d;
+    DesignGuard g(new_design(nout, pout, src->dtype, src->device));
+    DTYPE_DISPATCH(src, derive_t<T>(src, g.get(), rows, n_rows, cols, n_cols, centers, scales))
+    *out = g.release();
     ABI_CATCH
 }
 
@@ -1443,14 +1346,9 @@ int adelie_hip_design_create_concat(adelie_hip_design* const* srcs, int64_t k, i
             p = srcs[0]->p;
         }
     }
-    adelie_hip_design* d = new_design(n, p, srcs[0]->dtype, srcs[0]->device);
-    try {
-        DTYPE_DISPATCH(srcs[0], concat_t<T>(srcs, k, axis, d), concat_t<T>(srcs, k, axis, d))
-    } catch (...) {
-        adelie_hip_design_destroy(d);
-        throw;
-    }
-    *out = d;
+    DesignGuard g(new_design(n, p, srcs[0]->dtype, srcs[0]->device));
+    DTYPE_DISPATCH(srcs[0], concat_t<T>(srcs, k, axis, g.get()))
+    *out = g.release();
     ABI_CATCH
 }
 
@@ -1465,7 +1363,7 @@ int adelie_hip_design_create_one_hot(adelie_hip_design* Z, const int64_t* levels
         // continuous: [z] = the basis [1, z] without its constant column; discrete: [z == 0, ..., z == l - 1]
         blocks[size_t(j)] = FactorBlock{0, 0, int32_t(j), int32_t(j), l, 1, disc ? 0 : 1, (disc ? 1 : 0) | 4};
     }
-    DTYPE_DISPATCH(Z, create_factor_t<T>(Z, blocks, "one_hot", out), create_factor_t<T>(Z, blocks, "one_hot", out))
+    DTYPE_DISPATCH(Z, create_factor_t<T>(Z, blocks, "one_hot", out))
     ABI_CATCH
 }
 
@@ -1484,7 +1382,7 @@ int adelie_hip_design_create_interaction(adelie_hip_design* Z, const int64_t* pa
         const int32_t l0 = factor_basis(levels, i0, d0), l1 = factor_basis(levels, i1, d1);
         blocks[size_t(k)] = FactorBlock{0, 0, int32_t(i0), int32_t(i1), l0, l1, (!d0 && !d1) ? 1 : 0, (d0 ? 1 : 0) | (d1 ? 2 : 0)};
     }
-    DTYPE_DISPATCH(Z, create_factor_t<T>(Z, blocks, "interaction", out), create_factor_t<T>(Z, blocks, "interaction", out))
+    DTYPE_DISPATCH(Z, create_factor_t<T>(Z, blocks, "interaction", out))
     ABI_CATCH
 }
 
@@ -1502,7 +1400,7 @@ int adelie_hip_design_impute(adelie_hip_design* d, double* out) {
     ABI_TRY
     no_view(d);
     if (!d || !out) throw make_core_error("null argument.");
-    if (d->kind != 1) throw make_core_error("impute is only defined for SNP designs.");
+    if (!d->is_snp()) throw make_core_error("impute is only defined for SNP designs.");
     set_device(d);
     if (d->dtype == ADELIE_HIP_F64) {
         AHIP_CHECK(hipMemcpy(out, d->impute, size_t(d->p) * sizeof(double), hipMemcpyDeviceToHost));
@@ -1550,37 +1448,34 @@ int adelie_hip_design_cmul(adelie_hip_design* d, int64_t j, const void* v, const
     ABI_TRY
     no_view(d);
     check_col(d, j, 1, "cmul");
-    DTYPE_DISPATCH(d, { T o; op_sweep<T>(d, j, 1, (const T*)v, (const T*)weights, &o, false); *out = o; },
-                   { T o; op_sweep<T>(d, j, 1, (const T*)v, (const T*)weights, &o, false); *out = o; })
+    DTYPE_DISPATCH(d, { T o; op_sweep<T>(d, j, 1, (const T*)v, (const T*)weights, &o, false); *out = o; })
     ABI_CATCH
 }
 int adelie_hip_design_ctmul(adelie_hip_design* d, int64_t j, double v, void* out) {
     ABI_TRY
     no_view(d);
     check_col(d, j, 1, "ctmul");
-    DTYPE_DISPATCH(d, { T c = T(v); op_axpy<T>(d, j, 1, &c, (T*)out); }, { T c = T(v); op_axpy<T>(d, j, 1, &c, (T*)out); })
+    DTYPE_DISPATCH(d, { T c = T(v); op_axpy<T>(d, j, 1, &c, (T*)out); })
     ABI_CATCH
 }
 int adelie_hip_design_bmul(adelie_hip_design* d, int64_t j, int64_t q, const void* v, const void* weights, void* out) {
     ABI_TRY
     no_view(d);
     check_col(d, j, q, "bmul");
-    DTYPE_DISPATCH(d, op_sweep<T>(d, j, q, (const T*)v, (const T*)weights, (T*)out, false),
-                   op_sweep<T>(d, j, q, (const T*)v, (const T*)weights, (T*)out, false))
+    DTYPE_DISPATCH(d, op_sweep<T>(d, j, q, (const T*)v, (const T*)weights, (T*)out, false))
     ABI_CATCH
 }
 int adelie_hip_design_btmul(adelie_hip_design* d, int64_t j, int64_t q, const void* v, void* out) {
     ABI_TRY
     no_view(d);
     check_col(d, j, q, "btmul");
-    DTYPE_DISPATCH(d, op_axpy<T>(d, j, q, (const T*)v, (T*)out), op_axpy<T>(d, j, q, (const T*)v, (T*)out))
+    DTYPE_DISPATCH(d, op_axpy<T>(d, j, q, (const T*)v, (T*)out))
     ABI_CATCH
 }
 int adelie_hip_design_mul(adelie_hip_design* d, const void* v, const void* weights, void* out) {
     ABI_TRY
     no_view(d);
-    DTYPE_DISPATCH(d, op_sweep<T>(d, 0, d->p, (const T*)v, (const T*)weights, (T*)out, false),
-                   op_sweep<T>(d, 0, d->p, (const T*)v, (const T*)weights, (T*)out, false))
+    DTYPE_DISPATCH(d, op_sweep<T>(d, 0, d->p, (const T*)v, (const T*)weights, (T*)out, false))
     ABI_CATCH
 }
 int adelie_hip_design_mul_batch(adelie_hip_design* d, const void* V, int64_t L, void* out) {
@@ -1588,21 +1483,20 @@ int adelie_hip_design_mul_batch(adelie_hip_design* d, const void* V, int64_t L, 
     no_view(d);
     if (L < 0 || (L > 0 && (!V || !out))) throw make_core_error("mul_batch() is given inconsistent inputs!");
     if (L == 0) return 0;
-    DTYPE_DISPATCH(d, op_mul_batch<T>(d, (const T*)V, L, (T*)out), op_mul_batch<T>(d, (const T*)V, L, (T*)out))
+    DTYPE_DISPATCH(d, op_mul_batch<T>(d, (const T*)V, L, (T*)out))
     ABI_CATCH
 }
 int adelie_hip_design_cov(adelie_hip_design* d, int64_t j, int64_t q, const void* sqrt_weights, void* out) {
     ABI_TRY
     no_view(d);
     check_col(d, j, q, "cov");
-    DTYPE_DISPATCH(d, op_cov<T>(d, j, q, (const T*)sqrt_weights, (T*)out), op_cov<T>(d, j, q, (const T*)sqrt_weights, (T*)out))
+    DTYPE_DISPATCH(d, op_cov<T>(d, j, q, (const T*)sqrt_weights, (T*)out))
     ABI_CATCH
 }
 int adelie_hip_design_sq_mul(adelie_hip_design* d, const void* weights, void* out) {
     ABI_TRY
     no_view(d);
-    DTYPE_DISPATCH(d, op_sweep<T>(d, 0, d->p, (const T*)weights, (const T*)nullptr, (T*)out, true),
-                   op_sweep<T>(d, 0, d->p, (const T*)weights, (const T*)nullptr, (T*)out, true))
+    DTYPE_DISPATCH(d, op_sweep<T>(d, 0, d->p, (const T*)weights, (const T*)nullptr, (T*)out, true))
     ABI_CATCH
 }
 int adelie_hip_design_sp_tmul(adelie_hip_design* d, int64_t L, const int64_t* indptr, const int64_t* indices,
@@ -1611,8 +1505,7 @@ int adelie_hip_design_sp_tmul(adelie_hip_design* d, int64_t L, const int64_t* in
     no_view(d);
     if (L < 0) throw make_core_error("sp_tmul() is given inconsistent inputs!");
     if (L == 0) return 0;
-    DTYPE_DISPATCH(d, op_sp_tmul<T>(d, L, indptr, indices, (const T*)values, (T*)out),
-                   op_sp_tmul<T>(d, L, indptr, indices, (const T*)values, (T*)out))
+    DTYPE_DISPATCH(d, op_sp_tmul<T>(d, L, indptr, indices, (const T*)values, (T*)out))
     ABI_CATCH
 }
 
@@ -1629,9 +1522,7 @@ int adelie_hip_design_glm_path_losses(adelie_hip_design* d, int glm_kind, int64_
         throw make_core_error("glm_path_losses: elementwise single-response families only.");
     if (L > 0) {
         DTYPE_DISPATCH(d, op_path_losses<T>(d, glm_kind, L, indptr, indices, (const T*)values, (const T*)intercepts,
-                                            (const T*)offsets, (const T*)y, (const T*)weights_a, (const T*)weights_b, out),
-                       op_path_losses<T>(d, glm_kind, L, indptr, indices, (const T*)values, (const T*)intercepts,
-                                         (const T*)offsets, (const T*)y, (const T*)weights_a, (const T*)weights_b, out))
+                                            (const T*)offsets, (const T*)y, (const T*)weights_a, (const T*)weights_b, out))
     }
     ABI_CATCH
 }
@@ -1650,9 +1541,7 @@ int adelie_hip_design_multi_path_losses(adelie_hip_design* d, int glm_kind, int 
         throw make_core_error("multi_path_losses: glm_kind must be GAUSSIAN (multigaussian) or MULTINOMIAL.");
     if (L > 0) {
         DTYPE_DISPATCH(d, op_multi_path_losses<T>(d, glm_kind, K, L, indptr, indices, (const T*)values, (const T*)intercepts,
-                                                  (const T*)offsets, (const T*)y, (const T*)weights_a, (const T*)weights_b, out),
-                       op_multi_path_losses<T>(d, glm_kind, K, L, indptr, indices, (const T*)values, (const T*)intercepts,
-                                               (const T*)offsets, (const T*)y, (const T*)weights_a, (const T*)weights_b, out))
+                                                  (const T*)offsets, (const T*)y, (const T*)weights_a, (const T*)weights_b, out))
     }
     ABI_CATCH
 }

@@ -661,7 +661,7 @@ int adelie_hip_bvls_solve(adelie_hip_design* X, const adelie_hip_bvls_args* a, a
     adelie_hip_bvls_result* res = nullptr;
     try {
         if (!X || !a || !out) throw make_core_error("null argument.");
-        if (X->kind != 0 || X->cov || X->std_center)
+        if (!X->is_dense() || X->cov || X->std_center)
             throw make_core_error("bvls: X must be a plain dense design on this route.");
         const int64_t n = X->n, p = X->p;
         // state_bvls.ipp:15-74

@@ -11,6 +11,7 @@
 // p-vector or the design runs in the kernels of kernels_*.hip on the design's stream.  Per BASIL iteration the
 // host receives: the CD kernel's scalar block, the screen coefficients (<= |S| values) and abs_grad (G values).
 #include "common.hpp"
+#include "design_ops.hpp"
 #include "filter_host.hpp"
 #include "cox.hpp"
 
@@ -609,7 +610,7 @@ void run(adelie_hip_design* X, const adelie_hip_grpnet_args* a, adelie_hip_resul
         SweepBatcher* b = nullptr;
         ~BatchGuard() { if (b) b->remove(); }
     } guard;
-    if (g_sweep_batch && X->kind == 0) {
+    if (g_sweep_batch && X->is_dense()) {
         guard.b = batcher_of(X);
         guard.b->add();
         r->s.batcher = guard.b;
@@ -791,19 +792,13 @@ int adelie_hip_bench_sweep(adelie_hip_design* d, int64_t reps, double* ms_per_la
             using T = decltype(tag);
             DevBuf<T> v, out, xm, work, sc;
             v.reserve(d->n); out.reserve(d->p); xm.reserve(d->p); sc.reserve(1);
-            work.reserve(size_t(d->kind == 3 ? sweep_work_elems_csc(d->sp_parts(), d->p) : sweep_work_elems(d->n, d->p)));
             // a one-hot / interaction design: the structured sweep unless ADELIE_HIP_FACTOR_SWEEP says otherwise (read here)
-            const bool structured = d->kind == 0 && d->factor() && !d->std_center && factor_sweep_on(Hooks::factor_sweep_env());
-            if (structured) work.reserve(size_t(factor_sweep_work_elems(d->n, d->p, d->f_nchunk)));
+            const bool structured = raw_sweep_structured(*d, 0, d->p, nullptr, false, Hooks::factor_sweep_env());
+            work.reserve(size_t(raw_sweep_work_elems(*d, d->p, structured)));
             launch_fill<T>(v.p, T(1) / T(d->n), d->n, s);
             launch_fill<T>(xm.p, T(0.5), d->p, s);
             launch_fill<T>(sc.p, T(0.25), 1, s);
-            auto once = [&]() {
-                if (structured) launch_sweep_factor<T>(d->factor_view<T>(), v.p, out.p, sc.p, xm.p, work.p, s);
-                else if (d->kind == 0) launch_sweep<T>(d->dense<T>(), v.p, out.p, 0, d->p, nullptr, sc.p, xm.p, false, work.p, s);
-                else if (d->kind == 3) launch_sweep_csc<T>(d->csc<T>(), v.p, out.p, 0, d->p, nullptr, sc.p, xm.p, false, work.p, s);
-                else launch_sweep_snp<T>(d->snp(), static_cast<const T*>(d->impute), v.p, out.p, 0, d->p, nullptr, sc.p, xm.p, false, work.p, s);
-            };
+            auto once = [&]() { raw_sweep<T>(*d, v.p, out.p, 0, d->p, nullptr, sc.p, xm.p, false, structured, work.p, s); };
             once();
             AHIP_CHECK(hipStreamSynchronize(s));
             hipEvent_t e0, e1;
@@ -839,7 +834,7 @@ int adelie_hip_filter_sweep_test(adelie_hip_design* d, const double* w, const do
     try {
         if (!d || !w || !r || !groups || !group_sizes || !penalty || !grad || !exact || !info || G < 1 || n_screen < 0)
             throw make_core_error("bad arguments.");
-        if (d->kind != 0 || d->dtype != ADELIE_HIP_F64 || d->cov || d->std_center) throw make_core_error("a dense f64 design is required.");
+        if (!d->is_dense() || d->dtype != ADELIE_HIP_F64 || d->cov || d->std_center) throw make_core_error("a dense f64 design is required.");
         AHIP_CHECK(hipSetDevice(d->device));
         hipStream_t s = d->stream;
         const int64_t n = d->n, p = d->p;

@@ -683,18 +683,18 @@
 
     SweepBatcher* batcher = nullptr; // non-null while this solver is registered for sweep batching
     bool is_screen(idx i) const { return in_screen[i] != 0; }
-    bool dense() const { return D->kind == 0; }
+    bool dense() const { return D->is_dense(); }
     // sparse design kept sparse (adelie_hip_design_create_csc): sweeps, Gram rows and residual updates walk its compressed
     // forms; the solve runs on the full-Gram engines (the panel engines stream dense column slices)
-    bool sparse() const { return D->kind == 3; }
+    bool sparse() const { return D->is_csc(); }
     DevBuf<T> d_sp_delta; // p zeros between two residual updates
-    // standardized view over a dense or 2-bit design (adelie_hip_design_create_standardized): the base kernels run on the raw
-    // matrix, centring and scaling are applied around them (solver_screen.hpp: sweep / gram / axpy_cols); Gram engines only
-    bool std_generic() const { return D->std_center != nullptr && D->kind != 3; }
+    // standardized view over a dense or 2-bit design: its epilogues are composed around the raw operations of design_ops.hpp
+    // (solver_screen.hpp: sweep / gram / axpy_cols); Gram engines only
+    bool std_generic() const { return D->is_std_view(); }
     DevBuf<T> d_std_tmp, d_std_coef;
     // multi-response view (adelie_hip_design_create_multi): residual / weights live response-major on the device
-    bool multi() const { return D->kind == 2; }
-    int mk() const { return D->kind == 2 ? int(D->mK) : 1; } // class count handed to the GLM kernels
+    bool multi() const { return D->is_multi(); }
+    int mk() const { return multi() ? int(D->mK) : 1; } // class count handed to the GLM kernels
     bool multi_w_uniform = true;
     std::vector<int32_t> h_vcol, h_actcols, multi_seen; // host mirrors of d_vcol / d_actcols (block column lists)
     DevBuf<int32_t> d_mlist, d_mlist2;

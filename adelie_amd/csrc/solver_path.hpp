@@ -417,7 +417,7 @@
         }
         if (has_pen2) { // (ABI 8) the separate quadratic factors live in the one-coefficient solves only
             if (!all_scalar) throw make_core_error("penalty_l2 needs groups of one coefficient.");
-            if (cov_mode || X->kind == 2) throw make_core_error("penalty_l2 is not offered by the covariance method / the multi-response view.");
+            if (cov_mode || X->is_multi()) throw make_core_error("penalty_l2 is not offered by the covariance method / the multi-response view.");
             if (a->constraint_kind)
                 for (idx g = 0; g < G; ++g)
                     if (a->constraint_kind[g] != 0) throw make_core_error("penalty_l2 is not offered with constraints.");

@@ -16,13 +16,9 @@
             const T* is = static_cast<const T*>(D->std_iscale);
             T* tmp = d_std_tmp.reserve(size_t(2 * ncols + kVecSumScratch));
             T *raw = tmp, *raw_plain = tmp + ncols, *vsum = tmp + 2 * ncols;
-            T* work = d_work_sweep.reserve(size_t(sweep_work_elems(n, ncols)));
-            auto base = [&](T* dst, bool sq) {
-                if (dense()) launch_sweep<T>(D->dense<T>(), v, dst, 0, ncols, cols, nullptr, nullptr, sq, work, st);
-                else launch_sweep_snp<T>(D->snp(), static_cast<const T*>(D->impute), v, dst, 0, ncols, cols, nullptr, nullptr, sq, work, st);
-            };
-            base(raw, square);
-            if (square) base(raw_plain, false);
+            T* work = d_work_sweep.reserve(size_t(raw_sweep_work_elems(*D, ncols, false)));
+            raw_sweep<T>(*D, v, raw, 0, ncols, cols, nullptr, nullptr, square, false, work, st);
+            if (square) raw_sweep<T>(*D, v, raw_plain, 0, ncols, cols, nullptr, nullptr, false, false, work, st);
             launch_vec_sum<T>(v, n, vsum, st);
             launch_std_sweep_epilogue<T>(ce, is, raw, raw_plain, vsum, square, out, 0, ncols, cols, sub_scale, sub_vec, st);
             return;
@@ -32,21 +28,11 @@
             ++cnt.n_sweeps_shared;
             return;
         }
-        if (dense() && D->factor() && !cols && ncols == p && !square && factor_sweep_on(hooks.factor_sweep)) {
-            // a one-hot / interaction design: the full sweep reads Z and v instead of the expanded matrix (kernels_factor.hip)
-            launch_sweep_factor<T>(D->factor_view<T>(), v, out, sub_scale, sub_vec,
-                                   d_work_sweep.reserve(size_t(factor_sweep_work_elems(n, p, D->f_nchunk))), st);
-            ++cnt.n_sweeps_factor;
-            return;
-        }
-        if (sparse()) { // one wavefront per column over its stored entries (kernels_sparse.hip)
-            launch_sweep_csc<T>(D->csc<T>(), v, out, 0, ncols, cols, sub_scale, sub_vec, square,
-                                d_work_sweep.reserve(size_t(sweep_work_elems_csc(D->sp_parts(), ncols))), st);
-            return;
-        }
-        T* work = d_work_sweep.reserve(size_t(sweep_work_elems(n, ncols)));
-        if (dense()) launch_sweep<T>(D->dense<T>(), v, out, 0, ncols, cols, sub_scale, sub_vec, square, work, st);
-        else launch_sweep_snp<T>(D->snp(), static_cast<const T*>(D->impute), v, out, 0, ncols, cols, sub_scale, sub_vec, square, work, st);
+        // a one-hot / interaction design: the full sweep reads Z and v instead of the expanded matrix (kernels_factor.hip)
+        const bool structured = raw_sweep_structured(*D, 0, ncols, cols, square, hooks.factor_sweep);
+        T* work = d_work_sweep.reserve(size_t(raw_sweep_work_elems(*D, ncols, structured)));
+        raw_sweep<T>(*D, v, out, 0, ncols, cols, sub_scale, sub_vec, square, structured, work, st);
+        if (structured) ++cnt.n_sweeps_factor;
     }
     // `want_tail`: the step may leave the block's gradient in d_gblk itself (2-bit designs, StepTail; kernels.hpp) -- then
     // step_tailed is set and the caller skips panel_reduce; tail_xm = the by-column means of the intercept term (or nullptr)
@@ -212,57 +198,37 @@
             launch_multi_axpy_cols<T>(D->multi<T>(), cols, coef, cnt_dev, sign, out, st);
             return;
         }
-        if (sparse()) { // coefficients scattered into a p-vector that is all zero between calls, then one CSR pass
-            if (d_sp_delta.cap < size_t(p) + 8) {
-                d_sp_delta.reserve(size_t(p) + 8);
-                AHIP_CHECK(hipMemsetAsync(d_sp_delta.p, 0, (size_t(p) + 8) * sizeof(T), st));
-            }
-            launch_axpy_cols_csc<T>(D->csc<T>(), cols, coef, cnt_dev, count, sign, out, d_sp_delta.p, st);
-            return;
+        // compressed columns: coefficients scattered into a p-vector that is all zero between calls, then one CSR pass
+        if (sparse() && d_sp_delta.cap < size_t(p) + 8) {
+            d_sp_delta.reserve(size_t(p) + 8);
+            AHIP_CHECK(hipMemsetAsync(d_sp_delta.p, 0, (size_t(p) + 8) * sizeof(T), st));
         }
+        const T* kappa = nullptr;
         if (std_generic()) { // coefficients over the scales into the base design's update, then kappa off every row
-            const T* ce = static_cast<const T*>(D->std_center);
-            const T* is = static_cast<const T*>(D->std_iscale);
             const size_t cap = size_t(std::max<idx>(nv, idx(count))) + 8;
             T* c2 = d_std_coef.reserve(cap + 8);
-            T* kappa = c2 + cap;
-            launch_std_scale_coef<T>(ce, is, cols, coef, cnt_dev, count, c2, kappa, st);
-            if (dense()) launch_axpy_cols<T>(D->dense<T>(), cols, c2, cnt_dev, count, sign, out, st);
-            else launch_axpy_cols_snp<T>(D->snp(), static_cast<const T*>(D->impute), cols, c2, cnt_dev, count, sign, out, st);
-            launch_vec_shift<T>(out, n, kappa, sign, cnt_dev, st);
-            return;
+            launch_std_scale_coef<T>(static_cast<const T*>(D->std_center), static_cast<const T*>(D->std_iscale), cols, coef, cnt_dev,
+                                     count, c2, c2 + cap, st);
+            coef = c2;
+            kappa = c2 + cap;
         }
-        if (dense()) launch_axpy_cols<T>(D->dense<T>(), cols, coef, cnt_dev, count, sign, out, st);
-        else launch_axpy_cols_snp<T>(D->snp(), static_cast<const T*>(D->impute), cols, coef, cnt_dev, count, sign, out, st);
+        raw_axpy_cols<T>(*D, cols, coef, cnt_dev, count, sign, out, d_sp_delta.p, st);
+        if (kappa) launch_vec_shift<T>(out, n, kappa, sign, cnt_dev, st);
     }
     void gram(const T* w, idx M, idx pos0, idx N, const T* xm, bool center) {
-        T* work = d_work_gram.reserve(size_t(sparse() ? gram_work_elems_csc(n, M, N, D->sp_parts()) : gram_work_elems(n, M, N)));
+        T* work = d_work_gram.reserve(size_t(raw_gram_work_elems(*D, n, M, N)));
+        const bool stdv = std_generic(); // raw X^T W X of the base design in place, then the view's rank-one corrections over the panel
         t_gram.begin(st);
-        if (std_generic()) { // raw X^T W X of the base design in place, then the view's rank-one corrections over the panel
-            const T* ce = static_cast<const T*>(D->std_center);
-            const T* is = static_cast<const T*>(D->std_iscale);
-            if (dense())
-                launch_gram<T>(D->dense<T>(), w, d_vcol.p, int32_t(M), 0, d_vcol.p + pos0, int32_t(N), int32_t(pos0), xm, false, d_C.p,
-                               ldc, work, st);
-            else
-                launch_gram_snp<T>(D->snp(), static_cast<const T*>(D->impute), w, d_vcol.p, int32_t(M), 0, d_vcol.p + pos0, int32_t(N),
-                                   int32_t(pos0), xm, false, d_C.p, ldc, work, st);
+        raw_gram<T>(*D, w, d_vcol.p, int32_t(M), 0, d_vcol.p + pos0, int32_t(N), int32_t(pos0), xm, center && !stdv, d_C.p, ldc, work, st);
+        if (stdv) {
             T* tmp = d_std_tmp.reserve(size_t(M + kVecSumScratch));
             T *mv = tmp, *wsum = tmp + M;
-            T* swork = d_work_sweep.reserve(size_t(sweep_work_elems(n, M)));
-            if (dense()) launch_sweep<T>(D->dense<T>(), w, mv, 0, M, d_vcol.p, nullptr, nullptr, false, swork, st);
-            else launch_sweep_snp<T>(D->snp(), static_cast<const T*>(D->impute), w, mv, 0, M, d_vcol.p, nullptr, nullptr, false, swork, st);
+            T* swork = d_work_sweep.reserve(size_t(raw_sweep_work_elems(*D, M, false)));
+            raw_sweep<T>(*D, w, mv, 0, M, d_vcol.p, nullptr, nullptr, false, false, swork, st);
             launch_vec_sum<T>(w, n, wsum, st);
-            launch_std_gram_fix<T>(ce, is, d_C.p, ldc, int32_t(M), int32_t(pos0), int32_t(N), d_vcol.p, mv, wsum, xm, center, st);
-        } else if (sparse())
-            launch_gram_csc<T>(D->csc<T>(), w, d_vcol.p, int32_t(M), 0, d_vcol.p + pos0, int32_t(N), int32_t(pos0), xm, center, d_C.p,
-                               ldc, work, st);
-        else if (dense())
-            launch_gram<T>(D->dense<T>(), w, d_vcol.p, int32_t(M), 0, d_vcol.p + pos0, int32_t(N), int32_t(pos0), xm, center,
-                           d_C.p, ldc, work, st);
-        else
-            launch_gram_snp<T>(D->snp(), static_cast<const T*>(D->impute), w, d_vcol.p, int32_t(M), 0, d_vcol.p + pos0,
-                               int32_t(N), int32_t(pos0), xm, center, d_C.p, ldc, work, st);
+            launch_std_gram_fix<T>(static_cast<const T*>(D->std_center), static_cast<const T*>(D->std_iscale), d_C.p, ldc, int32_t(M),
+                                   int32_t(pos0), int32_t(N), d_vcol.p, mv, wsum, xm, center, st);
+        }
         t_gram.end(st);
         cnt.n_gram_col_reads += M + N;
         cnt.gram_flops += 2.0 * double(n) * double(M) * double(N);

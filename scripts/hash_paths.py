@@ -51,3 +51,55 @@ print("cov_lasso", digest(st, 128), st.counters["n_panel_blocks"], int(np.max(st
 A, v = cov_of(Xg_h, yg2)
 st = ad.gaussian_cov(A=A, v=v, groups=np.arange(0, 1200, 10), alpha=0.5, **kw_d)
 print("cov_groups10", digest(st, 128, 10), st.counters["n_panel_blocks"], int(np.max(st.screen_sizes)))
+# the storage kinds the legs above do not reach: compressed columns (Gaussian, binomial), lazily standardized views of the dense
+# and of the 2-bit design (alpha = 0.5: the views' own engines, the std-view branches of sweep / gram / axpy_cols), one_hot
+import scipy.sparse as sp
+Xs_h = sp.random(3000, 400, density=0.05, random_state=rng, format="csc", dtype=np.float64)
+Xs = ad.matrix.sparse(Xs_h, resident="csc")
+ys = np.asarray(Xs_h @ (rng.normal(size=400) * (rng.uniform(size=400) < 0.1))).ravel() + 0.3 * rng.normal(size=3000)
+st = ad.grpnet(Xs, ad.glm.gaussian(ys), **kw_d)
+print("csc_gaussian", digest(st), st.counters["n_panel_blocks"])
+st = ad.grpnet(Xs, ad.glm.binomial((ys > np.median(ys)).astype(float)), early_exit=False, progress_bar=False, min_ratio=0.1,
+               lmda_path_size=12)
+print("csc_binomial", digest(st), st.counters["n_panel_blocks"])
+st = ad.grpnet(ad.matrix.standardize(Xd, lazy=True), ad.glm.gaussian(yd), alpha=0.5, **kw_d)
+print("std_dense_a05", digest(st), st.counters["n_panel_blocks"])
+st = ad.grpnet(ad.matrix.standardize(X, lazy=True), ad.glm.gaussian(yg), alpha=0.5, early_exit=False, progress_bar=False,
+               min_ratio=0.05, lmda_path_size=12)
+print("std_snp_a05", digest(st), st.counters["n_panel_blocks"])
+Zt = np.asfortranarray(np.stack([rng.randint(0, 5, size=3000), rng.normal(size=3000), rng.randint(0, 40, size=3000)], axis=1).astype(float))
+Xo = ad.matrix.one_hot(Zt, np.array([5, 0, 40]))
+st = ad.grpnet(Xo, ad.glm.gaussian(yd), groups=Xo.groups, **kw_d)
+print("one_hot", digest(st), st.counters["n_panel_blocks"], st.counters["n_sweeps_factor"])
+# the matrix operations per storage kind: one digest over the result bytes of every raw operation (lazy_cov: dense and 2-bit only)
+def ops_digest(M, with_cov):
+    r = np.random.RandomState(9)
+    n_, p_ = M.shape
+    dt = M.dtype
+    f = lambda a: np.asarray(a, dtype=dt)
+    v, w, sw = f(r.normal(size=n_)), f(r.uniform(0.5, 1.5, size=n_)), f(r.uniform(0.5, 1.5, size=n_))
+    h = hashlib.sha1()
+    o = np.empty(p_, dtype=dt); M.mul(v, w, o); h.update(o.tobytes())
+    o = np.empty(9, dtype=dt); M.bmul(5, 9, v, w, o); h.update(o.tobytes())
+    o = f(r.normal(size=n_)); M.btmul(5, 9, f(r.normal(size=9)), o); h.update(o.tobytes())
+    o = np.empty((9, 9), dtype=dt); M.cov(5, 9, sw, o); h.update(np.ascontiguousarray(o).tobytes())
+    o = np.empty(p_, dtype=dt); M.sq_mul(w, o); h.update(o.tobytes())
+    B = sp.random(4, p_, density=0.2, random_state=r, format="csr", dtype=np.float64)
+    o = np.empty((4, n_), dtype=dt); M.sp_tmul(B.astype(dt), o); h.update(o.tobytes())
+    h.update(M.mul_batch(f(r.normal(size=(9, n_)))).tobytes())
+    wa = r.uniform(0.5, 1.5, size=n_); wa /= wa.sum()
+    wb = wa * (r.uniform(size=n_) < 0.8); wb /= wb.sum()
+    for part in M.glm_path_losses(1, B, r.normal(size=4), 0.1 * r.normal(size=n_), (r.uniform(size=n_) < 0.4).astype(float), wa, wb):
+        h.update(np.asarray(part).tobytes())
+    BK = sp.random(4, p_ * 3, density=0.1, random_state=r, format="csr", dtype=np.float64)
+    for part in M.multi_path_losses(0, 3, BK, r.normal(size=(4, 3)), 0.1 * r.normal(size=(n_, 3)), r.normal(size=(n_, 3)), wa, wb):
+        h.update(np.asarray(part).tobytes())
+    if with_cov:
+        A = ad.matrix.lazy_cov(M)
+        o = np.empty((p_, p_), dtype=dt); A.to_dense(0, p_, o); h.update(np.ascontiguousarray(o).tobytes())
+    return h.hexdigest()[:16]
+Xo_h = np.asfortranarray(rng.normal(size=(2003, 300)))
+for name, M, with_cov in [("dense_f64", ad.matrix.dense(Xo_h), True),
+                          ("dense_f32", ad.matrix.dense(np.asfortranarray(Xo_h.astype(np.float32))), True),
+                          ("snp", X, True), ("csc", Xs, False), ("std_csc", ad.matrix.standardize(Xs), False)]:
+    print("ops", name, ops_digest(M, with_cov))

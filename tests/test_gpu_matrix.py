@@ -5,6 +5,7 @@ import warnings
 
 import numpy as np
 import pytest
+from scipy.sparse import csc_matrix, csr_matrix
 
 import adelie_amd as ad
 from matrix_checks import run_naive
@@ -599,3 +600,60 @@ def test_standardized_view_on_the_panel_engines(hip, oracle, monkeypatch, kind):
         # the invariants handed back are the view's: residual / gradient of the last solution
         for name in ("grad", "resid") if "irls_tol" not in kw else ("grad", "eta"):
             assert np.abs(np.asarray(getattr(a, name)) - np.asarray(getattr(o, name))).max() < 1e-6, name
+
+
+def _integer_ops(X, E, dtype, rng, j1, j, q):
+    """Every raw operation of a design on integer inputs, each asserted against numpy's integer arithmetic on E (the matrix
+    as int64): the single-column operations at column j1 (cmul) and j (ctmul), the block ones at columns [j, j + q).  Returns the
+    results so that the storage kinds can be compared with each other."""
+    n, p = E.shape
+    v = rng.randint(-2, 3, size=n)
+    w = rng.randint(0, 4, size=n)
+    sw = rng.randint(0, 3, size=n)
+    c = rng.randint(-2, 3, size=q)
+    base = rng.randint(-3, 4, size=n)
+    V = rng.randint(-2, 3, size=(3, p)) * (rng.uniform(size=(3, p)) < 0.4)
+    VB = rng.randint(-2, 3, size=(9, n))   # 9 vectors: one K-wide pass of 8, then the lone last one through the single sweep
+    f = lambda a: np.asarray(a, dtype=dtype)
+    res = {}
+    out = np.empty(p, dtype=dtype); X.mul(f(v), f(w), out); res["mul"] = (out, (v * w) @ E)
+    B = E[:, j:j + q]
+    res["cmul"] = (np.array([X.cmul(j1, f(v), f(w))]), np.array([(v * w) @ E[:, j1]]))
+    out = np.empty(q, dtype=dtype); X.bmul(j, q, f(v), f(w), out); res["bmul"] = (out, (v * w) @ B)
+    out = f(base).copy(); X.ctmul(j, 2.0, out); res["ctmul"] = (out, base + 2 * E[:, j])
+    out = f(base).copy(); X.btmul(j, q, f(c), out); res["btmul"] = (out, base + B @ c)
+    out = np.empty((q, q), dtype=dtype); X.cov(j, q, f(sw), out); res["cov"] = (out, (B.T * sw ** 2) @ B)
+    out = np.empty(p, dtype=dtype); X.sq_mul(f(w), out); res["sq_mul"] = (out, w @ E ** 2)
+    out = np.empty((3, n), dtype=dtype); X.sp_tmul(csr_matrix(f(V)), out); res["sp_tmul"] = (out, V @ E.T)
+    res["mul_batch"] = (X.mul_batch(f(VB)), VB @ E)
+    for op, (got, ref) in res.items():
+        assert np.abs(ref).max() < 2 ** 24   # exact in float32, hence in both precisions
+        assert got.dtype == dtype and np.array_equal(got, ref), op
+    return {op: got for op, (got, _) in res.items()}
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_matrix_ops_agree_exactly_across_storage_kinds(hip, monkeypatch, dtype):
+    """One matrix with entries in {0, 1, 2} held dense, as 2-bit calls and as compressed columns: on integer inputs every sum
+    stays below 2^24, so each operation must return numpy's integers exactly, and therefore the same bits on the three kinds.
+    n = 1003 is no multiple of 4 or 64.  The same for one_hot of a two-column integer table against its dense expansion, the
+    full sweeps through the structured kernel and through the dense one."""
+    n, p = 1003, 37
+    M = np.random.RandomState(11).choice([0, 1, 2], size=(n, p), p=[0.6, 0.3, 0.1])
+    kinds = {
+        "dense": ad.matrix.dense(np.asfortranarray(M.astype(dtype))),
+        "snp": ad.matrix.snp_calldata(M.astype(np.int8), dtype=dtype),
+        "csc": ad.matrix.sparse(csc_matrix(M.astype(dtype)), resident="csc"),
+    }
+    res = {k: _integer_ops(X, M, dtype, np.random.RandomState(12), 36, 5, 9) for k, X in kinds.items()}
+    for k in ("snp", "csc"):
+        for op, got in res[k].items():
+            assert np.array_equal(got, res["dense"][op]), (k, op)
+    Z = np.asfortranarray(np.random.RandomState(13).randint(0, 3, size=(n, 2)).astype(dtype))
+    E = np.stack([Z[:, 0] == 0, Z[:, 0] == 1, Z[:, 0] == 2, Z[:, 1]], axis=1).astype(np.int64)   # levels (3, 0)
+    ref = _integer_ops(ad.matrix.dense(np.asfortranarray(E.astype(dtype))), E, dtype, np.random.RandomState(14), 3, 1, 3)
+    for hook in ("1", "0"):
+        monkeypatch.setenv("ADELIE_HIP_FACTOR_SWEEP", hook)
+        got = _integer_ops(ad.matrix.one_hot(Z, np.array([3, 0])), E, dtype, np.random.RandomState(14), 3, 1, 3)
+        for op in ref:
+            assert np.array_equal(got[op], ref[op]), (hook, op)
