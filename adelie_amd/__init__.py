@@ -4,7 +4,8 @@ Mirrors the user-facing surface of JamesYang007/adelie for the ``grpnet`` hot pa
 (``solver.grpnet``, ``cv.cv_grpnet``, ``matrix.dense`` / ``matrix.snp_unphased`` / ``matrix.kronecker_eye``,
 ``glm.gaussian`` / ``glm.binomial`` / ``glm.multigaussian`` / ``glm.multinomial``, the naive State objects), the covariance
 method (``solver.gaussian_cov``), column subset selection on a resident covariance (``solver.css_cov``,
-``sklearn.CSSModelSelection``) and bounded-variable least squares (``solver.bvls``).  All numerics run in hand-written HIP
+``sklearn.CSSModelSelection``), bounded-variable least squares (``solver.bvls``) and pinball least squares on a resident
+constraint matrix (``solver.pinball``, ``matrix.dense(method="constraint")``).  All numerics run in hand-written HIP
 kernels for gfx950 behind the C ABI declared in ``include/adelie_hip.h``.
 """
 from . import configs
@@ -23,6 +24,6 @@ except ImportError:  # pragma: no cover
     pass
 from .configs import set_configs
 from .cv import cv_grpnet
-from .solver import bvls, css_cov, gaussian_cov, grpnet
+from .solver import bvls, css_cov, gaussian_cov, grpnet, pinball
 
 __version__ = "0.1.0"

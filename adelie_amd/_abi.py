@@ -172,6 +172,27 @@ BVLS_V = dict(beta=0, resid=1, grad=2, screen_set=3, active_set=4, is_screen=5, 
 BVLS_S = dict(loss=0, iters=1, n_kkt=2, screen_set_size=3, active_set_size=4, total_time=5, t_sweep_ms=6, t_gram_ms=7,
               t_fit_ms=8, n_changed=9)
 
+class PinballArgs(C.Structure):
+    """``adelie_hip_pinball_args`` (an addition to ABI 14)."""
+
+    _fields_ = [("S", C.c_void_p), ("penalty_neg", C.c_void_p), ("penalty_pos", C.c_void_p),
+                ("beta", C.c_void_p), ("resid", C.c_void_p), ("grad", C.c_void_p),
+                ("S_rows", C.c_int64), ("S_cols", C.c_int64), ("n_penalty_neg", C.c_int64), ("n_penalty_pos", C.c_int64),
+                ("n_beta", C.c_int64), ("n_resid", C.c_int64), ("n_grad", C.c_int64),
+                ("screen_set", C.c_void_p), ("screen_set_size", C.c_int64),
+                ("active_set", C.c_void_p), ("active_set_size", C.c_int64),
+                ("n_screen_set", C.c_int64), ("n_is_screen", C.c_int64), ("n_active_set", C.c_int64), ("n_is_active", C.c_int64),
+                ("n_screen_ASAT_diag", C.c_int64), ("screen_AS_rows", C.c_int64), ("screen_AS_cols", C.c_int64),
+                ("y_var", C.c_double), ("loss", C.c_double), ("kappa", C.c_int64), ("max_iters", C.c_int64),
+                ("tol", C.c_double)]
+
+
+# enum adelie_hip_pinball_vec / adelie_hip_pinball_scalar / adelie_hip_constraint_op_kind
+PINBALL_V = dict(beta=0, resid=1, grad=2, screen_set=3, active_set=4, is_screen=5, is_active=6, screen_ASAT_diag=7, screen_AS=8)
+PINBALL_S = dict(loss=0, iters=1, n_kkt=2, screen_set_size=3, active_set_size=4, total_time=5, t_sweep_ms=6, t_gram_ms=7,
+                 t_fit_ms=8, n_changed=9)
+CONS_OP = dict(tmul=0, mul=1, sp_mul=2, rvmul=3, rvtmul=4, rmmul=5, cov=6, to_dense=7)
+
 # enum adelie_hip_vec / adelie_hip_scalar
 V = dict(
     intercepts=0, devs=1, lmdas=2, lmda_path=3, screen_beta=4, grad=5, abs_grad=6, resid=7, eta=8,
@@ -213,6 +234,9 @@ HIP_SYMBOLS = [
     "bench_sweep", "filter_sweep_test",
     "css_cov_solve", "css_result_destroy", "css_result_size", "css_result_copy", "css_result_scalar", "css_result_error",
     "bvls_solve", "bvls_result_destroy", "bvls_result_size", "bvls_result_copy", "bvls_result_scalar", "bvls_result_error",
+    "design_create_constraint_dense", "design_adopt_constraint_dense_dev", "constraint_op",
+    "pinball_solve", "pinball_result_destroy", "pinball_result_size", "pinball_result_copy", "pinball_result_scalar",
+    "pinball_result_error",
 ]
 
 
@@ -334,6 +358,15 @@ class Backend:
         sig("bvls_result_copy", ci, [vp, ci, vp, i64])
         sig("bvls_result_scalar", dbl, [vp, ci])
         sig("bvls_result_error", C.c_char_p, [vp])
+        sig("design_create_constraint_dense", ci, [vp, i64, i64, ci, ci, ci, p(vp)])
+        sig("design_adopt_constraint_dense_dev", ci, [vp, i64, i64, ci, ci, ci, p(vp)])
+        sig("constraint_op", ci, [vp, ci, i64, vp, vp, i64, vp])
+        sig("pinball_solve", ci, [vp, p(PinballArgs), p(vp)])
+        sig("pinball_result_destroy", ci, [vp])
+        sig("pinball_result_size", i64, [vp, ci])
+        sig("pinball_result_copy", ci, [vp, ci, vp, i64])
+        sig("pinball_result_scalar", dbl, [vp, ci])
+        sig("pinball_result_error", C.c_char_p, [vp])
 
     def check(self, rc):
         if rc != 0:

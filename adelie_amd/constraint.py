@@ -721,14 +721,32 @@ class _Linear(_ProxNewton, ConstraintBase):
 
 def linear(A, lower: np.ndarray, upper: np.ndarray, *, vars: np.ndarray = None, copy: bool = False,
            method: str = "proximal_newton", configs: dict = None, dtype: Union[np.float32, np.float64] = None):
-    """Linear constraint ``lower <= A x <= upper`` (``lower <= 0 <= upper``) for a dense / scipy-sparse ``(m, d)`` matrix ``A``;
-    reference ``constraint.py:137-306``.  ``vars`` (``diag(A A')``, computed when absent) scales the coordinate steps of the
+    """Linear constraint ``lower <= A x <= upper`` (``lower <= 0 <= upper``) for a dense / scipy-sparse ``(m, d)`` matrix ``A`` or a
+    ``matrix.MatrixConstraintBase64/32`` object (read back to the host); reference ``constraint.py:137-306``.  ``vars`` (``diag(A A')``, computed when absent) scales the coordinate steps of the
     reference's bounded least squares; ``copy`` is accepted and not needed here."""
     if method != "proximal_newton":
         raise KeyError(method)
+    A = _constraint_matrix_to_host(A)
     lower, ld = _coerce(lower, dtype)
     upper, _ = _coerce(upper, ld)
     return _Linear(A, lower, upper, ld, configs, vars)
+
+
+def _constraint_matrix_to_host(A):
+    """A ``MatrixConstraintBase64/32`` object (the only form the reference's ``linear`` accepts) read back as an ``(m, d)``
+    array: the resident matrix in one copy, any other subclass row by row through its ``rvtmul``.  Anything else is returned
+    as it is."""
+    from . import matrix as _matrix
+
+    if not isinstance(A, _matrix.MatrixConstraintBase):
+        return A
+    if hasattr(A, "to_dense"):
+        return A.to_dense()
+    m, d = int(A.rows()), int(A.cols())
+    out = np.zeros((m, d), dtype=A.dtype)
+    for j in range(m):
+        A.rvtmul(j, A.dtype(1), out[j])
+    return out
 
 
 def render_dual_groups(constraints):

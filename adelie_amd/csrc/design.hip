@@ -470,6 +470,8 @@ void no_view(const adelie_hip_design* d) {
     if (d && d->is_multi()) throw multi_view_error();
     if (d && d->cov)
         throw make_core_error("this entry point takes a design matrix, not a covariance matrix (matrix.dense(method=\"cov\")).");
+    if (d && d->constraint)
+        throw make_core_error("this entry point takes a design matrix, not a constraint matrix (matrix.dense(method=\"constraint\")).");
 }
 void need_cov(const adelie_hip_design* d) {
     if (!d) throw make_core_error("null argument.");
@@ -555,7 +557,7 @@ void create_factor_t(adelie_hip_design* Z, std::vector<FactorBlock>& blocks, con
 
 void check_factor_source(const adelie_hip_design* Z, const int64_t* levels, const void* out, const char* what) {
     if (!Z || !levels || !out) throw make_core_error("null argument.");
-    if (!Z->is_dense() || Z->cov || Z->std_center)
+    if (!Z->is_dense() || Z->cov || Z->constraint || Z->std_center)
         throw make_core_error(std::string(what) + "(): mat must be a resident dense naive design (not an SNP, sparse, view or "
                               "covariance handle).");
     for (int64_t j = 0; j < Z->p; ++j)
@@ -739,6 +741,78 @@ void op_cov_to_dense(adelie_hip_design* d, int64_t i, int64_t q, T* out) {
         for (int64_t b = 0; b < q; ++b)
             for (int64_t a = b + 1; a < q; ++a) std::swap(out[a + b * q], out[b + a * q]);
 }
+
+// The MatrixConstraintBase operations (matrix_constraint_base.hpp) on a constraint handle: d->n == d, d->p == m, a row of A is
+// column j of the stored matrix.  Host vectors in and out; none of these is a hot path.
+template <class T>
+void op_constraint(adelie_hip_design* A, int op, int64_t j, const T* in, const int64_t* indices, int64_t ni, T* out) {
+    set_device(A);
+    hipStream_t s = A->stream;
+    const int64_t d = A->n, m = A->p;
+    const DenseView<T> Av = A->dense<T>();
+    auto up = [&](T* dst, const T* src, size_t n) { AHIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, s)); };
+    auto down = [&](T* dst, const T* src, size_t n) {
+        AHIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, s));
+        AHIP_CHECK(hipStreamSynchronize(s));
+    };
+    switch (op) {
+        case ADELIE_HIP_CONS_TMUL:
+        case ADELIE_HIP_CONS_RVMUL: { // the column sweep, over all rows of A or over row j
+            const int64_t c0 = op == ADELIE_HIP_CONS_TMUL ? 0 : j, nc = op == ADELIE_HIP_CONS_TMUL ? m : 1;
+            T* dv = scratch<T>(A->s_n1, size_t(d));
+            T* dout = scratch<T>(A->s_p1, size_t(nc));
+            T* work = scratch<T>(A->s_work, size_t(sweep_work_elems(d, nc)));
+            up(dv, in, size_t(d));
+            launch_sweep<T>(Av, dv, dout, c0, nc, nullptr, nullptr, nullptr, false, work, s);
+            down(out, dout, size_t(nc));
+            break;
+        }
+        case ADELIE_HIP_CONS_MUL:
+        case ADELIE_HIP_CONS_SP_MUL:
+        case ADELIE_HIP_CONS_RVTMUL: { // the column axpy
+            const int64_t q = op == ADELIE_HIP_CONS_MUL ? m : (op == ADELIE_HIP_CONS_SP_MUL ? ni : 1);
+            T* dout = scratch<T>(A->s_n1, size_t(d));
+            T* dcoef = scratch<T>(A->s_p1, size_t(q));
+            int32_t* dcols = scratch<int32_t>(A->s_idx1, size_t(q));
+            std::vector<int32_t> cols(static_cast<size_t>(q));
+            for (int64_t k = 0; k < q; ++k)
+                cols[size_t(k)] = int32_t(op == ADELIE_HIP_CONS_MUL ? k : (op == ADELIE_HIP_CONS_SP_MUL ? indices[k] : j));
+            if (op == ADELIE_HIP_CONS_RVTMUL) up(dout, out, size_t(d));
+            else AHIP_CHECK(hipMemsetAsync(dout, 0, size_t(d) * sizeof(T), s));
+            if (q > 0) {
+                up(dcoef, in, size_t(q));
+                AHIP_CHECK(hipMemcpyAsync(dcols, cols.data(), size_t(q) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+                launch_axpy_cols<T>(Av, dcols, dcoef, nullptr, int32_t(q), T(1), dout, s);
+            }
+            down(out, dout, size_t(d));
+            break;
+        }
+        case ADELIE_HIP_CONS_RMMUL: { // out[c] = Q[:, c] . A[j, :]: the sweep of Q's columns with row j of A as the vector
+            T* dQ = scratch<T>(A->s_misc, size_t(d) * size_t(d));
+            T* dout = scratch<T>(A->s_p1, size_t(d));
+            T* work = scratch<T>(A->s_work, size_t(sweep_work_elems(d, d)));
+            up(dQ, in, size_t(d) * size_t(d));
+            launch_sweep<T>(DenseView<T>{dQ, d, d, d}, Av.X + j * Av.ld, dout, 0, d, nullptr, nullptr, nullptr, false, work, s);
+            down(out, dout, size_t(d));
+            break;
+        }
+        case ADELIE_HIP_CONS_COV: { // AQ[k, :] = A[k, :] Q for every row, then out[a, b] = AQ[a, :] . A[b, :]
+            DevBuf<T> dQ, dAQ, dC;
+            dQ.reserve(size_t(d) * size_t(d)), dAQ.reserve(size_t(d) * size_t(m)), dC.reserve(size_t(m) * size_t(m));
+            up(dQ.p, in, size_t(d) * size_t(d));
+            launch_ptq<T>(dQ.p, d, nullptr, int32_t(d), Av.X, Av.ld, nullptr, int32_t(m), d, dAQ.p, d, s);
+            launch_ptq<T>(dAQ.p, d, nullptr, int32_t(m), Av.X, Av.ld, nullptr, int32_t(m), d, dC.p, m, s);
+            down(out, dC.p, size_t(m) * size_t(m));
+            break;
+        }
+        case ADELIE_HIP_CONS_TO_DENSE:
+            AHIP_CHECK(hipMemcpy2DAsync(out, size_t(d) * sizeof(T), Av.X, size_t(Av.ld) * sizeof(T), size_t(d) * sizeof(T), size_t(m),
+                                        hipMemcpyDeviceToHost, s));
+            AHIP_CHECK(hipStreamSynchronize(s));
+            break;
+        default: throw make_core_error("unknown constraint matrix operation.");
+    }
+}
 } // namespace
 
 extern "C" {
@@ -779,6 +853,7 @@ int adelie_hip_design_create_cov_lazy(adelie_hip_design* X, adelie_hip_design** 
     ABI_TRY
     if (!X || !out) throw make_core_error("null argument.");
     if (X->cov) throw make_core_error("mat must be a naive (n, p) matrix, not a covariance matrix.");
+    no_view(X);
     if (!X->is_dense() && !X->is_snp()) throw make_core_error("lazy_cov takes a dense or SNP design.");
     if (X->p > (int64_t(1) << 31) - 1) throw make_core_error("too many columns.");
     set_device(X);
@@ -961,7 +1036,7 @@ int adelie_hip_design_create_standardized(adelie_hip_design* src, const double* 
                                           adelie_hip_design** out) {
     ABI_TRY
     if (!src || !centers || !scales || !out) throw make_core_error("null argument.");
-    if (src->is_multi() || src->cov) no_view(src);
+    if (src->is_multi() || src->cov || src->constraint) no_view(src);
     if (src->std_center) throw make_core_error("the design is a standardized view already.");
     for (int64_t j = 0; j < src->p; ++j)
         if (!(scales[j] != 0.0)) throw make_core_error("scales must be non-zero.");
@@ -985,6 +1060,47 @@ int adelie_hip_design_create_standardized(adelie_hip_design* src, const double* 
         AHIP_CHECK(hipMemcpy(d->std_iscale, is.data(), size_t(p) * vs, hipMemcpyHostToDevice));
     }
     *out = g.release();
+    ABI_CATCH
+}
+
+// adelie.matrix.dense(method="constraint"): the (m, d) matrix A is kept row-major, which is the (d, m) column-major A' of a dense
+// handle (a row of A is one contiguous column).  `order` is the memory order of the (m, d) source.
+static int create_constraint(const void* src, bool on_device, int64_t m, int64_t d, int dtype, int order, int device,
+                             adelie_hip_design** out) {
+    ABI_TRY
+    if (!src || !out) throw make_core_error("null argument.");
+    if (m <= 0 || d <= 0) throw make_core_error("mat must be a non-empty (m, d) matrix.");
+    DesignGuard g(new_design(d, m, dtype, device));
+    const int stored = order == ADELIE_HIP_ROW_MAJOR ? ADELIE_HIP_COL_MAJOR : ADELIE_HIP_ROW_MAJOR; // of the (d, m) matrix A'
+    DTYPE_DISPATCH(g, create_dense_t<T>(g.get(), src, on_device, stored))
+    g->constraint = 1;
+    *out = g.release();
+    ABI_CATCH
+}
+int adelie_hip_design_create_constraint_dense(const void* host, int64_t m, int64_t d, int dtype, int order, int device,
+                                              adelie_hip_design** out) {
+    return create_constraint(host, false, m, d, dtype, order, device, out);
+}
+int adelie_hip_design_adopt_constraint_dense_dev(const void* dev_ptr, int64_t m, int64_t d, int dtype, int order, int device,
+                                                 adelie_hip_design** out) {
+    return create_constraint(dev_ptr, true, m, d, dtype, order, device, out);
+}
+int adelie_hip_constraint_op(adelie_hip_design* A, int op, int64_t j, const void* in, const int64_t* indices, int64_t n_indices,
+                             void* out) {
+    ABI_TRY
+    if (!A || !out) throw make_core_error("null argument.");
+    if (!A->constraint) throw make_core_error("A must be a constraint matrix (matrix.dense(method=\"constraint\")).");
+    const int64_t m = A->p;
+    if (op != ADELIE_HIP_CONS_TO_DENSE && !in) throw make_core_error("null argument.");
+    if ((op == ADELIE_HIP_CONS_RVMUL || op == ADELIE_HIP_CONS_RVTMUL || op == ADELIE_HIP_CONS_RMMUL) && (j < 0 || j >= m))
+        throw make_core_error("row index out of range.");
+    if (op == ADELIE_HIP_CONS_SP_MUL) {
+        if (n_indices < 0 || (n_indices > 0 && !indices)) throw make_core_error("sp_mul() is given inconsistent inputs!");
+        for (int64_t k = 0; k < n_indices; ++k)
+            if (indices[k] < 0 || indices[k] >= m) throw make_core_error("sp_mul(): index out of range.");
+    }
+    if (op == ADELIE_HIP_CONS_COV && double(m) * double(m) > 4e9) throw make_core_error("cov(): the (m, m) output is too large.");
+    DTYPE_DISPATCH(A, op_constraint<T>(A, op, j, (const T*)in, indices, n_indices, (T*)out))
     ABI_CATCH
 }
 
@@ -1146,7 +1262,7 @@ static void shadow_free(adelie_hip_design* o) {
 }
 
 bool adelie_hip_internal_shadow_acquire(adelie_hip_design* d, ahip::ShadowView* out) {
-    if (!d || !d->is_dense() || d->dtype != ADELIE_HIP_F64 || d->cov || d->std_center || !d->X || d->n < 1 || d->p < 1) return false;
+    if (!d || !d->is_dense() || d->dtype != ADELIE_HIP_F64 || d->cov || d->constraint || d->std_center || !d->X || d->n < 1 || d->p < 1) return false;
     adelie_hip_design* o = shadow_owner(d);
     if (o->X != d->X || o->ld != d->ld || o->n != d->n || o->p != d->p) return false;
     std::lock_guard<std::mutex> lk(o->sh_mu);
@@ -1218,7 +1334,7 @@ int adelie_hip_design_shadow_stats(adelie_hip_design* d, int64_t* out) {
 int adelie_hip_design_alias(adelie_hip_design* src, adelie_hip_design** out) {
     ABI_TRY
     if (!src || !out) throw make_core_error("null argument.");
-    if (src->is_multi() || src->cov) no_view(src);
+    if (src->is_multi() || src->cov || src->constraint) no_view(src);
     DesignGuard g(new_design(src->n, src->p, src->dtype, src->device)); // own stream, own scratch
     adelie_hip_design* d = g.get();
     d->kind = src->kind;
@@ -1246,6 +1362,7 @@ int adelie_hip_design_create_slice(adelie_hip_design* base, int64_t r0, int64_t 
                                    adelie_hip_design** out) {
     ABI_TRY
     if (!base || !out) throw make_core_error("null argument.");
+    if (base->constraint) no_view(base);
     if ((!base->is_dense() && !base->is_snp()) || base->cov || base->std_center)
         throw make_core_error("only dense and 2-bit SNP designs are sliced in place.");
     if (r0 < 0 || nr < 1 || c0 < 0 || nc < 1 || r0 + nr > base->n || c0 + nc > base->p)
@@ -1273,6 +1390,7 @@ int adelie_hip_design_create_slice(adelie_hip_design* base, int64_t r0, int64_t 
 int adelie_hip_design_create_multi(adelie_hip_design* base, int64_t K, int intercept, adelie_hip_design** out) {
     ABI_TRY
     if (!base || !out) throw make_core_error("null argument.");
+    if (base->constraint) no_view(base);
     if ((!base->is_dense() && !base->is_snp()) || base->cov || base->std_center)
         throw make_core_error("the multi-response view needs a dense or 2-bit SNP base design.");
     if (K < 1) throw make_core_error("K must be >= 1.");

@@ -162,6 +162,12 @@ template <class T>
 void launch_sp_tmul_snp(const SnpView& X, const T* impute, int64_t L, const int64_t* indptr, const int64_t* indices,
                         const T* values, T* out, hipStream_t s);
 
+// ---- product of two column-major matrices over their common rows (kernels_pinball.hip, plain LDS tiles):
+//   C[r + c*ldc] = sum_{i<K} P[i + pcol(r)*ldp] * Q[i + qcol(c)*ldq],  r < M, c < N,  pcol(r) = pcols ? pcols[r] : r
+template <class T>
+void launch_ptq(const T* P, int64_t ldp, const int32_t* pcols, int32_t M, const T* Q, int64_t ldq, const int32_t* qcols, int32_t N,
+                int64_t K, T* C, int64_t ldc, hipStream_t s);
+
 // ---- Gram (MFMA): for a in [0,M), b in [0,N):
 //   C[rowpos[a] + colpos[b]*ldc] = C[colpos[b] + rowpos[a]*ldc]
 //        = sum_i w[i] X[i,mcols[a]] X[i,ncols[b]]  - (center ? xm[mcols[a]]*xm[ncols[b]] : 0)

@@ -18,17 +18,13 @@
 //     flagged non-members are appended, in screen order, at the end of the pass.  A screen pass visits in screen order, so the
 //     list is the same; it is complete before the pass's max-iterations exit is taken.
 //
-// Synchronisation inside the fit kernel.  Every thread evaluates the scalar update of a visit redundantly from broadcast
-// reads, so no shuffle or reduction sits on the visit chain and all control flow is uniform.  g and beta are double-buffered:
-// a changed visit reads buffer `cur`, writes ALL of g and beta to the other buffer and ends with the one barrier of the visit —
-// a slow wavefront still reading g[k] / beta[k] of buffer `cur` cannot see the fast ones' stores.  Unchanged visits have no
-// barrier and no store.  No atomics anywhere: reruns are bit-identical, and the LDS and the global-memory storage of the
-// per-coordinate arrays run the same code and give the same bits.
+// Synchronisation inside the fit kernel, which this solver shares with the pinball one: cd_fit_body.hpp.
 #include <cmath>
 #include <limits>
 #include <numeric>
 
 #include "common.hpp"
+#include "cd_fit_body.hpp"
 
 namespace ahip {
 void set_last_error(const std::string& s); // design.hip
@@ -38,228 +34,23 @@ int64_t g_bvls_lds_max_ns = 0;         // adelie_hip_set_config("bvls_lds_max_ns
 
 namespace {
 
-constexpr int kBvlsThreads = 1024;
-enum { BVLS_OK = 0, BVLS_MAX_ITERS = 1 };
 
-// what a fit and the host exchange; `loss`, `iters` and `n_active` are read on entry and written on exit
-struct BvlsRec {
-    double loss;
-    int64_t iters;
-    int64_t n_visits_changed; // visits that changed a coefficient (this fit)
-    int32_t status;
-    int32_t n_active;
-    int32_t n_changed;        // coordinates whose beta differs from its value at entry (= length of the compact list)
-    int32_t pad;
-};
-
-// bytes of per-coordinate state: g x 2, beta x 2, lower, upper, vars; active list, membership flag, touched flag
+// the fit kernel (cd_fit_body.hpp) with the box rule: coordinate_descent's update (solver_bvls.hpp:44-60) and prune's predicate
 template <class T>
-constexpr size_t bvls_state_bytes(int64_t ns) {
-    return size_t(ns) * (7 * sizeof(T) + 3 * sizeof(int32_t)) + 64;
-}
-
-template <class T>
-struct BvlsFitArgs {
-    const T* G;          // (ns, ns) column-major, leading dimension ld
-    int64_t ld;
-    int32_t ns;
-    const int32_t* cols; // screen members' columns, screen order
-    const T* lower_s;    // screen order
-    const T* upper_s;
-    const T* vars_s;
-    const T* g_s;        // gradient at entry
-    T* beta_s;           // in: beta at entry; out: beta at exit
-    int32_t* act;        // in / out: active set as positions in the screen set
-    T* beta_full;        // (p,) out: beta_full[cols[a]] = beta at exit
-    int32_t* dcol;       // out: compact list for launch_axpy_cols
-    T* dlt;
-    int32_t* cnt_dev;
-    BvlsRec* rec;
-    char* scratch;       // global storage of the per-coordinate state (the non-LDS form)
-    int64_t max_iters;
-    T tol_yvar;          // tol * y_var
-};
-
-// Appends to a list the positions k = src(i), i in [0, count_in) ascending, for which keep(i, k) holds, through emit(slot, k);
-// returns the number appended (the same value in every thread).  The slots are handed out in ascending i: per trip a ballot
-// gives the rank inside a wavefront and the wavefronts' counts go through `wcnt` (LDS, 16 ints).
-template <class Src, class Keep, class Emit>
-__device__ __forceinline__ int bvls_compact(int count_in, int* wcnt, Src src, Keep keep, Emit emit) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = (blockDim.x + 63) >> 6;
-    int total = 0;
-    for (int base = 0; base < count_in; base += blockDim.x) {
-        const int i = base + tid;
-        int k = 0;
-        bool f = false;
-        if (i < count_in) {
-            k = src(i);
-            f = keep(i, k);
-        }
-        const unsigned long long m = __ballot(f);
-        const int within = __popcll(m & ((1ull << lane) - 1ull));
-        if (lane == 0) wcnt[wave] = __popcll(m);
-        __syncthreads();
-        int off = 0, tot = 0;
-        for (int w = 0; w < nw; ++w) {
-            const int c = wcnt[w];
-            off += w < wave ? c : 0;
-            tot += c;
-        }
-        if (f) emit(total + off + within, k);
-        total += tot;
-        __syncthreads();
-    }
-    return total;
-}
-
-template <class T, bool LDS>
-__global__ __launch_bounds__(kBvlsThreads) void bvls_fit_kernel(BvlsFitArgs<T> A) {
-    extern __shared__ __attribute__((aligned(16))) char bvls_sm[];
-    __shared__ int wcnt[kBvlsThreads / 64];
-    const int tid = threadIdx.x, bd = blockDim.x, ns = A.ns;
-    // no __restrict__ on the state: the same arrays are read and written across barriers
-    char* base = LDS ? bvls_sm : A.scratch;
-    T* g0 = reinterpret_cast<T*>(base);
-    T* g1 = g0 + ns;
-    T* b0 = g1 + ns;
-    T* b1 = b0 + ns;
-    T* lo = b1 + ns;
-    T* up = lo + ns;
-    T* var = up + ns;
-    int32_t* act = reinterpret_cast<int32_t*>(var + ns);
-    int32_t* isact = act + ns;
-    int32_t* touched = isact + ns;
-
-    int nact = A.rec->n_active;
-    for (int a = tid; a < ns; a += bd) {
-        g0[a] = A.g_s[a];
-        b0[a] = A.beta_s[a];
-        lo[a] = A.lower_s[a];
-        up[a] = A.upper_s[a];
-        var[a] = A.vars_s[a];
-        isact[a] = 0;
-        touched[a] = 0;
-    }
-    __syncthreads();
-    for (int i = tid; i < nact; i += bd) {
-        const int k = A.act[i];
-        act[i] = k;
-        isact[k] = 1;
-    }
-    __syncthreads();
-
-    T loss = T(A.rec->loss);
-    int64_t iters = A.rec->iters;
-    int64_t nvis = 0;
-    const int64_t max_iters = A.max_iters;
-    const T tol_yvar = A.tol_yvar;
-    int cur = 0, status = BVLS_OK;
-    T convg = T(0);
-
-    // coordinate_descent's body for position k (solver_bvls.hpp:44-60); SCREEN: raise the touched flag (add_active)
-    auto visit = [&](int k, bool screen) {
+struct BvlsRule {
+    static __device__ __forceinline__ T update(T vk, T lk, T uk, T gk, T bk) {
 #pragma clang fp contract(off)
-        const T* gc = cur ? g1 : g0;
-        const T* bc = cur ? b1 : b0;
-        const T vk = var[k], lk = lo[k], uk = up[k], gk = gc[k], bk = bc[k];
         const T step = (vk <= T(0)) ? T(0) : (gk / vk);
         const T cand = bk + step;
         const T hi = (cand < lk) ? lk : cand; // std::max(cand, lk)
-        const T bn = (uk < hi) ? uk : hi;     // std::min(hi, uk)
-        if (bn == bk) return;
-        const T del = bn - bk;
-        const T sds = vk * del * del;
-        convg = (convg < sds) ? sds : convg;
-        loss -= del * gk - T(0.5) * sds;
-        T* gn = cur ? g0 : g1;
-        T* bx = cur ? b0 : b1;
-        const T* Gk = A.G + int64_t(k) * A.ld;
-        for (int a = tid; a < ns; a += bd) {
-            gn[a] = gc[a] - Gk[a] * del;
-            bx[a] = a == k ? bn : bc[a];
-        }
-        if (screen && tid == 0) touched[k] = 1;
-        ++nvis;
-        cur ^= 1;
-        __syncthreads();
-    };
-    auto prune = [&]() { // in place: a kept member moves to a slot at or before its own
-        const T* bc = cur ? b1 : b0;
-        nact = bvls_compact(
-            nact, wcnt, [&](int i) { return act[i]; },
-            [&](int, int k) {
-                const T b = bc[k];
-                const bool drop = b <= lo[k] || b >= up[k];
-                if (drop) isact[k] = 0;
-                return !drop;
-            },
-            [&](int slot, int k) { act[slot] = k; });
-    };
+        return (uk < hi) ? uk : hi;           // std::min(hi, uk)
+    }
+    static __device__ __forceinline__ bool drop(T b, T lk, T uk) { return b <= lk || b >= uk; }
+};
+using BvlsRec = CdFitRec;
+template <class T> using BvlsFitArgs = CdFitArgs<T>;
+enum { BVLS_OK = CD_FIT_OK, BVLS_MAX_ITERS = CD_FIT_MAX_ITERS };
 
-    while (true) { // fit(): solver_bvls.hpp:175-214
-        ++iters;
-        convg = T(0);
-        for (int k = 0; k < ns; ++k) visit(k, true);
-        {   // the pass's add_active calls, in screen order
-            const int base_n = nact;
-            nact += bvls_compact(
-                ns, wcnt, [&](int i) { return i; }, [&](int, int k) { return touched[k] != 0 && isact[k] == 0; },
-                [&](int slot, int k) { act[base_n + slot] = k; });
-            for (int a = tid; a < ns; a += bd) {
-                if (touched[a]) isact[a] = 1;
-                touched[a] = 0;
-            }
-            __syncthreads();
-        }
-        if (iters >= max_iters) {
-            status = BVLS_MAX_ITERS;
-            break;
-        }
-        if (convg <= tol_yvar) {
-            prune();
-            break;
-        }
-        bool stop = false;
-        while (true) { // solve_active(): solver_bvls.hpp:91-111
-            ++iters;
-            convg = T(0);
-            for (int i = 0; i < nact; ++i) visit(act[i], false);
-            if (iters >= max_iters) {
-                status = BVLS_MAX_ITERS;
-                stop = true;
-                break;
-            }
-            if (convg <= tol_yvar) break;
-        }
-        if (stop) break;
-        prune();
-    }
-
-    // exit: the compact (column, change) list, beta, the active set, the report
-    const T* bc = cur ? b1 : b0;
-    const int nchg = bvls_compact(
-        ns, wcnt, [&](int i) { return i; }, [&](int, int k) { return bc[k] != A.beta_s[k]; },
-        [&](int slot, int k) {
-            A.dcol[slot] = A.cols[k];
-            A.dlt[slot] = bc[k] - A.beta_s[k];
-        });
-    // (bvls_compact ends with a barrier: every read of beta at entry is done)
-    for (int a = tid; a < ns; a += bd) {
-        const T b = bc[a];
-        A.beta_s[a] = b;
-        A.beta_full[A.cols[a]] = b;
-    }
-    for (int i = tid; i < nact; i += bd) A.act[i] = act[i];
-    if (tid == 0) {
-        A.rec->loss = double(loss);
-        A.rec->iters = iters;
-        A.rec->n_visits_changed = nvis;
-        A.rec->status = status;
-        A.rec->n_active = nact;
-        A.rec->n_changed = nchg;
-        A.cnt_dev[0] = nchg;
-    }
-}
 
 // viols_j = max(grad_j, 0) [beta_j < upper_j] - min(grad_j, 0) [beta_j > lower_j]   (solver_bvls.hpp:266-271); grad is kept
 template <class T>
@@ -294,7 +85,6 @@ __global__ __launch_bounds__(256) void bvls_gather_kernel(const int32_t* __restr
     }
 }
 
-unsigned blocks_for(int64_t n, int per) { return unsigned((n + per - 1) / per); }
 
 } // namespace
 } // namespace ahip
@@ -314,55 +104,6 @@ struct adelie_hip_bvls_result {
 };
 
 namespace {
-
-struct Pinned {
-    void* p = nullptr;
-    size_t bytes = 0;
-    explicit Pinned(size_t n) : bytes((n + 4095) / 4096 * 4096) {
-        p = HostPool::take(bytes, hipHostMallocDefault);
-        if (!p) throw core_error("adelie_hip: hipHostMalloc failed");
-    }
-    ~Pinned() { HostPool::give(p, bytes, hipHostMallocDefault); }
-};
-
-// HIP-event time of the three device phases; collected after a stream synchronisation
-struct PhaseTimer {
-    struct Span { hipEvent_t a, b; int cat; };
-    std::vector<Span> open;
-    std::vector<hipEvent_t> idle;
-    double ms[3] = {0, 0, 0};
-    hipEvent_t get() {
-        if (!idle.empty()) {
-            hipEvent_t e = idle.back();
-            idle.pop_back();
-            return e;
-        }
-        hipEvent_t e;
-        AHIP_CHECK(hipEventCreate(&e));
-        return e;
-    }
-    void begin(int cat, hipStream_t s) {
-        Span sp{get(), get(), cat};
-        AHIP_CHECK(hipEventRecord(sp.a, s));
-        open.push_back(sp);
-    }
-    void end(hipStream_t s) { AHIP_CHECK(hipEventRecord(open.back().b, s)); }
-    void collect() { // (the stream is idle)
-        for (const Span& sp : open) {
-            float t = 0;
-            if (hipEventElapsedTime(&t, sp.a, sp.b) == hipSuccess) ms[sp.cat] += double(t);
-            else (void)hipGetLastError();
-            idle.push_back(sp.a);
-            idle.push_back(sp.b);
-        }
-        open.clear();
-    }
-    ~PhaseTimer() {
-        for (const Span& sp : open) idle.push_back(sp.a), idle.push_back(sp.b);
-        for (hipEvent_t e : idle) (void)hipEventDestroy(e);
-    }
-};
-enum { PH_SWEEP = 0, PH_GRAM = 1, PH_FIT = 2 };
 
 template <class T>
 struct BvlsSolver {
@@ -393,7 +134,7 @@ struct BvlsSolver {
     bool have_viols = false;
     int64_t ns = 0;
     int lds_limit = 0;
-    bool attr_done[2] = {false, false};
+    bool attr_done = false;
 
     T loss;
     int64_t iters = 0, n_kkt = 0, nact = 0;
@@ -457,39 +198,24 @@ struct BvlsSolver {
         timer.end(s);
     }
     void gather(int64_t a0, const T* src, bool by_col) {
-        hipLaunchKernelGGL((bvls_gather_kernel<T>), dim3(blocks_for(ns, 256)), dim3(256), 0, s, d_cols.p, int32_t(ns), int32_t(a0),
+        hipLaunchKernelGGL((bvls_gather_kernel<T>), dim3(cd_blocks_for(ns, 256)), dim3(256), 0, s, d_cols.p, int32_t(ns), int32_t(a0),
                            src, by_col ? 1 : 0, d_lower.p, d_upper.p, d_vars.p, d_beta.p, d_g.p, d_lower_s.p, d_upper_s.p,
                            d_vars_s.p, d_beta_s.p);
     }
 
-    template <bool LDS>
-    void launch_fit(const BvlsFitArgs<T>& fa, unsigned threads, size_t lds) {
-        if (LDS && !attr_done[1]) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(bvls_fit_kernel<T, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit);
-            (void)hipGetLastError();
-            attr_done[1] = true;
-        }
-        hipLaunchKernelGGL((bvls_fit_kernel<T, LDS>), dim3(1), dim3(threads), LDS ? lds : 0, s, fa);
-    }
     void fit(BvlsRec* h_rec) {
         BvlsFitArgs<T> fa;
         fa.G = d_G.p, fa.ld = ld, fa.ns = int32_t(ns), fa.cols = d_cols.p;
         fa.lower_s = d_lower_s.p, fa.upper_s = d_upper_s.p, fa.vars_s = d_vars_s.p, fa.g_s = d_g.p, fa.beta_s = d_beta_s.p;
         fa.act = d_act.p, fa.beta_full = d_beta.p, fa.dcol = d_dcol.p, fa.dlt = d_dlt.p, fa.cnt_dev = d_cnt.p, fa.rec = d_rec.p;
         fa.max_iters = a->max_iters;
+        fa.dcol_src = d_cols.p;
         fa.tol_yvar = T(a->tol) * T(a->y_var);
-        const size_t bytes = bvls_state_bytes<T>(ns);
-        // the static LDS of the kernel (the wavefront counts) comes out of the same budget
-        const bool lds = bytes + 256 <= size_t(lds_limit) && (g_bvls_lds_max_ns <= 0 || ns <= g_bvls_lds_max_ns);
-        fa.scratch = lds ? nullptr : d_scratch.reserve(bytes);
-        const unsigned threads = unsigned(std::min<int64_t>(kBvlsThreads, std::max<int64_t>(64, (ns + 63) / 64 * 64)));
         h_rec->loss = double(loss), h_rec->iters = iters, h_rec->n_visits_changed = 0, h_rec->status = 0;
         h_rec->n_active = int32_t(nact), h_rec->n_changed = 0, h_rec->pad = 0;
         AHIP_CHECK(hipMemcpyAsync(d_rec.p, h_rec, sizeof(BvlsRec), hipMemcpyHostToDevice, s));
         timer.begin(PH_FIT, s);
-        if (lds) launch_fit<true>(fa, threads, bytes);
-        else launch_fit<false>(fa, threads, 0);
+        launch_cd_fit<T, BvlsRule<T>>(fa, lds_limit, g_bvls_lds_max_ns, d_scratch, attr_done, s);
         timer.end(s);
         // r -= X * delta
         launch_axpy_cols<T>(Xv, d_dcol.p, d_dlt.p, d_cnt.p, 0, T(-1), d_r.p, s);
@@ -599,7 +325,7 @@ struct BvlsSolver {
             // kkt_screen(): :229-304
             ++n_kkt;
             vmul_sweep(nullptr, p, d_grad.p);
-            hipLaunchKernelGGL((bvls_viols_kernel<T>), dim3(blocks_for(p, 256)), dim3(256), 0, s, d_grad.p, d_beta.p, d_lower.p,
+            hipLaunchKernelGGL((bvls_viols_kernel<T>), dim3(cd_blocks_for(p, 256)), dim3(256), 0, s, d_grad.p, d_beta.p, d_lower.p,
                                d_upper.p, p, d_viols.p);
             AHIP_CHECK(hipMemcpyAsync(h_viols.data(), d_viols.p, size_t(p) * sizeof(T), hipMemcpyDeviceToHost, s));
             AHIP_CHECK(hipStreamSynchronize(s));
@@ -661,7 +387,7 @@ int adelie_hip_bvls_solve(adelie_hip_design* X, const adelie_hip_bvls_args* a, a
     adelie_hip_bvls_result* res = nullptr;
     try {
         if (!X || !a || !out) throw make_core_error("null argument.");
-        if (!X->is_dense() || X->cov || X->std_center)
+        if (!X->is_dense() || X->cov || X->constraint || X->std_center)
             throw make_core_error("bvls: X must be a plain dense design on this route.");
         const int64_t n = X->n, p = X->p;
         // state_bvls.ipp:15-74

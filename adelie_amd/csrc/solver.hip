@@ -652,6 +652,8 @@ void adelie_hip_internal_batch_stats(void* b, double* out) {
 namespace ahip {
 extern double g_bvls_gram_limit_mb; // kernels_bvls.hip
 extern int64_t g_bvls_lds_max_ns;
+extern double g_pinball_gram_limit_mb; // kernels_pinball.hip
+extern int64_t g_pinball_lds_max_ns;
 } // namespace ahip
 
 extern "C" {
@@ -667,6 +669,8 @@ int adelie_hip_set_config(const char* name, double value) {
     } else if (nm == "pool_trim") DevPool::trim();
     else if (nm == "bvls_gram_limit_mb") ahip::g_bvls_gram_limit_mb = value > 0 ? value : 16384.0;
     else if (nm == "bvls_lds_max_ns") ahip::g_bvls_lds_max_ns = value > 0 ? int64_t(value) : 0;
+    else if (nm == "pinball_gram_limit_mb") ahip::g_pinball_gram_limit_mb = value > 0 ? value : 16384.0;
+    else if (nm == "pinball_lds_max_ns") ahip::g_pinball_lds_max_ns = value > 0 ? int64_t(value) : 0;
     else {
         set_last_error("adelie_core: unknown config name.");
         return 1;
@@ -711,6 +715,7 @@ static int solve_entry(adelie_hip_design* X, const adelie_hip_grpnet_args* args,
         if (!X || !args || !out) throw make_core_error("null argument.");
         if (cov && !X->cov) throw make_core_error("A must be a covariance matrix (matrix.dense(method=\"cov\")).");
         if (!cov && X->cov) throw make_core_error("X is a covariance matrix: use gaussian_cov for the covariance method.");
+        if (X->constraint) throw make_core_error("X is a constraint matrix (matrix.dense(method=\"constraint\")): use pinball.");
         auto* res = new adelie_hip_result();
         try {
             if (X->dtype == ADELIE_HIP_F64) run<double>(X, args, res);
@@ -834,7 +839,7 @@ int adelie_hip_filter_sweep_test(adelie_hip_design* d, const double* w, const do
     try {
         if (!d || !w || !r || !groups || !group_sizes || !penalty || !grad || !exact || !info || G < 1 || n_screen < 0)
             throw make_core_error("bad arguments.");
-        if (!d->is_dense() || d->dtype != ADELIE_HIP_F64 || d->cov || d->std_center) throw make_core_error("a dense f64 design is required.");
+        if (!d->is_dense() || d->dtype != ADELIE_HIP_F64 || d->cov || d->constraint || d->std_center) throw make_core_error("a dense f64 design is required.");
         AHIP_CHECK(hipSetDevice(d->device));
         hipStream_t s = d->stream;
         const int64_t n = d->n, p = d->p;

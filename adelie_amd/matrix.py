@@ -45,8 +45,76 @@ class MatrixCovBase32(MatrixCovBase):
     dtype = np.float32
 
 
+class MatrixConstraintBase:
+    """Base of the constraint matrices ``A`` ``(m, d)`` (role of ``MatrixConstraintBase{32,64}``,
+    ``matrix_constraint_base.hpp``).  A subclass defines ``rows()``, ``cols()`` and the operations below; outputs are
+    pre-allocated arrays written in place, as in the reference:
+
+    * ``rmmul(j, Q, out)``: ``out = A[j] Q``; ``rvmul(j, v)``: ``A[j] . v``; ``rvtmul(j, v, out)``: ``out += v A[j]``
+      (``rmmul_safe`` / ``rvmul_safe`` are the same operations, callable from a parallel region in the reference);
+    * ``mul(v, out)``: ``out = v' A`` ``(d,)``; ``tmul(v, out)``: ``out = A v`` ``(m,)``; ``cov(Q, out)``: ``out = A Q A'``;
+    * ``sp_mul(indices, values, out)``: ``out = sum_i values[i] A[indices[i]]``."""
+
+    dtype = None
+
+    def rows(self):
+        raise NotImplementedError
+
+    def cols(self):
+        raise NotImplementedError
+
+    def rmmul(self, j, Q, out):
+        raise NotImplementedError
+
+    def rmmul_safe(self, j, Q, out):
+        return self.rmmul(j, Q, out)
+
+    def rvmul(self, j, v):
+        raise NotImplementedError
+
+    def rvmul_safe(self, j, v):
+        return self.rvmul(j, v)
+
+    def rvtmul(self, j, v, out):
+        raise NotImplementedError
+
+    def mul(self, v, out):
+        raise NotImplementedError
+
+    def tmul(self, v, out):
+        raise NotImplementedError
+
+    def cov(self, Q, out):
+        raise NotImplementedError
+
+    def sp_mul(self, indices, values, out):
+        raise NotImplementedError
+
+    @property
+    def ndim(self):
+        return 2
+
+    @property
+    def shape(self):
+        return (self.rows(), self.cols())
+
+
+class MatrixConstraintBase64(MatrixConstraintBase):
+    dtype = np.float64
+
+
+class MatrixConstraintBase32(MatrixConstraintBase):
+    dtype = np.float32
+
+
 def _as(v, dtype):
     return np.ascontiguousarray(v, dtype=dtype)
+
+
+def _no_constraint(mat, what):
+    """The views and copies of naive designs do not take a constraint matrix."""
+    if isinstance(mat, MatrixConstraintBase):
+        raise RuntimeError(f"adelie_amd: {what} takes a design matrix, not a constraint matrix (matrix.dense(method=\"constraint\")).")
 
 
 class PyMatrixNaiveTranspose:
@@ -662,6 +730,7 @@ def kronecker_eye(mat, K: int, *, n_threads: int = 1):
     """``mat (x) I_K`` as a view of a resident design (reference ``adelie.matrix.kronecker_eye``,
     ``matrix_naive_kronecker_eye.ipp``).  An ``(n, 1)`` array of ones is recognised as the intercept block that
     :func:`concatenate` puts in front of ``kronecker_eye(X, K)``."""
+    _no_constraint(mat, "kronecker_eye")
     if isinstance(mat, np.ndarray):
         if mat.ndim == 2 and mat.shape[1] == 1 and np.all(mat == 1):
             return _OnesKron(mat.shape[0], int(K), mat.dtype.type)
@@ -685,6 +754,8 @@ def concatenate(mats, *, axis: int = 0, n_threads: int = 1):
       dense design on the device (``adelie_hip_design_create_concat``); the reference keeps a list of views and dispatches
       every operation to the pieces (``matrix_naive_concatenate.ipp``)."""
     mats = list(mats)
+    for m in mats:
+        _no_constraint(m, "concatenate")
     if (axis == 1 and len(mats) == 2 and isinstance(mats[0], _OnesKron) and isinstance(mats[1], _MultiView)
             and mats[1]._icpt == 0 and mats[0].K == mats[1]._K and mats[0].n == mats[1]._base.rows()):
         return _multi_view(mats[1]._base, mats[1]._K, True)
@@ -734,7 +805,8 @@ def dense(mat, *, method: str = "naive", copy: bool = False, n_threads: int = 1,
         not be modified while the handle lives: a float64 design keeps a float32 copy of itself for the invariance sweeps of
         Gaussian paths (``drop_shadow()`` after a modification has the copy made again).
     method : str
-        Only ``"naive"`` is on the hot path.
+        ``"naive"`` (a design), ``"cov"`` (a covariance matrix for ``gaussian_cov`` / ``css_cov``) or ``"constraint"`` (an
+        ``(m, d)`` constraint matrix for ``pinball``, kept row-major in HBM).
     n_threads : int
         Accepted for API parity (the reference's OpenMP thread count); must be >= 1.
     device : int
@@ -742,8 +814,10 @@ def dense(mat, *, method: str = "naive", copy: bool = False, n_threads: int = 1,
     """
     if method == "cov":
         return _cov_dense(_abi.hip_backend(), "design_create_cov_dense", mat, n_threads, device)
+    if method == "constraint":
+        return _constraint_dense(_abi.hip_backend(), mat, n_threads, device)
     if method != "naive":
-        raise ValueError("method must be one of 'naive' or 'cov'.")
+        raise ValueError("method must be one of 'naive', 'cov' or 'constraint'.")
     if n_threads < 1:
         raise RuntimeError("adelie_core: n_threads must be >= 1.")
     backend = _abi.hip_backend()
@@ -1157,6 +1231,7 @@ def standardize(mat, centers=None, scales=None, ddof: int = 0, *, n_threads: int
       cell), a copy of dense ones.
 
     ``_centers`` / ``_scales`` are attached to the result."""
+    _no_constraint(mat, "standardize")
     if isinstance(mat, (list, np.ndarray)):
         mat = np.array(mat, order="F", copy=True)
         if centers is None:
@@ -1195,6 +1270,7 @@ def subset(mat, indices, *, axis: int = 0, n_threads: int = 1):
     """``mat[indices]`` (``axis=0``) or ``mat[:, indices]`` (``axis=1``) as a new design (reference ``adelie.matrix.subset``,
     ``matrix.py:1538-1640``, ``matrix_naive_subset.ipp``).  As the reference notes, to fit on a subset of the observations it
     is cheaper to zero their weights than to subset the rows."""
+    _no_constraint(mat, "subset")
     if isinstance(mat, np.ndarray):
         return mat[indices] if axis == 0 else mat[:, indices]
     indices = np.asarray(indices)
@@ -1289,6 +1365,8 @@ def as_design(X, *, n_threads: int = 1):
     :func:`dense`), a native design handle (returned as is), or a user-defined matrix class (:func:`from_plugin`)."""
     if isinstance(X, MatrixCovBase):
         raise RuntimeError("X is a covariance matrix (matrix.dense(method=\"cov\")): use gaussian_cov for the covariance method.")
+    if isinstance(X, MatrixConstraintBase):
+        raise RuntimeError("X is a constraint matrix (matrix.dense(method=\"constraint\")): use pinball.")
     if hasattr(X, "_backend"):
         return X
     if isinstance(X, np.ndarray) or type(X).__module__.startswith("torch"):
@@ -1369,6 +1447,146 @@ class _CovMatrix:
         buf = np.empty((p, p), dtype=self.dtype, order="F")
         self._backend.check(self._backend.fn("design_cov_to_dense")(self._handle, int(i), int(p), buf.ctypes.data))
         out[...] = buf
+
+
+class _ConstraintMatrix:
+    """An ``(m, d)`` constraint matrix resident in HBM (``adelie.matrix.dense(method="constraint")``, reference
+    ``MatrixConstraintDense``): row-major, so that a row of ``A`` is contiguous, ``A v`` is the column sweep of the stored
+    ``(d, m)`` matrix and ``v' A`` its column axpy.  Methods are the ``MatrixConstraintBase`` virtuals, one C-ABI call each
+    (``adelie_hip_constraint_op``).  ``solver.pinball`` solves on it natively."""
+
+    def _init_native(self, backend, handle, n_threads, keep):
+        self._backend, self._handle, self._n_threads, self._keep = backend, handle, n_threads, keep
+        self._m = int(backend.fn("design_cols")(handle))
+        self._d = int(backend.fn("design_rows")(handle))
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h is not None:
+            try:
+                self._backend.fn("design_destroy")(h)
+            except Exception:
+                pass
+            self._handle = None
+
+    def rows(self):
+        return self._m
+
+    def cols(self):
+        return self._d
+
+    def _chk(self, cond, what):
+        if not cond:
+            raise RuntimeError("adelie_core: %s() is given inconsistent inputs!" % what)
+
+    def _op(self, name, j, arr, out, indices=None):
+        n_idx = 0 if indices is None else indices.size
+        self._backend.check(self._backend.fn("constraint_op")(
+            self._handle, _abi.CONS_OP[name], int(j), None if arr is None else arr.ctypes.data,
+            indices.ctypes.data if n_idx else None, n_idx, out.ctypes.data))
+
+    def _buf(self, out, n):
+        ok = isinstance(out, np.ndarray) and out.dtype == self.dtype and out.flags.c_contiguous and out.ndim == 1
+        return out if ok else np.empty(n, dtype=self.dtype)
+
+    def rmmul(self, j, Q, out):
+        Q = np.asarray(Q)
+        self._chk(0 <= j < self._m and Q.shape == (self._d, self._d) and len(out) == self._d, "rmmul")
+        buf = self._buf(out, self._d)
+        self._op("rmmul", j, np.asfortranarray(Q, dtype=self.dtype), buf)
+        if buf is not out:
+            out[...] = buf
+
+    rmmul_safe = rmmul
+
+    def rvmul(self, j, v):
+        self._chk(0 <= j < self._m and len(v) == self._d, "rvmul")
+        o = np.empty(1, dtype=self.dtype)
+        self._op("rvmul", j, _as(v, self.dtype), o)
+        return o[0]
+
+    rvmul_safe = rvmul
+
+    def rvtmul(self, j, v, out):
+        self._chk(0 <= j < self._m and len(out) == self._d, "rvtmul")
+        buf = out if self._buf(out, self._d) is out else np.array(out, dtype=self.dtype)
+        self._op("rvtmul", j, np.array([v], dtype=self.dtype), buf)
+        if buf is not out:
+            out[...] = buf
+
+    def mul(self, v, out):
+        self._chk(len(v) == self._m and len(out) == self._d, "mul")
+        buf = self._buf(out, self._d)
+        self._op("mul", 0, _as(v, self.dtype), buf)
+        if buf is not out:
+            out[...] = buf
+
+    def tmul(self, v, out):
+        self._chk(len(v) == self._d and len(out) == self._m, "tmul")
+        buf = self._buf(out, self._m)
+        self._op("tmul", 0, _as(v, self.dtype), buf)
+        if buf is not out:
+            out[...] = buf
+
+    def cov(self, Q, out):
+        Q = np.asarray(Q)
+        self._chk(Q.shape == (self._d, self._d) and out.shape == (self._m, self._m), "cov")
+        buf = np.empty((self._m, self._m), dtype=self.dtype, order="F")
+        self._op("cov", 0, np.asfortranarray(Q, dtype=self.dtype), buf)
+        out[...] = buf
+
+    def sp_mul(self, indices, values, out):
+        indices = np.ascontiguousarray(indices, dtype=np.int64)
+        values = _as(values, self.dtype)
+        self._chk(indices.ndim == 1 and indices.size == values.size and len(out) == self._d, "sp_mul")
+        buf = self._buf(out, self._d)
+        self._op("sp_mul", 0, values, buf, indices)
+        if buf is not out:
+            out[...] = buf
+
+    def to_dense(self):
+        """``A`` as an ``(m, d)`` C-ordered host array."""
+        out = np.empty((self._m, self._d), dtype=self.dtype)
+        self._op("to_dense", 0, None, out)
+        return out
+
+
+def _constraint_dense(backend, mat, n_threads, device):
+    """``adelie.matrix.dense(mat, method="constraint")``: a C-ordered array goes to HBM as it lies, an F-ordered one is
+    transposed once on the host; a device tensor is adopted (C-contiguous: in place; F-contiguous: one transposed copy)."""
+    if n_threads < 1:
+        raise RuntimeError("adelie_core: n_threads must be >= 1.")
+    handle = _abi.C.c_void_p()
+    if not isinstance(mat, np.ndarray) and type(mat).__module__.startswith("torch"):
+        t = mat
+        if t.dim() != 2 or not t.is_cuda:
+            raise RuntimeError("torch input must be a 2-D tensor in device memory.")
+        dtype = np.dtype({"torch.float64": np.float64, "torch.float32": np.float32}[str(t.dtype)])
+        m, d = t.shape
+        if t.is_contiguous():
+            order = _abi.ROW_MAJOR
+        elif t.stride() == (1, m):
+            order = _abi.COL_MAJOR
+        else:
+            raise RuntimeError("torch input must be F- or C-contiguous.")
+        backend.check(backend.fn("design_adopt_constraint_dense_dev")(
+            t.data_ptr(), m, d, _abi.dtype_code(dtype), order, t.device.index or 0, handle))
+        keep = t
+    else:
+        mat = np.asarray(mat)
+        if mat.ndim != 2:
+            raise RuntimeError("mat must be 2-dimensional.")
+        dtype = mat.dtype
+        code = _abi.dtype_code(dtype)
+        mat = np.ascontiguousarray(mat)
+        backend.check(backend.fn("design_create_constraint_dense")(
+            mat.ctypes.data, mat.shape[0], mat.shape[1], code, _abi.ROW_MAJOR, device, handle))
+        keep = None
+    base = MatrixConstraintBase64 if dtype == np.float64 else MatrixConstraintBase32
+    cls = type("_constraint_matrix", (_ConstraintMatrix, base), {"dtype": base.dtype})
+    obj = cls()
+    obj._init_native(backend, handle, n_threads, keep)
+    return obj
 
 
 def _cov_dense(backend, ctor, mat, n_threads, device):

@@ -564,3 +564,56 @@ def bvls(
         screen_set_size=active_set_size, screen_set=active_set, is_screen=is_active, active_set_size=active_set_size,
         active_set=active_set, is_active=is_active, beta=beta, resid=resid, grad=np.empty(p, dtype=dtype), loss=loss)
     return state.solve()
+
+
+def pinball(
+    A, S: np.ndarray, v: np.ndarray, penalty_neg: np.ndarray, penalty_pos: np.ndarray, *, kappa: int = None,
+    max_iters: int = int(1e5), tol: float = 1e-7, n_threads: int = 1, warm_start=None,
+):
+    """Pinball least squares on an MI355X (reference ``adelie.solver.pinball``, ``adelie/solver.py:1119-1271``; arguments,
+    defaults and the returned state are the reference's):
+
+        minimise ``1/2 ||S^{-1/2} v - S^{1/2} A' beta||^2 + penalty_neg' beta_- + penalty_pos' beta_+``,
+
+    the dual of a quadratic programme under ``m`` two-sided linear constraints ``A`` ``(m, d)``; an infinite penalty on one
+    side gives the one-sided (sign-constrained) case.  ``kappa`` (violators admitted to the screen set per KKT round)
+    defaults to ``min(m, d)``; penalties are clipped to ``Configs.max_solver_value``; without a ``warm_start`` the start is
+    ``beta = 0``, with one it reuses the state's ``beta`` / ``active_set`` / ``is_active`` as both screen and active sets.
+
+    An ndarray (or device tensor) ``A`` goes through ``matrix.dense(method="constraint")`` and is solved by the reference's
+    coordinate descent run by one workgroup on the device: the gradients of all screen coordinates are kept current through
+    the resident matrix ``A_S S A_S'``, so a visit costs one column of it instead of a ``d``-long dot.  Any other
+    ``MatrixConstraintBase64/32`` subclass takes the same loop in Python over its ``rvmul`` / ``rmmul`` / ``tmul``: slow, and
+    meant for coverage rather than speed (``state.pinball``)."""
+    if isinstance(A, np.ndarray) or type(A).__module__.startswith("torch"):
+        A = matrix.dense(A, method="constraint", n_threads=n_threads)
+    if not isinstance(A, (matrix.MatrixConstraintBase64, matrix.MatrixConstraintBase32)):
+        raise ValueError("A must be an ndarray or an instance of MatrixConstraintBase32 or MatrixConstraintBase64.")
+    dtype = np.float64 if isinstance(A, matrix.MatrixConstraintBase64) else np.float32
+    m, d = A.shape
+    if kappa is None:
+        kappa = min(m, d)
+    S = np.asarray(S)
+    v = np.asarray(v)
+    y_var = v @ np.linalg.solve(S, v)
+    penalty_neg = np.minimum(penalty_neg, Configs.max_solver_value)
+    penalty_pos = np.minimum(penalty_pos, Configs.max_solver_value)
+    if warm_start is None:
+        active_set, active_set_size, is_active = np.empty(m, dtype=int), 0, np.zeros(m, dtype=bool)
+        beta = np.zeros(m, dtype=dtype)
+        resid = np.array(v, dtype=dtype)
+        loss = 0.5 * y_var
+    else:
+        active_set, active_set_size, is_active = warm_start.active_set, warm_start.active_set_size, warm_start.is_active
+        beta = warm_start.beta
+        resid = np.empty(d, dtype=dtype)
+        A.mul(np.asarray(beta, dtype=dtype), resid)
+        resid = v - S @ resid
+        loss = 0.5 * resid @ np.linalg.solve(S, resid)
+    # (screen_ASAT_diag / screen_AS of the screen set: computed by the solve, state.pinball)
+    state = _state.pinball(
+        A=A, y_var=y_var, S=S, penalty_neg=penalty_neg, penalty_pos=penalty_pos, kappa=kappa, max_iters=max_iters, tol=tol,
+        screen_set_size=active_set_size, screen_set=active_set, is_screen=is_active, screen_ASAT_diag=None, screen_AS=None,
+        active_set_size=active_set_size, active_set=active_set, is_active=is_active, beta=beta, resid=resid,
+        grad=np.empty(m, dtype=dtype), loss=loss)
+    return state.solve()

@@ -1571,3 +1571,332 @@ class bvls:
 
 class _BvlsError(RuntimeError):
     pass
+
+
+def _pinball_native(A):
+    """Whether ``A`` is the resident constraint matrix, i.e. what ``adelie_hip_pinball_solve`` accepts."""
+    return isinstance(A, _matrix._ConstraintMatrix)
+
+
+class pinball:
+    """Pinball least squares state (reference ``adelie.state.pinball``, ``state.py:3278-3440``; ``StatePinball``,
+    ``state_pinball.ipp``):
+
+        minimise ``1/2 ||S^{-1/2} v - S^{1/2} A' beta||^2 + penalty_neg' beta_- + penalty_pos' beta_+``.
+
+    Constructor arguments and attributes are the reference's, plus ``iters``, ``n_kkt``, ``error``, ``total_time`` and
+    ``benchmark``.  The constructor repeats the reference's checks; ``solve()`` returns a new solved state and leaves this one
+    untouched.  ``screen_ASAT_diag`` / ``screen_AS`` may be ``None``: the solve then computes them for the given screen set,
+    as ``solver.pinball`` does before it constructs the reference's state.
+
+    The resident constraint matrix (``matrix.dense(method="constraint")``) is solved on the device by
+    ``adelie_hip_pinball_solve``; ``screen_AS`` ``(m, d)`` and ``screen_ASAT_diag`` ``(m,)`` (filled in the rows of screen
+    members only, as in the reference; zero elsewhere) are then materialised from the compact device copy on first access.
+    Every other ``MatrixConstraintBase64/32`` subclass takes the same loop written in Python over its ``rvmul`` / ``rmmul`` /
+    ``tmul``, which is what the reference does through its matrix interface.  That route is slow and exists for coverage."""
+
+    def __init__(self, A, y_var, S, penalty_neg, penalty_pos, kappa, max_iters, tol, screen_set_size, screen_set, is_screen,
+                 screen_ASAT_diag, screen_AS, active_set_size, active_set, is_active, beta, resid, grad, loss):
+        if isinstance(A, np.ndarray):
+            A = _matrix.dense(A, method="constraint")
+        if not isinstance(A, (_matrix.MatrixConstraintBase64, _matrix.MatrixConstraintBase32)):
+            raise ValueError("A must be an instance of MatrixConstraintBase32 or MatrixConstraintBase64.")
+        dtype = np.dtype(np.float64 if isinstance(A, _matrix.MatrixConstraintBase64) else np.float32)
+        m, d = int(A.rows()), int(A.cols())
+        self.A, self._dtype = A, dtype
+        self.y_var = float(y_var)
+        self.S = np.asfortranarray(S, dtype=dtype)
+        with np.errstate(over="ignore"):  # (penalties of max_solver_value are infinite in float32)
+            self.penalty_neg = np.ascontiguousarray(penalty_neg, dtype=dtype)
+            self.penalty_pos = np.ascontiguousarray(penalty_pos, dtype=dtype)
+        self.kappa, self.max_iters, self.tol = int(kappa), int(max_iters), float(tol)
+        self.screen_set_size = int(screen_set_size)
+        self.screen_set = np.array(screen_set, copy=True, dtype=np.int64)
+        self.is_screen = np.array(is_screen, copy=True, dtype=bool)
+        self._screen_ASAT_diag = None if screen_ASAT_diag is None else np.array(screen_ASAT_diag, copy=True, dtype=dtype)
+        self._screen_AS = None if screen_AS is None else np.array(screen_AS, copy=True, dtype=dtype, order="C")
+        self.active_set_size = int(active_set_size)
+        self.active_set = np.array(active_set, copy=True, dtype=np.int64)
+        self.is_active = np.array(is_active, copy=True, dtype=bool)
+        self.beta = np.array(beta, copy=True, dtype=dtype)
+        self.resid = np.array(resid, copy=True, dtype=dtype)
+        self.grad = np.array(grad, copy=True, dtype=dtype)
+        self.loss = float(loss)
+        self.iters = self.n_kkt = 0
+        self.error, self.total_time, self.benchmark = "", 0.0, {}
+        self._result = self._backend = None
+        # state_pinball.ipp:15-94
+        pre, tail = "adelie_core solver: ", " where A is (m, d). "
+
+        def vec(name, arr, want, shape):
+            if arr is not None and (arr.ndim != 1 or arr.size != want):
+                raise RuntimeError(f"{pre}{name} must be {shape}{tail}")
+
+        if self.S.shape != (d, d):
+            raise RuntimeError(f"{pre}S must be (d, d){tail}")
+        vec("penalty_neg", self.penalty_neg, m, "(m,)")
+        vec("penalty_pos", self.penalty_pos, m, "(m,)")
+        if self.kappa <= 0:
+            raise RuntimeError(pre + "kappa must be > 0. ")
+        if self.tol < 0:
+            raise RuntimeError(pre + "tol must be >= 0.")
+        if self.screen_set_size > m:
+            raise RuntimeError(f"{pre}screen_set_size must be <= m{tail}")
+        vec("screen_set", self.screen_set, m, "(m,)")
+        vec("is_screen", self.is_screen, m, "(m,)")
+        vec("screen_ASAT_diag", self._screen_ASAT_diag, m, "(m,)")
+        if self._screen_AS is not None and self._screen_AS.shape != (m, d):
+            raise RuntimeError(f"{pre}screen_AS must be (m, d){tail}")
+        if self.active_set_size > m:
+            raise RuntimeError(f"{pre}active_set_size must be <= m{tail}")
+        vec("active_set", self.active_set, m, "(m,)")
+        vec("is_active", self.is_active, m, "(m,)")
+        vec("beta", self.beta, m, "(m,)")
+        vec("resid", self.resid, d, "(d,)")
+        vec("grad", self.grad, m, "(m,)")
+
+    def __del__(self):
+        self._drop_result()
+
+    def _drop_result(self):
+        r, self._result = getattr(self, "_result", None), None
+        if r is not None:
+            try:
+                self._backend.fn("pinball_result_destroy")(r)
+            except Exception:
+                pass
+
+    def _spawn(self):
+        return pinball(A=self.A, y_var=self.y_var, S=self.S, penalty_neg=self.penalty_neg, penalty_pos=self.penalty_pos,
+                       kappa=self.kappa, max_iters=self.max_iters, tol=self.tol, screen_set_size=self.screen_set_size,
+                       screen_set=self.screen_set, is_screen=self.is_screen, screen_ASAT_diag=self._screen_ASAT_diag,
+                       screen_AS=self._screen_AS, active_set_size=self.active_set_size, active_set=self.active_set,
+                       is_active=self.is_active, beta=self.beta, resid=self.resid, grad=self.grad, loss=self.loss)
+
+    def _fill_sets(self, screen, active):
+        m = int(self.A.rows())
+        for name, members in (("screen", screen), ("active", active)):
+            buf = np.array(getattr(self, name + "_set"), copy=True, dtype=np.int64)
+            buf[:len(members)] = members
+            flags = np.zeros(m, dtype=bool)
+            flags[np.asarray(members, dtype=np.int64)] = True
+            setattr(self, name + "_set", buf)
+            setattr(self, name + "_set_size", len(members))
+            setattr(self, "is_" + name, flags)
+
+    # ---- screen_AS / screen_ASAT_diag: given, computed by the Python route, or fetched from the device on first access ----
+    def _materialize(self):
+        m, d = int(self.A.rows()), int(self.A.cols())
+        members = self.screen_set[:self.screen_set_size]
+        AS = np.zeros((m, d), dtype=self._dtype)
+        diag = np.zeros(m, dtype=self._dtype)
+        if self._result is not None:
+            b, r = self._backend, self._result
+
+            def fetch(name):
+                n = b.fn("pinball_result_size")(r, _abi.PINBALL_V[name])
+                o = np.empty(max(n, 0), dtype=self._dtype)
+                if n > 0:
+                    b.check(b.fn("pinball_result_copy")(r, _abi.PINBALL_V[name], o.ctypes.data, n))
+                return o
+
+            if members.size:
+                AS[members] = fetch("screen_AS").reshape(members.size, d)
+                diag[members] = fetch("screen_ASAT_diag")
+            self._drop_result()
+        else:  # solver.py:1233-1236
+            for k in members:
+                self.A.rmmul(int(k), self.S, AS[k])
+                diag[k] = max(self.A.rvmul(int(k), AS[k]), 0)
+        self._screen_AS, self._screen_ASAT_diag = AS, diag
+
+    @property
+    def screen_AS(self):
+        if self._screen_AS is None:
+            self._materialize()
+        return self._screen_AS
+
+    @property
+    def screen_ASAT_diag(self):
+        if self._screen_ASAT_diag is None:
+            self._materialize()
+        return self._screen_ASAT_diag
+
+    def solve(self):
+        """Solves on the device (or, for matrices the native route does not take, through the matrix interface) and returns
+        the solved state.  Failures inside the solve are logged and stored in ``error``, as ``state.base.solve`` does."""
+        import time
+
+        out = self._spawn()
+        if _pinball_native(self.A):
+            out._solve_native()
+        else:
+            t0 = time.perf_counter()
+            try:
+                out._solve_generic()
+            except _PinballError as e:
+                out.error = str(e)
+            out.total_time = time.perf_counter() - t0
+        if out.error != "":
+            if out.error.startswith("adelie_core solver: "):
+                logger.error(RuntimeError(out.error))
+            else:
+                logger.warning(RuntimeError(out.error))
+        return out
+
+    def _solve_native(self):
+        A, dtype = self.A, self._dtype
+        b = A._backend
+        m, d = A.rows(), A.cols()
+        screen = np.ascontiguousarray(self.screen_set[:self.screen_set_size], dtype=np.int64)
+        active = np.ascontiguousarray(self.active_set[:self.active_set_size], dtype=np.int64)
+        diag, AS = self._screen_ASAT_diag, self._screen_AS
+        args = _abi.PinballArgs(
+            S=_abi.ptr(self.S), penalty_neg=_abi.ptr(self.penalty_neg), penalty_pos=_abi.ptr(self.penalty_pos),
+            beta=_abi.ptr(self.beta), resid=_abi.ptr(self.resid), grad=_abi.ptr(self.grad),
+            S_rows=self.S.shape[0], S_cols=self.S.shape[1], n_penalty_neg=self.penalty_neg.size,
+            n_penalty_pos=self.penalty_pos.size, n_beta=self.beta.size, n_resid=self.resid.size, n_grad=self.grad.size,
+            screen_set=_abi.ptr(screen) if screen.size else None, screen_set_size=screen.size,
+            active_set=_abi.ptr(active) if active.size else None, active_set_size=active.size,
+            n_screen_set=self.screen_set.size, n_is_screen=self.is_screen.size, n_active_set=self.active_set.size,
+            n_is_active=self.is_active.size, n_screen_ASAT_diag=m if diag is None else diag.size,
+            screen_AS_rows=m if AS is None else AS.shape[0], screen_AS_cols=d if AS is None else AS.shape[1],
+            y_var=self.y_var, loss=self.loss, kappa=self.kappa, max_iters=self.max_iters, tol=self.tol)
+        handle = _abi.C.c_void_p()
+        b.check(b.fn("pinball_solve")(A._handle, _abi.C.byref(args), handle))
+        self._backend, self._result = b, handle
+        self._screen_AS = self._screen_ASAT_diag = None  # (fetched from the result on first access)
+
+        def vec(name, dt):
+            which = _abi.PINBALL_V[name]
+            n = b.fn("pinball_result_size")(handle, which)
+            o = np.empty(max(n, 0), dtype=dt)
+            if n > 0:
+                b.check(b.fn("pinball_result_copy")(handle, which, o.ctypes.data, n))
+            return o
+
+        scalar = b.fn("pinball_result_scalar")
+        self.beta, self.resid, self.grad = vec("beta", dtype), vec("resid", dtype), vec("grad", dtype)
+        self._fill_sets(vec("screen_set", np.int64), vec("active_set", np.int64))
+        assert np.array_equal(self.is_screen, vec("is_screen", np.uint8).astype(bool))
+        assert np.array_equal(self.is_active, vec("is_active", np.uint8).astype(bool))
+        self.loss = float(scalar(handle, _abi.PINBALL_S["loss"]))
+        self.iters = int(scalar(handle, _abi.PINBALL_S["iters"]))
+        self.n_kkt = int(scalar(handle, _abi.PINBALL_S["n_kkt"]))
+        self.total_time = float(scalar(handle, _abi.PINBALL_S["total_time"]))
+        # device-phase times of the solve (scripts/bench_pinball.py)
+        self.benchmark = {k: float(scalar(handle, _abi.PINBALL_S[k])) for k in ("t_sweep_ms", "t_gram_ms", "t_fit_ms", "n_changed")}
+        msg = b.fn("pinball_result_error")(handle)
+        self.error = msg.decode() if msg else ""
+
+    def _solve_generic(self):
+        """solver_pinball.hpp:11-309 over ``A.rvmul`` / ``A.rmmul`` / ``A.tmul``, arithmetic in the matrix's dtype."""
+        A, dt = self.A, self._dtype.type
+        m = int(A.rows())
+        pneg, ppos, S = self.penalty_neg, self.penalty_pos, self.S
+        if self._screen_AS is None or self._screen_ASAT_diag is None:
+            self._materialize()
+        AS, diag = self._screen_AS, self._screen_ASAT_diag
+        beta, resid = self.beta, self.resid
+        screen = [int(k) for k in self.screen_set[:self.screen_set_size]]
+        active = [int(k) for k in self.active_set[:self.active_set_size]]
+        is_screen = np.array(self.is_screen, copy=True)
+        is_active = np.array(self.is_active, copy=True)
+        y_var, tol = dt(self.y_var), dt(self.tol)
+        loss = dt(self.loss)
+        half, zero = dt(0.5), dt(0)
+        n_changed = 0
+
+        def publish():
+            self.loss = float(loss)
+            self._fill_sets(screen, active)
+            self.benchmark = dict(n_changed=float(n_changed))
+
+        def descend(members, add):
+            nonlocal loss, n_changed
+            convg = zero
+            for k in members:
+                vk, lk, uk = diag[k], pneg[k], ppos[k]
+                gk = dt(A.rvmul(k, resid))
+                bk = beta[k]
+                if vk <= 0:
+                    continue
+                gk0 = gk + vk * bk
+                gk0_lk = gk0 + lk
+                bn = np.copysign(max(max(-gk0_lk, gk0 - uk), zero), gk0_lk) / vk
+                if bn == bk:
+                    continue
+                beta[k] = bn
+                dl = bn - bk
+                sds = vk * dl * dl
+                convg = max(convg, sds)
+                loss = loss - (dl * gk - half * sds)
+                resid[:] = resid - dl * AS[k]
+                n_changed += 1
+                if add and not is_active[k]:
+                    active.append(k)
+                    is_active[k] = True
+            return convg
+
+        def prune():
+            keep = [k for k in active if beta[k] != 0]
+            for k in active:
+                is_active[k] = False
+            for k in keep:
+                is_active[k] = True
+            active[:] = keep
+
+        def step_iters():
+            self.iters += 1
+            return self.iters >= self.max_iters
+
+        def fit():
+            while True:
+                hit = step_iters()
+                convg = descend(list(screen), True)
+                if hit:
+                    publish()
+                    raise _PinballError("adelie_core solver: pinball: max iterations reached!")
+                if convg <= tol * y_var:
+                    prune()
+                    return
+                while True:
+                    hit = step_iters()
+                    convg = descend(list(active), False)
+                    if hit:
+                        publish()
+                        raise _PinballError("adelie_core solver: pinball: max iterations reached!")
+                    if convg <= tol * y_var:
+                        break
+                prune()
+
+        with np.errstate(invalid="ignore"):
+            while True:
+                loss_prev = loss
+                fit()
+                if self.n_kkt > 0 and float(abs(loss - loss_prev)) < 1e-6 * float(abs(y_var)):
+                    break
+                self.n_kkt += 1
+                grad = np.empty(m, dtype=self._dtype)
+                A.tmul(resid, grad)
+                self.grad = np.maximum(grad - ppos, -pneg - grad).astype(self._dtype)
+                order = np.argsort(-self.grad, kind="stable")  # ties to the lower index (the reference leaves them open)
+                n_old, passed = len(screen), True
+                for k in order:
+                    if is_screen[k] or not self.grad[k] > 0:
+                        continue
+                    passed = False
+                    if len(screen) >= n_old + self.kappa:
+                        break
+                    k = int(k)
+                    screen.append(k)
+                    is_screen[k] = True
+                    A.rmmul(k, S, AS[k])
+                    diag[k] = max(dt(A.rvmul(k, AS[k])), zero)
+                if passed:
+                    break
+        publish()
+
+
+class _PinballError(RuntimeError):
+    pass

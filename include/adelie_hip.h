@@ -55,6 +55,7 @@ typedef struct adelie_hip_result adelie_hip_result; /* solved state snapshot (th
 typedef struct adelie_hip_glm_cox adelie_hip_glm_cox; /* ABI 11: a Cox family's sort orders and weights, resident on one device */
 typedef struct adelie_hip_css_result adelie_hip_css_result; /* ABI 13: a solved column-subset-selection state */
 typedef struct adelie_hip_bvls_result adelie_hip_bvls_result; /* ABI 14: a solved bounded-variable least squares state */
+typedef struct adelie_hip_pinball_result adelie_hip_pinball_result; /* a solved pinball least squares state (an addition to ABI 14) */
 
 /* ------------------------------------------------------------------------------------------
  * Library
@@ -697,6 +698,102 @@ int64_t     adelie_hip_bvls_result_size(const adelie_hip_bvls_result* r, int whi
 int         adelie_hip_bvls_result_copy(const adelie_hip_bvls_result* r, int which, void* out, int64_t cap);
 double      adelie_hip_bvls_result_scalar(const adelie_hip_bvls_result* r, int which);
 const char* adelie_hip_bvls_result_error(const adelie_hip_bvls_result* r);
+
+/* ------------------------------------------------------------------------------------------
+ * Constraint matrices and pinball least squares.  Additions to ABI 14: nothing that existed changes, so the version number
+ * stays (tests/test_bvls_host.py pins it).
+ *     min over beta in R^m   1/2 || S^{-1/2} v - S^{1/2} A' beta ||^2 + penalty_neg' beta_- + penalty_pos' beta_+
+ *   == adelie.matrix.dense(method="constraint") / MatrixConstraintDense{32,64}{C,F}   (matrix_constraint_base.hpp)
+ *   == adelie.solver.pinball / StatePinball{32,64}(...).solve()   (state_pinball.ipp:8-104, solver_pinball.hpp:11-309)
+ *
+ * A constraint handle holds the (m, d) matrix A row-major, i.e. the (d, m) column-major matrix A' of an ordinary dense handle
+ * (design_rows == d, design_cols == m) with a `constraint` flag: a row of A is one contiguous column, A v is the column sweep
+ * and v' A the column axpy.  `order` names the memory order of the (m, d) source: a row-major source is taken as it lies (a
+ * device one is adopted in place), a column-major one is transposed once.  Every entry point that takes a naive design
+ * (grpnet_solve, bvls_solve, the MatrixNaiveBase operations, views, slices, concatenations, factor designs, lazy_cov) refuses a
+ * handle with the flag; only adelie_hip_constraint_op, adelie_hip_pinball_solve and the design_{rows,cols,dtype,device,stream,
+ * destroy} accessors take one.  The handle makes no float32 shadow copy.
+ * ------------------------------------------------------------------------------------------ */
+int adelie_hip_design_create_constraint_dense(const void* host, int64_t m, int64_t d, int dtype, int order, int device,
+                                              adelie_hip_design** out);
+int adelie_hip_design_adopt_constraint_dense_dev(const void* dev_ptr, int64_t m, int64_t d, int dtype, int order, int device,
+                                                 adelie_hip_design** out);
+/* The MatrixConstraintBase operations; all vectors are host pointers of the handle's dtype.  None of them is a hot path. */
+enum adelie_hip_constraint_op_kind {
+    ADELIE_HIP_CONS_TMUL = 0,    /* out (m,) = A in,  in (d,) */
+    ADELIE_HIP_CONS_MUL = 1,     /* out (d,) = in' A, in (m,) */
+    ADELIE_HIP_CONS_SP_MUL = 2,  /* out (d,) = sum_i in[i] A[indices[i], :], n_indices entries, indices in [0, m) */
+    ADELIE_HIP_CONS_RVMUL = 3,   /* out (1,) = A[j, :] . in,  in (d,) */
+    ADELIE_HIP_CONS_RVTMUL = 4,  /* out (d,) += in[0] * A[j, :] */
+    ADELIE_HIP_CONS_RMMUL = 5,   /* out (d,) = A[j, :] Q,  in = Q (d, d) column-major */
+    ADELIE_HIP_CONS_COV = 6,     /* out (m, m) column-major = A Q A',  in = Q (d, d) column-major */
+    ADELIE_HIP_CONS_TO_DENSE = 7 /* out (m, d) row-major = A */
+};
+int adelie_hip_constraint_op(adelie_hip_design* A, int op, int64_t j, const void* in, const int64_t* indices, int64_t n_indices,
+                             void* out);
+
+/* The reference's coordinate descent with its visiting order, predicates and counters.  A visit reads the coordinate's gradient
+ * from a vector that is kept current through the resident matrix H = A_S S A_S' of the screen set instead of a d-long dot, one
+ * workgroup runs a whole fit() (the kernel bvls_solve runs, with the pinball update), the residual is caught up once per fit from
+ * the compact rows A_S S, and a KKT round is one sweep over the m rows plus a host sort (kernels_pinball.hip).  `S` is (d, d)
+ * column-major; all vectors are host pointers of the handle's dtype; the args carry the constructor arguments of the reference's
+ * state with their lengths, and its checks (state_pinball.ipp:15-94) fail the call.  screen_ASAT_diag / screen_AS are not passed
+ * in (the solve builds them for the caller's screen set); n_screen_ASAT_diag, screen_AS_rows and screen_AS_cols are the shapes
+ * of the caller's buffers for those checks.  Errors raised inside the solve ("pinball: max iterations reached!", the limit on H)
+ * are recorded in the result's error string and the result carries the state reached.  Ties between equal violations go to the
+ * lower index.  Results are bit-reproducible run to run.
+ * adelie_hip_set_config: "pinball_gram_limit_mb" (default 16384) bounds H; "pinball_lds_max_ns" (default 0 = as many as the
+ * device's LDS holds) keeps the fit kernel's per-coordinate state in global memory beyond that many screen members. */
+typedef struct adelie_hip_pinball_args {
+    const void*    S;           /* (S_rows, S_cols) column-major */
+    const void*    penalty_neg; /* (n_penalty_neg,) */
+    const void*    penalty_pos; /* (n_penalty_pos,) */
+    const void*    beta;        /* (n_beta,) */
+    const void*    resid;       /* (n_resid,) */
+    const void*    grad;        /* (n_grad,) returned unchanged when no KKT round runs */
+    int64_t        S_rows, S_cols, n_penalty_neg, n_penalty_pos, n_beta, n_resid, n_grad;
+    const int64_t* screen_set;  /* the first screen_set_size entries are read */
+    int64_t        screen_set_size;
+    const int64_t* active_set;  /* the first active_set_size entries are read */
+    int64_t        active_set_size;
+    int64_t        n_screen_set, n_is_screen, n_active_set, n_is_active; /* buffer lengths of the caller's state */
+    int64_t        n_screen_ASAT_diag, screen_AS_rows, screen_AS_cols;
+    double         y_var;
+    double         loss;
+    int64_t        kappa;
+    int64_t        max_iters;
+    double         tol;
+} adelie_hip_pinball_args;
+int adelie_hip_pinball_solve(adelie_hip_design* A, const adelie_hip_pinball_args* args, adelie_hip_pinball_result** out);
+int adelie_hip_pinball_result_destroy(adelie_hip_pinball_result* r);
+enum adelie_hip_pinball_vec {
+    ADELIE_HIP_PINBALL_BETA = 0,         /* (m,) handle's dtype */
+    ADELIE_HIP_PINBALL_RESID = 1,        /* (d,) handle's dtype */
+    ADELIE_HIP_PINBALL_GRAD = 2,         /* (m,) handle's dtype: the violations of the last KKT round */
+    ADELIE_HIP_PINBALL_SCREEN_SET = 3,   /* (screen_set_size,) int64, in order */
+    ADELIE_HIP_PINBALL_ACTIVE_SET = 4,   /* (active_set_size,) int64, in order */
+    ADELIE_HIP_PINBALL_IS_SCREEN = 5,    /* (m,) uint8 */
+    ADELIE_HIP_PINBALL_IS_ACTIVE = 6,    /* (m,) uint8 */
+    ADELIE_HIP_PINBALL_SCREEN_ASAT_DIAG = 7, /* (screen_set_size,) handle's dtype, screen order */
+    ADELIE_HIP_PINBALL_SCREEN_AS = 8     /* (screen_set_size, d) row-major, screen order: copied from the device at this call */
+};
+enum adelie_hip_pinball_scalar {
+    ADELIE_HIP_PINBALL_LOSS = 0,
+    ADELIE_HIP_PINBALL_ITERS,
+    ADELIE_HIP_PINBALL_N_KKT,
+    ADELIE_HIP_PINBALL_SCREEN_SET_SIZE,
+    ADELIE_HIP_PINBALL_ACTIVE_SET_SIZE,
+    ADELIE_HIP_PINBALL_TOTAL_TIME,       /* seconds */
+    ADELIE_HIP_PINBALL_T_SWEEP_MS,       /* HIP-event time of the full and screen sweeps */
+    ADELIE_HIP_PINBALL_T_GRAM_MS,        /* ... of the A_S S and H builds */
+    ADELIE_HIP_PINBALL_T_FIT_MS,         /* ... of the fit kernel */
+    ADELIE_HIP_PINBALL_N_CHANGED         /* visits that changed a coefficient, over all fits */
+};
+int64_t     adelie_hip_pinball_result_size(const adelie_hip_pinball_result* r, int which);
+/* Copies min(size, cap) elements in the element type named above. */
+int         adelie_hip_pinball_result_copy(const adelie_hip_pinball_result* r, int which, void* out, int64_t cap);
+double      adelie_hip_pinball_result_scalar(const adelie_hip_pinball_result* r, int which);
+const char* adelie_hip_pinball_result_error(const adelie_hip_pinball_result* r);
 
 /* ------------------------------------------------------------------------------------------
  * Kernel-level timing hook used by bench.py (HIP events on the design's own stream):
