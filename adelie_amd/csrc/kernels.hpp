@@ -74,25 +74,39 @@ struct ShadowView {
 };
 // makes the copy and measures err / nrm; *bad |= 1 when an entry is not finite or beyond FLT_MAX
 void launch_shadow_build(const DenseView<double>& X, float* Xs, int64_t lds, double* err, double* nrm, int32_t* bad, hipStream_t s);
-// out = a * b, and sq_part[0 .. filter_norm_parts(n)) = fixed-order partial sums of out^2
+// how many fixed-order partial sums of (w o r)^2 one filtered sweep leaves in sq_part
 int filter_norm_parts(int64_t n);
-void launch_vmul_sq(const double* a, const double* b, double* out, int64_t n, double* sq_part, hipStream_t s);
-// out[c] = xs_c . v - (sub_vec ? sub_scale[0] * sub_vec[c] : 0) for every column; work: shadow_sweep_work_elems(n, p)
-int64_t shadow_sweep_work_elems(int64_t n, int64_t p);
-void launch_shadow_sweep(const ShadowView& S, const double* v, double* out, const double* sub_scale, const double* sub_vec,
-                         double* work, hipStream_t s);
-// exact sweep of the first min(*count_dev, max_cols) columns of `cols` (count_dev == nullptr: max_cols), out[cols[c]] = the
-// bits launch_sweep over all X.p columns gives that column; guard != nullptr: out holds the shadow's values on entry and
-// *flags |= 2 when a pair differs by more than its bound (vnorm: device, the ||v||_2 of the bound).  work:
-// sweep_list_work_elems(n, p, max_cols)
-int64_t sweep_list_work_elems(int64_t n, int64_t p, int64_t max_cols);
-void launch_sweep_list(const DenseView<double>& X, const double* v, double* out, const int32_t* cols, int64_t max_cols,
-                       const int32_t* count_dev, const double* sub_scale, const double* sub_vec, const ShadowView* guard,
-                       const double* vnorm, int32_t* flags, double* work, hipStream_t s);
-// see filter_classify_kernel
-void launch_filter_classify(const double* grad, const int64_t* groups, const int64_t* group_sizes, int64_t G, const int32_t* slot,
-                            const double* penalty, double tstar, const ShadowView& S, const double* sq_part, int n_part,
-                            const double* sub_scale, int32_t* list, int64_t cap, int32_t* meta_i, double* meta_d, hipStream_t s);
+// One filtered invariance sweep, all device pointers.  In order on one stream:
+//   v = w o r and the partial sums of its squares;
+//   one launch that sweeps the shadow over all columns into grad and, in workgroups of its own, sweeps in f64 the columns
+//   that are exact whatever the shadow says (screen_cols, then pen0_cols: the groups without a penalty) into staging;
+//   the classification: ||v||, the staged columns reduced, compared with their shadow values and stored, and the columns of
+//   the groups that tstar cannot place listed (kernels_sweep.hip, filter_classify_kernel, also for meta_i / meta_d);
+//   the f64 sweep of the listed columns.
+// Every f64 value is the bits launch_sweep over all X.p columns gives that column.
+struct FilteredSweep {
+    const double *w, *r;
+    double* v;                          // n
+    double* grad;                       // p
+    const double *sub_scale, *sub_vec;  // grad[c] -= sub_scale[0] * sub_vec[c] (sub_vec == nullptr: no such term)
+    const int32_t* screen_cols;
+    int64_t n_screen_cols;
+    const int32_t* pen0_cols;
+    int64_t n_pen0_cols;
+    const int64_t *groups, *group_sizes;
+    int64_t G;
+    const int32_t* slot;                // per group: >= 0 in the screen set
+    const double* penalty;
+    double tstar;
+    double* sq_part;                    // filter_norm_parts(n)
+    int32_t* list;                      // cap
+    int64_t cap;
+    int32_t* meta_i;                    // 4
+    double* meta_d;                     // 2
+    double* work;                       // filtered_sweep_work_elems(n, p, n_screen_cols + n_pen0_cols, cap)
+};
+int64_t filtered_sweep_work_elems(int64_t n, int64_t p, int64_t n_before, int64_t cap);
+void enqueue_filtered_sweep(const DenseView<double>& X, const ShadowView& S, const FilteredSweep& a, hipStream_t s);
 // sparse design: one wavefront per (column, row block) over its stored entries; `work` holds sweep_work_elems_csc(X.nb, ncols)
 int64_t sweep_work_elems_csc(int nb, int64_t ncols);
 template <class T>

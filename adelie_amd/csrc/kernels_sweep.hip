@@ -17,6 +17,7 @@
 // splits are combined by a second tiny kernel so results are deterministic (no float atomics).
 #include "kernels.hpp"
 #include "accessors.hpp"
+#include "sweep_shape.hpp"
 #include <cstdlib>
 #include <cfloat>
 
@@ -137,26 +138,9 @@ __global__ void sweep_reduce_kernel(const T* __restrict__ part, T* __restrict__ 
     out[c] = s;
 }
 
-constexpr int kSweepCB = 4;
+static_assert(kThreads == kSweepThreads, "sweep_shape.hpp counts rows per iteration of a kThreads workgroup");
 // columns per sweep block (8 halves the re-reads of v through L2 and measured 6.66 against 6.85 TB/s)
 inline int sweep_cb() { return kSweepCB; }
-
-inline void sweep_shape(int64_t n, int64_t ncols, int vec, int64_t& blocks_c, int& nsplit, int64_t& rows_per_split) {
-    const int cbv = sweep_cb();
-    blocks_c = (ncols + cbv - 1) / cbv;
-    const int64_t unit = int64_t(kThreads) * vec;      // rows per block iteration
-    const int64_t max_split = (n + unit * 4 - 1) / (unit * 4); // >= 4 iterations per split
-    int64_t want = (1024 + blocks_c - 1) / blocks_c;
-    int64_t ns = want < 1 ? 1 : want;
-    if (ns > max_split) ns = max_split;
-    if (ns < 1) ns = 1;
-    if (ns > 65535) ns = 65535;
-    rows_per_split = (n + ns - 1) / ns;
-    rows_per_split = ((rows_per_split + unit - 1) / unit) * unit;
-    ns = (n + rows_per_split - 1) / rows_per_split;
-    if (ns < 1) ns = 1;
-    nsplit = int(ns);
-}
 
 template <class T, class Acc, int VEC>
 void sweep_dispatch(Acc acc, const T* v, T* out, int64_t n, int64_t c0, int64_t ncols, const int32_t* cols,
@@ -956,11 +940,19 @@ template void launch_snp_impute<float>(const uint8_t*, int64_t, int64_t, int64_t
 // The per-lambda gradient sweep is consumed almost only through comparisons with thresholds (KKT, the screening rules).  With
 // xs_j = column j rounded to float32 and e_j = ||x_j - xs_j||_2 measured when the copy is made, |x_j.v - xs_j.v| <= e_j ||v||_2:
 // a sweep of the copy (half the bytes) proves most columns to lie below every threshold, and only the others are swept
-// again in f64.  The exact sweeps over a column list (sweep_list_kernel) repeat, per column, the arithmetic of sweep_kernel
+// again in f64.  The exact sweeps over a column list (list_column_sum) repeat, per column, the arithmetic of sweep_kernel
 // on the row splits of the FULL design, so their values are the bits the full sweep gives.
+// One filtered sweep is four launches (enqueue_filtered_sweep, the one sequence the solver and the test entry share):
+//   vmul_sq_kernel          v = w o r and the partial sums of v^2
+//   shadow_sweep_kernel     the shadow over all columns (panels of kShadowCB = 8 columns: 16 B of v per 64 B of design) and,
+//                           in workgroups of its own first in the grid, the columns that are exact whatever the shadow says
+//                           (screen columns, columns of groups without a penalty), their split partials into staging
+//   filter_classify_kernel  ||v||; the staged columns reduced in split order, guarded against their shadow values and stored;
+//                           the open groups listed in group order.  It owns the four meta words: no memset ahead of it
+//   sweep_list_kernel       the listed columns (it reads their count from the device)
+// (a shape whose shadow or list splits the rows adds the reduce launch of those partials).
 namespace {
 
-constexpr int kShadowCB = 4, kShadowVec = 4;
 
 __global__ __launch_bounds__(kThreads) void shadow_build_kernel(const double* __restrict__ X, int64_t ld, int64_t n,
                                                                 float* __restrict__ Xs, int64_t lds, double* __restrict__ err,
@@ -1021,16 +1013,75 @@ __global__ __launch_bounds__(kThreads) void vmul_sq_kernel(const double* __restr
     }
 }
 
-// out[c] = sum_i float(Xs[i, c]) * v[i] over all columns, f64 accumulation; row splits and epilogue as sweep_kernel
+// |exact - shadow| <= bound must hold for every column swept both ways: a design modified after the copy was made shows here
+__device__ __forceinline__ void shadow_guard(double exact, double approx, int64_t j, const double* __restrict__ err,
+                                             const double* __restrict__ nrm, double fp_term, const double* __restrict__ vnorm,
+                                             int32_t* __restrict__ flags) {
+    const double bound = (err[j] + fp_term * nrm[j]) * vnorm[0];
+    if (!(fabs(exact - approx) <= bound)) atomicOr(flags, 2);
+}
+
+// One column, one row split: per thread the loop of sweep_kernel, then its wave and workgroup reductions (any CB gives a
+// column the same bits).  The sum is valid in thread 0; red: kThreads / 64 doubles of LDS.
+template <int VEC>
+__device__ __forceinline__ double list_column_sum(const DenseAcc<double>& X, const double* __restrict__ v, int64_t j, int64_t r0,
+                                                  int64_t r1, double* red) {
+    const int tid = threadIdx.x;
+    const double* cp = X.colptr(j);
+    double acc = 0;
+    const int64_t body_end = r0 + ((r1 - r0) / VEC) * VEC;
+#pragma unroll 8
+    for (int64_t i = r0 + int64_t(tid) * VEC; i < body_end; i += int64_t(kThreads) * VEC) {
+        const Pack<double, VEC> vv = load_vec<double, VEC>(v + i);
+        const Pack<double, VEC> xx = X.template load<VEC>(cp, i, j);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc = fma(xx.v[e], vv.v[e], acc);
+    }
+    for (int64_t i = body_end + tid; i < r1; i += kThreads) acc = fma(X.template load<1>(cp, i, j).v[0], v[i], acc);
+    const int lane = tid & 63, wv = tid >> 6;
+    const double ws = wave_sum(acc);
+    if (lane == 0) red[wv] = ws;
+    __syncthreads();
+    double s = 0;
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 0; w < kThreads / 64; ++w) s += red[w];
+    }
+    return s;
+}
+
+// One launch, two kinds of workgroup.  The first (na + nb) * x_nsplit workgroups sweep in f64 the columns that are exact
+// whatever the shadow says (xa: the screen columns, xb: the columns of the groups without a penalty): list_column_sum on the
+// row splits of the FULL design's shape, the split partial of list entry c to stage[split * (na + nb) + c].  They neither read
+// nor write `out`: filter_classify_kernel reduces the staged partials, compares with the shadow value and stores the exact one.
+// The other blocks_c * nsplit workgroups: out[c] = sum_i float(Xs[i, c]) * v[i] over all columns, f64 accumulation; row splits
+// (the shadow's own shape) and epilogue as sweep_kernel.
+template <int XVEC>
 __global__ __launch_bounds__(kThreads) void shadow_sweep_kernel(const float* __restrict__ Xs, int64_t ld,
                                                                 const double* __restrict__ v, double* __restrict__ out,
-                                                                int64_t n, int64_t ncols, int64_t rows_per_split, int nsplit,
-                                                                const double* __restrict__ sub_scale,
-                                                                const double* __restrict__ sub_vec) {
+                                                                int64_t n, int64_t ncols, int64_t blocks_c, int64_t rows_per_split,
+                                                                int nsplit, const double* __restrict__ sub_scale,
+                                                                const double* __restrict__ sub_vec, DenseAcc<double> X,
+                                                                const int32_t* __restrict__ xa, int64_t na,
+                                                                const int32_t* __restrict__ xb, int64_t nb, int64_t x_rows_per_split,
+                                                                int x_nsplit, double* __restrict__ stage) {
     constexpr int CB = kShadowCB, VEC = kShadowVec;
     const int tid = threadIdx.x;
-    const int64_t cb = blockIdx.x;
-    const int split = blockIdx.y;
+    const int64_t ne = na + nb;
+    const int64_t n_exact = ne * x_nsplit;
+    __shared__ double red[kThreads / 64][CB];
+    if (int64_t(blockIdx.x) < n_exact) {
+        const int64_t c = int64_t(blockIdx.x) % ne;
+        const int64_t xsplit = int64_t(blockIdx.x) / ne;
+        const int64_t j = c < na ? xa[c] : xb[c - na];
+        const int64_t xr0 = xsplit * x_rows_per_split;
+        const double s = list_column_sum<XVEC>(X, v, j, xr0, min(n, xr0 + x_rows_per_split), &red[0][0]);
+        if (tid == 0) stage[xsplit * ne + c] = s;
+        return;
+    }
+    const int64_t b = int64_t(blockIdx.x) - n_exact;
+    const int64_t cb = b % blocks_c;
+    const int split = int(b / blocks_c);
     const int64_t r0 = int64_t(split) * rows_per_split;
     const int64_t r1 = min(n, r0 + rows_per_split);
     const float* cp[CB];
@@ -1064,7 +1115,6 @@ __global__ __launch_bounds__(kThreads) void shadow_sweep_kernel(const float* __r
 #pragma unroll
         for (int k = 0; k < CB; ++k) acc[k] = fma(double(cp[k][i]), vi, acc[k]);
     }
-    __shared__ double red[kThreads / 64][CB];
     const int lane = tid & 63, wv = tid >> 6;
 #pragma unroll
     for (int k = 0; k < CB; ++k) {
@@ -1088,17 +1138,9 @@ __global__ __launch_bounds__(kThreads) void shadow_sweep_kernel(const float* __r
     }
 }
 
-// |exact - shadow| <= bound must hold for every column swept both ways: a design modified after the copy was made shows here
-__device__ __forceinline__ void shadow_guard(double exact, double approx, int64_t j, const double* __restrict__ err,
-                                             const double* __restrict__ nrm, double fp_term, const double* __restrict__ vnorm,
-                                             int32_t* __restrict__ flags) {
-    const double bound = (err[j] + fp_term * nrm[j]) * vnorm[0];
-    if (!(fabs(exact - approx) <= bound)) atomicOr(flags, 2);
-}
-
-// One column per workgroup, the first *count_dev (or max_cols) entries of `cols`: per column the loop, the reductions and the
-// epilogue of sweep_kernel (any CB gives a column the same bits) on the row splits the caller took from the full design's
-// shape; the result goes to out[column].  err != nullptr: out[column] holds the shadow's value on entry (shadow_guard).
+// One column per workgroup, the first *count_dev (or max_cols) entries of `cols`: list_column_sum on the row splits the caller
+// took from the full design's shape; the result goes to out[column].  err != nullptr: out[column] holds the shadow's value on
+// entry (shadow_guard).
 template <int VEC>
 __global__ __launch_bounds__(kThreads) void sweep_list_kernel(DenseAcc<double> X, const double* __restrict__ v,
                                                               double* __restrict__ out, double* __restrict__ part, int64_t n,
@@ -1111,31 +1153,12 @@ __global__ __launch_bounds__(kThreads) void sweep_list_kernel(DenseAcc<double> X
     const int64_t c = blockIdx.x;
     const int64_t count = count_dev ? min(int64_t(count_dev[0]), max_cols) : max_cols;
     if (c >= count) return;
-    const int tid = threadIdx.x;
     const int split = blockIdx.y;
     const int64_t r0 = int64_t(split) * rows_per_split;
-    const int64_t r1 = min(n, r0 + rows_per_split);
     const int64_t j = cols[c];
-    const double* cp = X.colptr(j);
-    double acc = 0;
-    const int64_t body_end = r0 + ((r1 - r0) / VEC) * VEC;
-#pragma unroll 8
-    for (int64_t i = r0 + int64_t(tid) * VEC; i < body_end; i += int64_t(kThreads) * VEC) {
-        const Pack<double, VEC> vv = load_vec<double, VEC>(v + i);
-        const Pack<double, VEC> xx = X.template load<VEC>(cp, i, j);
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) acc = fma(xx.v[e], vv.v[e], acc);
-    }
-    for (int64_t i = body_end + tid; i < r1; i += kThreads) acc = fma(X.template load<1>(cp, i, j).v[0], v[i], acc);
     __shared__ double red[kThreads / 64];
-    const int lane = tid & 63, wv = tid >> 6;
-    const double ws = wave_sum(acc);
-    if (lane == 0) red[wv] = ws;
-    __syncthreads();
-    if (tid == 0) {
-        double s = 0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) s += red[w];
+    double s = list_column_sum<VEC>(X, v, j, r0, min(n, r0 + rows_per_split), red);
+    if (threadIdx.x == 0) {
         if (nsplit == 1) {
             if (sub_vec) s -= sub_scale[0] * sub_vec[j];
             if (err) shadow_guard(s, out[j], j, err, nrm, fp_term, vnorm, flags);
@@ -1162,22 +1185,35 @@ __global__ void sweep_list_reduce_kernel(const double* __restrict__ part, double
     out[j] = s;
 }
 
-// One workgroup.  ||v||_2 from the partial sums of vmul_sq_kernel, then per group outside the screen set (slot < 0) with a
-// positive penalty: approximate norm a of its gradient block and the bound eps on its distance from the exact one; the
-// columns of every group that a + eps cannot place below thr_g = tstar * penalty_g are appended to `list`, in group order.
-// meta_i: [0] columns listed (at most cap), [1] flags (bit 0: more than cap), [2] columns wanted; meta_d: [0] the inflated
-// ||v||_2 the bounds use, [1] a copy of sub_scale[0] (what a later exact sweep of the same residual subtracts).
-constexpr int kClassifyThreads = 1024;
+// One workgroup, the step after the fused shadow launch.
+//  - ||v||_2 from the partial sums of vmul_sq_kernel.
+//  - The columns swept exactly inside the shadow launch (xa, then xb: entry c of the two lists taken as one has its x_nsplit
+//    split partials at stage[split * (na + nb) + c]): partials added in split order, the centring term, shadow_guard against
+//    the shadow's value in grad, then grad[column] = the exact value.  xb after xa, a barrier between: a column in both lists
+//    is compared the second time with what the first pass stored, as two list sweeps one after the other would.
+//  - Per group outside the screen set (slot < 0) with a positive penalty: approximate norm a of its gradient block and the
+//    bound eps on its distance from the exact one; the columns of every group that a + eps cannot place below
+//    thr_g = tstar * penalty_g are appended to `list`, in group order.  Per trip of kClassifyThreads * kClassifyRun groups
+//    a thread loads the descriptors of kClassifyRun groups together, then their entries together (two round trips to memory,
+//    coalesced), the counts pass through LDS, and the workgroup scans once over threads that each own kClassifyRun
+//    consecutive groups.  kClassifyRun = 6 is what 128 VGPRs (1024 threads on one CU) hold without spilling.
+// meta_i: [0] columns listed (at most cap), [1] flags (bit 0: more than cap, bit 1: shadow_guard), [2] columns wanted, [3] 0:
+// all four are written here and nothing before this kernel touches them; the open-list sweep that follows ORs into [1].
+// meta_d: [0] the inflated ||v||_2 the bounds use, [1] a copy of sub_scale[0] (what a later exact sweep of the same residual
+// subtracts).
+constexpr int kClassifyThreads = 1024, kClassifyRun = 6;
 __global__ __launch_bounds__(kClassifyThreads) void filter_classify_kernel(
-    const double* __restrict__ grad, const int64_t* __restrict__ groups, const int64_t* __restrict__ group_sizes, int64_t G,
+    double* __restrict__ grad, const int64_t* __restrict__ groups, const int64_t* __restrict__ group_sizes, int64_t G,
     const int32_t* __restrict__ slot, const double* __restrict__ penalty, double tstar, const double* __restrict__ err,
     const double* __restrict__ nrm, double fp_term, const double* __restrict__ sq_part, int n_part,
-    const double* __restrict__ sub_scale, int32_t* __restrict__ list, int64_t cap, int32_t* __restrict__ meta_i,
-    double* __restrict__ meta_d) {
-    constexpr int NW = kClassifyThreads / 64;
+    const double* __restrict__ sub_scale, const double* __restrict__ sub_vec, const double* __restrict__ stage,
+    const int32_t* __restrict__ xa, int64_t na, const int32_t* __restrict__ xb, int64_t nb, int x_nsplit,
+    int32_t* __restrict__ list, int64_t cap, int32_t* __restrict__ meta_i, double* __restrict__ meta_d) {
+    constexpr int NW = kClassifyThreads / 64, R = kClassifyRun;
     __shared__ double sred[NW];
     __shared__ int32_t wtot[NW];
     __shared__ double s_vnorm;
+    __shared__ int32_t s_first[kClassifyThreads * R], s_want[kClassifyThreads * R]; // per group of a trip: first column, columns wanted
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     {
         double a = 0;
@@ -1191,28 +1227,88 @@ __global__ __launch_bounds__(kClassifyThreads) void filter_classify_kernel(
             s_vnorm = sqrt(s) * (1.0 + 1e-6);
             meta_d[0] = s_vnorm;
             meta_d[1] = sub_scale ? sub_scale[0] : 0.0;
+            meta_i[1] = 0;
+            meta_i[3] = 0;
         }
         __syncthreads();
     }
     const double vnorm = s_vnorm;
-    int64_t run = 0;
-    for (int64_t g0 = 0; g0 < G; g0 += kClassifyThreads) {
-        const int64_t g = g0 + tid;
-        int32_t mine = 0;
-        int64_t k = 0;
-        if (g < G && slot[g] < 0 && penalty[g] > 0) {
-            k = groups[g];
-            const int64_t sz = group_sizes[g];
-            double a2 = 0, b2 = 0;
-            for (int64_t t = 0; t < sz; ++t) {
-                const double x = grad[k + t], b = err[k + t] + fp_term * nrm[k + t];
-                a2 = fma(x, x, a2);
-                b2 = fma(b, b, b2);
-            }
-            const double reach = (sqrt(a2) + sqrt(b2) * vnorm * (1.0 + 1e-9)) * (1.0 + 1e-9);
-            if (!(reach < tstar * penalty[g])) mine = int32_t(sz);
+    const int64_t ne = na + nb;
+    for (int pass = 0; pass < 2; ++pass) {
+        const int32_t* xl = pass ? xb : xa;
+        const int64_t c0 = pass ? na : 0, cnt = pass ? nb : na;
+        for (int64_t c = tid; c < cnt; c += kClassifyThreads) {
+            const int64_t j = xl[c];
+            double s = 0;
+            for (int r = 0; r < x_nsplit; ++r) s += stage[int64_t(r) * ne + c0 + c];
+            if (sub_vec) s -= sub_scale[0] * sub_vec[j];
+            shadow_guard(s, grad[j], j, err, nrm, fp_term, &s_vnorm, meta_i + 1);
+            grad[j] = s;
         }
-        // exclusive scan of `mine` over the workgroup
+        __syncthreads();
+    }
+    int64_t run = 0;
+    for (int64_t base = 0; base < G; base += int64_t(kClassifyThreads) * R) {
+        // the loads of R groups per thread, consecutive threads on consecutive groups: descriptors together, entries together
+        int32_t k[R], sz[R];
+        double thr[R], a2[R], b2[R];
+        {
+            int32_t sl[R];
+            double pn[R];
+            int64_t kk[R], ss[R];
+#pragma unroll
+            for (int u = 0; u < R; ++u) {
+                const int64_t gu = base + int64_t(u) * kClassifyThreads + tid;
+                const int64_t g = gu < G ? gu : G - 1;
+                sl[u] = slot[g];
+                pn[u] = penalty[g];
+                kk[u] = groups[g];
+                ss[u] = group_sizes[g];
+            }
+#pragma unroll
+            for (int u = 0; u < R; ++u) {
+                const bool on = base + int64_t(u) * kClassifyThreads + tid < G && sl[u] < 0 && pn[u] > 0 && ss[u] > 0;
+                k[u] = int32_t(kk[u]);
+                sz[u] = on ? int32_t(ss[u]) : 0;
+                thr[u] = tstar * pn[u];
+                a2[u] = 0;
+                b2[u] = 0;
+            }
+        }
+        int32_t longest = 0;
+#pragma unroll
+        for (int u = 0; u < R; ++u) longest = max(longest, sz[u]);
+        for (int32_t t = 0; t < longest; ++t) {
+            double x[R], e[R], m[R];
+#pragma unroll
+            for (int u = 0; u < R; ++u) {
+                const int64_t at = t < sz[u] ? int64_t(k[u]) + t : 0;
+                x[u] = grad[at];
+                e[u] = err[at];
+                m[u] = nrm[at];
+            }
+#pragma unroll
+            for (int u = 0; u < R; ++u)
+                if (t < sz[u]) {
+                    const double b = e[u] + fp_term * m[u];
+                    a2[u] = fma(x[u], x[u], a2[u]);
+                    b2[u] = fma(b, b, b2[u]);
+                }
+        }
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            if (sz[u] > 0) {
+                const double reach = (sqrt(a2[u]) + sqrt(b2[u]) * vnorm * (1.0 + 1e-9)) * (1.0 + 1e-9);
+                if (reach < thr[u]) sz[u] = 0;
+            }
+            s_first[u * kClassifyThreads + tid] = k[u];
+            s_want[u * kClassifyThreads + tid] = sz[u];
+        }
+        __syncthreads();
+        // a thread takes R consecutive groups of the trip: one exclusive scan of the per-thread counts over the workgroup
+        int32_t mine = 0;
+#pragma unroll
+        for (int u = 0; u < R; ++u) mine += s_want[tid * R + u];
         int32_t inc = mine;
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
@@ -1227,9 +1323,13 @@ __global__ __launch_bounds__(kClassifyThreads) void filter_classify_kernel(
             if (w < wv) before += t;
             total += t;
         }
-        const int64_t at = run + before + inc - mine;
-        for (int32_t t = 0; t < mine; ++t)
-            if (at + t < cap) list[at + t] = int32_t(k + t);
+        int64_t at = run + before + inc - mine;
+        if (mine > 0)
+            for (int u = 0; u < R; ++u) {
+                const int32_t first = s_first[tid * R + u], want = s_want[tid * R + u];
+                for (int32_t t = 0; t < want; ++t, ++at)
+                    if (at < cap) list[at] = first + t;
+            }
         run += total;
         __syncthreads();
     }
@@ -1248,62 +1348,84 @@ void launch_shadow_build(const DenseView<double>& X, float* Xs, int64_t lds, dou
     hipLaunchKernelGGL(shadow_build_kernel, dim3((unsigned)X.p), dim3(kThreads), 0, s, X.X, X.ld, X.n, Xs, lds, err, nrm, bad);
 }
 int filter_norm_parts(int64_t n) { return int(grid1d(n, kThreads, 1024)); }
-void launch_vmul_sq(const double* a, const double* b, double* out, int64_t n, double* sq_part, hipStream_t s) {
-    hipLaunchKernelGGL(vmul_sq_kernel, dim3(grid1d(n, kThreads, 1024)), dim3(kThreads), 0, s, a, b, out, n, sq_part);
+
+namespace {
+struct ListShape {
+    bool vec;
+    int ns;
+    int64_t rps;
+};
+// the row splits of the FULL design's sweep, whatever the length of a list
+ListShape list_shape(const DenseView<double>& X, const double* v) {
+    ListShape L;
+    L.vec = dense_vec_ok(X) && (reinterpret_cast<uintptr_t>(v) % 16) == 0;
+    int64_t blocks_c;
+    sweep_shape(X.n, X.p, L.vec ? VecOf<double>::N : 1, blocks_c, L.ns, L.rps);
+    return L;
 }
-int64_t shadow_sweep_work_elems(int64_t n, int64_t p) {
+// exact sweep of the first min(*count_dev, max_cols) columns of `cols`: out[cols[c]] = the bits launch_sweep over all X.p
+// columns gives that column; out holds the shadow's values on entry and *flags |= 2 when a pair differs by more than its bound
+void launch_sweep_list(const DenseView<double>& X, const double* v, double* out, const int32_t* cols, int64_t max_cols,
+                       const int32_t* count_dev, const double* sub_scale, const double* sub_vec, const ShadowView& guard,
+                       const double* vnorm, int32_t* flags, double* work, hipStream_t s) {
+    if (max_cols <= 0) return;
+    DenseAcc<double> acc{X.X, X.ld};
+    const ListShape L = list_shape(X, v);
+    dim3 grid((unsigned)max_cols, (unsigned)L.ns);
+    if (L.vec)
+        hipLaunchKernelGGL((sweep_list_kernel<VecOf<double>::N>), grid, dim3(kThreads), 0, s, acc, v, out, work, X.n, cols, max_cols,
+                           count_dev, L.rps, L.ns, sub_scale, sub_vec, guard.err, guard.nrm, guard.fp_term(), vnorm, flags);
+    else
+        hipLaunchKernelGGL((sweep_list_kernel<1>), grid, dim3(kThreads), 0, s, acc, v, out, work, X.n, cols, max_cols, count_dev,
+                           L.rps, L.ns, sub_scale, sub_vec, guard.err, guard.nrm, guard.fp_term(), vnorm, flags);
+    if (L.ns > 1)
+        hipLaunchKernelGGL(sweep_list_reduce_kernel, dim3((unsigned)((max_cols + 255) / 256)), dim3(256), 0, s, work, out, cols,
+                           max_cols, count_dev, L.ns, sub_scale, sub_vec, guard.err, guard.nrm, guard.fp_term(), vnorm, flags);
+}
+int64_t shadow_work_elems(int64_t n, int64_t p) {
     int64_t blocks_c, rps;
     int ns;
-    sweep_shape(n, p, kShadowVec, blocks_c, ns, rps);
+    sweep_shape(n, p, kShadowVec, blocks_c, ns, rps, kShadowCB);
     return int64_t(ns) * p + 16;
 }
-void launch_shadow_sweep(const ShadowView& S, const double* v, double* out, const double* sub_scale, const double* sub_vec,
-                         double* work, hipStream_t s) {
-    if (S.p <= 0) return;
-    int64_t blocks_c, rps;
-    int ns;
-    sweep_shape(S.n, S.p, kShadowVec, blocks_c, ns, rps);
-    static_assert(kShadowCB == kSweepCB, "sweep_shape counts panels of kSweepCB columns");
-    hipLaunchKernelGGL(shadow_sweep_kernel, dim3((unsigned)blocks_c, (unsigned)ns), dim3(kThreads), 0, s, S.X, S.ld, v,
-                       ns == 1 ? out : work, S.n, S.p, rps, ns, sub_scale, sub_vec);
-    if (ns > 1)
-        hipLaunchKernelGGL((sweep_reduce_kernel<double>), dim3((unsigned)((S.p + 255) / 256)), dim3(256), 0, s, work, out, S.p,
-                           ns, int64_t(0), (const int32_t*)nullptr, sub_scale, sub_vec);
-}
-int64_t sweep_list_work_elems(int64_t n, int64_t p, int64_t max_cols) {
+int64_t list_work_elems(int64_t n, int64_t p, int64_t max_cols) {
     int64_t blocks_c, rps;
     int ns;
     sweep_shape(n, p, 1, blocks_c, ns, rps); // VEC=1 gives the largest split count
     return int64_t(ns) * max_cols + 16;
 }
-void launch_sweep_list(const DenseView<double>& X, const double* v, double* out, const int32_t* cols, int64_t max_cols,
-                       const int32_t* count_dev, const double* sub_scale, const double* sub_vec, const ShadowView* guard,
-                       const double* vnorm, int32_t* flags, double* work, hipStream_t s) {
-    if (max_cols <= 0) return;
-    DenseAcc<double> acc{X.X, X.ld};
-    const bool vec = dense_vec_ok(X) && (reinterpret_cast<uintptr_t>(v) % 16) == 0;
+} // namespace
+
+int64_t filtered_sweep_work_elems(int64_t n, int64_t p, int64_t n_before, int64_t cap) {
+    return shadow_work_elems(n, p) + list_work_elems(n, p, std::max(n_before, cap));
+}
+void enqueue_filtered_sweep(const DenseView<double>& X, const ShadowView& S, const FilteredSweep& a, hipStream_t s) {
+    if (S.p <= 0) return;
+    const int64_t na = a.screen_cols ? a.n_screen_cols : 0, nb = a.pen0_cols ? a.n_pen0_cols : 0;
+    // work: the shadow's split partials, then the staged partials of the exact part (the open-list sweep's after them)
+    double* stage = a.work + shadow_work_elems(S.n, S.p);
+    hipLaunchKernelGGL(vmul_sq_kernel, dim3(grid1d(S.n, kThreads, 1024)), dim3(kThreads), 0, s, a.w, a.r, a.v, S.n, a.sq_part);
     int64_t blocks_c, rps;
     int ns;
-    sweep_shape(X.n, X.p, vec ? VecOf<double>::N : 1, blocks_c, ns, rps); // the FULL design's shape, whatever the list length
-    const double* err = guard ? guard->err : nullptr;
-    const double* nrm = guard ? guard->nrm : nullptr;
-    const double fp = guard ? guard->fp_term() : 0.0;
-    dim3 grid((unsigned)max_cols, (unsigned)ns);
-    if (vec)
-        hipLaunchKernelGGL((sweep_list_kernel<VecOf<double>::N>), grid, dim3(kThreads), 0, s, acc, v, out, work, X.n, cols, max_cols,
-                           count_dev, rps, ns, sub_scale, sub_vec, err, nrm, fp, vnorm, flags);
+    sweep_shape(S.n, S.p, kShadowVec, blocks_c, ns, rps, kShadowCB);
+    const ListShape L = list_shape(X, a.v);
+    DenseAcc<double> acc{X.X, X.ld};
+    const dim3 grid((unsigned)((na + nb) * L.ns + blocks_c * ns));
+    if (L.vec)
+        hipLaunchKernelGGL((shadow_sweep_kernel<VecOf<double>::N>), grid, dim3(kThreads), 0, s, S.X, S.ld, a.v,
+                           ns == 1 ? a.grad : a.work, S.n, S.p, blocks_c, rps, ns, a.sub_scale, a.sub_vec, acc, a.screen_cols, na,
+                           a.pen0_cols, nb, L.rps, L.ns, stage);
     else
-        hipLaunchKernelGGL((sweep_list_kernel<1>), grid, dim3(kThreads), 0, s, acc, v, out, work, X.n, cols, max_cols, count_dev, rps,
-                           ns, sub_scale, sub_vec, err, nrm, fp, vnorm, flags);
+        hipLaunchKernelGGL((shadow_sweep_kernel<1>), grid, dim3(kThreads), 0, s, S.X, S.ld, a.v, ns == 1 ? a.grad : a.work, S.n,
+                           S.p, blocks_c, rps, ns, a.sub_scale, a.sub_vec, acc, a.screen_cols, na, a.pen0_cols, nb, L.rps, L.ns,
+                           stage);
     if (ns > 1)
-        hipLaunchKernelGGL(sweep_list_reduce_kernel, dim3((unsigned)((max_cols + 255) / 256)), dim3(256), 0, s, work, out, cols,
-                           max_cols, count_dev, ns, sub_scale, sub_vec, err, nrm, fp, vnorm, flags);
-}
-void launch_filter_classify(const double* grad, const int64_t* groups, const int64_t* group_sizes, int64_t G, const int32_t* slot,
-                            const double* penalty, double tstar, const ShadowView& S, const double* sq_part, int n_part,
-                            const double* sub_scale, int32_t* list, int64_t cap, int32_t* meta_i, double* meta_d, hipStream_t s) {
-    hipLaunchKernelGGL(filter_classify_kernel, dim3(1), dim3(kClassifyThreads), 0, s, grad, groups, group_sizes, G, slot, penalty,
-                       tstar, S.err, S.nrm, S.fp_term(), sq_part, n_part, sub_scale, list, cap, meta_i, meta_d);
+        hipLaunchKernelGGL((sweep_reduce_kernel<double>), dim3((unsigned)((S.p + 255) / 256)), dim3(256), 0, s, a.work, a.grad, S.p,
+                           ns, int64_t(0), (const int32_t*)nullptr, a.sub_scale, a.sub_vec);
+    hipLaunchKernelGGL(filter_classify_kernel, dim3(1), dim3(kClassifyThreads), 0, s, a.grad, a.groups, a.group_sizes, a.G, a.slot,
+                       a.penalty, a.tstar, S.err, S.nrm, S.fp_term(), a.sq_part, filter_norm_parts(S.n), a.sub_scale, a.sub_vec,
+                       stage, a.screen_cols, na, a.pen0_cols, nb, L.ns, a.list, a.cap, a.meta_i, a.meta_d);
+    launch_sweep_list(X, a.v, a.grad, a.list, a.cap, a.meta_i, a.sub_scale, a.sub_vec, S, a.meta_d, a.meta_i + 1, stage, s);
 }
 
 #define INST(T)                                                                                                        \

@@ -864,8 +864,7 @@ int adelie_hip_filter_sweep_test(adelie_hip_design* d, const double* w, const do
         dgs.reserve(G); dslot.reserve(G); dlist.reserve(cap); dmeta.reserve(4); dmetad.reserve(2);
         const int n_part = filter_norm_parts(n);
         dpart.reserve(n_part);
-        const int64_t mx = std::max<int64_t>(std::max<int64_t>(cap, int64_t(scols.size())), int64_t(pen0.size()));
-        work.reserve(size_t(std::max(std::max(sweep_list_work_elems(n, p, mx), shadow_sweep_work_elems(n, p)), sweep_work_elems(n, p))));
+        work.reserve(size_t(std::max(filtered_sweep_work_elems(n, p, int64_t(scols.size() + pen0.size()), cap), sweep_work_elems(n, p))));
         dw.upload(w, n, s); dr.upload(r, n, s); dsc.upload(&sub_scale, 1, s); dpen.upload(penalty, G, s);
         dgroups.upload(groups, G, s); dgs.upload(group_sizes, G, s); dslot.upload(slot.data(), G, s);
         if (sub_vec) { dxm.reserve(p); dxm.upload(sub_vec, p, s); }
@@ -880,16 +879,13 @@ int adelie_hip_filter_sweep_test(adelie_hip_design* d, const double* w, const do
             launch_sweep<double>(X, dv.p, dgrad.p, 0, p, nullptr, dsc.p, xm, false, work.p, s);
             std::fill(exact, exact + p, uint8_t(1));
         } else {
-            AHIP_CHECK(hipMemsetAsync(dmeta.p, 0, 4 * sizeof(int32_t), s));
-            launch_vmul_sq(dw.p, dr.p, dv.p, n, dpart.p, s);
-            launch_shadow_sweep(sh, dv.p, dgrad.p, dsc.p, xm, work.p, s);
-            launch_filter_classify(dgrad.p, dgroups.p, dgs.p, G, dslot.p, dpen.p, tstar, sh, dpart.p, n_part, dsc.p, dlist.p, cap,
-                                   dmeta.p, dmetad.p, s);
-            if (!scols.empty())
-                launch_sweep_list(X, dv.p, dgrad.p, dscols.p, int64_t(scols.size()), nullptr, dsc.p, xm, &sh, dmetad.p, dmeta.p + 1, work.p, s);
-            if (!pen0.empty())
-                launch_sweep_list(X, dv.p, dgrad.p, dpen0.p, int64_t(pen0.size()), nullptr, dsc.p, xm, &sh, dmetad.p, dmeta.p + 1, work.p, s);
-            launch_sweep_list(X, dv.p, dgrad.p, dlist.p, cap, dmeta.p, dsc.p, xm, &sh, dmetad.p, dmeta.p + 1, work.p, s);
+            FilteredSweep a{};
+            a.w = dw.p; a.r = dr.p; a.v = dv.p; a.grad = dgrad.p; a.sub_scale = dsc.p; a.sub_vec = xm;
+            a.screen_cols = scols.empty() ? nullptr : dscols.p; a.n_screen_cols = int64_t(scols.size());
+            a.pen0_cols = pen0.empty() ? nullptr : dpen0.p; a.n_pen0_cols = int64_t(pen0.size());
+            a.groups = dgroups.p; a.group_sizes = dgs.p; a.G = G; a.slot = dslot.p; a.penalty = dpen.p; a.tstar = tstar;
+            a.sq_part = dpart.p; a.list = dlist.p; a.cap = cap; a.meta_i = dmeta.p; a.meta_d = dmetad.p; a.work = work.p;
+            enqueue_filtered_sweep(X, sh, a, s);
             AHIP_CHECK(hipMemcpyAsync(meta, dmeta.p, sizeof(meta), hipMemcpyDeviceToHost, s));
             AHIP_CHECK(hipStreamSynchronize(s));
             list.resize(size_t(meta[0]));

@@ -371,28 +371,20 @@
                     d_fs_pen0.upload(c0.data(), c0.size(), st);
                 }
             }
-            const int n_part = filter_norm_parts(n);
-            d_fs_part.reserve(size_t(n_part));
+            d_fs_part.reserve(size_t(filter_norm_parts(n)));
             d_fs_meta.reserve(4);
             d_fs_metad.reserve(2);
             d_fs_list.reserve(size_t(cap));
-            const int64_t wl = sweep_list_work_elems(n, p, std::max<int64_t>(std::max<int64_t>(cap, nv), fs_pen0_cols));
-            d_fs_work.reserve(size_t(std::max<int64_t>(wl, shadow_sweep_work_elems(n, p))));
-            const DenseView<T> X = D->dense<T>();
+            d_fs_work.reserve(size_t(filtered_sweep_work_elems(n, p, int64_t(nv) + fs_pen0_cols, cap)));
+            FilteredSweep a{};
+            a.w = d_w.p; a.r = d_r.p; a.v = d_v.p; a.grad = d_grad.p; a.sub_scale = rsum_dev; a.sub_vec = xm;
+            a.screen_cols = nv > 0 ? d_vcol.p : nullptr; a.n_screen_cols = nv;
+            a.pen0_cols = fs_pen0_cols > 0 ? d_fs_pen0.p : nullptr; a.n_pen0_cols = fs_pen0_cols;
+            a.groups = d_groups.p; a.group_sizes = d_gsizes.p; a.G = G; a.slot = d_slot.p; a.penalty = d_penalty.p; a.tstar = tstar;
+            a.sq_part = d_fs_part.p; a.list = d_fs_list.p; a.cap = cap; a.meta_i = d_fs_meta.p; a.meta_d = d_fs_metad.p;
+            a.work = d_fs_work.p;
             t_fsweep.begin(st);
-            AHIP_CHECK(hipMemsetAsync(d_fs_meta.p, 0, 4 * sizeof(int32_t), st));
-            launch_vmul_sq(d_w.p, d_r.p, d_v.p, n, d_fs_part.p, st);
-            launch_shadow_sweep(fs_shadow, d_v.p, d_grad.p, rsum_dev, xm, d_fs_work.p, st);
-            launch_filter_classify(d_grad.p, d_groups.p, d_gsizes.p, G, d_slot.p, d_penalty.p, tstar, fs_shadow, d_fs_part.p, n_part,
-                                   rsum_dev, d_fs_list.p, cap, d_fs_meta.p, d_fs_metad.p, st);
-            if (nv > 0)
-                launch_sweep_list(X, d_v.p, d_grad.p, d_vcol.p, nv, nullptr, rsum_dev, xm, &fs_shadow, d_fs_metad.p, d_fs_meta.p + 1,
-                                  d_fs_work.p, st);
-            if (fs_pen0_cols > 0)
-                launch_sweep_list(X, d_v.p, d_grad.p, d_fs_pen0.p, fs_pen0_cols, nullptr, rsum_dev, xm, &fs_shadow, d_fs_metad.p,
-                                  d_fs_meta.p + 1, d_fs_work.p, st);
-            launch_sweep_list(X, d_v.p, d_grad.p, d_fs_list.p, cap, d_fs_meta.p, rsum_dev, xm, &fs_shadow, d_fs_metad.p,
-                              d_fs_meta.p + 1, d_fs_work.p, st);
+            enqueue_filtered_sweep(D->dense<T>(), fs_shadow, a, st);
             t_fsweep.end(st);
             d_fs_meta.download(fs_meta, 4, st);
             grad_filtered = true;

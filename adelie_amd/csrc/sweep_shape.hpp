@@ -1,0 +1,32 @@
+// sweep_shape.hpp — how a sweep over a dense design cuts its grid: panels of columns times row splits.  Free of device code:
+// the kernels' launchers (kernels_sweep.hip) and a stand-alone host program of the tests include it.
+#pragma once
+#include <cstdint>
+
+namespace ahip {
+
+constexpr int kSweepThreads = 256; // threads of a sweep workgroup
+constexpr int kSweepCB = 4;        // columns per panel of sweep_kernel
+// the float32 shadow sweep (shadow_sweep_kernel): columns per panel, floats per load.  8 columns of 16-byte float loads read
+// 16 B of v per 64 B of design, as sweep_kernel does with 4 columns of doubles (measured: profiles/filter_sweep_fused.txt)
+constexpr int kShadowCB = 8, kShadowVec = 4;
+
+// vec: rows per thread and iteration; cb: columns per panel of the kernel the shape is for
+inline void sweep_shape(int64_t n, int64_t ncols, int vec, int64_t& blocks_c, int& nsplit, int64_t& rows_per_split,
+                        int cb = kSweepCB) {
+    blocks_c = (ncols + cb - 1) / cb;
+    const int64_t unit = int64_t(kSweepThreads) * vec;         // rows per block iteration
+    const int64_t max_split = (n + unit * 4 - 1) / (unit * 4); // >= 4 iterations per split
+    int64_t want = (1024 + blocks_c - 1) / blocks_c;
+    int64_t ns = want < 1 ? 1 : want;
+    if (ns > max_split) ns = max_split;
+    if (ns < 1) ns = 1;
+    if (ns > 65535) ns = 65535;
+    rows_per_split = (n + ns - 1) / ns;
+    rows_per_split = ((rows_per_split + unit - 1) / unit) * unit;
+    ns = (n + rows_per_split - 1) / rows_per_split;
+    if (ns < 1) ns = 1;
+    nsplit = int(ns);
+}
+
+} // namespace ahip
