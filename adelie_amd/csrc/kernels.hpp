@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "gram_shape.hpp"
 
 namespace ahip {
 
@@ -183,9 +184,10 @@ void launch_ptq(const T* P, int64_t ldp, const int32_t* pcols, int32_t M, const 
                 int64_t K, T* C, int64_t ldc, hipStream_t s);
 
 // ---- Gram (MFMA): for a in [0,M), b in [0,N):
-//   C[rowpos[a] + colpos[b]*ldc] = C[colpos[b] + rowpos[a]*ldc]
-//        = sum_i w[i] X[i,mcols[a]] X[i,ncols[b]]  - (center ? xm[mcols[a]]*xm[ncols[b]] : 0)
-// where rowpos[a] = m_pos0 + a, colpos[b] = n_pos0 + b.  `work` holds gram_work_elems(...) elements.
+//   C[rowpos[a] + colpos[b]*ldc] = sum_i w[i] X[i,mcols[a]] X[i,ncols[b]]  - (center ? xm[mcols[a]]*xm[ncols[b]] : 0)
+// where rowpos[a] = m_pos0 + a, colpos[b] = n_pos0 + b.  The mirror entry C[colpos[b] + rowpos[a]*ldc] gets the same value when
+// ncols is the tail of mcols at the same positions (the symmetric append); launch_gram_csc writes it on every call.
+// `work` holds gram_work_elems(...) elements.
 template <class T>
 void launch_gram(const DenseView<T>& X, const T* w, const int32_t* mcols, int32_t M, int32_t m_pos0,
                  const int32_t* ncols, int32_t N, int32_t n_pos0, const T* xm_by_col, bool center, T* C, int64_t ldc,
@@ -194,7 +196,9 @@ template <class T>
 void launch_gram_snp(const SnpView& X, const T* impute, const T* w, const int32_t* mcols, int32_t M, int32_t m_pos0,
                      const int32_t* ncols, int32_t N, int32_t n_pos0, const T* xm_by_col, bool center, T* C,
                      int64_t ldc, T* work, hipStream_t s);
-int64_t gram_work_elems(int64_t n, int64_t M, int64_t N);
+// gram_work_elems(n, M, N): gram_shape.hpp, like every *_work_elems of the MFMA block builds below
+// What the last block build launched by this host thread ran (the kernel-level test entry reports it).
+BuildLaunchInfo& last_build_launch();
 // symmetric diagonal block of M <= 128 columns: C[a + b*ldc] = C[b + a*ldc] = sum_i w_i X[i,cols[a]] X[i,cols[b]] (- xm xm^T);
 // only the lower-triangle MFMA tiles are computed.  `work` holds syrk_work_elems(n, M) elements.
 // Several diagonal blocks per launch (syrk_batch_kernel): block y of the batch has the nb[y] columns cols_base[off[y]...] and
@@ -206,7 +210,6 @@ struct SyrkBatch {
     int64_t dst[MAX];
     int32_t count;
 };
-int64_t syrk_batch_work_elems(int64_t n, int count);
 // the panel engine over compressed columns (kernels_sparse.hip): the panel step (phase (A) as launch_panel_step; the block's gradient straight
 // into gblk, centring included: no reduce launch) and the diagonal blocks of a batch (both triangles, leading dimension ldb)
 template <class T>
@@ -224,7 +227,6 @@ struct GramBatch {
     int64_t dst[MAX];
     int32_t count;
 };
-int64_t gram_batch_work_elems(int64_t n, int count);
 template <class T>
 void launch_gram_batch(const DenseView<T>& X, const T* w, const int32_t* cols_base, const GramBatch& b, const T* xm_by_col,
                        bool center, T* C_base, int64_t ldc, T* work, hipStream_t s);
@@ -242,9 +244,7 @@ struct StripBatch {
     int64_t dstX[MAX], dstD[MAX];
     int32_t count;
 };
-int strip_row_tiles(int m);                 // 16-row tiles the strip kernel is instantiated for (0: more rows than it takes)
-int64_t strip_work_elems(int64_t n, int count, int m_max);
-void set_strip_workgroups(int wgs);         // spread of the next strip builds launched by this host thread (default 512)
+void set_strip_workgroups(int wgs);         // spread of the next strip builds launched by this host thread (default kStripWgsDefault = 192, at most kStripWgsMax)
 void set_strip_lds(bool on);                // f64: fragments through the wave-private LDS transpose (default) or straight from HBM
 template <class T>
 void launch_strip_batch(const DenseView<T>& X, const T* w, const int32_t* cols_base, const StripBatch& b, const T* xm_by_col,
@@ -261,7 +261,6 @@ void launch_syrk(const DenseView<T>& X, const T* w, const int32_t* cols, int32_t
 template <class T>
 void launch_syrk_snp(const SnpView& X, const T* impute, const T* w, const int32_t* cols, int32_t M, const T* xm_by_col,
                        bool center, T* C, int64_t ldc, T* work, hipStream_t s);
-int64_t syrk_work_elems(int64_t n, int64_t M);
 
 // ---- abs_grad (solver_base.hpp:20-110) --------------------------------------------------------
 // abs_grad[g] = || grad[groups[g] : +gs] - regul_g * beta_slot ||,  regul_g = (1-alpha)*lmda*penalty[g] for screen

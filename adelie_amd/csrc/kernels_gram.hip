@@ -22,13 +22,19 @@
 namespace ahip {
 
 namespace {
+thread_local BuildLaunchInfo t_last_build;
+void record_build(int kind, int nsplit, int64_t kchunk, int tile, bool vecok, int n128 = 0, int n64 = 0, int symmetric = 0) {
+    BuildLaunchInfo r;
+    r.kind = kind; r.nsplit = nsplit; r.kchunk = kchunk; r.tile = tile; r.n128 = n128; r.n64 = n64;
+    r.vec16 = vecok ? 1 : 0; r.symmetric = symmetric;
+    t_last_build = r;
+}
+} // namespace
+BuildLaunchInfo& last_build_launch() { return t_last_build; }
 
-constexpr int BM = 128, KT = 32, LDK = KT + 2, GT = 256;
+namespace {
 
-// Workgroups a SMALL build (one diagonal block / one cross block / a batch of diagonal blocks) is spread over.  512 = one
-// full round of two resident workgroups per CU, the fastest for the build itself.  (Confining side-stream builds to fewer
-// workgroups was measured slower: 56 -> 2.69, 112 -> 2.99 vs 3.17 paths/s unconfined; the chain waits for the slower builds.)
-constexpr int kSmallGramWgs = 512;
+constexpr int BM = kGramBM, KT = kGramKT, LDK = KT + 2, GT = 256; // (gram_shape.hpp)
 
 // Block tile BM x BN = 128 x {64,128}; 4 waves: 2x2 of 64x64 (BN=128) or 4x1 of 32x64 (BN=64).
 // WNX = 4 (BN = 128): the four waves side by side, each 128 rows x 32 columns (8 x 2 MFMA tiles) — the "row strip" form of
@@ -595,17 +601,6 @@ __global__ void syrk_batch_reduce_kernel(const T* __restrict__ part, int nsplit,
     C[bb + int64_t(a) * ldc] = s;
 }
 
-inline void syrk_shape(int64_t n, int& nsplit, int64_t& kchunk) {
-    int64_t want = 512; // one full round of 2 resident blocks per CU
-    const int64_t max_split = (n + KT * 8 - 1) / (KT * 8);
-    if (want > max_split) want = max_split;
-    if (want < 1) want = 1;
-    kchunk = (n + want - 1) / want;
-    kchunk = ((kchunk + 255) / 256) * 256; // whole super-stages of the SNP body (a multiple of KT as well)
-    const int64_t ns = (n + kchunk - 1) / kchunk;
-    nsplit = int(ns < 1 ? 1 : ns);
-}
-
 template <class T, class Acc>
 void syrk_launch(Acc acc, bool vecok, const T* w, const int32_t* cols, int32_t M, int64_t n, const T* xm, bool center,
                  T* C, int64_t ldc, T* work, hipStream_t s) {
@@ -613,27 +608,16 @@ void syrk_launch(Acc acc, bool vecok, const T* w, const int32_t* cols, int32_t M
     int nsplit;
     int64_t kchunk;
     syrk_shape(n, nsplit, kchunk);
-    const int64_t SB = M <= 32 ? 32 : (M <= 64 ? 64 : 128);
+    const int64_t SB = syrk_tile_class(M);
+    record_build(BuildLaunchInfo::SYRK, nsplit, kchunk, int(SB), vecok);
 #define AHIP_SYRK(VOK, SBV) \
     hipLaunchKernelGGL((syrk_kernel<T, Acc, VOK, SBV>), dim3((unsigned)nsplit), dim3(GT), 0, s, acc, w, cols, M, n, kchunk, work)
-    if (M <= 32) { if (vecok) AHIP_SYRK(true, 32); else AHIP_SYRK(false, 32); }
-    else if (M <= 64) { if (vecok) AHIP_SYRK(true, 64); else AHIP_SYRK(false, 64); }
+    if (SB == 32) { if (vecok) AHIP_SYRK(true, 32); else AHIP_SYRK(false, 32); }
+    else if (SB == 64) { if (vecok) AHIP_SYRK(true, 64); else AHIP_SYRK(false, 64); }
     else { if (vecok) AHIP_SYRK(true, 128); else AHIP_SYRK(false, 128); }
 #undef AHIP_SYRK
     hipLaunchKernelGGL((gram_reduce_kernel<T>), dim3((unsigned)((M + 63) / 64), (unsigned)M), dim3(256), 0, s, work, nsplit, SB,
                        SB, M, M, cols, cols, 0, 0, xm, center ? 1 : 0, 1, C, ldc);
-}
-
-inline void syrk_batch_shape(int64_t n, int count, int& nsplit, int64_t& kchunk) {
-    // about one full round of 2 resident workgroups per CU over all the blocks of the batch (count = 1: the single-block shape)
-    int64_t want = (int64_t(kSmallGramWgs) + count - 1) / count;
-    const int64_t max_split = (n + KT * 8 - 1) / (KT * 8);
-    if (want > max_split) want = max_split;
-    if (want < 1) want = 1;
-    kchunk = (n + want - 1) / want;
-    kchunk = ((kchunk + 255) / 256) * 256; // whole super-stages of the SNP body (a multiple of KT as well)
-    const int64_t ns = (n + kchunk - 1) / kchunk;
-    nsplit = int(ns < 1 ? 1 : ns);
 }
 
 template <class T, class Acc>
@@ -645,7 +629,8 @@ void syrk_batch_launch(Acc acc, bool vecok, const T* w, const int32_t* cols_base
     syrk_batch_shape(n, b.count, nsplit, kchunk);
     int mx = 0;
     for (int y = 0; y < b.count; ++y) mx = std::max(mx, int(b.nb[y]));
-    const int SB = mx <= 32 ? 32 : (mx <= 64 ? 64 : 128);
+    const int SB = syrk_tile_class(mx);
+    record_build(BuildLaunchInfo::SYRK_BATCH, nsplit, kchunk, SB, vecok);
     const dim3 grid((unsigned)nsplit, (unsigned)b.count);
 #define AHIP_SYRKB(VOK, SBV) \
     hipLaunchKernelGGL((syrk_batch_kernel<T, Acc, VOK, SBV>), grid, dim3(GT), 0, s, acc, w, cols_base, b, n, kchunk, nsplit, work)
@@ -655,38 +640,6 @@ void syrk_batch_launch(Acc acc, bool vecok, const T* w, const int32_t* cols_base
 #undef AHIP_SYRKB
     hipLaunchKernelGGL((syrk_batch_reduce_kernel<T>), dim3((unsigned)((mx + 63) / 64), (unsigned)mx, (unsigned)b.count), dim3(256),
                        0, s, work, nsplit, SB, b, cols_base, xm, center ? 1 : 0, C_base, ldc);
-}
-
-// N tiling: full 128-wide tiles, then the remainder as one 64-wide tile when it fits (less padding than a 128 tile)
-struct GramShape {
-    int64_t Mt, n128, n64, Npad, kchunk;
-    int nsplit;
-};
-inline GramShape gram_shape(int64_t n, int64_t M, int64_t N) {
-    GramShape g;
-    g.Mt = (M + BM - 1) / BM;
-    g.n128 = N / 128;
-    const int64_t rem = N - g.n128 * 128;
-    g.n64 = 0;
-    if (rem > 64) ++g.n128;
-    else if (rem > 0) g.n64 = 1;
-    g.Npad = g.n128 * 128 + g.n64 * 64;
-    const int64_t tiles = g.Mt * (g.n128 + g.n64);
-    // Many tiles: ~3072 blocks so that the last partial round over the 256 CUs x 2 resident blocks costs little.  A single
-    // diagonal block of the panel engine: one full round (512 blocks) - more K-splits only add partial-tile traffic
-    // (128 KB written and re-read per split; measured -18 % at n = 500k).
-    const int64_t target = tiles <= 4 ? int64_t(kSmallGramWgs) : 3072;
-    int64_t want = (target + tiles - 1) / tiles;
-    const int64_t max_split = (n + KT * 8 - 1) / (KT * 8);
-    if (want > max_split) want = max_split;
-    const int64_t cap = (int64_t(1) << 28) / (g.Mt * BM * g.Npad); // partial buffer <= 2^28 elements
-    if (want > cap) want = cap;
-    if (want < 1) want = 1;
-    g.kchunk = (n + want - 1) / want;
-    g.kchunk = ((g.kchunk + KT - 1) / KT) * KT;
-    int64_t ns = (n + g.kchunk - 1) / g.kchunk;
-    g.nsplit = int(ns < 1 ? 1 : ns);
-    return g;
 }
 
 template <class T, class Acc>
@@ -699,6 +652,7 @@ void gram_launch(Acc acc, bool vecok, const T* w, const int32_t* mcols, int32_t 
     // "symmetric": the N list is the tail (or all) of the M list at the same positions -> skip tiles that lie
     // entirely above the diagonal of the (new x new) square; the reduce kernel mirrors them.
     const int symmetric = (mcols + (n_pos0 - m_pos0) == ncols && m_pos0 + M == n_pos0 + N && n_pos0 >= m_pos0) ? 1 : 0;
+    record_build(BuildLaunchInfo::GRAM, g.nsplit, g.kchunk, int(g.Mt), vecok, int(g.n128), int(g.n64), symmetric);
     auto blocks = [&](int64_t nt) {
         const int64_t npair = g.Mt * g.nsplit;
         return unsigned(((npair + 7) / 8) * 8 * nt);
@@ -720,13 +674,6 @@ void gram_launch(Acc acc, bool vecok, const T* w, const int32_t* mcols, int32_t 
 
 } // namespace
 
-int64_t gram_batch_work_elems(int64_t n, int count) {
-    int ns;
-    int64_t kc;
-    syrk_batch_shape(n, count, ns, kc);
-    return int64_t(count) * ns * BM * 128;
-}
-
 template <class T, class Acc>
 void gram_batch_launch(Acc acc, bool vecok, const T* w, const int32_t* cols_base, const GramBatch& b, int64_t n, const T* xm,
                        bool center, T* C_base, int64_t ldc, T* work, hipStream_t s) {
@@ -734,6 +681,7 @@ void gram_batch_launch(Acc acc, bool vecok, const T* w, const int32_t* cols_base
     int nsplit;
     int64_t kchunk;
     syrk_batch_shape(n, b.count, nsplit, kchunk);
+    record_build(BuildLaunchInfo::GRAM_BATCH, nsplit, kchunk, 128, vecok);
     const dim3 grid(unsigned(((nsplit + 7) / 8) * 8), unsigned(b.count));
     if (vecok)
         hipLaunchKernelGGL((gram_batch_kernel<T, Acc, true>), grid, dim3(GT), 0, s, acc, w, cols_base, b, n, kchunk, work,
@@ -759,12 +707,6 @@ void launch_gram_batch_snp(const SnpView& X, const T* impute, const T* w, const 
     gram_batch_launch<T, SnpAcc<T>>(acc, true, w, cols_base, b, X.n, xm_by_col, center, C_base, ldc, work, s);
 }
 
-int64_t syrk_batch_work_elems(int64_t n, int count) {
-    int nsplit;
-    int64_t kchunk;
-    syrk_batch_shape(n, count, nsplit, kchunk);
-    return int64_t(nsplit) * count * 128 * 128;
-}
 template <class T>
 void launch_syrk_batch(const DenseView<T>& X, const T* w, const int32_t* cols_base, const SyrkBatch& b, const T* xm_by_col,
                        bool center, T* C_base, int64_t ldc, T* work, hipStream_t s) {
@@ -780,13 +722,6 @@ void launch_syrk_batch_snp(const SnpView& X, const T* impute, const T* w, const 
     syrk_batch_launch<T, SnpAcc<T>>(acc, true, w, cols_base, b, X.n, xm_by_col, center, C_base, ldc, work, s);
 }
 
-int64_t syrk_work_elems(int64_t n, int64_t M) {
-    int nsplit;
-    int64_t kchunk;
-    syrk_shape(n, nsplit, kchunk);
-    const int64_t SB = M <= 32 ? 32 : (M <= 64 ? 64 : 128);
-    return int64_t(nsplit) * SB * SB;
-}
 template <class T>
 void launch_syrk(const DenseView<T>& X, const T* w, const int32_t* cols, int32_t M, const T* xm_by_col, bool center, T* C,
                    int64_t ldc, T* work, hipStream_t s) {
@@ -831,12 +766,6 @@ void launch_gram_multi(const MultiView<T>& X, const T* w, const int32_t* mcols, 
     const bool vecok = (X.ld % V == 0) && ((reinterpret_cast<uintptr_t>(X.X) % 16) == 0) &&
                        ((reinterpret_cast<uintptr_t>(X.ones) % 16) == 0);
     gram_launch<T, DenseOnesAcc<T>>(acc, vecok, w, mcols, M, 0, ncols, N, 0, X.nb, nullptr, false, C, ldc, work, s);
-}
-
-int64_t gram_work_elems(int64_t n, int64_t M, int64_t N) {
-    if (M <= 0 || N <= 0) return 0;
-    const GramShape g = gram_shape(n, M, N);
-    return int64_t(g.nsplit) * g.Mt * BM * g.Npad;
 }
 
 template <class T>

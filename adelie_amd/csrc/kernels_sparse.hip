@@ -643,6 +643,11 @@ template <class T>
 void launch_gram_csc(const CscView<T>& X, const T* w, const int32_t* mcols, int32_t M, int32_t m_pos0, const int32_t* ncols,
                      int32_t N, int32_t n_pos0, const T* xm_by_col, bool center, T* C, int64_t ldc, T* work, hipStream_t s) {
     if (M <= 0 || N <= 0) return;
+    {
+        BuildLaunchInfo r;
+        r.kind = BuildLaunchInfo::GRAM_CSC; r.nsplit = 1; r.tile = KB;
+        last_build_launch() = r;
+    }
     (void)hipMemsetAsync(work, 0, size_t(X.n) * KB * sizeof(T), s);
     T *mM = nullptr, *mN = nullptr, *wsum = nullptr;
     if (X.center) {
@@ -820,6 +825,11 @@ void launch_block_gram_csc(const CscView<T>& X, const T* w, const int32_t* cols_
     int mx = 0;
     for (int y = 0; y < sb.count; ++y) mx = std::max(mx, int(sb.nb[y]));
     if (mx <= 0) return;
+    {
+        BuildLaunchInfo r;
+        r.kind = BuildLaunchInfo::BLOCK_GRAM_CSC; r.nsplit = 1; r.tile = mx;
+        last_build_launch() = r;
+    }
     hipLaunchKernelGGL((csc_block_gram_kernel<T>), dim3(unsigned(mx), unsigned(sb.count)), dim3(256), 0, s, X, w, cols_base, sb,
                        xm_by_col, center ? 1 : 0, D0, ldb);
 }

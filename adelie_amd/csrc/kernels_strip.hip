@@ -33,8 +33,9 @@ namespace {
 constexpr int SGT = 256;      // threads per workgroup (4 waves = 4 column quarters)
 constexpr int SKC = 4;        // consecutive rows per lane and chunk
 constexpr int SCH = 4 * SKC;  // rows per chunk
+static_assert(SCH == kStripChunk, "gram_shape.hpp");
 constexpr int STG = 4;        // column tiles per wave
-constexpr int SW = 256;       // columns of a strip (previous block | own block)
+constexpr int SW = kStripW;   // columns of a strip (previous block | own block)
 
 // One wavefront's share of a K-split: 16 MT rows x 16 TGL columns.  The main loop is branch-free: rows / columns beyond the
 // strip's are CLAMPED to its last one (their products land in entries the reduce kernel never reads), whole 16-row chunks only;
@@ -389,22 +390,7 @@ __global__ __launch_bounds__(256) void strip_reduce_kernel(const T* __restrict__
     }
 }
 
-inline void strip_shape(int64_t n, int count, int wgs, int& nsplit, int64_t& kchunk) {
-    int64_t want = (int64_t(wgs) + count - 1) / count;
-    const int64_t max_split = (n + 8 * SCH - 1) / (8 * SCH);
-    if (want > max_split) want = max_split;
-    if (want < 1) want = 1;
-    kchunk = (n + want - 1) / want;
-    kchunk = ((kchunk + 2 * SCH - 1) / (2 * SCH)) * (2 * SCH); // whole pairs of chunks: 16-byte aligned row offsets
-    const int64_t ns = (n + kchunk - 1) / kchunk;
-    nsplit = int(ns < 1 ? 1 : ns);
-}
-
-// K-splits of a strip launch (per entry).  Each split writes a partial strip of 16 MT x 256 values that the reduce kernel reads
-// back (512 splits: 53 MB written per launch of the headline's screen strips, PMC), and in the path the strips only get the
-// ~60 CUs the fused launches leave, so more splits than that buy nothing: 192 instead of 512 is worth 1.5 ms per headline path
-// and 4.7 ms on config 3 (the chain starts to wait for the strips below ~112).  Hook ADELIE_HIP_STRIP_WGS.
-constexpr int kStripWgsDefault = 192;
+// (strip_shape, kStripWgsDefault: gram_shape.hpp)
 thread_local int t_strip_wgs = kStripWgsDefault;
 thread_local bool t_strip_lds = true;
 
@@ -412,16 +398,6 @@ thread_local bool t_strip_lds = true;
 
 void set_strip_workgroups(int wgs) { t_strip_wgs = wgs < 1 ? kStripWgsDefault : wgs; }
 void set_strip_lds(bool on) { t_strip_lds = on; }
-
-int strip_row_tiles(int m) { return m <= 16 ? 1 : (m <= 32 ? 2 : (m <= 48 ? 3 : (m <= 64 ? 4 : 0))); }
-
-int64_t strip_work_elems(int64_t n, int count, int m_max) {
-    int ns;
-    int64_t kc;
-    strip_shape(n, count, 1024, ns, kc); // (sized for the widest spread the hook allows)
-    const int mt = strip_row_tiles(m_max);
-    return int64_t(count) * ns * 16 * (mt ? mt : 4) * SW;
-}
 
 template <class T>
 void launch_strip_batch(const DenseView<T>& Xv, const T* w, const int32_t* cols_base, const StripBatch& b, const T* xm_by_col,
@@ -435,7 +411,12 @@ void launch_strip_batch(const DenseView<T>& Xv, const T* w, const int32_t* cols_
     const bool vecok = (Xv.ld % VecOf<T>::N == 0) && ((reinterpret_cast<uintptr_t>(Xv.X) % 16) == 0);
     int nsplit;
     int64_t kchunk;
-    strip_shape(Xv.n, b.count, std::min(t_strip_wgs, 1024), nsplit, kchunk);
+    strip_shape(Xv.n, b.count, std::min(t_strip_wgs, kStripWgsMax), nsplit, kchunk);
+    {
+        BuildLaunchInfo r;
+        r.kind = BuildLaunchInfo::STRIP; r.nsplit = nsplit; r.kchunk = kchunk; r.tile = MTv; r.vec16 = vecok ? 1 : 0;
+        last_build_launch() = r;
+    }
     const dim3 grid((unsigned)nsplit, (unsigned)b.count);
 #define AHIP_STRIP(VOK, MTV)                                                                                            \
     hipLaunchKernelGGL((strip_kernel<T, DenseAcc<T>, VOK, MTV>), grid, dim3(SGT), 0, s, acc, w, cols_base, b, Xv.n, kchunk, \
@@ -452,6 +433,7 @@ void launch_strip_batch(const DenseView<T>& Xv, const T* w, const int32_t* cols_
             else AHIP_STRIP_LT(4);
 #undef AHIP_STRIP_LT
             done = true;
+            last_build_launch().strip_lt = 1;
         }
     }
     if (!done) {

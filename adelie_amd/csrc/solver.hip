@@ -908,4 +908,151 @@ int adelie_hip_filter_sweep_test(adelie_hip_design* d, const double* w, const do
     return 0;
 }
 
+// One block build on caller-supplied inputs, through the launcher the solver calls (tests; include/adelie_hip.h has the layout of
+// `table` and `info`).  Everything the kernels index by is checked here against the buffers' sizes before anything is launched.
+int adelie_hip_block_build_test(adelie_hip_design* d, int mode, int64_t row_off, const void* w, const int32_t* cols, int64_t n_cols,
+                                const int64_t* table, int64_t count, const void* xm, int center, int64_t ldc, int strip_plain,
+                                void* out0, int64_t out0_elems, void* out1, int64_t out1_elems, int64_t* info) {
+    bool lds_changed = false;
+    try {
+        if (!d || !w || !cols || !table || !out0 || !info || n_cols < 1 || count < 1) throw make_core_error("bad arguments.");
+        if (d->cov || d->constraint || d->std_center || d->is_multi()) throw make_core_error("a plain dense, 2-bit or compressed-column design is required.");
+        if (!d->is_dense() && !d->is_snp() && !d->is_csc()) throw make_core_error("a plain dense, 2-bit or compressed-column design is required.");
+        if (center && !xm) throw make_core_error("center needs xm.");
+        if (row_off < 0 || row_off >= d->n || (row_off > 0 && !d->is_dense())) throw make_core_error("row_off: a dense design and 0 <= row_off < n are required.");
+        if (ldc < 1 || out0_elems < 1 || (out1 && out1_elems < 1)) throw make_core_error("bad output shape.");
+        const int64_t n = d->n - row_off, p = d->p;
+        for (int64_t i = 0; i < n_cols; ++i)
+            if (cols[i] < 0 || cols[i] >= p) throw make_core_error("column out of range.");
+        auto in_list = [&](int64_t off, int64_t cnt) { return off >= 0 && cnt >= 0 && off + cnt <= n_cols; };
+        // a block of rows x cs entries at `dst` (leading dimension ldc) lies inside a buffer of `elems` elements
+        auto fits = [&](int64_t dst, int64_t rows, int64_t cs, int64_t elems) {
+            return dst >= 0 && rows >= 1 && cs >= 1 && rows <= ldc && dst + (rows - 1) + (cs - 1) * ldc < elems;
+        };
+        enum { M_SYRK = 0, M_SYRK_BATCH = 1, M_GRAM = 2, M_GRAM_BATCH = 3, M_STRIP = 4 };
+        const int64_t* t = table;
+        SyrkBatch sb{};
+        GramBatch gb{};
+        StripBatch stb{};
+        int mx = 0;
+        if (mode == M_SYRK || mode == M_SYRK_BATCH) {
+            if (count > SyrkBatch::MAX || (mode == M_SYRK && count != 1)) throw make_core_error("bad block count.");
+            for (int64_t y = 0; y < count; ++y, t += 10) {
+                if (t[1] < 1 || t[1] > 128 || !in_list(t[0], t[1]) || !fits(t[2], t[1], t[1], out0_elems)) throw make_core_error("bad diagonal block.");
+                sb.off[y] = int32_t(t[0]); sb.nb[y] = int32_t(t[1]); sb.dst[y] = t[2];
+                mx = std::max(mx, int(t[1]));
+            }
+            sb.count = int32_t(count);
+        } else if (mode == M_GRAM) {
+            if (count != 1) throw make_core_error("bad block count.");
+            const int64_t M = t[1], m_pos0 = t[2], N = t[4], n_pos0 = t[5];
+            if (M < 1 || N < 1 || M > (1 << 20) || N > (1 << 20) || m_pos0 < 0 || n_pos0 < 0 || m_pos0 > (1 << 20) || n_pos0 > (1 << 20) ||
+                !in_list(t[0], M) || !in_list(t[3], N))
+                throw make_core_error("bad Gram panel.");
+            // the panel and its mirror image
+            const int64_t side = std::max(m_pos0 + M, n_pos0 + N);
+            if (side > ldc || (side - 1) * (ldc + 1) >= out0_elems) throw make_core_error("bad Gram panel.");
+        } else if (mode == M_GRAM_BATCH) {
+            if (count > GramBatch::MAX) throw make_core_error("bad block count.");
+            if (d->is_csc()) throw make_core_error("no batch of cross blocks on a compressed-column design.");
+            for (int64_t y = 0; y < count; ++y, t += 10) {
+                if (t[1] < 1 || t[1] > 128 || t[3] < 1 || t[3] > 128 || !in_list(t[0], t[1]) || !in_list(t[2], t[3]) ||
+                    !fits(t[4], t[1], t[3], out0_elems))
+                    throw make_core_error("bad cross block.");
+                gb.moff[y] = int32_t(t[0]); gb.m[y] = int32_t(t[1]); gb.noff[y] = int32_t(t[2]); gb.nn[y] = int32_t(t[3]); gb.dst[y] = t[4];
+            }
+            gb.count = int32_t(count);
+        } else if (mode == M_STRIP) {
+            if (count > StripBatch::MAX) throw make_core_error("bad block count.");
+            if (!d->is_dense()) throw make_core_error("strips are built on dense designs only.");
+            for (int64_t y = 0; y < count; ++y, t += 10) {
+                const int64_t m = t[1], c0n = t[3], c1n = t[5], row0 = t[6];
+                if (m < 1 || m > 64 || c0n < 0 || c0n > 128 || c1n < 1 || c1n > 128 || row0 < 0 || row0 + m != c1n || !in_list(t[0], m) ||
+                    !in_list(t[2], c0n) || !in_list(t[4], c1n) || !fits(t[8], c1n, c1n, out0_elems))
+                    throw make_core_error("bad strip.");
+                if (c0n > 0 && (!out1 || !fits(t[7], c1n, c0n, out1_elems))) throw make_core_error("bad strip (cross block).");
+                stb.voff[y] = int32_t(t[0]); stb.m[y] = int32_t(m); stb.c0off[y] = int32_t(t[2]); stb.c0n[y] = int32_t(c0n);
+                stb.c1off[y] = int32_t(t[4]); stb.c1n[y] = int32_t(c1n); stb.row0[y] = int32_t(row0); stb.dstX[y] = t[7]; stb.dstD[y] = t[8];
+                mx = std::max(mx, int(m));
+            }
+            stb.count = int32_t(count);
+        } else {
+            throw make_core_error("unknown mode.");
+        }
+        AHIP_CHECK(hipSetDevice(d->device));
+        hipStream_t s = d->stream;
+        last_build_launch() = BuildLaunchInfo{};
+        auto body = [&](auto tag) {
+            using T = decltype(tag);
+            DevBuf<T> dw, dxm, dC, dX, work;
+            DevBuf<int32_t> dcols;
+            dw.reserve(size_t(n)); dw.upload(static_cast<const T*>(w), size_t(n), s);
+            dcols.reserve(size_t(n_cols)); dcols.upload(cols, size_t(n_cols), s);
+            if (xm) { dxm.reserve(size_t(p)); dxm.upload(static_cast<const T*>(xm), size_t(p), s); }
+            dC.reserve(size_t(out0_elems)); dC.upload(static_cast<const T*>(out0), size_t(out0_elems), s);
+            if (out1) { dX.reserve(size_t(out1_elems)); dX.upload(static_cast<const T*>(out1), size_t(out1_elems), s); }
+            const T* xmp = xm ? dxm.p : nullptr;
+            const bool ctr = center != 0;
+            DenseView<T> Xd{};
+            if (d->is_dense()) {
+                Xd = d->dense<T>();
+                Xd.X += row_off;
+                Xd.n = n;
+            }
+            if (mode == M_SYRK) {
+                const int32_t* c = dcols.p + sb.off[0];
+                T* C = dC.p + sb.dst[0];
+                if (d->is_csc()) {
+                    SyrkBatch one = sb;
+                    one.off[0] = 0; one.dst[0] = 0;
+                    launch_block_gram_csc<T>(d->csc<T>(), dw.p, c, one, xmp, ctr, C, int(ldc), s);
+                } else {
+                    T* wk = work.reserve(size_t(syrk_work_elems(n, sb.nb[0])));
+                    if (d->is_dense()) launch_syrk<T>(Xd, dw.p, c, sb.nb[0], xmp, ctr, C, ldc, wk, s);
+                    else launch_syrk_snp<T>(d->snp(), snp_impute<T>(*d), dw.p, c, sb.nb[0], xmp, ctr, C, ldc, wk, s);
+                }
+            } else if (mode == M_SYRK_BATCH) {
+                if (d->is_csc()) {
+                    launch_block_gram_csc<T>(d->csc<T>(), dw.p, dcols.p, sb, xmp, ctr, dC.p, int(ldc), s);
+                } else {
+                    T* wk = work.reserve(size_t(syrk_batch_work_elems(n, sb.count)));
+                    if (d->is_dense()) launch_syrk_batch<T>(Xd, dw.p, dcols.p, sb, xmp, ctr, dC.p, ldc, wk, s);
+                    else launch_syrk_batch_snp<T>(d->snp(), snp_impute<T>(*d), dw.p, dcols.p, sb, xmp, ctr, dC.p, ldc, wk, s);
+                }
+            } else if (mode == M_GRAM) {
+                const int32_t M = int32_t(table[1]), N = int32_t(table[4]);
+                T* wk = work.reserve(size_t(std::max<int64_t>(raw_gram_work_elems(*d, n, M, N), 1)));
+                if (d->is_dense() && row_off > 0)
+                    launch_gram<T>(Xd, dw.p, dcols.p + table[0], M, int32_t(table[2]), dcols.p + table[3], N, int32_t(table[5]), xmp, ctr, dC.p, ldc, wk, s);
+                else
+                    raw_gram<T>(*d, dw.p, dcols.p + table[0], M, int32_t(table[2]), dcols.p + table[3], N, int32_t(table[5]), xmp, ctr, dC.p, ldc, wk, s);
+            } else if (mode == M_GRAM_BATCH) {
+                T* wk = work.reserve(size_t(gram_batch_work_elems(n, gb.count)));
+                if (d->is_dense()) launch_gram_batch<T>(Xd, dw.p, dcols.p, gb, xmp, ctr, dC.p, ldc, wk, s);
+                else launch_gram_batch_snp<T>(d->snp(), snp_impute<T>(*d), dw.p, dcols.p, gb, xmp, ctr, dC.p, ldc, wk, s);
+            } else {
+                T* wk = work.reserve(size_t(strip_work_elems(n, stb.count, mx)));
+                if (strip_plain) { set_strip_lds(false); lds_changed = true; }
+                launch_strip_batch<T>(Xd, dw.p, dcols.p, stb, xmp, ctr, dC.p, out1 ? dX.p : dC.p, ldc, wk, s);
+                if (lds_changed) { set_strip_lds(true); lds_changed = false; }
+            }
+            AHIP_CHECK(hipGetLastError());
+            AHIP_CHECK(hipMemcpyAsync(out0, dC.p, size_t(out0_elems) * sizeof(T), hipMemcpyDeviceToHost, s));
+            if (out1) AHIP_CHECK(hipMemcpyAsync(out1, dX.p, size_t(out1_elems) * sizeof(T), hipMemcpyDeviceToHost, s));
+            AHIP_CHECK(hipStreamSynchronize(s));
+        };
+        if (d->dtype == ADELIE_HIP_F64) body(double{});
+        else body(float{});
+        const BuildLaunchInfo& r = last_build_launch();
+        info[0] = r.kind; info[1] = r.nsplit; info[2] = r.kchunk; info[3] = r.tile; info[4] = r.n128; info[5] = r.n64;
+        info[6] = r.vec16; info[7] = r.strip_lt; info[8] = r.symmetric;
+        info[9] = d->is_csc() ? d->sp_nb : 0;
+    } catch (const std::exception& e) {
+        if (lds_changed) set_strip_lds(true);
+        set_last_error(e.what());
+        return 1;
+    }
+    return 0;
+}
+
 } // extern "C"

@@ -811,6 +811,27 @@ int adelie_hip_filter_sweep_test(adelie_hip_design* d, const double* w, const do
                                  const int64_t* screen_groups, int64_t n_screen, const int64_t* groups, const int64_t* group_sizes,
                                  int64_t G, const double* penalty, double tstar, double* grad, uint8_t* exact, int64_t* info);
 
+/* One block build of the panel engine on caller-supplied inputs (tests): ONE build launch and its reduce, through the launcher
+ * the solver calls.  The design is plain dense (f64 / f32), 2-bit or compressed-column; w (n - row_off), xm (p, may be null when
+ * center == 0) and the outputs are in the design's element type.  row_off > 0 (dense only) builds on rows [row_off, n) of the
+ * design: an offset that is not a multiple of 16 bytes selects the kernels' scalar-load variants.
+ * mode 0: one diagonal block; 1: a batch of diagonal blocks (<= 16); 2: the general Gram panel (the design-kind dispatch);
+ * 3: a batch of cross blocks (<= 16; dense, 2-bit); 4: a batch of strips (<= 8; dense).  `cols` (n_cols) is the column list the
+ * blocks index into; `table` holds `count` rows of 10 int64:
+ *   mode 0, 1: {off, nb, dst}                     block = cols[off .. off + nb), nb <= 128, written at out0 + dst
+ *   mode 2:    {moff, M, m_pos0, noff, N, n_pos0}  rows cols[moff ..), columns cols[noff ..), entry (m_pos0 + a, n_pos0 + b)
+ *   mode 3:    {moff, m, noff, nn, dst}
+ *   mode 4:    {voff, m, c0off, c0n, c1off, c1n, row0, dstX, dstD}   row0 + m == c1n; D in out0, the cross block in out1
+ * ldc is the leading dimension of every block.  strip_plain != 0 (mode 4): the f64 kernel without the LDS transpose.
+ * out0 (out0_elems) and out1 (out1_elems; may be null unless a strip has c0n > 0) are uploaded as the caller filled them and
+ * downloaded whole afterwards.  info[10] = {launcher (1 syrk, 2 syrk_batch, 3 gram, 4 gram_batch, 5 strip, 6 csc diagonal
+ * blocks, 7 csc gram), K-splits, rows per K-split, tile class (SB; M tiles of the general Gram; MT of a strip), 128-wide and
+ * 64-wide N tiles of the general Gram, 1 if the 16-byte-load variant ran, 1 if strip_lt_kernel ran, the general Gram's
+ * symmetric flag, row blocks of a compressed-column design}. */
+int adelie_hip_block_build_test(adelie_hip_design* d, int mode, int64_t row_off, const void* w, const int32_t* cols, int64_t n_cols,
+                                const int64_t* table, int64_t count, const void* xm, int center, int64_t ldc, int strip_plain,
+                                void* out0, int64_t out0_elems, void* out1, int64_t out1_elems, int64_t* info);
+
 #ifdef __cplusplus
 }
 #endif
