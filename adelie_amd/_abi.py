@@ -224,6 +224,7 @@ HIP_SYMBOLS = [
     "design_create_dense", "design_create_sparse", "design_create_csc", "design_create_standardized", "design_adopt_dense_dev", "design_create_snp_unphased",
     "design_create_snp_calldata", "design_create_snp_bed", "design_alias", "design_drop_shadow", "design_shadow_stats", "design_create_slice", "design_create_multi", "design_create_derived", "design_create_concat", "design_impute", "design_destroy",
     "design_create_one_hot", "design_create_interaction", "design_factor_groups",
+    "design_create_convex_relu",
     "design_glm_path_losses", "design_multi_path_losses", "design_batch_stats", "design_rows", "design_cols", "design_dtype",
     "design_device", "design_stream",
     "design_cmul", "design_ctmul", "design_bmul", "design_btmul", "design_mul", "design_mul_batch", "design_cov",
@@ -302,6 +303,7 @@ class Backend:
         sig("design_create_one_hot", ci, [vp, vp, p(vp)])
         sig("design_create_interaction", ci, [vp, vp, i64, vp, p(vp)])
         sig("design_factor_groups", i64, [vp, vp, vp, i64])
+        sig("design_create_convex_relu", ci, [vp, vp, i64, ci, p(vp)])
         sig("design_alias", ci, [vp, p(vp)])
         sig("design_drop_shadow", ci, [vp])
         sig("design_shadow_stats", ci, [vp, p(i64)])

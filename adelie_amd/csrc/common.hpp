@@ -18,7 +18,7 @@
 namespace ahip {
 
 // ---- every environment hook of libadelie_hip.so, in one place ------------------------------------------------------------------
-// Eleven variables.  They are read when a solve starts (Hooks::from_env, one call per solve): the tests force the multi-CU engines
+// Thirteen variables.  They are read when a solve starts (Hooks::from_env, one call per solve): the tests force the multi-CU engines
 // at sizes the CPU checker finishes in seconds and compare variants between two solves of ONE process, so reading them once at
 // library load would freeze the first test's setting.  None changes results beyond rounding.  (Python side: ADELIE_HIP_LIB picks
 // another build of this library, ADELIE_HIP_SWEEP_BATCH=0 keeps concurrent CV folds from sharing their sweeps.)
@@ -34,6 +34,9 @@ namespace ahip {
 //   ADELIE_HIP_FACTOR_SWEEP=0|1   full sweeps of a one-hot / interaction design read off Z (kernels_factor.hip) or off the
 //                                 expanded matrix like any dense design (default: kFactorSweepDefault below; the matrix
 //                                 operations read it at the call)                                                     [A/B, tests]
+//   ADELIE_HIP_RELU_SWEEP=0|1     full sweeps of a convex-relu design as the matrix product Z^T (mask o v) (kernels_relu.hip) or off
+//                                 the expanded matrix like any dense design (default: kReluSweepDefault below; the matrix
+//                                 operations read it at the call)                                                     [A/B, tests]
 //   ADELIE_HIP_FILTER_SWEEP=0|1   the invariance sweep of an eligible Gaussian lambda through the float32 shadow of the design
 //                                 (kernels_sweep.hip) or as the full f64 sweep; same results bit for bit             [A/B, tests]
 //   ADELIE_HIP_TIME_PANEL=1       per-launch HIP events around the panel step (bench.py's roofline leg)
@@ -45,6 +48,7 @@ struct Hooks {
     int std_panel = -1;      // ADELIE_HIP_STD_PANEL=0: a standardized dense / 2-bit view stays on its full-Gram engines
     int lookahead = -1, speculate = -1;
     int factor_sweep = -1;   // ADELIE_HIP_FACTOR_SWEEP (-1: unset)
+    int relu_sweep = -1;     // ADELIE_HIP_RELU_SWEEP (-1: unset)
     int filter_sweep = -1;   // ADELIE_HIP_FILTER_SWEEP (-1: unset)
     double irls_reuse = -1;
     bool time_panel = false;
@@ -66,6 +70,7 @@ struct Hooks {
         if (const char* e = std::getenv("ADELIE_HIP_STD_PANEL")) h.std_panel = std::atoi(e) != 0;
         if (const char* e = std::getenv("ADELIE_HIP_TRACE")) h.trace = std::max(1, std::atoi(e));
         h.factor_sweep = factor_sweep_env();
+        h.relu_sweep = relu_sweep_env();
         h.filter_sweep = filter_sweep_env();
         return h;
     }
@@ -77,11 +82,25 @@ struct Hooks {
         const char* e = std::getenv("ADELIE_HIP_FACTOR_SWEEP");
         return e ? int(std::atoi(e) != 0) : -1;
     }
+    static int relu_sweep_env() {
+        const char* e = std::getenv("ADELIE_HIP_RELU_SWEEP");
+        return e ? int(std::atoi(e) != 0) : -1;
+    }
+};
+// The hooks that choose a structured full sweep, one per structured kind of design (design_ops.hpp: raw_sweep_structured).  A
+// solve passes what it read when it started, the matrix operations read them at the call.
+struct SweepHooks {
+    int factor = -1, relu = -1;
+    static SweepHooks from_env() { return SweepHooks{Hooks::factor_sweep_env(), Hooks::relu_sweep_env()}; }
 };
 // Whether the full sweeps of a factor design take the structured kernel when ADELIE_HIP_FACTOR_SWEEP is unset: only once it is
 // measured at least as fast as the dense sweep on both shapes of scripts/bench_factor.py (profiles/factor_sweep.txt).
 constexpr bool kFactorSweepDefault = false;
 inline bool factor_sweep_on(int hook) { return hook < 0 ? kFactorSweepDefault : hook != 0; }
+// The same rule for a convex-relu design and ADELIE_HIP_RELU_SWEEP, on both shapes of scripts/bench_relu.py.  On: measured
+// faster than the dense sweep on both (profiles/relu_sweep.txt).
+constexpr bool kReluSweepDefault = true;
+inline bool relu_sweep_on(int hook) { return hook < 0 ? kReluSweepDefault : hook != 0; }
 // Whether an eligible Gaussian lambda takes the filtered invariance sweep (float32 shadow, kernels_sweep.hip) when
 // ADELIE_HIP_FILTER_SWEEP is unset.  On: the headline gains 16 ms of 252 ms per path against a parent-to-hook-off spread of
 // 0.3 ms in one interleaved job, with identical outputs (profiles/filter_sweep.txt).
@@ -504,6 +523,12 @@ struct adelie_hip_design {
     ahip::FactorChunk* fchunk = nullptr;
     int64_t f_nchunk = 0;
     std::vector<int64_t> f_outer;
+    // convex-relu design (adelie_hip_design_create_convex_relu): X above is the expanded (n, (gated ? 1 : 2) m d) matrix; next to
+    // it the column-major copy of Z in fz / fz_ld (d columns) and the (n, m) mask bytes, column-major with leading dimension
+    // rmask_ld, that the structured full sweep reads (kernels_relu.hip).  Owned unless alias.
+    uint8_t* rmask = nullptr;
+    int64_t rmask_ld = 0, r_d = 0, r_m = 0;
+    int r_gated = 0;
     // Sweep batching across solvers that run concurrently on one resident matrix (cv_grpnet folds on alias handles): the
     // batcher object lives with the design the aliases were made from (solver.hip::SweepBatcher, created on first use).
     adelie_hip_design* batch_owner = nullptr; // nullptr: this design itself
@@ -531,6 +556,10 @@ struct adelie_hip_design {
     bool factor() const { return fblk != nullptr; }
     template <class T> ahip::FactorView<T> factor_view() const {
         return ahip::FactorView<T>{static_cast<const T*>(fz), n, fz_ld, p, fblk, fchunk, f_nchunk};
+    }
+    bool relu() const { return rmask != nullptr; }
+    template <class T> ahip::ReluView<T> relu_view() const {
+        return ahip::ReluView<T>{static_cast<const T*>(fz), n, fz_ld, rmask, rmask_ld, r_d, r_m, r_gated};
     }
     template <class T> ahip::MultiView<T> multi() const {
         return ahip::MultiView<T>{static_cast<const T*>(X), nb, pb, ld, static_cast<const T*>(ones), int32_t(mK), int32_t(micpt),

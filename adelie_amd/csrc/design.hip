@@ -173,7 +173,7 @@ void op_sweep(adelie_hip_design* d, int64_t c0, int64_t ncols, const T* v, const
     T* dv = scratch<T>(d->s_n1, n);
     T* dw = scratch<T>(d->s_n2, n);
     T* dout = scratch<T>(d->s_p1, ncols);
-    const bool structured = raw_sweep_structured(*d, c0, ncols, nullptr, square, Hooks::factor_sweep_env());
+    const bool structured = raw_sweep_structured(*d, c0, ncols, nullptr, square, SweepHooks::from_env());
     T* work = scratch<T>(d->s_work, size_t(raw_sweep_work_elems(*d, ncols, structured)));
     AHIP_CHECK(hipMemcpyAsync(dv, v, n * sizeof(T), hipMemcpyHostToDevice, s));
     if (w) {
@@ -552,6 +552,54 @@ void create_factor_t(adelie_hip_design* Z, std::vector<FactorBlock>& blocks, con
     launch_derive_dense<T>(Z->dense<T>(), n, dz, nullptr, nullptr, nullptr, nullptr, fz, ld, s);
     launch_factor_expand<T>(d->factor_view<T>(), X, ld, s);
     AHIP_CHECK(hipStreamSynchronize(s)); // (the host tables above go out of scope)
+    *out = g.release();
+}
+
+// The expanded (n, P) convex-relu design of Z and the host's column-major (n, m) mask bytes, with the copies of Z and of the
+// mask that the structured sweep reads, on Z's device.
+template <class T>
+void create_relu_t(adelie_hip_design* Z, const uint8_t* mask, int64_t m, int gated, adelie_hip_design** out) {
+    constexpr int64_t kAlign = 32; // (>= kReluStep: a step of the structured sweep never leaves a column's padding)
+    static_assert(kAlign % kReluStep == 0, "the padded rows must cover the sweep's last step");
+    const int64_t n = Z->n, dz = Z->p;
+    const double cols = double(gated ? 1 : 2) * double(m) * double(dz);
+    if (cols > double((int64_t(1) << 31) - 64))
+        throw make_core_error("convex_relu(): the expanded design has more columns than the solver's 32-bit column indices address (" +
+                              gib(cols * double(n) * sizeof(T)) + " of values at least).");
+    const int64_t P = int64_t(cols);
+    DesignGuard g(new_design(n, P, Z->dtype, Z->device));
+    adelie_hip_design* d = g.get();
+    const int64_t ld = ((n + kAlign - 1) / kAlign) * kAlign;
+    hipStream_t s = d->stream;
+    T* X = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&X), std::max<size_t>(16, size_t(ld) * size_t(P) * sizeof(T))) != hipSuccess) {
+        (void)hipGetLastError();
+        throw make_core_error("convex_relu(): could not allocate the expanded design (" + std::to_string(n) + " x " + std::to_string(P) +
+                              ", " + gib(double(ld) * double(P) * sizeof(T)) + ") on the device.");
+    }
+    d->X = X;
+    d->ld = ld;
+    d->owned = true;
+    d->kind = adelie_hip_design::kDense;
+    T* fz = nullptr;
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fz), std::max<size_t>(16, size_t(ld) * size_t(dz) * sizeof(T))));
+    d->fz = fz;
+    d->fz_ld = ld;
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rmask), std::max<size_t>(16, size_t(ld) * size_t(m))));
+    d->rmask_ld = ld;
+    d->r_d = dz;
+    d->r_m = m;
+    d->r_gated = gated ? 1 : 0;
+    // zero the padding rows (the sweep's vector loads run into them), then copy Z and the mask and expand
+    AHIP_CHECK(hipMemsetAsync(fz, 0, size_t(ld) * size_t(dz) * sizeof(T), s));
+    AHIP_CHECK(hipMemsetAsync(d->rmask, 0, size_t(ld) * size_t(m), s));
+    if (ld > n && P > 0) AHIP_CHECK(hipMemset2DAsync(X + n, size_t(ld) * sizeof(T), 0, size_t(ld - n) * sizeof(T), size_t(P), s));
+    if (n > 0 && m > 0)
+        AHIP_CHECK(hipMemcpy2DAsync(d->rmask, size_t(ld), mask, size_t(n), size_t(n), size_t(m), hipMemcpyHostToDevice, s));
+    AHIP_CHECK(hipStreamSynchronize(Z->stream)); // (Z's own creation may still be in flight on its stream)
+    launch_derive_dense<T>(Z->dense<T>(), n, dz, nullptr, nullptr, nullptr, nullptr, fz, ld, s);
+    launch_relu_expand<T>(d->relu_view<T>(), X, ld, s);
+    AHIP_CHECK(hipStreamSynchronize(s)); // (the host's mask may go away)
     *out = g.release();
 }
 
@@ -1352,6 +1400,7 @@ int adelie_hip_design_alias(adelie_hip_design* src, adelie_hip_design** out) {
     d->std_center = src->std_center; d->std_iscale = src->std_iscale; // (not owned: std_owned stays false)
     d->fz = src->fz; d->fz_ld = src->fz_ld; d->fblk = src->fblk; d->fchunk = src->fchunk; d->f_nchunk = src->f_nchunk;
     d->f_outer = src->f_outer; // (a factor design's alias keeps the structure: CV folds sweep the same way)
+    d->rmask = src->rmask; d->rmask_ld = src->rmask_ld; d->r_d = src->r_d; d->r_m = src->r_m; d->r_gated = src->r_gated;
     d->alias = true;
     d->batch_owner = src->batch_owner ? src->batch_owner : src;
     *out = g.release();
@@ -1504,6 +1553,17 @@ int adelie_hip_design_create_interaction(adelie_hip_design* Z, const int64_t* pa
     ABI_CATCH
 }
 
+int adelie_hip_design_create_convex_relu(adelie_hip_design* Z, const uint8_t* mask, int64_t m, int gated, adelie_hip_design** out) {
+    ABI_TRY
+    if (!Z || !out || (!mask && m > 0 && Z->n > 0)) throw make_core_error("null argument.");
+    if (!Z->is_dense() || Z->cov || Z->constraint || Z->std_center)
+        throw make_core_error("convex_relu(): mat must be a resident dense naive design (not an SNP, sparse, view or covariance handle).");
+    if (m < 0) throw make_core_error("mask must be (n, m) where mat is (n, d).");
+    set_device(Z);
+    DTYPE_DISPATCH(Z, create_relu_t<T>(Z, mask, m, gated, out))
+    ABI_CATCH
+}
+
 int64_t adelie_hip_design_factor_groups(const adelie_hip_design* d, int64_t* groups, int64_t* group_sizes, int64_t cap) {
     if (!d || d->f_outer.empty()) return -1;
     const int64_t G = int64_t(d->f_outer.size()) - 1;
@@ -1546,6 +1606,7 @@ int adelie_hip_design_destroy(adelie_hip_design* d) {
         (void)hipFree(d->bptr);
         (void)hipFree(d->tptr); (void)hipFree(d->trow); (void)hipFree(d->tval);
         (void)hipFree(d->fz); (void)hipFree(d->fblk); (void)hipFree(d->fchunk);
+        (void)hipFree(d->rmask);
     }
     if (d->std_owned) { (void)hipFree(d->std_center); (void)hipFree(d->std_iscale); }
     if (d->ones) (void)hipFree(d->ones);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "gram_shape.hpp"
+#include "relu_shape.hpp"
 
 namespace ahip {
 
@@ -789,5 +790,26 @@ int64_t factor_sweep_work_elems(int64_t n, int64_t p, int64_t nchunk);
 template <class T>
 void launch_sweep_factor(const FactorView<T>& F, const T* v, T* out, const T* sub_scale, const T* sub_vec, T* work,
                          hipStream_t s);
+
+// ---- convex-relu designs (kernels_relu.hip): gated / signed ReLU expansions of a base matrix Z and a boolean mask ------------
+// Column j = sgn (m d) + j_m d + j_d of the (n, P) design holds mask[i, j_m] ? Z[i, j_d] : 0, negated for sgn = 1
+// (matrix_naive_convex_relu.ipp:10-30); a gated design has no sgn half (matrix_naive_convex_gated_relu.ipp), P = m d or 2 m d.
+template <class T>
+struct ReluView {
+    const T* Z;          // column-major copy of the d columns of Z, leading dimension ldz, rows n .. ldz - 1 zero
+    int64_t n, ldz;
+    const uint8_t* mask; // column-major (n, m) bytes, leading dimension ldm, rows n .. ldm - 1 zero
+    int64_t ldm, d, m;
+    int gated;
+    int64_t p() const { return (gated ? 1 : 2) * m * d; }
+};
+// X (column-major, leading dimension ld, rows >= n untouched) = the expanded design
+template <class T> void launch_relu_expand(const ReluView<T>& F, T* X, int64_t ld, hipStream_t s);
+// The full sweep out[c] = sum_i X[i, c] v[i] - (sub_vec ? sub_scale[0] * sub_vec[c] : 0) over all P columns as the (d, m) matrix
+// product Z^T (mask o v) on the matrix cores, read off Z, the mask and v alone; fixed summation order (row-slice partials in
+// `work`, relu_sweep_work_elems(n, d, m) elements, relu_shape.hpp).  Z must be finite: a non-finite value in a masked-out row
+// is a zero of the expanded design but poisons the product.
+template <class T>
+void launch_sweep_relu(const ReluView<T>& F, const T* v, T* out, const T* sub_scale, const T* sub_vec, T* work, hipStream_t s);
 
 } // namespace ahip

@@ -797,8 +797,8 @@ int adelie_hip_bench_sweep(adelie_hip_design* d, int64_t reps, double* ms_per_la
             using T = decltype(tag);
             DevBuf<T> v, out, xm, work, sc;
             v.reserve(d->n); out.reserve(d->p); xm.reserve(d->p); sc.reserve(1);
-            // a one-hot / interaction design: the structured sweep unless ADELIE_HIP_FACTOR_SWEEP says otherwise (read here)
-            const bool structured = raw_sweep_structured(*d, 0, d->p, nullptr, false, Hooks::factor_sweep_env());
+            // a one-hot / interaction or convex-relu design: the route ADELIE_HIP_FACTOR_SWEEP / ADELIE_HIP_RELU_SWEEP select (read here)
+            const bool structured = raw_sweep_structured(*d, 0, d->p, nullptr, false, SweepHooks::from_env());
             work.reserve(size_t(raw_sweep_work_elems(*d, d->p, structured)));
             launch_fill<T>(v.p, T(1) / T(d->n), d->n, s);
             launch_fill<T>(xm.p, T(0.5), d->p, s);

@@ -28,8 +28,9 @@
             ++cnt.n_sweeps_shared;
             return;
         }
-        // a one-hot / interaction design: the full sweep reads Z and v instead of the expanded matrix (kernels_factor.hip)
-        const bool structured = raw_sweep_structured(*D, 0, ncols, cols, square, hooks.factor_sweep);
+        // a one-hot / interaction or convex-relu design: the full sweep reads Z and v instead of the expanded matrix
+        // (kernels_factor.hip, kernels_relu.hip)
+        const bool structured = raw_sweep_structured(*D, 0, ncols, cols, square, SweepHooks{hooks.factor_sweep, hooks.relu_sweep});
         T* work = d_work_sweep.reserve(size_t(raw_sweep_work_elems(*D, ncols, structured)));
         raw_sweep<T>(*D, v, out, 0, ncols, cols, sub_scale, sub_vec, square, structured, work, st);
         if (structured) ++cnt.n_sweeps_factor;
@@ -335,6 +336,7 @@
         if constexpr (!std::is_same<T, double>::value) return T(0);
         if (fs_state < 0 || !filter_sweep_on(hooks.filter_sweep)) return T(0);
         if (!dense() || is_glm() || cov_mode || cons_on || multi() || std_generic() || batcher || D->factor() || has_pen2) return T(0);
+        if (D->relu() && relu_sweep_on(hooks.relu_sweep)) return T(0); // (its full sweeps are the structured kernel's)
         FilterRule f; // (filter_host.hpp: the rule itself, free of device calls)
         f.screen_rule = screen_rule == ADELIE_HIP_SCREEN_STRONG ? kFilterRuleStrong
                         : screen_rule == ADELIE_HIP_SCREEN_PIVOT ? kFilterRulePivot : -1;

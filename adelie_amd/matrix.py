@@ -12,7 +12,7 @@ vectors in/out, exactly the argument convention of the reference's pybind method
 import warnings
 
 import numpy as np
-from scipy.sparse import csc_matrix, csr_matrix
+from scipy.sparse import csc_matrix, csr_matrix, issparse
 
 from . import _abi
 
@@ -999,6 +999,113 @@ def interaction(mat, intr_map, levels=None, *, copy: bool = False, n_threads: in
         d = shape[1]
     pairs = _interaction_pairs(intr_map, d)
     return _factor_design("design_create_interaction", mat, levels, pairs, n_threads, device)
+
+
+# ---- convex-relu designs: gated / signed ReLU expansions of a base matrix and a boolean mask -------------------------------
+def _relu_column(j, d, m):
+    """``(sgn, j_m, j_d)`` of column ``j`` of a convex-relu design over ``d`` features and ``m`` mask columns, the reference's
+    order ``j = sgn * (m * d) + j_m * d + j_d`` (``matrix_naive_convex_relu.ipp:17-23``).  Needs no device."""
+    sgn, j = divmod(int(j), m * d)
+    j_m, j_d = divmod(j, d)
+    return sgn, j_m, j_d
+
+
+def _relu_expand(Z, mask, gated):
+    """The expanded ``(n, P)`` design in numpy, in the dtype of ``Z`` (what the device kernel writes).  Needs no device."""
+    Z, mask = np.asarray(Z), np.asarray(mask, dtype=bool)
+    n, d = Z.shape
+    m = mask.shape[1]
+    Y = np.where(mask[:, :, None], Z[:, None, :], Z.dtype.type(0)).reshape(n, m * d)
+    return np.asfortranarray(Y if gated else np.concatenate([Y, -Y], axis=1))
+
+
+# the grid of the structured sweep, restated from csrc/relu_shape.hpp (tests/test_relu_host.py compares the two)
+_RELU_TILE, _RELU_MT, _RELU_RUN = 16, 4, 8
+_RELU_STEP = 4 * _RELU_RUN
+
+
+def _relu_sweep_shape(n, d, m):
+    """``(d_tiles, m_groups, nslice, rows_per_slice)`` of the structured full sweep of a convex-relu design
+    (``relu_shape``, ``csrc/relu_shape.hpp``).  Needs no device."""
+    d_tiles = (d + _RELU_TILE - 1) // _RELU_TILE
+    m_groups = (m + _RELU_TILE * _RELU_MT - 1) // (_RELU_TILE * _RELU_MT)
+    groups = max(1, d_tiles * m_groups)
+    unit = _RELU_STEP
+    ns = max(1, min((2048 + groups - 1) // groups, (n + unit * 8 - 1) // (unit * 8), 1024))
+    rps = max(unit, ((n + ns - 1) // ns + unit - 1) // unit * unit)
+    ns = max(1, (n + rps - 1) // rps)
+    return d_tiles, m_groups, ns, rps
+
+
+class _ReluMatrix(_NativeMatrix):
+    """A convex-relu design: an ordinary resident dense design (every method of :class:`_NativeMatrix`) that also carries
+    the read-only ``_mask_shape = (n, m)`` and ``_gated``."""
+
+    @property
+    def _mask_shape(self):
+        return self._relu_mask_shape
+
+    @property
+    def _gated(self):
+        return self._relu_gated
+
+
+def convex_relu(mat, mask, *, gated: bool = False, copy: bool = False, n_threads: int = 1, device: int = 0):
+    """Feature matrix of the convex reformulation of a two-layer ReLU network (reference ``adelie.matrix.convex_relu``,
+    ``matrix.py:390-560``, ``matrix_naive_convex_gated_relu.ipp``, ``matrix_naive_convex_relu.ipp``).  From the base matrix
+    ``Z (n, d)`` and the boolean ``mask (n, m)`` whose columns are the diagonals of ``D_1 .. D_m``: ``Y = [D_1 Z, ..., D_m Z]``
+    with ``m * d`` columns when ``gated``, else ``[Y, -Y]`` with ``2 * m * d``.  Column ``sgn * (m * d) + j_m * d + j_d`` holds
+    ``Z[i, j_d]`` where ``mask[i, j_m]`` and zero elsewhere (whatever ``Z`` holds there), negated for ``sgn = 1``.
+
+    ``mat`` is anything :func:`dense` takes (an ndarray -- a C-ordered one warns as there --, a resident torch tensor), a
+    resident dense design, or a ``scipy.sparse.csc_matrix``, which is densified first (``Z`` is small beside the expansion,
+    and the expansion is dense anyway).  Only ``Z`` and the mask cross to the device; the ``n x P`` design is expanded there
+    by one kernel and lives in HBM next to copies of both: ``n*P + n*d`` values and ``n*m`` bytes (an f64 design that a
+    Gaussian path filters gets its float32 shadow on top, like any dense f64 design).  The result is an ordinary dense
+    design of the dtype of ``Z`` (it works under ``grpnet``, ``cv_grpnet``, ``standardize``, ``subset``, ``concatenate``,
+    ``kronecker_eye``, ``diagnostic`` ...) with read-only ``_mask_shape`` and ``_gated``; with ``ADELIE_HIP_RELU_SWEEP=1`` its
+    full gradient sweeps are the ``(d, m)`` matrix product ``Z^T (mask o v)`` on the matrix cores instead of a pass over the
+    expanded matrix (``Z`` must be finite for that).  ``copy`` and ``n_threads`` are accepted for parity."""
+    if n_threads < 1:
+        raise RuntimeError("adelie_core: n_threads must be >= 1.")
+    if isinstance(mat, _NativeMatrix):
+        if (getattr(mat, "_kind", None) != "dense" or isinstance(mat, (_MultiView, _StdView))):
+            raise RuntimeError("adelie_amd: mat must be an (n, d) array, a csc_matrix or a resident dense design.")
+        Z = mat
+    else:
+        if issparse(mat):
+            mat = np.asfortranarray(csc_matrix(mat).toarray())
+        Z = dense(mat, method="naive", n_threads=n_threads, device=device)
+    n, d = Z.rows(), Z.cols()
+    mask = np.asarray(mask)
+    if mask.ndim != 2 or mask.shape[0] != n:
+        raise RuntimeError("adelie_core: mask must be (n, m) where mat is (n, d).")
+    mask = np.asfortranarray(mask, dtype=bool)
+    m = mask.shape[1]
+    P = (1 if gated else 2) * m * d
+    itemsize = np.dtype(Z.dtype).itemsize
+    if P >= 2 ** 31 - 64:
+        raise RuntimeError(f"adelie_amd: the expanded design would have {P} columns "
+                           f"({n * float(P) * itemsize / 2 ** 30:.2f} GiB of values): more than the solver's "
+                           "32-bit column indices address.")
+    backend = Z._backend
+    if not backend.has("design_create_convex_relu"):
+        raise RuntimeError(f"{backend.path}: no adelie_hip_design_create_convex_relu -- rebuild the library.")
+    handle = _abi.C.c_void_p()
+    backend.check(backend.fn("design_create_convex_relu")(Z._handle, mask.view(np.uint8).ctypes.data, m, int(bool(gated)), handle))
+    mixin = MatrixNaiveBase64 if np.dtype(Z.dtype) == np.float64 else MatrixNaiveBase32
+
+    class _relu(_ReluMatrix, mixin):
+        pass
+
+    _relu.dtype = mixin.dtype
+    obj = _relu()
+    obj._init_native(backend, handle, n_threads)
+    obj._keep = None  # (the device copies of Z and of the mask are the design's own: nothing of the inputs is referenced)
+    obj._kind = "dense"
+    obj._relu_mask_shape = (n, m)
+    obj._relu_gated = bool(gated)
+    return obj
 
 
 # matrix.sparse(resident="auto"): kept sparse below this density or above this dense size, expanded to a dense design otherwise

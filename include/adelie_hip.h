@@ -196,6 +196,15 @@ int adelie_hip_design_create_one_hot(adelie_hip_design* Z, const int64_t* levels
  * two values of Z in the design's dtype.  Same kind of result and the same handle rules as adelie_hip_design_create_one_hot. */
 int adelie_hip_design_create_interaction(adelie_hip_design* Z, const int64_t* pairs, int64_t n_pairs, const int64_t* levels,
                                          adelie_hip_design** out);
+/* Additive entry point (the ABI version stays 14; callers look the symbol up).  Replaces MatrixNaiveConvexGatedReluDense and
+ * MatrixNaiveConvexReluDense {32,64}{C,F} and their Sparse forms (adelie/matrix.py:390-560, matrix_naive_convex_gated_relu.ipp,
+ * matrix_naive_convex_relu.ipp): from the (n, d) design Z and the (n, m) boolean mask the design [D_1 Z, ..., D_m Z] of m d
+ * columns (gated != 0) or [Y, -Y] of 2 m d columns (gated == 0); column sgn (m d) + j_m d + j_d holds Z[i, j_d] where
+ * mask[i, j_m] != 0 and zero elsewhere (a select: whatever Z holds in a masked-out row), negated for sgn = 1.  `mask` is the
+ * host's (n, m) column-major bytes.  Same kind of result and the same handle rules as adelie_hip_design_create_one_hot; what the
+ * design owns next to the expanded matrix is a column-major copy of Z and of the mask (n P + n d values and n m bytes), which
+ * the structured full sweep (ADELIE_HIP_RELU_SWEEP, kernels_relu.hip) multiplies on the matrix cores. */
+int adelie_hip_design_create_convex_relu(adelie_hip_design* Z, const uint8_t* mask, int64_t m, int gated, adelie_hip_design** out);
 /* The reference's read-only `groups` / `group_sizes` of the two classes above (outer[:-1] and diff(outer),
  * matrix_naive_one_hot.hpp / matrix_naive_interaction.hpp): copies min(G, cap) entries into each non-NULL array and returns the
  * number of blocks G, or -1 when `d` was not made by one of the two constructors (or is not an alias of such a design). */
@@ -800,6 +809,7 @@ const char* adelie_hip_pinball_result_error(const adelie_hip_pinball_result* r);
  * runs `reps` launches of the dominant kernel (the full gradient sweep grad = X^T(w*r) - rs*X_means
  * with fused per-group abs_grad) on resident buffers and returns the mean milliseconds per launch.
  * On a one-hot / interaction design it times the route ADELIE_HIP_FACTOR_SWEEP selects (read at the call).
+ * On a convex-relu design likewise the route ADELIE_HIP_RELU_SWEEP selects.
  * ------------------------------------------------------------------------------------------ */
 int adelie_hip_bench_sweep(adelie_hip_design* d, int64_t reps, double* ms_per_launch);
 /* One filtered invariance sweep on a dense f64 design (tests): v = w o r, the float32 shadow sweep, the classification of the
