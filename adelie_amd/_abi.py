@@ -222,7 +222,7 @@ S = dict(
 HIP_SYMBOLS = [
     "abi_version", "last_error", "device_count", "set_config",
     "design_create_dense", "design_create_sparse", "design_create_csc", "design_create_standardized", "design_adopt_dense_dev", "design_create_snp_unphased",
-    "design_create_snp_calldata", "design_create_snp_bed", "design_alias", "design_drop_shadow", "design_shadow_stats", "design_create_slice", "design_create_multi", "design_create_derived", "design_create_concat", "design_impute", "design_destroy",
+    "design_create_snp_calldata", "design_create_snp_bed", "design_alias", "design_drop_shadow", "design_shadow_stats", "design_shadow_info", "design_create_slice", "design_create_multi", "design_create_derived", "design_create_concat", "design_impute", "design_destroy",
     "design_create_one_hot", "design_create_interaction", "design_factor_groups",
     "design_create_convex_relu",
     "design_glm_path_losses", "design_multi_path_losses", "design_batch_stats", "design_rows", "design_cols", "design_dtype",
@@ -307,6 +307,7 @@ class Backend:
         sig("design_alias", ci, [vp, p(vp)])
         sig("design_drop_shadow", ci, [vp])
         sig("design_shadow_stats", ci, [vp, p(i64)])
+        sig("design_shadow_info", ci, [vp, p(i64), p(dbl)])
         sig("design_create_slice", ci, [vp, i64, i64, i64, i64, p(vp)])
         sig("design_batch_stats", ci, [vp, p(dbl)])
         sig("design_create_multi", ci, [vp, i64, ci, p(vp)])

@@ -18,7 +18,7 @@
 namespace ahip {
 
 // ---- every environment hook of libadelie_hip.so, in one place ------------------------------------------------------------------
-// Thirteen variables.  They are read when a solve starts (Hooks::from_env, one call per solve): the tests force the multi-CU engines
+// Fifteen variables.  They are read when a solve starts (Hooks::from_env, one call per solve): the tests force the multi-CU engines
 // at sizes the CPU checker finishes in seconds and compare variants between two solves of ONE process, so reading them once at
 // library load would freeze the first test's setting.  None changes results beyond rounding.  (Python side: ADELIE_HIP_LIB picks
 // another build of this library, ADELIE_HIP_SWEEP_BATCH=0 keeps concurrent CV folds from sharing their sweeps.)
@@ -39,6 +39,9 @@ namespace ahip {
 //                                 operations read it at the call)                                                     [A/B, tests]
 //   ADELIE_HIP_FILTER_SWEEP=0|1   the invariance sweep of an eligible Gaussian lambda through the float32 shadow of the design
 //                                 (kernels_sweep.hip) or as the full f64 sweep; same results bit for bit             [A/B, tests]
+//   ADELIE_HIP_SHADOW_KIND=f32|q15|auto  the encoding of that shadow copy, read when a design's copy is made: float32, int16
+//                                 with one scale per column, or (default) the rule of shadow_kind_host.hpp           [A/B, tests]
+//   ADELIE_HIP_SHADOW_MIN_BYTES=b `auto` considers q15 when the float32 copy would hold at least b bytes (default 2^30)  [test hook]
 //   ADELIE_HIP_TIME_PANEL=1       per-launch HIP events around the panel step (bench.py's roofline leg)
 //   ADELIE_HIP_TRACE=1|2          1: per-pass trace on stderr; 2: + enqueue / allocation / build timings
 struct Hooks {
@@ -77,6 +80,11 @@ struct Hooks {
     static int filter_sweep_env() {
         const char* e = std::getenv("ADELIE_HIP_FILTER_SWEEP");
         return e ? int(std::atoi(e) != 0) : -1;
+    }
+    static int shadow_kind_env() { return shadow_kind_parse(std::getenv("ADELIE_HIP_SHADOW_KIND")); }
+    static int64_t shadow_min_bytes_env() {
+        const char* e = std::getenv("ADELIE_HIP_SHADOW_MIN_BYTES");
+        return e ? int64_t(std::atoll(e)) : kShadowMinBytesDefault;
     }
     static int factor_sweep_env() {
         const char* e = std::getenv("ADELIE_HIP_FACTOR_SWEEP");
@@ -535,7 +543,10 @@ struct adelie_hip_design {
     void* batcher = nullptr;
     // float32 shadow of a dense f64 design for the filtered invariance sweep (kernels_sweep.hip: ShadowView), made on the first
     // eligible solve.  Like the batcher it lives with the design the aliases were made from, which frees it.
-    float* sh_X = nullptr;
+    // sh_kind (shadow_kind_host.hpp): float32 values, or int16 with the per-column scales in sh_scale.
+    void* sh_X = nullptr;
+    int sh_kind = ahip::kShadowF32;
+    double* sh_scale = nullptr; // (p,) q15 only
     int64_t sh_ld = 0;
     double* sh_err = nullptr; // (p,) ||x_j - xs_j||_2
     double* sh_nrm = nullptr; // (p,) ||xs_j||_2

@@ -1304,9 +1304,63 @@ int adelie_hip_design_batch_stats(adelie_hip_design* d, double* out) {
 
 static adelie_hip_design* shadow_owner(adelie_hip_design* d) { return d->batch_owner ? d->batch_owner : d; }
 static void shadow_free(adelie_hip_design* o) {
-    (void)hipFree(o->sh_X); (void)hipFree(o->sh_err); (void)hipFree(o->sh_nrm);
-    o->sh_X = nullptr; o->sh_err = nullptr; o->sh_nrm = nullptr;
+    (void)hipFree(o->sh_X); (void)hipFree(o->sh_err); (void)hipFree(o->sh_nrm); (void)hipFree(o->sh_scale);
+    o->sh_X = nullptr; o->sh_err = nullptr; o->sh_nrm = nullptr; o->sh_scale = nullptr;
     o->sh_ld = 0;
+    o->sh_kind = ahip::kShadowF32;
+}
+static size_t shadow_bytes(int kind, int64_t p, int64_t lds) {
+    return size_t(p) * size_t(lds) * (kind == ahip::kShadowQ15 ? sizeof(int16_t) : sizeof(float)) +
+           (kind == ahip::kShadowQ15 ? 3 : 2) * size_t(p) * sizeof(double);
+}
+// One copy of `kind` built and measured on d's stream: false (and nothing left allocated) when memory is short, a call fails or
+// an entry cannot be held.  (plain status checks: an error here must not leave the blocks behind with sh_state still 0)
+static bool shadow_build(adelie_hip_design* d, adelie_hip_design* o, int kind) {
+    const bool q15 = kind == ahip::kShadowQ15;
+    const int64_t lds = q15 ? ahip::shadow_q15_ld(d->n) : (d->n + 3) / 4 * 4; // 16-byte aligned columns
+    const size_t need = shadow_bytes(kind, d->p, lds);
+    size_t free_b = 0, total_b = 0;
+    AHIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    const size_t keep = std::max<size_t>(size_t(4) << 30, total_b / 10);
+    bool ok = free_b >= need && free_b - need >= keep;
+    int32_t* bad = nullptr;
+    if (ok) {
+        ok = hipMalloc(&o->sh_X, size_t(d->p) * size_t(lds) * (q15 ? sizeof(int16_t) : sizeof(float))) == hipSuccess &&
+             hipMalloc((void**)&o->sh_err, size_t(d->p) * sizeof(double)) == hipSuccess &&
+             hipMalloc((void**)&o->sh_nrm, size_t(d->p) * sizeof(double)) == hipSuccess &&
+             (!q15 || hipMalloc((void**)&o->sh_scale, size_t(d->p) * sizeof(double)) == hipSuccess) &&
+             hipMalloc((void**)&bad, sizeof(int32_t)) == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+    }
+    if (ok) {
+        int32_t h_bad = 0;
+        ok = hipMemsetAsync(bad, 0, sizeof(int32_t), d->stream) == hipSuccess;
+        if (ok && q15)
+            launch_shadow_build_q15(d->dense<double>(), static_cast<int16_t*>(o->sh_X), lds, o->sh_scale, o->sh_err, o->sh_nrm, bad,
+                                    d->stream);
+        else if (ok)
+            launch_shadow_build(d->dense<double>(), static_cast<float*>(o->sh_X), lds, o->sh_err, o->sh_nrm, bad, d->stream);
+        ok = ok && hipMemcpyAsync(&h_bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream) == hipSuccess;
+        ok = (hipStreamSynchronize(d->stream) == hipSuccess) && ok;
+        if (!ok) (void)hipGetLastError();
+        ok = ok && h_bad == 0; // an entry that is not finite (float32: or beyond FLT_MAX): no shadow for this design
+        o->sh_ld = lds;
+        o->sh_kind = kind;
+        ++o->sh_n_builds;
+    }
+    (void)hipFree(bad);
+    if (!ok) shadow_free(o);
+    return ok;
+}
+// err / nrm of the built copy on the host (the kind rule and shadow_info read them)
+static bool shadow_fetch_err_nrm(adelie_hip_design* d, adelie_hip_design* o, std::vector<double>& err, std::vector<double>& nrm) {
+    err.resize(size_t(d->p));
+    nrm.resize(size_t(d->p));
+    bool ok = hipMemcpyAsync(err.data(), o->sh_err, err.size() * sizeof(double), hipMemcpyDeviceToHost, d->stream) == hipSuccess;
+    ok = ok && hipMemcpyAsync(nrm.data(), o->sh_nrm, nrm.size() * sizeof(double), hipMemcpyDeviceToHost, d->stream) == hipSuccess;
+    ok = (hipStreamSynchronize(d->stream) == hipSuccess) && ok;
+    if (!ok) (void)hipGetLastError();
+    return ok;
 }
 
 bool adelie_hip_internal_shadow_acquire(adelie_hip_design* d, ahip::ShadowView* out) {
@@ -1315,41 +1369,28 @@ bool adelie_hip_internal_shadow_acquire(adelie_hip_design* d, ahip::ShadowView* 
     if (o->X != d->X || o->ld != d->ld || o->n != d->n || o->p != d->p) return false;
     std::lock_guard<std::mutex> lk(o->sh_mu);
     if (o->sh_state == 0) {
-        const int64_t lds = (d->n + 3) / 4 * 4; // 16-byte aligned columns
-        const size_t need = size_t(d->p) * size_t(lds) * sizeof(float) + 2 * size_t(d->p) * sizeof(double);
-        size_t free_b = 0, total_b = 0;
-        AHIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-        const size_t keep = std::max<size_t>(size_t(4) << 30, total_b / 10);
-        bool ok = free_b >= need && free_b - need >= keep;
-        int32_t* bad = nullptr;
-        if (ok) {
-            ok = hipMalloc((void**)&o->sh_X, size_t(d->p) * size_t(lds) * sizeof(float)) == hipSuccess &&
-                 hipMalloc((void**)&o->sh_err, size_t(d->p) * sizeof(double)) == hipSuccess &&
-                 hipMalloc((void**)&o->sh_nrm, size_t(d->p) * sizeof(double)) == hipSuccess &&
-                 hipMalloc((void**)&bad, sizeof(int32_t)) == hipSuccess;
-            if (!ok) (void)hipGetLastError();
+        // the kind (shadow_kind_host.hpp): q15 when forced, and under `auto` on a large design whose q15 copy measures well; a
+        // q15 copy the rule turns down is freed and the float32 copy made in its place
+        const int forced = ahip::Hooks::shadow_kind_env();
+        bool ok = false;
+        if (ahip::shadow_q15_wanted(forced, d->n, d->p, ahip::Hooks::shadow_min_bytes_env())) {
+            ok = shadow_build(d, o, ahip::kShadowQ15);
+            if (ok && forced != ahip::kShadowQ15) {
+                std::vector<double> err, nrm;
+                ok = shadow_fetch_err_nrm(d, o, err, nrm);
+                if (!ok || ahip::shadow_kind_pick(forced, err.data(), nrm.data(), d->p) != ahip::kShadowQ15) {
+                    shadow_free(o);
+                    ok = ok && shadow_build(d, o, ahip::kShadowF32);
+                }
+            }
+        } else {
+            ok = shadow_build(d, o, ahip::kShadowF32);
         }
-        if (ok) {
-            int32_t h_bad = 0;
-            // (plain status checks: an error here must not leave the blocks behind with sh_state still 0)
-            ok = hipMemsetAsync(bad, 0, sizeof(int32_t), d->stream) == hipSuccess;
-            if (ok) launch_shadow_build(d->dense<double>(), o->sh_X, lds, o->sh_err, o->sh_nrm, bad, d->stream);
-            ok = ok && hipMemcpyAsync(&h_bad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream) == hipSuccess;
-            ok = (hipStreamSynchronize(d->stream) == hipSuccess) && ok;
-            if (!ok) (void)hipGetLastError();
-            ok = ok && h_bad == 0; // an entry beyond FLT_MAX or not finite: no shadow for this design
-            o->sh_ld = lds;
-            ++o->sh_n_builds;
-        }
-        (void)hipFree(bad);
-        if (!ok) {
-            shadow_free(o);
-            ++o->sh_n_ineligible;
-        }
+        if (!ok) ++o->sh_n_ineligible;
         o->sh_state = ok ? 1 : -1;
     }
     if (o->sh_state != 1) return false;
-    *out = ahip::ShadowView{o->sh_X, d->n, d->p, o->sh_ld, o->sh_err, o->sh_nrm};
+    *out = ahip::ShadowView{o->sh_X, d->n, d->p, o->sh_ld, o->sh_err, o->sh_nrm, o->sh_kind, o->sh_scale};
     return true;
 }
 void adelie_hip_internal_shadow_mark_stale(adelie_hip_design* d) {
@@ -1376,6 +1417,30 @@ int adelie_hip_design_shadow_stats(adelie_hip_design* d, int64_t* out) {
     adelie_hip_design* o = shadow_owner(d);
     std::lock_guard<std::mutex> lk(o->sh_mu);
     out[0] = o->sh_state; out[1] = o->sh_n_builds; out[2] = o->sh_n_ineligible;
+    ABI_CATCH
+}
+int adelie_hip_design_shadow_info(adelie_hip_design* d, int64_t* out_i, double* out_d) {
+    ABI_TRY
+    if (!d || !out_i || !out_d) throw make_core_error("null argument.");
+    adelie_hip_design* o = shadow_owner(d);
+    AHIP_CHECK(hipSetDevice(o->device));
+    std::lock_guard<std::mutex> lk(o->sh_mu);
+    out_i[0] = -1; out_i[1] = 0;
+    out_d[0] = 0; out_d[1] = 0;
+    if (o->sh_state == 1 && o->sh_X) {
+        out_i[0] = o->sh_kind;
+        out_i[1] = int64_t(shadow_bytes(o->sh_kind, o->p, o->sh_ld));
+        std::vector<double> err, nrm;
+        if (!shadow_fetch_err_nrm(o, o, err, nrm)) throw make_core_error("could not read the shadow's measurements.");
+        // e_j / ||x_j|| with the copy's own norm for ||x_j|| (they differ by at most e_j); a zero column counts 0
+        for (size_t j = 0; j < err.size(); ++j) {
+            const double q = err[j] == 0 ? 0.0 : err[j] / nrm[j];
+            err[j] = q >= 0 ? q : HUGE_VAL; // (NaN: inf / inf)
+        }
+        std::sort(err.begin(), err.end());
+        out_d[0] = err[(err.size() - 1) / 2];
+        out_d[1] = err.back();
+    }
     ABI_CATCH
 }
 
@@ -1611,7 +1676,7 @@ int adelie_hip_design_destroy(adelie_hip_design* d) {
     if (d->std_owned) { (void)hipFree(d->std_center); (void)hipFree(d->std_iscale); }
     if (d->ones) (void)hipFree(d->ones);
     if (d->batcher) adelie_hip_internal_free_batcher(d->batcher);
-    (void)hipFree(d->sh_X); (void)hipFree(d->sh_err); (void)hipFree(d->sh_nrm);
+    shadow_free(d);
     delete d;
     if (live_designs().fetch_sub(1) == 1) DevPool::trim();
     return 0;

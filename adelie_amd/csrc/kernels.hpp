@@ -5,6 +5,7 @@
 #include <cstdint>
 #include "gram_shape.hpp"
 #include "relu_shape.hpp"
+#include "shadow_kind_host.hpp"
 
 namespace ahip {
 
@@ -67,15 +68,25 @@ int64_t sweep_work_elems(int64_t n, int64_t ncols);
 // ---- filtered invariance sweep (kernels_sweep.hip): a float32 shadow of a dense f64 design ----------------------------------
 // Xs: the columns rounded to float32 (column-major, ld a multiple of 4); err[j] = ||x_j - xs_j||_2, nrm[j] = ||xs_j||_2 (both
 // rounded up).  |x_j.v - xs_j.v| as the two sweeps compute them differ by at most (err[j] + fp_term() * nrm[j]) * ||v||_2.
+// kind kShadowQ15 (shadow_kind_host.hpp): X holds int16 q_ij = rint(x_ij * (32767 / max_i |x_ij|)) clamped to +-32767 (column-major, ld
+// a multiple of 64, pad rows 0) and scale[j] = max_i |x_ij| / 32767; xs_j = scale[j] q_j in the two definitions above.
 struct ShadowView {
-    const float* X;
+    const void* X; // float (kShadowF32) or int16_t (kShadowQ15)
     int64_t n, p, ld;
     const double* err;
     const double* nrm;
-    double fp_term() const { return 4.0 * double(n) * 1.1102230246251565e-16; } // 4 n 2^-53: both accumulations' rounding
+    int kind = kShadowF32;
+    const double* scale = nullptr; // (p,) q15 only
+    // float32: 4 n 2^-53, both accumulations' rounding.  q15: (4 n + 8) 2^-53, derived at shadow_sweep_q15_kernel.
+    double fp_term() const { return (4.0 * double(n) + (kind == kShadowQ15 ? 8.0 : 0.0)) * 1.1102230246251565e-16; }
+    double elem_bytes() const { return kind == kShadowQ15 ? 2.0 : 4.0; }
 };
 // makes the copy and measures err / nrm; *bad |= 1 when an entry is not finite or beyond FLT_MAX
 void launch_shadow_build(const DenseView<double>& X, float* Xs, int64_t lds, double* err, double* nrm, int32_t* bad, hipStream_t s);
+// the q15 copy: lds = shadow_q15_ld(n); *bad |= 1 when an entry is not finite (any finite entry can be held)
+int64_t shadow_q15_ld(int64_t n);
+void launch_shadow_build_q15(const DenseView<double>& X, int16_t* Xq, int64_t lds, double* scale, double* err, double* nrm,
+                             int32_t* bad, hipStream_t s);
 // how many fixed-order partial sums of (w o r)^2 one filtered sweep leaves in sq_part
 int filter_norm_parts(int64_t n);
 // One filtered invariance sweep, all device pointers.  In order on one stream:

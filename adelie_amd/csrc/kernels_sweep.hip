@@ -951,6 +951,9 @@ template void launch_snp_impute<float>(const uint8_t*, int64_t, int64_t, int64_t
 //                           the open groups listed in group order.  It owns the four meta words: no memset ahead of it
 //   sweep_list_kernel       the listed columns (it reads their count from the device)
 // (a shape whose shadow or list splits the rows adds the reduce launch of those partials).
+// The copy has two kinds (shadow_kind_host.hpp picks one per design): float32 values, or q15 -- int16 values with one f64 scale
+// per column, a quarter of the design's bytes, with e_j about 4e-5 ||x_j|| on Gaussian columns.  Nothing but the build kernel
+// and the shadow part of the second launch knows the kind: the bound is the measured e_j either way.
 namespace {
 
 
@@ -988,6 +991,70 @@ __global__ __launch_bounds__(kThreads) void shadow_build_kernel(const double* __
         // (rounded up a little: the sums above carry their own rounding error)
         err[j] = sqrt(a) * (1.0 + 1e-9);
         nrm[j] = sqrt(b) * (1.0 + 1e-9);
+    }
+    if (any_bad) atomicOr(bad, 1);
+}
+
+// The q15 copy of one column per workgroup, in two passes: m = max_i |x_i|, then q_i = clamp(rint(x_i * (32767 / m)), +-32767) with
+// scale[j] = m / 32767 (one multiplication, round-half-even: a numpy restatement gives the same integers).  The copy it stands
+// for is xs_i = fl(scale q_i): a 0/1 column has err 0.  err is summed on (x_i - xs_i) / scale and nrm on q_i, so neither overflows
+// on a column of huge entries.  A column whose m is 0, or so small that 32767 / m overflows or m / 32767 is subnormal (m below
+// about 7.3e-304), is stored as zeros with scale 0 and err = sqrt(n) m >= ||x_j||: every scale in use is a normal number, which
+// the fp_term of the kind assumes.  Rows n .. lds-1 are written as 0.
+__global__ __launch_bounds__(kThreads) void shadow_build_q15_kernel(const double* __restrict__ X, int64_t ld, int64_t n,
+                                                                    int16_t* __restrict__ Xq, int64_t lds,
+                                                                    double* __restrict__ scale, double* __restrict__ err,
+                                                                    double* __restrict__ nrm, int32_t* __restrict__ bad) {
+#pragma clang fp contract(off) // x - fl(scale q) must not become one fma: the copy is fl(scale q), and a 0/1 column has err 0
+    const int64_t j = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const double* col = X + j * ld;
+    int16_t* dst = Xq + j * lds;
+    __shared__ double red[2][kThreads / 64];
+    double m = 0;
+    bool any_bad = false;
+    for (int64_t i = tid; i < n; i += kThreads) {
+        const double a = fabs(col[i]);
+        const bool ok = a <= DBL_MAX; // (false for NaN and +-inf)
+        any_bad = any_bad || !ok;
+        m = ok ? fmax(m, a) : m;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_down(m, off, 64));
+    if (lane == 0) red[0][wv] = m;
+    __syncthreads();
+    m = red[0][0];
+#pragma unroll
+    for (int w = 1; w < kThreads / 64; ++w) m = fmax(m, red[0][w]);
+    __syncthreads();
+    double inv = m > 0 ? 32767.0 / m : 0.0;
+    double sc = m / 32767.0;
+    if (!(inv <= DBL_MAX) || !(sc >= DBL_MIN)) { inv = 0; sc = 0; } // (a subnormal scale would round absolutely, not relatively)
+    double e2 = 0, q2 = 0;
+    for (int64_t i = tid; i < lds; i += kThreads) {
+        int q = 0;
+        if (i < n && sc > 0) {
+            double x = col[i];
+            if (!(fabs(x) <= DBL_MAX)) x = 0;
+            const double t = fmin(fmax(rint(__dmul_rn(x, inv)), -32767.0), 32767.0);
+            q = int(t);
+            const double d = (x - __dmul_rn(sc, t)) / sc;
+            e2 = fma(d, d, e2);
+            q2 = fma(t, t, q2);
+        }
+        dst[i] = int16_t(q);
+    }
+    e2 = wave_sum(e2);
+    q2 = wave_sum(q2);
+    if (lane == 0) { red[0][wv] = e2; red[1][wv] = q2; }
+    __syncthreads();
+    if (tid == 0) {
+        double a = 0, b = 0;
+        for (int w = 0; w < kThreads / 64; ++w) { a += red[0][w]; b += red[1][w]; }
+        scale[j] = sc;
+        // (rounded up a little: the sums above carry their own rounding error)
+        err[j] = (sc > 0 ? sc * sqrt(a) : sqrt(double(n)) * m) * (1.0 + 1e-9);
+        nrm[j] = sc * sqrt(b) * (1.0 + 1e-9);
     }
     if (any_bad) atomicOr(bad, 1);
 }
@@ -1128,6 +1195,106 @@ __global__ __launch_bounds__(kThreads) void shadow_sweep_kernel(const float* __r
             double s = 0;
 #pragma unroll
             for (int w = 0; w < kThreads / 64; ++w) s += red[w][tid];
+            if (nsplit == 1) {
+                if (sub_vec) s -= sub_scale[0] * sub_vec[c];
+                out[c] = s;
+            } else {
+                out[int64_t(split) * ncols + c] = s; // partial
+            }
+        }
+    }
+}
+
+// The same launch over the q15 copy (ShadowView kind kShadowQ15).  The exact-part workgroups are those of shadow_sweep_kernel; the others
+// take 16-byte non-temporal loads of 8 rows per lane and column, accumulate q . v in f64 and multiply the sum of their rows by
+// scale[c] once, before the centring term (a row split's partial is scaled before it is stored: sweep_reduce_kernel is shared).
+// fp_term of this kind (ShadowView::fp_term), with u = 2^-53, xs_i = fl(scale q_i) the copy that err / nrm were measured on
+// (scale is 0 or a normal number, shadow_build_q15_kernel, so a product with it rounds relatively):
+//   q_i is exact in f64 and every product enters through an fma, so the sum of n terms in any order, with the one rounding of
+//   the multiplication by scale somewhere in its tree, is off by at most n u scale sum|q_i v_i| <= n u (1 + u) nrm ||v||;
+//   scale q_i against xs_i: u nrm ||v||;
+//   the f64 sweep it is compared with: n u ||x_j|| ||v||, with ||x_j|| <= nrm + err;
+//   the subtractions of the same centring term from both: as in the float32 kind.
+// (2 n + 1) u nrm, doubled as the float32 kind's 2 n u is, and rounded up: fp_term = (4 n + 8) u.
+typedef int i4_t __attribute__((ext_vector_type(4)));
+template <int XVEC, int CB>
+__global__ __launch_bounds__(kThreads) void shadow_sweep_q15_kernel(const int16_t* __restrict__ Xq, int64_t ld,
+                                                                    const double* __restrict__ scale, const double* __restrict__ v,
+                                                                    double* __restrict__ out, int64_t n, int64_t ncols,
+                                                                    int64_t blocks_c, int64_t rows_per_split, int nsplit,
+                                                                    const double* __restrict__ sub_scale,
+                                                                    const double* __restrict__ sub_vec, DenseAcc<double> X,
+                                                                    const int32_t* __restrict__ xa, int64_t na,
+                                                                    const int32_t* __restrict__ xb, int64_t nb,
+                                                                    int64_t x_rows_per_split, int x_nsplit, double* __restrict__ stage) {
+    constexpr int VEC = kShadowVec16;
+    static_assert(VEC == 8, "one 16-byte load holds 8 rows");
+    const int tid = threadIdx.x;
+    const int64_t ne = na + nb;
+    const int64_t n_exact = ne * x_nsplit;
+    __shared__ double red[kThreads / 64][CB];
+    if (int64_t(blockIdx.x) < n_exact) {
+        const int64_t c = int64_t(blockIdx.x) % ne;
+        const int64_t xsplit = int64_t(blockIdx.x) / ne;
+        const int64_t j = c < na ? xa[c] : xb[c - na];
+        const int64_t xr0 = xsplit * x_rows_per_split;
+        const double s = list_column_sum<XVEC>(X, v, j, xr0, min(n, xr0 + x_rows_per_split), &red[0][0]);
+        if (tid == 0) stage[xsplit * ne + c] = s;
+        return;
+    }
+    const int64_t b = int64_t(blockIdx.x) - n_exact;
+    const int64_t cb = b % blocks_c;
+    const int split = int(b / blocks_c);
+    const int64_t r0 = int64_t(split) * rows_per_split;
+    const int64_t r1 = min(n, r0 + rows_per_split);
+    const int16_t* cp[CB];
+#pragma unroll
+    for (int k = 0; k < CB; ++k) {
+        int64_t c = cb * CB + k;
+        if (c >= ncols) c = ncols - 1; // duplicate work on the tail panel, discarded below
+        cp[k] = Xq + c * ld;
+    }
+    double acc[CB];
+#pragma unroll
+    for (int k = 0; k < CB; ++k) acc[k] = 0;
+    // r0 is a multiple of 256 * 8 rows and ld of 64: every load below is 16-byte aligned and ends at or before row r1 <= n
+    const int64_t body_end = r0 + ((r1 - r0) / VEC) * VEC;
+    for (int64_t i = r0 + int64_t(tid) * VEC; i < body_end; i += int64_t(kThreads) * VEC) {
+        d2_t vv[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) vv[e] = *reinterpret_cast<const d2_t*>(v + i + 2 * e);
+        i4_t xx[CB];
+#pragma unroll
+        for (int k = 0; k < CB; ++k) xx[k] = __builtin_nontemporal_load(reinterpret_cast<const i4_t*>(cp[k] + i));
+#pragma unroll
+        for (int k = 0; k < CB; ++k) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int wd = xx[k][e]; // rows i + 2e (low half) and i + 2e + 1 (high half)
+                acc[k] = fma(double(int(int16_t(wd))), vv[e][0], acc[k]);
+                acc[k] = fma(double(wd >> 16), vv[e][1], acc[k]);
+            }
+        }
+    }
+    for (int64_t i = body_end + tid; i < r1; i += kThreads) {
+        const double vi = v[i];
+#pragma unroll
+        for (int k = 0; k < CB; ++k) acc[k] = fma(double(cp[k][i]), vi, acc[k]);
+    }
+    const int lane = tid & 63, wv = tid >> 6;
+#pragma unroll
+    for (int k = 0; k < CB; ++k) {
+        const double s = wave_sum(acc[k]);
+        if (lane == 0) red[wv][k] = s;
+    }
+    __syncthreads();
+    if (tid < CB) {
+        const int64_t c = cb * CB + tid;
+        if (c < ncols) {
+            double s = 0;
+#pragma unroll
+            for (int w = 0; w < kThreads / 64; ++w) s += red[w][tid];
+            s = __dmul_rn(s, scale[c]);
             if (nsplit == 1) {
                 if (sub_vec) s -= sub_scale[0] * sub_vec[c];
                 out[c] = s;
@@ -1347,6 +1514,13 @@ void launch_shadow_build(const DenseView<double>& X, float* Xs, int64_t lds, dou
     if (X.p <= 0) return;
     hipLaunchKernelGGL(shadow_build_kernel, dim3((unsigned)X.p), dim3(kThreads), 0, s, X.X, X.ld, X.n, Xs, lds, err, nrm, bad);
 }
+int64_t shadow_q15_ld(int64_t n) { return (n + kShadowPad16 - 1) / kShadowPad16 * kShadowPad16; }
+void launch_shadow_build_q15(const DenseView<double>& X, int16_t* Xq, int64_t lds, double* scale, double* err, double* nrm,
+                             int32_t* bad, hipStream_t s) {
+    if (X.p <= 0) return;
+    hipLaunchKernelGGL(shadow_build_q15_kernel, dim3((unsigned)X.p), dim3(kThreads), 0, s, X.X, X.ld, X.n, Xq, lds, scale, err, nrm,
+                       bad);
+}
 int filter_norm_parts(int64_t n) { return int(grid1d(n, kThreads, 1024)); }
 
 namespace {
@@ -1382,11 +1556,13 @@ void launch_sweep_list(const DenseView<double>& X, const double* v, double* out,
         hipLaunchKernelGGL(sweep_list_reduce_kernel, dim3((unsigned)((max_cols + 255) / 256)), dim3(256), 0, s, work, out, cols,
                            max_cols, count_dev, L.ns, sub_scale, sub_vec, guard.err, guard.nrm, guard.fp_term(), vnorm, flags);
 }
+// (the larger of the two kinds' split counts: the work buffer is sized before the kind is known to its owner)
 int64_t shadow_work_elems(int64_t n, int64_t p) {
     int64_t blocks_c, rps;
-    int ns;
+    int ns, ns16;
     sweep_shape(n, p, kShadowVec, blocks_c, ns, rps, kShadowCB);
-    return int64_t(ns) * p + 16;
+    sweep_shape(n, p, kShadowVec16, blocks_c, ns16, rps, kShadowCB16);
+    return int64_t(std::max(ns, ns16)) * p + 16;
 }
 int64_t list_work_elems(int64_t n, int64_t p, int64_t max_cols) {
     int64_t blocks_c, rps;
@@ -1407,16 +1583,27 @@ void enqueue_filtered_sweep(const DenseView<double>& X, const ShadowView& S, con
     hipLaunchKernelGGL(vmul_sq_kernel, dim3(grid1d(S.n, kThreads, 1024)), dim3(kThreads), 0, s, a.w, a.r, a.v, S.n, a.sq_part);
     int64_t blocks_c, rps;
     int ns;
-    sweep_shape(S.n, S.p, kShadowVec, blocks_c, ns, rps, kShadowCB);
+    const bool q15 = S.kind == kShadowQ15;
+    if (q15) sweep_shape(S.n, S.p, kShadowVec16, blocks_c, ns, rps, kShadowCB16);
+    else sweep_shape(S.n, S.p, kShadowVec, blocks_c, ns, rps, kShadowCB);
     const ListShape L = list_shape(X, a.v);
     DenseAcc<double> acc{X.X, X.ld};
     const dim3 grid((unsigned)((na + nb) * L.ns + blocks_c * ns));
-    if (L.vec)
-        hipLaunchKernelGGL((shadow_sweep_kernel<VecOf<double>::N>), grid, dim3(kThreads), 0, s, S.X, S.ld, a.v,
-                           ns == 1 ? a.grad : a.work, S.n, S.p, blocks_c, rps, ns, a.sub_scale, a.sub_vec, acc, a.screen_cols, na,
+    double* dst = ns == 1 ? a.grad : a.work;
+    if (q15 && L.vec)
+        hipLaunchKernelGGL((shadow_sweep_q15_kernel<VecOf<double>::N, kShadowCB16>), grid, dim3(kThreads), 0, s,
+                           static_cast<const int16_t*>(S.X), S.ld, S.scale, a.v, dst, S.n, S.p, blocks_c, rps, ns, a.sub_scale,
+                           a.sub_vec, acc, a.screen_cols, na, a.pen0_cols, nb, L.rps, L.ns, stage);
+    else if (q15)
+        hipLaunchKernelGGL((shadow_sweep_q15_kernel<1, kShadowCB16>), grid, dim3(kThreads), 0, s, static_cast<const int16_t*>(S.X),
+                           S.ld, S.scale, a.v, dst, S.n, S.p, blocks_c, rps, ns, a.sub_scale, a.sub_vec, acc, a.screen_cols, na,
                            a.pen0_cols, nb, L.rps, L.ns, stage);
+    else if (L.vec)
+        hipLaunchKernelGGL((shadow_sweep_kernel<VecOf<double>::N>), grid, dim3(kThreads), 0, s, static_cast<const float*>(S.X), S.ld,
+                           a.v, dst, S.n, S.p, blocks_c, rps, ns, a.sub_scale, a.sub_vec, acc, a.screen_cols, na, a.pen0_cols, nb,
+                           L.rps, L.ns, stage);
     else
-        hipLaunchKernelGGL((shadow_sweep_kernel<1>), grid, dim3(kThreads), 0, s, S.X, S.ld, a.v, ns == 1 ? a.grad : a.work, S.n,
+        hipLaunchKernelGGL((shadow_sweep_kernel<1>), grid, dim3(kThreads), 0, s, static_cast<const float*>(S.X), S.ld, a.v, dst, S.n,
                            S.p, blocks_c, rps, ns, a.sub_scale, a.sub_vec, acc, a.screen_cols, na, a.pen0_cols, nb, L.rps, L.ns,
                            stage);
     if (ns > 1)

@@ -403,7 +403,7 @@
         const int64_t exact = fs_pending_screen_cols + fs_meta[0];
         n_filter_exact_cols += exact;
         n_filter_shadow_cols += int64_t(p);
-        fsweep_bytes += double(n) * (double(exact) * 8.0 + double(p) * 4.0);
+        fsweep_bytes += double(n) * (double(exact) * 8.0 + double(p) * fs_shadow.elem_bytes());
         const FilterFollowUp fu = filter_follow_up(fs_meta[1]);
         if (fu.retire) {
             adelie_hip_internal_shadow_mark_stale(D);

@@ -10,6 +10,12 @@ constexpr int kSweepCB = 4;        // columns per panel of sweep_kernel
 // the float32 shadow sweep (shadow_sweep_kernel): columns per panel, floats per load.  8 columns of 16-byte float loads read
 // 16 B of v per 64 B of design, as sweep_kernel does with 4 columns of doubles (measured: profiles/filter_sweep_fused.txt)
 constexpr int kShadowCB = 8, kShadowVec = 4;
+// the 16-bit shadow sweep (shadow_sweep_q15_kernel): 16-byte loads of 8 rows.  At 8 columns a lane reads 64 B of v per 128 B of
+// design, at 16 columns 64 B per 256 B (the float32 kind's ratio).  Both widths were measured: 8 columns 421 us per launch on the
+// headline, 16 columns 477 us plus a reduce launch (one wave less per SIMD, two row splits: profiles/filter_sweep_q15.txt)
+constexpr int kShadowCB16 = 8, kShadowVec16 = 8;
+// leading dimension of the 16-bit copy: a multiple of this many elements (128 B), pad rows hold 0
+constexpr int kShadowPad16 = 64;
 
 // vec: rows per thread and iteration; cb: columns per panel of the kernel the shape is for
 inline void sweep_shape(int64_t n, int64_t ncols, int vec, int64_t& blocks_c, int& nsplit, int64_t& rows_per_split,

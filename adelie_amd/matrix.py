@@ -246,6 +246,17 @@ class _NativeMatrix:
         self._backend.check(self._backend.fn("design_shadow_stats")(self._handle, out))
         return {"state": int(out[0]), "builds": int(out[1]), "ineligible": int(out[2])}
 
+    def shadow_info(self):
+        """``{"kind", "bytes", "err_median", "err_max"}`` of the shadow copy as it stands: kind ``"f32"`` (float32 values) or
+        ``"q15"`` (int16 values with one scale per column; ``ADELIE_HIP_SHADOW_KIND`` forces either, the default picks q15 for
+        a design whose float32 copy would reach a gibibyte and whose columns a 16-bit copy holds to 2^-11 of their norm), or
+        ``None`` without a copy; its bytes on the device; median and maximum over the columns of ``e_j / ||x_j||``."""
+        oi = (_abi.C.c_int64 * 2)()
+        od = (_abi.C.c_double * 2)()
+        self._backend.check(self._backend.fn("design_shadow_info")(self._handle, oi, od))
+        kind = {0: "f32", 1: "q15"}.get(int(oi[0]))
+        return {"kind": kind, "bytes": int(oi[1]), "err_median": float(od[0]), "err_max": float(od[1])}
+
     def impute(self):
         """The ``(p,)`` impute values of an SNP design (what a missing call contributes)."""
         out = np.empty(self._cols, dtype=np.float64)
@@ -802,8 +813,8 @@ def dense(mat, *, method: str = "naive", copy: bool = False, n_threads: int = 1,
     mat : (n, p) ndarray or torch.Tensor
         float32/float64 matrix.  A numpy array is copied to HBM once.  A CUDA(ROCm) torch tensor is
         adopted in place (no copy); it must be F- or C-contiguous and is kept alive by the handle.  An adopted tensor must
-        not be modified while the handle lives: a float64 design keeps a float32 copy of itself for the invariance sweeps of
-        Gaussian paths (``drop_shadow()`` after a modification has the copy made again).
+        not be modified while the handle lives: a float64 design keeps a float32 or 16-bit copy of itself (``shadow_info()``)
+        for the invariance sweeps of Gaussian paths (``drop_shadow()`` after a modification has the copy made again).
     method : str
         ``"naive"`` (a design), ``"cov"`` (a covariance matrix for ``gaussian_cov`` / ``css_cov``) or ``"constraint"`` (an
         ``(m, d)`` constraint matrix for ``pinball``, kept row-major in HBM).

@@ -217,6 +217,10 @@ int adelie_hip_design_impute(adelie_hip_design* d, double* out);
  * times found ineligible (an entry float32 cannot hold, memory, a failed staleness check)}. */
 int adelie_hip_design_drop_shadow(adelie_hip_design* d);
 int adelie_hip_design_shadow_stats(adelie_hip_design* d, int64_t* out);
+/* The copy as it stands: out_i[2] = {kind (0 float32, 1 int16 with one f64 scale per column: ADELIE_HIP_SHADOW_KIND, -1 when
+ * there is no copy), its bytes on the device}, out_d[2] = {median, maximum over the columns of e_j / ||x_j||, the distance of a
+ * column from its copy relative to its norm}.  An addition to ABI 14. */
+int adelie_hip_design_shadow_info(adelie_hip_design* d, int64_t* out_i, double* out_d);
 int adelie_hip_design_destroy(adelie_hip_design* d);
 
 /* cv_grpnet post-processing on the device (adelie/cv.py:296-312, diagnostic.py:30-121): for the L

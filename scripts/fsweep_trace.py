@@ -12,7 +12,7 @@ import glob
 import statistics
 import sys
 
-FAMILY = ("shadow_sweep_kernel", "sweep_reduce_kernel", "filter_classify_kernel", "sweep_list_kernel", "sweep_list_reduce_kernel")
+FAMILY = ("shadow_sweep_kernel", "shadow_sweep_q15_kernel", "sweep_reduce_kernel", "filter_classify_kernel", "sweep_list_kernel", "sweep_list_reduce_kernel")
 
 
 def main(d):
