@@ -216,6 +216,7 @@ S = dict(
     t_sweep_ms=80, t_gram_ms=81, t_cd_ms=82, t_axpy_ms=83, n_sweep_launches=84, n_gram_launches=85,
     t_host_screen_ms=86, t_panel_step_ms=87, n_panel_step_launches=88, t_host_screen_wait_ms=89,
     t_fsweep_ms=90, n_fsweep_launches=91, fsweep_bytes=92,
+    n_screen_reads=93, n_screen_short=94, n_filter_open_cols=95,
 )
 
 # every symbol include/adelie_hip.h declares (checked by tests/test_abi.py)

@@ -39,6 +39,10 @@ namespace ahip {
 //                                 operations read it at the call)                                                     [A/B, tests]
 //   ADELIE_HIP_FILTER_SWEEP=0|1   the invariance sweep of an eligible Gaussian lambda through the float32 shadow of the design
 //                                 (kernels_sweep.hip) or as the full f64 sweep; same results bit for bit             [A/B, tests]
+//   ADELIE_HIP_FILTER_DEPTH=0|1   the pivot rule's threshold of a filtered sweep at the depth screen() is predicted to read
+//                                 (screen_reads_host.hpp) or at twice the worst case `need`; same results bit for bit [A/B, tests]
+//   ADELIE_HIP_FILTER_DEPTH_MARGIN=m  the margin of that depth over the prediction; 0 leaves none, so that threshold passes
+//                                 fall short and take the full sweep after all                                        [test hook]
 //   ADELIE_HIP_SHADOW_KIND=f32|q15|auto  the encoding of that shadow copy, read when a design's copy is made: float32, int16
 //                                 with one scale per column, or (default) the rule of shadow_kind_host.hpp           [A/B, tests]
 //   ADELIE_HIP_SHADOW_MIN_BYTES=b `auto` considers q15 when the float32 copy would hold at least b bytes (default 2^30)  [test hook]
@@ -53,6 +57,8 @@ struct Hooks {
     int factor_sweep = -1;   // ADELIE_HIP_FACTOR_SWEEP (-1: unset)
     int relu_sweep = -1;     // ADELIE_HIP_RELU_SWEEP (-1: unset)
     int filter_sweep = -1;   // ADELIE_HIP_FILTER_SWEEP (-1: unset)
+    int filter_depth = -1;   // ADELIE_HIP_FILTER_DEPTH (-1: unset)
+    double filter_depth_margin = -1; // ADELIE_HIP_FILTER_DEPTH_MARGIN (< 0: unset)
     double irls_reuse = -1;
     bool time_panel = false;
     bool cons_host = false; // ADELIE_HIP_CONS_HOST=1: box / one-sided objects on several coefficients visited on the host (A/B, tests)
@@ -75,6 +81,8 @@ struct Hooks {
         h.factor_sweep = factor_sweep_env();
         h.relu_sweep = relu_sweep_env();
         h.filter_sweep = filter_sweep_env();
+        if (const char* e = std::getenv("ADELIE_HIP_FILTER_DEPTH")) h.filter_depth = std::atoi(e) != 0;
+        if (const char* e = std::getenv("ADELIE_HIP_FILTER_DEPTH_MARGIN")) h.filter_depth_margin = std::max(0.0, std::atof(e));
         return h;
     }
     static int filter_sweep_env() {
@@ -114,6 +122,9 @@ inline bool relu_sweep_on(int hook) { return hook < 0 ? kReluSweepDefault : hook
 // 0.3 ms in one interleaved job, with identical outputs (profiles/filter_sweep.txt).
 constexpr bool kFilterSweepDefault = true;
 inline bool filter_sweep_on(int hook) { return hook < 0 ? kFilterSweepDefault : hook != 0; }
+// The same for ADELIE_HIP_FILTER_DEPTH (profiles/filter_depth.txt).
+constexpr bool kFilterDepthDefault = true;
+inline bool filter_depth_on(int hook) { return hook < 0 ? kFilterDepthDefault : hook != 0; }
 
 
 // util/exceptions.hpp:8-55 — same prefixes so that the Python layer's error-vs-warning split keeps working

@@ -13,6 +13,7 @@
 #include "common.hpp"
 #include "design_ops.hpp"
 #include "filter_host.hpp"
+#include "screen_reads_host.hpp"
 #include "cox.hpp"
 
 #include <algorithm>
@@ -570,6 +571,9 @@ struct Result : ResultBase {
             case ADELIE_HIP_S_T_FSWEEP_MS: return s.t_fsweep.ms;
             case ADELIE_HIP_S_N_FSWEEP_LAUNCHES: return double(s.t_fsweep.launches);
             case ADELIE_HIP_S_FSWEEP_BYTES: return s.fsweep_bytes;
+            case ADELIE_HIP_S_N_SCREEN_READS: return double(s.n_screen_reads);
+            case ADELIE_HIP_S_N_SCREEN_SHORT: return double(s.n_screen_short);
+            case ADELIE_HIP_S_N_FILTER_OPEN_COLS: return double(s.n_filter_open_cols);
             default:
                 if (which >= 900 && which < 908) return double(s.cd_dbg[which - 900]);
                 if (which >= 910 && which < 918) return 1e3 * s.t_host[which - 910];

@@ -160,6 +160,7 @@
         } else {
             const size_t old_groups = screen_transforms.size();
             update_screen_derived_base();
+            set_depth_threshold(n_new_active); // (in_screen knows the appends: the threshold of the next filtered sweep)
             device_append_screen();
             t_host[1] += sw.elapsed();
             sw.start();

@@ -329,14 +329,79 @@
     double fsweep_bytes = 0;
     int64_t n_sweeps_filtered = 0, n_sweeps_refilled = 0, n_filter_exact_cols = 0, n_filter_shadow_cols = 0;
     int64_t fs_pending_screen_cols = 0;
-    int64_t fs_cap() const { return filter_list_cap(int64_t(p)); }
+    int64_t fs_cap() const { return depth_rule() ? filter_depth_list_cap(int64_t(p)) : filter_list_cap(int64_t(p)); }
+
+    // whether the sweeps of this solve may be filtered at all (what does not change from lambda to lambda)
+    bool filter_eligible() const {
+        if constexpr (!std::is_same<T, double>::value) return false;
+        if (!filter_sweep_on(hooks.filter_sweep)) return false;
+        if (!dense() || is_glm() || cov_mode || cons_on || multi() || std_generic() || batcher || D->factor() || has_pen2) return false;
+        if (D->relu() && relu_sweep_on(hooks.relu_sweep)) return false; // (its full sweeps are the structured kernel's)
+        return true;
+    }
+
+    // ---- the depth rule (screen_reads_host.hpp, ADELIE_HIP_FILTER_DEPTH): screen_thr at the depth screen() is predicted to read
+    bool depth_rule() const {
+        return fs_state >= 0 && filter_depth_on(hooks.filter_depth) && screen_rule == ADELIE_HIP_SCREEN_PIVOT && filter_eligible();
+    }
+    bool depth_thr_valid = false;    // screen_thr was set by set_depth_threshold()
+    int64_t depth_pen0_cols = -1;    // columns of the groups without a penalty (-1: not counted yet)
+    int64_t depth_open_cols = 0;     // columns of the groups outside the screen set that lay at or above it then
+    int64_t depth_last_reads = 0, depth_last_subset = 0; // of the last screen() call that read the sorted scores
+    int64_t n_screen_reads = 0, n_screen_short = 0, n_filter_open_cols = 0;
+    std::vector<T> depth_scores, depth_scratch;
+    bool depth_scores_fresh = false; // depth_scores are the scores of every group under the present abs_grad and lmda
+    std::vector<idx> screen_append;
+
+    // after a screen() call, its appends known to in_screen: the threshold of the next sweep and of the call that follows it
+    void set_depth_threshold(int n_new_active) {
+        if (!depth_rule()) return;
+        const int64_t Gi = int64_t(G);
+        // the screen columns alone are past the byte rule: no later sweep of this path is filtered, and screen() sorts all G
+        if (fs_state == 1 && !filter_bytes_eligible(int64_t(screen_beta.size()) + std::max<int64_t>(depth_pen0_cols, 0), int64_t(n),
+                                                    int64_t(p), 0, double(fs_shadow.elem_bytes()))) {
+            depth_thr_valid = false;
+            depth_scores_fresh = false;
+            return;
+        }
+        const int64_t subset_next =
+            pivot_subset_size(int64_t(screen_set.size()), Gi, double(pivot_subset_ratio), int64_t(pivot_subset_min));
+        const int64_t reads_pred =
+            predict_reads(subset_next, depth_last_reads, depth_last_subset, int64_t(n_new_active), double(pivot_slack_ratio));
+        const double m = hooks.filter_depth_margin >= 0 ? hooks.filter_depth_margin : kDepthMargin;
+        const int64_t Dp = filter_depth(Gi, reads_pred, m);
+        if (!depth_scores_fresh) { // (screen() left them when it read the sorted scores itself)
+            depth_scores.resize(size_t(Gi));
+            for (idx i = 0; i < G; ++i) depth_scores[size_t(i)] = pivot_score(i);
+        }
+        depth_scores_fresh = false;
+        // (thresholds fall by a few per cent from lambda to lambda: the scores above 0.9 of the last one nearly always hold D)
+        screen_thr = depth_score_hinted(depth_scores, Dp, depth_thr_valid ? T(0.9) * screen_thr : T(0), depth_scratch);
+        depth_thr_valid = Gi > 0;
+        depth_open_cols = 0;
+        for (idx i = 0; i < G; ++i)
+            if (depth_scores[size_t(i)] >= screen_thr && !is_screen(i) && penalty[i] > 0) depth_open_cols += group_sizes[i];
+        if (hooks.trace)
+            std::fprintf(stderr, "[depth] lmda %.6g |S| %lld subset_next %lld reads_pred %lld D %lld thr %.9g open_cols %lld\n",
+                         double(lmda), (long long)screen_set.size(), (long long)subset_next, (long long)reads_pred, (long long)Dp,
+                         double(screen_thr), (long long)depth_open_cols);
+    }
 
     // tstar for the sweep at lambda lm, or 0 when this sweep has to be the full one
     T filter_threshold(T lm, int active_now) {
-        if constexpr (!std::is_same<T, double>::value) return T(0);
-        if (fs_state < 0 || !filter_sweep_on(hooks.filter_sweep)) return T(0);
-        if (!dense() || is_glm() || cov_mode || cons_on || multi() || std_generic() || batcher || D->factor() || has_pen2) return T(0);
-        if (D->relu() && relu_sweep_on(hooks.relu_sweep)) return T(0); // (its full sweeps are the structured kernel's)
+        if (fs_state < 0 || !filter_eligible()) return T(0);
+        if (depth_rule()) {
+            if (!depth_thr_valid || !(inv_next_lm > 0) || !(lm > 0) || !(alpha > 0)) return T(0);
+            const T tstar = std::min(std::min(alpha * lm, alpha * inv_next_lm), screen_thr);
+            if (!(tstar > 0) || !std::isfinite(tstar)) return T(0);
+            if (depth_pen0_cols < 0) depth_pen0_cols = int64_t(filter_unpenalized_cols(groups, group_sizes, penalty).size());
+            // (the open list overflows into a refill: a prediction near the capacity takes the full sweep directly)
+            if (depth_open_cols + depth_open_cols / 8 > fs_cap()) return T(0);
+            if (fs_state == 0) fs_state = adelie_hip_internal_shadow_acquire(D, &fs_shadow) ? 1 : -1;
+            if (fs_state != 1) return T(0);
+            const int64_t exact = int64_t(nv) + depth_pen0_cols + depth_open_cols;
+            return filter_bytes_eligible(exact, int64_t(n), int64_t(p), 0, double(fs_shadow.elem_bytes())) ? tstar : T(0);
+        }
         FilterRule f; // (filter_host.hpp: the rule itself, free of device calls)
         f.screen_rule = screen_rule == ADELIE_HIP_SCREEN_STRONG ? kFilterRuleStrong
                         : screen_rule == ADELIE_HIP_SCREEN_PIVOT ? kFilterRulePivot : -1;
@@ -402,6 +467,11 @@
         if (!grad_filtered) return;
         const int64_t exact = fs_pending_screen_cols + fs_meta[0];
         n_filter_exact_cols += exact;
+        n_filter_open_cols += fs_meta[0];
+        if (hooks.trace)
+            std::fprintf(stderr, "[fsweep] lmda %.6g screen+pen0 cols %lld open %d wanted %d flags %d predicted open %lld\n",
+                         double(fs_lm), (long long)fs_pending_screen_cols, int(fs_meta[0]), int(fs_meta[2]), int(fs_meta[1]),
+                         (long long)depth_open_cols);
         n_filter_shadow_cols += int64_t(p);
         fsweep_bytes += double(n) * (double(exact) * 8.0 + double(p) * fs_shadow.elem_bytes());
         const FilterFollowUp fu = filter_follow_up(fs_meta[1]);
@@ -881,32 +951,6 @@
         else update_gram_and_vars(d_w.p, d_xm.p, X_means, old_groups);
     }
 
-    // optimization/search_pivot.hpp:7-62
-    static int search_pivot(const std::vector<T>& x, const std::vector<T>& y, std::vector<T>& mses) {
-        const idx m = idx(x.size());
-        if (m <= 0) return -1;
-        mses[0] = std::numeric_limits<T>::infinity();
-        if (m == 1) return 0;
-        T y_mean = 0;
-        for (idx i = 0; i < m; ++i) y_mean += y[i];
-        y_mean /= T(m);
-        T x_sum = x[0], xsq_sum = x[0] * x[0], y_sum = y[0], yx_sum = y[0] * x[0], min_mse = mses[0];
-        int argmin = 0;
-        for (idx i = 1; i < m; ++i) {
-            x_sum += x[i];
-            xsq_sum += x[i] * x[i];
-            y_sum += y[i];
-            yx_sum += y[i] * x[i];
-            const T t_bar = ((i + 1) * x[i] - x_sum) / m;
-            const T var_t = ((i + 1) * x[i] * x[i] - 2 * x[i] * x_sum + xsq_sum - m * t_bar * t_bar);
-            const T cov_ty = (x[i] * (y_sum - (i + 1) * y_mean) - (yx_sum - y_mean * x_sum));
-            const T b1 = cov_ty / var_t;
-            mses[i] = -b1 * b1 * var_t;
-            if (mses[i] < min_mse) { argmin = int(i); min_mse = mses[i]; }
-        }
-        return argmin;
-    }
-
     // Stable LSD radix sort of (score, group) pairs by score: equal scores keep their group order, i.e. the same total
     // order as comparing the pairs, at a fraction of std::sort's cost for the G ~ 1e4..1e5 keys sorted once per lambda.
     static void sort_keyed(std::vector<std::pair<T, idx>>& v) {
@@ -951,6 +995,10 @@
     std::vector<std::pair<T, idx>> screen_keyed; // (kept between calls: no allocation per lambda)
     T screen_thr = 0;                            // see the pivot rule below
     bool screen_thr_valid = false;
+    // the pivot rule's score of a group at the lambda of the last sweep
+    T pivot_score(idx i) const {
+        return (penalty[i] <= 0) ? alpha * lmda : std::min(abs_grad[i] / penalty[i], alpha * lmda);
+    }
     void screen(T lmda_next, bool all_kkt_passed, int n_new_active) {
         const int old_size = int(screen_set.size());
         if (screen_rule == ADELIE_HIP_SCREEN_STRONG) {
@@ -971,57 +1019,66 @@
                 // group at or above it, in group order, and only those are sorted; whenever they are fewer than `need`
                 // (or there is no bound yet) all G are sorted as before.  Same pairs in the same order either way.
                 const int64_t need = int64_t(subset_size) + int64_t(std::ceil(pivot_slack_ratio * n_new_active)) + old_size + 2;
-                auto score = [&](int i) {
-                    return (penalty[i] <= 0) ? alpha * lmda : std::min(abs_grad[i] / penalty[i], alpha * lmda);
-                };
                 // (score, group) pairs, sorted in place: contiguous keys instead of an indirect comparator
                 std::vector<std::pair<T, idx>>& keyed = screen_keyed;
-                keyed.clear();
-                bool partial = false;
-                if (screen_thr_valid && need * 4 < Gi) {
+                const bool by_depth = depth_rule();
+                if (by_depth) depth_scores.resize(size_t(Gi)); // (set_depth_threshold() takes the scores from here)
+                auto collect = [&]() { // every group at or above screen_thr, in group order
+                    keyed.clear();
                     for (int i = 0; i < Gi; ++i) {
-                        const T wt = score(i);
+                        const T wt = pivot_score(idx(i));
+                        if (by_depth) depth_scores[size_t(i)] = wt;
                         if (wt >= screen_thr) keyed.emplace_back(wt, idx(i));
                     }
+                };
+                auto in_s = [&](idx i) { return is_screen(i); };
+                // The reference sorts with `weights[i] < weights[j]` only (solver_base.hpp:320-326): every group whose score is
+                // capped at alpha*lmda ties exactly, and std::sort leaves the order of ties unspecified.  Ties are broken by
+                // group index here (pair comparison) so that the screen insertion order (= CD visiting order) is reproducible.
+                bool partial = false;
+                PivotRead rd;
+                if (by_depth) {
+                    // The depth rule (screen_reads_host.hpp): screen_thr lies where set_depth_threshold() put it after the last
+                    // call, and the threshold pass stands iff the rule read nothing below what was collected.
+                    if (depth_thr_valid) {
+                        collect();
+                        sort_keyed(keyed);
+                        rd = pivot_read(keyed.data(), int64_t(keyed.size()), int64_t(Gi), int64_t(subset_size), pivot_slack_ratio,
+                                        int64_t(n_new_active), in_s, screen_append);
+                        partial = rd.sufficient;
+                        if (!partial) ++n_screen_short;
+                    }
+                } else if (screen_thr_valid && need * 4 < Gi) {
+                    collect();
                     partial = int64_t(keyed.size()) >= need;
+                    if (partial) sort_keyed(keyed);
                 }
                 if (!partial) {
                     ensure_exact_grad(); // (every score is read)
                     keyed.resize(size_t(Gi));
-                    for (int i = 0; i < Gi; ++i) keyed[size_t(i)] = std::make_pair(score(i), idx(i));
+                    for (int i = 0; i < Gi; ++i) keyed[size_t(i)] = std::make_pair(pivot_score(idx(i)), idx(i));
+                    if (by_depth)
+                        for (int i = 0; i < Gi; ++i) depth_scores[size_t(i)] = keyed[size_t(i)].first;
+                    sort_keyed(keyed);
                 }
-                // The reference sorts with `weights[i] < weights[j]` only (solver_base.hpp:320-326): every group whose score is
-                // capped at alpha*lmda ties exactly, and std::sort leaves the order of ties unspecified.  Ties are broken by
-                // group index here (pair comparison) so that the screen insertion order (= CD visiting order) is reproducible.
-                sort_keyed(keyed);
+                depth_scores_fresh = by_depth;
                 const int M = int(keyed.size()); // position ii of the full order is keyed[ii - (Gi - M)]
-                const int base = Gi - M;
-                {   // bound for the next lambda: the score twice as deep as this call could have read
+                if (!by_depth) { // bound for the next lambda: the score twice as deep as this call could have read
                     const int64_t depth = std::min<int64_t>(2 * need, M);
                     screen_thr = keyed[size_t(M - depth)].first;
                     screen_thr_valid = depth >= need;
                     screen_thr_count = depth;
                 }
-                std::vector<T> sub(subset_size), mses(subset_size), ind(subset_size);
-                for (int i = 0; i < subset_size; ++i) {
-                    sub[i] = keyed[size_t(Gi - subset_size + i - base)].first;
-                    ind[i] = T(i);
-                }
-                const int pivot_idx = search_pivot(ind, sub, mses);
-                const int full_pivot_idx = Gi - subset_size + pivot_idx;
-                for (int ii = Gi - 1; ii >= full_pivot_idx; --ii) {
-                    const idx i = keyed[size_t(ii - base)].second;
-                    if (is_screen(i)) continue;
-                    screen_set.push_back(i);
-                }
-                int count = 0;
-                for (int ii = full_pivot_idx - 1; ii >= base; --ii) {
-                    if (count >= pivot_slack_ratio * n_new_active) break;
-                    const idx i = keyed[size_t(ii - base)].second;
-                    if (is_screen(i)) continue;
-                    screen_set.push_back(i);
-                    ++count;
-                }
+                if (!by_depth || !partial)
+                    rd = pivot_read(keyed.data(), int64_t(M), int64_t(Gi), int64_t(subset_size), pivot_slack_ratio,
+                                    int64_t(n_new_active), in_s, screen_append);
+                screen_set.insert(screen_set.end(), screen_append.begin(), screen_append.end());
+                n_screen_reads += rd.reads;
+                depth_last_reads = rd.reads;
+                depth_last_subset = subset_size;
+                if (hooks.trace)
+                    std::fprintf(stderr, "[screen] lmda %.6g |S| %d n_new_active %d subset %d need %lld reads %lld M %d partial %d\n",
+                                 double(lmda), old_size, n_new_active, subset_size, (long long)need, (long long)rd.reads, M, int(partial));
             }
             if ((int(screen_set.size()) == old_size) && !all_kkt_passed) {
                 for (idx i = 0; i < G; ++i) {

@@ -57,7 +57,9 @@ _COUNTERS = ["n_basil_iters", "n_sweeps", "n_cd_visits_screen", "n_cd_visits_act
              "n_sweeps_filtered", "n_sweeps_refilled", "n_filter_exact_cols", "n_filter_shadow_cols"]
 _TIMERS = ["gram_flops", "t_sweep_ms", "t_gram_ms", "t_cd_ms", "t_axpy_ms", "n_sweep_launches", "n_gram_launches",
            "t_host_screen_ms", "t_panel_step_ms", "n_panel_step_launches", "t_host_screen_wait_ms",
-           "t_fsweep_ms", "n_fsweep_launches", "fsweep_bytes"]
+           "t_fsweep_ms", "n_fsweep_launches", "fsweep_bytes",
+           # (they follow the route a sweep took, like the three before them, so they stand with the timers)
+           "n_screen_reads", "n_screen_short", "n_filter_open_cols"]
 
 
 class _ProgressBar:

@@ -597,7 +597,11 @@ enum adelie_hip_scalar {
     ADELIE_HIP_S_T_HOST_SCREEN_WAIT_MS,
     /* the filtered invariance sweeps as a whole (T_SWEEP_MS / N_SWEEP_LAUNCHES count the launches that read the whole f64
      * design only): time, count, and the design bytes they asked for */
-    ADELIE_HIP_S_T_FSWEEP_MS, ADELIE_HIP_S_N_FSWEEP_LAUNCHES, ADELIE_HIP_S_FSWEEP_BYTES
+    ADELIE_HIP_S_T_FSWEEP_MS, ADELIE_HIP_S_N_FSWEEP_LAUNCHES, ADELIE_HIP_S_FSWEEP_BYTES,
+    /* the pivot rule's reading of the sorted scores (ADELIE_HIP_FILTER_DEPTH): positions screen() read, counted from the top
+     * and summed over its calls; threshold passes that fell short of what the rule read (each takes the full sweep and the
+     * sort of all G after all); columns the filtered sweeps listed as open and read a second time in f64 */
+    ADELIE_HIP_S_N_SCREEN_READS, ADELIE_HIP_S_N_SCREEN_SHORT, ADELIE_HIP_S_N_FILTER_OPEN_COLS
 };
 int64_t     adelie_hip_result_size(const adelie_hip_result* r, int which);
 /* Copies min(size, cap) elements: value vectors as double, index vectors as int64. */
