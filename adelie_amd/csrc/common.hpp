@@ -38,7 +38,7 @@ namespace ahip {
 //                                 the expanded matrix like any dense design (default: kReluSweepDefault below; the matrix
 //                                 operations read it at the call)                                                     [A/B, tests]
 //   ADELIE_HIP_FILTER_SWEEP=0|1   the invariance sweep of an eligible Gaussian lambda through the float32 shadow of the design
-//                                 (kernels_sweep.hip) or as the full f64 sweep; same results bit for bit             [A/B, tests]
+//                                 (kernels_filter.hip) or as the full f64 sweep; same results bit for bit             [A/B, tests]
 //   ADELIE_HIP_FILTER_DEPTH=0|1   the pivot rule's threshold of a filtered sweep at the depth screen() is predicted to read
 //                                 (screen_reads_host.hpp) or at twice the worst case `need`; same results bit for bit [A/B, tests]
 //   ADELIE_HIP_FILTER_DEPTH_MARGIN=m  the margin of that depth over the prediction; 0 leaves none, so that threshold passes
@@ -117,7 +117,7 @@ inline bool factor_sweep_on(int hook) { return hook < 0 ? kFactorSweepDefault : 
 // faster than the dense sweep on both (profiles/relu_sweep.txt).
 constexpr bool kReluSweepDefault = true;
 inline bool relu_sweep_on(int hook) { return hook < 0 ? kReluSweepDefault : hook != 0; }
-// Whether an eligible Gaussian lambda takes the filtered invariance sweep (float32 shadow, kernels_sweep.hip) when
+// Whether an eligible Gaussian lambda takes the filtered invariance sweep (float32 shadow, kernels_filter.hip) when
 // ADELIE_HIP_FILTER_SWEEP is unset.  On: the headline gains 16 ms of 252 ms per path against a parent-to-hook-off spread of
 // 0.3 ms in one interleaved job, with identical outputs (profiles/filter_sweep.txt).
 constexpr bool kFilterSweepDefault = true;
@@ -552,7 +552,7 @@ struct adelie_hip_design {
     // batcher object lives with the design the aliases were made from (solver.hip::SweepBatcher, created on first use).
     adelie_hip_design* batch_owner = nullptr; // nullptr: this design itself
     void* batcher = nullptr;
-    // float32 shadow of a dense f64 design for the filtered invariance sweep (kernels_sweep.hip: ShadowView), made on the first
+    // float32 shadow of a dense f64 design for the filtered invariance sweep (kernels_filter.hip: ShadowView), made on the first
     // eligible solve.  Like the batcher it lives with the design the aliases were made from, which frees it.
     // sh_kind (shadow_kind_host.hpp): float32 values, or int16 with the per-column scales in sh_scale.
     void* sh_X = nullptr;

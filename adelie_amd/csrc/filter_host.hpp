@@ -1,4 +1,4 @@
-// filter_host.hpp — the host-side decisions of the filtered invariance sweep (solver_screen.hpp, kernels_sweep.hip), free of
+// filter_host.hpp — the host-side decisions of the filtered invariance sweep (solver_screen.hpp, kernels_filter.hip), free of
 // any device call so that they also build into a stand-alone program (tests/native/filter_host_main.cpp, run under the address
 // and undefined-behaviour sanitizers by tests/test_filter_host.py).
 #pragma once

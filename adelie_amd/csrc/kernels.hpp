@@ -65,7 +65,7 @@ void launch_sweep_snp(const SnpView& X, const T* impute, const T* v, T* out, int
                       const int32_t* cols, const T* sub_scale, const T* sub_vec, bool square, T* work, hipStream_t s);
 int64_t sweep_work_elems(int64_t n, int64_t ncols);
 
-// ---- filtered invariance sweep (kernels_sweep.hip): a float32 shadow of a dense f64 design ----------------------------------
+// ---- filtered invariance sweep (kernels_filter.hip): a float32 shadow of a dense f64 design ----------------------------------
 // Xs: the columns rounded to float32 (column-major, ld a multiple of 4); err[j] = ||x_j - xs_j||_2, nrm[j] = ||xs_j||_2 (both
 // rounded up).  |x_j.v - xs_j.v| as the two sweeps compute them differ by at most (err[j] + fp_term() * nrm[j]) * ||v||_2.
 // kind kShadowQ15 (shadow_kind_host.hpp): X holds int16 q_ij = rint(x_ij * (32767 / max_i |x_ij|)) clamped to +-32767 (column-major, ld
@@ -77,7 +77,7 @@ struct ShadowView {
     const double* nrm;
     int kind = kShadowF32;
     const double* scale = nullptr; // (p,) q15 only
-    // float32: 4 n 2^-53, both accumulations' rounding.  q15: (4 n + 8) 2^-53, derived at shadow_sweep_q15_kernel.
+    // float32: 4 n 2^-53, both accumulations' rounding.  q15: (4 n + 8) 2^-53, derived at ShadowQ15 (kernels_filter.hip).
     double fp_term() const { return (4.0 * double(n) + (kind == kShadowQ15 ? 8.0 : 0.0)) * 1.1102230246251565e-16; }
     double elem_bytes() const { return kind == kShadowQ15 ? 2.0 : 4.0; }
 };
@@ -94,7 +94,7 @@ int filter_norm_parts(int64_t n);
 //   one launch that sweeps the shadow over all columns into grad and, in workgroups of its own, sweeps in f64 the columns
 //   that are exact whatever the shadow says (screen_cols, then pen0_cols: the groups without a penalty) into staging;
 //   the classification: ||v||, the staged columns reduced, compared with their shadow values and stored, and the columns of
-//   the groups that tstar cannot place listed (kernels_sweep.hip, filter_classify_kernel, also for meta_i / meta_d);
+//   the groups that tstar cannot place listed (kernels_filter.hip, filter_classify_kernel, also for meta_i / meta_d);
 //   the f64 sweep of the listed columns.
 // Every f64 value is the bits launch_sweep over all X.p columns gives that column.
 struct FilteredSweep {

@@ -1,4 +1,4 @@
-// shadow_kind_host.hpp — which encoding the shadow copy of a dense f64 design gets (design.hip, kernels_sweep.hip), free of any
+// shadow_kind_host.hpp — which encoding the shadow copy of a dense f64 design gets (design.hip, kernels_filter.hip), free of any
 // device call so that it also builds into a stand-alone program (tests/native/shadow_kind_main.cpp, run under the address and
 // undefined-behaviour sanitizers by tests/test_shadow_kind_host.py).
 #pragma once

@@ -308,7 +308,7 @@
         d_absgrad.download(abs_grad.data(), size_t(G), st);
     }
 
-    // ---- the filtered invariance sweep (kernels_sweep.hip: float32 shadow of a dense f64 design) ---------------------------
+    // ---- the filtered invariance sweep (kernels_filter.hip: float32 shadow of a dense f64 design) ---------------------------
     // A Gaussian lambda's full gradient is read exactly only for the screen set; every other group merely has to be placed
     // below or above the thresholds that kkt() and screen() compare it with.  tstar is the smallest of them: a sweep of the
     // shadow proves most groups below it, the rest are swept again in f64 (the bits of the full sweep).  Whoever needs every

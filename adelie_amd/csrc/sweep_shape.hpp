@@ -1,16 +1,17 @@
 // sweep_shape.hpp — how a sweep over a dense design cuts its grid: panels of columns times row splits.  Free of device code:
-// the kernels' launchers (kernels_sweep.hip) and a stand-alone host program of the tests include it.
+// the kernels' launchers (kernels_sweep.hip, kernels_filter.hip) and a stand-alone host program of the tests include it.
 #pragma once
 #include <cstdint>
 
 namespace ahip {
 
 constexpr int kSweepThreads = 256; // threads of a sweep workgroup
-constexpr int kSweepCB = 4;        // columns per panel of sweep_kernel
-// the float32 shadow sweep (shadow_sweep_kernel): columns per panel, floats per load.  8 columns of 16-byte float loads read
+// columns per panel of sweep_kernel (8 halves the re-reads of v through L2 and measured 6.66 against 6.85 TB/s)
+constexpr int kSweepCB = 4;
+// the float32 shadow sweep (shadow_sweep_kernel<ShadowF32>, kernels_filter.hip): columns per panel, floats per load.  8 columns of 16-byte float loads read
 // 16 B of v per 64 B of design, as sweep_kernel does with 4 columns of doubles (measured: profiles/filter_sweep_fused.txt)
 constexpr int kShadowCB = 8, kShadowVec = 4;
-// the 16-bit shadow sweep (shadow_sweep_q15_kernel): 16-byte loads of 8 rows.  At 8 columns a lane reads 64 B of v per 128 B of
+// the 16-bit shadow sweep (shadow_sweep_kernel<ShadowQ15>): 16-byte loads of 8 rows.  At 8 columns a lane reads 64 B of v per 128 B of
 // design, at 16 columns 64 B per 256 B (the float32 kind's ratio).  Both widths were measured: 8 columns 421 us per launch on the
 // headline, 16 columns 477 us plus a reduce launch (one wave less per SIMD, two row splits: profiles/filter_sweep_q15.txt)
 constexpr int kShadowCB16 = 8, kShadowVec16 = 8;

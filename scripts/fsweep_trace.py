@@ -12,7 +12,15 @@ import glob
 import statistics
 import sys
 
-FAMILY = ("shadow_sweep_kernel", "shadow_sweep_q15_kernel", "sweep_reduce_kernel", "filter_classify_kernel", "sweep_list_kernel", "sweep_list_reduce_kernel")
+FAMILY = ("shadow_sweep_kernel", "sweep_reduce_kernel", "filter_classify_kernel", "sweep_list_kernel", "sweep_list_reduce_kernel")
+
+
+def piece(name):
+    """The family a dispatch is listed under; the shadow launch by the kind of copy in its template arguments."""
+    k = next(k for k in FAMILY if k in name)
+    if k == "shadow_sweep_kernel":
+        return k + (", q15" if "ShadowQ15" in name else ", float32" if "ShadowF32" in name else "")
+    return k
 
 
 def main(d):
@@ -46,7 +54,7 @@ def main(d):
             if "sweep_list_kernel" in n2:
                 lists.append(e2 - s2)
             else:
-                pieces.setdefault(next(k for k in FAMILY if k in n2), []).append(e2 - s2)
+                pieces.setdefault(piece(n2), []).append(e2 - s2)
             j += 1
         if lists:
             pieces.setdefault("sweep_list_kernel, open list", []).append(lists[-1])

@@ -103,3 +103,37 @@ for name, M, with_cov in [("dense_f64", ad.matrix.dense(Xo_h), True),
                           ("dense_f32", ad.matrix.dense(np.asfortranarray(Xo_h.astype(np.float32))), True),
                           ("snp", X, True), ("csc", Xs, False), ("std_csc", ad.matrix.standardize(Xs), False)]:
     print("ops", name, ops_digest(M, with_cov))
+# the filtered invariance sweep at kernel level, per shadow kind: grad (the shadow's own values in the unlisted columns included),
+# the exact mask and info of adelie_hip_filter_sweep_test, with screen groups and one group without a penalty
+def filter_digest(n, p, gs, intercept, kind):
+    os.environ["ADELIE_HIP_SHADOW_KIND"] = kind
+    os.environ["ADELIE_HIP_FILTER_SWEEP"] = "1"
+    r_ = np.random.RandomState(n + p + gs)
+    Xh = np.asfortranarray(r_.normal(size=(n, p)))
+    w = r_.uniform(0.5, 1.5, size=n); w[::3] = 0.0; w /= w.sum()
+    r = r_.normal(size=n)
+    groups = np.arange(0, p, gs, dtype=np.int64)
+    gsizes = np.minimum(gs, p - groups).astype(np.int64)
+    pen = r_.uniform(0.5, 2.0, size=len(groups)); pen[2] = 0.0
+    xm = (Xh.T @ w) if intercept else None
+    rsum = float((w * r).sum()) if intercept else 0.0
+    g0 = Xh.T @ (w * r) - (rsum * xm if intercept else 0.0)
+    score = np.array([np.sqrt((g0[k:k + s] ** 2).sum()) for k, s in zip(groups, gsizes)]) / np.where(pen > 0, pen, np.inf)
+    screen = np.arange(0, len(groups), 7, dtype=np.int64)
+    M = ad.matrix.dense(Xh)
+    grad, exact, info = np.empty(p), np.zeros(p, dtype=np.uint8), np.zeros(4, dtype=np.int64)
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    b = M._backend
+    b.check(b.fn("filter_sweep_test")(M._handle, ptr(w), ptr(r), rsum, ptr(xm), ptr(screen), len(screen), ptr(groups), ptr(gsizes),
+                                      len(groups), ptr(pen), float(np.quantile(score, 0.9)), ptr(grad), ptr(exact), ptr(info)))
+    assert info[2] == 1 and 0 < exact.sum() < p, (info, exact.sum())   # routed through the filter, shadow values left in grad
+    return hashlib.sha1(grad.tobytes() + exact.tobytes() + info.tobytes()).hexdigest()[:16], int(exact.sum()), info.tolist()
+saved_env = {k: os.environ.get(k) for k in ("ADELIE_HIP_SHADOW_KIND", "ADELIE_HIP_FILTER_SWEEP")}   # (the caller's, put back below)
+for kind in ("f32", "q15"):
+    for n_, p_, gs, icpt in [(5000, 37, 4, False), (1000, 4100, 1, True), (5003, 37, 1, True), (20000, 24, 1, True)]:
+        print("filter", kind, (n_, p_), *filter_digest(n_, p_, gs, icpt, kind))
+for k, val in saved_env.items():
+    if val is None:
+        os.environ.pop(k, None)
+    else:
+        os.environ[k] = val
