@@ -1,5 +1,5 @@
 // cd_fit_body.hpp — the one-workgroup fit() shared by the box-constrained (kernels_bvls.hip) and the pinball
-// (kernels_pinball.hip) coordinate descents, with the host helpers both drivers use (Pinned, PhaseTimer).
+// (kernels_pinball.hip) coordinate descents, and its launch.  The host driver around it: cd_screen_driver.hpp.
 //
 // Both solvers of the reference (solver_bvls.hpp, solver_pinball.hpp) have the same fit(): screen-set passes that add the
 // changed coordinates to the active set, active-set passes until convergence, a prune, the max-iterations exit and the
@@ -270,57 +270,6 @@ void launch_cd_fit(CdFitArgs<T> fa, int lds_limit, int64_t lds_max_ns, DevBuf<ch
         hipLaunchKernelGGL((cd_fit_kernel<T, false, Rule>), dim3(1), dim3(threads), 0, s, fa);
     }
 }
-
-struct Pinned {
-    void* p = nullptr;
-    size_t bytes = 0;
-    explicit Pinned(size_t n) : bytes((n + 4095) / 4096 * 4096) {
-        p = HostPool::take(bytes, hipHostMallocDefault);
-        if (!p) throw core_error("adelie_hip: hipHostMalloc failed");
-    }
-    ~Pinned() { HostPool::give(p, bytes, hipHostMallocDefault); }
-};
-
-// HIP-event time of the three device phases; collected after a stream synchronisation
-struct PhaseTimer {
-    struct Span { hipEvent_t a, b; int cat; };
-    std::vector<Span> open;
-    std::vector<hipEvent_t> idle;
-    double ms[3] = {0, 0, 0};
-    hipEvent_t get() {
-        if (!idle.empty()) {
-            hipEvent_t e = idle.back();
-            idle.pop_back();
-            return e;
-        }
-        hipEvent_t e;
-        AHIP_CHECK(hipEventCreate(&e));
-        return e;
-    }
-    void begin(int cat, hipStream_t s) {
-        Span sp{get(), get(), cat};
-        AHIP_CHECK(hipEventRecord(sp.a, s));
-        open.push_back(sp);
-    }
-    void end(hipStream_t s) { AHIP_CHECK(hipEventRecord(open.back().b, s)); }
-    void collect() { // (the stream is idle)
-        for (const Span& sp : open) {
-            float t = 0;
-            if (hipEventElapsedTime(&t, sp.a, sp.b) == hipSuccess) ms[sp.cat] += double(t);
-            else (void)hipGetLastError();
-            idle.push_back(sp.a);
-            idle.push_back(sp.b);
-        }
-        open.clear();
-    }
-    ~PhaseTimer() {
-        for (const Span& sp : open) idle.push_back(sp.a), idle.push_back(sp.b);
-        for (hipEvent_t e : idle) (void)hipEventDestroy(e);
-    }
-};
-enum { PH_SWEEP = 0, PH_GRAM = 1, PH_FIT = 2 };
-
-inline unsigned cd_blocks_for(int64_t n, int per) { return unsigned((n + per - 1) / per); }
 
 } // namespace
 } // namespace ahip

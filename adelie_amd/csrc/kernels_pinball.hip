@@ -1,5 +1,5 @@
 // kernels_pinball.hip — pinball least squares on a resident constraint matrix (adelie.solver.pinball: solver_pinball.hpp,
-// state_pinball.ipp).  Kernels, the host driver and the C-ABI entry points of adelie_hip_pinball_solve.
+// state_pinball.ipp).  Kernels, the solver's part of the host driver and the C-ABI entry points of adelie_hip_pinball_solve.
 //
 //     minimise over beta in R^m   1/2 || S^{-1/2} v - S^{1/2} A' beta ||^2 + penalty_neg' beta_- + penalty_pos' beta_+
 //
@@ -12,7 +12,8 @@
 // a visit that changes beta_k by `del` does g_a -= H[a, k] * del for all a (one contiguous column of H), and a visit that
 // changes nothing touches no memory but a few broadcast reads.  One workgroup runs a whole fit() without leaving the compute
 // unit: the kernel is the one bvls runs (cd_fit_body.hpp, which also describes its synchronisation) with the pinball update
-// (solver_pinball.hpp:37-61) and prune predicate (beta == 0).  The residual is caught up once per fit from the compact list of
+// (solver_pinball.hpp:37-61) and prune predicate (beta == 0), and so is the host driver around it (cd_screen_driver.hpp: the
+// screen-order buffers, H's growth, fit, the warm start and the KKT loop).  The residual is caught up once per fit from the compact list of
 // changes (launch_axpy_cols on the compact rows A_S S, kept as a (d, capacity) column-major array in screen order), and the
 // H-updated gradients are thrown away at every KKT round: the members' g is re-read from the fresh full gradient.
 //
@@ -30,15 +31,9 @@
 //
 // An infinite penalty (max_solver_value is inf in float32) needs no special case: the update gives copysign(0, +-inf) = 0 on
 // that side and the violation -inf, which sorts last.
-#include <cmath>
-#include <limits>
-#include <numeric>
-
-#include "common.hpp"
-#include "cd_fit_body.hpp"
+#include "cd_screen_driver.hpp"
 
 namespace ahip {
-void set_last_error(const std::string& s); // design.hip
 
 double g_pinball_gram_limit_mb = 16384.0; // adelie_hip_set_config("pinball_gram_limit_mb", x)
 int64_t g_pinball_lds_max_ns = 0;         // adelie_hip_set_config("pinball_lds_max_ns", x): 0 = automatic
@@ -149,108 +144,82 @@ template void launch_ptq<double>(const double*, int64_t, const int32_t*, int32_t
 
 using namespace ahip;
 
-struct adelie_hip_pinball_result {
-    int dtype = ADELIE_HIP_F64, device = 0;
-    int64_t m = 0, d = 0;
-    std::vector<char> beta, resid, grad, asat_diag; // of dtype
-    std::vector<int64_t> screen_set, active_set;
-    std::vector<uint8_t> is_screen, is_active;
+struct adelie_hip_pinball_result : CdScreenResult { // n = d, p = m
+    std::vector<char> asat_diag; // of dtype
     // the compact rows A_S S, (d, ns) column-major = (ns, d) row-major, left on the device until somebody asks
     void* as_dev = nullptr;
     size_t as_bytes = 0;
-    double loss = 0;
-    int64_t iters = 0, n_kkt = 0, n_changed = 0;
-    double total_time = 0, t_sweep_ms = 0, t_gram_ms = 0, t_fit_ms = 0;
-    std::string error;
-    ~adelie_hip_pinball_result() {
+    ~adelie_hip_pinball_result() override {
         if (as_dev && !DevPool::give(as_dev, as_bytes)) (void)hipFree(as_dev);
+    }
+    int64_t extra_size(int which) const override {
+        if (which == ADELIE_HIP_PINBALL_SCREEN_ASAT_DIAG) return int64_t(screen_set.size());
+        if (which == ADELIE_HIP_PINBALL_SCREEN_AS) return as_dev ? int64_t(screen_set.size()) * n : 0;
+        return -1;
+    }
+    void extra_copy(int which, void* out, size_t m, size_t es) const override {
+        if (which == ADELIE_HIP_PINBALL_SCREEN_ASAT_DIAG) {
+            std::memcpy(out, asat_diag.data(), m * es);
+        } else {
+            AHIP_CHECK(hipSetDevice(device));
+            AHIP_CHECK(hipMemcpy(out, as_dev, m * es, hipMemcpyDeviceToHost));
+        }
     }
 };
 
+static_assert(ADELIE_HIP_PINBALL_BETA == CDS_BETA && ADELIE_HIP_PINBALL_RESID == CDS_RESID && ADELIE_HIP_PINBALL_GRAD == CDS_GRAD &&
+                  ADELIE_HIP_PINBALL_SCREEN_SET == CDS_SCREEN_SET && ADELIE_HIP_PINBALL_ACTIVE_SET == CDS_ACTIVE_SET &&
+                  ADELIE_HIP_PINBALL_IS_SCREEN == CDS_IS_SCREEN && ADELIE_HIP_PINBALL_IS_ACTIVE == CDS_IS_ACTIVE &&
+                  ADELIE_HIP_PINBALL_SCREEN_ASAT_DIAG > CDS_IS_ACTIVE && ADELIE_HIP_PINBALL_SCREEN_AS > CDS_IS_ACTIVE,
+              "the shared result vectors");
+static_assert(ADELIE_HIP_PINBALL_LOSS == CDS_LOSS && ADELIE_HIP_PINBALL_ITERS == CDS_ITERS && ADELIE_HIP_PINBALL_N_KKT == CDS_N_KKT &&
+                  ADELIE_HIP_PINBALL_SCREEN_SET_SIZE == CDS_SCREEN_SET_SIZE &&
+                  ADELIE_HIP_PINBALL_ACTIVE_SET_SIZE == CDS_ACTIVE_SET_SIZE && ADELIE_HIP_PINBALL_TOTAL_TIME == CDS_TOTAL_TIME &&
+                  ADELIE_HIP_PINBALL_T_SWEEP_MS == CDS_T_SWEEP_MS && ADELIE_HIP_PINBALL_T_GRAM_MS == CDS_T_GRAM_MS &&
+                  ADELIE_HIP_PINBALL_T_FIT_MS == CDS_T_FIT_MS && ADELIE_HIP_PINBALL_N_CHANGED == CDS_N_CHANGED,
+              "the shared result scalars");
+
 namespace {
 
+// what the shared driver (cd_screen_driver.hpp) does not know.  A is (m, d) and the handle the (d, m) column-major A', so the
+// driver's n is d and its p is m; its G is H.
 template <class T>
-struct PinballSolver {
-    adelie_hip_design* X;
-    adelie_hip_pinball_result* res;
-    const adelie_hip_pinball_args* a;
-    int64_t d, m; // A is (m, d); the handle is the (d, m) column-major A'
-    hipStream_t s;
-    DenseView<T> Av;
-    DeferredFrees deferred;
-    PhaseTimer timer;
+struct PinballSolver : CdScreenDriver<T, PinballSolver<T>, adelie_hip_pinball_args> {
+    using Base = CdScreenDriver<T, PinballSolver<T>, adelie_hip_pinball_args>;
+    using Base::a, Base::s, Base::Xv, Base::timer, Base::ns, Base::ld;
+    using Base::d_r, Base::d_grad, Base::d_viols, Base::d_beta, Base::d_cols, Base::d_dcol, Base::d_dlt, Base::d_cnt, Base::d_g;
+    using Base::d_lower_s, Base::d_upper_s, Base::d_vars_s, Base::d_beta_s, Base::d_G, Base::d_work_sweep;
+    using Rule = PinballRule<T>;
+    static constexpr const char* kName = "pinball";
+    static double gram_limit_mb() { return g_pinball_gram_limit_mb; }
+    static int64_t lds_max_ns() { return g_pinball_lds_max_ns; }
 
-    // full vectors
-    DevBuf<T> d_S, d_r, d_grad, d_viols, d_beta, d_pneg, d_ppos;
-    // screen order
-    DevBuf<int32_t> d_cols, d_act, d_dcol, d_cnt;
-    DevBuf<T> d_g, d_lower_s, d_upper_s, d_vars_s, d_beta_s, d_dlt, d_sweep_out;
-    DevBuf<T> d_AS, d_H, d_work_sweep;
-    DevBuf<char> d_scratch;
-    DevBuf<CdFitRec> d_rec;
-    int64_t ld = 0;
-    size_t cap_s = 0; // capacity of the screen-order buffers (members)
+    adelie_hip_pinball_result* pres;
+    const int64_t d, m;
+    DevBuf<T> d_S, d_pneg, d_ppos, d_AS;
 
-    std::vector<int64_t> screen_set;
-    std::vector<uint8_t> is_screen;
-    std::vector<int32_t> h_cols;
-    std::vector<T> h_viols;
-    bool have_viols = false;
-    int64_t ns = 0;
-    int lds_limit = 0;
-    bool attr_done = false;
+    PinballSolver(adelie_hip_design* A, const adelie_hip_pinball_args* a_, adelie_hip_pinball_result* r)
+        : Base(A, a_, r), pres(r), d(A->n), m(A->p) {}
 
-    T loss;
-    int64_t iters = 0, n_kkt = 0, nact = 0;
-
-    PinballSolver(adelie_hip_design* X_, const adelie_hip_pinball_args* a_, adelie_hip_pinball_result* r) : X(X_), res(r), a(a_) {
-        d = X->n;
-        m = X->p;
-        s = X->stream;
-        Av = X->dense<T>();
-        loss = T(a->loss);
+    void upload() {
+        d_S.reserve(size_t(d) * size_t(d)), d_pneg.reserve(size_t(m)), d_ppos.reserve(size_t(m));
+        d_S.upload(static_cast<const T*>(a->S), size_t(d) * size_t(d), s);
+        d_r.upload(static_cast<const T*>(a->resid), size_t(d), s);
+        d_beta.upload(static_cast<const T*>(a->beta), size_t(m), s);
+        d_pneg.upload(static_cast<const T*>(a->penalty_neg), size_t(m), s);
+        d_ppos.upload(static_cast<const T*>(a->penalty_pos), size_t(m), s);
     }
-
-    // grow the screen-order buffers to hold `want` members, keeping the first `keep`
-    void reserve_screen(int64_t want, int64_t keep) {
-        if (size_t(want) <= cap_s) return;
-        size_t c = std::max<size_t>(size_t(want), cap_s + cap_s / 2);
-        c = std::min<size_t>(std::max<size_t>(c, 64), size_t(m));
-        c = std::max<size_t>(c, size_t(want));
-        d_cols.grow(c, size_t(keep), s);
-        d_act.grow(c, size_t(keep), s);
-        d_lower_s.grow(c, size_t(keep), s);
-        d_upper_s.grow(c, size_t(keep), s);
-        d_vars_s.grow(c, size_t(keep), s);
-        d_beta_s.grow(c, size_t(keep), s);
-        d_AS.grow(c * size_t(d), size_t(keep) * size_t(d), s);
-        d_g.reserve(c), d_dcol.reserve(c), d_dlt.reserve(c), d_sweep_out.reserve(c);
-        cap_s = c;
-    }
-    // H for ns_new members: false when it would pass the limit
-    bool reserve_gram(int64_t ns_new, int64_t ns_old) {
-        if (double(ns_new) * double(ns_new) * double(sizeof(T)) > g_pinball_gram_limit_mb * 1048576.0) return false;
-        if (ns_new <= ld) return true;
-        int64_t nl = std::max<int64_t>(std::max<int64_t>(ns_new, ld + ld / 2), 64);
-        nl = std::min<int64_t>(nl, std::max<int64_t>(m, ns_new));
-        if (double(nl) * double(nl) * double(sizeof(T)) > g_pinball_gram_limit_mb * 1048576.0) nl = ns_new;
-        DevBuf<T> ng;
-        ng.reserve(size_t(nl) * size_t(nl));
-        if (ns_old > 0)
-            AHIP_CHECK(hipMemcpy2DAsync(ng.p, size_t(nl) * sizeof(T), d_H.p, size_t(ld) * sizeof(T), size_t(ns_old) * sizeof(T),
-                                        size_t(ns_old), hipMemcpyDeviceToDevice, s));
-        std::swap(ng.p, d_H.p);
-        std::swap(ng.cap, d_H.cap);
-        ng.release(); // (kept until the end of the solve: DeferredFrees)
-        ld = nl;
-        return true;
-    }
+    void grow_extra(size_t c, size_t keep) { d_AS.grow(c * size_t(d), keep * size_t(d), s); }
     // out[c] = A[col(c), :] . resid
     void sweep(const int32_t* cols, int64_t ncols, T* out) {
         timer.begin(PH_SWEEP, s);
         T* work = d_work_sweep.reserve(size_t(sweep_work_elems(d, ncols)));
-        launch_sweep<T>(Av, d_r.p, out, 0, ncols, cols, nullptr, nullptr, false, work, s);
+        launch_sweep<T>(Xv, d_r.p, out, 0, ncols, cols, nullptr, nullptr, false, work, s);
         timer.end(s);
+    }
+    void viols() {
+        hipLaunchKernelGGL((pinball_viols_kernel<T>), dim3(cd_blocks_for(m, 256)), dim3(256), 0, s, d_grad.p, d_pneg.p, d_ppos.p, m,
+                           d_viols.p);
     }
     // the rows [ns_old, ns_new) of AS, then the columns [ns_old, ns_new) of H for all members and its rows [ns_old, ns_new)
     // for the old ones
@@ -258,211 +227,42 @@ struct PinballSolver {
         const int64_t N = ns_new - ns_old;
         if (N <= 0) return;
         timer.begin(PH_GRAM, s);
-        launch_ptq<T>(d_S.p, d, nullptr, int32_t(d), Av.X, Av.ld, d_cols.p + ns_old, int32_t(N), d, d_AS.p + ns_old * d, d, s);
-        launch_ptq<T>(Av.X, Av.ld, d_cols.p, int32_t(ns_new), d_AS.p + ns_old * d, d, nullptr, int32_t(N), d, d_H.p + ns_old * ld,
+        launch_ptq<T>(d_S.p, d, nullptr, int32_t(d), Xv.X, Xv.ld, d_cols.p + ns_old, int32_t(N), d, d_AS.p + ns_old * d, d, s);
+        launch_ptq<T>(Xv.X, Xv.ld, d_cols.p, int32_t(ns_new), d_AS.p + ns_old * d, d, nullptr, int32_t(N), d, d_G.p + ns_old * ld,
                       ld, s);
         if (ns_old > 0)
-            launch_ptq<T>(Av.X, Av.ld, d_cols.p + ns_old, int32_t(N), d_AS.p, d, nullptr, int32_t(ns_old), d, d_H.p + ns_old, ld, s);
+            launch_ptq<T>(Xv.X, Xv.ld, d_cols.p + ns_old, int32_t(N), d_AS.p, d, nullptr, int32_t(ns_old), d, d_G.p + ns_old, ld, s);
         timer.end(s);
     }
     void gather(int64_t a0, const T* src, bool by_col) {
         hipLaunchKernelGGL((pinball_gather_kernel<T>), dim3(cd_blocks_for(ns, 256)), dim3(256), 0, s, d_cols.p, int32_t(ns),
-                           int32_t(a0), src, by_col ? 1 : 0, d_pneg.p, d_ppos.p, d_H.p, ld, d_beta.p, d_g.p, d_lower_s.p,
+                           int32_t(a0), src, by_col ? 1 : 0, d_pneg.p, d_ppos.p, d_G.p, ld, d_beta.p, d_g.p, d_lower_s.p,
                            d_upper_s.p, d_vars_s.p, d_beta_s.p);
     }
+    const int32_t* dcol_src() { return nullptr; } // the compact list names a member by its position: a column of the compact AS
+    // resid -= sum_k del_k AS[k, :]
+    void catch_up() { launch_axpy_cols<T>(DenseView<T>{d_AS.p, d, ns, d}, d_dcol.p, d_dlt.p, d_cnt.p, 0, T(-1), d_r.p, s); }
 
-    void fit(CdFitRec* h_rec) {
-        CdFitArgs<T> fa;
-        fa.G = d_H.p, fa.ld = ld, fa.ns = int32_t(ns), fa.cols = d_cols.p;
-        fa.dcol_src = nullptr; // the compact list names a member by its position: a column of the compact AS
-        fa.lower_s = d_lower_s.p, fa.upper_s = d_upper_s.p, fa.vars_s = d_vars_s.p, fa.g_s = d_g.p, fa.beta_s = d_beta_s.p;
-        fa.act = d_act.p, fa.beta_full = d_beta.p, fa.dcol = d_dcol.p, fa.dlt = d_dlt.p, fa.cnt_dev = d_cnt.p, fa.rec = d_rec.p;
-        fa.scratch = nullptr;
-        fa.max_iters = a->max_iters;
-        fa.tol_yvar = T(a->tol) * T(a->y_var);
-        h_rec->loss = double(loss), h_rec->iters = iters, h_rec->n_visits_changed = 0, h_rec->status = 0;
-        h_rec->n_active = int32_t(nact), h_rec->n_changed = 0, h_rec->pad = 0;
-        AHIP_CHECK(hipMemcpyAsync(d_rec.p, h_rec, sizeof(CdFitRec), hipMemcpyHostToDevice, s));
-        timer.begin(PH_FIT, s);
-        launch_cd_fit<T, PinballRule<T>>(fa, lds_limit, g_pinball_lds_max_ns, d_scratch, attr_done, s);
-        timer.end(s);
-        // resid -= sum_k del_k AS[k, :]
-        launch_axpy_cols<T>(DenseView<T>{d_AS.p, d, ns, d}, d_dcol.p, d_dlt.p, d_cnt.p, 0, T(-1), d_r.p, s);
-        AHIP_CHECK(hipMemcpyAsync(h_rec, d_rec.p, sizeof(CdFitRec), hipMemcpyDeviceToHost, s));
-        AHIP_CHECK(hipStreamSynchronize(s));
-        AHIP_CHECK(hipGetLastError());
-        timer.collect();
-        loss = T(h_rec->loss);
-        iters = h_rec->iters;
-        nact = h_rec->n_active;
-        res->n_changed += h_rec->n_visits_changed;
+    void finish_downloads(size_t es) {
+        pres->asat_diag.resize(size_t(ns) * es);
+        if (ns) AHIP_CHECK(hipMemcpyAsync(pres->asat_diag.data(), d_vars_s.p, size_t(ns) * es, hipMemcpyDeviceToHost, s));
     }
-
-    void finish() {
-        AHIP_CHECK(hipStreamSynchronize(s));
-        timer.collect();
-        const size_t es = sizeof(T);
-        res->beta.resize(size_t(m) * es), res->resid.resize(size_t(d) * es), res->grad.resize(size_t(m) * es);
-        res->asat_diag.resize(size_t(ns) * es);
-        AHIP_CHECK(hipMemcpyAsync(res->beta.data(), d_beta.p, size_t(m) * es, hipMemcpyDeviceToHost, s));
-        AHIP_CHECK(hipMemcpyAsync(res->resid.data(), d_r.p, size_t(d) * es, hipMemcpyDeviceToHost, s));
-        if (ns) AHIP_CHECK(hipMemcpyAsync(res->asat_diag.data(), d_vars_s.p, size_t(ns) * es, hipMemcpyDeviceToHost, s));
-        std::vector<int32_t> hact(static_cast<size_t>(nact));
-        if (nact) AHIP_CHECK(hipMemcpyAsync(hact.data(), d_act.p, size_t(nact) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        AHIP_CHECK(hipStreamSynchronize(s));
-        AHIP_CHECK(hipGetLastError());
-        if (have_viols) std::memcpy(res->grad.data(), h_viols.data(), size_t(m) * es);
-        else std::memcpy(res->grad.data(), a->grad, size_t(m) * es);
-        res->screen_set = screen_set;
-        res->is_screen = is_screen;
-        res->active_set.resize(size_t(nact));
-        res->is_active.assign(size_t(m), 0);
-        for (int64_t i = 0; i < nact; ++i) {
-            const int64_t j = screen_set[size_t(hact[size_t(i)])];
-            res->active_set[size_t(i)] = j;
-            res->is_active[size_t(j)] = 1;
-        }
+    void finish_extras() {
         if (ns > 0 && d_AS.p) { // the result takes the compact AS over
-            res->as_dev = d_AS.p;
-            res->as_bytes = d_AS.cap * sizeof(T);
+            pres->as_dev = d_AS.p;
+            pres->as_bytes = d_AS.cap * sizeof(T);
             d_AS.p = nullptr;
             d_AS.cap = 0;
         }
-        res->loss = double(loss);
-        res->iters = iters;
-        res->n_kkt = n_kkt;
-        res->t_sweep_ms = timer.ms[PH_SWEEP], res->t_gram_ms = timer.ms[PH_GRAM], res->t_fit_ms = timer.ms[PH_FIT];
-    }
-
-    void run() {
-        DeferredFrees::Scope scope(&deferred);
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, X->device) != hipSuccess || v <= 0) {
-            (void)hipGetLastError();
-            v = 65536;
-        }
-        lds_limit = v;
-        d_S.reserve(size_t(d) * size_t(d)), d_r.reserve(size_t(d));
-        d_grad.reserve(size_t(m)), d_viols.reserve(size_t(m)), d_beta.reserve(size_t(m));
-        d_pneg.reserve(size_t(m)), d_ppos.reserve(size_t(m));
-        d_cnt.reserve(4), d_rec.reserve(1);
-        d_S.upload(static_cast<const T*>(a->S), size_t(d) * size_t(d), s);
-        d_r.upload(static_cast<const T*>(a->resid), size_t(d), s);
-        d_beta.upload(static_cast<const T*>(a->beta), size_t(m), s);
-        d_pneg.upload(static_cast<const T*>(a->penalty_neg), size_t(m), s);
-        d_ppos.upload(static_cast<const T*>(a->penalty_pos), size_t(m), s);
-        h_viols.resize(size_t(m));
-        is_screen.assign(size_t(m), 0);
-        Pinned pin(sizeof(CdFitRec));
-        CdFitRec* h_rec = static_cast<CdFitRec*>(pin.p);
-
-        // the caller's screen and active sets (a warm start)
-        std::vector<int64_t> pos_of;
-        if (a->screen_set_size > 0) pos_of.assign(size_t(m), -1);
-        for (int64_t i = 0; i < a->screen_set_size; ++i) {
-            const int64_t j = a->screen_set[i];
-            screen_set.push_back(j);
-            is_screen[size_t(j)] = 1;
-            pos_of[size_t(j)] = i;
-        }
-        ns = int64_t(screen_set.size());
-        nact = a->active_set_size;
-        if (ns > 0) {
-            reserve_screen(ns, 0);
-            h_cols.assign(screen_set.begin(), screen_set.end());
-            d_cols.upload(h_cols.data(), size_t(ns), s);
-            std::vector<int32_t> hact(static_cast<size_t>(nact));
-            for (int64_t i = 0; i < nact; ++i) hact[size_t(i)] = int32_t(pos_of[size_t(a->active_set[i])]);
-            if (nact) d_act.upload(hact.data(), size_t(nact), s);
-            AHIP_CHECK(hipStreamSynchronize(s)); // (hact / h_cols are read by the copies)
-            if (!reserve_gram(ns, 0)) return gram_limit_error(ns);
-            extend(0, ns);
-            sweep(d_cols.p, ns, d_sweep_out.p);
-            gather(0, d_sweep_out.p, false);
-            AHIP_CHECK(hipStreamSynchronize(s));
-        }
-
-        while (true) { // solve(): solver_pinball.hpp:293-308
-            const T loss_prev = loss;
-            if (ns > 0) {
-                fit(h_rec);
-                if (h_rec->status == CD_FIT_MAX_ITERS) {
-                    res->error = "adelie_core solver: pinball: max iterations reached!";
-                    return finish();
-                }
-            } else { // an empty screen pass
-                ++iters;
-                if (iters >= a->max_iters) {
-                    res->error = "adelie_core solver: pinball: max iterations reached!";
-                    return finish();
-                }
-            }
-            if (n_kkt > 0 && double(std::abs(loss - loss_prev)) < 1e-6 * double(std::abs(T(a->y_var)))) return finish();
-            // kkt_screen(): :200-276
-            ++n_kkt;
-            sweep(nullptr, m, d_grad.p);
-            hipLaunchKernelGGL((pinball_viols_kernel<T>), dim3(cd_blocks_for(m, 256)), dim3(256), 0, s, d_grad.p, d_pneg.p, d_ppos.p,
-                               m, d_viols.p);
-            AHIP_CHECK(hipMemcpyAsync(h_viols.data(), d_viols.p, size_t(m) * sizeof(T), hipMemcpyDeviceToHost, s));
-            AHIP_CHECK(hipStreamSynchronize(s));
-            AHIP_CHECK(hipGetLastError());
-            timer.collect();
-            have_viols = true;
-            std::vector<int64_t> order(static_cast<size_t>(m));
-            std::iota(order.begin(), order.end(), int64_t(0));
-            std::stable_sort(order.begin(), order.end(),
-                             [&](int64_t i, int64_t j) { return h_viols[size_t(i)] > h_viols[size_t(j)]; });
-            std::vector<int64_t> added;
-            bool kkt_passed = true;
-            for (int64_t t = 0; t < m; ++t) {
-                const int64_t k = order[size_t(t)];
-                if (is_screen[size_t(k)] || h_viols[size_t(k)] <= T(0)) continue;
-                kkt_passed = false;
-                if (int64_t(added.size()) >= a->kappa) break;
-                added.push_back(k);
-            }
-            if (kkt_passed) return finish();
-            const int64_t ns_old = ns, ns_new = ns + int64_t(added.size());
-            if (!reserve_gram(ns_new, ns_old)) return gram_limit_error(ns_new);
-            reserve_screen(ns_new, ns_old);
-            for (int64_t k : added) {
-                screen_set.push_back(k);
-                is_screen[size_t(k)] = 1;
-            }
-            h_cols.assign(added.begin(), added.end());
-            d_cols.upload(h_cols.data(), h_cols.size(), s, size_t(ns_old));
-            ns = ns_new;
-            extend(ns_old, ns_new);
-            gather(ns_old, d_grad.p, true);
-            AHIP_CHECK(hipStreamSynchronize(s)); // (h_cols is read by the copy)
-        }
-    }
-    void gram_limit_error(int64_t ns_want) {
-        res->error = "adelie_core solver: pinball: screen set of " + std::to_string(ns_want) +
-                     " coordinates exceeds the device Gram limit";
-        finish();
     }
 };
-
-template <class T>
-void pinball_run(adelie_hip_design* X, const adelie_hip_pinball_args* a, adelie_hip_pinball_result* res) {
-    PinballSolver<T> sv(X, a, res);
-    try {
-        sv.run();
-    } catch (...) {
-        (void)hipStreamSynchronize(X->stream); // the buffers are parked by the destructors
-        throw;
-    }
-}
 
 } // namespace
 
 extern "C" {
 
 int adelie_hip_pinball_solve(adelie_hip_design* A, const adelie_hip_pinball_args* a, adelie_hip_pinball_result** out) {
-    adelie_hip_pinball_result* res = nullptr;
-    try {
-        if (!A || !a || !out) throw make_core_error("null argument.");
+    return cd_screen_solve<PinballSolver>(A, a, out, [&] {
         if (!A->constraint || !A->is_dense())
             throw make_core_error("A must be a constraint matrix (matrix.dense(method=\"constraint\")).");
         const int64_t d = A->n, m = A->p;
@@ -489,38 +289,11 @@ int adelie_hip_pinball_solve(adelie_hip_design* A, const adelie_hip_pinball_args
         if (a->screen_set_size < 0 || a->active_set_size < 0 || (a->screen_set_size && !a->screen_set) ||
             (a->active_set_size && !a->active_set))
             throw make_core_error("pinball: screen_set_size must be in [0, m].");
-        {   // distinct members in range; the active set inside the screen set (what the solver itself maintains)
-            std::vector<uint8_t> seen(size_t(m), 0);
-            for (int64_t i = 0; i < a->screen_set_size; ++i) {
-                const int64_t j = a->screen_set[i];
-                if (j < 0 || j >= m || seen[size_t(j)])
-                    throw make_core_error("pinball: screen_set must hold distinct indices in [0, m).");
-                seen[size_t(j)] = 1;
-            }
-            for (int64_t i = 0; i < a->active_set_size; ++i) {
-                const int64_t j = a->active_set[i];
-                if (j < 0 || j >= m || seen[size_t(j)] != 1)
-                    throw make_core_error("pinball: active_set must hold distinct members of screen_set.");
-                seen[size_t(j)] = 2;
-            }
-        }
-        AHIP_CHECK(hipSetDevice(A->device));
-        res = new adelie_hip_pinball_result;
-        res->dtype = A->dtype;
-        res->device = A->device;
-        res->m = m;
-        res->d = d;
-        const auto t0 = std::chrono::steady_clock::now();
-        if (A->dtype == ADELIE_HIP_F64) pinball_run<double>(A, a, res);
-        else pinball_run<float>(A, a, res);
-        res->total_time = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        *out = res;
-    } catch (const std::exception& e) {
-        delete res;
-        set_last_error(e.what());
-        return 1;
-    }
-    return 0;
+        if (const char* e = cd_screen_warm_start_error(a->screen_set, a->screen_set_size, a->active_set, a->active_set_size, m,
+                                                       "pinball: screen_set must hold distinct indices in [0, m).",
+                                                       "pinball: active_set must hold distinct members of screen_set."))
+            throw make_core_error(e);
+    });
 }
 
 int adelie_hip_pinball_result_destroy(adelie_hip_pinball_result* r) {
@@ -529,67 +302,12 @@ int adelie_hip_pinball_result_destroy(adelie_hip_pinball_result* r) {
     return 0;
 }
 
-int64_t adelie_hip_pinball_result_size(const adelie_hip_pinball_result* r, int which) {
-    if (!r) return -1;
-    switch (which) {
-        case ADELIE_HIP_PINBALL_BETA:
-        case ADELIE_HIP_PINBALL_GRAD:
-        case ADELIE_HIP_PINBALL_IS_SCREEN:
-        case ADELIE_HIP_PINBALL_IS_ACTIVE: return r->m;
-        case ADELIE_HIP_PINBALL_RESID: return r->d;
-        case ADELIE_HIP_PINBALL_SCREEN_SET:
-        case ADELIE_HIP_PINBALL_SCREEN_ASAT_DIAG: return int64_t(r->screen_set.size());
-        case ADELIE_HIP_PINBALL_ACTIVE_SET: return int64_t(r->active_set.size());
-        case ADELIE_HIP_PINBALL_SCREEN_AS: return r->as_dev ? int64_t(r->screen_set.size()) * r->d : 0;
-    }
-    return -1;
-}
-
+int64_t adelie_hip_pinball_result_size(const adelie_hip_pinball_result* r, int which) { return cd_result_size(r, which); }
 int adelie_hip_pinball_result_copy(const adelie_hip_pinball_result* r, int which, void* out, int64_t cap) {
-    try {
-        const int64_t size = adelie_hip_pinball_result_size(r, which);
-        if (size < 0 || !out) throw make_core_error("unknown result vector.");
-        const size_t n = size_t(std::min(size, cap));
-        const size_t es = r->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
-        if (!n) return 0;
-        switch (which) {
-            case ADELIE_HIP_PINBALL_BETA: std::memcpy(out, r->beta.data(), n * es); break;
-            case ADELIE_HIP_PINBALL_RESID: std::memcpy(out, r->resid.data(), n * es); break;
-            case ADELIE_HIP_PINBALL_GRAD: std::memcpy(out, r->grad.data(), n * es); break;
-            case ADELIE_HIP_PINBALL_SCREEN_ASAT_DIAG: std::memcpy(out, r->asat_diag.data(), n * es); break;
-            case ADELIE_HIP_PINBALL_SCREEN_SET: std::memcpy(out, r->screen_set.data(), n * sizeof(int64_t)); break;
-            case ADELIE_HIP_PINBALL_ACTIVE_SET: std::memcpy(out, r->active_set.data(), n * sizeof(int64_t)); break;
-            case ADELIE_HIP_PINBALL_IS_SCREEN: std::memcpy(out, r->is_screen.data(), n); break;
-            case ADELIE_HIP_PINBALL_IS_ACTIVE: std::memcpy(out, r->is_active.data(), n); break;
-            case ADELIE_HIP_PINBALL_SCREEN_AS:
-                AHIP_CHECK(hipSetDevice(r->device));
-                AHIP_CHECK(hipMemcpy(out, r->as_dev, n * es, hipMemcpyDeviceToHost));
-                break;
-        }
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return 1;
-    }
-    return 0;
+    return cd_result_copy(r, which, out, cap);
 }
-
-double adelie_hip_pinball_result_scalar(const adelie_hip_pinball_result* r, int which) {
-    if (!r) return 0;
-    switch (which) {
-        case ADELIE_HIP_PINBALL_LOSS: return r->loss;
-        case ADELIE_HIP_PINBALL_ITERS: return double(r->iters);
-        case ADELIE_HIP_PINBALL_N_KKT: return double(r->n_kkt);
-        case ADELIE_HIP_PINBALL_SCREEN_SET_SIZE: return double(r->screen_set.size());
-        case ADELIE_HIP_PINBALL_ACTIVE_SET_SIZE: return double(r->active_set.size());
-        case ADELIE_HIP_PINBALL_TOTAL_TIME: return r->total_time;
-        case ADELIE_HIP_PINBALL_T_SWEEP_MS: return r->t_sweep_ms;
-        case ADELIE_HIP_PINBALL_T_GRAM_MS: return r->t_gram_ms;
-        case ADELIE_HIP_PINBALL_T_FIT_MS: return r->t_fit_ms;
-        case ADELIE_HIP_PINBALL_N_CHANGED: return double(r->n_changed);
-    }
-    return 0;
-}
-
+double adelie_hip_pinball_result_scalar(const adelie_hip_pinball_result* r, int which) { return cd_result_scalar(r, which); }
 const char* adelie_hip_pinball_result_error(const adelie_hip_pinball_result* r) { return r ? r->error.c_str() : ""; }
 
 } // extern "C"
+

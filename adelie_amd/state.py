@@ -1326,13 +1326,187 @@ class css_cov:
         return self._S_resid
 
 
+class _ScreenSetError(RuntimeError):
+    pass
+
+
+class _ScreenSetState:
+    """What ``bvls`` and ``pinball`` share: a coordinate descent over a screen set that KKT rounds grow by ``kappa`` (the
+    native side of it: ``cd_screen_driver.hpp``).  A subclass has ``_name`` (in messages, and the prefix of its native entry
+    points), ``_coords()``, ``_native()``, ``_spawn()``, ``_solve_native()`` and, for the route through the matrix interface,
+    ``_update`` / ``_step_resid`` / ``_drop`` / ``_violations`` / ``_admitted``."""
+
+    _errstate = {}               # np.errstate of the generic route's loop
+    _generic_benchmark = False   # whether the generic route publishes ``benchmark`` (n_changed only)
+
+    def _fill_sets(self, screen, active):
+        p = self._coords()
+        for name, members in (("screen", screen), ("active", active)):
+            buf = np.array(getattr(self, name + "_set"), copy=True, dtype=np.int64)
+            if buf.size < len(members):
+                buf = np.resize(buf, p)
+            buf[:len(members)] = members
+            flags = np.zeros(p, dtype=bool)
+            flags[np.asarray(members, dtype=np.int64)] = True
+            setattr(self, name + "_set", buf)
+            setattr(self, name + "_set_size", len(members))
+            setattr(self, "is_" + name, flags)
+
+    def solve(self):
+        """Solves on the device (or, for designs the native route does not take, through the matrix interface) and returns
+        the solved state.  Failures inside the solve are logged and stored in ``error``, as ``state.base.solve`` does."""
+        import time
+
+        out = self._spawn()
+        if self._native():
+            out._solve_native()
+        else:
+            t0 = time.perf_counter()
+            try:
+                out._solve_generic()
+            except _ScreenSetError as e:
+                out.error = str(e)
+            out.total_time = time.perf_counter() - t0
+        if out.error != "":
+            if out.error.startswith("adelie_core solver: "):
+                logger.error(RuntimeError(out.error))
+            else:
+                logger.warning(RuntimeError(out.error))
+        return out
+
+    def _read_result(self, b, handle, prefix, V, S):
+        """The vectors and scalars every native result of this family has."""
+        dtype = self._dtype
+
+        def vec(name, dt):
+            m = b.fn(prefix + "_result_size")(handle, V[name])
+            o = np.empty(max(m, 0), dtype=dt)
+            if m > 0:
+                b.check(b.fn(prefix + "_result_copy")(handle, V[name], o.ctypes.data, m))
+            return o
+
+        scalar = b.fn(prefix + "_result_scalar")
+        self.beta, self.resid, self.grad = vec("beta", dtype), vec("resid", dtype), vec("grad", dtype)
+        self._fill_sets(vec("screen_set", np.int64), vec("active_set", np.int64))
+        assert np.array_equal(self.is_screen, vec("is_screen", np.uint8).astype(bool))
+        assert np.array_equal(self.is_active, vec("is_active", np.uint8).astype(bool))
+        self.loss = float(scalar(handle, S["loss"]))
+        self.iters = int(scalar(handle, S["iters"]))
+        self.n_kkt = int(scalar(handle, S["n_kkt"]))
+        self.total_time = float(scalar(handle, S["total_time"]))
+        # device-phase times of the solve (scripts/bench_bvls.py, scripts/bench_pinball.py)
+        self.benchmark = {k: float(scalar(handle, S[k])) for k in ("t_sweep_ms", "t_gram_ms", "t_fit_ms", "n_changed")}
+        msg = b.fn(prefix + "_result_error")(handle)
+        self.error = msg.decode() if msg else ""
+
+    def _solve_generic(self):
+        """The reference's ``solve()`` (solver_bvls.hpp:22-348, solver_pinball.hpp:11-309) over the matrix's own operations,
+        arithmetic in its dtype."""
+        dt = self._dtype.type
+        beta = self.beta
+        screen = [int(k) for k in self.screen_set[:self.screen_set_size]]
+        active = [int(k) for k in self.active_set[:self.active_set_size]]
+        is_screen = np.array(self.is_screen, copy=True)
+        is_active = np.array(self.is_active, copy=True)
+        y_var, tol = dt(self.y_var), dt(self.tol)
+        loss = dt(self.loss)
+        half = dt(0.5)
+        n_changed = 0
+        max_iters = f"adelie_core solver: {self._name}: max iterations reached!"
+
+        def publish():
+            self.loss = float(loss)
+            self._fill_sets(screen, active)
+            if self._generic_benchmark:
+                self.benchmark = dict(n_changed=float(n_changed))
+
+        def descend(members, add):
+            nonlocal loss, n_changed
+            convg = dt(0)
+            for k in members:
+                bk = beta[k]
+                visit = self._update(k, bk)
+                if visit is None:
+                    continue
+                vk, gk, bn = visit
+                if bn == bk:
+                    continue
+                beta[k] = bn
+                d = bn - bk
+                sds = vk * d * d
+                convg = max(convg, sds)
+                loss = loss - (d * gk - half * sds)
+                self._step_resid(k, d)
+                n_changed += 1
+                if add and not is_active[k]:
+                    active.append(k)
+                    is_active[k] = True
+            return convg
+
+        def prune():
+            keep = [k for k in active if not self._drop(k)]
+            for k in active:
+                is_active[k] = False
+            for k in keep:
+                is_active[k] = True
+            active[:] = keep
+
+        def step_iters():
+            self.iters += 1
+            return self.iters >= self.max_iters
+
+        def fit():
+            while True:
+                hit = step_iters()
+                convg = descend(list(screen), True)
+                if hit:
+                    publish()
+                    raise _ScreenSetError(max_iters)
+                if convg <= tol * y_var:
+                    prune()
+                    return
+                while True:
+                    hit = step_iters()
+                    convg = descend(list(active), False)
+                    if hit:
+                        publish()
+                        raise _ScreenSetError(max_iters)
+                    if convg <= tol * y_var:
+                        break
+                prune()
+
+        with np.errstate(**self._errstate):
+            while True:
+                loss_prev = loss
+                fit()
+                if self.n_kkt > 0 and float(abs(loss - loss_prev)) < 1e-6 * float(abs(y_var)):
+                    break
+                self.n_kkt += 1
+                self.grad = self._violations().astype(self._dtype)
+                order = np.argsort(-self.grad, kind="stable")  # ties to the lower index (the reference leaves them open)
+                n_old, passed = len(screen), True
+                for k in order:
+                    if is_screen[k] or not self.grad[k] > 0:
+                        continue
+                    passed = False
+                    if len(screen) >= n_old + self.kappa:
+                        break
+                    k = int(k)
+                    screen.append(k)
+                    is_screen[k] = True
+                    self._admitted(k)
+                if passed:
+                    break
+        publish()
+
+
 def _bvls_native(X):
     """Whether ``X`` is a plain dense design, i.e. what ``adelie_hip_bvls_solve`` accepts."""
     return (isinstance(X, _matrix._NativeMatrix) and getattr(X, "_kind", None) == "dense"
             and not isinstance(X, (_matrix._MultiView, _matrix._StdView)))
 
 
-class bvls:
+class bvls(_ScreenSetState):
     """Bounded-variable least squares state (reference ``adelie.state.bvls``, ``state.py:3124-3275``; ``StateBVLS``,
     ``state_bvls.ipp``): ``min 1/2 ||y - X beta||_W^2`` subject to ``lower <= beta <= upper``.  Constructor arguments and
     attributes are the reference's, plus ``iters``, ``n_kkt``, ``error`` and ``total_time``.  The constructor repeats the
@@ -1397,45 +1571,17 @@ class bvls:
                     active_set=self.active_set, is_active=self.is_active, beta=self.beta, resid=self.resid, grad=self.grad,
                     loss=self.loss)
 
-    def _fill_sets(self, screen, active):
-        p = self.X.cols()
-        for name, members in (("screen", screen), ("active", active)):
-            buf = np.array(getattr(self, name + "_set"), copy=True, dtype=np.int64)
-            if buf.size < len(members):
-                buf = np.resize(buf, p)
-            buf[:len(members)] = members
-            flags = np.zeros(p, dtype=bool)
-            flags[np.asarray(members, dtype=np.int64)] = True
-            setattr(self, name + "_set", buf)
-            setattr(self, name + "_set_size", len(members))
-            setattr(self, "is_" + name, flags)
+    _name = "bvls"
 
-    def solve(self):
-        """Solves on the device (or, for designs the native route does not take, through the matrix interface) and returns
-        the solved state.  Failures inside the solve are logged and stored in ``error``, as ``state.base.solve`` does."""
-        import time
+    def _coords(self):
+        return self.X.cols()
 
-        out = self._spawn()
-        if _bvls_native(self.X):
-            out._solve_native()
-        else:
-            t0 = time.perf_counter()
-            try:
-                out._solve_generic()
-            except _BvlsError as e:
-                out.error = str(e)
-            out.total_time = time.perf_counter() - t0
-        if out.error != "":
-            if out.error.startswith("adelie_core solver: "):
-                logger.error(RuntimeError(out.error))
-            else:
-                logger.warning(RuntimeError(out.error))
-        return out
+    def _native(self):
+        return _bvls_native(self.X)
 
     def _solve_native(self):
-        X, dtype = self.X, self._dtype
+        X = self.X
         b = X._backend
-        p = X.cols()
         screen = np.ascontiguousarray(self.screen_set[:self.screen_set_size], dtype=np.int64)
         active = np.ascontiguousarray(self.active_set[:self.active_set_size], dtype=np.int64)
         args = _abi.BvlsArgs(
@@ -1450,129 +1596,30 @@ class bvls:
         handle = _abi.C.c_void_p()
         b.check(b.fn("bvls_solve")(X._handle, _abi.C.byref(args), handle))
         try:
-            def vec(name, dt):
-                which = _abi.BVLS_V[name]
-                m = b.fn("bvls_result_size")(handle, which)
-                o = np.empty(max(m, 0), dtype=dt)
-                if m > 0:
-                    b.check(b.fn("bvls_result_copy")(handle, which, o.ctypes.data, m))
-                return o
-
-            scalar = b.fn("bvls_result_scalar")
-            self.beta, self.resid, self.grad = vec("beta", dtype), vec("resid", dtype), vec("grad", dtype)
-            self._fill_sets(vec("screen_set", np.int64), vec("active_set", np.int64))
-            assert np.array_equal(self.is_screen, vec("is_screen", np.uint8).astype(bool))
-            assert np.array_equal(self.is_active, vec("is_active", np.uint8).astype(bool))
-            self.loss = float(scalar(handle, _abi.BVLS_S["loss"]))
-            self.iters = int(scalar(handle, _abi.BVLS_S["iters"]))
-            self.n_kkt = int(scalar(handle, _abi.BVLS_S["n_kkt"]))
-            self.total_time = float(scalar(handle, _abi.BVLS_S["total_time"]))
-            # device-phase times of the solve (scripts/bench_bvls.py)
-            self.benchmark = {k: float(scalar(handle, _abi.BVLS_S[k])) for k in ("t_sweep_ms", "t_gram_ms", "t_fit_ms", "n_changed")}
-            msg = b.fn("bvls_result_error")(handle)
-            self.error = msg.decode() if msg else ""
+            self._read_result(b, handle, "bvls", _abi.BVLS_V, _abi.BVLS_S)
         finally:
             b.fn("bvls_result_destroy")(handle)
 
-    def _solve_generic(self):
-        """solver_bvls.hpp:22-348 over ``X.cmul`` / ``X.ctmul`` / ``X.mul``, arithmetic in the design's dtype."""
-        X, dt = self.X, self._dtype.type
-        p = X.cols()
-        lower, upper, w, X_vars = self.lower, self.upper, self.weights, self.X_vars
-        beta, resid = self.beta, self.resid
-        screen = [int(k) for k in self.screen_set[:self.screen_set_size]]
-        active = [int(k) for k in self.active_set[:self.active_set_size]]
-        is_screen = np.array(self.is_screen, copy=True)
-        is_active = np.array(self.is_active, copy=True)
-        y_var, tol = dt(self.y_var), dt(self.tol)
-        loss = dt(self.loss)
-        half = dt(0.5)
+    # ---- the route over ``X.cmul`` / ``X.ctmul`` / ``X.mul`` ----
+    def _update(self, k, bk):
+        vk, lk, uk = self.X_vars[k], self.lower[k], self.upper[k]
+        gk = self._dtype.type(self.X.cmul(k, self.resid, self.weights))
+        step = self._dtype.type(0) if vk <= 0 else gk / vk
+        return vk, gk, min(max(bk + step, lk), uk)
 
-        def publish():
-            self.loss = float(loss)
-            self._fill_sets(screen, active)
+    def _step_resid(self, k, d):
+        self.X.ctmul(k, -d, self.resid)
 
-        def descend(members, add):
-            nonlocal loss
-            convg = dt(0)
-            for k in members:
-                vk, lk, uk = X_vars[k], lower[k], upper[k]
-                gk = dt(X.cmul(k, resid, w))
-                bk = beta[k]
-                step = dt(0) if vk <= 0 else gk / vk
-                bn = min(max(bk + step, lk), uk)
-                if bn == bk:
-                    continue
-                beta[k] = bn
-                d = bn - bk
-                sds = vk * d * d
-                convg = max(convg, sds)
-                loss = loss - (d * gk - half * sds)
-                X.ctmul(k, -d, resid)
-                if add and not is_active[k]:
-                    active.append(k)
-                    is_active[k] = True
-            return convg
+    def _drop(self, k):
+        return self.beta[k] <= self.lower[k] or self.beta[k] >= self.upper[k]
 
-        def prune():
-            keep = [k for k in active if not (beta[k] <= lower[k] or beta[k] >= upper[k])]
-            for k in active:
-                is_active[k] = False
-            for k in keep:
-                is_active[k] = True
-            active[:] = keep
+    def _violations(self):
+        grad = np.empty(self.X.cols(), dtype=self._dtype)
+        self.X.mul(self.resid, self.weights, grad)
+        return np.maximum(grad, 0) * (self.beta < self.upper) - np.minimum(grad, 0) * (self.beta > self.lower)
 
-        def step_iters():
-            self.iters += 1
-            return self.iters >= self.max_iters
-
-        def fit():
-            while True:
-                hit = step_iters()
-                convg = descend(list(screen), True)
-                if hit:
-                    publish()
-                    raise _BvlsError("adelie_core solver: bvls: max iterations reached!")
-                if convg <= tol * y_var:
-                    prune()
-                    return
-                while True:
-                    hit = step_iters()
-                    convg = descend(list(active), False)
-                    if hit:
-                        publish()
-                        raise _BvlsError("adelie_core solver: bvls: max iterations reached!")
-                    if convg <= tol * y_var:
-                        break
-                prune()
-
-        while True:
-            loss_prev = loss
-            fit()
-            if self.n_kkt > 0 and float(abs(loss - loss_prev)) < 1e-6 * float(abs(y_var)):
-                break
-            self.n_kkt += 1
-            grad = np.empty(p, dtype=self._dtype)
-            X.mul(resid, w, grad)
-            viols = np.maximum(grad, 0) * (beta < upper) - np.minimum(grad, 0) * (beta > lower)
-            self.grad = viols.astype(self._dtype)
-            order = np.argsort(-self.grad, kind="stable")  # ties to the lower index (the reference leaves them open)
-            n_old, passed = len(screen), True
-            for k in order:
-                if is_screen[k] or not self.grad[k] > 0:
-                    continue
-                passed = False
-                if len(screen) >= n_old + self.kappa:
-                    break
-                screen.append(int(k))
-                is_screen[k] = True
-            if passed:
-                break
-        publish()
-
-
-class _BvlsError(RuntimeError):
-    pass
+    def _admitted(self, k):
+        pass
 
 
 def _pinball_native(A):
@@ -1580,7 +1627,7 @@ def _pinball_native(A):
     return isinstance(A, _matrix._ConstraintMatrix)
 
 
-class pinball:
+class pinball(_ScreenSetState):
     """Pinball least squares state (reference ``adelie.state.pinball``, ``state.py:3278-3440``; ``StatePinball``,
     ``state_pinball.ipp``):
 
@@ -1675,17 +1722,6 @@ class pinball:
                        screen_AS=self._screen_AS, active_set_size=self.active_set_size, active_set=self.active_set,
                        is_active=self.is_active, beta=self.beta, resid=self.resid, grad=self.grad, loss=self.loss)
 
-    def _fill_sets(self, screen, active):
-        m = int(self.A.rows())
-        for name, members in (("screen", screen), ("active", active)):
-            buf = np.array(getattr(self, name + "_set"), copy=True, dtype=np.int64)
-            buf[:len(members)] = members
-            flags = np.zeros(m, dtype=bool)
-            flags[np.asarray(members, dtype=np.int64)] = True
-            setattr(self, name + "_set", buf)
-            setattr(self, name + "_set_size", len(members))
-            setattr(self, "is_" + name, flags)
-
     # ---- screen_AS / screen_ASAT_diag: given, computed by the Python route, or fetched from the device on first access ----
     def _materialize(self):
         m, d = int(self.A.rows()), int(self.A.cols())
@@ -1724,30 +1760,18 @@ class pinball:
             self._materialize()
         return self._screen_ASAT_diag
 
-    def solve(self):
-        """Solves on the device (or, for matrices the native route does not take, through the matrix interface) and returns
-        the solved state.  Failures inside the solve are logged and stored in ``error``, as ``state.base.solve`` does."""
-        import time
+    _name = "pinball"
+    _errstate = dict(invalid="ignore")
+    _generic_benchmark = True
 
-        out = self._spawn()
-        if _pinball_native(self.A):
-            out._solve_native()
-        else:
-            t0 = time.perf_counter()
-            try:
-                out._solve_generic()
-            except _PinballError as e:
-                out.error = str(e)
-            out.total_time = time.perf_counter() - t0
-        if out.error != "":
-            if out.error.startswith("adelie_core solver: "):
-                logger.error(RuntimeError(out.error))
-            else:
-                logger.warning(RuntimeError(out.error))
-        return out
+    def _coords(self):
+        return int(self.A.rows())
+
+    def _native(self):
+        return _pinball_native(self.A)
 
     def _solve_native(self):
-        A, dtype = self.A, self._dtype
+        A = self.A
         b = A._backend
         m, d = A.rows(), A.cols()
         screen = np.ascontiguousarray(self.screen_set[:self.screen_set_size], dtype=np.int64)
@@ -1768,137 +1792,36 @@ class pinball:
         b.check(b.fn("pinball_solve")(A._handle, _abi.C.byref(args), handle))
         self._backend, self._result = b, handle
         self._screen_AS = self._screen_ASAT_diag = None  # (fetched from the result on first access)
+        self._read_result(b, handle, "pinball", _abi.PINBALL_V, _abi.PINBALL_S)
 
-        def vec(name, dt):
-            which = _abi.PINBALL_V[name]
-            n = b.fn("pinball_result_size")(handle, which)
-            o = np.empty(max(n, 0), dtype=dt)
-            if n > 0:
-                b.check(b.fn("pinball_result_copy")(handle, which, o.ctypes.data, n))
-            return o
-
-        scalar = b.fn("pinball_result_scalar")
-        self.beta, self.resid, self.grad = vec("beta", dtype), vec("resid", dtype), vec("grad", dtype)
-        self._fill_sets(vec("screen_set", np.int64), vec("active_set", np.int64))
-        assert np.array_equal(self.is_screen, vec("is_screen", np.uint8).astype(bool))
-        assert np.array_equal(self.is_active, vec("is_active", np.uint8).astype(bool))
-        self.loss = float(scalar(handle, _abi.PINBALL_S["loss"]))
-        self.iters = int(scalar(handle, _abi.PINBALL_S["iters"]))
-        self.n_kkt = int(scalar(handle, _abi.PINBALL_S["n_kkt"]))
-        self.total_time = float(scalar(handle, _abi.PINBALL_S["total_time"]))
-        # device-phase times of the solve (scripts/bench_pinball.py)
-        self.benchmark = {k: float(scalar(handle, _abi.PINBALL_S[k])) for k in ("t_sweep_ms", "t_gram_ms", "t_fit_ms", "n_changed")}
-        msg = b.fn("pinball_result_error")(handle)
-        self.error = msg.decode() if msg else ""
-
+    # ---- the route over ``A.rvmul`` / ``A.rmmul`` / ``A.tmul`` ----
     def _solve_generic(self):
-        """solver_pinball.hpp:11-309 over ``A.rvmul`` / ``A.rmmul`` / ``A.tmul``, arithmetic in the matrix's dtype."""
-        A, dt = self.A, self._dtype.type
-        m = int(A.rows())
-        pneg, ppos, S = self.penalty_neg, self.penalty_pos, self.S
         if self._screen_AS is None or self._screen_ASAT_diag is None:
             self._materialize()
-        AS, diag = self._screen_AS, self._screen_ASAT_diag
-        beta, resid = self.beta, self.resid
-        screen = [int(k) for k in self.screen_set[:self.screen_set_size]]
-        active = [int(k) for k in self.active_set[:self.active_set_size]]
-        is_screen = np.array(self.is_screen, copy=True)
-        is_active = np.array(self.is_active, copy=True)
-        y_var, tol = dt(self.y_var), dt(self.tol)
-        loss = dt(self.loss)
-        half, zero = dt(0.5), dt(0)
-        n_changed = 0
+        super()._solve_generic()
 
-        def publish():
-            self.loss = float(loss)
-            self._fill_sets(screen, active)
-            self.benchmark = dict(n_changed=float(n_changed))
+    def _update(self, k, bk):
+        dt = self._dtype.type
+        vk, lk, uk = self._screen_ASAT_diag[k], self.penalty_neg[k], self.penalty_pos[k]
+        gk = dt(self.A.rvmul(k, self.resid))
+        if vk <= 0:
+            return None
+        gk0 = gk + vk * bk
+        gk0_lk = gk0 + lk
+        return vk, gk, np.copysign(max(max(-gk0_lk, gk0 - uk), dt(0)), gk0_lk) / vk
 
-        def descend(members, add):
-            nonlocal loss, n_changed
-            convg = zero
-            for k in members:
-                vk, lk, uk = diag[k], pneg[k], ppos[k]
-                gk = dt(A.rvmul(k, resid))
-                bk = beta[k]
-                if vk <= 0:
-                    continue
-                gk0 = gk + vk * bk
-                gk0_lk = gk0 + lk
-                bn = np.copysign(max(max(-gk0_lk, gk0 - uk), zero), gk0_lk) / vk
-                if bn == bk:
-                    continue
-                beta[k] = bn
-                dl = bn - bk
-                sds = vk * dl * dl
-                convg = max(convg, sds)
-                loss = loss - (dl * gk - half * sds)
-                resid[:] = resid - dl * AS[k]
-                n_changed += 1
-                if add and not is_active[k]:
-                    active.append(k)
-                    is_active[k] = True
-            return convg
+    def _step_resid(self, k, dl):
+        self.resid[:] = self.resid - dl * self._screen_AS[k]
 
-        def prune():
-            keep = [k for k in active if beta[k] != 0]
-            for k in active:
-                is_active[k] = False
-            for k in keep:
-                is_active[k] = True
-            active[:] = keep
+    def _drop(self, k):
+        return self.beta[k] == 0
 
-        def step_iters():
-            self.iters += 1
-            return self.iters >= self.max_iters
+    def _violations(self):
+        grad = np.empty(int(self.A.rows()), dtype=self._dtype)
+        self.A.tmul(self.resid, grad)
+        return np.maximum(grad - self.penalty_pos, -self.penalty_neg - grad)
 
-        def fit():
-            while True:
-                hit = step_iters()
-                convg = descend(list(screen), True)
-                if hit:
-                    publish()
-                    raise _PinballError("adelie_core solver: pinball: max iterations reached!")
-                if convg <= tol * y_var:
-                    prune()
-                    return
-                while True:
-                    hit = step_iters()
-                    convg = descend(list(active), False)
-                    if hit:
-                        publish()
-                        raise _PinballError("adelie_core solver: pinball: max iterations reached!")
-                    if convg <= tol * y_var:
-                        break
-                prune()
-
-        with np.errstate(invalid="ignore"):
-            while True:
-                loss_prev = loss
-                fit()
-                if self.n_kkt > 0 and float(abs(loss - loss_prev)) < 1e-6 * float(abs(y_var)):
-                    break
-                self.n_kkt += 1
-                grad = np.empty(m, dtype=self._dtype)
-                A.tmul(resid, grad)
-                self.grad = np.maximum(grad - ppos, -pneg - grad).astype(self._dtype)
-                order = np.argsort(-self.grad, kind="stable")  # ties to the lower index (the reference leaves them open)
-                n_old, passed = len(screen), True
-                for k in order:
-                    if is_screen[k] or not self.grad[k] > 0:
-                        continue
-                    passed = False
-                    if len(screen) >= n_old + self.kappa:
-                        break
-                    k = int(k)
-                    screen.append(k)
-                    is_screen[k] = True
-                    A.rmmul(k, S, AS[k])
-                    diag[k] = max(dt(A.rvmul(k, AS[k])), zero)
-                if passed:
-                    break
-        publish()
-
-
-class _PinballError(RuntimeError):
-    pass
+    def _admitted(self, k):
+        dt = self._dtype.type
+        self.A.rmmul(k, self.S, self._screen_AS[k])
+        self._screen_ASAT_diag[k] = max(dt(self.A.rvmul(k, self._screen_AS[k])), dt(0))

@@ -137,3 +137,64 @@ for k, val in saved_env.items():
         os.environ.pop(k, None)
     else:
         os.environ[k] = val
+# solver.bvls and solver.pinball (cd_screen_driver.hpp, state._ScreenSetState) on the inputs of the tests' restatements: one
+# digest per leg over beta, resid, grad, the ordered sets, the flags, loss, iters, n_kkt and error (pinball: screen_AS and
+# screen_ASAT_diag as well); after it ns, iters, n_kkt
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+import bvls_checks as bc, pinball_checks as pc
+def cd_digest(st):
+    h = hashlib.sha1()
+    for a in (st.beta, st.resid, st.grad, st.screen_set[:st.screen_set_size], st.active_set[:st.active_set_size], st.is_screen, st.is_active):
+        h.update(np.ascontiguousarray(a).tobytes())
+    h.update(repr((st.loss, st.iters, st.n_kkt, st.error)).encode())
+    if hasattr(st, "screen_AS"):
+        h.update(np.ascontiguousarray(st.screen_AS).tobytes() + st.screen_ASAT_diag.tobytes())
+    return h.hexdigest()[:16], int(st.screen_set_size), st.iters, st.n_kkt
+def with_config(name, value, default, solve):
+    b = ad._abi.hip_backend()
+    b.check(b.fn("set_config")(name.encode(), float(value)))
+    try:
+        return solve()
+    finally:
+        b.check(b.fn("set_config")(name.encode(), float(default)))
+def cd_legs(name, solve, small, crossing):
+    """`small` ends by the KKT pass; `crossing` is solved with kappa = 7 and passes ns = 64 (the resident matrix is regrown with
+    members in it)."""
+    cold = solve(small)
+    assert cold.error == "", cold.error
+    print(name, "cold", *cd_digest(cold))
+    k7 = solve(crossing, kappa=7)
+    assert k7.error == "" and k7.screen_set_size > 64 and k7.n_kkt > 10, (k7.error, k7.screen_set_size)
+    print(name, "kappa7", *cd_digest(k7))
+    print(name, "warm", *cd_digest(solve(small, tol=1e-9, warm_start=cold)))
+    print(name, "global", *cd_digest(with_config(name.split()[0] + "_lds_max_ns", 16, 0, lambda: solve(crossing, kappa=7))))
+    st = solve(crossing, max_iters=3)
+    assert st.error.endswith("max iterations reached!"), st.error
+    print(name, "max_iters", *cd_digest(st))
+    st = with_config(name.split()[0] + "_gram_limit_mb", 0.0005, 16384, lambda: solve(crossing, kappa=7))   # 524 bytes: 7 x 7 fit, 14 x 14 do not
+    assert "screen set of 14 coordinates" in st.error and st.screen_set_size == 7, st.error
+    print(name, "gram_limit", *cd_digest(st))
+for dt in (np.float64, np.float32):
+    def bvls_solve(case, **kw):
+        Xb, yb, lo, up = bc.gaussian(*case)
+        return ad.bvls(np.asfortranarray(Xb, dtype=dt), yb.astype(dt), lo, up, **kw)
+    cd_legs("bvls " + np.dtype(dt).name, bvls_solve, (200, 70, 0), (64, 300, 0))
+    st = bvls_solve((400, 2000, 0), kappa=2000)
+    assert st.error == "" and st.screen_set_size > 1024, (st.error, st.screen_set_size)
+    print("bvls", np.dtype(dt).name, "ns>1024", *cd_digest(st))
+    def pinball_solve(case, **kw):
+        Ap, Sp, vp, pneg, ppos = pc.gen(*case)
+        return ad.pinball(Ap.astype(dt), np.asfortranarray(Sp.astype(dt)), vp.astype(dt), pneg, ppos, **kw)
+    cd_legs("pinball " + np.dtype(dt).name, pinball_solve, (130, 40, 0, 0.3), (300, 64, 0, 0.1))
+# the routes through the matrix interface: bvls on a lazily standardized design, pinball with the resident matrix routed there
+Xb, yb, lo, up = bc.gaussian(40, 13, 0)
+st = ad.bvls(ad.matrix.standardize(ad.matrix.dense(Xb), lazy=True), yb, lo, up)
+assert st.error == "" and not hasattr(st, "benchmark")
+print("bvls python_route", *cd_digest(st))
+native_rule, ad.state._pinball_native = ad.state._pinball_native, lambda A: False
+try:
+    st = ad.pinball(*pc.gen(20, 5, 0, 1.0))
+finally:
+    ad.state._pinball_native = native_rule
+assert st.error == "" and st.benchmark.keys() == {"n_changed"}
+print("pinball python_route", *cd_digest(st), st.benchmark["n_changed"])
