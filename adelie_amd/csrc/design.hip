@@ -5,6 +5,7 @@
 #include <memory>
 #include "common.hpp"
 #include "design_ops.hpp"
+#include "phased_decode_host.hpp"
 
 #include <mutex>
 
@@ -960,6 +961,58 @@ int adelie_hip_design_create_sparse(const int64_t* indptr, const int32_t* indice
     ABI_CATCH
 }
 
+// The second half of every constructor of a design kept sparse, from the point where the six compressed arrays lie in device
+// memory (d->kind, d->nnz set; the copies or kernels that fill them enqueued on d->stream): the row-block pointers and the
+// tile-major copy for the full sweeps.
+static void csc_finish(adelie_hip_design* d) {
+    const int64_t n = d->n, p = d->p, nnz = d->nnz;
+    const size_t vs = d->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
+    const size_t nz1 = size_t(std::max<int64_t>(nnz, 1));
+    hipStream_t s = d->stream;
+    csc_block_layout(n, vs, &d->sp_nb, &d->sp_rb);
+    if (d->sp_nb > 1) {
+        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bptr), size_t(p) * size_t(d->sp_nb + 1) * sizeof(int64_t)));
+        launch_csc_block_ptr(d->cptr, d->cidx, p, d->sp_nb, d->sp_rb, d->bptr, s);
+    }
+    // Tile-major copy for the full sweeps (csc_tile_sweep_kernel): tiles of kCscTileBytes of an n-vector.  Built on the
+    // device from the per-column tile pointers; the tile-major offsets are a prefix sum over (tile, column) on the host.
+    {
+        const int64_t th = kCscTileBytes / int64_t(vs);
+        const int64_t nt = (n + th - 1) / th;
+        // (the tile of v is 128 KB of dynamic LDS — gfx950 has 160 KB per workgroup, the only target of this library; a launch
+        // the device refuses raises in raw_sweep)
+        const bool worth = nt > 1 && nt <= 4096 && nnz >= (int64_t(1) << 16) && nt * (p + 1) * 8 <= (int64_t(1) << 30) &&
+                           nnz / (nt * p) >= 4; // (segments of a few entries at least: below, the pointers outweigh the entries)
+        if (worth) {
+            DevTmp ctmp;
+            AHIP_CHECK(hipMalloc(&ctmp.p, size_t(p) * size_t(nt + 1) * sizeof(int64_t)));
+            int64_t* colptr = static_cast<int64_t*>(ctmp.p);
+            launch_csc_block_ptr(d->cptr, d->cidx, p, int(nt), th, colptr, s);
+            std::vector<int64_t> cp(size_t(p) * size_t(nt + 1)), tp(size_t(nt) * size_t(p + 1));
+            AHIP_CHECK(hipMemcpyAsync(cp.data(), colptr, cp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+            AHIP_CHECK(hipStreamSynchronize(s));
+            int64_t run = 0;
+            for (int64_t t = 0; t < nt; ++t) {
+                int64_t* row = tp.data() + size_t(t) * size_t(p + 1);
+                for (int64_t c = 0; c < p; ++c) {
+                    row[c] = run;
+                    run += cp[size_t(c) * size_t(nt + 1) + size_t(t) + 1] - cp[size_t(c) * size_t(nt + 1) + size_t(t)];
+                }
+                row[p] = run;
+            }
+            AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->tptr), tp.size() * sizeof(int64_t)));
+            AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->trow), nz1 * sizeof(uint16_t)));
+            AHIP_CHECK(hipMalloc(&d->tval, nz1 * vs));
+            AHIP_CHECK(hipMemcpyAsync(d->tptr, tp.data(), tp.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            DTYPE_DISPATCH(d, launch_csc_tile_scatter<T>(colptr, d->cidx, static_cast<const T*>(d->cval), p, int(nt), th, d->tptr, d->trow,
+                                                         static_cast<T*>(d->tval), s))
+            AHIP_CHECK(hipStreamSynchronize(s));
+            d->sp_nt = int(nt);
+            d->sp_th = th;
+        }
+    }
+}
+
 int adelie_hip_design_create_csc(const int64_t* indptr, const int32_t* indices, const void* values, const int64_t* row_indptr,
                                  const int32_t* row_indices, const void* row_values, int64_t n, int64_t p, int dtype, int device,
                                  adelie_hip_design** out) {
@@ -1033,52 +1086,113 @@ int adelie_hip_design_create_csc(const int64_t* indptr, const int32_t* indices, 
         AHIP_CHECK(hipMemcpyAsync(d->rcol, row_indices, size_t(nnz) * sizeof(int32_t), hipMemcpyHostToDevice, s));
         AHIP_CHECK(hipMemcpyAsync(d->rval, row_values, size_t(nnz) * vs, hipMemcpyHostToDevice, s));
     }
-    csc_block_layout(n, vs, &d->sp_nb, &d->sp_rb);
-    if (d->sp_nb > 1) {
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bptr), size_t(p) * size_t(d->sp_nb + 1) * sizeof(int64_t)));
-        launch_csc_block_ptr(d->cptr, d->cidx, p, d->sp_nb, d->sp_rb, d->bptr, s);
-    }
-    // Tile-major copy for the full sweeps (csc_tile_sweep_kernel): tiles of kCscTileBytes of an n-vector.  Built on the
-    // device from the per-column tile pointers; the tile-major offsets are a prefix sum over (tile, column) on the host.
-    {
-        const int64_t th = kCscTileBytes / int64_t(vs);
-        const int64_t nt = (n + th - 1) / th;
-        // (the tile of v is 128 KB of dynamic LDS — gfx950 has 160 KB per workgroup, the only target of this library; a launch
-        // the device refuses raises in raw_sweep)
-        const bool worth = nt > 1 && nt <= 4096 && nnz >= (int64_t(1) << 16) && nt * (p + 1) * 8 <= (int64_t(1) << 30) &&
-                           nnz / (nt * p) >= 4; // (segments of a few entries at least: below, the pointers outweigh the entries)
-        if (worth) {
-            DevTmp ctmp;
-            AHIP_CHECK(hipMalloc(&ctmp.p, size_t(p) * size_t(nt + 1) * sizeof(int64_t)));
-            int64_t* colptr = static_cast<int64_t*>(ctmp.p);
-            launch_csc_block_ptr(d->cptr, d->cidx, p, int(nt), th, colptr, s);
-            std::vector<int64_t> cp(size_t(p) * size_t(nt + 1)), tp(size_t(nt) * size_t(p + 1));
-            AHIP_CHECK(hipMemcpyAsync(cp.data(), colptr, cp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-            AHIP_CHECK(hipStreamSynchronize(s));
-            int64_t run = 0;
-            for (int64_t t = 0; t < nt; ++t) {
-                int64_t* row = tp.data() + size_t(t) * size_t(p + 1);
-                for (int64_t c = 0; c < p; ++c) {
-                    row[c] = run;
-                    run += cp[size_t(c) * size_t(nt + 1) + size_t(t) + 1] - cp[size_t(c) * size_t(nt + 1) + size_t(t)];
-                }
-                row[p] = run;
-            }
-            AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->tptr), tp.size() * sizeof(int64_t)));
-            AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->trow), nz1 * sizeof(uint16_t)));
-            AHIP_CHECK(hipMalloc(&d->tval, nz1 * vs));
-            AHIP_CHECK(hipMemcpyAsync(d->tptr, tp.data(), tp.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-            DTYPE_DISPATCH(d, launch_csc_tile_scatter<T>(colptr, d->cidx, static_cast<const T*>(d->cval), p, int(nt), th, d->tptr, d->trow,
-                                                         static_cast<T*>(d->tval), s))
-            AHIP_CHECK(hipStreamSynchronize(s));
-            d->sp_nt = int(nt);
-            d->sp_th = th;
-        }
-    }
+    csc_finish(d);
     AHIP_CHECK(hipStreamSynchronize(s));
     *out = g.release();
     ABI_CATCH
 }
+
+// A phased-ancestry design from its host code table (phased_decode_host.hpp): the table is uploaded (2 n s bytes), counted,
+// the counts are summed on the host into cptr, the (column, tile) segment starts and rptr, and kernels_phased.hip fills the
+// six arrays of a design kept sparse in the canonical form adelie_hip_design_create_csc demands of its caller.
+static void phased_build(adelie_hip_design* d, const uint8_t* table, int64_t s, int A) {
+    const int64_t n = d->n, p = d->p;
+    const int nt = phased_tiles(n);
+    if (s * int64_t(nt) >= (int64_t(1) << 31)) throw make_core_error("snp_phased_ancestry: too many (SNP, row tile) pairs.");
+    hipStream_t st = d->stream;
+    d->kind = adelie_hip_design::kCsc;
+    const size_t segs = size_t(p) * size_t(nt), vs = d->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
+    DevTmp code, ccnt, rcnt, cpos;
+    AHIP_CHECK(hipMalloc(&code.p, size_t(n) * size_t(2 * s)));
+    AHIP_CHECK(hipMalloc(&ccnt.p, segs * sizeof(int32_t)));
+    AHIP_CHECK(hipMalloc(&rcnt.p, size_t(n) * sizeof(int64_t)));
+    const uint8_t* dcode = static_cast<const uint8_t*>(code.p);
+    AHIP_CHECK(hipMemcpyAsync(code.p, table, size_t(n) * size_t(2 * s), hipMemcpyHostToDevice, st));
+    launch_phased_count(dcode, n, s, A, static_cast<int32_t*>(ccnt.p), static_cast<int64_t*>(rcnt.p), st);
+    AHIP_CHECK(hipGetLastError());
+    std::vector<int32_t> col_cnt(segs);
+    std::vector<int64_t> col_pos(segs), cptr(size_t(p) + 1), rptr(size_t(n) + 1);
+    AHIP_CHECK(hipMemcpyAsync(col_cnt.data(), ccnt.p, segs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    AHIP_CHECK(hipMemcpyAsync(rptr.data() + 1, rcnt.p, size_t(n) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    AHIP_CHECK(hipStreamSynchronize(st));
+    int64_t run = 0;
+    for (size_t k = 0; k < segs; ++k) { // (column-major over (column, tile): a column's segments are consecutive)
+        if (k % size_t(nt) == 0) cptr[k / size_t(nt)] = run;
+        col_pos[k] = run;
+        run += col_cnt[k];
+    }
+    cptr[size_t(p)] = run;
+    rptr[0] = 0;
+    for (int64_t i = 0; i < n; ++i) rptr[size_t(i) + 1] += rptr[size_t(i)];
+    if (rptr[size_t(n)] != run) throw make_core_error("snp_phased_ancestry: the row and column counts of the build disagree.");
+    const int64_t nnz = d->nnz = run;
+    const size_t nz1 = size_t(std::max<int64_t>(nnz, 1));
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cptr), size_t(p + 1) * sizeof(int64_t)));
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cidx), nz1 * sizeof(int32_t)));
+    AHIP_CHECK(hipMalloc(&d->cval, nz1 * vs));
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rptr), size_t(n + 1) * sizeof(int64_t)));
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rcol), nz1 * sizeof(int32_t)));
+    AHIP_CHECK(hipMalloc(&d->rval, nz1 * vs));
+    AHIP_CHECK(hipMalloc(&cpos.p, segs * sizeof(int64_t)));
+    AHIP_CHECK(hipMemcpyAsync(d->cptr, cptr.data(), size_t(p + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    AHIP_CHECK(hipMemcpyAsync(d->rptr, rptr.data(), size_t(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    AHIP_CHECK(hipMemcpyAsync(cpos.p, col_pos.data(), segs * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    DTYPE_DISPATCH(d, launch_phased_fill<T>(dcode, n, s, A, static_cast<const int64_t*>(cpos.p), d->rptr, d->cidx,
+                                            static_cast<T*>(d->cval), d->rcol, static_cast<T*>(d->rval), st))
+    AHIP_CHECK(hipGetLastError());
+    AHIP_CHECK(hipStreamSynchronize(st)); // (the table and the segment starts are freed on the way out)
+    csc_finish(d);
+    AHIP_CHECK(hipStreamSynchronize(st));
+}
+
+int adelie_hip_design_create_snp_phased_ancestry(const void* snpdat, int64_t n_bytes, int dtype, int device, adelie_hip_design** out) {
+    ABI_TRY
+    if (!snpdat || !out) throw make_core_error("null argument.");
+    const uint8_t* buf = static_cast<const uint8_t*>(snpdat);
+    PhasedDims dims;
+    if (const char* e = phased_header(buf, n_bytes < 0 ? 0 : uint64_t(n_bytes), &dims)) throw make_core_error(e);
+    std::vector<uint8_t> table(size_t(dims.n) * size_t(2 * dims.s));
+    if (const char* e = phased_decode(buf, uint64_t(n_bytes), dims, table.data())) throw make_core_error(e);
+    DesignGuard g(new_design(int64_t(dims.n), int64_t(dims.s * dims.A), dtype, device));
+    phased_build(g.get(), table.data(), int64_t(dims.s), int(dims.A));
+    *out = g.release();
+    ABI_CATCH
+}
+
+int adelie_hip_design_create_snp_phased_calldata(const int8_t* calldata, const int8_t* ancestries, int64_t n, int64_t s, int64_t A,
+                                                 int dtype, int device, adelie_hip_design** out) {
+    ABI_TRY
+    if (!calldata || !ancestries || !out) throw make_core_error("null argument.");
+    if (const char* e = phased_pack_dims(n, s, A)) throw make_core_error(e);
+    std::vector<uint8_t> table(size_t(n) * size_t(2 * s));
+    if (const char* e = phased_pack(calldata, ancestries, n, s, A, table.data())) throw make_core_error(e);
+    DesignGuard g(new_design(n, s * A, dtype, device));
+    phased_build(g.get(), table.data(), s, int(A));
+    *out = g.release();
+    ABI_CATCH
+}
+
+int adelie_hip_design_csc_download(adelie_hip_design* d, int64_t* indptr, int32_t* indices, void* values, int64_t* row_indptr,
+                                   int32_t* row_indices, void* row_values) {
+    ABI_TRY
+    if (!d) throw make_core_error("null argument.");
+    if (!d->is_csc()) throw make_core_error("csc_download() takes a design kept sparse.");
+    set_device(d);
+    hipStream_t s = d->stream;
+    const size_t vs = d->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float), nnz = size_t(d->nnz);
+    auto down = [&](void* dst, const void* src, size_t bytes) {
+        if (dst && bytes) AHIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+    };
+    down(indptr, d->cptr, size_t(d->p + 1) * sizeof(int64_t));
+    down(indices, d->cidx, nnz * sizeof(int32_t));
+    down(values, d->cval, nnz * vs);
+    down(row_indptr, d->rptr, size_t(d->n + 1) * sizeof(int64_t));
+    down(row_indices, d->rcol, nnz * sizeof(int32_t));
+    down(row_values, d->rval, nnz * vs);
+    AHIP_CHECK(hipStreamSynchronize(s));
+    ABI_CATCH
+}
+int64_t adelie_hip_design_nnz(const adelie_hip_design* d) { return d && d->is_csc() ? d->nnz : -1; }
 
 int adelie_hip_design_create_standardized(adelie_hip_design* src, const double* centers, const double* scales,
                                           adelie_hip_design** out) {

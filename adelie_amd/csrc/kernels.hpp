@@ -823,4 +823,18 @@ template <class T> void launch_relu_expand(const ReluView<T>& F, T* X, int64_t l
 template <class T>
 void launch_sweep_relu(const ReluView<T>& F, const T* v, T* out, const T* sub_scale, const T* sub_vec, T* work, hipStream_t s);
 
+// ---- phased-ancestry SNP designs (kernels_phased.hip): the arrays of a CscView built from the (n, 2 s) code table -------------
+// `code` is the column-major uint8 table of phased_decode_host.hpp (ancestry of a mutation, or 255); the design has s A columns,
+// column j A + a counting the haplotypes of SNP j mutated with ancestry a.  Rows are cut into phased_tiles(n) tiles of
+// kPhasedTileRows; the caller keeps s * phased_tiles(n) below 2^31 (one workgroup each).
+int phased_tiles(int64_t n);
+// col_cnt[(j A + a) nt + t] = stored entries of column j A + a in tile t; row_cnt[i] = stored entries of row i
+void launch_phased_count(const uint8_t* code, int64_t n, int64_t s, int A, int32_t* col_cnt, int64_t* row_cnt, hipStream_t st);
+// col_pos = the exclusive prefix sum of col_cnt in its own order (so cptr[c] = col_pos[c nt]), rptr that of row_cnt: fills
+// cidx / cval and rcol / rval in canonical form (rows ascending in a column, columns ascending in a row, one entry of value 2
+// where both haplotypes carry the same ancestry).  Positions come from the counts alone: two calls write identical arrays.
+template <class T>
+void launch_phased_fill(const uint8_t* code, int64_t n, int64_t s, int A, const int64_t* col_pos, const int64_t* rptr, int32_t* cidx,
+                        T* cval, int32_t* rcol, T* rval, hipStream_t st);
+
 } // namespace ahip

@@ -1,5 +1,5 @@
 """Synthetic data generators — self-contained restatement of the recipes in reference ``adelie/data.py``:
-``dense`` (``:84-219``) and ``snp_unphased`` (``:222-359``), single-response gaussian / binomial / cox only.
+``dense`` (``:84-219``), ``snp_unphased`` (``:222-359``) and ``snp_phased_ancestry`` (``:362-503``), single-response gaussian / binomial / cox only.
 Used by the tests and by ``bench.py``."""
 import numpy as np
 
@@ -117,3 +117,48 @@ def snp_unphased(n: int, p: int, G: int = None, *, glm: str = "gaussian", sparsi
     eta = Xd @ beta
     glm_o = _sample_y(glm, eta[:, None] if glm == "gaussian" else eta, beta[beta != 0], 0, snr)
     return {"X": X, "glm": glm_o, "groups": groups, "group_sizes": group_sizes, "impute": impute}
+
+
+def snp_phased_ancestry(n: int, s: int, A: int, *, glm: str = "gaussian", sparsity: float = 0.95, one_ratio: float = 0.25,
+                        two_ratio: float = 0.05, zero_penalty: float = 0, snr: float = 1, seed: int = 0):
+    """Phased calldata with local ancestry (reference ``adelie.data.snp_phased_ancestry``, ``data.py:362-503``): int8
+    ``(n, 2s)`` ``X`` (calls in {0, 1}; column ``2j + k`` is haplotype ``k`` of SNP ``j``) and ``ancestries`` (labels in
+    ``[0, A)``, zero where nothing was drawn).  An unphased matrix with ``one_ratio`` ones and ``two_ratio`` twos is drawn and
+    phased: a one mutates a random haplotype, a two both.  Groups are the ``s`` SNPs of ``A`` columns each.  The legacy global
+    stream is consumed in the reference's order.  Returns ``X``, ``ancestries``, ``glm`` (and its response as ``y``),
+    ``groups``, ``group_sizes``, ``penalty``."""
+    if not (n >= 1 and s >= 1 and A >= 1 and snr > 0 and seed >= 0):
+        raise ValueError("n, s, A >= 1, snr > 0 and seed >= 0 are required")
+    for r in (sparsity, one_ratio, two_ratio, zero_penalty):
+        if not 0 <= r <= 1:
+            raise ValueError("sparsity, one_ratio, two_ratio and zero_penalty must lie in [0, 1]")
+    np.random.seed(seed)
+    stored_ratio = one_ratio + two_ratio
+    stored = int(stored_ratio * n * s)
+    cells = np.random.permutation(np.random.choice(n * s, stored, replace=False))  # (sample, SNP) cells that are 1 or 2
+    n_ones = int(one_ratio / max(stored_ratio, 1e-300) * stored)
+    ones = 2 * cells[:n_ones] + np.random.binomial(1, 0.5, n_ones)  # the mutated haplotype of a one
+    twos = 2 * cells[n_ones:]                                       # the first haplotype of a two
+    X = np.zeros((n, 2 * s), dtype=np.int8)
+    anc = np.zeros((n, 2 * s), dtype=np.int8)
+    Xf, af = X.reshape(-1), anc.reshape(-1)
+    Xf[ones] = 1
+    Xf[twos] = 1
+    Xf[twos + 1] = 1
+    af[ones] = np.random.choice(A, len(ones), replace=True)
+    af[twos] = np.random.choice(A, len(twos), replace=True)
+    af[twos + 1] = np.random.choice(A, len(twos), replace=True)
+
+    groups = A * np.arange(s)
+    group_sizes = np.full(s, A, dtype=int)
+    penalty = np.sqrt(group_sizes)
+    penalty[np.random.choice(s, int(zero_penalty * s), replace=False)] = 0
+    penalty /= np.linalg.norm(penalty) / np.sqrt(s * A)
+
+    coef = np.random.normal(0, 1, (2 * s, 1))
+    support = np.random.choice(2 * s, int((1 - sparsity) * s * 2), replace=False)
+    signal = coef[support]
+    eta = X[:, support] @ signal
+    response = _sample_y(glm, eta, signal, 0, snr)
+    return {"X": np.asfortranarray(X), "ancestries": np.asfortranarray(anc), "glm": response, "y": getattr(response, "y", None),
+            "groups": groups, "group_sizes": group_sizes, "penalty": penalty}

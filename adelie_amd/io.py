@@ -10,6 +10,10 @@ File layout (little endian, reference ``io_snp_unphased.ipp:117-135,225-274``)::
 
 The codec below is integer/byte work done once on the host in numpy; the device design keeps a dense
 2-bit-per-call layout built from it (``adelie_hip_design_create_snp_unphased``).
+
+``snp_phased_ancestry`` mirrors ``adelie.io.snp_phased_ancestry`` (reference ``adelie/io.py:6-111``,
+``io_snp_phased_ancestry.hpp:20-41``, ``.ipp:10-42,143-347``) the same way; its layout is in the class docstring, and its device
+design is a design kept sparse (``adelie_hip_design_create_snp_phased_ancestry``).
 """
 import os
 
@@ -167,6 +171,166 @@ class snp_unphased:
                     rows = buf[pos + 5:pos + 5 + k].astype(np.int64) + cidx * CHUNK
                     out[rows, j] = vals[c]
                     pos += 5 + k
+        return out
+
+
+def _chunk_blob(rows):
+    """``[u32 n_chunks]`` then ``[u32 chunk_idx][u8 nnz-1][u8 row_in_chunk * nnz]`` per non-empty 256-row chunk of the
+    ascending row indices ``rows``."""
+    uniq, starts, counts = np.unique(rows // CHUNK, return_index=True, return_counts=True)
+    parts = [np.uint32(len(uniq)).tobytes()]
+    for u, s, k in zip(uniq, starts, counts):
+        parts.append(np.uint32(u).tobytes())
+        parts.append(np.uint8(k - 1).tobytes())
+        parts.append((rows[s:s + k] % CHUNK).astype(np.uint8).tobytes())
+    return b"".join(parts)
+
+
+class snp_phased_ancestry:
+    """IO handler for the ``.snpdat`` phased-ancestry format (reference ``adelie.io.snp_phased_ancestry``, ``adelie/io.py:6-111``,
+    ``io_snp_phased_ancestry.hpp:20-41``, ``.ipp:10-42,143-347``).  ``n`` samples, ``s`` SNPs with two haplotypes each and
+    ``A < 256`` ancestries; the matrix it stands for is ``(n, s * A)`` with ``X[i, j*A + a]`` the number of haplotypes
+    ``k in {0, 1}`` with ``calldata[i, 2j+k] == 1 and ancestries[i, 2j+k] == a``.  Layout (little endian)::
+
+        [u8 is_big_endian][u64 n][u64 s][u8 A][u64 nnz0[s*A]][u64 nnz1[s*A]][u64 outer[s+1]]    outer[] absolute
+        SNP j at outer[j]:             [u64 anc_off[A]]   relative to the SNP block, anc_off[0] = 8*A
+          ancestry a at anc_off[a]:    [u64 hap_off[2]]   relative to the ancestry block, hap_off[0] = 16
+            haplotype k at hap_off[k]: [u32 n_chunks], per non-empty chunk [u32 chunk_idx][u8 nnz-1][u8 row_in_chunk * nnz]
+
+    ``nnz0`` / ``nnz1`` count, per column ``j*A + a``, the stored rows of haplotype 0 / 1.  A numpy codec on the host; the
+    device design is built by ``matrix.snp_phased_ancestry`` from the image."""
+
+    def __init__(self, filename: str, read_mode: str = "file"):
+        if read_mode not in ("file", "mmap"):
+            raise RuntimeError("adelie_core: read_mode must be 'file' or 'mmap'.")
+        self._filename = filename
+        self._read_mode = read_mode
+        self._buffer = None
+
+    @property
+    def is_read(self):
+        return self._buffer is not None
+
+    def _need(self):
+        if not self.is_read:
+            raise RuntimeError("adelie_core: File is not read yet. Call read() first.")
+
+    @property
+    def endian(self):
+        self._need()
+        return bool(self._buffer[0])
+
+    @property
+    def rows(self):
+        self._need()
+        return int(self._buffer[1:9].view(np.uint64)[0])
+
+    @property
+    def snps(self):
+        self._need()
+        return int(self._buffer[9:17].view(np.uint64)[0])
+
+    @property
+    def ancestries(self):
+        self._need()
+        return int(self._buffer[17])
+
+    @property
+    def cols(self):
+        return self.snps * self.ancestries
+
+    def _vec(self, k):
+        p = self.cols
+        off = 18 + 8 * p * k
+        return self._buffer[off:off + 8 * p].view(np.uint64)
+
+    @property
+    def nnz0(self):
+        return self._vec(0).copy()
+
+    @property
+    def nnz1(self):
+        return self._vec(1).copy()
+
+    @property
+    def outer(self):
+        off = 18 + 16 * self.cols
+        return self._buffer[off:off + 8 * (self.snps + 1)].view(np.uint64)
+
+    def read(self):
+        """Reads (or memory-maps) the whole file image; returns the number of bytes (the endianness check of
+        ``io_snp_base.ipp:21-85``)."""
+        if self._read_mode == "mmap":
+            buf = np.memmap(self._filename, dtype=np.uint8, mode="r")
+        else:
+            buf = np.fromfile(self._filename, dtype=np.uint8)
+        if buf.size < 18:
+            raise RuntimeError("adelie_core: file is too small to be a .snpdat file.")
+        if bool(buf[0]) != (not np.little_endian):
+            raise RuntimeError("adelie_core: Endianness is inconsistent! Regenerate the file on this machine.")
+        self._buffer = np.ascontiguousarray(buf)
+        return int(buf.size)
+
+    def write(self, calldata: np.ndarray, ancestries: np.ndarray, A: int, n_threads: int = 1):
+        """Writes int8 ``(n, 2s)`` ``calldata`` (0 / 1) and ``ancestries`` (in ``[0, A)`` everywhere; ignored where the call
+        is 0) (reference ``io_snp_phased_ancestry.ipp:73-361``).  Returns ``(bytes_written, benchmark)``."""
+        calldata, ancestries = np.asarray(calldata), np.asarray(ancestries)
+        if (calldata.ndim != 2 or ancestries.ndim != 2 or calldata.shape != ancestries.shape or calldata.shape[1] % 2):
+            raise RuntimeError("adelie_core: calldata and ancestries must have shape (n, 2*s).")
+        A = int(A)
+        if A >= CHUNK:
+            raise RuntimeError(f"adelie_core: Number of ancestries A must be < {CHUNK}.")
+        if np.any(ancestries < 0) or np.any(ancestries >= A):
+            raise RuntimeError("adelie_core: Detected an ancestry not in the range [0, A). "
+                               "Make sure ancestries only contains values in [0, A). ")
+        if np.any((calldata != 0) & (calldata != 1)):
+            raise RuntimeError("adelie_core: Detected a non-binary value. Make sure calldata only contains 0 or 1 values. ")
+        n, s = calldata.shape[0], calldata.shape[1] // 2
+        nnz = np.zeros((2, s * A), dtype=np.uint64)
+        blocks = []
+        for j in range(s):
+            anc_blobs = []
+            for a in range(A):
+                haps = []
+                for k in range(2):
+                    rows = np.flatnonzero((calldata[:, 2 * j + k] == 1) & (ancestries[:, 2 * j + k] == a))
+                    nnz[k, j * A + a] = len(rows)
+                    haps.append(_chunk_blob(rows))
+                anc_blobs.append(np.array([16, 16 + len(haps[0])], dtype=np.uint64).tobytes() + haps[0] + haps[1])
+            offs = 8 * A + np.concatenate([[0], np.cumsum([len(b) for b in anc_blobs[:-1]])]).astype(np.uint64)
+            blocks.append(offs.astype(np.uint64).tobytes() + b"".join(anc_blobs))
+        outer = np.zeros(s + 1, dtype=np.uint64)
+        outer[0] = 18 + 16 * s * A + 8 * (s + 1)
+        outer[1:] = outer[0] + np.cumsum([len(b) for b in blocks]).astype(np.uint64)
+        blob = (np.uint8(0 if np.little_endian else 1).tobytes() + np.uint64(n).tobytes() + np.uint64(s).tobytes()
+                + np.uint8(A).tobytes() + nnz[0].tobytes() + nnz[1].tobytes() + outer.tobytes() + b"".join(blocks))
+        with open(self._filename, "wb") as f:
+            f.write(blob)
+        return len(blob), {}
+
+    def to_dense(self, n_threads: int = 1):
+        """Dense int8 ``(n, s * A)`` matrix with entries in {0, 1, 2} (reference ``io_snp_phased_ancestry.ipp:44-71``)."""
+        self._need()
+        n, s, A = self.rows, self.snps, self.ancestries
+        out = np.zeros((n, s * A), dtype=np.int8)
+        buf = self._buffer
+        outer = self.outer
+        for j in range(s):
+            base = int(outer[j])
+            anc_off = buf[base:base + 8 * A].view(np.uint64)
+            for a in range(A):
+                ablk = base + int(anc_off[a])
+                hap_off = buf[ablk:ablk + 16].view(np.uint64)
+                for k in range(2):
+                    pos = ablk + int(hap_off[k])
+                    n_chunks = int(buf[pos:pos + 4].view(np.uint32)[0])
+                    pos += 4
+                    for _ in range(n_chunks):
+                        cidx = int(buf[pos:pos + 4].view(np.uint32)[0])
+                        cnt = int(buf[pos + 4]) + 1
+                        rows = buf[pos + 5:pos + 5 + cnt].astype(np.int64) + cidx * CHUNK
+                        out[rows, j * A + a] += 1
+                        pos += 5 + cnt
         return out
 
 

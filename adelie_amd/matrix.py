@@ -1279,6 +1279,123 @@ def snp_bed(bed, n: int, p: int = None, *, dtype=np.float64, n_threads: int = 1,
     return _wrap(backend, handle, np.dtype(dtype).type, n_threads, kind="snp")
 
 
+_PHASED_TILE_ROWS = 4096  # kPhasedTileRows (csrc/phased_decode_host.hpp): rows per workgroup of the device build
+
+
+def _csc_download(m):
+    """The six arrays of a design kept sparse, copied back from the device (``adelie_hip_design_csc_download``):
+    ``(indptr, indices, values, row_indptr, row_indices, row_values)``."""
+    backend = m._backend
+    nnz = int(backend.fn("design_nnz")(m._handle))
+    if nnz < 0:
+        raise RuntimeError("adelie_amd: only a design kept sparse holds compressed arrays.")
+    n, p = m.rows(), m.cols()
+    c_ptr, r_ptr = np.empty(p + 1, dtype=np.int64), np.empty(n + 1, dtype=np.int64)
+    c_idx, r_idx = np.empty(nnz, dtype=np.int32), np.empty(nnz, dtype=np.int32)
+    c_val, r_val = np.empty(nnz, dtype=m.dtype), np.empty(nnz, dtype=m.dtype)
+    backend.check(backend.fn("design_csc_download")(
+        m._handle, c_ptr.ctypes.data, c_idx.ctypes.data, c_val.ctypes.data, r_ptr.ctypes.data, r_idx.ctypes.data, r_val.ctypes.data))
+    return c_ptr, c_idx, c_val, r_ptr, r_idx, r_val
+
+
+class _PhasedMatrix(_NativeMatrix):
+    """A phased-ancestry design: a design kept sparse (every method of :class:`_NativeMatrix`) built on the device, with the
+    read-only ``groups``, ``group_sizes`` and ``ancestries`` of the reference class.  The host ``csc_matrix`` that derived
+    designs (``subset``, ``concatenate``, ``standardize``, CV folds) start from is downloaded on first use, not at creation."""
+
+    _scipy_host = None
+
+    @property
+    def _scipy(self):
+        if self._scipy_host is None:
+            c_ptr, c_idx, c_val = _csc_download(self)[:3]
+            self._scipy_host = csc_matrix((c_val, c_idx, c_ptr), shape=(self._rows, self._cols))
+        return self._scipy_host
+
+    @property
+    def ancestries(self):
+        return self._ancestries
+
+    @property
+    def groups(self):
+        return self._ancestries * np.arange(self._cols // self._ancestries)
+
+    @property
+    def group_sizes(self):
+        return np.full(self._cols // self._ancestries, self._ancestries, dtype=int)
+
+
+def _phased_wrap(backend, handle, dtype, n_threads, device, A, keep=None):
+    mixin = MatrixNaiveBase64 if np.dtype(dtype) == np.float64 else MatrixNaiveBase32
+
+    class _phased(_PhasedMatrix, mixin):
+        pass
+
+    _phased.dtype = mixin.dtype
+    obj = _phased()
+    obj._init_native(backend, handle, n_threads)
+    obj._keep = keep
+    obj._kind = "sparse"
+    obj._device = device
+    obj._ancestries = int(A)
+    return obj
+
+
+def _phased_backend():
+    backend = _abi.hip_backend()
+    for name in ("design_create_snp_phased_ancestry", "design_create_snp_phased_calldata", "design_csc_download", "design_nnz"):
+        if not backend.has(name):
+            raise RuntimeError(f"{backend.path}: no adelie_hip_{name} -- rebuild the library.")
+    return backend
+
+
+def snp_phased_ancestry(io, *, dtype=np.float64, n_threads: int = 1, device: int = 0):
+    """Creates a SNP phased-ancestry design (reference ``adelie.matrix.snp_phased_ancestry``, ``matrix.py:1189-1242``,
+    ``matrix_naive_snp_phased_ancestry.ipp``): ``n`` samples, ``s`` SNPs, ``A`` ancestries, the ``(n, s * A)`` matrix whose
+    column ``j * A + a`` counts the haplotypes of SNP ``j`` mutated with ancestry ``a`` (entries 0, 1, 2).
+
+    ``io`` is an ``adelie_amd.io.snp_phased_ancestry`` handler (read here if it is not yet).  The image is decoded on the host
+    into one byte per haplotype call -- every offset and row is checked; a damaged image raises -- and those ``2 * n * s``
+    bytes are all that crosses to the device, where kernels build the column- and row-compressed arrays of a design *kept
+    sparse*: the result is what ``matrix.sparse(..., resident="csc")`` gives for the same matrix (at most two stored entries
+    per sample and SNP; 24 bytes per entry in f64, 34 with the tile-major copy of larger designs), and runs under ``grpnet``,
+    ``cv_grpnet``, ``standardize``, ``subset``, ``concatenate`` and ``diagnostic`` the same way.  With it come the limits of a
+    design kept sparse: Gaussian fits with constraints are refused, and two runs of a GLM path agree to rounding, not bit for
+    bit.  No ``(n, s * A)`` array and no host copy of the matrix is formed; derived designs download the entries when they
+    first need them.  Carries the read-only ``groups``, ``group_sizes`` and ``ancestries``."""
+    if n_threads < 1:
+        raise RuntimeError("adelie_core: n_threads must be >= 1.")
+    if not io.is_read:
+        io.read()
+    backend = _phased_backend()
+    handle = _abi.C.c_void_p()
+    buf = io._buffer
+    backend.check(backend.fn("design_create_snp_phased_ancestry")(buf.ctypes.data, buf.size, _abi.dtype_code(dtype), device, handle))
+    return _phased_wrap(backend, handle, np.dtype(dtype).type, n_threads, device, io.ancestries)
+
+
+def snp_phased_calldata(calldata, ancestries, A: int, *, dtype=np.float64, n_threads: int = 1, device: int = 0):
+    """:func:`snp_phased_ancestry` straight from the int8 ``(n, 2s)`` ``calldata`` (0 / 1) and ``ancestries`` (in ``[0, A)``)
+    that ``io.snp_phased_ancestry.write`` takes, skipping the file; the writer's errors are raised for a non-binary call, an
+    ancestry out of range and ``A >= 256``."""
+    if n_threads < 1:
+        raise RuntimeError("adelie_core: n_threads must be >= 1.")
+    calldata, ancestries = np.asarray(calldata), np.asarray(ancestries)
+    if calldata.ndim != 2 or ancestries.ndim != 2 or calldata.shape != ancestries.shape or calldata.shape[1] % 2:
+        raise RuntimeError("adelie_core: calldata and ancestries must have shape (n, 2*s).")
+    for name, a in (("calldata", calldata), ("ancestries", ancestries)):
+        if a.dtype != np.int8 and a.size and (a.min() < -128 or a.max() > 127):
+            raise RuntimeError(f"adelie_core: {name} must hold int8 values.")
+    calldata = np.asfortranarray(calldata, dtype=np.int8)
+    ancestries = np.asfortranarray(ancestries, dtype=np.int8)
+    n, s = calldata.shape[0], calldata.shape[1] // 2
+    backend = _phased_backend()
+    handle = _abi.C.c_void_p()
+    backend.check(backend.fn("design_create_snp_phased_calldata")(
+        calldata.ctypes.data, ancestries.ctypes.data, n, s, int(A), _abi.dtype_code(dtype), device, handle))
+    return _phased_wrap(backend, handle, np.dtype(dtype).type, n_threads, device, A)
+
+
 def _derived(mat, rows, cols, centers, scales, n_threads):
     if isinstance(mat, _StdView):  # derived designs of a lazily standardized design start from its materialised form
         mat = mat._materialize()

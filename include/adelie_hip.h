@@ -108,6 +108,29 @@ int adelie_hip_design_create_sparse(const int64_t* indptr, const int32_t* indice
 int adelie_hip_design_create_csc(const int64_t* indptr, const int32_t* indices, const void* values, const int64_t* row_indptr,
                                  const int32_t* row_indices, const void* row_values, int64_t n, int64_t p, int dtype, int device,
                                  adelie_hip_design** out);
+/* Additive entry points (the ABI version stays 14; callers look the symbols up).  Replace MatrixNaiveSNPPhasedAncestry{32,64}
+ * (adelie/matrix.py:1189-1242, matrix_naive_snp_phased_ancestry.ipp) over an adelie.io.snp_phased_ancestry image
+ * (io_snp_phased_ancestry.ipp:10-42,143-347): n samples, s SNPs, A < 256 ancestries, the (n, s A) matrix whose column j A + a
+ * counts the two haplotypes of SNP j that are mutated with ancestry a (entries 0, 1, 2; at most two stored per sample and
+ * SNP).  The result is a design kept sparse, exactly what adelie_hip_design_create_csc gives for the same matrix in canonical
+ * form, with everything said there (engines, reproducibility of GLM paths to rounding, constrained Gaussian fits refused).  The
+ * host decodes `snpdat` -- every offset, chunk header and row is checked against the image before it is used; a damaged image
+ * is an error and creates nothing -- into one byte per haplotype call (the ancestry, or 255); those 2 n s bytes are uploaded
+ * and the device builds the compressed arrays from counts and prefix sums (kernels_phased.hip; two builds give identical
+ * arrays), then frees the bytes.  No (n, s A) array is formed on either side. */
+int adelie_hip_design_create_snp_phased_ancestry(const void* snpdat, int64_t n_bytes, int dtype, int device, adelie_hip_design** out);
+/* Same, from the int8 (n, 2 s) column-major `calldata` (0 / 1) and `ancestries` (in [0, A), also where the call is 0, where the
+ * value is otherwise ignored) that adelie.io.snp_phased_ancestry.write takes (column 2 j + k = haplotype k of SNP j), with the
+ * writer's errors for a non-binary call, an ancestry out of range and A >= 256, without the file. */
+int adelie_hip_design_create_snp_phased_calldata(const int8_t* calldata, const int8_t* ancestries, int64_t n, int64_t s, int64_t A,
+                                                 int dtype, int device, adelie_hip_design** out);
+/* The arrays of a design kept sparse copied back to the host: the column-compressed form (indptr of cols + 1, indices and
+ * values of nnz entries, values in the design's dtype) and the row-compressed form likewise (rows + 1).  A NULL pointer skips
+ * that array.  On a standardized view these are the entries of the matrix underneath.  adelie_hip_design_nnz gives the number
+ * of stored entries, -1 for a design that is not kept sparse. */
+int adelie_hip_design_csc_download(adelie_hip_design* d, int64_t* indptr, int32_t* indices, void* values, int64_t* row_indptr,
+                                   int32_t* row_indices, void* row_values);
+int64_t adelie_hip_design_nnz(const adelie_hip_design* d);
 /* Replaces MatrixNaiveStandardize (adelie/matrix.py:1414-1533, matrix_naive_standardize.ipp), the lazy wrapper: the view
  * (x_ij - centers[j]) / scales[j]  of `src` (dense, 2-bit SNP or kept sparse) with the resident matrix untouched and shared.
  * Over a design kept sparse every operation below applies the centring / scaling as a rank-one correction in its epilogue
