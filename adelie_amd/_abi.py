@@ -219,6 +219,29 @@ S = dict(
     n_screen_reads=93, n_screen_short=94, n_filter_open_cols=95,
 )
 
+# adelie_hip_group_piece_mode
+GROUP_EIG, GROUP_ROTATE, GROUP_LAYOUT, GROUP_PANEL_SOLVE, GROUP_GRAM_PASS = range(5)
+GDESC = dict(VMAP=0, VGRP=128, VSS=256, GOFF=384, GQ=520, GSS=648, NG=776, NVAL=777, VOFF=784, VPOS=912, VQ=1040, STRIDE=1168)
+
+
+class GroupPiece(C.Structure):
+    """adelie_hip_group_piece (include/adelie_hip.h): every field 8 bytes wide."""
+    _fields_ = (
+        [(n, C.c_int64) for n in ("dtype", "mode", "count", "max_q")]
+        + [("eig", C.c_void_p), ("src", C.c_void_p), ("src_elems", C.c_int64), ("vars", C.c_void_p), ("vars_elems", C.c_int64),
+           ("V", C.c_void_p), ("V_elems", C.c_int64), ("ng", C.c_int64), ("goff", C.c_void_p), ("rvoff", C.c_void_p),
+           ("D", C.c_void_p), ("Dsrc", C.c_void_p)]
+        + [(n, C.c_int64) for n in ("ns", "nv", "nblk", "n_list")]
+        + [(n, C.c_void_p) for n in ("sbegin", "ssize", "voff", "blk_g0", "list", "desc", "Dblk", "gblk", "C")]
+        + [("ldc", C.c_int64)]
+        + [(n, C.c_void_p) for n in ("xmean", "spen", "vcol", "beta", "g", "is_active", "active_set")]
+        + [(n, C.c_double) for n in ("l1", "l2", "newton_tol", "dbeta_tol")]
+        + [(n, C.c_int64) for n in ("newton_max_iters", "max_active_size", "mark")]
+        + [("rsq", C.c_double), ("resid_sum", C.c_double), ("n_updates", C.c_int64), ("active_size", C.c_int64)]
+        + [(n, C.c_void_p) for n in ("dcol", "dlt", "dd", "st_f", "st_i")]
+    )
+
+
 # every symbol include/adelie_hip.h declares (checked by tests/test_abi.py)
 HIP_SYMBOLS = [
     "abi_version", "last_error", "device_count", "set_config",
@@ -234,7 +257,7 @@ HIP_SYMBOLS = [
     "design_create_cov_dense", "design_create_cov_lazy", "design_cov_bmul", "design_cov_mul", "design_cov_to_dense", "gaussian_cov_solve",
     "glm_cox_create", "glm_cox_destroy", "glm_cox_eval",
     "grpnet_solve", "grpnet_solve_many", "result_destroy", "result_size", "result_copy", "result_scalar", "result_error", "result_sync",
-    "bench_sweep", "filter_sweep_test", "block_build_test",
+    "bench_sweep", "filter_sweep_test", "block_build_test", "group_piece_test",
     "css_cov_solve", "css_result_destroy", "css_result_size", "css_result_copy", "css_result_scalar", "css_result_error",
     "bvls_solve", "bvls_result_destroy", "bvls_result_size", "bvls_result_copy", "bvls_result_scalar", "bvls_result_error",
     "design_create_constraint_dense", "design_adopt_constraint_dense_dev", "constraint_op",
@@ -356,6 +379,7 @@ class Backend:
         sig("bench_sweep", ci, [vp, i64, p(dbl)])
         sig("filter_sweep_test", ci, [vp, vp, vp, dbl, vp, vp, i64, vp, vp, i64, vp, dbl, vp, vp, vp])
         sig("block_build_test", ci, [vp, ci, i64, vp, vp, i64, vp, i64, vp, ci, i64, ci, vp, i64, vp, i64, vp])
+        sig("group_piece_test", ci, [p(GroupPiece), vp])
         sig("css_cov_solve", ci, [vp, p(CssArgs), p(vp)])
         sig("css_result_destroy", ci, [vp])
         sig("css_result_size", i64, [vp, ci])

@@ -537,6 +537,11 @@ constexpr int GDESC_STRIDE = 1168;
 template <class T> void launch_grp_layout(const CdGrpBlkParams<T>& p, int nblk, int32_t* desc, hipStream_t s);
 // Dptr <- R^T Dsrc R for one 128 x 128 slot (ld 128; Dsrc == Dptr: in place): `ng` groups, group k = block values [goff[k], goff[k+1]) with eigenbasis
 // (q, q) column-major at V + voff[k] (ignored for q == 1).  `scratch` holds 128 * 128 elements, private to the stream.
+// Footprint, nval = goff[ng]: all 128 rows of the first nval columns of Dsrc are read.  In place, nothing outside the leading
+// nval x nval entries changes.  Dsrc != Dptr: the leading nval x nval entries are written, and when no group is wider than 16 and
+// nval is odd also row nval of the first nval columns (the paired store), with Dsrc's entries there; every other entry of Dptr
+// keeps what it held.  Entries whose row and column groups both have q == 1 are copied bit for bit.  The result is symmetric
+// only up to rounding: the solves read it below the diagonal only.
 struct GrpRotArgs {
     int32_t ng;
     int32_t goff[129];

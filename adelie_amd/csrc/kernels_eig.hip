@@ -40,6 +40,10 @@ __global__ __launch_bounds__(64) void grp_eig_kernel(const T* __restrict__ src_b
             dg += A[i + i * q] * A[i + i * q];
             for (int j = i + 1; j < q; ++j) off += A[i + j * q] * A[i + j * q];
         }
+        // The test squares the entries as they are, without scaling the block first (Eigen's solver divides by the largest
+        // entry): it is invariant under a scaling of the block only while the squares stay in range.  Entries below ~1e-154
+        // square to zero (the sweep loop leaves with the block unrotated), above ~1e+154 to infinity (inf <= inf: it leaves as
+        // well).  Gram blocks of standardized or raw columns are nowhere near either; tests/group_checks.py covers 1e-6 .. 1e+6.
         if (off == 0 || off <= 1e-32 * (dg + off)) break;
         for (int r = 0; r < q - 1; ++r)
             for (int c = r + 1; c < q; ++c) {

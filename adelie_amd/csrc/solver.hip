@@ -1059,4 +1059,230 @@ int adelie_hip_block_build_test(adelie_hip_design* d, int mode, int64_t row_off,
     return 0;
 }
 
+// One device piece of the group engine on caller-supplied inputs, through the launcher the solver calls (tests; include/adelie_hip.h
+// has the modes and the arrays).  Everything the kernels index by is checked here against the buffers' sizes before anything is
+// launched; the outputs are written only after the last download.
+int adelie_hip_group_piece_test(const adelie_hip_group_piece* a, int64_t* info) {
+    try {
+        if (!a || !info) throw make_core_error("bad arguments.");
+        if (a->dtype != ADELIE_HIP_F64 && a->dtype != ADELIE_HIP_F32) throw make_core_error("bad dtype.");
+        constexpr int64_t G = 128, SLOT = G * G;
+        const int mode = int(a->mode);
+        const bool solve = mode == ADELIE_HIP_GROUP_PANEL_SOLVE || mode == ADELIE_HIP_GROUP_GRAM_PASS;
+        // a (q, q) eigenbasis at `off` lies inside V
+        auto v_fits = [&](int64_t off, int64_t q) { return off >= 0 && off <= a->V_elems && q * q <= a->V_elems - off; };
+        std::vector<EigDesc> edesc;
+        GrpRotArgs rot{};
+        bool rot_wide = false;
+        int64_t n_pos = 0; // list positions the pass covers
+        if (mode == ADELIE_HIP_GROUP_EIG) {
+            if (a->count < 1 || a->count > 4096 || a->max_q < 1 || a->max_q > kEigMaxQ || !a->eig || !a->src || a->src_elems < 1 ||
+                !a->vars || a->vars_elems < 1 || !a->V || a->V_elems < 1)
+                throw make_core_error("EIG: bad arguments.");
+            for (int64_t y = 0; y < a->count; ++y) {
+                const int64_t* t = a->eig + 5 * y;
+                const int64_t src = t[0], vp = t[1], vo = t[2], ld = t[3], q = t[4];
+                if (q < 1 || q > a->max_q) throw make_core_error("EIG: group size outside 1 .. max_q <= " + std::to_string(kEigMaxQ) + ".");
+                if (ld < 1 || ld > (int64_t(1) << 30) || src < 0 || src >= a->src_elems || (q - 1) * (ld + 1) >= a->src_elems - src)
+                    throw make_core_error("EIG: block outside the source.");
+                if (vp < 0 || vp > a->vars_elems || q > a->vars_elems - vp) throw make_core_error("EIG: variances outside vars.");
+                if (q > 1 && !v_fits(vo, q)) throw make_core_error("EIG: eigenbasis outside V.");
+                edesc.push_back(EigDesc{src, vp, vo, int32_t(ld), int32_t(q)});
+            }
+        } else if (mode == ADELIE_HIP_GROUP_ROTATE) {
+            if (a->ng < 1 || a->ng > G || !a->goff || !a->rvoff || !a->D || !a->V || a->V_elems < 1) throw make_core_error("ROTATE: bad arguments.");
+            if (a->goff[0] != 0) throw make_core_error("ROTATE: goff[0] must be 0.");
+            rot.ng = int32_t(a->ng);
+            for (int64_t k = 0; k < a->ng; ++k) {
+                const int64_t q = int64_t(a->goff[k + 1]) - a->goff[k];
+                if (q < 1 || a->goff[k + 1] > G) throw make_core_error("ROTATE: groups must be non-empty and hold at most 128 values together.");
+                if (q > 1 && !v_fits(a->rvoff[k], q)) throw make_core_error("ROTATE: eigenbasis outside V.");
+                rot.goff[k] = a->goff[k];
+                rot.voff[k] = q > 1 ? a->rvoff[k] : 0;
+                rot_wide = rot_wide || q > 16;
+            }
+            for (int64_t k = a->ng; k <= G; ++k) rot.goff[k] = a->goff[a->ng];
+        } else if (mode == ADELIE_HIP_GROUP_LAYOUT || solve) {
+            if (a->ns < 1 || a->ns > (1 << 20) || a->nv < 1 || a->nv > (1 << 20) || a->nblk < 1 || a->nblk > 4096 || !a->sbegin || !a->ssize ||
+                !a->voff || !a->blk_g0 || !a->desc || (a->list && a->n_list < 1))
+                throw make_core_error("bad arguments.");
+            for (int64_t ss = 0; ss < a->ns; ++ss) {
+                const int64_t b = a->sbegin[ss], q = a->ssize[ss];
+                if (q < 1 || b < 0 || b > a->nv || q > a->nv - b) throw make_core_error("a screen group lies outside the screen values.");
+                if (q > 1 && solve && !v_fits(a->voff[ss], q)) throw make_core_error("eigenbasis outside V.");
+                if (q > 1 && (a->voff[ss] < 0 || a->voff[ss] > INT32_MAX)) throw make_core_error("voff out of range.");
+            }
+            n_pos = a->list ? a->n_list : a->ns;
+            std::vector<char> seen(size_t(a->ns), 0);
+            if (a->list)
+                for (int64_t i = 0; i < a->n_list; ++i) {
+                    if (a->list[i] < 0 || a->list[i] >= a->ns) throw make_core_error("list index out of range.");
+                    if (seen[size_t(a->list[i])]++) throw make_core_error("list names a group twice.");
+                }
+            if (a->blk_g0[0] < 0) throw make_core_error("blk_g0 must start at >= 0.");
+            for (int64_t j = 0; j < a->nblk; ++j) {
+                const int64_t g0 = a->blk_g0[j], g1 = a->blk_g0[j + 1];
+                if (g1 <= g0 || g1 - g0 > G || g1 > n_pos) throw make_core_error("blk_g0 must increase, by at most 128, inside the list.");
+                int64_t nval = 0;
+                for (int64_t g = g0; g < g1; ++g) nval += a->ssize[a->list ? a->list[g] : g];
+                if (nval > G) throw make_core_error("a block holds more than 128 values.");
+            }
+            if (solve) {
+                if (!a->vars || a->vars_elems < a->nv || !a->V || a->V_elems < 1 || !a->xmean || !a->spen || !a->vcol || !a->beta || !a->is_active ||
+                    !a->active_set || !a->st_f || !a->st_i)
+                    throw make_core_error("solve: bad arguments.");
+                if (a->max_active_size < 0 || a->max_active_size > INT32_MAX) throw make_core_error("max_active_size must be >= 0.");
+                if (a->active_size < 0 || a->active_size > a->ns) throw make_core_error("active_size outside 0 .. ns.");
+                if (a->newton_max_iters < 0 || a->newton_max_iters > INT32_MAX || !(a->newton_tol >= 0) || !(a->dbeta_tol >= 0))
+                    throw make_core_error("bad Newton / change tolerances.");
+                for (int64_t i = 0; i < a->nv; ++i)
+                    if (a->vcol[i] < 0) throw make_core_error("vcol out of range.");
+                if (mode == ADELIE_HIP_GROUP_PANEL_SOLVE && (!a->Dblk || !a->gblk || !a->dcol || !a->dlt || !a->dd))
+                    throw make_core_error("PANEL_SOLVE: bad arguments.");
+                if (mode == ADELIE_HIP_GROUP_GRAM_PASS && (!a->C || !a->g || a->ldc < a->nv || a->ldc > (1 << 20)))
+                    throw make_core_error("GRAM_PASS: bad arguments.");
+            }
+        } else {
+            throw make_core_error("unknown mode.");
+        }
+        AHIP_CHECK(hipSetDevice(0));
+        hipStream_t s = nullptr;
+        int64_t launches = 0;
+        auto body = [&](auto tag) {
+            using T = decltype(tag);
+            auto up = [&](auto& buf, const auto* h, int64_t n) { buf.reserve(size_t(n)); buf.upload(h, size_t(n), s); };
+            auto down = [&](void* h, const void* dev, size_t bytes) { AHIP_CHECK(hipMemcpyAsync(h, dev, bytes, hipMemcpyDeviceToHost, s)); };
+            if (mode == ADELIE_HIP_GROUP_EIG) {
+                DevBuf<T> dsrc, dvars, dV;
+                DevBuf<EigDesc> dd;
+                up(dsrc, static_cast<const T*>(a->src), a->src_elems);
+                up(dvars, static_cast<const T*>(a->vars), a->vars_elems);
+                up(dV, static_cast<const T*>(a->V), a->V_elems);
+                up(dd, edesc.data(), int64_t(edesc.size()));
+                launch_grp_eig<T>(dsrc.p, dd.p, int(a->count), int(a->max_q), dvars.p, dV.p, s);
+                ++launches;
+                AHIP_CHECK(hipGetLastError());
+                std::vector<T> hvars(size_t(a->vars_elems)), hV(size_t(a->V_elems));
+                down(hvars.data(), dvars.p, hvars.size() * sizeof(T));
+                down(hV.data(), dV.p, hV.size() * sizeof(T));
+                AHIP_CHECK(hipStreamSynchronize(s));
+                std::memcpy(a->vars, hvars.data(), hvars.size() * sizeof(T));
+                std::memcpy(a->V, hV.data(), hV.size() * sizeof(T));
+                return;
+            }
+            if (mode == ADELIE_HIP_GROUP_ROTATE) {
+                DevBuf<T> dD, dS, dV, scratch;
+                up(dD, static_cast<const T*>(a->D), SLOT);
+                if (a->Dsrc) up(dS, static_cast<const T*>(a->Dsrc), SLOT);
+                up(dV, static_cast<const T*>(a->V), a->V_elems);
+                scratch.reserve(size_t(SLOT));
+                launch_grp_block_rotate<T>(dD.p, a->Dsrc ? dS.p : dD.p, dV.p, rot, scratch.p, s);
+                ++launches;
+                AHIP_CHECK(hipGetLastError());
+                std::vector<T> hD(static_cast<size_t>(SLOT));
+                down(hD.data(), dD.p, hD.size() * sizeof(T));
+                AHIP_CHECK(hipStreamSynchronize(s));
+                std::memcpy(a->D, hD.data(), hD.size() * sizeof(T));
+                return;
+            }
+            const int64_t nblk = a->nblk, ns = a->ns, nv = a->nv;
+            DevBuf<int32_t> dsb, dsz, dg0, dlist, ddesc, dvcol, dact, ddcol, ddidx;
+            DevBuf<int64_t> dvoff;
+            DevBuf<int8_t> disact;
+            DevBuf<T> dvars, dV, dxm, dspen, dbeta, dg, dC, dDb, dgb, ddlt, ddd, dDbuf;
+            DevBuf<CdBlkState<T>> dst;
+            up(dsb, a->sbegin, ns); up(dsz, a->ssize, ns); up(dvoff, a->voff, ns); up(dg0, a->blk_g0, nblk + 1);
+            if (a->list) up(dlist, a->list, a->n_list);
+            ddesc.reserve(size_t(nblk * GDESC_STRIDE));
+            AHIP_CHECK(hipMemsetAsync(ddesc.p, 0, size_t(nblk * GDESC_STRIDE) * sizeof(int32_t), s)); // (the unnamed gaps)
+            CdGrpBlkParams<T> p{};
+            p.nv = int32_t(nv);
+            p.sbegin = dsb.p; p.ssize = dsz.p; p.voff = dvoff.p; p.blk_g0 = dg0.p; p.list = a->list ? dlist.p : nullptr;
+            p.nblk = int32_t(nblk);
+            launch_grp_layout<T>(p, int(nblk), ddesc.p, s);
+            ++launches;
+            AHIP_CHECK(hipGetLastError());
+            std::vector<int32_t> hdesc(size_t(nblk * GDESC_STRIDE));
+            down(hdesc.data(), ddesc.p, hdesc.size() * sizeof(int32_t));
+            if (!solve) {
+                AHIP_CHECK(hipStreamSynchronize(s));
+                std::memcpy(a->desc, hdesc.data(), hdesc.size() * sizeof(int32_t));
+                return;
+            }
+            const bool panel = mode == ADELIE_HIP_GROUP_PANEL_SOLVE;
+            up(dvars, static_cast<const T*>(a->vars), nv); up(dV, static_cast<const T*>(a->V), a->V_elems);
+            up(dxm, static_cast<const T*>(a->xmean), nv); up(dspen, static_cast<const T*>(a->spen), ns);
+            up(dbeta, static_cast<const T*>(a->beta), nv); up(dvcol, a->vcol, nv); up(disact, a->is_active, ns);
+            dact.reserve(size_t(2 * ns + 1)); // a group is marked at most once: active_size <= ns on entry, at most ns more
+            dact.upload(a->active_set, size_t(ns), s);
+            CdBlkState<T> st0{};
+            st0.rsq = T(a->rsq); st0.resid_sum = T(a->resid_sum); st0.n_updates = a->n_updates; st0.active_size = int32_t(a->active_size);
+            up(dst, &st0, 1);
+            p.vars = dvars.p; p.xmean = dxm.p; p.beta = dbeta.p; p.is_active = disact.p; p.active_set = dact.p;
+            p.l1 = T(a->l1); p.l2 = T(a->l2); p.newton_tol = T(a->newton_tol); p.dbeta_tol = T(a->dbeta_tol);
+            p.newton_max_iters = int32_t(a->newton_max_iters); p.max_active_size = int32_t(a->max_active_size); p.mark = a->mark ? 1 : 0;
+            p.V = dV.p; p.spen = dspen.p; p.st = dst.p; p.vcol = dvcol.p;
+            std::vector<CdBlkState<T>> hst(size_t(panel ? nblk : 1));
+            std::vector<T> hdlt, hdd, hbeta(static_cast<size_t>(nv)), hg;
+            std::vector<int32_t> hdcol, hact(static_cast<size_t>(ns));
+            std::vector<int8_t> hisact(static_cast<size_t>(ns));
+            if (panel) {
+                up(dDb, static_cast<const T*>(a->Dblk), nblk * SLOT); up(dgb, static_cast<const T*>(a->gblk), nblk * G);
+                up(ddlt, static_cast<const T*>(a->dlt), nblk * G); up(ddd, static_cast<const T*>(a->dd), nblk * G); up(ddcol, a->dcol, nblk * G);
+                p.rot = 1; p.desc = ddesc.p;
+                for (int64_t j = 0; j < nblk; ++j) {
+                    p.Dptr = dDb.p + j * SLOT; p.gblk = dgb.p + j * G;
+                    p.dlt = ddlt.p + j * G; p.dd = ddd.p + j * G; p.dcol = ddcol.p + j * G;
+                    launch_cd_group_panel_solve<T>(p, int(j), s);
+                    ++launches;
+                    down(&hst[size_t(j)], dst.p, sizeof(CdBlkState<T>));
+                }
+                AHIP_CHECK(hipGetLastError());
+                hdlt.resize(size_t(nblk * G)); hdd.resize(size_t(nblk * G)); hdcol.resize(size_t(nblk * G));
+                down(hdlt.data(), ddlt.p, hdlt.size() * sizeof(T)); down(hdd.data(), ddd.p, hdd.size() * sizeof(T));
+                down(hdcol.data(), ddcol.p, hdcol.size() * sizeof(int32_t));
+            } else {
+                dC.reserve(size_t(a->ldc * nv)); dC.upload(static_cast<const T*>(a->C), size_t(a->ldc * nv), s);
+                up(dg, static_cast<const T*>(a->g), nv);
+                dDbuf.reserve(size_t(2 * SLOT)); ddlt.reserve(size_t(G)); ddidx.reserve(size_t(G));
+                p.C = dC.p; p.ldc = a->ldc; p.g = dg.p; p.Dbuf = dDbuf.p; p.dlt = ddlt.p; p.didx = ddidx.p; p.rot = 0;
+                launch_cd_group_block_pass<T>(p, s);
+                launches += 1 + 2 * nblk;
+                AHIP_CHECK(hipGetLastError());
+                down(&hst[0], dst.p, sizeof(CdBlkState<T>));
+                hg.resize(size_t(nv));
+                down(hg.data(), dg.p, hg.size() * sizeof(T));
+            }
+            down(hbeta.data(), dbeta.p, hbeta.size() * sizeof(T));
+            down(hact.data(), dact.p, hact.size() * sizeof(int32_t));
+            down(hisact.data(), disact.p, hisact.size());
+            AHIP_CHECK(hipStreamSynchronize(s));
+            std::memcpy(a->desc, hdesc.data(), hdesc.size() * sizeof(int32_t));
+            std::memcpy(a->beta, hbeta.data(), hbeta.size() * sizeof(T));
+            std::memcpy(a->active_set, hact.data(), hact.size() * sizeof(int32_t));
+            std::memcpy(a->is_active, hisact.data(), hisact.size());
+            if (panel) {
+                std::memcpy(a->dlt, hdlt.data(), hdlt.size() * sizeof(T));
+                std::memcpy(a->dd, hdd.data(), hdd.size() * sizeof(T));
+                std::memcpy(a->dcol, hdcol.data(), hdcol.size() * sizeof(int32_t));
+            } else {
+                std::memcpy(a->g, hg.data(), hg.size() * sizeof(T));
+            }
+            for (size_t j = 0; j < hst.size(); ++j) {
+                a->st_f[3 * j] = double(hst[j].rsq); a->st_f[3 * j + 1] = double(hst[j].resid_sum); a->st_f[3 * j + 2] = double(hst[j].cm);
+                a->st_i[4 * j] = hst[j].n_updates; a->st_i[4 * j + 1] = hst[j].active_size; a->st_i[4 * j + 2] = hst[j].status;
+                a->st_i[4 * j + 3] = hst[j].nz;
+            }
+        };
+        if (a->dtype == ADELIE_HIP_F64) body(double{});
+        else body(float{});
+        info[0] = launches;
+        info[1] = rot_wide ? 1 : 0;
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return 1;
+    }
+    return 0;
+}
+
 } // extern "C"

@@ -873,6 +873,82 @@ int adelie_hip_block_build_test(adelie_hip_design* d, int mode, int64_t row_off,
                                 const int64_t* table, int64_t count, const void* xm, int center, int64_t ldc, int strip_plain,
                                 void* out0, int64_t out0_elems, void* out1, int64_t out1_elems, int64_t* info);
 
+/* One device piece of the group engine on caller-supplied inputs, through the launcher the solver calls (tests): uploads, launches
+ * on the default stream, synchronises, downloads.  No design handle.  Every field is 8 bytes wide; value arrays (`void*`) are in
+ * `dtype`, scalars cross as double.  Everything a kernel indexes by is checked against the sizes given here before anything is
+ * launched: a bad table is refused with an error string, nothing runs and no output is written.  A block is at most 128 values.
+ *
+ * mode  ADELIE_HIP_GROUP_EIG: launch_grp_eig over `count` descriptors eig[5 y ..] = {src, vars_pos, v_off, ld, q} (1 <= q <= max_q
+ *       <= 96; the block is src[src + r + c ld]); in/out: vars, V (pre-filled by the caller).
+ *       ADELIE_HIP_GROUP_ROTATE: launch_grp_block_rotate, D <- R^T Dsrc R on 128 x 128 slots (ld 128); Dsrc null: in place.  `ng`
+ *       groups, goff [ng + 1] (goff[0] = 0, increasing, goff[ng] <= 128), rvoff [ng] into V.  in/out: D.  info[1] = 1 if a group
+ *       is wider than 16 (the global-scratch route).
+ *       ADELIE_HIP_GROUP_LAYOUT: launch_grp_layout for `nblk` blocks of the pass {blk_g0 [nblk + 1], list [n_list] or null (then
+ *       positions are screen groups), sbegin / ssize / voff [ns]}; out: desc [nblk * 1168].
+ *       ADELIE_HIP_GROUP_PANEL_SOLVE: the layout, then launch_cd_group_panel_solve for j = 0 .. nblk - 1 in order with rot = 1, no
+ *       look-ahead, on the caller's rotated blocks Dblk [nblk * 128 * 128] and gradients gblk [nblk * 128]; in/out: beta [nv],
+ *       is_active [ns], active_set [ns]; out: desc, dcol / dlt / dd [nblk * 128] (pre-filled by the caller), st_f [nblk * 3] =
+ *       {rsq, resid_sum, cm} and st_i [nblk * 4] = {n_updates, active_size, status, nz} after each block.
+ *       ADELIE_HIP_GROUP_GRAM_PASS: launch_cd_group_block_pass over the pass on the Gram matrix C (nv x nv, leading dimension
+ *       ldc) and gradient g [nv]; in/out: beta, g, is_active, active_set; out: st_f [3], st_i [4] after the pass.
+ * The solves read vars / xmean [nv], spen [ns], vcol [nv], V, the penalties l1 / l2 (already multiplied with lambda) and start
+ * from the state {rsq, resid_sum, n_updates, active_size}, status 0.  A pass names every screen group at most once.
+ * info [2]: info[0] = kernels launched, info[1] as under ROTATE (0 otherwise).
+ * The entry is additive and changes the layout of no existing structure: ADELIE_HIP_ABI_VERSION stays as it is. */
+enum adelie_hip_group_piece_mode {
+    ADELIE_HIP_GROUP_EIG = 0, ADELIE_HIP_GROUP_ROTATE = 1, ADELIE_HIP_GROUP_LAYOUT = 2, ADELIE_HIP_GROUP_PANEL_SOLVE = 3,
+    ADELIE_HIP_GROUP_GRAM_PASS = 4
+};
+typedef struct adelie_hip_group_piece {
+    int64_t dtype, mode;
+    /* EIG */
+    int64_t count, max_q;
+    const int64_t* eig;
+    const void* src;
+    int64_t src_elems;
+    /* eigenvalues and eigenbases: in/out of EIG, inputs of the other modes */
+    void* vars;
+    int64_t vars_elems;
+    void* V;
+    int64_t V_elems;
+    /* ROTATE */
+    int64_t ng;
+    const int32_t* goff;
+    const int64_t* rvoff;
+    void* D;
+    const void* Dsrc;
+    /* LAYOUT and the solves */
+    int64_t ns, nv, nblk, n_list;
+    const int32_t* sbegin;
+    const int32_t* ssize;
+    const int64_t* voff;
+    const int32_t* blk_g0;
+    const int32_t* list;
+    int32_t* desc;
+    /* the solves */
+    const void* Dblk;
+    const void* gblk;
+    const void* C;
+    int64_t ldc;
+    const void* xmean;
+    const void* spen;
+    const int32_t* vcol;
+    void* beta;
+    void* g;
+    int8_t* is_active;
+    int32_t* active_set;
+    double l1, l2, newton_tol, dbeta_tol;
+    int64_t newton_max_iters, max_active_size, mark;
+    double rsq, resid_sum;
+    int64_t n_updates, active_size;
+    int32_t* dcol;
+    void* dlt;
+    void* dd;
+    double* st_f;
+    int64_t* st_i;
+} adelie_hip_group_piece;
+int adelie_hip_group_piece_test(const adelie_hip_group_piece* a, int64_t* info);
+
 #ifdef __cplusplus
 }
 #endif
