@@ -36,7 +36,9 @@ namespace ahip {
 //                                 operations read it at the call)                                                     [A/B, tests]
 //   ADELIE_HIP_RELU_SWEEP=0|1     full sweeps of a convex-relu design as the matrix product Z^T (mask o v) (kernels_relu.hip) or off
 //                                 the expanded matrix like any dense design (default: kReluSweepDefault below; the matrix
-//                                 operations read it at the call)                                                     [A/B, tests]
+//                                 operations read it at the call); on a convex-relu design kept sparse, off Z's compressed
+//                                 columns and the packed mask (kernels_relu_sparse.hip) or off the expansion's compressed
+//                                 columns (default: kReluSparseSweepDefault)                                          [A/B, tests]
 //   ADELIE_HIP_FILTER_SWEEP=0|1   the invariance sweep of an eligible Gaussian lambda through the float32 shadow of the design
 //                                 (kernels_filter.hip) or as the full f64 sweep; same results bit for bit             [A/B, tests]
 //   ADELIE_HIP_FILTER_DEPTH=0|1   the pivot rule's threshold of a filtered sweep at the depth screen() is predicted to read
@@ -117,6 +119,11 @@ inline bool factor_sweep_on(int hook) { return hook < 0 ? kFactorSweepDefault : 
 // faster than the dense sweep on both (profiles/relu_sweep.txt).
 constexpr bool kReluSweepDefault = true;
 inline bool relu_sweep_on(int hook) { return hook < 0 ? kReluSweepDefault : hook != 0; }
+// The same hook on a convex-relu design kept sparse (kernels_relu_sparse.hip), by the same rule on both shapes of
+// scripts/bench_relu_sparse.py against the compressed-column sweep of the expansion (profiles/relu_sparse_sweep.txt).
+// On: measured faster on both, far beyond the spread.
+constexpr bool kReluSparseSweepDefault = true;
+inline bool relu_sparse_sweep_on(int hook) { return hook < 0 ? kReluSparseSweepDefault : hook != 0; }
 // Whether an eligible Gaussian lambda takes the filtered invariance sweep (float32 shadow, kernels_filter.hip) when
 // ADELIE_HIP_FILTER_SWEEP is unset.  On: the headline gains 16 ms of 252 ms per path against a parent-to-hook-off spread of
 // 0.3 ms in one interleaved job, with identical outputs (profiles/filter_sweep.txt).
@@ -548,6 +555,15 @@ struct adelie_hip_design {
     uint8_t* rmask = nullptr;
     int64_t rmask_ld = 0, r_d = 0, r_m = 0;
     int r_gated = 0;
+    // convex-relu design over a sparse base, kept sparse (adelie_hip_design_create_convex_relu_csc): kind is kCsc and the six
+    // arrays above hold the expansion; next to them a copy of Z's column-compressed entries (rz_seg: Z's column pointers refined
+    // by the row tiles of relu_sparse_shape, rz_idx, rz_val) and the mask packed to 32-bit words per row (rbits), which the
+    // structured full sweep reads (kernels_relu_sparse.hip); r_d / r_m / r_gated as above.  Owned unless alias.
+    int64_t* rz_seg = nullptr;
+    int32_t* rz_idx = nullptr;
+    void* rz_val = nullptr;
+    uint32_t* rbits = nullptr;
+    int64_t rz_nnz = 0;
     // Sweep batching across solvers that run concurrently on one resident matrix (cv_grpnet folds on alias handles): the
     // batcher object lives with the design the aliases were made from (solver.hip::SweepBatcher, created on first use).
     adelie_hip_design* batch_owner = nullptr; // nullptr: this design itself
@@ -582,6 +598,11 @@ struct adelie_hip_design {
     bool relu() const { return rmask != nullptr; }
     template <class T> ahip::ReluView<T> relu_view() const {
         return ahip::ReluView<T>{static_cast<const T*>(fz), n, fz_ld, rmask, rmask_ld, r_d, r_m, r_gated};
+    }
+    bool relu_csc() const { return rbits != nullptr; }
+    template <class T> ahip::ReluCscView<T> relu_csc_view() const {
+        const ahip::ReluSparseShape sh = ahip::relu_sparse_shape(n, r_m);
+        return ahip::ReluCscView<T>{rz_seg, rz_idx, static_cast<const T*>(rz_val), rbits, n, r_d, r_m, r_gated, sh.tile_rows, int(sh.tiles)};
     }
     template <class T> ahip::MultiView<T> multi() const {
         return ahip::MultiView<T>{static_cast<const T*>(X), nb, pb, ld, static_cast<const T*>(ones), int32_t(mK), int32_t(micpt),

@@ -194,13 +194,14 @@ void op_mul_batch(adelie_hip_design* d, const T* V, int64_t L, T* out) {
     hipStream_t s = d->stream;
     const int64_t n = d->n, p = d->p;
     constexpr int64_t KB = 8;
-    if (d->is_csc()) { // sparse: one pass over the stored entries per vector
+    if (d->is_csc()) { // sparse: one pass over the stored entries per vector (a convex-relu design: over those of Z, by the hook)
         T* dv1 = scratch<T>(d->s_n1, size_t(n));
         T* dout1 = scratch<T>(d->s_p1, size_t(p));
-        T* work1 = scratch<T>(d->s_work, size_t(raw_sweep_work_elems(*d, p, false)));
+        const bool structured = raw_sweep_structured(*d, 0, p, nullptr, false, SweepHooks::from_env());
+        T* work1 = scratch<T>(d->s_work, size_t(raw_sweep_work_elems(*d, p, structured)));
         for (int64_t l = 0; l < L; ++l) {
             AHIP_CHECK(hipMemcpyAsync(dv1, V + l * n, size_t(n) * sizeof(T), hipMemcpyHostToDevice, s));
-            raw_sweep<T>(*d, dv1, dout1, 0, p, nullptr, nullptr, nullptr, false, false, work1, s);
+            raw_sweep<T>(*d, dv1, dout1, 0, p, nullptr, nullptr, nullptr, false, structured, work1, s);
             AHIP_CHECK(hipMemcpyAsync(out + l * p, dout1, size_t(p) * sizeof(T), hipMemcpyDeviceToHost, s));
             AHIP_CHECK(hipStreamSynchronize(s));
         }
@@ -1172,6 +1173,107 @@ int adelie_hip_design_create_snp_phased_calldata(const int8_t* calldata, const i
     ABI_CATCH
 }
 
+// A convex-relu design over the kept-sparse Z, kept sparse itself (kernels_relu_sparse.hip): Z's compressed columns are copied
+// and cut at the row tiles, the host's column-major (n, m) mask bytes are uploaded and packed to words, the entries are counted
+// per (column, tile) and per row, the counts are summed on the host into cptr, the segment starts and rptr, and the fill
+// kernels write the six arrays in the canonical form adelie_hip_design_create_csc demands of its caller.  The copy of Z and
+// the mask words stay with the handle for the structured sweep.
+static void relu_csc_build(adelie_hip_design* Z, const uint8_t* mask, int64_t m, int gated, adelie_hip_design** out) {
+    const int64_t n = Z->n, dz = Z->p, znnz = Z->nnz;
+    const size_t vs = Z->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
+    const double cols = double(gated ? 1 : 2) * double(m) * double(dz);
+    if (cols > double((int64_t(1) << 31) - 64))
+        throw make_core_error("convex_relu(): the expanded design has more columns than the solver's 32-bit column indices address (" +
+                              std::to_string(double(gated ? 1 : 2) * double(m) * double(znnz)) + " stored entries at most).");
+    const int64_t P = int64_t(cols), md = m * dz;
+    const ReluSparseShape sh = relu_sparse_shape(n, m);
+    const int nt = int(sh.tiles);
+    if (dz * sh.tiles >= (int64_t(1) << 31) || sh.words > 65535)
+        throw make_core_error("convex_relu(): too many (column of mat, row tile) pairs or mask columns for one launch.");
+    DesignGuard g(new_design(n, P, Z->dtype, Z->device));
+    adelie_hip_design* d = g.get();
+    hipStream_t st = d->stream;
+    d->kind = adelie_hip_design::kCsc;
+    d->r_d = dz;
+    d->r_m = m;
+    d->r_gated = gated ? 1 : 0;
+    d->rz_nnz = znnz;
+    const size_t zn1 = size_t(std::max<int64_t>(znnz, 1));
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rz_seg), size_t(dz) * size_t(nt + 1) * sizeof(int64_t)));
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rz_idx), zn1 * sizeof(int32_t)));
+    AHIP_CHECK(hipMalloc(&d->rz_val, zn1 * vs));
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rbits), size_t(sh.words) * size_t(n) * sizeof(uint32_t)));
+    AHIP_CHECK(hipStreamSynchronize(Z->stream)); // (Z's own creation may still be in flight on its stream)
+    if (znnz) {
+        AHIP_CHECK(hipMemcpyAsync(d->rz_idx, Z->cidx, size_t(znnz) * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        AHIP_CHECK(hipMemcpyAsync(d->rz_val, Z->cval, size_t(znnz) * vs, hipMemcpyDeviceToDevice, st));
+    }
+    launch_csc_block_ptr(Z->cptr, d->rz_idx, dz, nt, sh.tile_rows, d->rz_seg, st);
+    const size_t segs = size_t(md) * size_t(nt), psegs = size_t(P) * size_t(nt);
+    DevTmp mbytes, ccnt, rcnt, cpos;
+    AHIP_CHECK(hipMalloc(&mbytes.p, size_t(n) * size_t(m)));
+    AHIP_CHECK(hipMalloc(&ccnt.p, segs * sizeof(int32_t)));
+    AHIP_CHECK(hipMalloc(&rcnt.p, size_t(n) * sizeof(int64_t)));
+    AHIP_CHECK(hipMemcpyAsync(mbytes.p, mask, size_t(n) * size_t(m), hipMemcpyHostToDevice, st));
+    launch_relu_sparse_pack(static_cast<const uint8_t*>(mbytes.p), n, m, d->rbits, st);
+    DTYPE_DISPATCH(d, launch_relu_sparse_count<T>(d->relu_csc_view<T>(), Z->rptr, static_cast<int32_t*>(ccnt.p),
+                                                  static_cast<int64_t*>(rcnt.p), st))
+    AHIP_CHECK(hipGetLastError());
+    std::vector<int32_t> col_cnt(segs);
+    std::vector<int64_t> col_pos(psegs), cptr(size_t(P) + 1), rptr(size_t(n) + 1);
+    AHIP_CHECK(hipMemcpyAsync(col_cnt.data(), ccnt.p, segs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    AHIP_CHECK(hipMemcpyAsync(rptr.data() + 1, rcnt.p, size_t(n) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    AHIP_CHECK(hipStreamSynchronize(st));
+    int64_t run = 0;
+    for (size_t k = 0; k < psegs; ++k) { // (column-major over (column, tile); the signed half repeats the counts of the first)
+        if (k % size_t(nt) == 0) cptr[k / size_t(nt)] = run;
+        col_pos[k] = run;
+        run += col_cnt[k % segs];
+    }
+    cptr[size_t(P)] = run;
+    rptr[0] = 0;
+    for (int64_t i = 0; i < n; ++i) rptr[size_t(i) + 1] += rptr[size_t(i)];
+    if (rptr[size_t(n)] != run) throw make_core_error("convex_relu(): the row and column counts of the build disagree.");
+    const int64_t nnz = d->nnz = run;
+    const size_t nz1 = size_t(std::max<int64_t>(nnz, 1));
+    auto alloc = [&](void** p, size_t bytes) {
+        if (hipMalloc(p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            throw make_core_error("convex_relu(): could not allocate the expanded design (" + std::to_string(n) + " x " + std::to_string(P) +
+                                  ", " + std::to_string(nnz) + " stored entries) on the device.");
+        }
+    };
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cptr), size_t(P + 1) * sizeof(int64_t)));
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rptr), size_t(n + 1) * sizeof(int64_t)));
+    alloc(reinterpret_cast<void**>(&d->cidx), nz1 * sizeof(int32_t));
+    alloc(&d->cval, nz1 * vs);
+    alloc(reinterpret_cast<void**>(&d->rcol), nz1 * sizeof(int32_t));
+    alloc(&d->rval, nz1 * vs);
+    AHIP_CHECK(hipMalloc(&cpos.p, psegs * sizeof(int64_t)));
+    AHIP_CHECK(hipMemcpyAsync(d->cptr, cptr.data(), size_t(P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    AHIP_CHECK(hipMemcpyAsync(d->rptr, rptr.data(), size_t(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    AHIP_CHECK(hipMemcpyAsync(cpos.p, col_pos.data(), psegs * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    DTYPE_DISPATCH(d, launch_relu_sparse_fill<T>(d->relu_csc_view<T>(), Z->rptr, Z->rcol, static_cast<const T*>(Z->rval),
+                                                 static_cast<const int64_t*>(cpos.p), d->rptr, d->cidx, static_cast<T*>(d->cval), d->rcol,
+                                                 static_cast<T*>(d->rval), st))
+    AHIP_CHECK(hipGetLastError());
+    AHIP_CHECK(hipStreamSynchronize(st)); // (the mask bytes and the segment starts are freed on the way out)
+    csc_finish(d);
+    AHIP_CHECK(hipStreamSynchronize(st));
+    *out = g.release();
+}
+
+int adelie_hip_design_create_convex_relu_csc(adelie_hip_design* Z, const uint8_t* mask, int64_t m, int gated, adelie_hip_design** out) {
+    ABI_TRY
+    if (!Z || !out || (!mask && m > 0)) throw make_core_error("null argument.");
+    if (!Z->is_csc() || Z->std_center)
+        throw make_core_error("convex_relu(): mat must be a resident design kept sparse without a standardized view on it.");
+    if (m < 0) throw make_core_error("mask must be (n, m) where mat is (n, d).");
+    set_device(Z);
+    relu_csc_build(Z, mask, m, gated, out);
+    ABI_CATCH
+}
+
 int adelie_hip_design_csc_download(adelie_hip_design* d, int64_t* indptr, int32_t* indices, void* values, int64_t* row_indptr,
                                    int32_t* row_indices, void* row_values) {
     ABI_TRY
@@ -1580,6 +1682,7 @@ int adelie_hip_design_alias(adelie_hip_design* src, adelie_hip_design** out) {
     d->fz = src->fz; d->fz_ld = src->fz_ld; d->fblk = src->fblk; d->fchunk = src->fchunk; d->f_nchunk = src->f_nchunk;
     d->f_outer = src->f_outer; // (a factor design's alias keeps the structure: CV folds sweep the same way)
     d->rmask = src->rmask; d->rmask_ld = src->rmask_ld; d->r_d = src->r_d; d->r_m = src->r_m; d->r_gated = src->r_gated;
+    d->rz_seg = src->rz_seg; d->rz_idx = src->rz_idx; d->rz_val = src->rz_val; d->rbits = src->rbits; d->rz_nnz = src->rz_nnz;
     d->alias = true;
     d->batch_owner = src->batch_owner ? src->batch_owner : src;
     *out = g.release();
@@ -1786,6 +1889,7 @@ int adelie_hip_design_destroy(adelie_hip_design* d) {
         (void)hipFree(d->tptr); (void)hipFree(d->trow); (void)hipFree(d->tval);
         (void)hipFree(d->fz); (void)hipFree(d->fblk); (void)hipFree(d->fchunk);
         (void)hipFree(d->rmask);
+        (void)hipFree(d->rz_seg); (void)hipFree(d->rz_idx); (void)hipFree(d->rz_val); (void)hipFree(d->rbits);
     }
     if (d->std_owned) { (void)hipFree(d->std_center); (void)hipFree(d->std_iscale); }
     if (d->ones) (void)hipFree(d->ones);

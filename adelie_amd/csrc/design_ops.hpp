@@ -18,14 +18,18 @@ const T* snp_impute(const adelie_hip_design& d) { return static_cast<const T*>(d
 
 // ---- sweep: out[k] = x_col(k) . v (kernels.hpp: launch_sweep) -----------------------------------------------------------------
 // Whether a sweep takes the structured kernel of a one-hot / interaction design (kernels_factor.hip) or of a convex-relu design
-// (kernels_relu.hip), which only do the plain full sweep.  `hooks`: the ADELIE_HIP_FACTOR_SWEEP / ADELIE_HIP_RELU_SWEEP values
+// (kernels_relu.hip; kept sparse: kernels_relu_sparse.hip), which only do the plain full sweep.  `hooks`: the ADELIE_HIP_FACTOR_SWEEP / ADELIE_HIP_RELU_SWEEP values
 // the caller goes by (a solve reads them once when it starts, the matrix operations at the call).
 inline bool raw_sweep_structured(const adelie_hip_design& d, int64_t c0, int64_t ncols, const int32_t* cols, bool square,
                                  const SweepHooks& hooks) {
-    if (!d.is_dense() || d.is_std_view() || cols || c0 != 0 || ncols != d.p || square) return false;
+    if (cols || c0 != 0 || ncols != d.p || square) return false;
+    // a convex-relu design kept sparse (kernels_relu_sparse.hip); a standardized view of one sweeps its compressed columns
+    if (d.is_csc()) return d.relu_csc() && !d.std_center && relu_sparse_sweep_on(hooks.relu);
+    if (!d.is_dense() || d.is_std_view()) return false;
     return (d.factor() && factor_sweep_on(hooks.factor)) || (d.relu() && relu_sweep_on(hooks.relu));
 }
 inline int64_t raw_sweep_work_elems(const adelie_hip_design& d, int64_t ncols, bool structured) {
+    if (structured && d.relu_csc()) return relu_sparse_sweep_work_elems(d.n, d.r_d, d.r_m);
     if (structured && d.relu()) return relu_sweep_work_elems(d.n, d.r_d, d.r_m);
     if (structured) return factor_sweep_work_elems(d.n, d.p, d.f_nchunk);
     return d.is_csc() ? sweep_work_elems_csc(d.sp_parts(), ncols) : sweep_work_elems(d.n, ncols);
@@ -33,7 +37,8 @@ inline int64_t raw_sweep_work_elems(const adelie_hip_design& d, int64_t ncols, b
 template <class T>
 void raw_sweep(const adelie_hip_design& d, const T* v, T* out, int64_t c0, int64_t ncols, const int32_t* cols, const T* sub_scale,
                const T* sub_vec, bool square, bool structured, T* work, hipStream_t s) {
-    if (structured && d.relu()) launch_sweep_relu<T>(d.relu_view<T>(), v, out, sub_scale, sub_vec, work, s);
+    if (structured && d.relu_csc()) launch_sweep_relu_sparse<T>(d.relu_csc_view<T>(), v, out, sub_scale, sub_vec, work, s);
+    else if (structured && d.relu()) launch_sweep_relu<T>(d.relu_view<T>(), v, out, sub_scale, sub_vec, work, s);
     else if (structured) launch_sweep_factor<T>(d.factor_view<T>(), v, out, sub_scale, sub_vec, work, s);
     else if (d.is_dense()) launch_sweep<T>(d.dense<T>(), v, out, c0, ncols, cols, sub_scale, sub_vec, square, work, s);
     else if (d.is_snp()) launch_sweep_snp<T>(d.snp(), snp_impute<T>(d), v, out, c0, ncols, cols, sub_scale, sub_vec, square, work, s);

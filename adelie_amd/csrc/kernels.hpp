@@ -5,6 +5,7 @@
 #include <cstdint>
 #include "gram_shape.hpp"
 #include "relu_shape.hpp"
+#include "relu_sparse_shape.hpp"
 #include "shadow_kind_host.hpp"
 
 namespace ahip {
@@ -827,6 +828,38 @@ template <class T> void launch_relu_expand(const ReluView<T>& F, T* X, int64_t l
 // is a zero of the expanded design but poisons the product.
 template <class T>
 void launch_sweep_relu(const ReluView<T>& F, const T* v, T* out, const T* sub_scale, const T* sub_vec, T* work, hipStream_t s);
+
+// ---- convex-relu designs over a sparse base matrix, kept sparse (kernels_relu_sparse.hip) -----------------------------------------
+// The same matrix as above with Z held by compressed columns: column sgn (m d) + j_m d + j_d stores +-Z[i, j_d] at the rows where
+// Z stores an entry and mask[i, j_m] is set.  Rows are cut into the tiles of relu_sparse_shape(n, m), gates into words of
+// kReluSpWordBits bits; one wavefront owns a (column of Z, tile, word).
+template <class T>
+struct ReluCscView {
+    const int64_t* seg;   // (d, nt + 1): seg[j (nt + 1) + t] = first entry of Z's column j in tile t, [.. + nt] = the column's end
+    const int32_t* zidx;  // Z's row indices, rows ascending inside a column
+    const T* zval;        // Z's values
+    const uint32_t* bits; // the mask packed by row: bit g of bits[w n + i] = mask[i, 32 w + g]; bits beyond m are zero
+    int64_t n, d, m;
+    int gated;
+    int64_t tile_rows;
+    int nt;
+};
+// bits (words * n words, word-major) from the column-major (n, m) mask bytes on the device
+void launch_relu_sparse_pack(const uint8_t* mask, int64_t n, int64_t m, uint32_t* bits, hipStream_t s);
+// col_cnt[(j_m d + j_d) nt + t] = stored entries of column j_m d + j_d of the unsigned half in tile t (m d nt counts);
+// row_cnt[i] = stored entries of row i of the whole design.  zrptr: Z's row pointers.
+template <class T>
+void launch_relu_sparse_count(const ReluCscView<T>& F, const int64_t* zrptr, int32_t* col_cnt, int64_t* row_cnt, hipStream_t s);
+// col_pos (P nt, the exclusive prefix sum of the counts of all P columns in (column, tile) order) and rptr (that of row_cnt)
+// place every entry: fills cidx / cval and rcol / rval in canonical form.  Z's row-compressed arrays are read for the rows.
+template <class T>
+void launch_relu_sparse_fill(const ReluCscView<T>& F, const int64_t* zrptr, const int32_t* zrcol, const T* zrval, const int64_t* col_pos,
+                             const int64_t* rptr, int32_t* cidx, T* cval, int32_t* rcol, T* rval, hipStream_t s);
+// The full sweep out[c] = sum_i X[i, c] v[i] - (sub_vec ? sub_scale[0] * sub_vec[c] : 0) over all P columns read off Z's nnz(Z)
+// entries, the mask words and v; fixed summation order (tile partials in `work`, relu_sparse_sweep_work_elems(n, d, m)
+// elements), the signed half the negation of the first.  A masked-out entry is skipped by a select, whatever Z and v hold.
+template <class T>
+void launch_sweep_relu_sparse(const ReluCscView<T>& F, const T* v, T* out, const T* sub_scale, const T* sub_vec, T* work, hipStream_t s);
 
 // ---- phased-ancestry SNP designs (kernels_phased.hip): the arrays of a CscView built from the (n, 2 s) code table -------------
 // `code` is the column-major uint8 table of phased_decode_host.hpp (ancestry of a mutation, or 255); the design has s A columns,

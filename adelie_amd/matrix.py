@@ -1061,29 +1061,124 @@ class _ReluMatrix(_NativeMatrix):
         return self._relu_gated
 
 
-def convex_relu(mat, mask, *, gated: bool = False, copy: bool = False, n_threads: int = 1, device: int = 0):
+def _relu_expand_sparse(Z_csc, mask, gated):
+    """The canonical ``csc_matrix`` of the expansion over a sparse ``Z``, in the dtype of ``Z``: column
+    ``sgn * (m * d) + j_m * d + j_d`` stores ``+-Z[i, j_d]`` at the rows where ``Z`` stores a (non-zero) entry and ``mask[i, j_m]``
+    is set -- what the device builder of ``convex_relu(..., resident="csc")`` writes.  Needs no device."""
+    import scipy.sparse as _sp
+
+    Z = csc_matrix(Z_csc, copy=True)
+    Z.sum_duplicates()
+    Z.eliminate_zeros()
+    Z.sort_indices()
+    mask = np.asarray(mask, dtype=bool)
+    n, d = Z.shape
+    m = mask.shape[1]
+    ptr = np.asarray(Z.indptr, dtype=np.int64)
+    blocks = []
+    for j_m in range(m):
+        keep = mask[Z.indices, j_m]  # per stored entry of Z, in column order
+        indptr = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])[ptr]  # kept entries before each column's start
+        blocks.append(csc_matrix((Z.data[keep], Z.indices[keep], indptr), shape=(n, d)))
+    Y = _sp.hstack(blocks, format="csc") if blocks else csc_matrix((n, 0), dtype=Z.dtype)
+    out = Y if gated else _sp.hstack([Y, -Y], format="csc")
+    out = csc_matrix(out, dtype=Z.dtype)
+    out.sort_indices()
+    return out
+
+
+# the row tiles of the builder and of the structured sweep over a sparse base, restated from csrc/relu_sparse_shape.hpp
+# (tests/test_relu_sparse_host.py compares the two)
+_RELU_SP_WORD_BITS, _RELU_SP_TILE_UNIT, _RELU_SP_MAX_TILES = 32, 4096, 16
+
+
+def _relu_sparse_sweep_shape(n, m):
+    """``(tile_rows, tiles, words)`` of a convex-relu design kept sparse (``relu_sparse_shape``,
+    ``csrc/relu_sparse_shape.hpp``).  Needs no device."""
+    span = _RELU_SP_TILE_UNIT * _RELU_SP_MAX_TILES
+    tile_rows = _RELU_SP_TILE_UNIT * max(1, (n + span - 1) // span)
+    return tile_rows, max(1, (n + tile_rows - 1) // tile_rows), (m + _RELU_SP_WORD_BITS - 1) // _RELU_SP_WORD_BITS
+
+
+class _ReluSparseMatrix(_ReluMatrix):
+    """A convex-relu design over a sparse base: a design kept sparse (every method of :class:`_NativeMatrix`) built on the
+    device, with ``_mask_shape`` and ``_gated``.  The host ``csc_matrix`` that derived designs (``subset``, ``concatenate``,
+    ``standardize``, CV folds) start from is downloaded on first use, not at creation."""
+
+    _scipy_host = None
+
+    @property
+    def _scipy(self):
+        if self._scipy_host is None:
+            c_ptr, c_idx, c_val = _csc_download(self)[:3]
+            self._scipy_host = csc_matrix((c_val, c_idx, c_ptr), shape=(self._rows, self._cols))
+        return self._scipy_host
+
+
+_RELU_MAT_ERROR = ("adelie_amd: mat must be an (n, d) array, a csc_matrix, a resident dense design or a resident design kept "
+                   "sparse (no standardized view, SNP design or multi-response view).")
+
+
+def convex_relu(mat, mask, *, gated: bool = False, copy: bool = False, n_threads: int = 1, device: int = 0,
+                resident: str = "dense"):
     """Feature matrix of the convex reformulation of a two-layer ReLU network (reference ``adelie.matrix.convex_relu``,
     ``matrix.py:390-560``, ``matrix_naive_convex_gated_relu.ipp``, ``matrix_naive_convex_relu.ipp``).  From the base matrix
     ``Z (n, d)`` and the boolean ``mask (n, m)`` whose columns are the diagonals of ``D_1 .. D_m``: ``Y = [D_1 Z, ..., D_m Z]``
     with ``m * d`` columns when ``gated``, else ``[Y, -Y]`` with ``2 * m * d``.  Column ``sgn * (m * d) + j_m * d + j_d`` holds
     ``Z[i, j_d]`` where ``mask[i, j_m]`` and zero elsewhere (whatever ``Z`` holds there), negated for ``sgn = 1``.
 
-    ``mat`` is anything :func:`dense` takes (an ndarray -- a C-ordered one warns as there --, a resident torch tensor), a
-    resident dense design, or a ``scipy.sparse.csc_matrix``, which is densified first (``Z`` is small beside the expansion,
-    and the expansion is dense anyway).  Only ``Z`` and the mask cross to the device; the ``n x P`` design is expanded there
-    by one kernel and lives in HBM next to copies of both: ``n*P + n*d`` values and ``n*m`` bytes (an f64 design that a
-    Gaussian path filters gets its float32 shadow on top, like any dense f64 design).  The result is an ordinary dense
-    design of the dtype of ``Z`` (it works under ``grpnet``, ``cv_grpnet``, ``standardize``, ``subset``, ``concatenate``,
-    ``kronecker_eye``, ``diagnostic`` ...) with read-only ``_mask_shape`` and ``_gated``; with ``ADELIE_HIP_RELU_SWEEP=1`` its
-    full gradient sweeps are the ``(d, m)`` matrix product ``Z^T (mask o v)`` on the matrix cores instead of a pass over the
-    expanded matrix (``Z`` must be finite for that).  ``copy`` and ``n_threads`` are accepted for parity."""
+    ``resident="dense"`` (the default): ``mat`` is anything :func:`dense` takes (an ndarray -- a C-ordered one warns as there
+    --, a resident torch tensor), a resident dense design, or a ``scipy.sparse.csc_matrix``, which is densified first.  Only
+    ``Z`` and the mask cross to the device; the ``n x P`` design is expanded there by one kernel and lives in HBM next to
+    copies of both: ``n*P + n*d`` values and ``n*m`` bytes (an f64 design that a Gaussian path filters gets its float32 shadow
+    on top, like any dense f64 design).  The result is an ordinary dense design of the dtype of ``Z`` (it works under
+    ``grpnet``, ``cv_grpnet``, ``standardize``, ``subset``, ``concatenate``, ``kronecker_eye``, ``diagnostic`` ...) with
+    read-only ``_mask_shape`` and ``_gated``; with ``ADELIE_HIP_RELU_SWEEP=1`` its full gradient sweeps are the ``(d, m)``
+    matrix product ``Z^T (mask o v)`` on the matrix cores instead of a pass over the expanded matrix (``Z`` must be finite for
+    that).
+
+    ``resident="csc"`` with a ``scipy.sparse`` matrix, or a resident design kept sparse as ``mat`` whatever ``resident`` says
+    (``matrix.sparse(..., resident="csc")``; a standardized view, an SNP design and a multi-response view are refused): the
+    expansion stays sparse (the reference's ``MatrixNaiveConvexReluSparse`` / ``MatrixNaiveConvexGatedReluSparse``).  ``Z`` is
+    pruned of explicit zeros, sorted and its duplicates summed (a resident design is taken as it is stored); column ``sgn * (m * d) + j_m * d + j_d`` stores ``+-Z[i, j_d]`` at the rows where
+    ``Z`` stores an entry and ``mask[i, j_m]`` is set, ``(1 if gated else 2) * sum_i popcount(mask[i]) * nnz(Z[i])`` entries
+    in all, written on the device straight into the compressed arrays of a design kept sparse; no ``n x P`` array and no host
+    copy of the expansion is made (the host ``csc_matrix`` that derived designs start from is downloaded on first use).  The
+    result has ``_kind == "sparse"``: every method, engine, view and limit of ``matrix.sparse(..., resident="csc")``, and
+    ``_mask_shape`` / ``_gated``; ``subset`` / ``concatenate`` / ``standardize`` give plain sparse designs.  Next to the
+    arrays the design owns a copy of ``Z``'s compressed columns and the mask packed to 32-bit words per row; its
+    full gradient sweeps read those -- ``nnz(Z)`` entries -- instead of the expansion's (``ADELIE_HIP_RELU_SWEEP=0`` sweeps
+    the expansion's compressed columns; ``profiles/relu_sparse_sweep.txt``).  ``resident="csc"`` with a dense array or dense design raises: ``Z``
+    has no compressed arrays.
+
+    ``copy`` and ``n_threads`` are accepted for parity."""
     if n_threads < 1:
         raise RuntimeError("adelie_core: n_threads must be >= 1.")
+    if resident not in ("dense", "csc"):
+        raise ValueError("resident must be one of 'dense' or 'csc'.")
+    keep_sparse = False
     if isinstance(mat, _NativeMatrix):
-        if (getattr(mat, "_kind", None) != "dense" or isinstance(mat, (_MultiView, _StdView))):
-            raise RuntimeError("adelie_amd: mat must be an (n, d) array, a csc_matrix or a resident dense design.")
+        if isinstance(mat, (_MultiView, _StdView)):
+            raise RuntimeError(_RELU_MAT_ERROR)
+        kind = getattr(mat, "_kind", None)
+        if kind == "sparse" and getattr(mat, "_std", None) is None:
+            keep_sparse = True
+        elif kind != "dense":
+            raise RuntimeError(_RELU_MAT_ERROR)
+        elif resident == "csc":
+            raise RuntimeError("adelie_amd: resident='csc' needs a scipy.sparse matrix or a resident design kept sparse: "
+                               "a dense design has no compressed arrays.")
         Z = mat
+    elif issparse(mat) and resident == "csc":
+        mat = csc_matrix(mat, copy=True)
+        mat.sum_duplicates()
+        mat.eliminate_zeros()  # (an explicit zero of Z is no entry of the expansion)
+        Z = sparse(mat, method="naive", n_threads=n_threads, device=device, resident="csc")
+        keep_sparse = True
     else:
+        if resident == "csc":
+            raise RuntimeError("adelie_amd: resident='csc' needs a scipy.sparse matrix or a resident design kept sparse: "
+                               "a dense array has no compressed arrays.")
         if issparse(mat):
             mat = np.asfortranarray(csc_matrix(mat).toarray())
         Z = dense(mat, method="naive", n_threads=n_threads, device=device)
@@ -1095,16 +1190,41 @@ def convex_relu(mat, mask, *, gated: bool = False, copy: bool = False, n_threads
     m = mask.shape[1]
     P = (1 if gated else 2) * m * d
     itemsize = np.dtype(Z.dtype).itemsize
+    backend = Z._backend
+    mixin = MatrixNaiveBase64 if np.dtype(Z.dtype) == np.float64 else MatrixNaiveBase32
+    if keep_sparse:
+        if P >= 2 ** 31 - 64:
+            znnz = int(backend.fn("design_nnz")(Z._handle))
+            raise RuntimeError(f"adelie_amd: the expanded design would have {P} columns "
+                               f"({(1 if gated else 2) * m * znnz} stored entries at most): more than the solver's "
+                               "32-bit column indices address.")
+        for name in ("design_create_convex_relu_csc", "design_csc_download", "design_nnz"):
+            if not backend.has(name):
+                raise RuntimeError(f"{backend.path}: no adelie_hip_{name} -- rebuild the library.")
+        handle = _abi.C.c_void_p()
+        backend.check(backend.fn("design_create_convex_relu_csc")(Z._handle, mask.view(np.uint8).ctypes.data, m, int(bool(gated)),
+                                                                  handle))
+
+        class _relu_sparse(_ReluSparseMatrix, mixin):
+            pass
+
+        _relu_sparse.dtype = mixin.dtype
+        obj = _relu_sparse()
+        obj._init_native(backend, handle, n_threads)
+        obj._keep = None  # (the device copies of Z's columns and of the mask are the design's own)
+        obj._kind = "sparse"
+        obj._device = getattr(Z, "_device", device)
+        obj._relu_mask_shape = (n, m)
+        obj._relu_gated = bool(gated)
+        return obj
     if P >= 2 ** 31 - 64:
         raise RuntimeError(f"adelie_amd: the expanded design would have {P} columns "
                            f"({n * float(P) * itemsize / 2 ** 30:.2f} GiB of values): more than the solver's "
                            "32-bit column indices address.")
-    backend = Z._backend
     if not backend.has("design_create_convex_relu"):
         raise RuntimeError(f"{backend.path}: no adelie_hip_design_create_convex_relu -- rebuild the library.")
     handle = _abi.C.c_void_p()
     backend.check(backend.fn("design_create_convex_relu")(Z._handle, mask.view(np.uint8).ctypes.data, m, int(bool(gated)), handle))
-    mixin = MatrixNaiveBase64 if np.dtype(Z.dtype) == np.float64 else MatrixNaiveBase32
 
     class _relu(_ReluMatrix, mixin):
         pass

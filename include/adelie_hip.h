@@ -228,6 +228,15 @@ int adelie_hip_design_create_interaction(adelie_hip_design* Z, const int64_t* pa
  * design owns next to the expanded matrix is a column-major copy of Z and of the mask (n P + n d values and n m bytes), which
  * the structured full sweep (ADELIE_HIP_RELU_SWEEP, kernels_relu.hip) multiplies on the matrix cores. */
 int adelie_hip_design_create_convex_relu(adelie_hip_design* Z, const uint8_t* mask, int64_t m, int gated, adelie_hip_design** out);
+/* Additive entry point (the ABI version stays 14; callers look the symbol up).  The same design over a Z kept sparse
+ * (adelie_hip_design_create_csc or an alias of one; a standardized view and every other kind of handle are refused), kept sparse
+ * itself: column sgn (m d) + j_m d + j_d stores +-Z[i, j_d] at the rows where Z stores an entry and mask[i, j_m] != 0, so the
+ * result holds (gated ? 1 : 2) sum_i popcount(mask[i, :]) nnz(Z[i, :]) entries and no n x P array is ever formed.  Built on the
+ * device into the canonical six arrays of a design kept sparse (kernels_relu_sparse.hip; two builds give identical arrays), with
+ * every operation, view and limit of adelie_hip_design_create_csc.  Next to the arrays the handle owns a copy of Z's compressed
+ * columns and the mask packed to 32-bit words per row, which the structured full sweep (ADELIE_HIP_RELU_SWEEP) reads instead of
+ * the expansion.  `mask` is the host's (n, m) column-major bytes. */
+int adelie_hip_design_create_convex_relu_csc(adelie_hip_design* Z, const uint8_t* mask, int64_t m, int gated, adelie_hip_design** out);
 /* The reference's read-only `groups` / `group_sizes` of the two classes above (outer[:-1] and diff(outer),
  * matrix_naive_one_hot.hpp / matrix_naive_interaction.hpp): copies min(G, cap) entries into each non-NULL array and returns the
  * number of blocks G, or -1 when `d` was not made by one of the two constructors (or is not an alias of such a design). */
