@@ -2,12 +2,14 @@
 // (include/adelie_hip.h documents which reference method each entry point replaces.)
 #include <atomic>
 #include <cstdio>
+#include <functional>
 #include <memory>
+#include <mutex>
 #include "common.hpp"
 #include "design_ops.hpp"
+#include "csc_build_host.hpp"
 #include "phased_decode_host.hpp"
-
-#include <mutex>
+#include "snp_decode_host.hpp"
 
 using namespace ahip;
 
@@ -35,6 +37,12 @@ void check_device(int device) {
     AHIP_CHECK(hipSetDevice(device));
 }
 
+// a temporary device block, freed on every way out
+struct DevTmp {
+    void* p = nullptr;
+    ~DevTmp() { (void)hipFree(p); }
+};
+
 template <class T>
 void create_dense_t(adelie_hip_design* d, const void* src, bool src_on_device, int order) {
     constexpr int64_t kAlign = 32; // elements: columns start 128/256-byte aligned
@@ -60,16 +68,15 @@ void create_dense_t(adelie_hip_design* d, const void* src, bool src_on_device, i
     } else {
         // row-major source: stage (if on host) and transpose on device
         const T* rsrc = static_cast<const T*>(src);
-        T* tmp = nullptr;
+        DevTmp tmp;
         if (!src_on_device) {
-            AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&tmp), size_t(n) * size_t(p) * sizeof(T)));
-            AHIP_CHECK(hipMemcpyAsync(tmp, src, size_t(n) * size_t(p) * sizeof(T), hipMemcpyHostToDevice, d->stream));
-            rsrc = tmp;
+            AHIP_CHECK(hipMalloc(&tmp.p, size_t(n) * size_t(p) * sizeof(T)));
+            AHIP_CHECK(hipMemcpyAsync(tmp.p, src, size_t(n) * size_t(p) * sizeof(T), hipMemcpyHostToDevice, d->stream));
+            rsrc = static_cast<const T*>(tmp.p);
         }
         AHIP_CHECK(hipMemsetAsync(X, 0, size_t(ld) * size_t(p) * sizeof(T), d->stream));
         launch_transpose<T>(rsrc, n, p, X, ld, d->stream);
         AHIP_CHECK(hipStreamSynchronize(d->stream));
-        if (tmp) (void)hipFree(tmp);
     }
     AHIP_CHECK(hipStreamSynchronize(d->stream));
 }
@@ -86,24 +93,17 @@ void create_sparse_t(adelie_hip_design* d, const int64_t* indptr, const int32_t*
     d->ld = ld;
     d->owned = true;
     AHIP_CHECK(hipMemsetAsync(X, 0, size_t(ld) * size_t(p) * sizeof(T), d->stream));
-    int64_t* dptr = nullptr;
-    int32_t* didx = nullptr;
-    T* dval = nullptr;
-    auto release = [&] { (void)hipFree(dptr); (void)hipFree(didx); (void)hipFree(dval); };
-    try {
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dptr), size_t(p + 1) * sizeof(int64_t)));
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&didx), size_t(std::max<int64_t>(nnz, 1)) * sizeof(int32_t)));
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dval), size_t(std::max<int64_t>(nnz, 1)) * sizeof(T)));
-        AHIP_CHECK(hipMemcpyAsync(dptr, indptr, size_t(p + 1) * sizeof(int64_t), hipMemcpyHostToDevice, d->stream));
-        AHIP_CHECK(hipMemcpyAsync(didx, indices, size_t(nnz) * sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
-        AHIP_CHECK(hipMemcpyAsync(dval, values, size_t(nnz) * sizeof(T), hipMemcpyHostToDevice, d->stream));
-        launch_csc_scatter<T>(dptr, didx, dval, n, p, X, ld, d->stream);
-        AHIP_CHECK(hipStreamSynchronize(d->stream));
-    } catch (...) {
-        release();
-        throw;
-    }
-    release();
+    const size_t nz1 = size_t(std::max<int64_t>(nnz, 1));
+    DevTmp dptr, didx, dval;
+    AHIP_CHECK(hipMalloc(&dptr.p, size_t(p + 1) * sizeof(int64_t)));
+    AHIP_CHECK(hipMalloc(&didx.p, nz1 * sizeof(int32_t)));
+    AHIP_CHECK(hipMalloc(&dval.p, nz1 * sizeof(T)));
+    AHIP_CHECK(hipMemcpyAsync(dptr.p, indptr, size_t(p + 1) * sizeof(int64_t), hipMemcpyHostToDevice, d->stream));
+    AHIP_CHECK(hipMemcpyAsync(didx.p, indices, size_t(nnz) * sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
+    AHIP_CHECK(hipMemcpyAsync(dval.p, values, size_t(nnz) * sizeof(T), hipMemcpyHostToDevice, d->stream));
+    launch_csc_scatter<T>(static_cast<const int64_t*>(dptr.p), static_cast<const int32_t*>(didx.p), static_cast<const T*>(dval.p), n, p, X, ld,
+                          d->stream);
+    AHIP_CHECK(hipStreamSynchronize(d->stream));
 }
 
 // Designs alive in this process.  When the last one goes, the device blocks that finished solves parked for re-use (DevPool,
@@ -132,38 +132,6 @@ struct DesignDeleter {
     void operator()(adelie_hip_design* d) const { adelie_hip_design_destroy(d); }
 };
 using DesignGuard = std::unique_ptr<adelie_hip_design, DesignDeleter>;
-// a temporary device block, freed on every way out
-struct DevTmp {
-    void* p = nullptr;
-    ~DevTmp() { (void)hipFree(p); }
-};
-
-void create_snp_from_calldata(adelie_hip_design* d, const int8_t* calldata, const double* impute) {
-    const int64_t n = d->n, p = d->p;
-    d->kind = adelie_hip_design::kSnp;
-    d->ldb = (((n + 3) / 4 + 127) / 128) * 128;
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bits), size_t(d->ldb) * size_t(p)));
-    int8_t* tmp = nullptr;
-    // stage the calldata in panels of columns to bound the temporary
-    const int64_t panel = std::max<int64_t>(1, (int64_t(1) << 28) / n);
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&tmp), size_t(n) * size_t(std::min(panel, p))));
-    for (int64_t j0 = 0; j0 < p; j0 += panel) {
-        const int64_t pc = std::min(panel, p - j0);
-        // hipMemcpyDefault: the calldata may live on the host or (generated in place) on this device
-        AHIP_CHECK(hipMemcpyAsync(tmp, calldata + j0 * n, size_t(n) * size_t(pc), hipMemcpyDefault, d->stream));
-        launch_pack_snp(tmp, n, pc, d->bits + j0 * d->ldb, d->ldb, d->stream);
-        AHIP_CHECK(hipStreamSynchronize(d->stream));
-    }
-    (void)hipFree(tmp);
-    if (d->dtype == ADELIE_HIP_F64) {
-        AHIP_CHECK(hipMalloc(&d->impute, size_t(p) * sizeof(double)));
-        AHIP_CHECK(hipMemcpy(d->impute, impute, size_t(p) * sizeof(double), hipMemcpyHostToDevice));
-    } else {
-        std::vector<float> f(impute, impute + p);
-        AHIP_CHECK(hipMalloc(&d->impute, size_t(p) * sizeof(float)));
-        AHIP_CHECK(hipMemcpy(d->impute, f.data(), size_t(p) * sizeof(float), hipMemcpyHostToDevice));
-    }
-}
 
 // ---- host-vector matrix operations ----------------------------------------------------------------------
 template <class T>
@@ -483,15 +451,6 @@ void need_cov(const adelie_hip_design* d) {
 void check_col(const adelie_hip_design* d, int64_t j, int64_t q, const char* what) {
     if (j < 0 || q < 0 || j + q > d->p) throw make_core_error(std::string(what) + "() is given inconsistent inputs!");
 }
-
-// .snpdat decoder (io_snp_unphased.ipp:10-68; layout in adelie_amd/io.py)
-template <class U>
-U read_as(const uint8_t* p) {
-    U v;
-    std::memcpy(&v, p, sizeof(U));
-    return v;
-}
-
 
 // ---- factor designs: one-hot / pairwise interactions of a resident table Z ---------------------------------------------------
 std::string gib(double bytes) {
@@ -962,339 +921,7 @@ int adelie_hip_design_create_sparse(const int64_t* indptr, const int32_t* indice
     ABI_CATCH
 }
 
-// The second half of every constructor of a design kept sparse, from the point where the six compressed arrays lie in device
-// memory (d->kind, d->nnz set; the copies or kernels that fill them enqueued on d->stream): the row-block pointers and the
-// tile-major copy for the full sweeps.
-static void csc_finish(adelie_hip_design* d) {
-    const int64_t n = d->n, p = d->p, nnz = d->nnz;
-    const size_t vs = d->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
-    const size_t nz1 = size_t(std::max<int64_t>(nnz, 1));
-    hipStream_t s = d->stream;
-    csc_block_layout(n, vs, &d->sp_nb, &d->sp_rb);
-    if (d->sp_nb > 1) {
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bptr), size_t(p) * size_t(d->sp_nb + 1) * sizeof(int64_t)));
-        launch_csc_block_ptr(d->cptr, d->cidx, p, d->sp_nb, d->sp_rb, d->bptr, s);
-    }
-    // Tile-major copy for the full sweeps (csc_tile_sweep_kernel): tiles of kCscTileBytes of an n-vector.  Built on the
-    // device from the per-column tile pointers; the tile-major offsets are a prefix sum over (tile, column) on the host.
-    {
-        const int64_t th = kCscTileBytes / int64_t(vs);
-        const int64_t nt = (n + th - 1) / th;
-        // (the tile of v is 128 KB of dynamic LDS — gfx950 has 160 KB per workgroup, the only target of this library; a launch
-        // the device refuses raises in raw_sweep)
-        const bool worth = nt > 1 && nt <= 4096 && nnz >= (int64_t(1) << 16) && nt * (p + 1) * 8 <= (int64_t(1) << 30) &&
-                           nnz / (nt * p) >= 4; // (segments of a few entries at least: below, the pointers outweigh the entries)
-        if (worth) {
-            DevTmp ctmp;
-            AHIP_CHECK(hipMalloc(&ctmp.p, size_t(p) * size_t(nt + 1) * sizeof(int64_t)));
-            int64_t* colptr = static_cast<int64_t*>(ctmp.p);
-            launch_csc_block_ptr(d->cptr, d->cidx, p, int(nt), th, colptr, s);
-            std::vector<int64_t> cp(size_t(p) * size_t(nt + 1)), tp(size_t(nt) * size_t(p + 1));
-            AHIP_CHECK(hipMemcpyAsync(cp.data(), colptr, cp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-            AHIP_CHECK(hipStreamSynchronize(s));
-            int64_t run = 0;
-            for (int64_t t = 0; t < nt; ++t) {
-                int64_t* row = tp.data() + size_t(t) * size_t(p + 1);
-                for (int64_t c = 0; c < p; ++c) {
-                    row[c] = run;
-                    run += cp[size_t(c) * size_t(nt + 1) + size_t(t) + 1] - cp[size_t(c) * size_t(nt + 1) + size_t(t)];
-                }
-                row[p] = run;
-            }
-            AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->tptr), tp.size() * sizeof(int64_t)));
-            AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->trow), nz1 * sizeof(uint16_t)));
-            AHIP_CHECK(hipMalloc(&d->tval, nz1 * vs));
-            AHIP_CHECK(hipMemcpyAsync(d->tptr, tp.data(), tp.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-            DTYPE_DISPATCH(d, launch_csc_tile_scatter<T>(colptr, d->cidx, static_cast<const T*>(d->cval), p, int(nt), th, d->tptr, d->trow,
-                                                         static_cast<T*>(d->tval), s))
-            AHIP_CHECK(hipStreamSynchronize(s));
-            d->sp_nt = int(nt);
-            d->sp_th = th;
-        }
-    }
-}
-
-int adelie_hip_design_create_csc(const int64_t* indptr, const int32_t* indices, const void* values, const int64_t* row_indptr,
-                                 const int32_t* row_indices, const void* row_values, int64_t n, int64_t p, int dtype, int device,
-                                 adelie_hip_design** out) {
-    ABI_TRY
-    if (!indptr || !row_indptr || !out) throw make_core_error("null argument.");
-    if (n <= 0 || p <= 0) throw make_core_error("matrix must have positive dimensions.");
-    if (n >= (int64_t(1) << 31)) throw make_core_error("number of rows must fit in int32.");
-    if (indptr[0] != 0 || row_indptr[0] != 0) throw make_core_error("sparse(): indptr must start at 0.");
-    for (int64_t j = 0; j < p; ++j)
-        if (indptr[j + 1] < indptr[j]) throw make_core_error("sparse(): indptr must be non-decreasing.");
-    for (int64_t i = 0; i < n; ++i)
-        if (row_indptr[i + 1] < row_indptr[i]) throw make_core_error("sparse(): indptr must be non-decreasing.");
-    const int64_t nnz = indptr[p];
-    if (row_indptr[n] != nnz) throw make_core_error("sparse(): the two compressed forms must hold the same entries.");
-    if (nnz > 0 && (!indices || !values || !row_indices || !row_values)) throw make_core_error("null argument.");
-    for (int64_t j = 0; j < p; ++j) // rows ascending and distinct inside a column (scipy: sort_indices + sum_duplicates)
-        for (int64_t k = indptr[j]; k < indptr[j + 1]; ++k) {
-            if (indices[k] < 0 || indices[k] >= n) throw make_core_error("sparse(): row index out of range.");
-            if (k > indptr[j] && indices[k] <= indices[k - 1]) throw make_core_error("sparse(): row indices must be sorted and distinct inside a column.");
-        }
-    if (p >= (int64_t(1) << 31)) throw make_core_error("number of columns must fit in int32.");
-    {
-        // The two forms must hold the SAME entries: gradients read the column form, residual updates the row form, and an
-        // inconsistent pair would make them disagree silently.  Columns ascending and distinct inside a row, the same number of
-        // entries per column in both forms, and an order-independent checksum over (row, column, value bits).
-        const size_t vsz = dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
-        auto mix = [](uint64_t r, uint64_t c, uint64_t v) {
-            uint64_t h = (r * 0x9E3779B97F4A7C15ull) ^ (c * 0xC2B2AE3D27D4EB4Full) ^ (v * 0x165667B19E3779F9ull);
-            h ^= h >> 29; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 32;
-            return h;
-        };
-        auto bits = [&](const void* vals, int64_t k) {
-            uint64_t b = 0;
-            std::memcpy(&b, static_cast<const char*>(vals) + size_t(k) * vsz, vsz);
-            return b;
-        };
-        std::vector<int64_t> per_col(static_cast<size_t>(p), 0);
-        uint64_t sum_r = 0, sum_c = 0;
-        for (int64_t i = 0; i < n; ++i)
-            for (int64_t k = row_indptr[i]; k < row_indptr[i + 1]; ++k) {
-                const int32_t c = row_indices[k];
-                if (c < 0 || c >= p) throw make_core_error("sparse(): column index out of range.");
-                if (k > row_indptr[i] && c <= row_indices[k - 1]) throw make_core_error("sparse(): column indices must be sorted and distinct inside a row.");
-                ++per_col[size_t(c)];
-                sum_r += mix(uint64_t(i), uint64_t(c), bits(row_values, k));
-            }
-        for (int64_t j = 0; j < p; ++j) {
-            if (per_col[size_t(j)] != indptr[j + 1] - indptr[j]) throw make_core_error("sparse(): the two compressed forms must hold the same entries.");
-            for (int64_t k = indptr[j]; k < indptr[j + 1]; ++k) sum_c += mix(uint64_t(indices[k]), uint64_t(j), bits(values, k));
-        }
-        if (sum_r != sum_c) throw make_core_error("sparse(): the two compressed forms must hold the same entries.");
-    }
-    DesignGuard g(new_design(n, p, dtype, device));
-    adelie_hip_design* d = g.get();
-    d->kind = adelie_hip_design::kCsc;
-    d->nnz = nnz;
-    const size_t vs = dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
-    const size_t nz1 = size_t(std::max<int64_t>(nnz, 1));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cptr), size_t(p + 1) * sizeof(int64_t)));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cidx), nz1 * sizeof(int32_t)));
-    AHIP_CHECK(hipMalloc(&d->cval, nz1 * vs));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rptr), size_t(n + 1) * sizeof(int64_t)));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rcol), nz1 * sizeof(int32_t)));
-    AHIP_CHECK(hipMalloc(&d->rval, nz1 * vs));
-    hipStream_t s = d->stream;
-    AHIP_CHECK(hipMemcpyAsync(d->cptr, indptr, size_t(p + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    AHIP_CHECK(hipMemcpyAsync(d->rptr, row_indptr, size_t(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    if (nnz) {
-        AHIP_CHECK(hipMemcpyAsync(d->cidx, indices, size_t(nnz) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        AHIP_CHECK(hipMemcpyAsync(d->cval, values, size_t(nnz) * vs, hipMemcpyHostToDevice, s));
-        AHIP_CHECK(hipMemcpyAsync(d->rcol, row_indices, size_t(nnz) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        AHIP_CHECK(hipMemcpyAsync(d->rval, row_values, size_t(nnz) * vs, hipMemcpyHostToDevice, s));
-    }
-    csc_finish(d);
-    AHIP_CHECK(hipStreamSynchronize(s));
-    *out = g.release();
-    ABI_CATCH
-}
-
-// A phased-ancestry design from its host code table (phased_decode_host.hpp): the table is uploaded (2 n s bytes), counted,
-// the counts are summed on the host into cptr, the (column, tile) segment starts and rptr, and kernels_phased.hip fills the
-// six arrays of a design kept sparse in the canonical form adelie_hip_design_create_csc demands of its caller.
-static void phased_build(adelie_hip_design* d, const uint8_t* table, int64_t s, int A) {
-    const int64_t n = d->n, p = d->p;
-    const int nt = phased_tiles(n);
-    if (s * int64_t(nt) >= (int64_t(1) << 31)) throw make_core_error("snp_phased_ancestry: too many (SNP, row tile) pairs.");
-    hipStream_t st = d->stream;
-    d->kind = adelie_hip_design::kCsc;
-    const size_t segs = size_t(p) * size_t(nt), vs = d->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
-    DevTmp code, ccnt, rcnt, cpos;
-    AHIP_CHECK(hipMalloc(&code.p, size_t(n) * size_t(2 * s)));
-    AHIP_CHECK(hipMalloc(&ccnt.p, segs * sizeof(int32_t)));
-    AHIP_CHECK(hipMalloc(&rcnt.p, size_t(n) * sizeof(int64_t)));
-    const uint8_t* dcode = static_cast<const uint8_t*>(code.p);
-    AHIP_CHECK(hipMemcpyAsync(code.p, table, size_t(n) * size_t(2 * s), hipMemcpyHostToDevice, st));
-    launch_phased_count(dcode, n, s, A, static_cast<int32_t*>(ccnt.p), static_cast<int64_t*>(rcnt.p), st);
-    AHIP_CHECK(hipGetLastError());
-    std::vector<int32_t> col_cnt(segs);
-    std::vector<int64_t> col_pos(segs), cptr(size_t(p) + 1), rptr(size_t(n) + 1);
-    AHIP_CHECK(hipMemcpyAsync(col_cnt.data(), ccnt.p, segs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    AHIP_CHECK(hipMemcpyAsync(rptr.data() + 1, rcnt.p, size_t(n) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    AHIP_CHECK(hipStreamSynchronize(st));
-    int64_t run = 0;
-    for (size_t k = 0; k < segs; ++k) { // (column-major over (column, tile): a column's segments are consecutive)
-        if (k % size_t(nt) == 0) cptr[k / size_t(nt)] = run;
-        col_pos[k] = run;
-        run += col_cnt[k];
-    }
-    cptr[size_t(p)] = run;
-    rptr[0] = 0;
-    for (int64_t i = 0; i < n; ++i) rptr[size_t(i) + 1] += rptr[size_t(i)];
-    if (rptr[size_t(n)] != run) throw make_core_error("snp_phased_ancestry: the row and column counts of the build disagree.");
-    const int64_t nnz = d->nnz = run;
-    const size_t nz1 = size_t(std::max<int64_t>(nnz, 1));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cptr), size_t(p + 1) * sizeof(int64_t)));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cidx), nz1 * sizeof(int32_t)));
-    AHIP_CHECK(hipMalloc(&d->cval, nz1 * vs));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rptr), size_t(n + 1) * sizeof(int64_t)));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rcol), nz1 * sizeof(int32_t)));
-    AHIP_CHECK(hipMalloc(&d->rval, nz1 * vs));
-    AHIP_CHECK(hipMalloc(&cpos.p, segs * sizeof(int64_t)));
-    AHIP_CHECK(hipMemcpyAsync(d->cptr, cptr.data(), size_t(p + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    AHIP_CHECK(hipMemcpyAsync(d->rptr, rptr.data(), size_t(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    AHIP_CHECK(hipMemcpyAsync(cpos.p, col_pos.data(), segs * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    DTYPE_DISPATCH(d, launch_phased_fill<T>(dcode, n, s, A, static_cast<const int64_t*>(cpos.p), d->rptr, d->cidx,
-                                            static_cast<T*>(d->cval), d->rcol, static_cast<T*>(d->rval), st))
-    AHIP_CHECK(hipGetLastError());
-    AHIP_CHECK(hipStreamSynchronize(st)); // (the table and the segment starts are freed on the way out)
-    csc_finish(d);
-    AHIP_CHECK(hipStreamSynchronize(st));
-}
-
-int adelie_hip_design_create_snp_phased_ancestry(const void* snpdat, int64_t n_bytes, int dtype, int device, adelie_hip_design** out) {
-    ABI_TRY
-    if (!snpdat || !out) throw make_core_error("null argument.");
-    const uint8_t* buf = static_cast<const uint8_t*>(snpdat);
-    PhasedDims dims;
-    if (const char* e = phased_header(buf, n_bytes < 0 ? 0 : uint64_t(n_bytes), &dims)) throw make_core_error(e);
-    std::vector<uint8_t> table(size_t(dims.n) * size_t(2 * dims.s));
-    if (const char* e = phased_decode(buf, uint64_t(n_bytes), dims, table.data())) throw make_core_error(e);
-    DesignGuard g(new_design(int64_t(dims.n), int64_t(dims.s * dims.A), dtype, device));
-    phased_build(g.get(), table.data(), int64_t(dims.s), int(dims.A));
-    *out = g.release();
-    ABI_CATCH
-}
-
-int adelie_hip_design_create_snp_phased_calldata(const int8_t* calldata, const int8_t* ancestries, int64_t n, int64_t s, int64_t A,
-                                                 int dtype, int device, adelie_hip_design** out) {
-    ABI_TRY
-    if (!calldata || !ancestries || !out) throw make_core_error("null argument.");
-    if (const char* e = phased_pack_dims(n, s, A)) throw make_core_error(e);
-    std::vector<uint8_t> table(size_t(n) * size_t(2 * s));
-    if (const char* e = phased_pack(calldata, ancestries, n, s, A, table.data())) throw make_core_error(e);
-    DesignGuard g(new_design(n, s * A, dtype, device));
-    phased_build(g.get(), table.data(), s, int(A));
-    *out = g.release();
-    ABI_CATCH
-}
-
-// A convex-relu design over the kept-sparse Z, kept sparse itself (kernels_relu_sparse.hip): Z's compressed columns are copied
-// and cut at the row tiles, the host's column-major (n, m) mask bytes are uploaded and packed to words, the entries are counted
-// per (column, tile) and per row, the counts are summed on the host into cptr, the segment starts and rptr, and the fill
-// kernels write the six arrays in the canonical form adelie_hip_design_create_csc demands of its caller.  The copy of Z and
-// the mask words stay with the handle for the structured sweep.
-static void relu_csc_build(adelie_hip_design* Z, const uint8_t* mask, int64_t m, int gated, adelie_hip_design** out) {
-    const int64_t n = Z->n, dz = Z->p, znnz = Z->nnz;
-    const size_t vs = Z->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
-    const double cols = double(gated ? 1 : 2) * double(m) * double(dz);
-    if (cols > double((int64_t(1) << 31) - 64))
-        throw make_core_error("convex_relu(): the expanded design has more columns than the solver's 32-bit column indices address (" +
-                              std::to_string(double(gated ? 1 : 2) * double(m) * double(znnz)) + " stored entries at most).");
-    const int64_t P = int64_t(cols), md = m * dz;
-    const ReluSparseShape sh = relu_sparse_shape(n, m);
-    const int nt = int(sh.tiles);
-    if (dz * sh.tiles >= (int64_t(1) << 31) || sh.words > 65535)
-        throw make_core_error("convex_relu(): too many (column of mat, row tile) pairs or mask columns for one launch.");
-    DesignGuard g(new_design(n, P, Z->dtype, Z->device));
-    adelie_hip_design* d = g.get();
-    hipStream_t st = d->stream;
-    d->kind = adelie_hip_design::kCsc;
-    d->r_d = dz;
-    d->r_m = m;
-    d->r_gated = gated ? 1 : 0;
-    d->rz_nnz = znnz;
-    const size_t zn1 = size_t(std::max<int64_t>(znnz, 1));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rz_seg), size_t(dz) * size_t(nt + 1) * sizeof(int64_t)));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rz_idx), zn1 * sizeof(int32_t)));
-    AHIP_CHECK(hipMalloc(&d->rz_val, zn1 * vs));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rbits), size_t(sh.words) * size_t(n) * sizeof(uint32_t)));
-    AHIP_CHECK(hipStreamSynchronize(Z->stream)); // (Z's own creation may still be in flight on its stream)
-    if (znnz) {
-        AHIP_CHECK(hipMemcpyAsync(d->rz_idx, Z->cidx, size_t(znnz) * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        AHIP_CHECK(hipMemcpyAsync(d->rz_val, Z->cval, size_t(znnz) * vs, hipMemcpyDeviceToDevice, st));
-    }
-    launch_csc_block_ptr(Z->cptr, d->rz_idx, dz, nt, sh.tile_rows, d->rz_seg, st);
-    const size_t segs = size_t(md) * size_t(nt), psegs = size_t(P) * size_t(nt);
-    DevTmp mbytes, ccnt, rcnt, cpos;
-    AHIP_CHECK(hipMalloc(&mbytes.p, size_t(n) * size_t(m)));
-    AHIP_CHECK(hipMalloc(&ccnt.p, segs * sizeof(int32_t)));
-    AHIP_CHECK(hipMalloc(&rcnt.p, size_t(n) * sizeof(int64_t)));
-    AHIP_CHECK(hipMemcpyAsync(mbytes.p, mask, size_t(n) * size_t(m), hipMemcpyHostToDevice, st));
-    launch_relu_sparse_pack(static_cast<const uint8_t*>(mbytes.p), n, m, d->rbits, st);
-    DTYPE_DISPATCH(d, launch_relu_sparse_count<T>(d->relu_csc_view<T>(), Z->rptr, static_cast<int32_t*>(ccnt.p),
-                                                  static_cast<int64_t*>(rcnt.p), st))
-    AHIP_CHECK(hipGetLastError());
-    std::vector<int32_t> col_cnt(segs);
-    std::vector<int64_t> col_pos(psegs), cptr(size_t(P) + 1), rptr(size_t(n) + 1);
-    AHIP_CHECK(hipMemcpyAsync(col_cnt.data(), ccnt.p, segs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    AHIP_CHECK(hipMemcpyAsync(rptr.data() + 1, rcnt.p, size_t(n) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    AHIP_CHECK(hipStreamSynchronize(st));
-    int64_t run = 0;
-    for (size_t k = 0; k < psegs; ++k) { // (column-major over (column, tile); the signed half repeats the counts of the first)
-        if (k % size_t(nt) == 0) cptr[k / size_t(nt)] = run;
-        col_pos[k] = run;
-        run += col_cnt[k % segs];
-    }
-    cptr[size_t(P)] = run;
-    rptr[0] = 0;
-    for (int64_t i = 0; i < n; ++i) rptr[size_t(i) + 1] += rptr[size_t(i)];
-    if (rptr[size_t(n)] != run) throw make_core_error("convex_relu(): the row and column counts of the build disagree.");
-    const int64_t nnz = d->nnz = run;
-    const size_t nz1 = size_t(std::max<int64_t>(nnz, 1));
-    auto alloc = [&](void** p, size_t bytes) {
-        if (hipMalloc(p, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            throw make_core_error("convex_relu(): could not allocate the expanded design (" + std::to_string(n) + " x " + std::to_string(P) +
-                                  ", " + std::to_string(nnz) + " stored entries) on the device.");
-        }
-    };
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cptr), size_t(P + 1) * sizeof(int64_t)));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rptr), size_t(n + 1) * sizeof(int64_t)));
-    alloc(reinterpret_cast<void**>(&d->cidx), nz1 * sizeof(int32_t));
-    alloc(&d->cval, nz1 * vs);
-    alloc(reinterpret_cast<void**>(&d->rcol), nz1 * sizeof(int32_t));
-    alloc(&d->rval, nz1 * vs);
-    AHIP_CHECK(hipMalloc(&cpos.p, psegs * sizeof(int64_t)));
-    AHIP_CHECK(hipMemcpyAsync(d->cptr, cptr.data(), size_t(P + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    AHIP_CHECK(hipMemcpyAsync(d->rptr, rptr.data(), size_t(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    AHIP_CHECK(hipMemcpyAsync(cpos.p, col_pos.data(), psegs * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    DTYPE_DISPATCH(d, launch_relu_sparse_fill<T>(d->relu_csc_view<T>(), Z->rptr, Z->rcol, static_cast<const T*>(Z->rval),
-                                                 static_cast<const int64_t*>(cpos.p), d->rptr, d->cidx, static_cast<T*>(d->cval), d->rcol,
-                                                 static_cast<T*>(d->rval), st))
-    AHIP_CHECK(hipGetLastError());
-    AHIP_CHECK(hipStreamSynchronize(st)); // (the mask bytes and the segment starts are freed on the way out)
-    csc_finish(d);
-    AHIP_CHECK(hipStreamSynchronize(st));
-    *out = g.release();
-}
-
-int adelie_hip_design_create_convex_relu_csc(adelie_hip_design* Z, const uint8_t* mask, int64_t m, int gated, adelie_hip_design** out) {
-    ABI_TRY
-    if (!Z || !out || (!mask && m > 0)) throw make_core_error("null argument.");
-    if (!Z->is_csc() || Z->std_center)
-        throw make_core_error("convex_relu(): mat must be a resident design kept sparse without a standardized view on it.");
-    if (m < 0) throw make_core_error("mask must be (n, m) where mat is (n, d).");
-    set_device(Z);
-    relu_csc_build(Z, mask, m, gated, out);
-    ABI_CATCH
-}
-
-int adelie_hip_design_csc_download(adelie_hip_design* d, int64_t* indptr, int32_t* indices, void* values, int64_t* row_indptr,
-                                   int32_t* row_indices, void* row_values) {
-    ABI_TRY
-    if (!d) throw make_core_error("null argument.");
-    if (!d->is_csc()) throw make_core_error("csc_download() takes a design kept sparse.");
-    set_device(d);
-    hipStream_t s = d->stream;
-    const size_t vs = d->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float), nnz = size_t(d->nnz);
-    auto down = [&](void* dst, const void* src, size_t bytes) {
-        if (dst && bytes) AHIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
-    };
-    down(indptr, d->cptr, size_t(d->p + 1) * sizeof(int64_t));
-    down(indices, d->cidx, nnz * sizeof(int32_t));
-    down(values, d->cval, nnz * vs);
-    down(row_indptr, d->rptr, size_t(d->n + 1) * sizeof(int64_t));
-    down(row_indices, d->rcol, nnz * sizeof(int32_t));
-    down(row_values, d->rval, nnz * vs);
-    AHIP_CHECK(hipStreamSynchronize(s));
-    ABI_CATCH
-}
-int64_t adelie_hip_design_nnz(const adelie_hip_design* d) { return d && d->is_csc() ? d->nnz : -1; }
+#include "design_csc.hpp"
 
 int adelie_hip_design_create_standardized(adelie_hip_design* src, const double* centers, const double* scales,
                                           adelie_hip_design** out) {
@@ -1378,137 +1005,7 @@ int adelie_hip_design_adopt_dense_dev(const void* dev_ptr, int64_t n, int64_t p,
     ABI_CATCH
 }
 
-int adelie_hip_design_create_snp_calldata(const int8_t* calldata, int64_t n, int64_t p, const double* impute, int dtype,
-                                          int device, adelie_hip_design** out) {
-    ABI_TRY
-    if (!calldata || !impute || !out) throw make_core_error("null argument.");
-    DesignGuard g(new_design(n, p, dtype, device));
-    create_snp_from_calldata(g.get(), calldata, impute);
-    *out = g.release();
-    ABI_CATCH
-}
-
-// Decodes one column of a .snpdat image into int8 calls (missing = -9; `col` zeroed by the caller).  Every read is checked
-// against the end of the column BEFORE it happens (io_snp_unphased.ipp:117-135,225-274 is the layout).
-static void decode_snpdat_column(const uint8_t* buf, uint64_t base, uint64_t endc, uint64_t n, int8_t* col) {
-    for (int c = 0; c < 3; ++c) {
-        const uint64_t off = read_as<uint64_t>(buf + base + 8 * c);
-        if (off > endc - base || endc - base - off < 4) throw make_core_error("corrupt .snpdat category offset.");
-        uint64_t pos = base + off;
-        const uint32_t n_chunks = read_as<uint32_t>(buf + pos);
-        pos += 4;
-        const int8_t val = c == 0 ? int8_t(-9) : int8_t(c);
-        for (uint32_t k = 0; k < n_chunks; ++k) {
-            if (endc - pos < 5) throw make_core_error("corrupt .snpdat chunk (overrun).");
-            const uint32_t cidx = read_as<uint32_t>(buf + pos);
-            const uint32_t cnt = uint32_t(buf[pos + 4]) + 1;
-            pos += 5;
-            if (endc - pos < cnt) throw make_core_error("corrupt .snpdat chunk (overrun).");
-            for (uint32_t t = 0; t < cnt; ++t) {
-                const uint64_t row = uint64_t(cidx) * 256 + buf[pos + t];
-                if (row >= n) throw make_core_error("corrupt .snpdat chunk (row out of range).");
-                col[row] = val;
-            }
-            pos += cnt;
-        }
-    }
-}
-
-int adelie_hip_design_create_snp_unphased(const void* snpdat, int64_t n_bytes, int dtype, int device,
-                                          adelie_hip_design** out) {
-    ABI_TRY
-    if (!snpdat || !out) throw make_core_error("null argument.");
-    const uint8_t* buf = static_cast<const uint8_t*>(snpdat);
-    if (n_bytes < 17) throw make_core_error("buffer is too small to be a .snpdat image.");
-    const uint64_t n = read_as<uint64_t>(buf + 1), p = read_as<uint64_t>(buf + 9);
-    // Nothing below is sized from the header before the header is bounded.  Every column costs 32 header bytes (nnz, nnm,
-    // impute, outer) plus its own 24-byte offset table, which bounds p by the image size; the rows are only bounded by what
-    // the format can address, so a plausibility cap stands in (2^32 rows; the largest biobanks have < 2^24).  The host side
-    // then never holds more than one panel of decoded columns (256 MB, or one column), whatever the header claims, and the
-    // packed matrix is allocated on the device BEFORE any decoding: an image whose counts were damaged fails there.
-    if (p == 0 || n == 0) throw make_core_error("corrupt .snpdat header (row / column counts).");
-    if (p > uint64_t(n_bytes) / 32 || n > (uint64_t(1) << 32)) throw make_core_error("corrupt .snpdat header (row / column counts).");
-    const size_t hdr = 17 + 8 * p * 3 + 8 * (p + 1);
-    if (size_t(n_bytes) < hdr) throw make_core_error("truncated .snpdat header.");
-    const uint8_t* impute_p = buf + 17 + 16 * p;
-    const uint8_t* outer_p = buf + 17 + 24 * p;
-    std::vector<double> impute(p);
-    std::memcpy(impute.data(), impute_p, 8 * p);
-    for (uint64_t j = 0; j < p; ++j) { // the column index, before anything is allocated
-        const uint64_t base = read_as<uint64_t>(outer_p + 8 * j), endc = read_as<uint64_t>(outer_p + 8 * (j + 1));
-        if (endc > uint64_t(n_bytes) || base < hdr || base > endc || endc - base < 24)
-            throw make_core_error("corrupt .snpdat column index.");
-    }
-    DesignGuard g(new_design(int64_t(n), int64_t(p), dtype, device));
-    adelie_hip_design* d = g.get();
-    d->kind = adelie_hip_design::kSnp;
-    d->ldb = int64_t((((n + 3) / 4 + 127) / 128) * 128);
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bits), size_t(d->ldb) * size_t(p)));
-    // decode -> int8 panel on the host -> 2-bit on the device, a panel of columns at a time
-    const uint64_t panel = std::min<uint64_t>(p, std::max<uint64_t>(1, (uint64_t(1) << 28) / n));
-    DevTmp tmp;
-    AHIP_CHECK(hipMalloc(&tmp.p, size_t(n) * size_t(panel)));
-    int8_t* dcalls = static_cast<int8_t*>(tmp.p);
-    std::vector<int8_t> calls(size_t(n) * size_t(panel));
-    for (uint64_t j0 = 0; j0 < p; j0 += panel) {
-        const uint64_t pc = std::min(panel, p - j0);
-        std::fill(calls.begin(), calls.begin() + size_t(n) * size_t(pc), int8_t(0));
-        for (uint64_t j = j0; j < j0 + pc; ++j)
-            decode_snpdat_column(buf, read_as<uint64_t>(outer_p + 8 * j), read_as<uint64_t>(outer_p + 8 * (j + 1)), n,
-                                 calls.data() + size_t(j - j0) * size_t(n));
-        AHIP_CHECK(hipMemcpyAsync(dcalls, calls.data(), size_t(n) * size_t(pc), hipMemcpyHostToDevice, d->stream));
-        launch_pack_snp(dcalls, int64_t(n), int64_t(pc), d->bits + int64_t(j0) * d->ldb, d->ldb, d->stream);
-        AHIP_CHECK(hipStreamSynchronize(d->stream));
-    }
-    if (d->dtype == ADELIE_HIP_F64) {
-        AHIP_CHECK(hipMalloc(&d->impute, size_t(p) * sizeof(double)));
-        AHIP_CHECK(hipMemcpy(d->impute, impute.data(), size_t(p) * sizeof(double), hipMemcpyHostToDevice));
-    } else {
-        std::vector<float> f(impute.begin(), impute.end());
-        AHIP_CHECK(hipMalloc(&d->impute, size_t(p) * sizeof(float)));
-        AHIP_CHECK(hipMemcpy(d->impute, f.data(), size_t(p) * sizeof(float), hipMemcpyHostToDevice));
-    }
-    *out = g.release();
-    ABI_CATCH
-}
-
-int adelie_hip_design_create_snp_bed(const void* bed, int64_t n_bytes, int64_t n, int64_t p, int dtype, int device,
-                                     adelie_hip_design** out) {
-    ABI_TRY
-    if (!bed || !out) throw make_core_error("null argument.");
-    if (n <= 0 || p <= 0) throw make_core_error("n and p must be positive.");
-    const uint8_t* buf = static_cast<const uint8_t*>(bed);
-    const int64_t stride = (n + 3) / 4;
-    if (n_bytes < 3 || buf[0] != 0x6c || buf[1] != 0x1b) throw make_core_error("not a PLINK .bed image (bad magic).");
-    if (buf[2] != 0x01) throw make_core_error("only SNP-major .bed files (third byte 0x01) are supported.");
-    if (n_bytes < 3 + stride * p) throw make_core_error("truncated .bed image: expected 3 + ceil(n/4)*p bytes.");
-    DesignGuard g(new_design(n, p, dtype, device));
-    adelie_hip_design* d = g.get();
-    d->kind = adelie_hip_design::kSnp;
-    d->ldb = (((n + 3) / 4 + 127) / 128) * 128;
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bits), size_t(d->ldb) * size_t(p)));
-    // stage the records in panels of SNPs to bound the temporary
-    const int64_t panel = std::max<int64_t>(1, (int64_t(1) << 28) / stride);
-    uint8_t* tmp = nullptr;
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&tmp), size_t(stride) * size_t(std::min(panel, p))));
-    for (int64_t j0 = 0; j0 < p; j0 += panel) {
-        const int64_t pc = std::min(panel, p - j0);
-        AHIP_CHECK(hipMemcpyAsync(tmp, buf + 3 + j0 * stride, size_t(stride) * size_t(pc), hipMemcpyDefault, d->stream));
-        launch_bed_transcode(tmp, n, pc, stride, d->bits + j0 * d->ldb, d->ldb, d->stream);
-        AHIP_CHECK(hipStreamSynchronize(d->stream));
-    }
-    (void)hipFree(tmp);
-    if (d->dtype == ADELIE_HIP_F64) {
-        AHIP_CHECK(hipMalloc(&d->impute, size_t(p) * sizeof(double)));
-        launch_snp_impute<double>(d->bits, n, p, d->ldb, static_cast<double*>(d->impute), d->stream);
-    } else {
-        AHIP_CHECK(hipMalloc(&d->impute, size_t(p) * sizeof(float)));
-        launch_snp_impute<float>(d->bits, n, p, d->ldb, static_cast<float*>(d->impute), d->stream);
-    }
-    AHIP_CHECK(hipStreamSynchronize(d->stream));
-    *out = g.release();
-    ABI_CATCH
-}
+#include "design_snp.hpp"
 
 int adelie_hip_design_batch_stats(adelie_hip_design* d, double* out) {
     ABI_TRY

@@ -15,32 +15,23 @@
 //
 // Every function returns nullptr on success and a message otherwise (the caller raises it as a core_error).  The decoder
 // trusts nothing in the image: every offset, chunk header and run of row bytes is checked against the end of its SNP block
-// BEFORE it is read, every row against n before it is written, as decode_snpdat_column does for the unphased format.
+// BEFORE it is read, every row against n before it is written (the chunk walk is snp_decode_host.hpp's, shared with the
+// unphased format).
 #pragma once
 #include <cstdint>
 #include <cstring>
+#include "snp_decode_host.hpp" // phased_read_u64 / _u32, snp_walk_chunks
 
 namespace ahip {
 
 constexpr int64_t kPhasedTileRows = 4096; // rows per (SNP, tile) workgroup of kernels_phased.hip
 constexpr uint8_t kPhasedNone = 255;      // "no mutation" in the code table
-constexpr uint64_t kPhasedChunk = 256;    // rows per chunk of the file format
+constexpr uint64_t kPhasedChunk = kSnpChunk; // rows per chunk of the file format
 
 struct PhasedDims {
     uint64_t n = 0, s = 0, A = 0;
     uint64_t header_bytes() const { return 18 + 16 * s * A + 8 * (s + 1); }
 };
-
-inline uint64_t phased_read_u64(const uint8_t* p) {
-    uint64_t v;
-    std::memcpy(&v, p, sizeof v);
-    return v;
-}
-inline uint32_t phased_read_u32(const uint8_t* p) {
-    uint32_t v;
-    std::memcpy(&v, p, sizeof v);
-    return v;
-}
 
 // The counts of the image, bounded by what the image can hold before anything is sized from them: a SNP costs at least its
 // outer entry and, per ancestry, two nnz counts, one ancestry offset, two haplotype offsets and two chunk counts.
@@ -76,24 +67,13 @@ inline const char* phased_decode(const uint8_t* buf, uint64_t n_bytes, const Pha
             for (uint64_t k = 0; k < 2; ++k) {
                 const uint64_t hoff = phased_read_u64(buf + ablk + 8 * k);
                 if (hoff > endc - ablk || endc - ablk - hoff < 4) return "corrupt .snpdat haplotype offset.";
-                uint64_t pos = ablk + hoff;
-                const uint32_t n_chunks = phased_read_u32(buf + pos);
-                pos += 4;
                 uint8_t* col = table + size_t(2 * j + k) * size_t(n);
-                for (uint32_t c = 0; c < n_chunks; ++c) {
-                    if (endc - pos < 5) return "corrupt .snpdat chunk (overrun).";
-                    const uint64_t cidx = phased_read_u32(buf + pos);
-                    const uint64_t cnt = uint64_t(buf[pos + 4]) + 1;
-                    pos += 5;
-                    if (endc - pos < cnt) return "corrupt .snpdat chunk (overrun).";
-                    for (uint64_t t = 0; t < cnt; ++t) {
-                        const uint64_t row = cidx * kPhasedChunk + buf[pos + t];
-                        if (row >= n) return "corrupt .snpdat chunk (row out of range).";
-                        if (col[row] != kPhasedNone) return "corrupt .snpdat chunk (a haplotype stored twice).";
-                        col[row] = uint8_t(a);
-                    }
-                    pos += cnt;
-                }
+                const char* e = snp_walk_chunks(buf, ablk + hoff, endc, n, [&](uint64_t row) -> const char* {
+                    if (col[row] != kPhasedNone) return "corrupt .snpdat chunk (a haplotype stored twice).";
+                    col[row] = uint8_t(a);
+                    return nullptr;
+                });
+                if (e) return e;
             }
         }
     }

@@ -92,6 +92,20 @@ def test_build_equals_the_canonical_compressed_forms(hip, tmp_path, dtype, n, s,
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_build_without_a_single_entry(hip, dtype):
+    """All-zero calldata: the build's counts sum to nothing, the six arrays are those of an empty csc_matrix, mul gives zeros."""
+    n, s, A = 5, 2, 2
+    cal = np.zeros((n, 2 * s), dtype=np.int8, order="F")
+    anc = np.asfortranarray(np.random.RandomState(0).randint(0, A, size=(n, 2 * s)).astype(np.int8))
+    X = ad.matrix.snp_phased_calldata(cal, anc, A, dtype=dtype)
+    assert int(hip.fn("design_nnz")(X._handle)) == 0
+    assert_equals_canonical(M._csc_download(X), np.zeros((n, s * A)), dtype)
+    out = np.full(s * A, 7, dtype=dtype)
+    X.mul(np.arange(1, n + 1, dtype=dtype), np.ones(n, dtype=dtype), out)
+    assert not out.any()
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("n,s,A", SHAPES[:4] + SHAPES[5:])
 def test_design_runs_the_reference_check_list(hip, dtype, n, s, A):
     cal, anc, E = case(n, s, A)

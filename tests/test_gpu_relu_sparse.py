@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 NS = [1, 5, 257, 1031]
 DMS = [(3, 1), (17, 19), (5, 37), (2, 70)]   # the last two cross a 32- and a 64-gate mask word
 HOOK = "ADELIE_HIP_RELU_SWEEP"
-TILE_MAJOR = dict(n=2 * 16384 + 37, d=4, m=3, density=0.5)   # large enough for csc_finish's tile-major copy (design.hip)
+TILE_MAJOR = dict(n=2 * 16384 + 37, d=4, m=3, density=0.5)   # large enough for csc_finish's tile-major copy (design_csc.hpp)
 
 
 def nnz_of(X):
@@ -97,6 +97,23 @@ def test_masked_out_entries_are_not_stored_whatever_z_holds(hip, dtype, gated):
     assert not np.isin(arrays[1], [0, 100, 256]).any()
     assert_equals_canonical(arrays, _relu_expand_sparse(Z, mask, gated), dtype)
     assert nnz_of(X) == stored_entries(Z, mask, gated)
+
+
+@pytest.mark.parametrize("gated", [True, False])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_build_without_a_single_entry(hip, dtype, gated):
+    """An all-false mask: the build's counts sum to nothing, the six arrays are those of an empty csc_matrix, mul gives zeros
+    (test_structured_sweep_of_an_all_false_mask_is_zero builds such a design too, signed and at three row tiles, for the sweep)."""
+    n, d, m = 5, 3, 1
+    Z, _ = make_inputs(n, d, m, dtype)
+    mask = np.zeros((n, m), dtype=bool)
+    X = build(Z, mask, gated=gated)
+    P = (1 if gated else 2) * m * d
+    assert X.shape == (n, P) and nnz_of(X) == 0
+    assert_equals_canonical(_csc_download(X), csc_matrix((n, P), dtype=dtype), dtype)
+    out = np.full(P, 7, dtype=dtype)
+    X.mul(np.arange(1, n + 1, dtype=dtype), np.ones(n, dtype=dtype), out)
+    assert not out.any()
 
 
 @pytest.fixture(scope="module")
