@@ -260,7 +260,7 @@ HIP_SYMBOLS = [
     "bench_sweep", "filter_sweep_test", "block_build_test", "group_piece_test",
     "css_cov_solve", "css_result_destroy", "css_result_size", "css_result_copy", "css_result_scalar", "css_result_error",
     "bvls_solve", "bvls_result_destroy", "bvls_result_size", "bvls_result_copy", "bvls_result_scalar", "bvls_result_error",
-    "design_create_constraint_dense", "design_adopt_constraint_dense_dev", "constraint_op",
+    "design_create_constraint_dense", "design_adopt_constraint_dense_dev", "design_create_constraint_csc", "constraint_op",
     "pinball_solve", "pinball_result_destroy", "pinball_result_size", "pinball_result_copy", "pinball_result_scalar",
     "pinball_result_error",
 ]
@@ -395,6 +395,7 @@ class Backend:
         sig("bvls_result_error", C.c_char_p, [vp])
         sig("design_create_constraint_dense", ci, [vp, i64, i64, ci, ci, ci, p(vp)])
         sig("design_adopt_constraint_dense_dev", ci, [vp, i64, i64, ci, ci, ci, p(vp)])
+        sig("design_create_constraint_csc", ci, [vp, vp, vp, vp, vp, vp, i64, i64, ci, ci, p(vp)])
         sig("constraint_op", ci, [vp, ci, i64, vp, vp, i64, vp])
         sig("pinball_solve", ci, [vp, p(PinballArgs), p(vp)])
         sig("pinball_result_destroy", ci, [vp])

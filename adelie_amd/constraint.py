@@ -734,12 +734,14 @@ def linear(A, lower: np.ndarray, upper: np.ndarray, *, vars: np.ndarray = None, 
 
 def _constraint_matrix_to_host(A):
     """A ``MatrixConstraintBase64/32`` object (the only form the reference's ``linear`` accepts) read back as an ``(m, d)``
-    array: the resident matrix in one copy, any other subclass row by row through its ``rvtmul``.  Anything else is returned
-    as it is."""
+    array: the resident matrix in one copy, any other subclass row by row through its ``rvtmul``.  The matrix kept sparse
+    (``matrix.sparse(method="constraint")``) gives the host ``csr_matrix`` it keeps.  Anything else is returned as it is."""
     from . import matrix as _matrix
 
     if not isinstance(A, _matrix.MatrixConstraintBase):
         return A
+    if isinstance(A, _matrix._ConstraintMatrixSparse):
+        return A._scipy
     if hasattr(A, "to_dense"):
         return A.to_dense()
     m, d = int(A.rows()), int(A.cols())

@@ -501,8 +501,8 @@ struct adelie_hip_design {
     // covariance-method matrix A (adelie_hip_design_create_cov_dense): a dense (p, p) design with n == p that only
     // adelie_hip_gaussian_cov_solve and the cov_* operations accept; cov == 2: the stored matrix is A^T (row-major input)
     int cov = 0;
-    // constraint matrix (adelie_hip_design_create_constraint_dense): this dense handle is the (d, m) column-major A' of an (m, d)
-    // constraint matrix A, so n == d and p == m; only adelie_hip_constraint_op and adelie_hip_pinball_solve accept it
+    // constraint matrix (adelie_hip_design_create_constraint_dense / _csc): this dense or kCsc handle is the (d, m) matrix A' of an
+    // (m, d) constraint matrix A, so n == d and p == m; only adelie_hip_constraint_op and adelie_hip_pinball_solve accept it
     int constraint = 0;
     int64_t n = 0, p = 0;
     // dense

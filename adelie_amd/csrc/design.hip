@@ -752,13 +752,15 @@ void op_cov_to_dense(adelie_hip_design* d, int64_t i, int64_t q, T* out) {
 }
 
 // The MatrixConstraintBase operations (matrix_constraint_base.hpp) on a constraint handle: d->n == d, d->p == m, a row of A is
-// column j of the stored matrix.  Host vectors in and out; none of these is a hot path.
+// column j of the stored matrix, dense or compressed (adelie_hip_design_create_constraint_csc).  Host vectors in and out; none
+// of these is a hot path.
 template <class T>
 void op_constraint(adelie_hip_design* A, int op, int64_t j, const T* in, const int64_t* indices, int64_t ni, T* out) {
     set_device(A);
     hipStream_t s = A->stream;
     const int64_t d = A->n, m = A->p;
-    const DenseView<T> Av = A->dense<T>();
+    const bool sparse = A->is_csc();
+    const DenseView<T> Av = A->dense<T>(); // (null on a matrix kept sparse, and unused there)
     auto up = [&](T* dst, const T* src, size_t n) { AHIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, s)); };
     auto down = [&](T* dst, const T* src, size_t n) {
         AHIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, s));
@@ -770,28 +772,47 @@ void op_constraint(adelie_hip_design* A, int op, int64_t j, const T* in, const i
             const int64_t c0 = op == ADELIE_HIP_CONS_TMUL ? 0 : j, nc = op == ADELIE_HIP_CONS_TMUL ? m : 1;
             T* dv = scratch<T>(A->s_n1, size_t(d));
             T* dout = scratch<T>(A->s_p1, size_t(nc));
-            T* work = scratch<T>(A->s_work, size_t(sweep_work_elems(d, nc)));
+            T* work = scratch<T>(A->s_work, size_t(raw_sweep_work_elems(*A, nc, false)));
             up(dv, in, size_t(d));
-            launch_sweep<T>(Av, dv, dout, c0, nc, nullptr, nullptr, nullptr, false, work, s);
+            raw_sweep<T>(*A, dv, dout, c0, nc, nullptr, nullptr, nullptr, false, false, work, s);
             down(out, dout, size_t(nc));
             break;
         }
         case ADELIE_HIP_CONS_MUL:
         case ADELIE_HIP_CONS_SP_MUL:
         case ADELIE_HIP_CONS_RVTMUL: { // the column axpy
-            const int64_t q = op == ADELIE_HIP_CONS_MUL ? m : (op == ADELIE_HIP_CONS_SP_MUL ? ni : 1);
-            T* dout = scratch<T>(A->s_n1, size_t(d));
-            T* dcoef = scratch<T>(A->s_p1, size_t(q));
-            int32_t* dcols = scratch<int32_t>(A->s_idx1, size_t(q));
+            int64_t q = op == ADELIE_HIP_CONS_MUL ? m : (op == ADELIE_HIP_CONS_SP_MUL ? ni : 1);
             std::vector<int32_t> cols(static_cast<size_t>(q));
             for (int64_t k = 0; k < q; ++k)
                 cols[size_t(k)] = int32_t(op == ADELIE_HIP_CONS_MUL ? k : (op == ADELIE_HIP_CONS_SP_MUL ? indices[k] : j));
+            std::vector<T> coef;
+            if (sparse && op == ADELIE_HIP_CONS_SP_MUL) { // the compressed axpy wants distinct columns: repeats are summed here
+                std::vector<int64_t> pos(static_cast<size_t>(q));
+                for (int64_t k = 0; k < q; ++k) pos[size_t(k)] = k;
+                std::stable_sort(pos.begin(), pos.end(), [&](int64_t a, int64_t b) { return indices[a] < indices[b]; });
+                int64_t u = 0;
+                for (int64_t k = 0; k < q; ++k) {
+                    const int64_t at = pos[size_t(k)];
+                    if (u > 0 && cols[size_t(u - 1)] == int32_t(indices[at])) coef[size_t(u - 1)] += in[at];
+                    else cols[size_t(u++)] = int32_t(indices[at]), coef.push_back(in[at]);
+                }
+                q = u;
+                in = coef.data();
+            }
+            T* dout = scratch<T>(A->s_n1, size_t(d));
+            T* dcoef = scratch<T>(A->s_p1, size_t(q));
+            int32_t* dcols = scratch<int32_t>(A->s_idx1, size_t(q));
+            T* delta = nullptr;
+            if (sparse) { // the zeroed p + 8 elements the compressed axpy scatters the coefficients into
+                delta = scratch<T>(A->s_work, size_t(m) + 8);
+                AHIP_CHECK(hipMemsetAsync(delta, 0, (size_t(m) + 8) * sizeof(T), s));
+            }
             if (op == ADELIE_HIP_CONS_RVTMUL) up(dout, out, size_t(d));
             else AHIP_CHECK(hipMemsetAsync(dout, 0, size_t(d) * sizeof(T), s));
             if (q > 0) {
                 up(dcoef, in, size_t(q));
                 AHIP_CHECK(hipMemcpyAsync(dcols, cols.data(), size_t(q) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-                launch_axpy_cols<T>(Av, dcols, dcoef, nullptr, int32_t(q), T(1), dout, s);
+                raw_axpy_cols<T>(*A, dcols, dcoef, nullptr, int32_t(q), T(1), dout, delta, s);
             }
             down(out, dout, size_t(d));
             break;
@@ -799,8 +820,19 @@ void op_constraint(adelie_hip_design* A, int op, int64_t j, const T* in, const i
         case ADELIE_HIP_CONS_RMMUL: { // out[c] = Q[:, c] . A[j, :]: the sweep of Q's columns with row j of A as the vector
             T* dQ = scratch<T>(A->s_misc, size_t(d) * size_t(d));
             T* dout = scratch<T>(A->s_p1, size_t(d));
-            T* work = scratch<T>(A->s_work, size_t(sweep_work_elems(d, d)));
             up(dQ, in, size_t(d) * size_t(d));
+            if (sparse) { // row j of A times Q, through Q' (kernels_pinball_sparse.hip)
+                DevBuf<T> dQT;
+                dQT.reserve(size_t(d) * size_t(d));
+                int32_t* dcol = scratch<int32_t>(A->s_idx1, 1);
+                const int32_t jj = int32_t(j);
+                AHIP_CHECK(hipMemcpyAsync(dcol, &jj, sizeof(int32_t), hipMemcpyHostToDevice, s));
+                launch_transpose_square<T>(dQ, d, dQT.p, s);
+                launch_csc_rows_dense<T>(A->csc<T>(), dcol, 1, dQT.p, dout, d, s);
+                down(out, dout, size_t(d));
+                break;
+            }
+            T* work = scratch<T>(A->s_work, size_t(sweep_work_elems(d, d)));
             launch_sweep<T>(DenseView<T>{dQ, d, d, d}, Av.X + j * Av.ld, dout, 0, d, nullptr, nullptr, nullptr, false, work, s);
             down(out, dout, size_t(d));
             break;
@@ -809,12 +841,33 @@ void op_constraint(adelie_hip_design* A, int op, int64_t j, const T* in, const i
             DevBuf<T> dQ, dAQ, dC;
             dQ.reserve(size_t(d) * size_t(d)), dAQ.reserve(size_t(d) * size_t(m)), dC.reserve(size_t(m) * size_t(m));
             up(dQ.p, in, size_t(d) * size_t(d));
-            launch_ptq<T>(dQ.p, d, nullptr, int32_t(d), Av.X, Av.ld, nullptr, int32_t(m), d, dAQ.p, d, s);
-            launch_ptq<T>(dAQ.p, d, nullptr, int32_t(m), Av.X, Av.ld, nullptr, int32_t(m), d, dC.p, m, s);
+            if (sparse) { // over the stored entries (kernels_pinball_sparse.hip): the rows-times-dense kernel reads the transpose of
+                          // its matrix, so Q as it lies gives AQ[:, b] = Q A[b, :]', and out[a, b] = A[a, :] . AQ[:, b] = (A Q A')[a, b]
+                launch_csc_rows_dense<T>(A->csc<T>(), nullptr, m, dQ.p, dAQ.p, d, s);
+                launch_csc_rows_cols<T>(A->csc<T>(), nullptr, m, dAQ.p, d, m, dC.p, m, s);
+            } else {
+                launch_ptq<T>(dQ.p, d, nullptr, int32_t(d), Av.X, Av.ld, nullptr, int32_t(m), d, dAQ.p, d, s);
+                launch_ptq<T>(dAQ.p, d, nullptr, int32_t(m), Av.X, Av.ld, nullptr, int32_t(m), d, dC.p, m, s);
+            }
             down(out, dC.p, size_t(m) * size_t(m));
             break;
         }
         case ADELIE_HIP_CONS_TO_DENSE:
+            if (sparse) { // zeros plus the scattered entries (for tests and small matrices)
+                std::vector<int64_t> ptr(static_cast<size_t>(m) + 1);
+                std::vector<int32_t> idx(static_cast<size_t>(A->nnz));
+                std::vector<T> val(static_cast<size_t>(A->nnz));
+                AHIP_CHECK(hipMemcpyAsync(ptr.data(), A->cptr, ptr.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+                if (A->nnz) {
+                    AHIP_CHECK(hipMemcpyAsync(idx.data(), A->cidx, idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+                    AHIP_CHECK(hipMemcpyAsync(val.data(), A->cval, val.size() * sizeof(T), hipMemcpyDeviceToHost, s));
+                }
+                AHIP_CHECK(hipStreamSynchronize(s));
+                std::fill(out, out + size_t(m) * size_t(d), T(0));
+                for (int64_t r = 0; r < m; ++r)
+                    for (int64_t t = ptr[size_t(r)]; t < ptr[size_t(r) + 1]; ++t) out[r * d + idx[size_t(t)]] = val[size_t(t)];
+                break;
+            }
             AHIP_CHECK(hipMemcpy2DAsync(out, size_t(d) * sizeof(T), Av.X, size_t(Av.ld) * sizeof(T), size_t(d) * sizeof(T), size_t(m),
                                         hipMemcpyDeviceToHost, s));
             AHIP_CHECK(hipStreamSynchronize(s));
@@ -980,7 +1033,8 @@ int adelie_hip_constraint_op(adelie_hip_design* A, int op, int64_t j, const void
                              void* out) {
     ABI_TRY
     if (!A || !out) throw make_core_error("null argument.");
-    if (!A->constraint) throw make_core_error("A must be a constraint matrix (matrix.dense(method=\"constraint\")).");
+    if (!A->constraint || !(A->is_dense() || A->is_csc()))
+        throw make_core_error("A must be a constraint matrix (matrix.dense(method=\"constraint\")).");
     const int64_t m = A->p;
     if (op != ADELIE_HIP_CONS_TO_DENSE && !in) throw make_core_error("null argument.");
     if ((op == ADELIE_HIP_CONS_RVMUL || op == ADELIE_HIP_CONS_RVTMUL || op == ADELIE_HIP_CONS_RMMUL) && (j < 0 || j >= m))

@@ -207,6 +207,24 @@ int adelie_hip_design_create_csc(const int64_t* indptr, const int32_t* indices, 
     ABI_CATCH
 }
 
+// adelie.matrix.sparse(method="constraint"): the (m, d) matrix A kept sparse is the design kept sparse of the (d, m) matrix A'
+// with the constraint flag.  A's compressed rows are the compressed columns of A' and A's compressed columns its compressed
+// rows, so the two forms go to adelie_hip_design_create_csc as they are: a row of A is one compressed column.
+int adelie_hip_design_create_constraint_csc(const int64_t* row_indptr, const int32_t* row_indices, const void* row_values,
+                                            const int64_t* col_indptr, const int32_t* col_indices, const void* col_values, int64_t m,
+                                            int64_t d, int dtype, int device, adelie_hip_design** out) {
+    ABI_TRY
+    if (!out) throw make_core_error("null argument.");
+    if (m <= 0 || d <= 0) throw make_core_error("mat must be a non-empty (m, d) matrix.");
+    if (m >= (int64_t(1) << 31) || d >= (int64_t(1) << 31)) throw make_core_error("sparse(): m and d must be below 2^31.");
+    adelie_hip_design* g = nullptr;
+    if (adelie_hip_design_create_csc(row_indptr, row_indices, row_values, col_indptr, col_indices, col_values, d, m, dtype, device, &g))
+        throw make_core_error(g_last_error);
+    g->constraint = 1;
+    *out = g;
+    ABI_CATCH
+}
+
 int adelie_hip_design_create_snp_phased_ancestry(const void* snpdat, int64_t n_bytes, int dtype, int device, adelie_hip_design** out) {
     ABI_TRY
     if (!snpdat || !out) throw make_core_error("null argument.");
@@ -237,7 +255,7 @@ int adelie_hip_design_create_snp_phased_calldata(const int8_t* calldata, const i
 int adelie_hip_design_create_convex_relu_csc(adelie_hip_design* Z, const uint8_t* mask, int64_t m, int gated, adelie_hip_design** out) {
     ABI_TRY
     if (!Z || !out || (!mask && m > 0)) throw make_core_error("null argument.");
-    if (!Z->is_csc() || Z->std_center)
+    if (!Z->is_csc() || Z->std_center || Z->constraint)
         throw make_core_error("convex_relu(): mat must be a resident design kept sparse without a standardized view on it.");
     if (m < 0) throw make_core_error("mask must be (n, m) where mat is (n, d).");
     set_device(Z);

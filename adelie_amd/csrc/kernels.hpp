@@ -195,6 +195,17 @@ void launch_sp_tmul_snp(const SnpView& X, const T* impute, int64_t L, const int6
 template <class T>
 void launch_ptq(const T* P, int64_t ldp, const int32_t* pcols, int32_t M, const T* Q, int64_t ldq, const int32_t* qcols, int32_t N,
                 int64_t K, T* C, int64_t ldc, hipStream_t s);
+// The same products where the (d, m) matrix A' is kept sparse (kernels_pinball_sparse.hip), a row of A being compressed column
+// col of A (entries e, stored indices ascending); every element is one ascending sum in one accumulator, as in launch_ptq:
+//   AS[r + c*ld]  = sum_e val_e ST[r + idx_e*d],    r < d = A.n, c < N, col = cols ? cols[c] : c    (ST: S' column-major)
+//   C[r + c*ldc]  = sum_e val_e Q[idx_e + c*ldq],   r < M, c < N,       col = pcols ? pcols[r] : r
+template <class T>
+void launch_csc_rows_dense(const CscView<T>& A, const int32_t* cols, int64_t N, const T* ST, T* AS, int64_t ld, hipStream_t s);
+template <class T>
+void launch_csc_rows_cols(const CscView<T>& A, const int32_t* pcols, int64_t M, const T* Q, int64_t ldq, int64_t N, T* C,
+                          int64_t ldc, hipStream_t s);
+// out[c + r*d] = in[r + c*d]: the transposed copy of a (d, d) column-major matrix
+template <class T> void launch_transpose_square(const T* in, int64_t d, T* out, hipStream_t s);
 
 // ---- Gram (MFMA): for a in [0,M), b in [0,N):
 //   C[rowpos[a] + colpos[b]*ldc] = sum_i w[i] X[i,mcols[a]] X[i,ncols[b]]  - (center ? xm[mcols[a]]*xm[ncols[b]] : 0)

@@ -4,7 +4,10 @@
 //     minimise over beta in R^m   1/2 || S^{-1/2} v - S^{1/2} A' beta ||^2 + penalty_neg' beta_- + penalty_pos' beta_+
 //
 // The handle holds A (m, d) row-major, i.e. the (d, m) column-major matrix A' of a dense design: the full gradient A resid is
-// launch_sweep over the m columns, a row of A is one contiguous column.
+// launch_sweep over the m columns, a row of A is one contiguous column.  A matrix kept sparse
+// (adelie_hip_design_create_constraint_csc) is the kCsc design of A' in the same sense: the full gradient is launch_sweep_csc,
+// a row of A one compressed column, and the products of extend() below come from kernels_pinball_sparse.hip, term for term
+// those of the dense route.  Everything after them (H, the compact AS, the fit kernel, the catch-up) is dense either way.
 //
 // The reference visits one coordinate at a time and pays a d-long dot per visit (rvmul for the gradient) plus a d-long update
 // of the residual when the visit changes the coefficient.  Here the gradient g_a = A[a, :] . resid of EVERY screen coordinate
@@ -196,10 +199,11 @@ struct PinballSolver : CdScreenDriver<T, PinballSolver<T>, adelie_hip_pinball_ar
 
     adelie_hip_pinball_result* pres;
     const int64_t d, m;
-    DevBuf<T> d_S, d_pneg, d_ppos, d_AS;
+    const bool sparse; // A is kept sparse: Xv is null and stays unused
+    DevBuf<T> d_S, d_ST, d_pneg, d_ppos, d_AS;
 
     PinballSolver(adelie_hip_design* A, const adelie_hip_pinball_args* a_, adelie_hip_pinball_result* r)
-        : Base(A, a_, r), pres(r), d(A->n), m(A->p) {}
+        : Base(A, a_, r), pres(r), d(A->n), m(A->p), sparse(A->is_csc()) {}
 
     void upload() {
         d_S.reserve(size_t(d) * size_t(d)), d_pneg.reserve(size_t(m)), d_ppos.reserve(size_t(m));
@@ -208,13 +212,22 @@ struct PinballSolver : CdScreenDriver<T, PinballSolver<T>, adelie_hip_pinball_ar
         d_beta.upload(static_cast<const T*>(a->beta), size_t(m), s);
         d_pneg.upload(static_cast<const T*>(a->penalty_neg), size_t(m), s);
         d_ppos.upload(static_cast<const T*>(a->penalty_pos), size_t(m), s);
+        if (sparse) { // S' for the rows-times-S kernel, whose lanes run along a row of S
+            d_ST.reserve(size_t(d) * size_t(d));
+            launch_transpose_square<T>(d_S.p, d, d_ST.p, s);
+        }
     }
     void grow_extra(size_t c, size_t keep) { d_AS.grow(c * size_t(d), keep * size_t(d), s); }
     // out[c] = A[col(c), :] . resid
     void sweep(const int32_t* cols, int64_t ncols, T* out) {
         timer.begin(PH_SWEEP, s);
-        T* work = d_work_sweep.reserve(size_t(sweep_work_elems(d, ncols)));
-        launch_sweep<T>(Xv, d_r.p, out, 0, ncols, cols, nullptr, nullptr, false, work, s);
+        if (sparse) {
+            T* work = d_work_sweep.reserve(size_t(sweep_work_elems_csc(Base::X->sp_parts(), ncols)));
+            launch_sweep_csc<T>(Base::X->template csc<T>(), d_r.p, out, 0, ncols, cols, nullptr, nullptr, false, work, s);
+        } else {
+            T* work = d_work_sweep.reserve(size_t(sweep_work_elems(d, ncols)));
+            launch_sweep<T>(Xv, d_r.p, out, 0, ncols, cols, nullptr, nullptr, false, work, s);
+        }
         timer.end(s);
     }
     void viols() {
@@ -227,6 +240,14 @@ struct PinballSolver : CdScreenDriver<T, PinballSolver<T>, adelie_hip_pinball_ar
         const int64_t N = ns_new - ns_old;
         if (N <= 0) return;
         timer.begin(PH_GRAM, s);
+        if (sparse) {
+            const CscView<T> Av = Base::X->template csc<T>();
+            launch_csc_rows_dense<T>(Av, d_cols.p + ns_old, N, d_ST.p, d_AS.p + ns_old * d, d, s);
+            launch_csc_rows_cols<T>(Av, d_cols.p, ns_new, d_AS.p + ns_old * d, d, N, d_G.p + ns_old * ld, ld, s);
+            if (ns_old > 0) launch_csc_rows_cols<T>(Av, d_cols.p + ns_old, N, d_AS.p, d, ns_old, d_G.p + ns_old, ld, s);
+            timer.end(s);
+            return;
+        }
         launch_ptq<T>(d_S.p, d, nullptr, int32_t(d), Xv.X, Xv.ld, d_cols.p + ns_old, int32_t(N), d, d_AS.p + ns_old * d, d, s);
         launch_ptq<T>(Xv.X, Xv.ld, d_cols.p, int32_t(ns_new), d_AS.p + ns_old * d, d, nullptr, int32_t(N), d, d_G.p + ns_old * ld,
                       ld, s);
@@ -263,7 +284,7 @@ extern "C" {
 
 int adelie_hip_pinball_solve(adelie_hip_design* A, const adelie_hip_pinball_args* a, adelie_hip_pinball_result** out) {
     return cd_screen_solve<PinballSolver>(A, a, out, [&] {
-        if (!A->constraint || !A->is_dense())
+        if (!A->constraint || !(A->is_dense() || A->is_csc()))
             throw make_core_error("A must be a constraint matrix (matrix.dense(method=\"constraint\")).");
         const int64_t d = A->n, m = A->p;
         // state_pinball.ipp:15-94

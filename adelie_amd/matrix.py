@@ -1247,6 +1247,10 @@ _SPARSE_AUTO_DENSE_BYTES = 32 << 30
 def sparse(mat, *, method: str = "naive", copy: bool = False, n_threads: int = 1, device: int = 0, resident: str = "auto"):
     """Creates a design from a scipy sparse matrix (reference ``adelie.matrix.sparse``, ``matrix.py:1301-1385``).
 
+    ``method="cov"`` takes a symmetric ``(p, p)`` matrix for ``gaussian_cov``; ``method="constraint"`` an ``(m, d)`` constraint
+    matrix for ``pinball`` and ``constraint.linear``, kept sparse in HBM (reference ``MatrixConstraintSparse``; ``resident``
+    is ignored): a ``csc_matrix`` is converted to CSR with the reference's warning, duplicates are summed, and the result has
+    the ``MatrixConstraintBase64/32`` operations over the stored entries.  For ``method="naive"``,
     ``resident`` chooses what lives in HBM:
 
     * ``"csc"`` — the matrix stays sparse, as in the reference (``matrix_naive_sparse.ipp`` walks the CSC arrays per
@@ -1267,8 +1271,10 @@ def sparse(mat, *, method: str = "naive", copy: bool = False, n_threads: int = 1
         if mat.shape[0] != mat.shape[1]:
             raise RuntimeError("adelie_core: mat must be (p, p).")
         return _cov_dense(_abi.hip_backend(), "design_create_cov_dense", np.asfortranarray(mat.toarray()), n_threads, device)
+    if method == "constraint":
+        return _constraint_sparse(_abi.hip_backend(), mat, copy, n_threads, device)
     if method != "naive":
-        raise ValueError("method must be one of 'naive' or 'cov'.")
+        raise ValueError("method must be one of 'naive' or 'cov', or 'constraint' for a constraint matrix.")
     if n_threads < 1:
         raise RuntimeError("adelie_core: n_threads must be >= 1.")
     if isinstance(mat, csr_matrix):
@@ -1941,6 +1947,54 @@ def _constraint_dense(backend, mat, n_threads, device):
     cls = type("_constraint_matrix", (_ConstraintMatrix, base), {"dtype": base.dtype})
     obj = cls()
     obj._init_native(backend, handle, n_threads, keep)
+    return obj
+
+
+class _ConstraintMatrixSparse(_ConstraintMatrix):
+    """An ``(m, d)`` constraint matrix kept sparse in HBM (``adelie.matrix.sparse(method="constraint")``, reference
+    ``MatrixConstraintSparse``, ``matrix_constraint_sparse.ipp``): the handle is the design kept sparse of ``A'``, a row of ``A``
+    one compressed column.  The operations are :class:`_ConstraintMatrix`'s, the same C call over the stored entries, and
+    ``solver.pinball`` solves on it natively; ``to_dense()`` (zeros and the stored entries) is for tests and small matrices.
+    The canonical host ``csr_matrix`` is kept in ``_scipy`` (``constraint.linear`` reads it)."""
+
+
+def _constraint_sparse(backend, mat, copy, n_threads, device):
+    """``adelie.matrix.sparse(mat, method="constraint")``: the canonical CSR of ``A`` and its CSC go to HBM as the design kept
+    sparse of ``A'`` (``adelie_hip_design_create_constraint_csc``)."""
+    if n_threads < 1:
+        raise RuntimeError("adelie_core: n_threads must be >= 1.")
+    if not backend.has("design_create_constraint_csc"):
+        raise RuntimeError(f"{backend.path}: no adelie_hip_design_create_constraint_csc -- rebuild the library.")
+    if isinstance(mat, csc_matrix):
+        warnings.warn("Converting to CSR format.")
+        mat = mat.tocsr(copy=True)
+    elif copy or not mat.has_canonical_format:
+        mat = mat.copy()
+    mat.prune()
+    mat.sort_indices()
+    mat.sum_duplicates()
+    dtype = np.dtype(mat.dtype).type
+    if dtype not in (np.float32, np.float64):
+        raise RuntimeError("mat must have dtype float32 or float64.")
+    m, d = mat.shape
+    cols = mat.tocsc()
+    cols.sort_indices()
+    r_ptr = np.ascontiguousarray(mat.indptr, dtype=np.int64)
+    r_idx = np.ascontiguousarray(mat.indices, dtype=np.int32)
+    r_val = np.ascontiguousarray(mat.data, dtype=dtype)
+    c_ptr = np.ascontiguousarray(cols.indptr, dtype=np.int64)
+    c_idx = np.ascontiguousarray(cols.indices, dtype=np.int32)
+    c_val = np.ascontiguousarray(cols.data, dtype=dtype)
+    handle = _abi.C.c_void_p()
+    backend.check(backend.fn("design_create_constraint_csc")(
+        r_ptr.ctypes.data, r_idx.ctypes.data, r_val.ctypes.data, c_ptr.ctypes.data, c_idx.ctypes.data, c_val.ctypes.data,
+        m, d, _abi.dtype_code(dtype), device, handle))
+    base = MatrixConstraintBase64 if dtype == np.float64 else MatrixConstraintBase32
+    cls = type("_constraint_matrix_sparse", (_ConstraintMatrixSparse, base), {"dtype": base.dtype})
+    obj = cls()
+    obj._init_native(backend, handle, n_threads, None)
+    obj._scipy = mat
+    obj._device = device
     return obj
 
 

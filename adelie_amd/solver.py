@@ -582,7 +582,9 @@ def pinball(
 
     An ndarray (or device tensor) ``A`` goes through ``matrix.dense(method="constraint")`` and is solved by the reference's
     coordinate descent run by one workgroup on the device: the gradients of all screen coordinates are kept current through
-    the resident matrix ``A_S S A_S'``, so a visit costs one column of it instead of a ``d``-long dot.  Any other
+    the resident matrix ``A_S S A_S'``, so a visit costs one column of it instead of a ``d``-long dot.  A large constraint set
+    whose rows touch a few of the ``d`` variables is passed as ``matrix.sparse(csr, method="constraint")``: it stays sparse in HBM,
+    the same solve runs on it, and ``A_S S`` and ``A_S S A_S'`` are built over the stored entries only.  Any other
     ``MatrixConstraintBase64/32`` subclass takes the same loop in Python over its ``rvmul`` / ``rmmul`` / ``tmul``: slow, and
     meant for coverage rather than speed (``state.pinball``)."""
     if isinstance(A, np.ndarray) or type(A).__module__.startswith("torch"):

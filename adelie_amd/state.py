@@ -1623,8 +1623,8 @@ class bvls(_ScreenSetState):
 
 
 def _pinball_native(A):
-    """Whether ``A`` is the resident constraint matrix, i.e. what ``adelie_hip_pinball_solve`` accepts."""
-    return isinstance(A, _matrix._ConstraintMatrix)
+    """Whether ``A`` is a resident constraint matrix, dense or kept sparse, i.e. what ``adelie_hip_pinball_solve`` accepts."""
+    return isinstance(A, _matrix._ConstraintMatrix)  # (_ConstraintMatrixSparse derives from it)
 
 
 class pinball(_ScreenSetState):
@@ -1638,8 +1638,8 @@ class pinball(_ScreenSetState):
     untouched.  ``screen_ASAT_diag`` / ``screen_AS`` may be ``None``: the solve then computes them for the given screen set,
     as ``solver.pinball`` does before it constructs the reference's state.
 
-    The resident constraint matrix (``matrix.dense(method="constraint")``) is solved on the device by
-    ``adelie_hip_pinball_solve``; ``screen_AS`` ``(m, d)`` and ``screen_ASAT_diag`` ``(m,)`` (filled in the rows of screen
+    The resident constraint matrix (``matrix.dense(method="constraint")``, or kept sparse:
+    ``matrix.sparse(method="constraint")``) is solved on the device by ``adelie_hip_pinball_solve``; ``screen_AS`` ``(m, d)`` and ``screen_ASAT_diag`` ``(m,)`` (filled in the rows of screen
     members only, as in the reference; zero elsewhere) are then materialised from the compact device copy on first access.
     Every other ``MatrixConstraintBase64/32`` subclass takes the same loop written in Python over its ``rvmul`` / ``rmmul`` /
     ``tmul``, which is what the reference does through its matrix interface.  That route is slow and exists for coverage."""

@@ -767,6 +767,18 @@ int adelie_hip_design_create_constraint_dense(const void* host, int64_t m, int64
                                               adelie_hip_design** out);
 int adelie_hip_design_adopt_constraint_dense_dev(const void* dev_ptr, int64_t m, int64_t d, int dtype, int order, int device,
                                                  adelie_hip_design** out);
+/* Additive entry point (the ABI version stays 14; callers look the symbol up).  Replaces MatrixConstraintSparse{32,64}
+ * (adelie.matrix.sparse(method="constraint"), adelie/matrix.py:1301-1411, matrix_constraint_sparse.ipp): the (m, d) matrix A kept
+ * sparse.  A is given twice in canonical form (sorted distinct indices), row-compressed (row_indptr of m + 1) and
+ * column-compressed (col_indptr of d + 1) -- the pair adelie_hip_design_create_csc takes for the (d, m) matrix A', whose
+ * compressed columns are A's rows.  The handle is that design kept sparse (design_rows == d, design_cols == m, 24 bytes per
+ * stored entry in f64) with the `constraint` flag: a row of A is one compressed column.  It is taken and refused exactly where
+ * the dense constraint handle is: adelie_hip_constraint_op (all operations; rmmul, cov and the solve's A_S S and A_S S A_S' run
+ * over the stored entries, kernels_pinball_sparse.hip) and adelie_hip_pinball_solve take it, every naive entry point refuses it.
+ * m and d must be positive and below 2^31. */
+int adelie_hip_design_create_constraint_csc(const int64_t* row_indptr, const int32_t* row_indices, const void* row_values,
+                                            const int64_t* col_indptr, const int32_t* col_indices, const void* col_values, int64_t m,
+                                            int64_t d, int dtype, int device, adelie_hip_design** out);
 /* The MatrixConstraintBase operations; all vectors are host pointers of the handle's dtype.  None of them is a hot path. */
 enum adelie_hip_constraint_op_kind {
     ADELIE_HIP_CONS_TMUL = 0,    /* out (m,) = A in,  in (d,) */
