@@ -219,6 +219,8 @@ S = dict(
     n_screen_reads=93, n_screen_short=94, n_filter_open_cols=95,
 )
 
+# adelie_hip_cov_piece
+COV_PIECE_GATHER, COV_PIECE_GRAD = range(2)
 # adelie_hip_group_piece_mode
 GROUP_EIG, GROUP_ROTATE, GROUP_LAYOUT, GROUP_PANEL_SOLVE, GROUP_GRAM_PASS = range(5)
 GDESC = dict(VMAP=0, VGRP=128, VSS=256, GOFF=384, GQ=520, GSS=648, NG=776, NVAL=777, VOFF=784, VPOS=912, VQ=1040, STRIDE=1168)
@@ -254,10 +256,10 @@ HIP_SYMBOLS = [
     "design_device", "design_stream",
     "design_cmul", "design_ctmul", "design_bmul", "design_btmul", "design_mul", "design_mul_batch", "design_cov",
     "design_sq_mul", "design_sp_tmul",
-    "design_create_cov_dense", "design_create_cov_lazy", "design_cov_bmul", "design_cov_mul", "design_cov_to_dense", "gaussian_cov_solve",
+    "design_create_cov_dense", "design_create_cov_csc", "design_create_cov_lazy", "design_cov_bmul", "design_cov_mul", "design_cov_to_dense", "gaussian_cov_solve",
     "glm_cox_create", "glm_cox_destroy", "glm_cox_eval",
     "grpnet_solve", "grpnet_solve_many", "result_destroy", "result_size", "result_copy", "result_scalar", "result_error", "result_sync",
-    "bench_sweep", "filter_sweep_test", "block_build_test", "group_piece_test",
+    "bench_sweep", "filter_sweep_test", "block_build_test", "group_piece_test", "cov_piece_test",
     "css_cov_solve", "css_result_destroy", "css_result_size", "css_result_copy", "css_result_scalar", "css_result_error",
     "bvls_solve", "bvls_result_destroy", "bvls_result_size", "bvls_result_copy", "bvls_result_scalar", "bvls_result_error",
     "design_create_constraint_dense", "design_adopt_constraint_dense_dev", "design_create_constraint_csc", "constraint_op",
@@ -367,6 +369,7 @@ class Backend:
         sig("grpnet_solve_many", ci, [p(vp), p(p(GrpnetArgs)), C.c_int32, p(vp), DONE_FN, vp])
         sig("gaussian_cov_solve", ci, [vp, p(GrpnetArgs), p(vp)])
         sig("design_create_cov_dense", ci, [vp, i64, ci, ci, ci, p(vp)])
+        sig("design_create_cov_csc", ci, [vp, vp, vp, i64, ci, ci, p(vp)])
         sig("design_create_cov_lazy", ci, [vp, p(vp)])
         sig("design_cov_bmul", ci, [vp, vp, i64, vp, vp, i64, vp])
         sig("design_cov_mul", ci, [vp, vp, vp, i64, vp])
@@ -381,6 +384,7 @@ class Backend:
         sig("filter_sweep_test", ci, [vp, vp, vp, dbl, vp, vp, i64, vp, vp, i64, vp, dbl, vp, vp, vp])
         sig("block_build_test", ci, [vp, ci, i64, vp, vp, i64, vp, i64, vp, ci, i64, ci, vp, i64, vp, i64, vp])
         sig("group_piece_test", ci, [p(GroupPiece), vp])
+        sig("cov_piece_test", ci, [vp, ci, vp, i64, i64, i64, i64, dbl, vp, vp, vp, i64, vp])
         sig("css_cov_solve", ci, [vp, p(CssArgs), p(vp)])
         sig("css_result_destroy", ci, [vp])
         sig("css_result_size", i64, [vp, ci])

@@ -501,6 +501,11 @@ struct adelie_hip_design {
     // covariance-method matrix A (adelie_hip_design_create_cov_dense): a dense (p, p) design with n == p that only
     // adelie_hip_gaussian_cov_solve and the cov_* operations accept; cov == 2: the stored matrix is A^T (row-major input)
     int cov = 0;
+    // ... or kept sparse (adelie_hip_design_create_cov_csc): kind is kCsc with the column-compressed arrays cptr / cidx / cval
+    // only -- the row arrays, block pointers and tile copy stay null, so whatever reads those must test `cov` first;
+    // cov_lanes is the lane group of kernels_cov_sparse.hip
+    int cov_lanes = 0;
+    bool cov_csc() const { return cov != 0 && kind == kCsc; }
     // constraint matrix (adelie_hip_design_create_constraint_dense / _csc): this dense or kCsc handle is the (d, m) matrix A' of an
     // (m, d) constraint matrix A, so n == d and p == m; only adelie_hip_constraint_op and adelie_hip_pinball_solve accept it
     int constraint = 0;
@@ -590,6 +595,9 @@ struct adelie_hip_design {
         return ahip::CscView<T>{cptr, cidx, static_cast<const T*>(cval), rptr, rcol, static_cast<const T*>(rval), n, p, nnz,
                                 bptr, sp_nb, sp_rb, static_cast<const T*>(std_center), static_cast<const T*>(std_iscale),
                                 tptr, trow, static_cast<const T*>(tval), sp_nt, sp_th};
+    }
+    template <class T> ahip::CovCscView<T> cov_csc_view() const {
+        return ahip::CovCscView<T>{cptr, cidx, static_cast<const T*>(cval), p, cov_lanes};
     }
     bool factor() const { return fblk != nullptr; }
     template <class T> ahip::FactorView<T> factor_view() const {

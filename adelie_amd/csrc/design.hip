@@ -8,6 +8,7 @@
 #include "common.hpp"
 #include "design_ops.hpp"
 #include "csc_build_host.hpp"
+#include "cov_csc_host.hpp"
 #include "phased_decode_host.hpp"
 #include "snp_decode_host.hpp"
 
@@ -710,6 +711,17 @@ void adelie_hip_internal_free_batcher(void* b); // solver.hip
 void adelie_hip_internal_batch_stats(void* b, double* out);
 
 namespace {
+// A matrix kept sparse (kernels_cov_sparse.hip): the dense (p,) vector its column dots read, values[i] summed at indices[i] on
+// the host (an index that repeats adds up, as in the dense kernels) and uploaded into s_work.  Not a hot path.
+template <class T>
+const T* cov_csc_upload_w(adelie_hip_design* d, const int64_t* indices, const T* values, int64_t ni) {
+    std::vector<T> w(size_t(d->p), T(0));
+    for (int64_t k = 0; k < ni; ++k) w[size_t(indices[k])] += values[k];
+    T* dw = scratch<T>(d->s_work, size_t(d->p));
+    AHIP_CHECK(hipMemcpyAsync(dw, w.data(), size_t(d->p) * sizeof(T), hipMemcpyHostToDevice, d->stream));
+    AHIP_CHECK(hipStreamSynchronize(d->stream)); // (w goes out of scope)
+    return dw;
+}
 template <class T>
 void op_cov_bmul(adelie_hip_design* d, const int64_t* subset, int64_t ns, const int64_t* indices, const T* values, int64_t ni,
                  T* out) {
@@ -722,7 +734,8 @@ void op_cov_bmul(adelie_hip_design* d, const int64_t* subset, int64_t ns, const 
     AHIP_CHECK(hipMemcpyAsync(dsub, subset, size_t(ns) * sizeof(int64_t), hipMemcpyHostToDevice, s));
     AHIP_CHECK(hipMemcpyAsync(dind, indices, size_t(ni) * sizeof(int64_t), hipMemcpyHostToDevice, s));
     AHIP_CHECK(hipMemcpyAsync(dval, values, size_t(ni) * sizeof(T), hipMemcpyHostToDevice, s));
-    launch_cov_bmul<T>(static_cast<const T*>(d->X), d->ld, d->cov == 2, dsub, ns, dind, dval, ni, dout, s);
+    if (d->cov_csc()) launch_cov_csc_coldot<T>(d->cov_csc_view<T>(), dsub, ns, cov_csc_upload_w<T>(d, indices, values, ni), nullptr, dout, s);
+    else launch_cov_bmul<T>(static_cast<const T*>(d->X), d->ld, d->cov == 2, dsub, ns, dind, dval, ni, dout, s);
     AHIP_CHECK(hipMemcpyAsync(out, dout, size_t(ns) * sizeof(T), hipMemcpyDeviceToHost, s));
     AHIP_CHECK(hipStreamSynchronize(s));
 }
@@ -735,13 +748,21 @@ void op_cov_mul(adelie_hip_design* d, const int64_t* indices, const T* values, i
     T* dout = scratch<T>(d->s_p1, d->p);
     AHIP_CHECK(hipMemcpyAsync(dind, indices, size_t(ni) * sizeof(int64_t), hipMemcpyHostToDevice, s));
     AHIP_CHECK(hipMemcpyAsync(dval, values, size_t(ni) * sizeof(T), hipMemcpyHostToDevice, s));
-    launch_cov_mul<T>(static_cast<const T*>(d->X), d->ld, d->p, dind, dval, ni, dout, s);
+    if (d->cov_csc()) launch_cov_csc_coldot<T>(d->cov_csc_view<T>(), nullptr, d->p, cov_csc_upload_w<T>(d, indices, values, ni), nullptr, dout, s);
+    else launch_cov_mul<T>(static_cast<const T*>(d->X), d->ld, d->p, dind, dval, ni, dout, s);
     AHIP_CHECK(hipMemcpyAsync(out, dout, size_t(d->p) * sizeof(T), hipMemcpyDeviceToHost, s));
     AHIP_CHECK(hipStreamSynchronize(s));
 }
 template <class T>
 void op_cov_to_dense(adelie_hip_design* d, int64_t i, int64_t q, T* out) {
     set_device(d);
+    if (d->cov_csc()) { // zeros and the stored entries of the block
+        T* dout = scratch<T>(d->s_p1, size_t(q) * size_t(q));
+        launch_cov_csc_to_dense<T>(d->cov_csc_view<T>(), i, q, dout, d->stream);
+        AHIP_CHECK(hipMemcpyAsync(out, dout, size_t(q) * size_t(q) * sizeof(T), hipMemcpyDeviceToHost, d->stream));
+        AHIP_CHECK(hipStreamSynchronize(d->stream));
+        return;
+    }
     const T* S = static_cast<const T*>(d->X);
     AHIP_CHECK(hipMemcpy2DAsync(out, size_t(q) * sizeof(T), S + i + i * d->ld, size_t(d->ld) * sizeof(T), size_t(q) * sizeof(T),
                                 size_t(q), hipMemcpyDeviceToHost, d->stream));
@@ -910,6 +931,37 @@ int adelie_hip_design_create_cov_dense(const void* host, int64_t p, int dtype, i
     ABI_CATCH
 }
 
+// adelie.matrix.sparse(method="cov", resident="csc") / block_diag(method="cov", resident="csc"): the column-compressed form of
+// the symmetric (p, p) matrix and nothing else (cov_csc_host.hpp has the checks; kernels_cov_sparse.hip the operations).  A kCsc
+// handle with the row arrays, block pointers and tile copy left null.
+int adelie_hip_design_create_cov_csc(const int64_t* indptr, const int32_t* indices, const void* values, int64_t p, int dtype, int device,
+                                     adelie_hip_design** out) {
+    ABI_TRY
+    if (!indptr || !out) throw make_core_error("null argument.");
+    if (p <= 0) throw make_core_error("mat must be (p, p).");
+    if (const char* e = cov_csc_validate(indptr, indices, values, p)) throw make_core_error(e);
+    const int64_t nnz = indptr[p];
+    DesignGuard g(new_design(p, p, dtype, device));
+    adelie_hip_design* d = g.get();
+    const size_t vs = dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
+    const size_t nz1 = size_t(std::max<int64_t>(nnz, 1));
+    d->kind = adelie_hip_design::kCsc;
+    d->cov = 1;
+    d->nnz = nnz;
+    d->cov_lanes = cov_csc_lanes(nnz, p);
+    hipStream_t s = d->stream;
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cptr), size_t(p + 1) * sizeof(int64_t)));
+    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cidx), nz1 * sizeof(int32_t)));
+    AHIP_CHECK(hipMalloc(&d->cval, nz1 * vs));
+    AHIP_CHECK(hipMemcpyAsync(d->cptr, indptr, size_t(p + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    if (nnz) {
+        AHIP_CHECK(hipMemcpyAsync(d->cidx, indices, size_t(nnz) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        AHIP_CHECK(hipMemcpyAsync(d->cval, values, size_t(nnz) * vs, hipMemcpyHostToDevice, s));
+    }
+    AHIP_CHECK(hipStreamSynchronize(s));
+    *out = g.release();
+    ABI_CATCH
+}
 
 int adelie_hip_design_create_cov_lazy(adelie_hip_design* X, adelie_hip_design** out) {
     ABI_TRY

@@ -255,7 +255,7 @@ int adelie_hip_design_create_snp_phased_calldata(const int8_t* calldata, const i
 int adelie_hip_design_create_convex_relu_csc(adelie_hip_design* Z, const uint8_t* mask, int64_t m, int gated, adelie_hip_design** out) {
     ABI_TRY
     if (!Z || !out || (!mask && m > 0)) throw make_core_error("null argument.");
-    if (!Z->is_csc() || Z->std_center || Z->constraint)
+    if (!Z->is_csc() || Z->cov || Z->std_center || Z->constraint)
         throw make_core_error("convex_relu(): mat must be a resident design kept sparse without a standardized view on it.");
     if (m < 0) throw make_core_error("mask must be (n, m) where mat is (n, d).");
     set_device(Z);
@@ -268,6 +268,8 @@ int adelie_hip_design_csc_download(adelie_hip_design* d, int64_t* indptr, int32_
     ABI_TRY
     if (!d) throw make_core_error("null argument.");
     if (!d->is_csc()) throw make_core_error("csc_download() takes a design kept sparse.");
+    if (d->cov && (row_indptr || row_indices || row_values))
+        throw make_core_error("csc_download(): a covariance matrix kept sparse has the column-compressed form only.");
     set_device(d);
     hipStream_t s = d->stream;
     const size_t vs = d->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float), nnz = size_t(d->nnz);

@@ -1,5 +1,6 @@
 // design_ops.hpp — the raw operations on a resident design (sweep, Gram, axpy, sp_tmul), dispatched over its storage kind in
-// one place.  Host only: design.hip and solver.hip include it, no kernel file does.
+// one place, and the two reads of a covariance-method matrix (dense or kept sparse) at the end.  Host only: design.hip and
+// solver.hip include it, no kernel file does.
 // "Raw" is what the stored matrix gives.  A standardized view of a dense / 2-bit design composes its epilogues around these
 // calls (solver_screen.hpp: sweep / gram / axpy_cols); one over compressed columns is handled inside the csc kernels, whose
 // CscView carries the centers and scales.  The multi-response view has K-wide kernels of its own (the solver calls them) and
@@ -80,6 +81,28 @@ void raw_sp_tmul(const adelie_hip_design& d, int64_t L, const int64_t* indptr, c
     else if (d.is_snp()) launch_sp_tmul_snp<T>(d.snp(), snp_impute<T>(d), L, indptr, indices, values, out, s);
     else if (d.is_csc()) launch_sp_tmul_csc<T>(d.csc<T>(), L, indptr, indices, values, out, work, s);
     else throw multi_view_error();
+}
+
+// ---- covariance method: the two places the path solver touches A, over its storage (kernels_cov.hip, kernels_cov_sparse.hip) ----
+// C[a, pos0 + b] = A(vcol[a], vcol[pos0 + b]) for a < nv, b < N, mirrored for the old values.  `pos` is the caller's (p,) int32
+// scratch, read on a matrix kept sparse only.
+template <class T>
+void raw_cov_gather(const adelie_hip_design& d, const int32_t* vcol, int32_t nv, int32_t pos0, int32_t N, T* C, int64_t ldc,
+                    int32_t* pos, hipStream_t s) {
+    if (d.cov_csc()) launch_cov_csc_gather<T>(d.cov_csc_view<T>(), vcol, nv, pos0, N, C, ldc, pos, s);
+    else launch_cov_gather<T>(static_cast<const T*>(d.X), d.ld, d.cov == 2, vcol, nv, pos0, N, C, ldc, s);
+}
+// grad = v - sum_k coef[k] A[:, cols[k]] for k < *cnt (on the device; at most max_cnt).  `w` is the caller's (p,) scratch, read
+// on a matrix kept sparse only.
+template <class T>
+void raw_cov_grad(const adelie_hip_design& d, const T* v, const int32_t* cols, const T* coef, const int32_t* cnt, int64_t max_cnt,
+                  T* grad, T* w, hipStream_t s) {
+    if (d.cov_csc()) {
+        launch_cov_csc_fill_w<T>(cols, coef, cnt, max_cnt, w, d.p, s);
+        launch_cov_csc_coldot<T>(d.cov_csc_view<T>(), nullptr, d.p, w, v, grad, s);
+    } else {
+        launch_cov_grad<T>(static_cast<const T*>(d.X), d.ld, d.p, v, cols, coef, cnt, grad, s);
+    }
 }
 
 } // namespace ahip

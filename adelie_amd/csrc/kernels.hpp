@@ -719,6 +719,31 @@ void launch_cov_mul(const T* S, int64_t lda, int64_t p, const int64_t* indices, 
 template <class T>
 void launch_cov_grad(const T* S, int64_t lda, int64_t p, const T* v, const int32_t* cols, const T* coef, const int32_t* cnt,
                      T* grad, hipStream_t s);
+// covariance-method matrix kept sparse (kernels_cov_sparse.hip): the column-compressed form of the symmetric (p, p) matrix;
+// `lanes` (4, 16 or 64; cov_csc_host.hpp) is the group that walks one column
+template <class T>
+struct CovCscView {
+    const int64_t* cptr;
+    const int32_t* cidx;
+    const T* cval;
+    int64_t p;
+    int lanes;
+};
+// w (p,) = 0, then w[cols[k]] = coef[k] for k < *cnt (read on the device; at most max_cnt, distinct columns)
+template <class T>
+void launch_cov_csc_fill_w(const int32_t* cols, const T* coef, const int32_t* cnt, int64_t max_cnt, T* w, int64_t p, hipStream_t s);
+// out[jj] = (base ? base[j] - dot : dot), dot = sum over the stored entries of column j of cval[e] * w[cidx[e]], j = subset ?
+// subset[jj] : jj, for jj < ncols
+template <class T>
+void launch_cov_csc_coldot(const CovCscView<T>& A, const int64_t* subset, int64_t ncols, const T* w, const T* base, T* out,
+                           hipStream_t s);
+// launch_cov_gather's cells from the stored entries; `pos` is a (p,) scratch the launcher fills itself
+template <class T>
+void launch_cov_csc_gather(const CovCscView<T>& A, const int32_t* vcol, int32_t nv, int32_t pos0, int32_t N, T* C, int64_t ldc,
+                           int32_t* pos, hipStream_t s);
+// out (q, q) column-major on the device = A[i:i+q, i:i+q]
+template <class T>
+void launch_cov_csc_to_dense(const CovCscView<T>& A, int64_t i, int64_t q, T* out, hipStream_t s);
 template <class T> void launch_copy2d(const T* src, int64_t lds, T* dst, int64_t ldd, int64_t rows, int64_t cols, hipStream_t s);
 // vars[pos0 + a] = max(C[(pos0+a)*(ldc+1)], 0) for a < cnt   (gs == 1 groups)
 // Appending new screen groups to the device mirrors (solver.hip::device_append_screen): ONE packed upload + one scatter

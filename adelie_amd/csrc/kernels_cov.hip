@@ -6,6 +6,8 @@
 // (kernels_cd.hip, kernels_cd_lasso.hip, kernels_cd_block*.hip) iterate on — for the naive method that matrix is built by an
 // MFMA kernel from X, here it is a gather: 8 bytes read and written per entry, HBM-bound, no flops.
 // `tr` != 0: the stored matrix is the transpose of A (a row-major input uploaded as is), A(i, j) = S[j + i * lda].
+// A matrix kept sparse (adelie_hip_design_create_cov_csc) has the same four operations over its stored entries in
+// kernels_cov_sparse.hip; design_ops.hpp (raw_cov_gather / raw_cov_grad) and design.hip (op_cov_*) dispatch on the storage.
 #include "kernels.hpp"
 
 namespace ahip {

@@ -599,6 +599,8 @@ int adelie_hip_css_cov_solve(adelie_hip_design* A, const adelie_hip_css_args* a,
     try {
         if (!A || !a || !out) throw make_core_error("null argument.");
         if (!A->cov) throw make_core_error("S must be a covariance matrix (matrix.dense(method=\"cov\")).");
+        if (A->cov_csc()) // (the solve keeps a dense (p, p) residual of S anyway)
+            throw make_core_error("css_cov works on a dense covariance matrix: use matrix.sparse(..., method=\"cov\", resident=\"dense\").");
         // state_css_cov.ipp:15-57
         if (A->n != A->p) throw make_core_error("S must be (p, p).");
         if (a->subset_size < 0 || a->subset_size > A->p) throw make_core_error("subset_size must be <= p.");

@@ -795,6 +795,7 @@ int adelie_hip_result_sync(const adelie_hip_result* live) {
 int adelie_hip_bench_sweep(adelie_hip_design* d, int64_t reps, double* ms_per_launch) {
     try {
         if (!d || !ms_per_launch || reps <= 0) throw make_core_error("bad arguments.");
+        if (d->cov_csc()) throw make_core_error("bench_sweep takes a design matrix, not a covariance matrix kept sparse.");
         AHIP_CHECK(hipSetDevice(d->device));
         hipStream_t s = d->stream;
         auto body = [&](auto tag) {
@@ -1278,6 +1279,68 @@ int adelie_hip_group_piece_test(const adelie_hip_group_piece* a, int64_t* info) 
         else body(float{});
         info[0] = launches;
         info[1] = rot_wide ? 1 : 0;
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return 1;
+    }
+    return 0;
+}
+
+// One of the two places where the path solver touches the covariance matrix A, through the dispatcher the solver calls
+// (design_ops.hpp: raw_cov_gather / raw_cov_grad), on either storage (tests; include/adelie_hip.h has the arguments).  Everything
+// the kernels index by is checked here before anything is launched.
+int adelie_hip_cov_piece_test(adelie_hip_design* A, int what, const int32_t* vcol, int64_t nv, int64_t pos0, int64_t N, int64_t ldc,
+                              double sentinel, const void* v, const int32_t* cols, const void* coef, int64_t count, void* out) {
+    try {
+        if (!A || !out) throw make_core_error("bad arguments.");
+        if (!A->cov) throw make_core_error("A must be a covariance matrix (matrix.dense(method=\"cov\")).");
+        const int64_t p = A->p;
+        const bool gather = what == ADELIE_HIP_COV_PIECE_GATHER;
+        if (!gather && what != ADELIE_HIP_COV_PIECE_GRAD) throw make_core_error("unknown piece.");
+        const int32_t* list = gather ? vcol : cols;
+        const int64_t n_list = gather ? nv : count;
+        if (gather && (!vcol || nv < 1 || nv > p || pos0 < 0 || N < 1 || pos0 + N != nv || ldc < nv || ldc > (int64_t(1) << 20)))
+            throw make_core_error("GATHER: vcol (nv), 1 <= nv <= p, pos0 + N == nv and nv <= ldc are required.");
+        if (!gather && (!v || count < 0 || count > p || (count > 0 && (!cols || !coef))))
+            throw make_core_error("GRAD: v (p), cols and coef (count), 0 <= count <= p are required.");
+        std::vector<uint8_t> seen(size_t(p), 0);
+        for (int64_t k = 0; k < n_list; ++k) {
+            if (list[k] < 0 || list[k] >= p || seen[size_t(list[k])]) throw make_core_error("the columns must be distinct and in [0, p).");
+            seen[size_t(list[k])] = 1;
+        }
+        AHIP_CHECK(hipSetDevice(A->device));
+        hipStream_t s = A->stream;
+        auto body = [&](auto tag) {
+            using T = decltype(tag);
+            DevBuf<int32_t> dlist, dpos, dcnt;
+            dlist.reserve(size_t(n_list) + 1);
+            if (n_list) AHIP_CHECK(hipMemcpyAsync(dlist.p, list, size_t(n_list) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            if (gather) {
+                DevBuf<T> dC;
+                std::vector<T> hC(size_t(ldc) * size_t(nv), T(sentinel));
+                dC.reserve(hC.size());
+                dpos.reserve(size_t(p));
+                AHIP_CHECK(hipMemcpyAsync(dC.p, hC.data(), hC.size() * sizeof(T), hipMemcpyHostToDevice, s));
+                if (pos0 > 0) raw_cov_gather<T>(*A, dlist.p, int32_t(pos0), 0, int32_t(pos0), dC.p, ldc, dpos.p, s);
+                raw_cov_gather<T>(*A, dlist.p, int32_t(nv), int32_t(pos0), int32_t(N), dC.p, ldc, dpos.p, s);
+                AHIP_CHECK(hipGetLastError());
+                AHIP_CHECK(hipMemcpyAsync(out, dC.p, hC.size() * sizeof(T), hipMemcpyDeviceToHost, s));
+                AHIP_CHECK(hipStreamSynchronize(s));
+            } else {
+                DevBuf<T> dv, dcoef, dgrad, dw;
+                dv.reserve(size_t(p)); dcoef.reserve(size_t(count) + 1); dgrad.reserve(size_t(p)); dw.reserve(size_t(p)); dcnt.reserve(1);
+                const int32_t c32 = int32_t(count);
+                AHIP_CHECK(hipMemcpyAsync(dv.p, v, size_t(p) * sizeof(T), hipMemcpyHostToDevice, s));
+                if (count) AHIP_CHECK(hipMemcpyAsync(dcoef.p, coef, size_t(count) * sizeof(T), hipMemcpyHostToDevice, s));
+                AHIP_CHECK(hipMemcpyAsync(dcnt.p, &c32, sizeof(int32_t), hipMemcpyHostToDevice, s));
+                raw_cov_grad<T>(*A, dv.p, dlist.p, dcoef.p, dcnt.p, count, dgrad.p, dw.p, s);
+                AHIP_CHECK(hipGetLastError());
+                AHIP_CHECK(hipMemcpyAsync(out, dgrad.p, size_t(p) * sizeof(T), hipMemcpyDeviceToHost, s));
+                AHIP_CHECK(hipStreamSynchronize(s));
+            }
+        };
+        if (A->dtype == ADELIE_HIP_F64) body(double{});
+        else body(float{});
     } catch (const std::exception& e) {
         set_last_error(e.what());
         return 1;

@@ -686,8 +686,11 @@
     bool dense() const { return D->is_dense(); }
     // sparse design kept sparse (adelie_hip_design_create_csc): sweeps, Gram rows and residual updates walk its compressed
     // forms; the solve runs on the full-Gram engines (the panel engines stream dense column slices)
-    bool sparse() const { return D->is_csc(); }
+    // (not a covariance matrix kept sparse: the covariance method never sweeps its matrix, and runs as on the dense handle)
+    bool sparse() const { return D->is_csc() && !D->cov; }
     DevBuf<T> d_sp_delta; // p zeros between two residual updates
+    DevBuf<T> d_cov_w;          // covariance matrix kept sparse: the (p,) coefficient vector of a gradient ...
+    DevBuf<int32_t> d_cov_pos;  // ... and the (p,) row -> screen position map of a gather
     // standardized view over a dense or 2-bit design: its epilogues are composed around the raw operations of design_ops.hpp
     // (solver_screen.hpp: sweep / gram / axpy_cols); Gram engines only
     bool std_generic() const { return D->is_std_view(); }

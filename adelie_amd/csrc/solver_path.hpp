@@ -79,7 +79,7 @@
                 launch_cd_compact<T>(d_beta.p, d_zero.p, d_vcol.p, int(nv), d_dcols.p, d_dvals.p, &d_sc.p->n_delta, st);
             }
             t_sweep.begin(st);
-            launch_cov_grad<T>(static_cast<const T*>(D->X), D->ld, p, d_covv.p, d_dcols.p, d_dvals.p, &d_sc.p->n_delta, d_grad.p, st);
+            raw_cov_grad<T>(*D, d_covv.p, d_dcols.p, d_dvals.p, &d_sc.p->n_delta, nv, d_grad.p, d_cov_w.p, st);
             t_sweep.end(st);
         } else if (is_glm()) {
             t_sweep.begin(st);
@@ -658,6 +658,7 @@
         if (cov_mode) {
             if (!a->cov_v) throw make_core_error("v must be (p,) where A is (p, p).");
             d_covv.reserve(p); d_xm.reserve(p);
+            if (D->cov_csc()) { d_cov_w.reserve(p); d_cov_pos.reserve(p); } // the scratch of kernels_cov_sparse.hip
             d_covv.upload((const T*)a->cov_v, p, st);
             X_means.assign(size_t(p), T(0)); // no centring in the covariance method
             d_xm.upload(X_means.data(), p, st);

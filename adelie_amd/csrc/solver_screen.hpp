@@ -626,8 +626,11 @@
         screen_transforms.resize(ns);
         if (N <= 0) return;
         if (cov_mode) // the rows / columns of A of the new screen values (solver_gaussian_cov.hpp:63-97 reads A_gg from them)
-            launch_cov_gather<T>(static_cast<const T*>(D->X), D->ld, D->cov == 2, d_vcol.p, int32_t(nv), int32_t(pos0), int32_t(N),
-                                 d_C.p, ldc, st);
+        {
+            t_gram.begin(st);
+            raw_cov_gather<T>(*D, d_vcol.p, int32_t(nv), int32_t(pos0), int32_t(N), d_C.p, ldc, d_cov_pos.p, st);
+            t_gram.end(st);
+        }
         else
             gram(w_dev, nv, pos0, N, xm_dev, intercept);
         AHIP_CHECK(hipGetLastError());

@@ -112,9 +112,11 @@ def _as(v, dtype):
 
 
 def _no_constraint(mat, what):
-    """The views and copies of naive designs do not take a constraint matrix."""
+    """The views and copies of naive designs do not take a constraint matrix, nor a covariance matrix."""
     if isinstance(mat, MatrixConstraintBase):
         raise RuntimeError(f"adelie_amd: {what} takes a design matrix, not a constraint matrix (matrix.dense(method=\"constraint\")).")
+    if isinstance(mat, MatrixCovBase):
+        raise RuntimeError(f"adelie_amd: {what} takes a design matrix, not a covariance matrix (method=\"cov\").")
 
 
 class PyMatrixNaiveTranspose:
@@ -1247,7 +1249,10 @@ _SPARSE_AUTO_DENSE_BYTES = 32 << 30
 def sparse(mat, *, method: str = "naive", copy: bool = False, n_threads: int = 1, device: int = 0, resident: str = "auto"):
     """Creates a design from a scipy sparse matrix (reference ``adelie.matrix.sparse``, ``matrix.py:1301-1385``).
 
-    ``method="cov"`` takes a symmetric ``(p, p)`` matrix for ``gaussian_cov``; ``method="constraint"`` an ``(m, d)`` constraint
+    ``method="cov"`` takes a symmetric ``(p, p)`` matrix for ``gaussian_cov``: with ``resident="csc"`` it is kept sparse in HBM
+    (reference ``MatrixCovSparse``; :class:`_CovMatrixSparse`: only the column-compressed form is uploaded, 12 bytes per stored
+    entry in f64, and the ``(p, p)`` array is never formed on either side), with ``"dense"`` or ``"auto"`` it is expanded on the
+    host and lives dense in HBM, which stops at what the host can ``toarray()``.  ``method="constraint"`` takes an ``(m, d)`` constraint
     matrix for ``pinball`` and ``constraint.linear``, kept sparse in HBM (reference ``MatrixConstraintSparse``; ``resident``
     is ignored): a ``csc_matrix`` is converted to CSR with the reference's warning, duplicates are summed, and the result has
     the ``MatrixConstraintBase64/32`` operations over the stored entries.  For ``method="naive"``,
@@ -1267,9 +1272,13 @@ def sparse(mat, *, method: str = "naive", copy: bool = False, n_threads: int = 1
     Same results either way up to the summation order of the dot products."""
     if not (isinstance(mat, csr_matrix) or isinstance(mat, csc_matrix)):
         raise TypeError("mat must be scipy.sparse.csr_matrix or scipy.sparse.csc_matrix.")
-    if method == "cov":  # MatrixCovSparse (matrix_cov_sparse.ipp): a symmetric sparse (p, p) matrix, dense in HBM here
+    if method == "cov":  # MatrixCovSparse (matrix_cov_sparse.ipp): a symmetric sparse (p, p) matrix
         if mat.shape[0] != mat.shape[1]:
             raise RuntimeError("adelie_core: mat must be (p, p).")
+        if resident not in ("auto", "csc", "dense"):
+            raise ValueError("resident must be one of 'auto', 'csc' or 'dense'.")
+        if resident == "csc":
+            return _cov_sparse(_abi.hip_backend(), mat, copy, n_threads, device)
         return _cov_dense(_abi.hip_backend(), "design_create_cov_dense", np.asfortranarray(mat.toarray()), n_threads, device)
     if method == "constraint":
         return _constraint_sparse(_abi.hip_backend(), mat, copy, n_threads, device)
@@ -2021,6 +2030,58 @@ def _cov_dense(backend, ctor, mat, n_threads, device):
     return obj
 
 
+class _CovMatrixSparse(_CovMatrix):
+    """A symmetric ``(p, p)`` matrix kept sparse in HBM for the covariance method (``adelie.matrix.sparse(method="cov",
+    resident="csc")``, reference ``MatrixCovSparse``, ``matrix_cov_sparse.ipp``; also what ``block_diag(method="cov",
+    resident="csc")`` returns).  Only the column-compressed form lives on the device (``adelie_hip_design_create_cov_csc``); the
+    operations are :class:`_CovMatrix`'s, the same C calls over the stored entries, and ``solver.gaussian_cov`` solves on it
+    natively.  ``css_cov``, ``grpnet``, ``bvls``, views and derived designs refuse it.  The canonical host ``csc_matrix`` is kept
+    in ``_scipy``."""
+
+    @property
+    def nnz(self):
+        """Stored entries (explicit zeros included)."""
+        return int(self._backend.fn("design_nnz")(self._handle))
+
+
+def _cov_sparse_from_csc(backend, mat, n_threads, device):
+    """The handle and object of a canonical ``csc_matrix`` (sorted, distinct row indices per column)."""
+    dtype = np.dtype(mat.dtype).type
+    c_ptr = np.ascontiguousarray(mat.indptr, dtype=np.int64)
+    c_idx = np.ascontiguousarray(mat.indices, dtype=np.int32)
+    c_val = np.ascontiguousarray(mat.data, dtype=dtype)
+    handle = _abi.C.c_void_p()
+    backend.check(backend.fn("design_create_cov_csc")(
+        c_ptr.ctypes.data, c_idx.ctypes.data, c_val.ctypes.data, mat.shape[0], _abi.dtype_code(dtype), device, handle))
+    base = MatrixCovBase64 if dtype == np.float64 else MatrixCovBase32
+    cls = type("_cov_matrix_sparse", (_CovMatrixSparse, base), {"dtype": base.dtype})
+    obj = cls()
+    obj._init_native(backend, handle, n_threads, None)
+    obj._scipy = mat
+    obj._device = device
+    return obj
+
+
+def _cov_sparse(backend, mat, copy, n_threads, device):
+    """``adelie.matrix.sparse(mat, method="cov", resident="csc")``: duplicates summed, indices sorted, explicit zeros kept.  A
+    ``csr_matrix`` is taken as the CSC of its transpose -- the same matrix, since the method assumes ``A`` symmetric -- with the
+    reference's warning."""
+    if n_threads < 1:
+        raise RuntimeError("adelie_core: n_threads must be >= 1.")
+    if not backend.has("design_create_cov_csc"):
+        raise RuntimeError(f"{backend.path}: no adelie_hip_design_create_cov_csc -- rebuild the library.")
+    if np.dtype(mat.dtype).type not in (np.float32, np.float64):
+        raise RuntimeError("mat must have dtype float32 or float64.")
+    if isinstance(mat, csr_matrix):
+        warnings.warn("Converting to CSC format.")
+        mat = csc_matrix((mat.data, mat.indices, mat.indptr), shape=mat.shape, copy=True)
+    elif copy or not mat.has_canonical_format:
+        mat = mat.copy()
+    mat.sum_duplicates()
+    mat.sort_indices()
+    return _cov_sparse_from_csc(backend, mat, n_threads, device)
+
+
 def lazy_cov(mat, *, copy: bool = False, n_threads: int = 1, device: int = 0):
     """``A = X^T X`` for the covariance method (reference ``adelie.matrix.lazy_cov``, ``matrix.py:1000-1065``,
     ``MatrixCovLazyCov``).  The reference computes the rows of ``A`` that the solver asks for on demand, because ``A`` may not
@@ -2042,20 +2103,27 @@ def lazy_cov(mat, *, copy: bool = False, n_threads: int = 1, device: int = 0):
     return obj
 
 
-def block_diag(mats, *, method: str = "naive", n_threads: int = 1, device: int = 0):
+def block_diag(mats, *, method: str = "naive", n_threads: int = 1, device: int = 0, resident: str = "dense"):
     """Block-diagonal matrix (reference ``adelie.matrix.block_diag``, ``matrix.py:198-300``).  ``method="cov"``
     (``MatrixCovBlockDiag``): the blocks are symmetric matrices — ndarrays or covariance matrices of this module — and the result
-    is one resident ``(p, p)`` covariance matrix with them on its diagonal (dense in HBM; the reference keeps the list and
-    dispatches per block).  ``method="naive"`` is not implemented."""
+    is one resident ``(p, p)`` covariance matrix with them on its diagonal (the reference keeps the list and dispatches per
+    block).  ``resident="dense"`` (the default) pastes them into a dense ``(p, p)`` array that lives in HBM;
+    ``resident="csc"`` writes the column-compressed form straight from the blocks -- every entry of a block is stored, zeros
+    included, so a column is one contiguous run of rows -- and returns a :class:`_CovMatrixSparse` without a ``(p, p)`` array on
+    either side.  ``method="naive"`` is not implemented."""
     if method == "naive":
         raise NotImplementedError("adelie_amd.matrix.block_diag: only method='cov' is implemented.")
     if method != "cov":
         raise ValueError("method must be one of 'naive' or 'cov'.")
+    if resident not in ("dense", "csc"):
+        raise ValueError("resident must be one of 'dense' or 'csc'.")
     if len(mats) == 0:
         raise RuntimeError("adelie_core: mats must be non-empty.")
     blocks = []
     for m in mats:
-        if isinstance(m, _CovMatrix):
+        if isinstance(m, _CovMatrixSparse) and resident == "csc":
+            blocks.append(np.asfortranarray(m._scipy.toarray()))
+        elif isinstance(m, _CovMatrix):
             q = m.cols()
             out = np.empty((q, q), dtype=m.dtype, order="F")
             m.to_dense(0, q, out)
@@ -2069,6 +2137,18 @@ def block_diag(mats, *, method: str = "naive", n_threads: int = 1, device: int =
     if any(b.dtype != dtype for b in blocks):
         raise RuntimeError("adelie_core: all blocks must have the same dtype.")
     p = sum(b.shape[0] for b in blocks)
+    if resident == "csc":
+        if n_threads < 1:
+            raise RuntimeError("adelie_core: n_threads must be >= 1.")
+        if np.dtype(dtype).type not in (np.float32, np.float64):
+            raise RuntimeError("mat must have dtype float32 or float64.")
+        sizes = np.array([b.shape[0] for b in blocks], dtype=np.int64)
+        starts = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+        indptr = np.concatenate([[0], np.cumsum(np.repeat(sizes, sizes))])
+        indices = np.concatenate([np.tile(np.arange(o, o + q, dtype=np.int32), q) for o, q in zip(starts, sizes)])
+        data = np.concatenate([np.asarray(b).ravel(order="F") for b in blocks])
+        A = csc_matrix((data, indices, indptr), shape=(p, p))
+        return _cov_sparse_from_csc(_abi.hip_backend(), A, n_threads, device)
     A = np.zeros((p, p), dtype=dtype, order="F")
     o = 0
     for b in blocks:

@@ -442,7 +442,9 @@ def gaussian_cov(
     Minimises ``1/2 beta' A beta - v' beta + lmda * sum_g penalty_g (alpha ||beta_g|| + (1 - alpha) / 2 ||beta_g||^2)``
     along a decreasing path of ``lmda`` (reference ``adelie.solver.gaussian_cov``, ``adelie/solver.py:39-351``; arguments,
     defaults and the returned state are the reference's).  ``A`` is a symmetric positive semi-definite ``(p, p)`` ndarray
-    or an ``adelie_amd.matrix.dense(A, method="cov")`` handle (resident in HBM); ``v`` is ``(p,)``.  With ``A = X_c' W X_c``
+    or an ``adelie_amd.matrix.dense(A, method="cov")`` handle (resident in HBM), or a covariance matrix kept sparse in HBM
+    (``matrix.sparse(A, method="cov", resident="csc")``, ``matrix.block_diag(..., method="cov", resident="csc")``: no ``(p, p)``
+    array is formed, so ``p`` may be in the millions); ``v`` is ``(p,)``.  With ``A = X_c' W X_c``
     and ``v = X_c' W y_c`` this is the Gaussian ``grpnet`` problem (``devs`` then holds the unnormalised ``rsq``)."""
     if isinstance(A, np.ndarray):
         A = matrix.dense(A, method="cov", n_threads=n_threads)

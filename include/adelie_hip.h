@@ -126,8 +126,9 @@ int adelie_hip_design_create_snp_phased_calldata(const int8_t* calldata, const i
                                                  int dtype, int device, adelie_hip_design** out);
 /* The arrays of a design kept sparse copied back to the host: the column-compressed form (indptr of cols + 1, indices and
  * values of nnz entries, values in the design's dtype) and the row-compressed form likewise (rows + 1).  A NULL pointer skips
- * that array.  On a standardized view these are the entries of the matrix underneath.  adelie_hip_design_nnz gives the number
- * of stored entries, -1 for a design that is not kept sparse. */
+ * that array.  On a standardized view these are the entries of the matrix underneath.  A covariance matrix kept sparse
+ * (adelie_hip_design_create_cov_csc) has the column form only: asking for a row array is an error.  adelie_hip_design_nnz gives
+ * the number of stored entries, -1 for a design that is not kept sparse. */
 int adelie_hip_design_csc_download(adelie_hip_design* d, int64_t* indptr, int32_t* indices, void* values, int64_t* row_indptr,
                                    int32_t* row_indices, void* row_values);
 int64_t adelie_hip_design_nnz(const adelie_hip_design* d);
@@ -545,6 +546,16 @@ int adelie_hip_grpnet_solve_many(adelie_hip_design* const* X, const adelie_hip_g
  * Result accessors as above: devs holds rsq (the unnormalised decrease of the loss), intercepts are zero.
  * ------------------------------------------------------------------------------------------ */
 int adelie_hip_design_create_cov_dense(const void* host, int64_t p, int dtype, int order, int device, adelie_hip_design** out);
+/* == adelie.matrix.sparse(method="cov", resident="csc") / MatrixCovSparse{32,64}{C,F} (matrix_cov_sparse.ipp) and
+ * adelie.matrix.block_diag(method="cov", resident="csc") / MatrixCovBlockDiag: the covariance matrix kept sparse in HBM.  Only
+ * the column-compressed form of the symmetric (p, p) matrix is uploaded (indptr of p + 1, row indices and values of indptr[p]
+ * entries: 12 bytes per entry in f64, 8 in f32); the (p, p) array is never formed.  Inside a column the row indices must be
+ * sorted and distinct and lie in [0, p); indptr starts at 0 and does not decrease; explicit zeros are kept.  The values are not
+ * checked for symmetry, as on the dense handle.  The handle serves adelie_hip_gaussian_cov_solve, the three cov_* operations
+ * below, adelie_hip_design_nnz, adelie_hip_design_csc_download (column form only) and adelie_hip_design_destroy;
+ * adelie_hip_css_cov_solve refuses it (it keeps a dense (p, p) residual anyway). */
+int adelie_hip_design_create_cov_csc(const int64_t* indptr, const int32_t* indices, const void* values, int64_t p, int dtype, int device,
+                                     adelie_hip_design** out);
 /* == adelie.matrix.lazy_cov(mat) / MatrixCovLazyCov{32,64}{C,F} (matrix_cov_lazy_cov.ipp): A = X^T X of a resident naive design
  * (dense or 2-bit SNP).  The reference computes rows of A on demand and caches them because A may not fit in host memory;
  * here the whole (p, p) matrix is formed once by the MFMA Gram kernel and kept in HBM (p = 100 000 is 80 GB of the 288),
@@ -644,7 +655,7 @@ const char* adelie_hip_result_error(const adelie_hip_result* r);
 /* ------------------------------------------------------------------------------------------
  * ABI 13.  Column subset selection on a resident covariance matrix
  *   == adelie.solver.css_cov / StateCSSCov{32,64}(...).solve()   (state_css_cov.ipp:8-67, solver_css_cov.hpp:164-537)
- * `A` is a covariance-method handle (adelie_hip_design_create_cov_dense / _cov_lazy), assumed symmetric and never modified.
+ * `A` is a dense covariance-method handle (adelie_hip_design_create_cov_dense / _cov_lazy; one kept sparse is refused), assumed symmetric and never modified.
  * The solve keeps one (p, p) residual covariance in HBM (both triangles, so that every access is a contiguous column) and
  * streams it once per rank-one update with the loss's per-column score fused into the pass (kernels_css.hip).  Greedy runs
  * without a host synchronisation inside its loop; swapping makes one small device -> host read per attempt (a record of
@@ -969,6 +980,18 @@ typedef struct adelie_hip_group_piece {
     int64_t* st_i;
 } adelie_hip_group_piece;
 int adelie_hip_group_piece_test(const adelie_hip_group_piece* a, int64_t* info);
+
+/* One of the two places where the path solver touches the covariance matrix A (dense or kept sparse), through exactly the launcher
+ * the solver calls (tests): uploads, launches on A's stream, synchronises, downloads.  Column lists must be distinct and in [0, p).
+ *   ADELIE_HIP_COV_PIECE_GATHER: the copy of A[S, S] into the screen Gram matrix for the new screen values [pos0, nv) of the
+ *     column list vcol (nv), N = nv - pos0, leading dimension ldc >= nv.  A (ldc, nv) buffer is filled with `sentinel`, the gather
+ *     for the values [0, pos0) runs as a first step when pos0 > 0, then the step under test; `out` receives the whole buffer.
+ *   ADELIE_HIP_COV_PIECE_GRAD: out (p) = v - sum_k coef[k] A[:, cols[k]] over k < count, the count read on the device.
+ * Arguments of the other piece are ignored.  This entry and adelie_hip_design_create_cov_csc are additive and change the layout of
+ * no existing structure: ADELIE_HIP_ABI_VERSION stays as it is. */
+enum adelie_hip_cov_piece { ADELIE_HIP_COV_PIECE_GATHER = 0, ADELIE_HIP_COV_PIECE_GRAD = 1 };
+int adelie_hip_cov_piece_test(adelie_hip_design* A, int what, const int32_t* vcol, int64_t nv, int64_t pos0, int64_t N, int64_t ldc,
+                              double sentinel, const void* v, const int32_t* cols, const void* coef, int64_t count, void* out);
 
 #ifdef __cplusplus
 }
