@@ -5,7 +5,9 @@ Mirrors the user-facing surface of JamesYang007/adelie for the ``grpnet`` hot pa
 ``glm.gaussian`` / ``glm.binomial`` / ``glm.multigaussian`` / ``glm.multinomial``, the naive State objects), the covariance
 method (``solver.gaussian_cov``), column subset selection on a resident covariance (``solver.css_cov``,
 ``sklearn.CSSModelSelection``), bounded-variable least squares (``solver.bvls``) and pinball least squares on a resident
-constraint matrix (``solver.pinball``, ``matrix.dense(method="constraint")``).  All numerics run in hand-written HIP
+constraint matrix (``solver.pinball``, ``matrix.dense(method="constraint")``), and the full-matrix NNQP / lasso / pinball
+descents, one or a batch per call (``optimization.StateNNQPFull`` / ``StateLassoFull`` / ``StatePinballFull``,
+``optimization.solve_many``).  All numerics run in hand-written HIP
 kernels for gfx950 behind the C ABI declared in ``include/adelie_hip.h``.
 """
 from . import configs
@@ -18,6 +20,7 @@ from . import diagnostic
 from . import cv
 from . import data
 from . import io
+from . import optimization
 try:  # the estimator wrapper needs scikit-learn's base classes; everything else does not
     from . import sklearn
 except ImportError:  # pragma: no cover

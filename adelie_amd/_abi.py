@@ -219,6 +219,20 @@ S = dict(
     n_screen_reads=93, n_screen_short=94, n_filter_open_cols=95,
 )
 
+class QpFullArgs(C.Structure):
+    """``adelie_hip_qp_full_args`` (an addition to ABI 14)."""
+
+    _fields_ = [("kind", C.c_int32), ("dtype", C.c_int32), ("device", C.c_int32), ("_pad0", C.c_int32),
+                ("n_problems", C.c_int64), ("d", C.c_void_p), ("quad", C.c_void_p), ("quad_is_dev", C.c_void_p),
+                ("penalty_a", C.c_void_p), ("penalty_b", C.c_void_p), ("x", C.c_void_p), ("grad", C.c_void_p),
+                ("tol", C.c_void_p), ("y_var", C.c_void_p), ("max_iters", C.c_void_p), ("iters", C.c_void_p),
+                ("status", C.c_void_p), ("time_elapsed", C.c_void_p)]
+
+
+# enum adelie_hip_qp_full_kind / adelie_hip_qp_full_status
+QP_FULL_KIND = dict(nnqp=0, lasso=1, pinball=2)
+QP_FULL_MAX_ITERS = 1
+
 # adelie_hip_cov_piece
 COV_PIECE_GATHER, COV_PIECE_GRAD = range(2)
 # adelie_hip_group_piece_mode
@@ -265,6 +279,7 @@ HIP_SYMBOLS = [
     "design_create_constraint_dense", "design_adopt_constraint_dense_dev", "design_create_constraint_csc", "constraint_op",
     "pinball_solve", "pinball_result_destroy", "pinball_result_size", "pinball_result_copy", "pinball_result_scalar",
     "pinball_result_error",
+    "qp_full_solve",
 ]
 
 
@@ -407,6 +422,7 @@ class Backend:
         sig("pinball_result_copy", ci, [vp, ci, vp, i64])
         sig("pinball_result_scalar", dbl, [vp, ci])
         sig("pinball_result_error", C.c_char_p, [vp])
+        sig("qp_full_solve", ci, [p(QpFullArgs)])
 
     def check(self, rc):
         if rc != 0:

@@ -658,6 +658,7 @@ extern double g_bvls_gram_limit_mb; // kernels_bvls.hip
 extern int64_t g_bvls_lds_max_ns;
 extern double g_pinball_gram_limit_mb; // kernels_pinball.hip
 extern int64_t g_pinball_lds_max_ns;
+extern int64_t g_qp_full_lds_max_d; // kernels_qp_full.hip
 } // namespace ahip
 
 extern "C" {
@@ -675,6 +676,7 @@ int adelie_hip_set_config(const char* name, double value) {
     else if (nm == "bvls_lds_max_ns") ahip::g_bvls_lds_max_ns = value > 0 ? int64_t(value) : 0;
     else if (nm == "pinball_gram_limit_mb") ahip::g_pinball_gram_limit_mb = value > 0 ? value : 16384.0;
     else if (nm == "pinball_lds_max_ns") ahip::g_pinball_lds_max_ns = value > 0 ? int64_t(value) : 0;
+    else if (nm == "qp_full_lds_max_d") ahip::g_qp_full_lds_max_d = value > 0 ? int64_t(value) : 0;
     else {
         set_last_error("adelie_core: unknown config name.");
         return 1;

@@ -75,7 +75,9 @@ int         adelie_hip_device_count(void);
  * "pool_trim" (any value) returns the parked blocks to the driver.
  * adelie_hip_bvls_solve (ABI 14): "bvls_gram_limit_mb" (default 16384) bounds the screen Gram matrix of a solve;
  * "bvls_lds_max_ns" (default 0 = as many as the device's LDS holds) keeps the fit kernel's per-coordinate state in global
- * memory for screen sets larger than the value (test hook: both forms give the same bits). */
+ * memory for screen sets larger than the value (test hook: both forms give the same bits).
+ * adelie_hip_qp_full_solve: "qp_full_lds_max_d" (default 0 = as many as the device's LDS holds) keeps the per-coordinate state of
+ * a problem with d > 64 in global memory from that d on (test hook: both forms give the same bits). */
 int         adelie_hip_set_config(const char* name, double value);
 
 /* ------------------------------------------------------------------------------------------
@@ -992,6 +994,59 @@ int adelie_hip_group_piece_test(const adelie_hip_group_piece* a, int64_t* info);
 enum adelie_hip_cov_piece { ADELIE_HIP_COV_PIECE_GATHER = 0, ADELIE_HIP_COV_PIECE_GRAD = 1 };
 int adelie_hip_cov_piece_test(adelie_hip_design* A, int what, const int32_t* vcol, int64_t nv, int64_t pos0, int64_t N, int64_t ldc,
                               double sentinel, const void* v, const int32_t* cols, const void* coef, int64_t count, void* out);
+
+/* ------------------------------------------------------------------------------------------
+ * Full-matrix quadratic programs   min 1/2 x' Q x - v' x + pen(x),   Q a full (d, d) matrix, a batch per call
+ *   == adelie.optimization.StateNNQPFull / StateLassoFull / StatePinballFull (...).solve()
+ *      (py_optimization.cpp; nnqp_full.hpp:30-99, lasso_full.hpp:29-107, pinball_full.hpp:31-120)
+ *   NNQP     pen = indicator of x >= 0                                   visit nnqp_full.hpp:76-92,     thr = d * tol
+ *   LASSO    pen = sum_i penalty_a[i] |x_i|                              visit lasso_full.hpp:82-100,   thr = tol
+ *   PINBALL  pen = sum_i penalty_b[i] max(x_i, 0) + penalty_a[i] max(-x_i, 0)   (penalty_a = penalty_neg, penalty_b = penalty_pos)
+ *                                                                        visit pinball_full.hpp:92-113, thr = y_var * tol
+ * Cyclic coordinate descent, the reference's visit restated operation for operation in the value type (no contraction): sweeps
+ * over i = 0 .. d-1 until one ends with max_i q_ii del_i^2 < thr (thr formed in the value type), at most max_iters of them.
+ * grad must hold v - Q x on entry and does so on exit; a changed visit does grad[a] -= del * Q[a, i] as a multiply and a
+ * subtract with Q[., i] the i-th contiguous slice of the buffer (a column of a column-major Q, a row of a row-major one: the
+ * reference reads the same slice of either, so both orders are one path and no order is passed).
+ *
+ * One call solves n_problems independent problems of one kind and dtype (kernels_qp_full.hip): those with d <= 64 in one launch
+ * with a wavefront per problem (Q in LDS, the iterate in registers), those with d > 64 in another with a workgroup per problem
+ * (Q read from HBM; the per-coordinate state in LDS, or in global memory when it does not fit or from the d that
+ * adelie_hip_set_config("qp_full_lds_max_d", d) names -- default 0 = automatic; both forms give the same bits).  There is no
+ * reduction and no atomic on the path, so results are bit-reproducible and no problem's result depends on the batch it is in.
+ *
+ * All per-problem arrays have n_problems entries.  quad[k], penalty_a[k], penalty_b[k], x[k], grad[k] are HOST pointers of
+ * `dtype` ((d, d) contiguous; (d,) each), except that quad[k] is a DEVICE pointer on `device` where quad_is_dev[k] != 0: that
+ * matrix is read in place and never written.  penalty_a may be NULL for NNQP, penalty_b and y_var unless PINBALL.  x[k] / grad[k]
+ * are read and overwritten; iters[k] receives the sweeps run and status[k] an adelie_hip_qp_full_status.  *time_elapsed (may be
+ * NULL) receives the wall-clock seconds of the whole call.
+ * Returns 0 when every problem was run, whether or not one stopped at max_iters (the statuses say which; x / grad / iters are
+ * then those of the last sweep); nonzero with adelie_hip_last_error for malformed arguments (nothing is written then).
+ * The entry is additive and changes the layout of no existing structure: ADELIE_HIP_ABI_VERSION stays as it is.
+ * ------------------------------------------------------------------------------------------ */
+enum adelie_hip_qp_full_kind { ADELIE_HIP_QP_FULL_NNQP = 0, ADELIE_HIP_QP_FULL_LASSO = 1, ADELIE_HIP_QP_FULL_PINBALL = 2 };
+enum adelie_hip_qp_full_status { ADELIE_HIP_QP_FULL_OK = 0, ADELIE_HIP_QP_FULL_MAX_ITERS = 1 };
+typedef struct adelie_hip_qp_full_args {
+    int32_t            kind;         /* adelie_hip_qp_full_kind */
+    int32_t            dtype;        /* adelie_hip_dtype */
+    int32_t            device;
+    int32_t            _pad0;
+    int64_t            n_problems;
+    const int64_t*     d;
+    const void* const* quad;
+    const uint8_t*     quad_is_dev;  /* NULL: every quad is a host pointer */
+    const void* const* penalty_a;
+    const void* const* penalty_b;
+    void* const*       x;
+    void* const*       grad;
+    const double*      tol;
+    const double*      y_var;
+    const int64_t*     max_iters;
+    int64_t*           iters;        /* out */
+    int32_t*           status;       /* out */
+    double*            time_elapsed; /* out, may be NULL */
+} adelie_hip_qp_full_args;
+int adelie_hip_qp_full_solve(const adelie_hip_qp_full_args* args);
 
 #ifdef __cplusplus
 }
