@@ -262,7 +262,7 @@ class GroupPiece(C.Structure):
 HIP_SYMBOLS = [
     "abi_version", "last_error", "device_count", "set_config",
     "design_create_dense", "design_create_sparse", "design_create_csc", "design_create_standardized", "design_adopt_dense_dev", "design_create_snp_unphased",
-    "design_create_snp_calldata", "design_create_snp_bed", "design_alias", "design_drop_shadow", "design_shadow_stats", "design_shadow_info", "design_create_slice", "design_create_multi", "design_create_derived", "design_create_concat", "design_impute", "design_destroy",
+    "design_create_snp_calldata", "design_create_snp_bed", "design_alias", "design_drop_shadow", "design_shadow_stats", "design_shadow_info", "design_create_slice", "design_create_multi", "design_create_derived", "design_create_concat", "design_impute", "design_destroy", "design_owned_bytes",
     "design_create_one_hot", "design_create_interaction", "design_factor_groups",
     "design_create_convex_relu", "design_create_convex_relu_csc",
     "design_create_snp_phased_ancestry", "design_create_snp_phased_calldata", "design_csc_download", "design_nnz",
@@ -363,6 +363,7 @@ class Backend:
         sig("design_glm_path_losses", ci, [vp, ci, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp])
         sig("design_multi_path_losses", ci, [vp, ci, ci, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp])
         sig("design_destroy", ci, [vp])
+        sig("design_owned_bytes", i64, [])
         sig("design_rows", i64, [vp])
         sig("design_cols", i64, [vp])
         sig("design_dtype", ci, [vp])

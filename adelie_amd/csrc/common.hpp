@@ -14,6 +14,7 @@
 
 #include "../../include/adelie_hip.h"
 #include "kernels.hpp"
+#include "dev_array_host.hpp"
 
 namespace ahip {
 
@@ -134,10 +135,7 @@ constexpr bool kFilterDepthDefault = true;
 inline bool filter_depth_on(int hook) { return hook < 0 ? kFilterDepthDefault : hook != 0; }
 
 
-// util/exceptions.hpp:8-55 — same prefixes so that the Python layer's error-vs-warning split keeps working
-struct core_error : std::runtime_error {
-    using std::runtime_error::runtime_error;
-};
+// (core_error itself: dev_array_host.hpp)
 inline core_error make_core_error(const std::string& m) { return core_error("adelie_core: " + m); }
 inline core_error make_solver_error(const std::string& m) { return core_error("adelie_core solver: " + m); }
 
@@ -481,10 +479,122 @@ struct DevBuf {
     }
 };
 
+// The memory of the arrays a design handle owns (dev_array_host.hpp).  A refusal leaves no sticky error behind; a request for
+// no bytes still yields a block, so that "null" always means "refused".
+struct HipMem {
+    static void* alloc(size_t bytes) {
+        void* q = nullptr;
+        if (hipMalloc(&q, bytes ? bytes : 1) == hipSuccess) return q;
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    static void free(void* p) { (void)hipFree(p); }
+};
+template <class T> using DevArr = OwnedArr<T, HipMem>;
+
+// ---- the device arrays of a design handle, grouped by what they belong to ------------------------------------------------------
+// Every array is a DevArr: the handle that allocated it frees it when it is deleted, a handle that borrowed it (an alias, a
+// slice, a view) frees nothing.  borrow_from() under each group is all that adelie_hip_design_alias does with it, so a new
+// array goes into its group's fields and into the borrow_from below them.  Arrays of the design's value type are DevArr<void>.
+struct DenseArrs {
+    DevArr<void> X; // column-major, leading dimension ld
+    int64_t ld = 0;
+    void borrow_from(const DenseArrs& o) { X.borrow(o.X), ld = o.ld; }
+};
+struct SnpArrs {
+    DevArr<uint8_t> bits; // 2 bits per call, ldb bytes per column
+    int64_t ldb = 0;
+    DevArr<void> impute; // (p,) value_t
+    void borrow_from(const SnpArrs& o) { bits.borrow(o.bits), ldb = o.ldb, impute.borrow(o.impute); }
+};
+// sparse (kind 3): column-compressed and row-compressed copies of the stored entries
+struct CscArrs {
+    DevArr<int64_t> cptr, rptr;
+    DevArr<int32_t> cidx, rcol;
+    DevArr<void> cval, rval;
+    int64_t nnz = 0;
+    DevArr<int64_t> bptr; // per-column row-block pointers (p x (sp_nb + 1)) when sp_nb > 1
+    int sp_nb = 1;
+    int64_t sp_rb = 0;
+    // tile-major copy of the entries for the full sweeps (kernels_sparse.hip: csc_tile_sweep_kernel), sp_nt > 0
+    DevArr<int64_t> tptr;
+    DevArr<uint16_t> trow;
+    DevArr<void> tval;
+    int sp_nt = 0;
+    int64_t sp_th = 0;
+    int sp_parts() const { return sp_nb > sp_nt ? sp_nb : sp_nt; } // partial sums per column a sweep may leave
+    void borrow_from(const CscArrs& o) {
+        cptr.borrow(o.cptr), cidx.borrow(o.cidx), cval.borrow(o.cval), rptr.borrow(o.rptr), rcol.borrow(o.rcol), rval.borrow(o.rval);
+        nnz = o.nnz;
+        bptr.borrow(o.bptr), sp_nb = o.sp_nb, sp_rb = o.sp_rb;
+        tptr.borrow(o.tptr), trow.borrow(o.trow), tval.borrow(o.tval), sp_nt = o.sp_nt, sp_th = o.sp_th;
+    }
+};
+// standardized view (adelie_hip_design_create_standardized): (p,) value_t each, allocated by the view on top of an alias
+struct StdArrs {
+    DevArr<void> std_center, std_iscale;
+    void borrow_from(const StdArrs& o) { std_center.borrow(o.std_center), std_iscale.borrow(o.std_iscale); }
+};
+// factor design (adelie_hip_design_create_one_hot / _interaction): X is the expanded matrix; next to it a column-major copy of
+// the d columns of Z and the per-block descriptors that the structured full sweep reads (kernels_factor.hip).  f_outer (host) =
+// the blocks' first columns and P; an alias keeps the structure: CV folds sweep the same way.
+struct FactorArrs {
+    DevArr<void> fz; // (a convex-relu design keeps its copy of Z here too)
+    int64_t fz_ld = 0;
+    DevArr<ahip::FactorBlock> fblk;
+    DevArr<ahip::FactorChunk> fchunk;
+    int64_t f_nchunk = 0;
+    std::vector<int64_t> f_outer;
+    void borrow_from(const FactorArrs& o) {
+        fz.borrow(o.fz), fz_ld = o.fz_ld, fblk.borrow(o.fblk), fchunk.borrow(o.fchunk), f_nchunk = o.f_nchunk, f_outer = o.f_outer;
+    }
+};
+// convex-relu design (adelie_hip_design_create_convex_relu): X is the expanded (n, (gated ? 1 : 2) m d) matrix; next to it the
+// column-major copy of Z in fz / fz_ld (d columns) and the (n, m) mask bytes, column-major with leading dimension rmask_ld, that
+// the structured full sweep reads (kernels_relu.hip).  r_d / r_m / r_gated also describe the form kept sparse below.
+struct ReluArrs {
+    DevArr<uint8_t> rmask;
+    int64_t rmask_ld = 0, r_d = 0, r_m = 0;
+    int r_gated = 0;
+    void borrow_from(const ReluArrs& o) { rmask.borrow(o.rmask), rmask_ld = o.rmask_ld, r_d = o.r_d, r_m = o.r_m, r_gated = o.r_gated; }
+};
+// convex-relu design over a sparse base, kept sparse (adelie_hip_design_create_convex_relu_csc): kind is kCsc and the compressed
+// arrays hold the expansion; next to them a copy of Z's column-compressed entries (rz_seg: Z's column pointers refined by the row
+// tiles of relu_sparse_shape, rz_idx, rz_val) and the mask packed to 32-bit words per row (rbits), which the structured full
+// sweep reads (kernels_relu_sparse.hip).
+struct ReluCscArrs {
+    DevArr<int64_t> rz_seg;
+    DevArr<int32_t> rz_idx;
+    DevArr<void> rz_val;
+    DevArr<uint32_t> rbits;
+    int64_t rz_nnz = 0;
+    void borrow_from(const ReluCscArrs& o) {
+        rz_seg.borrow(o.rz_seg), rz_idx.borrow(o.rz_idx), rz_val.borrow(o.rz_val), rbits.borrow(o.rbits), rz_nnz = o.rz_nnz;
+    }
+};
+// float32 shadow of a dense f64 design for the filtered invariance sweep (kernels_filter.hip: ShadowView), made on the first
+// eligible solve.  Like the batcher it lives with the design the aliases were made from: nobody borrows it, the aliases read
+// their owner's.  sh_kind (shadow_kind_host.hpp): float32 values, or int16 with the per-column scales in sh_scale.
+struct ShadowArrs {
+    DevArr<void> sh_X;
+    int sh_kind = ahip::kShadowF32;
+    DevArr<double> sh_scale; // (p,) q15 only
+    int64_t sh_ld = 0;
+    DevArr<double> sh_err; // (p,) ||x_j - xs_j||_2
+    DevArr<double> sh_nrm; // (p,) ||xs_j||_2
+    void reset() { sh_X.reset(), sh_err.reset(), sh_nrm.reset(), sh_scale.reset(), sh_ld = 0, sh_kind = ahip::kShadowF32; }
+};
+
 } // namespace ahip
 
 // ---- the opaque handles of include/adelie_hip.h ------------------------------------------------------------
-struct adelie_hip_design {
+struct adelie_hip_design : ahip::DenseArrs, ahip::SnpArrs, ahip::CscArrs, ahip::StdArrs, ahip::FactorArrs, ahip::ReluArrs,
+                           ahip::ReluCscArrs, ahip::ShadowArrs {
+    // what adelie_hip_design_alias shares with `o`; o must outlive this handle
+    void borrow_arrays(const adelie_hip_design& o) {
+        DenseArrs::borrow_from(o), SnpArrs::borrow_from(o), CscArrs::borrow_from(o), StdArrs::borrow_from(o);
+        FactorArrs::borrow_from(o), ReluArrs::borrow_from(o), ReluCscArrs::borrow_from(o);
+    }
     int dtype = ADELIE_HIP_F64;
     int device = 0;
     // storage kinds: dense, snp (2-bit), multi-response view of a dense or 2-bit design (adelie_hip_design_create_multi),
@@ -510,79 +620,15 @@ struct adelie_hip_design {
     // (m, d) constraint matrix A, so n == d and p == m; only adelie_hip_constraint_op and adelie_hip_pinball_solve accept it
     int constraint = 0;
     int64_t n = 0, p = 0;
-    // dense
-    void* X = nullptr;
-    int64_t ld = 0;
-    bool owned = false;
-    // snp
-    uint8_t* bits = nullptr;
-    int64_t ldb = 0;
-    void* impute = nullptr; // (p,) value_t on device
-    bool alias = false;     // shares X / bits / impute / the sparse arrays with another design (adelie_hip_design_alias): never frees them
-    // sparse (kind 3): column-compressed and row-compressed copies of the stored entries
-    int64_t* cptr = nullptr;
-    int32_t* cidx = nullptr;
-    void* cval = nullptr;
-    int64_t* rptr = nullptr;
-    int32_t* rcol = nullptr;
-    void* rval = nullptr;
-    int64_t nnz = 0;
-    int64_t* bptr = nullptr; // per-column row-block pointers (p x (sp_nb + 1)) when sp_nb > 1
-    int sp_nb = 1;
-    int64_t sp_rb = 0;
-    // standardized view of a sparse design (adelie_hip_design_create_csc_standardized): (p,) value_t each, owned unless alias
-    // tile-major copy of the entries for the full sweeps (kernels_sparse.hip: csc_tile_sweep_kernel), sp_nt > 0
-    int64_t* tptr = nullptr;
-    uint16_t* trow = nullptr;
-    void* tval = nullptr;
-    int sp_nt = 0;
-    int64_t sp_th = 0;
-    int sp_parts() const { return sp_nb > sp_nt ? sp_nb : sp_nt; } // partial sums per column a sweep may leave
-    void* std_center = nullptr;
-    void* std_iscale = nullptr;
-    bool std_owned = false;
     // multi-response view: [1 (x) I_K, X (x) I_K] over the base's X (nb x pb); n = nb*K, p = (pb + micpt)*K
     int64_t mK = 0, nb = 0, pb = 0;
     int micpt = 0;
-    void* ones = nullptr; // nb ones (owned)
-    // factor design (adelie_hip_design_create_one_hot / _interaction): X above is the expanded matrix; next to it a column-major
-    // copy of the d columns of Z and the per-block descriptors that the structured full sweep reads (kernels_factor.hip).  Owned
-    // unless alias; f_outer (host) = the blocks' first columns and P.
-    void* fz = nullptr;
-    int64_t fz_ld = 0;
-    ahip::FactorBlock* fblk = nullptr;
-    ahip::FactorChunk* fchunk = nullptr;
-    int64_t f_nchunk = 0;
-    std::vector<int64_t> f_outer;
-    // convex-relu design (adelie_hip_design_create_convex_relu): X above is the expanded (n, (gated ? 1 : 2) m d) matrix; next to
-    // it the column-major copy of Z in fz / fz_ld (d columns) and the (n, m) mask bytes, column-major with leading dimension
-    // rmask_ld, that the structured full sweep reads (kernels_relu.hip).  Owned unless alias.
-    uint8_t* rmask = nullptr;
-    int64_t rmask_ld = 0, r_d = 0, r_m = 0;
-    int r_gated = 0;
-    // convex-relu design over a sparse base, kept sparse (adelie_hip_design_create_convex_relu_csc): kind is kCsc and the six
-    // arrays above hold the expansion; next to them a copy of Z's column-compressed entries (rz_seg: Z's column pointers refined
-    // by the row tiles of relu_sparse_shape, rz_idx, rz_val) and the mask packed to 32-bit words per row (rbits), which the
-    // structured full sweep reads (kernels_relu_sparse.hip); r_d / r_m / r_gated as above.  Owned unless alias.
-    int64_t* rz_seg = nullptr;
-    int32_t* rz_idx = nullptr;
-    void* rz_val = nullptr;
-    uint32_t* rbits = nullptr;
-    int64_t rz_nnz = 0;
+    ahip::DevArr<void> ones; // nb ones
     // Sweep batching across solvers that run concurrently on one resident matrix (cv_grpnet folds on alias handles): the
     // batcher object lives with the design the aliases were made from (solver.hip::SweepBatcher, created on first use).
     adelie_hip_design* batch_owner = nullptr; // nullptr: this design itself
     void* batcher = nullptr;
-    // float32 shadow of a dense f64 design for the filtered invariance sweep (kernels_filter.hip: ShadowView), made on the first
-    // eligible solve.  Like the batcher it lives with the design the aliases were made from, which frees it.
-    // sh_kind (shadow_kind_host.hpp): float32 values, or int16 with the per-column scales in sh_scale.
-    void* sh_X = nullptr;
-    int sh_kind = ahip::kShadowF32;
-    double* sh_scale = nullptr; // (p,) q15 only
-    int64_t sh_ld = 0;
-    double* sh_err = nullptr; // (p,) ||x_j - xs_j||_2
-    double* sh_nrm = nullptr; // (p,) ||xs_j||_2
-    int sh_state = 0;         // 0: none yet, 1: built, -1: ineligible (an entry float32 cannot hold, memory, a failed staleness check)
+    int sh_state = 0; // the shadow: 0: none yet, 1: built, -1: ineligible (an entry float32 cannot hold, memory, a failed staleness check)
     int64_t sh_n_ineligible = 0, sh_n_builds = 0;
     std::mutex sh_mu;
     hipStream_t stream = nullptr;

@@ -39,43 +39,65 @@ void check_device(int device) {
 }
 
 // a temporary device block, freed on every way out
-struct DevTmp {
-    void* p = nullptr;
-    ~DevTmp() { (void)hipFree(p); }
-};
+using DevTmp = DevArr<void>;
+
+std::string gib(double bytes) {
+    char buf[64];
+    std::snprintf(buf, sizeof buf, "%.2f GiB", bytes / double(int64_t(1) << 30));
+    return buf;
+}
+
+// The padded column-major (d->n, d->p) matrix of a design under construction: columns start 128/256-byte aligned (32 elements;
+// kernels_relu.hip's steps never leave a column's padding), at least 16 bytes.  zero_all clears the array on d's stream, otherwise
+// only the padding rows are cleared, so that vector loads past n never see NaN payloads.  With `what` (a constructor's name) a
+// refusal names the size that did not fit.
+template <class T>
+T* alloc_dense(adelie_hip_design* d, bool zero_all, const char* what = nullptr) {
+    constexpr int64_t kAlign = 32;
+    static_assert(kAlign % kReluStep == 0, "the padded rows must cover the structured relu sweep's last step");
+    const int64_t n = d->n, p = d->p, ld = ((n + kAlign - 1) / kAlign) * kAlign;
+    const size_t bytes = size_t(ld) * size_t(p) * sizeof(T);
+    if (!what) d->X.alloc(std::max<size_t>(16, bytes));
+    else if (!d->X.try_alloc(std::max<size_t>(16, bytes)))
+        throw make_core_error(std::string(what) + "(): could not allocate the expanded design (" + std::to_string(n) + " x " +
+                              std::to_string(p) + ", " + gib(double(ld) * double(p) * sizeof(T)) + ") on the device.");
+    d->ld = ld;
+    d->kind = adelie_hip_design::kDense;
+    T* X = static_cast<T*>(d->X);
+    if (zero_all) AHIP_CHECK(hipMemsetAsync(X, 0, bytes, d->stream));
+    else if (ld > n && p > 0) AHIP_CHECK(hipMemset2DAsync(X + n, size_t(ld) * sizeof(T), 0, size_t(ld - n) * sizeof(T), size_t(p), d->stream));
+    return X;
+}
+// the same for a 2-bit design: kind, the leading dimension of the 2-bit columns and the packed matrix itself; the (p,) imputed means
+void snp_alloc_bits(adelie_hip_design* d) {
+    d->kind = adelie_hip_design::kSnp;
+    d->ldb = (((d->n + 3) / 4 + 127) / 128) * 128;
+    d->bits.alloc(size_t(d->ldb) * size_t(d->p));
+}
+void snp_alloc_impute(adelie_hip_design* d) { d->impute.alloc(size_t(d->p) * (d->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float))); }
 
 template <class T>
 void create_dense_t(adelie_hip_design* d, const void* src, bool src_on_device, int order) {
-    constexpr int64_t kAlign = 32; // elements: columns start 128/256-byte aligned
     const int64_t n = d->n, p = d->p;
-    if (src_on_device && order == ADELIE_HIP_COL_MAJOR) {
-        d->X = const_cast<void*>(src);
+    if (src_on_device && order == ADELIE_HIP_COL_MAJOR) { // adopted in place: the caller frees it
+        d->X.borrow(const_cast<void*>(src));
         d->ld = n;
-        d->owned = false;
         return;
     }
-    const int64_t ld = ((n + kAlign - 1) / kAlign) * kAlign;
-    T* X = nullptr;
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&X), size_t(ld) * size_t(p > 0 ? p : 1) * sizeof(T)));
-    d->X = X;
-    d->ld = ld;
-    d->owned = true;
+    T* X = alloc_dense<T>(d, order != ADELIE_HIP_COL_MAJOR);
+    const int64_t ld = d->ld;
     if (order == ADELIE_HIP_COL_MAJOR) {
         AHIP_CHECK(hipMemcpy2DAsync(X, size_t(ld) * sizeof(T), src, size_t(n) * sizeof(T), size_t(n) * sizeof(T), size_t(p),
                                     hipMemcpyHostToDevice, d->stream));
-        // zero the padding rows so that vector loads past n never see NaN payloads
-        if (ld > n)
-            AHIP_CHECK(hipMemset2DAsync(X + n, size_t(ld) * sizeof(T), 0, size_t(ld - n) * sizeof(T), size_t(p), d->stream));
     } else {
         // row-major source: stage (if on host) and transpose on device
         const T* rsrc = static_cast<const T*>(src);
         DevTmp tmp;
         if (!src_on_device) {
-            AHIP_CHECK(hipMalloc(&tmp.p, size_t(n) * size_t(p) * sizeof(T)));
-            AHIP_CHECK(hipMemcpyAsync(tmp.p, src, size_t(n) * size_t(p) * sizeof(T), hipMemcpyHostToDevice, d->stream));
-            rsrc = static_cast<const T*>(tmp.p);
+            tmp.alloc(size_t(n) * size_t(p) * sizeof(T));
+            AHIP_CHECK(hipMemcpyAsync(tmp, src, size_t(n) * size_t(p) * sizeof(T), hipMemcpyHostToDevice, d->stream));
+            rsrc = static_cast<const T*>(tmp);
         }
-        AHIP_CHECK(hipMemsetAsync(X, 0, size_t(ld) * size_t(p) * sizeof(T), d->stream));
         launch_transpose<T>(rsrc, n, p, X, ld, d->stream);
         AHIP_CHECK(hipStreamSynchronize(d->stream));
     }
@@ -84,26 +106,18 @@ void create_dense_t(adelie_hip_design* d, const void* src, bool src_on_device, i
 
 template <class T>
 void create_sparse_t(adelie_hip_design* d, const int64_t* indptr, const int32_t* indices, const void* values) {
-    constexpr int64_t kAlign = 32;
     const int64_t n = d->n, p = d->p;
     const int64_t nnz = indptr[p];
-    const int64_t ld = ((n + kAlign - 1) / kAlign) * kAlign;
-    T* X = nullptr;
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&X), size_t(ld) * size_t(p) * sizeof(T)));
-    d->X = X;
-    d->ld = ld;
-    d->owned = true;
-    AHIP_CHECK(hipMemsetAsync(X, 0, size_t(ld) * size_t(p) * sizeof(T), d->stream));
+    T* X = alloc_dense<T>(d, true);
     const size_t nz1 = size_t(std::max<int64_t>(nnz, 1));
-    DevTmp dptr, didx, dval;
-    AHIP_CHECK(hipMalloc(&dptr.p, size_t(p + 1) * sizeof(int64_t)));
-    AHIP_CHECK(hipMalloc(&didx.p, nz1 * sizeof(int32_t)));
-    AHIP_CHECK(hipMalloc(&dval.p, nz1 * sizeof(T)));
-    AHIP_CHECK(hipMemcpyAsync(dptr.p, indptr, size_t(p + 1) * sizeof(int64_t), hipMemcpyHostToDevice, d->stream));
-    AHIP_CHECK(hipMemcpyAsync(didx.p, indices, size_t(nnz) * sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
-    AHIP_CHECK(hipMemcpyAsync(dval.p, values, size_t(nnz) * sizeof(T), hipMemcpyHostToDevice, d->stream));
-    launch_csc_scatter<T>(static_cast<const int64_t*>(dptr.p), static_cast<const int32_t*>(didx.p), static_cast<const T*>(dval.p), n, p, X, ld,
-                          d->stream);
+    DevArr<int64_t> dptr;
+    DevArr<int32_t> didx;
+    DevArr<T> dval;
+    dptr.alloc(size_t(p + 1)), didx.alloc(nz1), dval.alloc(nz1);
+    AHIP_CHECK(hipMemcpyAsync(dptr, indptr, size_t(p + 1) * sizeof(int64_t), hipMemcpyHostToDevice, d->stream));
+    AHIP_CHECK(hipMemcpyAsync(didx, indices, size_t(nnz) * sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
+    AHIP_CHECK(hipMemcpyAsync(dval, values, size_t(nnz) * sizeof(T), hipMemcpyHostToDevice, d->stream));
+    launch_csc_scatter<T>(dptr, didx, dval, n, p, X, d->ld, d->stream);
     AHIP_CHECK(hipStreamSynchronize(d->stream));
 }
 
@@ -252,16 +266,11 @@ void op_cov(adelie_hip_design* d, int64_t j, int64_t q, const T* sw, T* out) {
 // A = X^T X in column panels of 2048 columns (the Gram kernel's K-split partials stay bounded); unit weights, no centring
 template <class T>
 static void cov_lazy_t(adelie_hip_design* X, adelie_hip_design* A) {
-    constexpr int64_t kAlign = 32, PANEL = 2048;
+    constexpr int64_t PANEL = 2048;
     const int64_t n = X->n, p = X->p;
-    const int64_t ld = ((p + kAlign - 1) / kAlign) * kAlign;
     hipStream_t s = A->stream;
-    T* C = nullptr;
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&C), size_t(ld) * size_t(p) * sizeof(T)));
-    A->X = C;
-    A->ld = ld;
-    A->owned = true;
-    AHIP_CHECK(hipMemsetAsync(C, 0, size_t(ld) * size_t(p) * sizeof(T), s));
+    T* C = alloc_dense<T>(A, true);
+    const int64_t ld = A->ld;
     DevBuf<T> ones, work;
     DevBuf<int32_t> cols;
     std::vector<T> h1(size_t(n), T(1));
@@ -454,17 +463,10 @@ void check_col(const adelie_hip_design* d, int64_t j, int64_t q, const char* wha
 }
 
 // ---- factor designs: one-hot / pairwise interactions of a resident table Z ---------------------------------------------------
-std::string gib(double bytes) {
-    char buf[64];
-    std::snprintf(buf, sizeof buf, "%.2f GiB", bytes / double(int64_t(1) << 30));
-    return buf;
-}
-
 // `blocks` describe the expanded design (col0 / ncols still unset); fills them in, allocates the expanded matrix, the copy of Z
 // and the tables on Z's device, and runs the expansion kernel.  `what`: "one_hot" / "interaction" for the messages.
 template <class T>
 void create_factor_t(adelie_hip_design* Z, std::vector<FactorBlock>& blocks, const char* what, adelie_hip_design** out) {
-    constexpr int64_t kAlign = 32;
     const int64_t n = Z->n, dz = Z->p;
     std::vector<int64_t> outer(blocks.size() + 1, 0);
     const double max_cols = double((int64_t(1) << 31) - 64);
@@ -485,31 +487,20 @@ void create_factor_t(adelie_hip_design* Z, std::vector<FactorBlock>& blocks, con
     }
     DesignGuard g(new_design(n, P, Z->dtype, Z->device));
     adelie_hip_design* d = g.get();
-    const int64_t ld = ((n + kAlign - 1) / kAlign) * kAlign;
     hipStream_t s = d->stream;
-    T* X = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&X), size_t(ld) * size_t(P) * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        throw make_core_error(std::string(what) + "(): could not allocate the expanded design (" + std::to_string(n) + " x " +
-                              std::to_string(P) + ", " + gib(double(ld) * double(P) * sizeof(T)) + ") on the device.");
-    }
-    d->X = X;
-    d->ld = ld;
-    d->owned = true;
-    d->kind = adelie_hip_design::kDense;
-    T* fz = nullptr;
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fz), size_t(ld) * size_t(dz) * sizeof(T)));
-    d->fz = fz;
+    T* X = alloc_dense<T>(d, false, what); // (padding rows zeroed: vector loads past n never see NaN payloads)
+    const int64_t ld = d->ld;
+    d->fz.alloc(size_t(ld) * size_t(dz) * sizeof(T));
+    T* fz = static_cast<T*>(d->fz);
     d->fz_ld = ld;
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->fblk), blocks.size() * sizeof(FactorBlock)));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->fchunk), chunks.size() * sizeof(FactorChunk)));
+    d->fblk.alloc(blocks.size());
+    d->fchunk.alloc(chunks.size());
     d->f_nchunk = int64_t(chunks.size());
     d->f_outer = outer;
     AHIP_CHECK(hipMemcpyAsync(d->fblk, blocks.data(), blocks.size() * sizeof(FactorBlock), hipMemcpyHostToDevice, s));
     AHIP_CHECK(hipMemcpyAsync(d->fchunk, chunks.data(), chunks.size() * sizeof(FactorChunk), hipMemcpyHostToDevice, s));
-    // zero the padding rows (vector loads past n never see NaN payloads), then copy Z and expand
+    // copy Z (its padding rows zeroed too) and expand
     AHIP_CHECK(hipMemsetAsync(fz, 0, size_t(ld) * size_t(dz) * sizeof(T), s));
-    if (ld > n) AHIP_CHECK(hipMemset2DAsync(X + n, size_t(ld) * sizeof(T), 0, size_t(ld - n) * sizeof(T), size_t(P), s));
     AHIP_CHECK(hipStreamSynchronize(Z->stream)); // (Z's own creation may still be in flight on its stream)
     launch_derive_dense<T>(Z->dense<T>(), n, dz, nullptr, nullptr, nullptr, nullptr, fz, ld, s);
     launch_factor_expand<T>(d->factor_view<T>(), X, ld, s);
@@ -521,8 +512,6 @@ void create_factor_t(adelie_hip_design* Z, std::vector<FactorBlock>& blocks, con
 // mask that the structured sweep reads, on Z's device.
 template <class T>
 void create_relu_t(adelie_hip_design* Z, const uint8_t* mask, int64_t m, int gated, adelie_hip_design** out) {
-    constexpr int64_t kAlign = 32; // (>= kReluStep: a step of the structured sweep never leaves a column's padding)
-    static_assert(kAlign % kReluStep == 0, "the padded rows must cover the sweep's last step");
     const int64_t n = Z->n, dz = Z->p;
     const double cols = double(gated ? 1 : 2) * double(m) * double(dz);
     if (cols > double((int64_t(1) << 31) - 64))
@@ -531,31 +520,20 @@ void create_relu_t(adelie_hip_design* Z, const uint8_t* mask, int64_t m, int gat
     const int64_t P = int64_t(cols);
     DesignGuard g(new_design(n, P, Z->dtype, Z->device));
     adelie_hip_design* d = g.get();
-    const int64_t ld = ((n + kAlign - 1) / kAlign) * kAlign;
     hipStream_t s = d->stream;
-    T* X = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&X), std::max<size_t>(16, size_t(ld) * size_t(P) * sizeof(T))) != hipSuccess) {
-        (void)hipGetLastError();
-        throw make_core_error("convex_relu(): could not allocate the expanded design (" + std::to_string(n) + " x " + std::to_string(P) +
-                              ", " + gib(double(ld) * double(P) * sizeof(T)) + ") on the device.");
-    }
-    d->X = X;
-    d->ld = ld;
-    d->owned = true;
-    d->kind = adelie_hip_design::kDense;
-    T* fz = nullptr;
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&fz), std::max<size_t>(16, size_t(ld) * size_t(dz) * sizeof(T))));
-    d->fz = fz;
+    T* X = alloc_dense<T>(d, false, "convex_relu"); // (padding rows zeroed: the sweep's vector loads run into them)
+    const int64_t ld = d->ld;
+    d->fz.alloc(std::max<size_t>(16, size_t(ld) * size_t(dz) * sizeof(T)));
+    T* fz = static_cast<T*>(d->fz);
     d->fz_ld = ld;
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rmask), std::max<size_t>(16, size_t(ld) * size_t(m))));
+    d->rmask.alloc(std::max<size_t>(16, size_t(ld) * size_t(m)));
     d->rmask_ld = ld;
     d->r_d = dz;
     d->r_m = m;
     d->r_gated = gated ? 1 : 0;
-    // zero the padding rows (the sweep's vector loads run into them), then copy Z and the mask and expand
+    // copy Z and the mask (their padding rows zeroed too) and expand
     AHIP_CHECK(hipMemsetAsync(fz, 0, size_t(ld) * size_t(dz) * sizeof(T), s));
     AHIP_CHECK(hipMemsetAsync(d->rmask, 0, size_t(ld) * size_t(m), s));
-    if (ld > n && P > 0) AHIP_CHECK(hipMemset2DAsync(X + n, size_t(ld) * sizeof(T), 0, size_t(ld - n) * sizeof(T), size_t(P), s));
     if (n > 0 && m > 0)
         AHIP_CHECK(hipMemcpy2DAsync(d->rmask, size_t(ld), mask, size_t(n), size_t(n), size_t(m), hipMemcpyHostToDevice, s));
     AHIP_CHECK(hipStreamSynchronize(Z->stream)); // (Z's own creation may still be in flight on its stream)
@@ -598,41 +576,9 @@ namespace {
 template <class T>
 void derive_t(adelie_hip_design* src, adelie_hip_design* d, const int64_t* rows, int64_t nrows, const int64_t* cols,
               int64_t ncols, const double* centers, const double* scales) {
-    constexpr int64_t kAlign = 32;
     const int64_t nout = d->n, pout = d->p;
-    if (src->is_snp() && !centers && !scales) { // a subset of a 2-bit design stays 2 bits per call
-        hipStream_t s = d->stream;
-        d->kind = adelie_hip_design::kSnp;
-        d->ldb = (((nout + 3) / 4 + 127) / 128) * 128;
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bits), size_t(d->ldb) * size_t(pout)));
-        AHIP_CHECK(hipMalloc(&d->impute, size_t(pout) * sizeof(T)));
-        int64_t *drows = nullptr, *dcols = nullptr;
-        if (rows) {
-            drows = scratch<int64_t>(d->s_idx1, size_t(nrows));
-            AHIP_CHECK(hipMemcpyAsync(drows, rows, size_t(nrows) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        }
-        if (cols) {
-            dcols = scratch<int64_t>(d->s_idx2, size_t(ncols));
-            AHIP_CHECK(hipMemcpyAsync(dcols, cols, size_t(ncols) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-        }
-        AHIP_CHECK(hipStreamSynchronize(src->stream));
-        launch_snp_subset(src->snp(), nout, pout, drows, dcols, d->bits, d->ldb, s);
-        launch_gather_cols<T>(snp_impute<T>(*src), dcols, pout, static_cast<T*>(d->impute), s);
-        AHIP_CHECK(hipStreamSynchronize(s));
-        return;
-    }
-    const int64_t ld = ((nout + kAlign - 1) / kAlign) * kAlign;
-    T* X = nullptr;
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&X), size_t(ld) * size_t(pout) * sizeof(T)));
-    d->X = X;
-    d->ld = ld;
-    d->owned = true;
-    d->kind = adelie_hip_design::kDense;
     hipStream_t s = d->stream;
-    AHIP_CHECK(hipMemsetAsync(X, 0, size_t(ld) * size_t(pout) * sizeof(T), s));
     int64_t *drows = nullptr, *dcols = nullptr;
-    T *dc = nullptr, *ds = nullptr;
-    std::vector<T> hc, hs;
     if (rows) {
         drows = scratch<int64_t>(d->s_idx1, size_t(nrows));
         AHIP_CHECK(hipMemcpyAsync(drows, rows, size_t(nrows) * sizeof(int64_t), hipMemcpyHostToDevice, s));
@@ -641,6 +587,19 @@ void derive_t(adelie_hip_design* src, adelie_hip_design* d, const int64_t* rows,
         dcols = scratch<int64_t>(d->s_idx2, size_t(ncols));
         AHIP_CHECK(hipMemcpyAsync(dcols, cols, size_t(ncols) * sizeof(int64_t), hipMemcpyHostToDevice, s));
     }
+    if (src->is_snp() && !centers && !scales) { // a subset of a 2-bit design stays 2 bits per call
+        snp_alloc_bits(d);
+        snp_alloc_impute(d);
+        AHIP_CHECK(hipStreamSynchronize(src->stream));
+        launch_snp_subset(src->snp(), nout, pout, drows, dcols, d->bits, d->ldb, s);
+        launch_gather_cols<T>(snp_impute<T>(*src), dcols, pout, static_cast<T*>(d->impute), s);
+        AHIP_CHECK(hipStreamSynchronize(s));
+        return;
+    }
+    T* X = alloc_dense<T>(d, true);
+    const int64_t ld = d->ld;
+    T *dc = nullptr, *ds = nullptr;
+    std::vector<T> hc, hs;
     if (centers) {
         hc.assign(centers, centers + pout);
         dc = scratch<T>(d->s_p1, size_t(pout));
@@ -662,16 +621,12 @@ void derive_t(adelie_hip_design* src, adelie_hip_design* d, const int64_t* rows,
 // decoded) into its slice of a new dense array
 template <class T>
 void concat_t(adelie_hip_design* const* srcs, int64_t k, int axis, adelie_hip_design* d) {
-    constexpr int64_t kAlign = 32;
-    const int64_t nout = d->n, pout = d->p;
+    hipStream_t s = d->stream;
     bool all_snp = axis == 1;
     for (int64_t m = 0; m < k && all_snp; ++m) all_snp = srcs[m]->is_snp() && !srcs[m]->std_center && srcs[m]->ldb == srcs[0]->ldb;
     if (all_snp) { // 2-bit designs side by side stay a 2-bit design: their columns are copied as they are
-        hipStream_t s = d->stream;
-        d->kind = adelie_hip_design::kSnp;
-        d->ldb = srcs[0]->ldb;
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bits), size_t(d->ldb) * size_t(pout)));
-        AHIP_CHECK(hipMalloc(&d->impute, size_t(pout) * sizeof(T)));
+        snp_alloc_bits(d); // (ldb follows from n alone: the sources' own)
+        snp_alloc_impute(d);
         int64_t off = 0;
         for (int64_t m = 0; m < k; ++m) {
             adelie_hip_design* src = srcs[m];
@@ -683,15 +638,8 @@ void concat_t(adelie_hip_design* const* srcs, int64_t k, int axis, adelie_hip_de
         AHIP_CHECK(hipStreamSynchronize(s));
         return;
     }
-    const int64_t ld = ((nout + kAlign - 1) / kAlign) * kAlign;
-    T* X = nullptr;
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&X), size_t(ld) * size_t(pout) * sizeof(T)));
-    d->X = X;
-    d->ld = ld;
-    d->owned = true;
-    d->kind = adelie_hip_design::kDense;
-    hipStream_t s = d->stream;
-    AHIP_CHECK(hipMemsetAsync(X, 0, size_t(ld) * size_t(pout) * sizeof(T), s));
+    T* X = alloc_dense<T>(d, true);
+    const int64_t ld = d->ld;
     int64_t off = 0;
     for (int64_t m = 0; m < k; ++m) {
         adelie_hip_design* src = srcs[m];
@@ -950,9 +898,7 @@ int adelie_hip_design_create_cov_csc(const int64_t* indptr, const int32_t* indic
     d->nnz = nnz;
     d->cov_lanes = cov_csc_lanes(nnz, p);
     hipStream_t s = d->stream;
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cptr), size_t(p + 1) * sizeof(int64_t)));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cidx), nz1 * sizeof(int32_t)));
-    AHIP_CHECK(hipMalloc(&d->cval, nz1 * vs));
+    d->cptr.alloc(size_t(p + 1)), d->cidx.alloc(nz1), d->cval.alloc(nz1 * vs);
     AHIP_CHECK(hipMemcpyAsync(d->cptr, indptr, size_t(p + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
     if (nnz) {
         AHIP_CHECK(hipMemcpyAsync(d->cidx, indices, size_t(nnz) * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -1041,9 +987,7 @@ int adelie_hip_design_create_standardized(adelie_hip_design* src, const double* 
     DesignGuard g(d);
     const int64_t p = src->p;
     const size_t vs = src->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
-    AHIP_CHECK(hipMalloc(&d->std_center, size_t(p) * vs));
-    d->std_owned = true;
-    AHIP_CHECK(hipMalloc(&d->std_iscale, size_t(p) * vs));
+    d->std_center.alloc(size_t(p) * vs), d->std_iscale.alloc(size_t(p) * vs);
     if (src->dtype == ADELIE_HIP_F64) {
         std::vector<double> is(static_cast<size_t>(p));
         for (int64_t j = 0; j < p; ++j) is[size_t(j)] = 1.0 / scales[j];
@@ -1122,12 +1066,7 @@ int adelie_hip_design_batch_stats(adelie_hip_design* d, double* out) {
 }
 
 static adelie_hip_design* shadow_owner(adelie_hip_design* d) { return d->batch_owner ? d->batch_owner : d; }
-static void shadow_free(adelie_hip_design* o) {
-    (void)hipFree(o->sh_X); (void)hipFree(o->sh_err); (void)hipFree(o->sh_nrm); (void)hipFree(o->sh_scale);
-    o->sh_X = nullptr; o->sh_err = nullptr; o->sh_nrm = nullptr; o->sh_scale = nullptr;
-    o->sh_ld = 0;
-    o->sh_kind = ahip::kShadowF32;
-}
+static void shadow_free(adelie_hip_design* o) { o->ShadowArrs::reset(); }
 static size_t shadow_bytes(int kind, int64_t p, int64_t lds) {
     return size_t(p) * size_t(lds) * (kind == ahip::kShadowQ15 ? sizeof(int16_t) : sizeof(float)) +
            (kind == ahip::kShadowQ15 ? 3 : 2) * size_t(p) * sizeof(double);
@@ -1142,15 +1081,10 @@ static bool shadow_build(adelie_hip_design* d, adelie_hip_design* o, int kind) {
     AHIP_CHECK(hipMemGetInfo(&free_b, &total_b));
     const size_t keep = std::max<size_t>(size_t(4) << 30, total_b / 10);
     bool ok = free_b >= need && free_b - need >= keep;
-    int32_t* bad = nullptr;
-    if (ok) {
-        ok = hipMalloc(&o->sh_X, size_t(d->p) * size_t(lds) * (q15 ? sizeof(int16_t) : sizeof(float))) == hipSuccess &&
-             hipMalloc((void**)&o->sh_err, size_t(d->p) * sizeof(double)) == hipSuccess &&
-             hipMalloc((void**)&o->sh_nrm, size_t(d->p) * sizeof(double)) == hipSuccess &&
-             (!q15 || hipMalloc((void**)&o->sh_scale, size_t(d->p) * sizeof(double)) == hipSuccess) &&
-             hipMalloc((void**)&bad, sizeof(int32_t)) == hipSuccess;
-        if (!ok) (void)hipGetLastError();
-    }
+    DevArr<int32_t> bad;
+    if (ok)
+        ok = o->sh_X.try_alloc(size_t(d->p) * size_t(lds) * (q15 ? sizeof(int16_t) : sizeof(float))) && o->sh_err.try_alloc(size_t(d->p)) &&
+             o->sh_nrm.try_alloc(size_t(d->p)) && (!q15 || o->sh_scale.try_alloc(size_t(d->p))) && bad.try_alloc(1);
     if (ok) {
         int32_t h_bad = 0;
         ok = hipMemsetAsync(bad, 0, sizeof(int32_t), d->stream) == hipSuccess;
@@ -1167,7 +1101,6 @@ static bool shadow_build(adelie_hip_design* d, adelie_hip_design* o, int kind) {
         o->sh_kind = kind;
         ++o->sh_n_builds;
     }
-    (void)hipFree(bad);
     if (!ok) shadow_free(o);
     return ok;
 }
@@ -1270,23 +1203,7 @@ int adelie_hip_design_alias(adelie_hip_design* src, adelie_hip_design** out) {
     DesignGuard g(new_design(src->n, src->p, src->dtype, src->device)); // own stream, own scratch
     adelie_hip_design* d = g.get();
     d->kind = src->kind;
-    d->X = src->X;
-    d->ld = src->ld;
-    d->owned = false;
-    d->bits = src->bits;
-    d->ldb = src->ldb;
-    d->impute = src->impute;
-    d->cptr = src->cptr; d->cidx = src->cidx; d->cval = src->cval;
-    d->rptr = src->rptr; d->rcol = src->rcol; d->rval = src->rval;
-    d->nnz = src->nnz;
-    d->bptr = src->bptr; d->sp_nb = src->sp_nb; d->sp_rb = src->sp_rb;
-    d->tptr = src->tptr; d->trow = src->trow; d->tval = src->tval; d->sp_nt = src->sp_nt; d->sp_th = src->sp_th;
-    d->std_center = src->std_center; d->std_iscale = src->std_iscale; // (not owned: std_owned stays false)
-    d->fz = src->fz; d->fz_ld = src->fz_ld; d->fblk = src->fblk; d->fchunk = src->fchunk; d->f_nchunk = src->f_nchunk;
-    d->f_outer = src->f_outer; // (a factor design's alias keeps the structure: CV folds sweep the same way)
-    d->rmask = src->rmask; d->rmask_ld = src->rmask_ld; d->r_d = src->r_d; d->r_m = src->r_m; d->r_gated = src->r_gated;
-    d->rz_seg = src->rz_seg; d->rz_idx = src->rz_idx; d->rz_val = src->rz_val; d->rbits = src->rbits; d->rz_nnz = src->rz_nnz;
-    d->alias = true;
+    d->borrow_arrays(*src);
     d->batch_owner = src->batch_owner ? src->batch_owner : src;
     *out = g.release();
     ABI_CATCH
@@ -1307,15 +1224,13 @@ int adelie_hip_design_create_slice(adelie_hip_design* base, int64_t r0, int64_t 
     DesignGuard g(new_design(nr, nc, base->dtype, base->device)); // own stream, own scratch
     adelie_hip_design* d = g.get();
     d->kind = base->kind;
-    d->owned = false;
-    d->alias = true; // never frees what it points into
-    if (base->is_dense()) {
-        d->X = static_cast<char*>(base->X) + (c0 * base->ld + r0) * es;
+    if (base->is_dense()) { // (borrowed: a slice never frees what it points into)
+        d->X.borrow(static_cast<char*>(base->X) + (c0 * base->ld + r0) * es);
         d->ld = base->ld;
     } else {
-        d->bits = base->bits + c0 * base->ldb;
+        d->bits.borrow(base->bits + c0 * base->ldb);
         d->ldb = base->ldb;
-        d->impute = static_cast<char*>(base->impute) + c0 * es;
+        d->impute.borrow(static_cast<char*>(base->impute) + c0 * es);
     }
     *out = g.release();
     ABI_CATCH
@@ -1334,13 +1249,8 @@ int adelie_hip_design_create_multi(adelie_hip_design* base, int64_t K, int inter
     DesignGuard g(new_design(base->n * K, (base->p + icpt) * K, base->dtype, base->device)); // own stream + scratch
     adelie_hip_design* d = g.get();
     d->kind = adelie_hip_design::kMulti;
-    d->X = base->X;
-    d->ld = base->ld;
-    d->bits = base->bits; // (2-bit base: the K-wide kernels decode the calls themselves, MultiView::bits)
-    d->ldb = base->ldb;
-    d->impute = base->impute;
-    d->owned = false;
-    d->alias = true;
+    d->DenseArrs::borrow_from(*base);
+    d->SnpArrs::borrow_from(*base); // (2-bit base: the K-wide kernels decode the calls themselves, MultiView::bits)
     d->mK = K;
     d->micpt = int(icpt);
     d->nb = base->n;
@@ -1348,7 +1258,7 @@ int adelie_hip_design_create_multi(adelie_hip_design* base, int64_t K, int inter
     {   // the column of ones (padded like a design column so that vector loads past nb stay in bounds)
         const size_t esz = base->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
         const int64_t len = ((base->n + 31) / 32) * 32;
-        AHIP_CHECK(hipMalloc(&d->ones, size_t(len) * esz));
+        d->ones.alloc(size_t(len) * esz);
         AHIP_CHECK(hipMemsetAsync(d->ones, 0, size_t(len) * esz, d->stream));
         DTYPE_DISPATCH(d, launch_fill<T>((T*)d->ones, T(1), base->n, d->stream))
         AHIP_CHECK(hipStreamSynchronize(d->stream));
@@ -1482,26 +1392,13 @@ int adelie_hip_design_destroy(adelie_hip_design* d) {
         (void)hipStreamSynchronize(d->stream);
         (void)hipStreamDestroy(d->stream);
     }
-    if (d->owned && d->X && !d->alias) (void)hipFree(d->X);
-    if (d->bits && !d->alias) (void)hipFree(d->bits);
-    if (d->impute && !d->alias) (void)hipFree(d->impute);
-    if (!d->alias) {
-        (void)hipFree(d->cptr); (void)hipFree(d->cidx); (void)hipFree(d->cval);
-        (void)hipFree(d->rptr); (void)hipFree(d->rcol); (void)hipFree(d->rval);
-        (void)hipFree(d->bptr);
-        (void)hipFree(d->tptr); (void)hipFree(d->trow); (void)hipFree(d->tval);
-        (void)hipFree(d->fz); (void)hipFree(d->fblk); (void)hipFree(d->fchunk);
-        (void)hipFree(d->rmask);
-        (void)hipFree(d->rz_seg); (void)hipFree(d->rz_idx); (void)hipFree(d->rz_val); (void)hipFree(d->rbits);
-    }
-    if (d->std_owned) { (void)hipFree(d->std_center); (void)hipFree(d->std_iscale); }
-    if (d->ones) (void)hipFree(d->ones);
     if (d->batcher) adelie_hip_internal_free_batcher(d->batcher);
-    shadow_free(d);
-    delete d;
+    delete d; // (releases the arrays the handle owns)
     if (live_designs().fetch_sub(1) == 1) DevPool::trim();
     return 0;
 }
+
+int64_t adelie_hip_design_owned_bytes(void) { return owned_arr_bytes().load(); }
 
 int64_t adelie_hip_design_rows(const adelie_hip_design* d) { return d->n; }
 int64_t adelie_hip_design_cols(const adelie_hip_design* d) { return d->p; }

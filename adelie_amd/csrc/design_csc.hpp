@@ -11,7 +11,7 @@ static void csc_finish(adelie_hip_design* d) {
     hipStream_t s = d->stream;
     csc_block_layout(n, vs, &d->sp_nb, &d->sp_rb);
     if (d->sp_nb > 1) {
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bptr), size_t(p) * size_t(d->sp_nb + 1) * sizeof(int64_t)));
+        d->bptr.alloc(size_t(p) * size_t(d->sp_nb + 1));
         launch_csc_block_ptr(d->cptr, d->cidx, p, d->sp_nb, d->sp_rb, d->bptr, s);
     }
     // Tile-major copy for the full sweeps (csc_tile_sweep_kernel): tiles of kCscTileBytes of an n-vector.  Built on the
@@ -23,9 +23,8 @@ static void csc_finish(adelie_hip_design* d) {
     const bool worth = nt > 1 && nt <= 4096 && nnz >= (int64_t(1) << 16) && nt * (p + 1) * 8 <= (int64_t(1) << 30) &&
                        nnz / (nt * p) >= 4; // (segments of a few entries at least: below, the pointers outweigh the entries)
     if (worth) {
-        DevTmp ctmp;
-        AHIP_CHECK(hipMalloc(&ctmp.p, size_t(p) * size_t(nt + 1) * sizeof(int64_t)));
-        int64_t* colptr = static_cast<int64_t*>(ctmp.p);
+        DevArr<int64_t> colptr;
+        colptr.alloc(size_t(p) * size_t(nt + 1));
         launch_csc_block_ptr(d->cptr, d->cidx, p, int(nt), th, colptr, s);
         std::vector<int64_t> cp(size_t(p) * size_t(nt + 1)), tp(size_t(nt) * size_t(p + 1));
         AHIP_CHECK(hipMemcpyAsync(cp.data(), colptr, cp.size() * sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -39,9 +38,7 @@ static void csc_finish(adelie_hip_design* d) {
             }
             row[p] = run;
         }
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->tptr), tp.size() * sizeof(int64_t)));
-        AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->trow), nz1 * sizeof(uint16_t)));
-        AHIP_CHECK(hipMalloc(&d->tval, nz1 * vs));
+        d->tptr.alloc(tp.size()), d->trow.alloc(nz1), d->tval.alloc(nz1 * vs);
         AHIP_CHECK(hipMemcpyAsync(d->tptr, tp.data(), tp.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
         DTYPE_DISPATCH(d, launch_csc_tile_scatter<T>(colptr, d->cidx, static_cast<const T*>(d->cval), p, int(nt), th, d->tptr, d->trow,
                                                      static_cast<T*>(d->tval), s))
@@ -58,20 +55,11 @@ static void csc_alloc(adelie_hip_design* d, int64_t nnz, const char* what) {
     d->nnz = nnz;
     const size_t vs = d->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
     const size_t nz1 = size_t(std::max<int64_t>(nnz, 1));
-    auto alloc = [&](void** p, size_t bytes) {
-        if (!what) AHIP_CHECK(hipMalloc(p, bytes));
-        else if (hipMalloc(p, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            throw make_core_error(std::string(what) + "could not allocate the expanded design (" + std::to_string(d->n) + " x " +
-                                  std::to_string(d->p) + ", " + std::to_string(nnz) + " stored entries) on the device.");
-        }
-    };
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->cptr), size_t(d->p + 1) * sizeof(int64_t)));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rptr), size_t(d->n + 1) * sizeof(int64_t)));
-    alloc(reinterpret_cast<void**>(&d->cidx), nz1 * sizeof(int32_t));
-    alloc(&d->cval, nz1 * vs);
-    alloc(reinterpret_cast<void**>(&d->rcol), nz1 * sizeof(int32_t));
-    alloc(&d->rval, nz1 * vs);
+    d->cptr.alloc(size_t(d->p + 1)), d->rptr.alloc(size_t(d->n + 1));
+    if (!what) d->cidx.alloc(nz1), d->cval.alloc(nz1 * vs), d->rcol.alloc(nz1), d->rval.alloc(nz1 * vs);
+    else if (!(d->cidx.try_alloc(nz1) && d->cval.try_alloc(nz1 * vs) && d->rcol.try_alloc(nz1) && d->rval.try_alloc(nz1 * vs)))
+        throw make_core_error(std::string(what) + "could not allocate the expanded design (" + std::to_string(d->n) + " x " +
+                              std::to_string(d->p) + ", " + std::to_string(nnz) + " stored entries) on the device.");
 }
 
 // The tail of a device build (d->p == cols_out): count(ccnt, rcnt) enqueues the kernels that count the entries per
@@ -85,25 +73,25 @@ static void csc_build_from_counts(adelie_hip_design* d, int64_t cols_counted, in
     const int64_t n = d->n;
     hipStream_t st = d->stream;
     const size_t segs = size_t(cols_counted) * size_t(nt), psegs = size_t(cols_out) * size_t(nt);
-    DevTmp ccnt, rcnt, cpos;
-    AHIP_CHECK(hipMalloc(&ccnt.p, segs * sizeof(int32_t)));
-    AHIP_CHECK(hipMalloc(&rcnt.p, size_t(n) * sizeof(int64_t)));
-    count(static_cast<int32_t*>(ccnt.p), static_cast<int64_t*>(rcnt.p));
+    DevArr<int32_t> ccnt;
+    DevArr<int64_t> rcnt, cpos;
+    ccnt.alloc(segs), rcnt.alloc(size_t(n));
+    count(ccnt, rcnt);
     AHIP_CHECK(hipGetLastError());
     std::vector<int32_t> col_cnt(segs);
     std::vector<int64_t> col_pos(psegs), cptr(size_t(cols_out) + 1), rptr(size_t(n) + 1);
-    AHIP_CHECK(hipMemcpyAsync(col_cnt.data(), ccnt.p, segs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    AHIP_CHECK(hipMemcpyAsync(rptr.data() + 1, rcnt.p, size_t(n) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    AHIP_CHECK(hipMemcpyAsync(col_cnt.data(), ccnt, segs * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    AHIP_CHECK(hipMemcpyAsync(rptr.data() + 1, rcnt, size_t(n) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     AHIP_CHECK(hipStreamSynchronize(st));
     int64_t nnz = 0;
     if (const char* e = csc_offsets_from_counts(col_cnt.data(), cols_counted, cols_out, nt, rptr.data() + 1, n, cptr.data(), col_pos.data(), rptr.data(), &nnz))
         throw make_core_error(std::string(prefix) + e);
     csc_alloc(d, nnz, oom_what);
-    AHIP_CHECK(hipMalloc(&cpos.p, psegs * sizeof(int64_t)));
+    cpos.alloc(psegs);
     AHIP_CHECK(hipMemcpyAsync(d->cptr, cptr.data(), cptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     AHIP_CHECK(hipMemcpyAsync(d->rptr, rptr.data(), rptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    AHIP_CHECK(hipMemcpyAsync(cpos.p, col_pos.data(), psegs * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    fill(static_cast<const int64_t*>(cpos.p));
+    AHIP_CHECK(hipMemcpyAsync(cpos, col_pos.data(), psegs * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    fill(cpos);
     AHIP_CHECK(hipGetLastError());
     AHIP_CHECK(hipStreamSynchronize(st)); // (the counts, the segment starts and the caller's own temporaries are freed on the way out)
     csc_finish(d);
@@ -117,10 +105,10 @@ static void phased_build(adelie_hip_design* d, const uint8_t* table, int64_t s, 
     const int nt = phased_tiles(n);
     if (s * int64_t(nt) >= (int64_t(1) << 31)) throw make_core_error("snp_phased_ancestry: too many (SNP, row tile) pairs.");
     hipStream_t st = d->stream;
-    DevTmp code;
-    AHIP_CHECK(hipMalloc(&code.p, size_t(n) * size_t(2 * s)));
-    const uint8_t* dcode = static_cast<const uint8_t*>(code.p);
-    AHIP_CHECK(hipMemcpyAsync(code.p, table, size_t(n) * size_t(2 * s), hipMemcpyHostToDevice, st));
+    DevArr<uint8_t> code;
+    code.alloc(size_t(n) * size_t(2 * s));
+    const uint8_t* dcode = code;
+    AHIP_CHECK(hipMemcpyAsync(code, table, size_t(n) * size_t(2 * s), hipMemcpyHostToDevice, st));
     csc_build_from_counts(
         d, d->p, d->p, nt, [&](int32_t* ccnt, int64_t* rcnt) { launch_phased_count(dcode, n, s, A, ccnt, rcnt, st); },
         [&](const int64_t* cpos) {
@@ -154,20 +142,18 @@ static void relu_csc_build(adelie_hip_design* Z, const uint8_t* mask, int64_t m,
     d->r_gated = gated ? 1 : 0;
     d->rz_nnz = znnz;
     const size_t zn1 = size_t(std::max<int64_t>(znnz, 1));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rz_seg), size_t(dz) * size_t(nt + 1) * sizeof(int64_t)));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rz_idx), zn1 * sizeof(int32_t)));
-    AHIP_CHECK(hipMalloc(&d->rz_val, zn1 * vs));
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->rbits), size_t(sh.words) * size_t(n) * sizeof(uint32_t)));
+    d->rz_seg.alloc(size_t(dz) * size_t(nt + 1)), d->rz_idx.alloc(zn1), d->rz_val.alloc(zn1 * vs);
+    d->rbits.alloc(size_t(sh.words) * size_t(n));
     AHIP_CHECK(hipStreamSynchronize(Z->stream)); // (Z's own creation may still be in flight on its stream)
     if (znnz) {
         AHIP_CHECK(hipMemcpyAsync(d->rz_idx, Z->cidx, size_t(znnz) * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
         AHIP_CHECK(hipMemcpyAsync(d->rz_val, Z->cval, size_t(znnz) * vs, hipMemcpyDeviceToDevice, st));
     }
     launch_csc_block_ptr(Z->cptr, d->rz_idx, dz, nt, sh.tile_rows, d->rz_seg, st);
-    DevTmp mbytes;
-    AHIP_CHECK(hipMalloc(&mbytes.p, size_t(n) * size_t(m)));
-    AHIP_CHECK(hipMemcpyAsync(mbytes.p, mask, size_t(n) * size_t(m), hipMemcpyHostToDevice, st));
-    launch_relu_sparse_pack(static_cast<const uint8_t*>(mbytes.p), n, m, d->rbits, st);
+    DevArr<uint8_t> mbytes;
+    mbytes.alloc(size_t(n) * size_t(m));
+    AHIP_CHECK(hipMemcpyAsync(mbytes, mask, size_t(n) * size_t(m), hipMemcpyHostToDevice, st));
+    launch_relu_sparse_pack(mbytes, n, m, d->rbits, st);
     csc_build_from_counts(
         d, md, P, nt,
         [&](int32_t* ccnt, int64_t* rcnt) { DTYPE_DISPATCH(d, launch_relu_sparse_count<T>(d->relu_csc_view<T>(), Z->rptr, ccnt, rcnt, st)) },

@@ -1,28 +1,19 @@
 // design_snp.hpp — part of design.hip, which includes it inside its extern "C" block (one translation unit, several readable
 // files): the constructors of a 2-bit SNP design (int8 calldata, an unphased .snpdat image, a PLINK .bed image) and what they share.
 
-// kind, the leading dimension of the 2-bit columns, and the packed matrix itself
-static void snp_alloc_bits(adelie_hip_design* d) {
-    d->kind = adelie_hip_design::kSnp;
-    d->ldb = (((d->n + 3) / 4 + 127) / 128) * 128;
-    AHIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->bits), size_t(d->ldb) * size_t(d->p)));
-}
-
+// (snp_alloc_bits / snp_alloc_impute: design.hip, next to alloc_dense)
 // The columns go through a temporary device block in panels that bound it by 2^28 bytes (or one column) where a column takes
 // col_bytes there: stage(j0, pc, tmp) fills the block for columns [j0, j0 + pc) and launches their transcode on d->stream.
 static void snp_for_each_panel(adelie_hip_design* d, int64_t col_bytes, const std::function<void(int64_t, int64_t, void*)>& stage) {
     const int64_t p = d->p, panel = std::min(p, std::max<int64_t>(1, (int64_t(1) << 28) / col_bytes));
     DevTmp tmp;
-    AHIP_CHECK(hipMalloc(&tmp.p, size_t(col_bytes) * size_t(panel)));
+    tmp.alloc(size_t(col_bytes) * size_t(panel));
     for (int64_t j0 = 0; j0 < p; j0 += panel) {
-        stage(j0, std::min(panel, p - j0), tmp.p);
+        stage(j0, std::min(panel, p - j0), tmp);
         AHIP_CHECK(hipStreamSynchronize(d->stream));
     }
 }
 
-static void snp_alloc_impute(adelie_hip_design* d) {
-    AHIP_CHECK(hipMalloc(&d->impute, size_t(d->p) * (d->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float))));
-}
 static void upload_impute(adelie_hip_design* d, const double* impute) {
     const size_t p = size_t(d->p);
     snp_alloc_impute(d);

@@ -348,7 +348,7 @@
         int vec = 4;
         if (dense()) {
             constexpr int V = int(16 / sizeof(T));
-            const bool vecok = (D->ld % V == 0) && ((reinterpret_cast<uintptr_t>(D->X) % 16) == 0);
+            const bool vecok = (D->ld % V == 0) && ((reinterpret_cast<uintptr_t>(D->X.get()) % 16) == 0);
             vec = vecok ? V : 1;
         }
         const int64_t rs = 64 * vec, ns = (n + rs - 1) / rs, nwg = (ns + 3) / 4;

@@ -899,7 +899,7 @@
         if (!multi()) {
             if (dense()) {
                 constexpr int V = int(16 / sizeof(T));
-                tail_ok = (64 * V >= 128) && (D->ld % V == 0) && ((reinterpret_cast<uintptr_t>(D->X) % 16) == 0);
+                tail_ok = (64 * V >= 128) && (D->ld % V == 0) && ((reinterpret_cast<uintptr_t>(D->X.get()) % 16) == 0);
             } else {
                 tail_ok = true; // (SNP: 4 rows per lane and load, 256-row slices)
             }

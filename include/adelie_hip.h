@@ -257,6 +257,12 @@ int adelie_hip_design_shadow_stats(adelie_hip_design* d, int64_t* out);
  * column from its copy relative to its norm}.  An addition to ABI 14. */
 int adelie_hip_design_shadow_info(adelie_hip_design* d, int64_t* out_i, double* out_d);
 int adelie_hip_design_destroy(adelie_hip_design* d);
+/* Diagnostic, an addition to ABI 14: the bytes of device memory that the design handles of this process own right now -- the
+ * matrices, index arrays, tables and shadow copies that adelie_hip_design_destroy (or adelie_hip_design_drop_shadow) gives back,
+ * plus the temporaries of a constructor while it runs.  Aliases, slices, views over a base and adopted tensors count nothing for
+ * what they share.  Not counted: the handles' scratch space, the block cache, the sweep batcher and a solve's memory.  Free
+ * device memory is device-wide; this count is the process's own, so tests can check the handles' ownership exactly. */
+int64_t adelie_hip_design_owned_bytes(void);
 
 /* cv_grpnet post-processing on the device (adelie/cv.py:296-312, diagnostic.py:30-121): for the L
  * sparse coefficient rows (CSR, int64 indices) computes eta_l = X beta_l + intercepts[l] + offsets and returns

@@ -99,9 +99,21 @@ def ops_digest(M, with_cov):
         o = np.empty((p_, p_), dtype=dt); A.to_dense(0, p_, o); h.update(np.ascontiguousarray(o).tobytes())
     return h.hexdigest()[:16]
 Xo_h = np.asfortranarray(rng.normal(size=(2003, 300)))
-for name, M, with_cov in [("dense_f64", ad.matrix.dense(Xo_h), True),
+Mo = ad.matrix.dense(Xo_h)
+# (handles that borrow their arrays -- an alias, a column slice -- and the derived 2-bit, convex-relu and phased designs included)
+rmask = np.random.RandomState(12).uniform(size=(2003, 4)) < 0.5
+Zs_h = sp.random(2003, 10, density=0.2, random_state=np.random.RandomState(13), format="csc", dtype=np.float64)
+pr = np.random.RandomState(14)
+for name, M, with_cov in [("dense_f64", Mo, True),
                           ("dense_f32", ad.matrix.dense(np.asfortranarray(Xo_h.astype(np.float32))), True),
-                          ("snp", X, True), ("csc", Xs, False), ("std_csc", ad.matrix.standardize(Xs), False)]:
+                          ("snp", X, True), ("csc", Xs, False), ("std_csc", ad.matrix.standardize(Xs), False),
+                          ("alias_dense", Mo.alias(), True), ("slice_dense", ad.matrix.subset(Mo, np.arange(10, 110), axis=1), True),
+                          ("concat_snp", ad.matrix.concatenate([X, X], axis=1), True),
+                          ("subset_snp", ad.matrix.subset(X, np.arange(0, 600, 3), axis=1), True),
+                          ("relu_dense", ad.matrix.convex_relu(Xo_h[:, :6], rmask), True),
+                          ("relu_csc", ad.matrix.convex_relu(Zs_h, rmask, resident="csc"), False),
+                          ("phased", ad.matrix.snp_phased_calldata(pr.randint(0, 2, size=(2003, 40)).astype(np.int8),
+                                                                   pr.randint(0, 3, size=(2003, 40)).astype(np.int8), 3), False)]:
     print("ops", name, ops_digest(M, with_cov))
 # the filtered invariance sweep at kernel level, per shadow kind: grad (the shadow's own values in the unlisted columns included),
 # the exact mask and info of adelie_hip_filter_sweep_test, with screen groups and one group without a penalty
