@@ -186,17 +186,21 @@ __device__ __forceinline__ double list_column_sum(const DenseAcc<double>& X, con
 }
 
 // The two kinds of copy as the shadow sweep sees them: the element type, the 16-byte load of VEC rows of one column, row e of
-// a loaded vector as a double (the sweep takes e = 0 .. VEC-1 in order), the panel width CB, the unroll count of the body
-// loop, and whether a column's sum is multiplied by scale[c] before the centring term.
+// a loaded vector as a double (the sweep takes e = 0 .. VEC-1 in order), the panel width CB, whether the body loop is the
+// rotation of two half panels (kPipelined) or the plain loop unrolled kUnroll times, the waves per SIMD the compiler has to
+// leave room for (1: no demand), and whether a column's sum is multiplied by scale[c] before the centring term.
 struct ShadowF32 {
     using elem = float;
     using vec = f4_t;
     static constexpr int CB = kShadowCB, VEC = kShadowVec, kUnroll = 2;
-    static constexpr bool kScaled = false;
+    static constexpr bool kScaled = false, kPipelined = false;
+    static constexpr int kMinWaves = 1;
     static __device__ __forceinline__ double row(vec x, int e) { return double(x[e]); }
 };
 // q15: 16-byte non-temporal loads of 8 rows per lane and column, q . v accumulated in f64 and the sum of a workgroup's rows
 // multiplied by scale[c] once (a row split's partial is scaled before it is stored: sweep_reduce_kernel is shared).
+// The body loop is pipelined (shadow_sweep_kernel): 88 VGPRs, no scratch, 5 waves per SIMD, and per column the fmas of the plain
+// loop in its order, so the values are those it gave (profiles/shadow_q15_rate.txt).
 // fp_term of this kind (ShadowView::fp_term), with u = 2^-53, xs_i = fl(scale q_i) the copy that err / nrm were measured on
 // (scale is 0 or a normal number, shadow_build_q15_kernel, so a product with it rounds relatively):
 //   q_i is exact in f64 and every product enters through an fma, so the sum of n terms in any order, with the one rounding of
@@ -209,13 +213,25 @@ typedef int i4_t __attribute__((ext_vector_type(4)));
 struct ShadowQ15 {
     using elem = int16_t;
     using vec = i4_t;
-    static constexpr int CB = kShadowCB16, VEC = kShadowVec16, kUnroll = 1;
-    static constexpr bool kScaled = true;
+    static constexpr int CB = kShadowCB16, VEC = kShadowVec16;
+    static constexpr bool kScaled = true, kPipelined = true;
+    static constexpr int kMinWaves = 5;
     static_assert(VEC == 8, "one 16-byte load holds 8 rows");
     static __device__ __forceinline__ double row(vec x, int e) { // word w holds rows 2w (low half) and 2w + 1 (high half)
         return e % 2 ? double(x[e / 2] >> 16) : double(int(int16_t(x[e / 2])));
     }
 };
+
+// p, which every lane holds alike, as a value the compiler keeps in scalar registers (the address of a load is then this base
+// plus the lane's 32-bit offset, and no lane spends two registers per column on it)
+template <class T>
+using global_ptr = const __attribute__((address_space(1))) T*;
+template <class T>
+__device__ __forceinline__ global_ptr<T> uniform_ptr(const T* p) {
+    const uint64_t u = reinterpret_cast<uint64_t>(p);
+    const uint32_t l = __builtin_amdgcn_readfirstlane(uint32_t(u)), h = __builtin_amdgcn_readfirstlane(uint32_t(u >> 32));
+    return reinterpret_cast<global_ptr<T>>((uint64_t(h) << 32) | l);
+}
 
 // A workgroup of the exact part of the shadow launch: entry c of the lists xa, xb taken as one, row split xsplit of the FULL
 // design's shape; the split's partial goes to stage[xsplit * (na + nb) + c].  red: kThreads / 64 doubles of LDS.
@@ -238,7 +254,8 @@ __device__ __forceinline__ void exact_part(const DenseAcc<double>& X, const doub
 // one.  The other blocks_c * nsplit workgroups: out[c] = sum_i xs[i, c] * v[i] over all columns of the copy (Kind), f64
 // accumulation, per column rows ascending with one fma each; row splits (the shadow's own shape) and epilogue as sweep_kernel.
 template <class Kind, int XVEC>
-__global__ __launch_bounds__(kThreads) void shadow_sweep_kernel(const typename Kind::elem* __restrict__ Xs, int64_t ld,
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(Kind::kMinWaves))) void shadow_sweep_kernel(
+                                                                const typename Kind::elem* __restrict__ Xs, int64_t ld,
                                                                 const double* __restrict__ scale, const double* __restrict__ v,
                                                                 double* __restrict__ out, int64_t n, int64_t ncols,
                                                                 int64_t blocks_c, int64_t rows_per_split, int nsplit,
@@ -272,18 +289,88 @@ __global__ __launch_bounds__(kThreads) void shadow_sweep_kernel(const typename K
     for (int k = 0; k < CB; ++k) acc[k] = 0;
     // r0 is a multiple of 256 * VEC rows and ld of 16 bytes: every load below is 16-byte aligned and ends at or before row r1 <= n
     const int64_t body_end = r0 + ((r1 - r0) / VEC) * VEC;
+    if constexpr (Kind::kPipelined) {
+        // The trips in which every lane has a load (all but the last, when the split's rows are no multiple of kThreads * VEC)
+        // run as two half panels in rotation: while the columns of one half are multiplied, the loads of the other half (of
+        // the same rows, or of the next trip's) are in flight.  Per column and lane the fmas are those of the plain loop
+        // below, in its order.  The trip count is uniform and a trip's addresses are uniform bases, advanced per trip, plus
+        // the lane's offset of tid * VEC elements: the column pointers stay in scalar registers, which is what keeps the
+        // rotation within the registers of 5 waves per SIMD.  The last, partial trip follows on its own.
+        constexpr int H = CB / 2;
+        static_assert(CB % 2 == 0, "two half panels");
+        constexpr int64_t kStep = int64_t(kThreads) * VEC;
+        const uint32_t lo = uint32_t(tid) * VEC;
+        const int64_t full_trips = (body_end - r0) / kStep;
+        int64_t row = r0; // the first row of the trip
+        const auto xbase = [&](int k) { return uniform_ptr(cp[k] + row) + lo; };
+        const auto vbase = [&]() { return uniform_ptr(v + row) + lo; };
+        if (full_trips > 0) {
+            d2_t vc[VEC / 2], vn[VEC / 2];
+            typename Kind::vec ha[H], hb[H];
+            // the fmas of one half panel between two scheduling barriers: the compiler keeps the loads written before them
+            // before them and those written after them after them, which is the rotation
+            const auto half = [&](typename Kind::vec(&x)[H], int k0) {
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int k = 0; k < H; ++k) {
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) acc[k0 + k] = fma(Kind::row(x[k], e), vc[e / 2][e % 2], acc[k0 + k]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            const auto load_half = [&](typename Kind::vec(&x)[H], int k0) {
+#pragma unroll
+                for (int k = 0; k < H; ++k) x[k] = __builtin_nontemporal_load(reinterpret_cast<global_ptr<typename Kind::vec>>(xbase(k0 + k)));
+            };
+            const auto load_v = [&](d2_t(&vv)[VEC / 2]) {
+#pragma unroll
+                for (int e = 0; e < VEC / 2; ++e) vv[e] = *reinterpret_cast<global_ptr<d2_t>>(vbase() + 2 * e);
+            };
+            load_v(vc);
+            load_half(ha, 0);
+            load_half(hb, H);
+            for (int64_t t = 1; t < full_trips; ++t) { // (every trip but the last loads the next one's rows: no load under a condition)
+                row += kStep;
+                half(ha, 0);
+                load_half(ha, 0);
+                load_v(vn);
+                half(hb, H);
+                load_half(hb, H);
+#pragma unroll
+                for (int e = 0; e < VEC / 2; ++e) vc[e] = vn[e];
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            row += kStep;
+            half(ha, 0);
+            half(hb, H);
+        }
+        if (row + int64_t(lo) < body_end) { // (row: the first row after the full trips)
+            d2_t vv[VEC / 2];
+#pragma unroll
+            for (int e = 0; e < VEC / 2; ++e) vv[e] = *reinterpret_cast<global_ptr<d2_t>>(vbase() + 2 * e);
+            typename Kind::vec xx[CB];
+#pragma unroll
+            for (int k = 0; k < CB; ++k) xx[k] = __builtin_nontemporal_load(reinterpret_cast<global_ptr<typename Kind::vec>>(xbase(k)));
+#pragma unroll
+            for (int k = 0; k < CB; ++k) {
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) acc[k] = fma(Kind::row(xx[k], e), vv[e / 2][e % 2], acc[k]);
+            }
+        }
+    } else {
 #pragma unroll Kind::kUnroll
-    for (int64_t i = r0 + int64_t(tid) * VEC; i < body_end; i += int64_t(kThreads) * VEC) {
-        d2_t vv[VEC / 2];
+        for (int64_t i = r0 + int64_t(tid) * VEC; i < body_end; i += int64_t(kThreads) * VEC) {
+            d2_t vv[VEC / 2];
 #pragma unroll
-        for (int e = 0; e < VEC / 2; ++e) vv[e] = *reinterpret_cast<const d2_t*>(v + i + 2 * e);
-        typename Kind::vec xx[CB];
+            for (int e = 0; e < VEC / 2; ++e) vv[e] = *reinterpret_cast<const d2_t*>(v + i + 2 * e);
+            typename Kind::vec xx[CB];
 #pragma unroll
-        for (int k = 0; k < CB; ++k) xx[k] = __builtin_nontemporal_load(reinterpret_cast<const typename Kind::vec*>(cp[k] + i));
+            for (int k = 0; k < CB; ++k) xx[k] = __builtin_nontemporal_load(reinterpret_cast<const typename Kind::vec*>(cp[k] + i));
 #pragma unroll
-        for (int k = 0; k < CB; ++k) {
+            for (int k = 0; k < CB; ++k) {
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) acc[k] = fma(Kind::row(xx[k], e), vv[e / 2][e % 2], acc[k]);
+                for (int e = 0; e < VEC; ++e) acc[k] = fma(Kind::row(xx[k], e), vv[e / 2][e % 2], acc[k]);
+            }
         }
     }
     for (int64_t i = body_end + tid; i < r1; i += kThreads) {

@@ -146,7 +146,8 @@ inline T depth_score_hinted(const std::vector<T>& scores, int64_t D, T lo_hint, 
 // rho, measured on the headline (profiles/filter_depth.txt): a filtered sweep through the 16-bit copy takes 462 us + 0.128 us per
 // exact column (they go one per workgroup) and meets sweep_kernel's 1153 us at 5400 of 10000 columns, 0.79 of the bytes; with
 // every sweep below that filtered the path is no faster than with rho = 0.6, which keeps a fifth of the full sweep's time as
-// the gain of the last sweep it admits.  A design under 2^28 bytes is not held to the rule: its sweeps are launch-bound (under
+// the gain of the last sweep it admits.  With the pipelined 16-bit sweep the span is about 50 us shorter and that fifth is met
+// at 0.67 of the bytes, but rho = 0.6, 0.65, 0.7 and 1 gave the same wall clock (profiles/shadow_q15_rate.txt): 0.6 stays.  A design under 2^28 bytes is not held to the rule: its sweeps are launch-bound (under
 // 50 us either way) and the model has nothing to say about them.
 #ifndef AHIP_FILTER_BYTES_RHO // (a compile-time variant for measuring the crossing: build.sh, AHIP_VARIANT / AHIP_EXTRA_FLAGS)
 #define AHIP_FILTER_BYTES_RHO 0.6

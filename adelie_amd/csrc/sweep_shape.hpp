@@ -14,7 +14,9 @@ constexpr int kShadowCB = 8, kShadowVec = 4;
 // the 16-bit shadow sweep (shadow_sweep_kernel<ShadowQ15>): 16-byte loads of 8 rows.  At 8 columns a lane reads 64 B of v per 128 B of
 // design, at 16 columns 64 B per 256 B (the float32 kind's ratio).  Both widths were measured: 8 columns 421 us per launch on the
 // headline, 16 columns 477 us plus a reduce launch (one wave less per SIMD, two row splits: profiles/filter_sweep_q15.txt)
+// (with the plain body loop; the rotation of two half panels the kernel runs now needs CB even: 374 us, profiles/shadow_q15_rate.txt)
 constexpr int kShadowCB16 = 8, kShadowVec16 = 8;
+static_assert(kShadowCB16 % 2 == 0, "the q15 body loop rotates two half panels");
 // leading dimension of the 16-bit copy: a multiple of this many elements (128 B), pad rows hold 0
 constexpr int kShadowPad16 = 64;
 
