@@ -216,7 +216,7 @@ S = dict(
     t_sweep_ms=80, t_gram_ms=81, t_cd_ms=82, t_axpy_ms=83, n_sweep_launches=84, n_gram_launches=85,
     t_host_screen_ms=86, t_panel_step_ms=87, n_panel_step_launches=88, t_host_screen_wait_ms=89,
     t_fsweep_ms=90, n_fsweep_launches=91, fsweep_bytes=92,
-    n_screen_reads=93, n_screen_short=94, n_filter_open_cols=95,
+    n_screen_reads=93, n_screen_short=94, n_filter_open_cols=95, engine_panel=96,
 )
 
 class QpFullArgs(C.Structure):
@@ -262,13 +262,13 @@ class GroupPiece(C.Structure):
 HIP_SYMBOLS = [
     "abi_version", "last_error", "device_count", "set_config",
     "design_create_dense", "design_create_sparse", "design_create_csc", "design_create_standardized", "design_adopt_dense_dev", "design_create_snp_unphased",
-    "design_create_snp_calldata", "design_create_snp_bed", "design_alias", "design_drop_shadow", "design_shadow_stats", "design_shadow_info", "design_create_slice", "design_create_multi", "design_create_derived", "design_create_concat", "design_impute", "design_destroy", "design_owned_bytes",
+    "design_create_snp_calldata", "design_create_snp_bed", "design_alias", "design_drop_shadow", "design_shadow_stats", "design_shadow_info", "design_create_slice", "design_create_multi", "design_create_derived", "design_create_concat", "design_create_pieces", "design_impute", "design_destroy", "design_owned_bytes",
     "design_create_one_hot", "design_create_interaction", "design_factor_groups",
     "design_create_convex_relu", "design_create_convex_relu_csc",
     "design_create_snp_phased_ancestry", "design_create_snp_phased_calldata", "design_csc_download", "design_nnz",
     "design_glm_path_losses", "design_multi_path_losses", "design_batch_stats", "design_rows", "design_cols", "design_dtype",
     "design_device", "design_stream",
-    "design_cmul", "design_ctmul", "design_bmul", "design_btmul", "design_mul", "design_mul_batch", "design_cov",
+    "design_cmul", "design_ctmul", "design_bmul", "design_btmul", "design_bmul_cols", "design_btmul_cols", "design_mul", "design_mul_batch", "design_cov",
     "design_sq_mul", "design_sp_tmul",
     "design_create_cov_dense", "design_create_cov_csc", "design_create_cov_lazy", "design_cov_bmul", "design_cov_mul", "design_cov_to_dense", "gaussian_cov_solve",
     "glm_cox_create", "glm_cox_destroy", "glm_cox_eval",
@@ -360,6 +360,7 @@ class Backend:
         sig("design_create_multi", ci, [vp, i64, ci, p(vp)])
         sig("design_create_derived", ci, [vp, vp, i64, vp, i64, vp, vp, p(vp)])
         sig("design_create_concat", ci, [vp, i64, ci, p(vp)])
+        sig("design_create_pieces", ci, [vp, i64, p(vp)])
         sig("design_glm_path_losses", ci, [vp, ci, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp])
         sig("design_multi_path_losses", ci, [vp, ci, ci, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp])
         sig("design_destroy", ci, [vp])
@@ -373,6 +374,8 @@ class Backend:
         sig("design_ctmul", ci, [vp, i64, dbl, vp])
         sig("design_bmul", ci, [vp, i64, i64, vp, vp, vp])
         sig("design_btmul", ci, [vp, i64, i64, vp, vp])
+        sig("design_bmul_cols", ci, [vp, vp, i64, vp, vp, vp])
+        sig("design_btmul_cols", ci, [vp, vp, i64, vp, vp])
         sig("design_mul", ci, [vp, vp, vp, vp])
         sig("design_mul_batch", ci, [vp, vp, i64, vp])
         sig("design_cov", ci, [vp, i64, i64, vp, vp])

@@ -572,6 +572,22 @@ struct ReluCscArrs {
         rz_seg.borrow(o.rz_seg), rz_idx.borrow(o.rz_idx), rz_val.borrow(o.rz_val), rbits.borrow(o.rbits), rz_nnz = o.rz_nnz;
     }
 };
+// design made of pieces (adelie_hip_design_create_pieces; pieces_host.hpp): the arrays of up to kMaxPieces dense or 2-bit designs,
+// all borrowed -- the pieces own them and outlive this handle (the Python wrapper keeps them) -- with their leading dimensions,
+// kinds and first columns.  pc_impute[m] is null on a dense piece.
+struct PiecesArrs {
+    DevArr<void> pc_base[kMaxPieces], pc_impute[kMaxPieces];
+    int64_t pc_ld[kMaxPieces] = {};
+    int pc_kind[kMaxPieces] = {};
+    int32_t pc_first[kMaxPieces + 1] = {};
+    int pc_k = 0;
+    void borrow_from(const PiecesArrs& o) {
+        for (int m = 0; m < kMaxPieces; ++m)
+            pc_base[m].borrow(o.pc_base[m]), pc_impute[m].borrow(o.pc_impute[m]), pc_ld[m] = o.pc_ld[m], pc_kind[m] = o.pc_kind[m];
+        for (int m = 0; m <= kMaxPieces; ++m) pc_first[m] = o.pc_first[m];
+        pc_k = o.pc_k;
+    }
+};
 // float32 shadow of a dense f64 design for the filtered invariance sweep (kernels_filter.hip: ShadowView), made on the first
 // eligible solve.  Like the batcher it lives with the design the aliases were made from: nobody borrows it, the aliases read
 // their owner's.  sh_kind (shadow_kind_host.hpp): float32 values, or int16 with the per-column scales in sh_scale.
@@ -589,22 +605,24 @@ struct ShadowArrs {
 
 // ---- the opaque handles of include/adelie_hip.h ------------------------------------------------------------
 struct adelie_hip_design : ahip::DenseArrs, ahip::SnpArrs, ahip::CscArrs, ahip::StdArrs, ahip::FactorArrs, ahip::ReluArrs,
-                           ahip::ReluCscArrs, ahip::ShadowArrs {
+                           ahip::ReluCscArrs, ahip::PiecesArrs, ahip::ShadowArrs {
     // what adelie_hip_design_alias shares with `o`; o must outlive this handle
     void borrow_arrays(const adelie_hip_design& o) {
         DenseArrs::borrow_from(o), SnpArrs::borrow_from(o), CscArrs::borrow_from(o), StdArrs::borrow_from(o);
-        FactorArrs::borrow_from(o), ReluArrs::borrow_from(o), ReluCscArrs::borrow_from(o);
+        FactorArrs::borrow_from(o), ReluArrs::borrow_from(o), ReluCscArrs::borrow_from(o), PiecesArrs::borrow_from(o);
     }
     int dtype = ADELIE_HIP_F64;
     int device = 0;
     // storage kinds: dense, snp (2-bit), multi-response view of a dense or 2-bit design (adelie_hip_design_create_multi),
-    // sparse kept sparse (adelie_hip_design_create_csc: CSC + CSR copies of the entries, kernels_sparse.hip)
-    enum : int { kDense = 0, kSnp = 1, kMulti = 2, kCsc = 3 };
+    // sparse kept sparse (adelie_hip_design_create_csc: CSC + CSR copies of the entries, kernels_sparse.hip), column blocks of
+    // dense and 2-bit designs that stay as they are (adelie_hip_design_create_pieces: PiecesArrs; X, bits and the rest are null)
+    enum : int { kDense = 0, kSnp = 1, kMulti = 2, kCsc = 3, kPieces = 4 };
     int kind = kDense;
     bool is_dense() const { return kind == kDense; }
     bool is_snp() const { return kind == kSnp; }
     bool is_multi() const { return kind == kMulti; }
     bool is_csc() const { return kind == kCsc; }
+    bool is_pieces() const { return kind == kPieces; }
     // standardized view over a dense or 2-bit design (adelie_hip_design_create_standardized): the base kernels run on the raw
     // matrix, centring and scaling are applied around them; a view over compressed columns applies them inside its kernels
     bool is_std_view() const { return std_center != nullptr && kind != kCsc; }
@@ -637,6 +655,14 @@ struct adelie_hip_design : ahip::DenseArrs, ahip::SnpArrs, ahip::CscArrs, ahip::
 
     template <class T> ahip::DenseView<T> dense() const { return ahip::DenseView<T>{static_cast<const T*>(X), n, p, ld}; }
     ahip::SnpView snp() const { return ahip::SnpView{bits, n, p, ldb}; }
+    template <class T> ahip::PiecesView<T> pieces() const {
+        ahip::PiecesView<T> v{};
+        for (int m = 0; m < ahip::kMaxPieces; ++m)
+            v.base[m] = pc_base[m], v.ld[m] = pc_ld[m], v.impute[m] = static_cast<const T*>(pc_impute[m]);
+        for (int m = 0; m <= ahip::kMaxPieces; ++m) v.first[m] = pc_first[m];
+        v.k = pc_k, v.n = n, v.p = p;
+        return v;
+    }
     template <class T> ahip::CscView<T> csc() const {
         return ahip::CscView<T>{cptr, cidx, static_cast<const T*>(cval), rptr, rcol, static_cast<const T*>(rval), n, p, nnz,
                                 bptr, sp_nb, sp_rb, static_cast<const T*>(std_center), static_cast<const T*>(std_iscale),

@@ -149,22 +149,29 @@ struct DesignDeleter {
 using DesignGuard = std::unique_ptr<adelie_hip_design, DesignDeleter>;
 
 // ---- host-vector matrix operations ----------------------------------------------------------------------
+// (cols_host: the sweep over a column list, adelie_hip_design_bmul_cols; c0 is 0 then)
 template <class T>
-void op_sweep(adelie_hip_design* d, int64_t c0, int64_t ncols, const T* v, const T* w, T* out, bool square) {
+void op_sweep(adelie_hip_design* d, int64_t c0, int64_t ncols, const T* v, const T* w, T* out, bool square,
+              const int32_t* cols_host = nullptr) {
     set_device(d);
     hipStream_t s = d->stream;
     const int64_t n = d->n;
     T* dv = scratch<T>(d->s_n1, n);
     T* dw = scratch<T>(d->s_n2, n);
     T* dout = scratch<T>(d->s_p1, ncols);
-    const bool structured = raw_sweep_structured(*d, c0, ncols, nullptr, square, SweepHooks::from_env());
-    T* work = scratch<T>(d->s_work, size_t(raw_sweep_work_elems(*d, ncols, structured)));
+    int32_t* dcols = nullptr;
+    if (cols_host) {
+        dcols = scratch<int32_t>(d->s_idx1, ncols);
+        AHIP_CHECK(hipMemcpyAsync(dcols, cols_host, ncols * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    const bool structured = raw_sweep_structured(*d, c0, ncols, dcols, square, SweepHooks::from_env());
+    T* work = scratch<T>(d->s_work, size_t(raw_sweep_work_elems(*d, ncols, structured, c0)));
     AHIP_CHECK(hipMemcpyAsync(dv, v, n * sizeof(T), hipMemcpyHostToDevice, s));
     if (w) {
         AHIP_CHECK(hipMemcpyAsync(dw, w, n * sizeof(T), hipMemcpyHostToDevice, s));
         launch_vmul<T>(dv, dw, dv, n, s);
     }
-    raw_sweep<T>(*d, dv, dout, c0, ncols, nullptr, nullptr, nullptr, square, structured, work, s);
+    raw_sweep<T>(*d, dv, dout, c0, ncols, dcols, nullptr, nullptr, square, structured, work, s);
     AHIP_CHECK(hipMemcpyAsync(out, dout, ncols * sizeof(T), hipMemcpyDeviceToHost, s));
     AHIP_CHECK(hipStreamSynchronize(s));
 }
@@ -177,7 +184,9 @@ void op_mul_batch(adelie_hip_design* d, const T* V, int64_t L, T* out) {
     hipStream_t s = d->stream;
     const int64_t n = d->n, p = d->p;
     constexpr int64_t KB = 8;
-    if (d->is_csc()) { // sparse: one pass over the stored entries per vector (a convex-relu design: over those of Z, by the hook)
+    // sparse: one pass over the stored entries per vector (a convex-relu design: over those of Z, by the hook); a design made of
+    // pieces: one sweep per vector as well, every piece at its own rate (the K-wide kernels below take one dense or 2-bit view)
+    if (d->is_csc() || d->is_pieces()) {
         T* dv1 = scratch<T>(d->s_n1, size_t(n));
         T* dout1 = scratch<T>(d->s_p1, size_t(p));
         const bool structured = raw_sweep_structured(*d, 0, p, nullptr, false, SweepHooks::from_env());
@@ -206,6 +215,7 @@ void op_mul_batch(adelie_hip_design* d, const T* V, int64_t L, T* out) {
             AHIP_CHECK(hipStreamSynchronize(s));
             continue;
         }
+        no_pieces(*d, "the K-wide sweep"); // (unreachable: taken above)
         if (d->is_dense()) {
             const DenseView<T> X = d->dense<T>();
             launch_multi_sweep<T>(MultiView<T>{X.X, n, p, X.ld, nullptr, int32_t(K), 0}, dv, dout, work, s);
@@ -221,8 +231,9 @@ void op_mul_batch(adelie_hip_design* d, const T* V, int64_t L, T* out) {
     }
 }
 
+// (cols_host: the q columns of adelie_hip_design_btmul_cols instead of j .. j + q - 1)
 template <class T>
-void op_axpy(adelie_hip_design* d, int64_t j, int64_t q, const T* coef, T* out) {
+void op_axpy(adelie_hip_design* d, int64_t j, int64_t q, const T* coef, T* out, const int32_t* cols_host = nullptr) {
     set_device(d);
     hipStream_t s = d->stream;
     const int64_t n = d->n;
@@ -230,7 +241,7 @@ void op_axpy(adelie_hip_design* d, int64_t j, int64_t q, const T* coef, T* out) 
     T* dcoef = scratch<T>(d->s_p1, q);
     int32_t* dcols = scratch<int32_t>(d->s_idx1, q);
     std::vector<int32_t> cols(q);
-    for (int64_t k = 0; k < q; ++k) cols[k] = int32_t(j + k);
+    for (int64_t k = 0; k < q; ++k) cols[k] = cols_host ? cols_host[k] : int32_t(j + k);
     AHIP_CHECK(hipMemcpyAsync(dout, out, n * sizeof(T), hipMemcpyHostToDevice, s));
     AHIP_CHECK(hipMemcpyAsync(dcoef, coef, q * sizeof(T), hipMemcpyHostToDevice, s));
     AHIP_CHECK(hipMemcpyAsync(dcols, cols.data(), q * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -576,6 +587,7 @@ namespace {
 template <class T>
 void derive_t(adelie_hip_design* src, adelie_hip_design* d, const int64_t* rows, int64_t nrows, const int64_t* cols,
               int64_t ncols, const double* centers, const double* scales) {
+    no_pieces(*src, "subset / standardize"); // (unreachable: adelie_hip_design_create_derived refuses it before allocating)
     const int64_t nout = d->n, pout = d->p;
     hipStream_t s = d->stream;
     int64_t *drows = nullptr, *dcols = nullptr;
@@ -621,6 +633,7 @@ void derive_t(adelie_hip_design* src, adelie_hip_design* d, const int64_t* rows,
 // decoded) into its slice of a new dense array
 template <class T>
 void concat_t(adelie_hip_design* const* srcs, int64_t k, int axis, adelie_hip_design* d) {
+    for (int64_t m = 0; m < k; ++m) no_pieces(*srcs[m], "a further concatenate"); // (unreachable: refused at the entry point)
     hipStream_t s = d->stream;
     bool all_snp = axis == 1;
     for (int64_t m = 0; m < k && all_snp; ++m) all_snp = srcs[m]->is_snp() && !srcs[m]->std_center && srcs[m]->ldb == srcs[0]->ldb;
@@ -914,6 +927,7 @@ int adelie_hip_design_create_cov_lazy(adelie_hip_design* X, adelie_hip_design** 
     if (!X || !out) throw make_core_error("null argument.");
     if (X->cov) throw make_core_error("mat must be a naive (n, p) matrix, not a covariance matrix.");
     no_view(X);
+    no_pieces(*X, "lazy_cov");
     if (!X->is_dense() && !X->is_snp()) throw make_core_error("lazy_cov takes a dense or SNP design.");
     if (X->p > (int64_t(1) << 31) - 1) throw make_core_error("too many columns.");
     set_device(X);
@@ -979,6 +993,7 @@ int adelie_hip_design_create_standardized(adelie_hip_design* src, const double* 
     ABI_TRY
     if (!src || !centers || !scales || !out) throw make_core_error("null argument.");
     if (src->is_multi() || src->cov || src->constraint) no_view(src);
+    no_pieces(*src, "standardize (standardize the dense piece with lazy=False before concatenating instead)");
     if (src->std_center) throw make_core_error("the design is a standardized view already.");
     for (int64_t j = 0; j < src->p; ++j)
         if (!(scales[j] != 0.0)) throw make_core_error("scales must be non-zero.");
@@ -1060,6 +1075,7 @@ int adelie_hip_design_adopt_dense_dev(const void* dev_ptr, int64_t n, int64_t p,
 int adelie_hip_design_batch_stats(adelie_hip_design* d, double* out) {
     ABI_TRY
     if (!d || !out) throw make_core_error("null argument.");
+    // (a design made of pieces never joins the batching: its batcher stays null and the counts are zero)
     adelie_hip_design* owner = d->batch_owner ? d->batch_owner : d;
     adelie_hip_internal_batch_stats(owner->batcher, out);
     ABI_CATCH
@@ -1214,6 +1230,7 @@ int adelie_hip_design_create_slice(adelie_hip_design* base, int64_t r0, int64_t 
     ABI_TRY
     if (!base || !out) throw make_core_error("null argument.");
     if (base->constraint) no_view(base);
+    no_pieces(*base, "subset");
     if ((!base->is_dense() && !base->is_snp()) || base->cov || base->std_center)
         throw make_core_error("only dense and 2-bit SNP designs are sliced in place.");
     if (r0 < 0 || nr < 1 || c0 < 0 || nc < 1 || r0 + nr > base->n || c0 + nc > base->p)
@@ -1240,6 +1257,7 @@ int adelie_hip_design_create_multi(adelie_hip_design* base, int64_t K, int inter
     ABI_TRY
     if (!base || !out) throw make_core_error("null argument.");
     if (base->constraint) no_view(base);
+    no_pieces(*base, "kronecker_eye / a multi-response family");
     if ((!base->is_dense() && !base->is_snp()) || base->cov || base->std_center)
         throw make_core_error("the multi-response view needs a dense or 2-bit SNP base design.");
     if (K < 1) throw make_core_error("K must be >= 1.");
@@ -1272,6 +1290,7 @@ int adelie_hip_design_create_derived(adelie_hip_design* src, const int64_t* rows
     ABI_TRY
     if (!src || !out) throw make_core_error("null argument.");
     no_view(src);
+    no_pieces(*src, (centers || scales) ? "standardize (standardize the dense piece with lazy=False before concatenating instead)" : "subset");
     const int64_t nout = rows ? n_rows : src->n, pout = cols ? n_cols : src->p;
     if (rows)
         for (int64_t i = 0; i < n_rows; ++i)
@@ -1296,6 +1315,7 @@ int adelie_hip_design_create_concat(adelie_hip_design* const* srcs, int64_t k, i
     for (int64_t m = 0; m < k; ++m) {
         if (!srcs[m]) throw make_core_error("null argument.");
         no_view(srcs[m]);
+        no_pieces(*srcs[m], "a further concatenate");
         if (srcs[m]->dtype != srcs[0]->dtype || srcs[m]->device != srcs[0]->device)
             throw make_core_error("concatenate(): the matrices must share dtype and device.");
         if (axis == 1) {
@@ -1310,6 +1330,40 @@ int adelie_hip_design_create_concat(adelie_hip_design* const* srcs, int64_t k, i
     }
     DesignGuard g(new_design(n, p, srcs[0]->dtype, srcs[0]->device));
     DTYPE_DISPATCH(srcs[0], concat_t<T>(srcs, k, axis, g.get()))
+    *out = g.release();
+    ABI_CATCH
+}
+
+int adelie_hip_design_create_pieces(adelie_hip_design* const* srcs, int64_t k, adelie_hip_design** out) {
+    ABI_TRY
+    if (!srcs || !out) throw make_core_error("null argument.");
+    std::vector<PieceInfo> info;
+    for (int64_t m = 0; m < k; ++m) {
+        const adelie_hip_design* s = srcs[m];
+        if (!s) throw make_core_error("null argument.");
+        info.push_back(PieceInfo{s->kind, s->std_center != nullptr, s->cov != 0, s->constraint != 0, s->dtype, s->device, s->n, s->p});
+    }
+    const std::string refusal = pieces_validate(info.data(), k);
+    if (!refusal.empty()) throw make_core_error(refusal);
+    int64_t p_of[kMaxPieces], p = 0;
+    for (int64_t m = 0; m < k; ++m) {
+        p += (p_of[m] = srcs[m]->p);
+        if (srcs[m]->is_snp() ? (!srcs[m]->bits || !srcs[m]->impute) : !srcs[m]->X) throw make_core_error("a piece holds no array.");
+    }
+    set_device(srcs[0]);
+    DesignGuard g(new_design(srcs[0]->n, p, srcs[0]->dtype, srcs[0]->device)); // own stream, own scratch; no array of its own
+    adelie_hip_design* d = g.get();
+    d->kind = adelie_hip_design::kPieces;
+    d->pc_k = int(k);
+    pieces_first_cols(p_of, int(k), d->pc_first);
+    for (int64_t m = 0; m < k; ++m) {
+        const adelie_hip_design* s = srcs[m];
+        // the piece's own creation (or whatever wrote it last) ran on its stream: order this design's work after it
+        AHIP_CHECK(hipStreamSynchronize(s->stream));
+        d->pc_kind[m] = s->is_snp() ? kPieceSnp : kPieceDense;
+        if (s->is_snp()) d->pc_base[m].borrow(static_cast<void*>(s->bits.get())), d->pc_ld[m] = s->ldb, d->pc_impute[m].borrow(s->impute);
+        else d->pc_base[m].borrow(s->X), d->pc_ld[m] = s->ld;
+    }
     *out = g.release();
     ABI_CATCH
 }
@@ -1373,6 +1427,7 @@ int adelie_hip_design_impute(adelie_hip_design* d, double* out) {
     ABI_TRY
     no_view(d);
     if (!d || !out) throw make_core_error("null argument.");
+    no_pieces(*d, "impute (ask the 2-bit pieces)");
     if (!d->is_snp()) throw make_core_error("impute is only defined for SNP designs.");
     set_device(d);
     if (d->dtype == ADELIE_HIP_F64) {
@@ -1432,6 +1487,36 @@ int adelie_hip_design_btmul(adelie_hip_design* d, int64_t j, int64_t q, const vo
     no_view(d);
     check_col(d, j, q, "btmul");
     DTYPE_DISPATCH(d, op_axpy<T>(d, j, q, (const T*)v, (T*)out))
+    ABI_CATCH
+}
+// the column list of bmul_cols / btmul_cols, checked and narrowed to the kernels' int32
+static std::vector<int32_t> checked_cols(const adelie_hip_design* d, const int64_t* cols, int64_t q, const char* what) {
+    if (!d || !cols || q < 1) throw make_core_error(std::string(what) + "() is given inconsistent inputs!");
+    std::vector<int32_t> c(static_cast<size_t>(q));
+    for (int64_t k = 0; k < q; ++k) {
+        if (cols[k] < 0 || cols[k] >= d->p) throw make_core_error(std::string(what) + "(): column index out of range.");
+        c[size_t(k)] = int32_t(cols[k]);
+    }
+    return c;
+}
+int adelie_hip_design_bmul_cols(adelie_hip_design* d, const int64_t* cols, int64_t q, const void* v, const void* weights, void* out) {
+    ABI_TRY
+    no_view(d);
+    const std::vector<int32_t> c = checked_cols(d, cols, q, "bmul_cols");
+    DTYPE_DISPATCH(d, op_sweep<T>(d, 0, q, (const T*)v, (const T*)weights, (T*)out, false, c.data()))
+    ABI_CATCH
+}
+int adelie_hip_design_btmul_cols(adelie_hip_design* d, const int64_t* cols, int64_t q, const void* v, void* out) {
+    ABI_TRY
+    no_view(d);
+    const std::vector<int32_t> c = checked_cols(d, cols, q, "btmul_cols");
+    if (d->is_csc()) { // (the compressed-column update scatters the coefficients by column)
+        std::vector<int32_t> srt(c);
+        std::sort(srt.begin(), srt.end());
+        if (std::adjacent_find(srt.begin(), srt.end()) != srt.end())
+            throw make_core_error("btmul_cols(): the columns must be distinct on a design kept sparse.");
+    }
+    DTYPE_DISPATCH(d, op_axpy<T>(d, 0, q, (const T*)v, (T*)out, c.data()))
     ABI_CATCH
 }
 int adelie_hip_design_mul(adelie_hip_design* d, const void* v, const void* weights, void* out) {

@@ -4,7 +4,8 @@
 // "Raw" is what the stored matrix gives.  A standardized view of a dense / 2-bit design composes its epilogues around these
 // calls (solver_screen.hpp: sweep / gram / axpy_cols); one over compressed columns is handled inside the csc kernels, whose
 // CscView carries the centers and scales.  The multi-response view has K-wide kernels of its own (the solver calls them) and
-// is refused here.  Every work buffer is the caller's: the solver and the matrix operations keep different scratch, and a
+// is refused here.  A design made of pieces (kPieces) is the fourth branch of each: a sweep over a column range goes piece by
+// piece through the dense / 2-bit launches, everything else through the same kernels over PiecesAcc.  Every work buffer is the caller's: the solver and the matrix operations keep different scratch, and a
 // caller may hold live data in one buffer while an operation works in another, so nothing here reserves memory.
 #pragma once
 #include "common.hpp"
@@ -13,6 +14,14 @@ namespace ahip {
 
 inline core_error multi_view_error() {
     return make_core_error("this entry point is not offered on a multi-response view; use the base design.");
+}
+// A design made of pieces has neither a dense nor a 2-bit view of its own.  Every two-way branch `dense ? ... : ...snp...` of
+// the solver and of the design entry points calls this in front of it, so that no launch is ever handed a null view; the
+// solver keeps such a design off the panel engines (solver_path.hpp), which is what makes those branches unreachable.
+inline void no_pieces(const adelie_hip_design& d, const char* where) {
+    if (d.is_pieces())
+        throw make_core_error(std::string(where) + " is not offered on a design made of pieces (concatenate(..., resident=\"pieces\")); "
+                              "resident=\"auto\" gives one design, on which everything works.");
 }
 template <class T>
 const T* snp_impute(const adelie_hip_design& d) { return static_cast<const T*>(d.impute); }
@@ -29,7 +38,11 @@ inline bool raw_sweep_structured(const adelie_hip_design& d, int64_t c0, int64_t
     if (!d.is_dense() || d.is_std_view()) return false;
     return (d.factor() && factor_sweep_on(hooks.factor)) || (d.relu() && relu_sweep_on(hooks.relu));
 }
-inline int64_t raw_sweep_work_elems(const adelie_hip_design& d, int64_t ncols, bool structured) {
+// (c0: the first column of a sweep over a column range; only a design made of pieces sizes its work by where the range lies)
+inline int64_t raw_sweep_work_elems(const adelie_hip_design& d, int64_t ncols, bool structured, int64_t c0 = 0) {
+    if (d.is_pieces())
+        return d.dtype == ADELIE_HIP_F64 ? sweep_work_elems_pieces<double>(d.pieces<double>(), c0, ncols)
+                                         : sweep_work_elems_pieces<float>(d.pieces<float>(), c0, ncols);
     if (structured && d.relu_csc()) return relu_sparse_sweep_work_elems(d.n, d.r_d, d.r_m);
     if (structured && d.relu()) return relu_sweep_work_elems(d.n, d.r_d, d.r_m);
     if (structured) return factor_sweep_work_elems(d.n, d.p, d.f_nchunk);
@@ -44,6 +57,7 @@ void raw_sweep(const adelie_hip_design& d, const T* v, T* out, int64_t c0, int64
     else if (d.is_dense()) launch_sweep<T>(d.dense<T>(), v, out, c0, ncols, cols, sub_scale, sub_vec, square, work, s);
     else if (d.is_snp()) launch_sweep_snp<T>(d.snp(), snp_impute<T>(d), v, out, c0, ncols, cols, sub_scale, sub_vec, square, work, s);
     else if (d.is_csc()) launch_sweep_csc<T>(d.csc<T>(), v, out, c0, ncols, cols, sub_scale, sub_vec, square, work, s);
+    else if (d.is_pieces()) launch_sweep_pieces<T>(d.pieces<T>(), v, out, c0, ncols, cols, sub_scale, sub_vec, square, work, s);
     else throw multi_view_error();
 }
 
@@ -57,6 +71,7 @@ void raw_gram(const adelie_hip_design& d, const T* w, const int32_t* mcols, int3
     if (d.is_dense()) launch_gram<T>(d.dense<T>(), w, mcols, M, m_pos0, ncols, N, n_pos0, xm, center, C, ldc, work, s);
     else if (d.is_snp()) launch_gram_snp<T>(d.snp(), snp_impute<T>(d), w, mcols, M, m_pos0, ncols, N, n_pos0, xm, center, C, ldc, work, s);
     else if (d.is_csc()) launch_gram_csc<T>(d.csc<T>(), w, mcols, M, m_pos0, ncols, N, n_pos0, xm, center, C, ldc, work, s);
+    else if (d.is_pieces()) launch_gram_pieces<T>(d.pieces<T>(), w, mcols, M, m_pos0, ncols, N, n_pos0, xm, center, C, ldc, work, s);
     else throw multi_view_error();
 }
 
@@ -69,6 +84,7 @@ void raw_axpy_cols(const adelie_hip_design& d, const int32_t* cols, const T* coe
     if (d.is_dense()) launch_axpy_cols<T>(d.dense<T>(), cols, coef, count_dev, count, sign, out, s);
     else if (d.is_snp()) launch_axpy_cols_snp<T>(d.snp(), snp_impute<T>(d), cols, coef, count_dev, count, sign, out, s);
     else if (d.is_csc()) launch_axpy_cols_csc<T>(d.csc<T>(), cols, coef, count_dev, count, sign, out, delta_zeroed, s);
+    else if (d.is_pieces()) launch_axpy_cols_pieces<T>(d.pieces<T>(), cols, coef, count_dev, count, sign, out, s);
     else throw multi_view_error();
 }
 
@@ -80,6 +96,7 @@ void raw_sp_tmul(const adelie_hip_design& d, int64_t L, const int64_t* indptr, c
     if (d.is_dense()) launch_sp_tmul<T>(d.dense<T>(), L, indptr, indices, values, out, s);
     else if (d.is_snp()) launch_sp_tmul_snp<T>(d.snp(), snp_impute<T>(d), L, indptr, indices, values, out, s);
     else if (d.is_csc()) launch_sp_tmul_csc<T>(d.csc<T>(), L, indptr, indices, values, out, work, s);
+    else if (d.is_pieces()) launch_sp_tmul_pieces<T>(d.pieces<T>(), L, indptr, indices, values, out, s);
     else throw multi_view_error();
 }
 

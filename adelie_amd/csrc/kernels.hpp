@@ -7,6 +7,7 @@
 #include "relu_shape.hpp"
 #include "relu_sparse_shape.hpp"
 #include "shadow_kind_host.hpp"
+#include "pieces_host.hpp"
 
 namespace ahip {
 
@@ -21,6 +22,30 @@ struct DenseView {
 struct SnpView {
     const uint8_t* bits;
     int64_t n, p, ldb; // ldb = bytes per column (padded)
+};
+
+// Design made of k <= kMaxPieces column blocks that stay as they are (pieces_host.hpp): piece m holds columns
+// [first[m], first[m + 1]) and is a dense design (impute[m] null; X = base[m], leading dimension ld[m]) or a 2-bit design (bits =
+// base[m], ldb = ld[m], impute[m] its (p_m,) values).  Unused slots: base / impute null, first INT32_MAX.
+template <class T>
+struct PiecesView {
+    const void* base[kMaxPieces];
+    int64_t ld[kMaxPieces];
+    const T* impute[kMaxPieces];
+    int32_t first[kMaxPieces + 1];
+    int k;
+    int64_t n, p;
+    bool is_snp(int m) const { return impute[m] != nullptr; }
+    int64_t cols_of(int m) const { return int64_t(first[m + 1]) - int64_t(first[m]); }
+    DenseView<T> dense_piece(int m) const { return DenseView<T>{static_cast<const T*>(base[m]), n, cols_of(m), ld[m]}; }
+    SnpView snp_piece(int m) const { return SnpView{static_cast<const uint8_t*>(base[m]), n, cols_of(m), ld[m]}; }
+    // whether the kernels over PiecesAcc may read 16 bytes at a time (pieces_host.hpp: pieces_vec_ok)
+    bool vec_ok() const {
+        int kind[kMaxPieces];
+        uintptr_t at[kMaxPieces];
+        for (int m = 0; m < k; ++m) kind[m] = is_snp(m) ? kPieceSnp : kPieceDense, at[m] = reinterpret_cast<uintptr_t>(base[m]);
+        return pieces_vec_ok(kind, at, ld, k, int(16 / sizeof(T)));
+    }
 };
 
 // Sparse design kept sparse (kernels_sparse.hip): the same matrix column-compressed (cptr / cidx / cval, row indices ascending
@@ -65,6 +90,24 @@ template <class T>
 void launch_sweep_snp(const SnpView& X, const T* impute, const T* v, T* out, int64_t c0, int64_t ncols,
                       const int32_t* cols, const T* sub_scale, const T* sub_vec, bool square, T* work, hipStream_t s);
 int64_t sweep_work_elems(int64_t n, int64_t ncols);
+// The same operations on a design made of pieces (kernels_sweep.hip, kernels_gram.hip).  A sweep over a column range
+// (cols == nullptr) is issued piece by piece with launch_sweep / launch_sweep_snp on the piece's part of the range: every block
+// runs at the rate its storage has and a column's value is what its piece alone gives.  A sweep over a column list, Gram, axpy
+// and sp_tmul run the kernels above over PiecesAcc (accessors.hpp).  `work` holds sweep_work_elems_pieces(X, c0, ncols) elements.
+template <class T>
+void launch_sweep_pieces(const PiecesView<T>& X, const T* v, T* out, int64_t c0, int64_t ncols, const int32_t* cols,
+                         const T* sub_scale, const T* sub_vec, bool square, T* work, hipStream_t s);
+template <class T> int64_t sweep_work_elems_pieces(const PiecesView<T>& X, int64_t c0, int64_t ncols);
+template <class T>
+void launch_axpy_cols_pieces(const PiecesView<T>& X, const int32_t* cols, const T* coef, const int32_t* count_dev, int32_t count,
+                             T sign, T* out, hipStream_t s);
+template <class T>
+void launch_sp_tmul_pieces(const PiecesView<T>& X, int64_t L, const int64_t* indptr, const int64_t* indices, const T* values,
+                           T* out, hipStream_t s);
+// launch_gram below on a design made of pieces; `work` holds gram_work_elems(n, M, N) elements
+template <class T>
+void launch_gram_pieces(const PiecesView<T>& X, const T* w, const int32_t* mcols, int32_t M, int32_t m_pos0, const int32_t* ncols,
+                        int32_t N, int32_t n_pos0, const T* xm_by_col, bool center, T* C, int64_t ldc, T* work, hipStream_t s);
 
 // ---- filtered invariance sweep (kernels_filter.hip): a float32 shadow of a dense f64 design ----------------------------------
 // Xs: the columns rounded to float32 (column-major, ld a multiple of 4); err[j] = ||x_j - xs_j||_2, nrm[j] = ||xs_j||_2 (both

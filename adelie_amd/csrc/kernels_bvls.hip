@@ -161,6 +161,9 @@ extern "C" {
 
 int adelie_hip_bvls_solve(adelie_hip_design* X, const adelie_hip_bvls_args* a, adelie_hip_bvls_result** out) {
     return cd_screen_solve<BvlsSolver>(X, a, out, [&] {
+        if (X->is_pieces())
+            throw make_core_error("bvls is not offered on a design made of pieces (concatenate(..., resident=\"pieces\")); "
+                                  "resident=\"auto\" gives one design, on which everything works.");
         if (!X->is_dense() || X->cov || X->constraint || X->std_center)
             throw make_core_error("bvls: X must be a plain dense design on this route.");
         const int64_t n = X->n, p = X->p;

@@ -785,7 +785,18 @@ void launch_gram_snp(const SnpView& X, const T* impute, const T* w, const int32_
     gram_launch<T, SnpAcc<T>>(acc, true, w, mcols, M, m_pos0, ncols, N, n_pos0, X.n, xm_by_col, center, C, ldc, work, s);
 }
 
+// a design made of pieces: the general Gram over PiecesAcc (lanes that hold columns of a dense and of a 2-bit piece diverge in
+// load_rows; accepted: the blocks that straddle a piece boundary are few)
+template <class T>
+void launch_gram_pieces(const PiecesView<T>& X, const T* w, const int32_t* mcols, int32_t M, int32_t m_pos0, const int32_t* ncols,
+                        int32_t N, int32_t n_pos0, const T* xm_by_col, bool center, T* C, int64_t ldc, T* work, hipStream_t s) {
+    gram_launch<T, PiecesAcc<T>>(pieces_acc<T>(X), X.vec_ok(), w, mcols, M, m_pos0, ncols, N, n_pos0, X.n, xm_by_col, center, C, ldc,
+                                 work, s);
+}
+
 #define INST(T)                                                                                                        \
+    template void launch_gram_pieces<T>(const PiecesView<T>&, const T*, const int32_t*, int32_t, int32_t, const int32_t*, \
+                                        int32_t, int32_t, const T*, bool, T*, int64_t, T*, hipStream_t);               \
     template void launch_gram<T>(const DenseView<T>&, const T*, const int32_t*, int32_t, int32_t, const int32_t*,      \
                                  int32_t, int32_t, const T*, bool, T*, int64_t, T*, hipStream_t);                      \
     template void launch_gram_snp<T>(const SnpView&, const T*, const T*, const int32_t*, int32_t, int32_t,             \

@@ -471,7 +471,58 @@ void launch_sp_tmul_snp(const SnpView& X, const T* impute, int64_t L, const int6
     sp_tmul_any(SnpAcc<T>{X.bits, X.ldb, impute}, X.n, true, L, indptr, indices, values, out, s);
 }
 
+// ---- a design made of pieces (kernels.hpp: PiecesView) -----------------------------------------------------------------------
+template <class T>
+int64_t sweep_work_elems_pieces(const PiecesView<T>& X, int64_t c0, int64_t ncols) {
+    int64_t need = sweep_work_elems(X.n, ncols); // (a sweep over a column list)
+    PieceRange rg[kMaxPieces];
+    const int nr = pieces_split(X.first, X.k, c0, ncols, rg);
+    for (int r = 0; r < nr; ++r) need = std::max(need, sweep_work_elems(X.n, rg[r].count));
+    return need;
+}
+template <class T>
+void launch_sweep_pieces(const PiecesView<T>& X, const T* v, T* out, int64_t c0, int64_t ncols, const int32_t* cols,
+                         const T* sub_scale, const T* sub_vec, bool square, T* work, hipStream_t s) {
+    if (ncols <= 0) return;
+    if (!cols) { // a column range: piece by piece with the pieces' own launches (in order on s: they share `work`)
+        PieceRange rg[kMaxPieces];
+        const int nr = pieces_split(X.first, X.k, c0, ncols, rg);
+        for (int r = 0; r < nr; ++r) {
+            const int m = rg[r].piece;
+            const T* sv = sub_vec ? sub_vec + X.first[m] : nullptr; // (the piece's launch indexes it by its own columns)
+            if (X.is_snp(m))
+                launch_sweep_snp<T>(X.snp_piece(m), X.impute[m], v, out + rg[r].out0, rg[r].local0, rg[r].count, nullptr, sub_scale, sv,
+                                    square, work, s);
+            else
+                launch_sweep<T>(X.dense_piece(m), v, out + rg[r].out0, rg[r].local0, rg[r].count, nullptr, sub_scale, sv, square, work, s);
+        }
+        return;
+    }
+    const PiecesAcc<T> acc = pieces_acc<T>(X);
+    if (X.vec_ok() && (reinterpret_cast<uintptr_t>(v) % 16) == 0)
+        sweep_dispatch<T, PiecesAcc<T>, VecOf<T>::N>(acc, v, out, X.n, c0, ncols, cols, sub_scale, sub_vec, square, work, s);
+    else
+        sweep_dispatch<T, PiecesAcc<T>, 1>(acc, v, out, X.n, c0, ncols, cols, sub_scale, sub_vec, square, work, s);
+}
+template <class T>
+void launch_axpy_cols_pieces(const PiecesView<T>& X, const int32_t* cols, const T* coef, const int32_t* count_dev, int32_t count,
+                             T sign, T* out, hipStream_t s) {
+    axpy_cols_any<true>(pieces_acc<T>(X), X.n, X.vec_ok(), cols, coef, count_dev, count, sign, out, s);
+}
+template <class T>
+void launch_sp_tmul_pieces(const PiecesView<T>& X, int64_t L, const int64_t* indptr, const int64_t* indices, const T* values,
+                           T* out, hipStream_t s) {
+    sp_tmul_any(pieces_acc<T>(X), X.n, X.vec_ok(), L, indptr, indices, values, out, s);
+}
+
 #define INST(T)                                                                                                        \
+    template int64_t sweep_work_elems_pieces<T>(const PiecesView<T>&, int64_t, int64_t);                               \
+    template void launch_sweep_pieces<T>(const PiecesView<T>&, const T*, T*, int64_t, int64_t, const int32_t*, const T*, \
+                                         const T*, bool, T*, hipStream_t);                                             \
+    template void launch_axpy_cols_pieces<T>(const PiecesView<T>&, const int32_t*, const T*, const int32_t*, int32_t, T, T*, \
+                                             hipStream_t);                                                             \
+    template void launch_sp_tmul_pieces<T>(const PiecesView<T>&, int64_t, const int64_t*, const int64_t*, const T*, T*, \
+                                           hipStream_t);                                                               \
     template void launch_vmul<T>(const T*, const T*, T*, int64_t, hipStream_t);                                        \
     template void launch_fill<T>(T*, T, int64_t, hipStream_t);                                                         \
     template void launch_sweep<T>(const DenseView<T>&, const T*, T*, int64_t, int64_t, const int32_t*, const T*,       \

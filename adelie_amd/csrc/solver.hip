@@ -574,6 +574,7 @@ struct Result : ResultBase {
             case ADELIE_HIP_S_N_SCREEN_READS: return double(s.n_screen_reads);
             case ADELIE_HIP_S_N_SCREEN_SHORT: return double(s.n_screen_short);
             case ADELIE_HIP_S_N_FILTER_OPEN_COLS: return double(s.n_filter_open_cols);
+            case ADELIE_HIP_S_ENGINE_PANEL: return s.engine_panel ? 1.0 : 0.0;
             default:
                 if (which >= 900 && which < 908) return double(s.cd_dbg[which - 900]);
                 if (which >= 910 && which < 918) return 1e3 * s.t_host[which - 910];
@@ -805,6 +806,7 @@ int adelie_hip_bench_sweep(adelie_hip_design* d, int64_t reps, double* ms_per_la
             DevBuf<T> v, out, xm, work, sc;
             v.reserve(d->n); out.reserve(d->p); xm.reserve(d->p); sc.reserve(1);
             // a one-hot / interaction or convex-relu design: the route ADELIE_HIP_FACTOR_SWEEP / ADELIE_HIP_RELU_SWEEP select (read here)
+            // (a design made of pieces: raw_sweep issues the full range piece by piece, as a solve's per-lambda sweep does)
             const bool structured = raw_sweep_structured(*d, 0, d->p, nullptr, false, SweepHooks::from_env());
             work.reserve(size_t(raw_sweep_work_elems(*d, d->p, structured)));
             launch_fill<T>(v.p, T(1) / T(d->n), d->n, s);
@@ -924,6 +926,7 @@ int adelie_hip_block_build_test(adelie_hip_design* d, int mode, int64_t row_off,
     try {
         if (!d || !w || !cols || !table || !out0 || !info || n_cols < 1 || count < 1) throw make_core_error("bad arguments.");
         if (d->cov || d->constraint || d->std_center || d->is_multi()) throw make_core_error("a plain dense, 2-bit or compressed-column design is required.");
+        no_pieces(*d, "adelie_hip_block_build_test"); // (the block builds below take a dense, a 2-bit or a compressed view)
         if (!d->is_dense() && !d->is_snp() && !d->is_csc()) throw make_core_error("a plain dense, 2-bit or compressed-column design is required.");
         if (center && !xm) throw make_core_error("center needs xm.");
         if (row_off < 0 || row_off >= d->n || (row_off > 0 && !d->is_dense())) throw make_core_error("row_off: a dense design and 0 <= row_off < n are required.");

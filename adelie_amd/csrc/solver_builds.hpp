@@ -454,6 +454,7 @@
                 T* work = (side ? d_work_gram2 : d_work_gram)
                               .reserve(size_t(std::max<int64_t>(gram_batch_work_elems(n, gb.count), syrk_work_elems(n, 128))));
                 t_gram.begin(gs);
+                no_pieces(*D, "a batch of cross blocks"); // (unreachable: engine_panel is off)
                 if (dense()) launch_gram_batch<T>(D->dense<T>(), cur_w, cols_base, gb, cur_xm, intercept, xpool, SL, work, gs);
                 else launch_gram_batch_snp<T>(D->snp(), static_cast<const T*>(D->impute), cur_w, cols_base, gb, cur_xm, intercept,
                                               xpool, SL, work, gs);
@@ -694,6 +695,10 @@
     // standardized view over a dense or 2-bit design: its epilogues are composed around the raw operations of design_ops.hpp
     // (solver_screen.hpp: sweep / gram / axpy_cols); Gram engines only
     bool std_generic() const { return D->is_std_view(); }
+    // design made of pieces (adelie_hip_design_create_pieces): dense and 2-bit column blocks that stay as they are.  Gram engines
+    // only, through raw_sweep / raw_gram / raw_axpy_cols (design_ops.hpp); it has no dense and no 2-bit view of its own, so
+    // every `dense() ? ... : ...snp...` branch of the panel engines and of the block builds has no_pieces() in front of it
+    bool pieces() const { return D->is_pieces(); }
     DevBuf<T> d_std_tmp, d_std_coef;
     // multi-response view (adelie_hip_design_create_multi): residual / weights live response-major on the device
     bool multi() const { return D->is_multi(); }

@@ -239,6 +239,7 @@
     // residual, partial gradients of this block) -> reduce -> one-workgroup solve against the cached diagonal block.
     // The residual is current when this returns (no end-of-fit update), also on failure (changes are undone).
     void run_panel_passes(const CdParams<T>& cp, CdScalars<T>& sc, T* r_dev) {
+        no_pieces(*D, "the panel engine"); // (unreachable: engine_panel is off; the fused launches below take a dense or a 2-bit view)
         // Block size: 128 visits under fixed weights (Gaussian: a diagonal block is built once and re-used for the rest of
         // the path); 64 under IRLS, where every block is rebuilt per IRLS iteration and used about once, so the MFMA cost
         // per coordinate (block size x n MACs, lower triangle only below 64) matters more than the per-block latencies.
@@ -853,6 +854,7 @@
     }
 
     void run_group_panel_passes(const CdParams<T>& cp, CdScalars<T>& sc, T* r_dev) {
+        no_pieces(*D, "the group panel engine"); // (unreachable: engine_panel is off; the fused launches below take a dense or a 2-bit view)
         const int SL = cd_block_size();
         panel_setup(group_maxblk());
         const size_t maxblk = panel_maxblk;

@@ -469,6 +469,7 @@
             adev_tol = 0; ddev_tol = 0;
             rdev_tol = T(a->rdev_tol);
         }
+        if (pieces()) engine_panel = false; // Gram engines only; no rule below turns the panel engines back on (checked at the end)
         if (sparse() || std_generic()) engine_panel = false; // Gram engines: C = X_S^T W X_S from launch_gram_csc, residual updated once per fit
         // ... except IRLS on the plain compressed columns (groups of one, or groups of at most 128): the panel engine's sequential form (step over
         // the stored entries, 64-visit diagonal blocks by row-list merges; kernels_sparse.hip) -- a Gram of the whole screen set
@@ -503,6 +504,9 @@
             bool any = false;
             for (idx g = 0; g < G; ++g) any = any || a->constraint_kind[g] != 0;
             if (any) {
+                if (pieces())
+                    throw make_core_error("constraints are not implemented on a design made of pieces (their solves live in the panel engines); "
+                                          "use concatenate(..., resident=\"auto\").");
                 // the constrained solves live in the panel engines: a design kept sparse has them under IRLS only (compressed-column
                 // panel form), a standardized view of a dense / 2-bit design whenever its panel form is on (ADELIE_HIP_STD_PANEL)
                 if (sparse() && !engine_panel)
@@ -629,6 +633,7 @@
                 }
             }
         }
+        if (pieces() && engine_panel) throw make_core_error("internal: the panel engines were chosen for a design made of pieces.");
         // device allocations
         d_r.reserve(n); d_v.reserve(n); d_grad.reserve(p); d_absgrad.reserve(G); d_penalty.reserve(G);
         d_groups.reserve(G); d_gsizes.reserve(G); d_slot.reserve(G);

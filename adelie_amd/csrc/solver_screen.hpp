@@ -44,6 +44,7 @@
                    bool want_tail = false, const T* tail_xm = nullptr) {
         step_tailed = false;
         if (multi()) return launch_multi_panel_step<T>(D->multi<T>(), w, r, dcol, dlt, nz_dev, cols, nb, d_part.p, st);
+        no_pieces(*D, "the panel step"); // (unreachable: engine_panel is off)
         const T* kappa = nullptr;
         const bool stdv = D->std_center != nullptr; // a standardized view (of a dense / 2-bit design, or of compressed columns)
         if (stdv) { // the changes over the scales into the base design's step, then kappa = sum c delta / s off every row
@@ -110,6 +111,7 @@
     // `sb.count` diagonal blocks in one launch (non-multi designs): block y = columns cols_base[sb.off[y] ...], into
     // D0 + sb.dst[y] (ld = B)
     void gram_block_batch(const T* w, const int32_t* cols_base, const SyrkBatch& sb, const T* xm, T* D0, int side) {
+        no_pieces(*D, "a batch of diagonal blocks"); // (unreachable: engine_panel is off)
         const int B = cd_block_size();
         hipStream_t gs = side == 0 ? st : (side >= 2 ? st_x[side - 2] : st2);
         if (sparse()) { // compressed columns: one thread per pair of columns merges the two row lists (kernels_sparse.hip)
@@ -137,6 +139,7 @@
     }
     // B x B block  X_cols^T W X_cols - xm xm^T  into Dptr (ld = B)
     void gram_block(const T* w, const int32_t* cols, int nb, const T* xm, T* Dptr, int side = 0) {
+        no_pieces(*D, "a diagonal block"); // (unreachable: engine_panel is off)
         const int B = cd_block_size();
         hipStream_t gs = side == 0 ? st : (side >= 2 ? st_x[side - 2] : st2);
         t_gram.begin(gs);

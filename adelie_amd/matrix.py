@@ -119,6 +119,14 @@ def _no_constraint(mat, what):
         raise RuntimeError(f"adelie_amd: {what} takes a design matrix, not a covariance matrix (method=\"cov\").")
 
 
+def _no_pieces(mat, what, instead=""):
+    """What a design made of pieces (``concatenate(..., resident="pieces")``) does not offer is refused here, before anything
+    is launched on it; the C entry points refuse it as well."""
+    if getattr(mat, "_kind", None) == "pieces":
+        raise RuntimeError(f"adelie_amd: {what} is not offered on a design made of pieces (concatenate(..., resident=\"pieces\"))."
+                           f"{instead}  resident=\"auto\" copies the pieces into one design, on which everything works.")
+
+
 class PyMatrixNaiveTranspose:
     """``X.T @ v`` (reference ``matrix.py:52-76``)."""
 
@@ -222,6 +230,8 @@ class _NativeMatrix:
         self._backend.check(self._backend.fn("design_alias")(self._handle, handle))
         out = _wrap(self._backend, handle, self.dtype, self._n_threads, kind=getattr(self, "_kind", None))
         out._alias_of = self
+        if hasattr(self, "pieces"):
+            out.pieces = list(self.pieces)
         if hasattr(self, "_scipy"):
             out._scipy, out._device = self._scipy, getattr(self, "_device", 0)
             if getattr(self, "_std", None) is not None:
@@ -261,6 +271,7 @@ class _NativeMatrix:
 
     def impute(self):
         """The ``(p,)`` impute values of an SNP design (what a missing call contributes)."""
+        _no_pieces(self, "impute", "  Ask the 2-bit pieces.")
         out = np.empty(self._cols, dtype=np.float64)
         self._backend.check(self._backend.fn("design_impute")(self._handle, out.ctypes.data))
         return out
@@ -342,6 +353,29 @@ class _NativeMatrix:
         w = _as(weights, self.dtype)
         o = self._out(out)
         self._backend.check(self._backend.fn("design_mul")(self._handle, v.ctypes.data, w.ctypes.data, o.ctypes.data))
+        self._writeback(o, out)
+
+    def bmul_cols(self, cols, v, weights, out):
+        """:meth:`bmul` over an explicit column list (any order, repeats allowed): ``out[k] = X[:, cols[k]] . (v * weights)``."""
+        cols = np.ascontiguousarray(cols, dtype=np.int64)
+        self._chk(cols.ndim == 1 and cols.size >= 1 and len(v) == self._rows and len(weights) == self._rows
+                  and len(out) == cols.size, "bmul_cols() is given inconsistent inputs!")
+        v = _as(v, self.dtype)
+        w = _as(weights, self.dtype)
+        o = self._out(out)
+        self._backend.check(self._backend.fn("design_bmul_cols")(self._handle, cols.ctypes.data, cols.size, v.ctypes.data,
+                                                                 w.ctypes.data, o.ctypes.data))
+        self._writeback(o, out)
+
+    def btmul_cols(self, cols, v, out):
+        """:meth:`btmul` over an explicit column list: ``out += sum_k v[k] X[:, cols[k]]`` (a design kept sparse takes distinct
+        columns only)."""
+        cols = np.ascontiguousarray(cols, dtype=np.int64)
+        self._chk(cols.ndim == 1 and cols.size >= 1 and len(v) == cols.size and len(out) == self._rows,
+                  "btmul_cols() is given inconsistent inputs!")
+        v = _as(v, self.dtype)
+        o = self._out(out)
+        self._backend.check(self._backend.fn("design_btmul_cols")(self._handle, cols.ctypes.data, cols.size, v.ctypes.data, o.ctypes.data))
         self._writeback(o, out)
 
     def mul_batch(self, V):
@@ -713,6 +747,7 @@ def _std_view(base, centers, scales, n_threads):
 
 
 def _multi_view(base, K, intercept):
+    _no_pieces(base, "a multi-response view (kronecker_eye, the multigaussian and multinomial families)")
     if not isinstance(base, _NativeMatrix) or isinstance(base, _MultiView):
         raise RuntimeError("adelie_amd: the multi-response view needs a resident (dense or 2-bit SNP) design as its base.")
     if int(K) < 1:
@@ -744,6 +779,7 @@ def kronecker_eye(mat, K: int, *, n_threads: int = 1):
     ``matrix_naive_kronecker_eye.ipp``).  An ``(n, 1)`` array of ones is recognised as the intercept block that
     :func:`concatenate` puts in front of ``kronecker_eye(X, K)``."""
     _no_constraint(mat, "kronecker_eye")
+    _no_pieces(mat, "kronecker_eye")
     if isinstance(mat, np.ndarray):
         if mat.ndim == 2 and mat.shape[1] == 1 and np.all(mat == 1):
             return _OnesKron(mat.shape[0], int(K), mat.dtype.type)
@@ -758,17 +794,108 @@ class _OnesKron:
         self.n, self.K, self.dtype = n, K, dtype
 
 
-def concatenate(mats, *, axis: int = 0, n_threads: int = 1):
+# pieces a design made of pieces may have (adelie_amd/csrc/pieces_host.hpp: kMaxPieces -- the table travels in the kernel arguments)
+_MAX_PIECES = 8
+
+
+def _piece_kind(m):
+    """What a piece is, for the refusals of ``concatenate(..., resident="pieces")``."""
+    if isinstance(m, MatrixConstraintBase):
+        return "constraint matrix"
+    if isinstance(m, MatrixCovBase):
+        return "covariance matrix"
+    if isinstance(m, (_MultiView, _OnesKron)):
+        return "multi-response view"
+    if isinstance(m, _StdView) or getattr(m, "_std", None) is not None:
+        return "standardized view"
+    if not isinstance(m, _NativeMatrix):
+        return type(m).__name__
+    kind = getattr(m, "_kind", None)
+    return "kept sparse" if kind == "sparse" else str(kind)
+
+
+def _concatenate_pieces(mats, axis, n_threads):
+    """``concatenate(..., axis=1, resident="pieces")``: every refusal is raised here, before a piece is uploaded or a handle made."""
+    tail = " (concatenate(..., resident=\"pieces\"); resident=\"auto\" copies the pieces into one design, on which everything works)."
+    if axis != 1:
+        raise RuntimeError(f"adelie_amd: concatenate(): resident=\"pieces\" keeps column blocks, axis must be 1, not {axis}{tail}")
+    if len(mats) == 0:
+        raise RuntimeError("mats must be non-empty.")
+    if len(mats) > _MAX_PIECES:
+        raise RuntimeError(f"adelie_amd: concatenate(): {len(mats)} pieces given, at most {_MAX_PIECES} are kept as they are{tail}")
+    for k, m in enumerate(mats):
+        if isinstance(m, np.ndarray):
+            if m.ndim != 2:
+                raise RuntimeError(f"adelie_amd: concatenate(): piece {k} (ndarray) must be 2-dimensional{tail}")
+            continue
+        kind = _piece_kind(m)
+        if kind not in ("dense", "snp"):
+            raise RuntimeError(f"adelie_amd: concatenate(): piece {k} ({kind}) is neither a plain dense nor a plain 2-bit design{tail}")
+    kinds = ["dense" if isinstance(m, np.ndarray) else m._kind for m in mats]
+    first = mats[0]
+    dt0, n0 = np.dtype(first.dtype), first.shape[0]
+    dev0 = getattr(first, "_device", None) if isinstance(first, np.ndarray) else int(first._backend.fn("design_device")(first._handle))
+    for k, m in enumerate(mats):
+        who = f"piece {k} ({kinds[k]})"
+        if np.dtype(m.dtype) != dt0:
+            raise RuntimeError(f"adelie_amd: concatenate(): {who} differs in dtype from piece 0{tail}")
+        if m.shape[0] != n0:
+            raise RuntimeError(f"adelie_amd: concatenate(): {who} differs in its number of rows from piece 0{tail}")
+        if not isinstance(m, np.ndarray):
+            dev = int(m._backend.fn("design_device")(m._handle))
+            if dev0 is None:
+                dev0 = dev
+            if dev != dev0:
+                raise RuntimeError(f"adelie_amd: concatenate(): {who} lives on another device than piece 0{tail}")
+    if dt0 not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise RuntimeError(f"adelie_amd: concatenate(): the pieces must be float32 or float64{tail}")
+    mats = [dense(m, n_threads=n_threads, device=dev0 or 0) if isinstance(m, np.ndarray) else m for m in mats]
+    backend = mats[0]._backend
+    handles = (_abi.C.c_void_p * len(mats))(*[m._handle for m in mats])
+    handle = _abi.C.c_void_p()
+    backend.check(backend.fn("design_create_pieces")(handles, len(mats), handle))
+    out = _wrap(backend, handle, mats[0].dtype, n_threads, keep=list(mats), kind="pieces")  # (borrows the pieces' arrays)
+    firsts = np.concatenate([[0], np.cumsum([m.cols() for m in mats])[:-1]])
+    out.pieces = [(int(f), k) for f, k in zip(firsts, kinds)]
+    return out
+
+
+def concatenate(mats, *, axis: int = 0, n_threads: int = 1, resident: str = "auto"):
     """Reference ``adelie.matrix.concatenate`` (``matrix.py:214-310``).
 
     * ``[kronecker_eye(ones((n, 1)), K), kronecker_eye(X, K)]`` along ``axis=1`` — the combination the multi-response
       solver builds (``state.py:1110-1120``) — becomes the multi-response view of ``X`` (nothing materialised);
     * resident designs (dense, SNP, sparse, derived; ndarrays are uploaded first) are copied side by side into one new
       dense design on the device (``adelie_hip_design_create_concat``); the reference keeps a list of views and dispatches
-      every operation to the pieces (``matrix_naive_concatenate.ipp``)."""
+      every operation to the pieces (``matrix_naive_concatenate.ipp``).
+
+    ``resident`` says what happens to resident pieces along ``axis=1``:
+
+    * ``"auto"`` (default) -- the copy above: 2-bit pieces side by side stay one 2-bit design, sparse pieces stay sparse,
+      every other mixture is decoded into one new dense design (a few dense covariates in front of a 2-bit block turn
+      ``n p / 4`` bytes into ``8 n p``);
+    * ``"pieces"`` -- no copy (``adelie_hip_design_create_pieces``): the result borrows the device arrays of its pieces and
+      keeps them alive.  Up to 8 pieces in any order, each a plain resident dense design or a plain 2-bit design (column
+      slices from :func:`subset` and the expanded one-hot / interaction / convex-relu designs count as the dense designs
+      they are; ndarrays are uploaded first).  Different dtypes, row counts or devices, ``axis=0``, more than 8 pieces and
+      every other kind of piece (kept sparse, a standardized or multi-response view, a covariance or constraint matrix,
+      another pieces design) are refused before anything is allocated, with a message that names the piece.  The result has
+      ``_kind == "pieces"`` and ``pieces``, the list of ``(first column, kind)``.  Every matrix operation, ``grpnet`` with the
+      Gaussian and the single-response GLM families (any groups, penalties with zeros), ``cv_grpnet``, ``diagnostic`` and
+      ``glm_path_losses`` work on it; the path runs on the full-Gram engines, and a full sweep runs piece by piece with the
+      pieces' own kernels.  Refused on it: ``kronecker_eye`` and the multi-response families, ``standardize`` (standardize
+      the dense piece with ``lazy=False`` before concatenating), ``subset`` other than the identity, a further
+      ``concatenate``, ``lazy_cov``, ``bvls``, constraints."""
+    if resident not in ("auto", "pieces"):
+        raise ValueError("resident must be 'auto' or 'pieces'.")
     mats = list(mats)
+    if resident == "pieces":
+        if n_threads < 1:
+            raise RuntimeError("adelie_core: n_threads must be >= 1.")
+        return _concatenate_pieces(mats, axis, n_threads)
     for m in mats:
         _no_constraint(m, "concatenate")
+        _no_pieces(m, "a further concatenate")
     if (axis == 1 and len(mats) == 2 and isinstance(mats[0], _OnesKron) and isinstance(mats[1], _MultiView)
             and mats[1]._icpt == 0 and mats[0].K == mats[1]._K and mats[0].n == mats[1]._base.rows()):
         return _multi_view(mats[1]._base, mats[1]._K, True)
@@ -1602,6 +1729,7 @@ def standardize(mat, centers=None, scales=None, ddof: int = 0, *, n_threads: int
 
     ``_centers`` / ``_scales`` are attached to the result."""
     _no_constraint(mat, "standardize")
+    _no_pieces(mat, "standardize", "  Standardize the dense piece with lazy=False before concatenating instead.")
     if isinstance(mat, (list, np.ndarray)):
         mat = np.array(mat, order="F", copy=True)
         if centers is None:
@@ -1648,6 +1776,11 @@ def subset(mat, indices, *, axis: int = 0, n_threads: int = 1):
         indices = np.flatnonzero(indices)
     if axis not in (0, 1):
         raise RuntimeError("axis must be 0 or 1.")
+    if getattr(mat, "_kind", None) == "pieces":  # (the identity is the design itself; anything else would need a copy)
+        size = mat.rows() if axis == 0 else mat.cols()
+        if indices.ndim == 1 and indices.size == size and np.array_equal(indices, np.arange(size)):
+            return mat
+        _no_pieces(mat, "subset other than the identity", "  Subset the pieces before concatenating instead.")
     view = _slice_view(mat, indices, axis, n_threads)
     if view is not None:
         return view
@@ -2090,6 +2223,7 @@ def lazy_cov(mat, *, copy: bool = False, n_threads: int = 1, device: int = 0):
     ``copy`` is accepted for signature parity (the data matrix is copied to HBM in any case and released afterwards)."""
     if n_threads < 1:
         raise RuntimeError("adelie_core: n_threads must be >= 1.")
+    _no_pieces(mat, "lazy_cov")
     X = mat if isinstance(mat, _NativeMatrix) else dense(mat, method="naive", n_threads=n_threads, device=device)
     backend = X._backend
     if not backend.has("design_create_cov_lazy"):

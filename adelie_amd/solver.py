@@ -533,6 +533,7 @@ def bvls(
     sparse, standardized and multi-response views) take the same loop in Python over their ``cmul`` / ``ctmul`` / ``mul``:
     slow, and meant for coverage rather than speed (``state.bvls``)."""
     X = matrix.as_design(X, n_threads=n_threads)
+    matrix._no_pieces(X, "bvls")
     dtype = np.dtype(X.dtype)
     n, p = X.shape
     if weights is None:

@@ -54,7 +54,10 @@ _COUNTERS = ["n_basil_iters", "n_sweeps", "n_cd_visits_screen", "n_cd_visits_act
              "n_resid_col_reads", "n_panel_blocks", "n_panel_grams", "n_panel_cols", "n_irls_screen_cols",
              "n_speculated", "n_spec_rollbacks", "n_sweeps_shared", "n_update_cols", "n_device_screens",
              "n_host_screens", "n_host_cons_visits", "n_dev_cons_visits", "n_sweeps_factor",
-             "n_sweeps_filtered", "n_sweeps_refilled", "n_filter_exact_cols", "n_filter_shadow_cols"]
+             "n_sweeps_filtered", "n_sweeps_refilled", "n_filter_exact_cols", "n_filter_shadow_cols",
+             # (1 when the solve's set-up left the panel engines open to it, 0 when it kept the solve on the Gram engines; summed
+             # over several solves it counts the former)
+             "engine_panel"]
 _TIMERS = ["gram_flops", "t_sweep_ms", "t_gram_ms", "t_cd_ms", "t_axpy_ms", "n_sweep_launches", "n_gram_launches",
            "t_host_screen_ms", "t_panel_step_ms", "n_panel_step_launches", "t_host_screen_wait_ms",
            "t_fsweep_ms", "n_fsweep_launches", "fsweep_bytes",
@@ -1521,6 +1524,7 @@ class bvls(_ScreenSetState):
     def __init__(self, X, y_var, X_vars, lower, upper, weights, kappa, max_iters, tol, screen_set_size, screen_set,
                  is_screen, active_set_size, active_set, is_active, beta, resid, grad, loss):
         X = _matrix.as_design(X)
+        _matrix._no_pieces(X, "bvls")
         dtype = np.dtype(X.dtype)
         _abi.dtype_code(dtype)
         n, p = X.rows(), X.cols()

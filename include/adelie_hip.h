@@ -193,6 +193,22 @@ int adelie_hip_design_create_derived(adelie_hip_design* src, const int64_t* rows
  * are decoded, except that 2-bit designs side by side (axis 1, all of them SNP) give a 2-bit design.  The sources stay valid and
  * independent.  The reference's error strings for mismatched shapes are kept. */
 int adelie_hip_design_create_concat(adelie_hip_design* const* srcs, int64_t k, int axis, adelie_hip_design** out);
+/* Column blocks kept as they are (adelie_amd.matrix.concatenate(..., axis=1, resident="pieces"); the reference's
+ * matrix_naive_concatenate.ipp keeps its pieces too): the (n, sum of p_m) design whose columns are those of the k <= 8 sources side
+ * by side, without a copy.  Every source is a plain dense design or a plain 2-bit SNP design (a column slice and the expanded
+ * one-hot / interaction / convex-relu designs count as the dense designs they are); all share rows, dtype and device.  Anything
+ * else -- a design kept sparse, a standardized or multi-response view, a covariance or constraint matrix, another pieces design,
+ * more than 8 sources -- is refused before anything is allocated, with a message that names the piece and its kind.  The new
+ * handle BORROWS the sources' device arrays and owns none: the sources must outlive it and every alias of it
+ * (adelie_hip_design_owned_bytes does not move).
+ * Offered on it: the matrix operations (cmul, ctmul, bmul, btmul, mul, mul_batch, cov, sq_mul, sp_tmul, glm_path_losses),
+ * adelie_hip_design_alias, adelie_hip_bench_sweep, and adelie_hip_grpnet_solve for the Gaussian and the single-response GLM
+ * families without constraints, always on the full-Gram engines (ADELIE_HIP_INFO_ENGINE_PANEL of such a solve is 0).  A sweep
+ * over a column range runs piece by piece with the kernels of the pieces' own storage, so a column's value is what its piece
+ * alone gives.  Refused on it with an error: create_multi, create_standardized, create_derived, create_slice, a further
+ * create_concat / create_pieces, create_cov_lazy, impute, bvls / pinball solves, constraints, adelie_hip_block_build_test.
+ * The entry is additive and changes the layout of no existing structure: ADELIE_HIP_ABI_VERSION stays as it is. */
+int adelie_hip_design_create_pieces(adelie_hip_design* const* srcs, int64_t k, adelie_hip_design** out);
 /* Multi-response view of a resident dense or 2-bit SNP design: the (n*K) x ((p + intercept)*K) matrix
  *     [ 1_n (x) I_K ,  X (x) I_K ]      (the first block only when `intercept` != 0)
  * that adelie/state.py:1100-1125 (_render_multi_inputs) builds from matrix.kronecker_eye / matrix.concatenate
@@ -299,6 +315,12 @@ int adelie_hip_design_ctmul(adelie_hip_design* d, int64_t j, double v, void* out
 int adelie_hip_design_bmul(adelie_hip_design* d, int64_t j, int64_t q, const void* v, const void* weights, void* out);
 /* btmul (:106-123): out += v^T X[:, j:j+q]^T */
 int adelie_hip_design_btmul(adelie_hip_design* d, int64_t j, int64_t q, const void* v, void* out);
+/* bmul / btmul over an explicit column list (any order, a column may repeat; on a design kept sparse the columns of btmul_cols
+ * must be distinct): out[k] = x_cols[k] . (v o weights) for k < q, and out += sum_k v[k] x_cols[k].  On every design the matrix
+ * operations take; on a design made of pieces (adelie_hip_design_create_pieces) these are the direct way to the kernels that
+ * resolve a column's piece one by one, which bmul / btmul over a range do not take.  Additive: the ABI version stays. */
+int adelie_hip_design_bmul_cols(adelie_hip_design* d, const int64_t* cols, int64_t q, const void* v, const void* weights, void* out);
+int adelie_hip_design_btmul_cols(adelie_hip_design* d, const int64_t* cols, int64_t q, const void* v, void* out);
 /* mul   (:125-146): out = (v * weights)^T X */
 int adelie_hip_design_mul(adelie_hip_design* d, const void* v, const void* weights, void* out);
 /* L sweeps in one call: out[l,:] = V[l,:]^T X for l < L; V is (L,n) and out (L,p), both row-major.  Replaces the loop of
@@ -652,7 +674,11 @@ enum adelie_hip_scalar {
     /* the pivot rule's reading of the sorted scores (ADELIE_HIP_FILTER_DEPTH): positions screen() read, counted from the top
      * and summed over its calls; threshold passes that fell short of what the rule read (each takes the full sweep and the
      * sort of all G after all); columns the filtered sweeps listed as open and read a second time in f64 */
-    ADELIE_HIP_S_N_SCREEN_READS, ADELIE_HIP_S_N_SCREEN_SHORT, ADELIE_HIP_S_N_FILTER_OPEN_COLS
+    ADELIE_HIP_S_N_SCREEN_READS, ADELIE_HIP_S_N_SCREEN_SHORT, ADELIE_HIP_S_N_FILTER_OPEN_COLS,
+    /* 1 when the set-up of this solve left the panel engines open to it (they take a fit once its screen set is large enough),
+     * 0 when it kept the solve on the full-Gram engines throughout: the covariance method, a design kept sparse or a
+     * standardized view without their panel forms, and always a design made of pieces (adelie_hip_design_create_pieces) */
+    ADELIE_HIP_S_ENGINE_PANEL
 };
 int64_t     adelie_hip_result_size(const adelie_hip_result* r, int which);
 /* Copies min(size, cap) elements: value vectors as double, index vectors as int64. */
