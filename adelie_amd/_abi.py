@@ -266,7 +266,7 @@ HIP_SYMBOLS = [
     "design_create_one_hot", "design_create_interaction", "design_factor_groups",
     "design_create_convex_relu", "design_create_convex_relu_csc",
     "design_create_snp_phased_ancestry", "design_create_snp_phased_calldata", "design_csc_download", "design_nnz",
-    "design_glm_path_losses", "design_multi_path_losses", "design_batch_stats", "design_rows", "design_cols", "design_dtype",
+    "design_glm_path_losses", "design_multi_path_losses", "design_cox_path_losses", "design_batch_stats", "design_rows", "design_cols", "design_dtype",
     "design_device", "design_stream",
     "design_cmul", "design_ctmul", "design_bmul", "design_btmul", "design_bmul_cols", "design_btmul_cols", "design_mul", "design_mul_batch", "design_cov",
     "design_sq_mul", "design_sp_tmul",
@@ -363,6 +363,7 @@ class Backend:
         sig("design_create_pieces", ci, [vp, i64, p(vp)])
         sig("design_glm_path_losses", ci, [vp, ci, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp])
         sig("design_multi_path_losses", ci, [vp, ci, ci, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp])
+        sig("design_cox_path_losses", ci, [vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp])
         sig("design_destroy", ci, [vp])
         sig("design_owned_bytes", i64, [])
         sig("design_rows", i64, [vp])

@@ -43,6 +43,15 @@ template <class T>
 void cox_eval(const CoxPack& pk, const T* eta, T* grad, T* hess, bool want_loss, double* scratch, hipStream_t st);
 size_t cox_loss_slot(int64_t n);
 
+// The losses of `lc` etas under two packs over the same n rows (cv_grpnet: the full-data family and a fold's training family),
+// eta_l[i] = T(base[l * n + i] + b0[l] + off[i]), in five launches whatever `lc`: out[2 l] is the double cox_eval(pa, eta_l,
+// null, null, true) leaves in its loss slot, out[2 l + 1] the same under pb, bit for bit (same tiles, same combination trees).
+// Device pointers, enqueued on `st`; `scratch` holds cox_loss_batch_scratch_doubles(n, lc) doubles.
+template <class T>
+void cox_loss_batch(const CoxPack& pa, const CoxPack& pb, const T* base, const T* b0, const T* off, int64_t lc,
+                    double* scratch, double* out, hipStream_t st);
+size_t cox_loss_batch_scratch_doubles(int64_t n, int64_t lc);
+
 } // namespace ahip
 
 struct adelie_hip_glm_cox;

@@ -6,6 +6,7 @@
 #include <memory>
 #include <mutex>
 #include "common.hpp"
+#include "cox.hpp"
 #include "design_ops.hpp"
 #include "csc_build_host.hpp"
 #include "cov_csc_host.hpp"
@@ -451,6 +452,40 @@ void op_multi_path_losses(adelie_hip_design* d, int kind, int K, int64_t L, cons
         }
     });
     download_loss_pairs<T>(d, dres, L, out);
+}
+
+// The Cox losses of eta_l = X beta_l + intercepts[l] + offsets under two families over the same rows: the etas stay in their
+// panel, cox_loss_batch evaluates them `mb` at a time (five launches per sub-batch, whatever its size).
+template <class T>
+void op_cox_path_losses(adelie_hip_design* d, const CoxPack& pa, const CoxPack& pb, int64_t L, const int64_t* indptr,
+                        const int64_t* indices, const T* values, const T* intercepts, const T* offsets, int64_t max_batch,
+                        double* out) {
+    set_device(d);
+    hipStream_t s = d->stream;
+    const int64_t n = d->n;
+    for (int64_t e = indptr[0]; e < indptr[L]; ++e)
+        if (indices[e] < 0 || indices[e] >= d->p) throw make_core_error("cox_path_losses: column index out of range.");
+    // etas per cox_loss_batch call: as many as keep the Cox scratch within 1 GiB (the eta panel's own bound) unless told
+    constexpr int64_t kMaxGridY = 65535;
+    const int64_t fit = (int64_t(1) << 30) / int64_t(cox_loss_batch_scratch_doubles(n, 1) * sizeof(double));
+    const int64_t mb = std::min(std::min(kMaxGridY, L), std::max<int64_t>(1, max_batch > 0 ? max_batch : fit));
+    const DevCsr<T> A = upload_csr<T>(d, L, indptr, indices, values);
+    // one buffer: the loss pairs and the Cox scratch (doubles), then the offsets and the intercepts
+    const size_t nscr = cox_loss_batch_scratch_doubles(n, mb);
+    const size_t tail = ((size_t(n) + size_t(L)) * sizeof(T) + sizeof(double) - 1) / sizeof(double);
+    double* dres = scratch<double>(d->s_n1, size_t(2) * L + nscr + tail);
+    double* scr = dres + size_t(2) * L;
+    T* doff = reinterpret_cast<T*>(scr + nscr);
+    T* db0 = doff + n;
+    AHIP_CHECK(hipMemcpyAsync(doff, offsets, n * sizeof(T), hipMemcpyHostToDevice, s));
+    AHIP_CHECK(hipMemcpyAsync(db0, intercepts, L * sizeof(T), hipMemcpyHostToDevice, s));
+    for_each_eta_panel<T>(d, A, L, 1, [&](int64_t l0, int64_t lc, const T* eta) {
+        for (int64_t l = 0; l < lc; l += mb) {
+            const int64_t c = std::min(mb, lc - l);
+            cox_loss_batch<T>(pa, pb, eta + size_t(l) * size_t(n), db0 + l0 + l, doff, c, scr, dres + 2 * (l0 + l), s);
+        }
+    });
+    download_loss_pairs<double>(d, dres, L, out);
 }
 
 // the multi-response view only serves grpnet_solve; its matrix ops go through the base design
@@ -1589,6 +1624,26 @@ int adelie_hip_design_multi_path_losses(adelie_hip_design* d, int glm_kind, int 
     if (L > 0) {
         DTYPE_DISPATCH(d, op_multi_path_losses<T>(d, glm_kind, K, L, indptr, indices, (const T*)values, (const T*)intercepts,
                                                   (const T*)offsets, (const T*)y, (const T*)weights_a, (const T*)weights_b, out))
+    }
+    ABI_CATCH
+}
+
+int adelie_hip_design_cox_path_losses(adelie_hip_design* d, const adelie_hip_glm_cox* ga, const adelie_hip_glm_cox* gb, int64_t L,
+                                      const int64_t* indptr, const int64_t* indices, const void* values,
+                                      const void* intercepts, const void* offsets, int64_t max_batch, double* out) {
+    ABI_TRY
+    no_view(d);
+    if (!d || !ga || !gb || !indptr || !intercepts || !offsets || !out) throw make_core_error("null argument.");
+    if (L < 0) throw make_core_error("cox_path_losses: L must be >= 0.");
+    if (max_batch < 0) throw make_core_error("cox_path_losses: max_batch must be >= 0 (0: chosen by the scratch bound).");
+    for (const adelie_hip_glm_cox* g : {ga, gb}) {
+        if (g->device != d->device) throw make_core_error("cox_path_losses: the family's handle is on another device than the design.");
+        if (g->dtype != d->dtype) throw make_core_error("cox_path_losses: the family's dtype differs from the design's.");
+        if (g->pack.n != d->n) throw make_core_error("cox_path_losses: the family and the design differ in their number of rows.");
+    }
+    if (L > 0) {
+        DTYPE_DISPATCH(d, op_cox_path_losses<T>(d, ga->pack, gb->pack, L, indptr, indices, (const T*)values,
+                                                (const T*)intercepts, (const T*)offsets, max_batch, out))
     }
     ABI_CATCH
 }

@@ -13,6 +13,7 @@
 // Scans are reduce-then-scan over tiles of TILE elements with a fixed combination tree (the carry of tile b is folded from
 // the aggregates of tiles 0..b-1 by each block itself, no look-back, no atomics): two evaluations of the same input are
 // bit-identical.  A segmented sum never crosses a stratum (or tie group) boundary.
+// cox_loss_batch (B1-B5 below) is the loss-only form of the chain for many etas under two packs at once: cv_grpnet's fold losses.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -406,6 +407,256 @@ __global__ __launch_bounds__(CT) void cox_loss_final_kernel(double* __restrict__
     if (threadIdx.x == 0) scr[L.loss()] = s;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// cox_loss_batch: the loss alone at `lc` etas under two packs over the same rows (cv_grpnet's full-data and training families).
+// The chain above with lambda on blockIdx.y and both packs in one kernel body, without scan 2's prefix scans:
+//   B1 cox_batch_max         c_l = max eta_l (one maximum per lambda; it does not depend on the weights)
+//   B2 cox_batch_scan1_up    K2 for both packs: eta is gathered and exp(eta - c_l) taken once where the packs name the same row
+//   B3 cox_batch_scan1_down  K3 for both packs, in place (a thread reads its own z before it writes the sums over them)
+//   B4 cox_batch_loss_parts  the loss halves of K4 (log-risk, stop order) and K6 (-sum w d (eta - c), row order)
+//   B5 cox_batch_loss_final  K7 per (lambda, pack)
+// Every sum runs over the same tiles through the same trees as in cox_eval (thread_fold = the loops of K2 / K3, block_seg_scan,
+// tile_carry, block_sum, the chunked final fold over "log-risk partials, then row partials"), so the losses are cox_eval's bits.
+// Each pack's own index arrays are read: nothing assumes that two cox_create calls sorted alike.
+
+// scratch layout (doubles): per (lambda, pack) 3 n-vectors, then per (lambda, pack) the scan-1 tile aggregates, per lambda the
+// max partials, per (lambda, pack) the loss partials
+struct BatchLayout {
+    int64_t n, nt, lc;
+    __host__ __device__ size_t lf(int64_t l, int f) const { return size_t(l) * 2 + size_t(f); }
+    __host__ __device__ size_t vec(int64_t l, int f, int k) const { return (lf(l, f) * 3 + size_t(k)) * size_t(n); } // z_to -> S_stop, z_so -> S_start, T_tie
+    __host__ __device__ size_t agg0() const { return size_t(6) * size_t(lc) * size_t(n); }
+    __host__ __device__ size_t agg(int64_t l, int f) const { return agg0() + lf(l, f) * 6 * size_t(nt); }   // nt * 3 sums, nt * 3 flags
+    __host__ __device__ size_t pmax(int64_t l) const { return agg0() + (size_t(12) * size_t(lc) + size_t(l)) * size_t(nt); }
+    __host__ __device__ size_t lossp(int64_t l, int f) const { return agg0() + (size_t(13) * size_t(lc) + lf(l, f) * 2) * size_t(nt); } // 2 nt
+    __host__ __device__ size_t total() const { return agg0() + size_t(17) * size_t(lc) * size_t(nt); }
+};
+
+// eta_l at row i, formed in T in the order glm_loss2_kernel forms it
+template <class T>
+__device__ __forceinline__ T batch_eta(const T* __restrict__ bl, T b0, const T* __restrict__ off, int64_t i) {
+    return bl[i] + b0 + off[i];
+}
+
+// a thread's aggregate of its CE consecutive elements
+template <int C>
+__device__ __forceinline__ void thread_fold(const double (&v)[CE][C], const bool (&fl)[CE][C], bool (&f)[C], double (&s)[C]) {
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        f[k] = false; s[k] = 0;
+#pragma unroll
+        for (int e = 0; e < CE; ++e) {
+            bool F = fl[e][k];
+            double S = v[e][k];
+            seg_combine(f[k], s[k], F, S);
+            f[k] = F; s[k] = S;
+        }
+    }
+}
+
+// scan 1's three channels of one element from its z values and flags (as K2 / K3 fill them)
+__device__ __forceinline__ void scan1_channels(uint8_t g, double zt, double zs, double (&v)[3], bool (&fl)[3]) {
+    v[0] = zt; v[1] = (g & COX_IND) ? zt : 0.0; v[2] = zs;
+    fl[0] = (g & COX_STRATUM_LAST) != 0; fl[1] = (g & COX_TIE_LAST) != 0; fl[2] = fl[0];
+}
+__device__ __forceinline__ void scan1_padding(double (&v)[3], bool (&fl)[3]) {
+    v[0] = v[1] = v[2] = 0;
+    fl[0] = fl[1] = fl[2] = true;
+}
+
+template <class T>
+__global__ __launch_bounds__(CT) void cox_batch_max_kernel(const T* __restrict__ base, const T* __restrict__ b0,
+                                                           const T* __restrict__ off, BatchLayout L, double* __restrict__ scr) {
+    __shared__ double red[NW];
+    const int64_t n = L.n, l = blockIdx.y;
+    const T* bl = base + size_t(l) * size_t(n);
+    const T bb = b0[l];
+    double m = -INFINITY;
+    const int64_t first = int64_t(blockIdx.x) * TILE;
+#pragma unroll
+    for (int e = 0; e < CE; ++e) {
+        const int64_t i = first + int64_t(e) * CT + threadIdx.x;
+        if (i < n) m = fmax(m, double(batch_eta(bl, bb, off, i)));
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) m = fmax(m, __shfl_down(m, d, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r = red[0];
+        for (int w = 1; w < NW; ++w) r = fmax(r, red[w]);
+        scr[L.pmax(l) + blockIdx.x] = r;
+    }
+}
+
+// B2 for one pack.  FIRST: the rows and exp(eta - c) of this pack's stop / start positions are kept in rt / rs / xt / xs; the
+// second pack takes them over wherever it names the same row, and gathers for itself where it does not.
+template <class T, bool FIRST>
+__device__ __forceinline__ void batch_scan1_up_pack(const CoxPack& pk, const T* __restrict__ bl, T bb, const T* __restrict__ off,
+                                                    double c, int64_t b, int64_t (&rt)[CE], int64_t (&rs)[CE], double (&xt)[CE],
+                                                    double (&xs)[CE], double* __restrict__ zto, double* __restrict__ zso,
+                                                    double* __restrict__ agg, int64_t nt) {
+    const int64_t n = pk.n;
+    double v[CE][3];
+    bool fl[CE][3];
+#pragma unroll
+    for (int e = 0; e < CE; ++e) {
+        const int64_t j = b * TILE + int64_t(threadIdx.x) * CE + e;
+        if (j < n) {
+            const int64_t q = n - 1 - j;
+            const int64_t r1 = pk.to[q], r2 = pk.so[q];
+            double x1, x2;
+            if (FIRST) {
+                rt[e] = r1; rs[e] = r2;
+                xt[e] = x1 = exp(double(batch_eta(bl, bb, off, r1)) - c);
+                xs[e] = x2 = exp(double(batch_eta(bl, bb, off, r2)) - c);
+            } else {
+                x1 = r1 == rt[e] ? xt[e] : exp(double(batch_eta(bl, bb, off, r1)) - c);
+                x2 = r2 == rs[e] ? xs[e] : exp(double(batch_eta(bl, bb, off, r2)) - c);
+            }
+            const double zt = pk.w[r1] * x1;
+            const double zs = pk.w[r2] * x2;
+            zto[q] = zt;
+            zso[q] = zs;
+            scan1_channels(pk.flags[q], zt, zs, v[e], fl[e]);
+        } else {
+            scan1_padding(v[e], fl[e]);
+        }
+    }
+    bool f[3], tf[3];
+    double s[3], ts[3];
+    thread_fold<3>(v, fl, f, s);
+    block_seg_scan<3>(f, s, tf, ts);
+    if (threadIdx.x < 3) {
+        agg[b * 3 + threadIdx.x] = ts[threadIdx.x];
+        agg[nt * 3 + b * 3 + threadIdx.x] = tf[threadIdx.x] ? 1.0 : 0.0;
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(CT) void cox_batch_scan1_up_kernel(CoxPack pa, CoxPack pb, const T* __restrict__ base,
+                                                                const T* __restrict__ b0, const T* __restrict__ off,
+                                                                BatchLayout L, double* __restrict__ scr) {
+    const int64_t b = blockIdx.x, l = blockIdx.y;
+    const T* bl = base + size_t(l) * size_t(L.n);
+    const T bb = b0[l];
+    const double c = fold_max(scr + L.pmax(l), L.nt);
+    int64_t rt[CE], rs[CE];
+    double xt[CE], xs[CE];
+    batch_scan1_up_pack<T, true>(pa, bl, bb, off, c, b, rt, rs, xt, xs, scr + L.vec(l, 0, 0), scr + L.vec(l, 0, 1),
+                                 scr + L.agg(l, 0), L.nt);
+    batch_scan1_up_pack<T, false>(pb, bl, bb, off, c, b, rt, rs, xt, xs, scr + L.vec(l, 1, 0), scr + L.vec(l, 1, 1),
+                                  scr + L.agg(l, 1), L.nt);
+}
+
+// B3 for one pack: z_to -> S_stop and z_so -> S_start in place, T_tie beside them
+__device__ __forceinline__ void batch_scan1_down_pack(const CoxPack& pk, int64_t b, double* zto, double* zso,
+                                                      double* __restrict__ ttie, const double* __restrict__ agg, int64_t nt) {
+    const int64_t n = pk.n;
+    double v[CE][3];
+    bool fl[CE][3];
+#pragma unroll
+    for (int e = 0; e < CE; ++e) {
+        const int64_t j = b * TILE + int64_t(threadIdx.x) * CE + e;
+        if (j < n) {
+            const int64_t q = n - 1 - j;
+            scan1_channels(pk.flags[q], zto[q], zso[q], v[e], fl[e]);
+        } else {
+            scan1_padding(v[e], fl[e]);
+        }
+    }
+    bool f[3], tf[3], cf[3];
+    double s[3], ts[3], cs[3];
+    thread_fold<3>(v, fl, f, s);
+    block_seg_scan<3>(f, s, tf, ts);
+    tile_carry<3>(agg, nt, b, cf, cs);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) seg_combine(cf[k], cs[k], f[k], s[k]); // incoming sum of the thread's first element
+#pragma unroll
+    for (int e = 0; e < CE; ++e) {
+        const int64_t j = b * TILE + int64_t(threadIdx.x) * CE + e;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s[k] = fl[e][k] ? v[e][k] : s[k] + v[e][k];
+        if (j < n) {
+            const int64_t q = n - 1 - j;
+            zto[q] = s[0];
+            ttie[q] = s[1];
+            zso[q] = s[2];
+        }
+    }
+}
+
+__global__ __launch_bounds__(CT) void cox_batch_scan1_down_kernel(CoxPack pa, CoxPack pb, BatchLayout L, double* scr) {
+    const int64_t b = blockIdx.x, l = blockIdx.y;
+    batch_scan1_down_pack(pa, b, scr + L.vec(l, 0, 0), scr + L.vec(l, 0, 1), scr + L.vec(l, 0, 2), scr + L.agg(l, 0), L.nt);
+    batch_scan1_down_pack(pb, b, scr + L.vec(l, 1, 0), scr + L.vec(l, 1, 1), scr + L.vec(l, 1, 2), scr + L.agg(l, 1), L.nt);
+}
+
+// the log-risk part of one pack's loss over tile b (stop order): K4's risk totals and its sum, nothing else of K4
+__device__ __forceinline__ double batch_log_risk(const CoxPack& pk, int64_t b, const double* __restrict__ s_stop,
+                                                 const double* __restrict__ s_start, const double* __restrict__ t_tie,
+                                                 double neg_max) {
+    const int64_t n = pk.n;
+    double lsum = 0;
+#pragma unroll
+    for (int e = 0; e < CE; ++e) {
+        const int64_t q = b * TILE + int64_t(threadIdx.x) * CE + e;
+        if (q < n) {
+            const uint8_t g = pk.flags[q];
+            const double sc = pk.scale[q];
+            const int64_t gs = pk.gstart[q], bp = pk.bpos[q];
+            const double risk = s_stop[gs] - (bp >= 0 ? s_start[bp] : 0.0);
+            const double rt = risk - sc * ((g & COX_IND) ? t_tie[gs] : 0.0);
+            const double dw = pk.dw[q];
+            if (dw != 0) lsum += dw * fmax(log(fmax(rt, 0.0)), neg_max);
+        }
+    }
+    return block_sum(lsum);
+}
+
+template <class T>
+__global__ __launch_bounds__(CT) void cox_batch_loss_parts_kernel(CoxPack pa, CoxPack pb, const T* __restrict__ base,
+                                                                  const T* __restrict__ b0, const T* __restrict__ off,
+                                                                  BatchLayout L, double* __restrict__ scr, double neg_max) {
+    const int64_t n = L.n, b = blockIdx.x, l = blockIdx.y;
+    const T* bl = base + size_t(l) * size_t(n);
+    const T bb = b0[l];
+    const double c = fold_max(scr + L.pmax(l), L.nt);
+    const double ga = batch_log_risk(pa, b, scr + L.vec(l, 0, 0), scr + L.vec(l, 0, 1), scr + L.vec(l, 0, 2), neg_max);
+    const double gb = batch_log_risk(pb, b, scr + L.vec(l, 1, 0), scr + L.vec(l, 1, 1), scr + L.vec(l, 1, 2), neg_max);
+    double la = 0, lb = 0;
+#pragma unroll
+    for (int e = 0; e < CE; ++e) {
+        const int64_t r = b * TILE + int64_t(e) * CT + threadIdx.x;
+        if (r >= n) continue;
+        const double er = double(batch_eta(bl, bb, off, r)) - c;
+        la -= pa.wd[r] * er;
+        lb -= pb.wd[r] * er;
+    }
+    la = block_sum(la);
+    lb = block_sum(lb);
+    if (threadIdx.x == 0) {
+        scr[L.lossp(l, 0) + b] = ga;
+        scr[L.lossp(l, 0) + L.nt + b] = la;
+        scr[L.lossp(l, 1) + b] = gb;
+        scr[L.lossp(l, 1) + L.nt + b] = lb;
+    }
+}
+
+// grid (2, lc): pack blockIdx.x of lambda blockIdx.y
+__global__ __launch_bounds__(CT) void cox_batch_loss_final_kernel(BatchLayout L, const double* __restrict__ scr,
+                                                                  double* __restrict__ out) {
+    const int64_t l = blockIdx.y;
+    const int f = int(blockIdx.x);
+    const double* part = scr + L.lossp(l, f);
+    const int64_t m = 2 * L.nt;
+    const int64_t chunk = (m + CT - 1) / CT;
+    double s = 0;
+    for (int64_t t = int64_t(threadIdx.x) * chunk; t < min(int64_t(threadIdx.x + 1) * chunk, m); ++t) s += part[t];
+    s = block_sum(s);
+    if (threadIdx.x == 0) out[size_t(l) * 2 + size_t(f)] = s;
+}
+
 } // namespace
 
 size_t cox_scratch_doubles(int64_t n) { return Layout{n, n_tiles(n)}.total(); }
@@ -429,6 +680,30 @@ void cox_eval(const CoxPack& pk, const T* eta, T* grad, T* hess, bool want_loss,
 
 template void cox_eval<float>(const CoxPack&, const float*, float*, float*, bool, double*, hipStream_t);
 template void cox_eval<double>(const CoxPack&, const double*, double*, double*, bool, double*, hipStream_t);
+
+size_t cox_loss_batch_scratch_doubles(int64_t n, int64_t lc) { return BatchLayout{n, n_tiles(n), lc}.total(); }
+
+template <class T>
+void cox_loss_batch(const CoxPack& pa, const CoxPack& pb, const T* base, const T* b0, const T* off, int64_t lc,
+                    double* scratch, double* out, hipStream_t st) {
+    if (pa.n != pb.n) throw make_core_error("cox_loss_batch: the two families have different numbers of rows.");
+    if (lc > 65535) throw make_core_error("cox_loss_batch: at most 65535 etas per call.");
+    if (pa.n <= 0 || lc <= 0) return;
+    const BatchLayout L{pa.n, n_tiles(pa.n), lc};
+    const dim3 g(static_cast<unsigned>(L.nt), static_cast<unsigned>(lc)), blk(CT);
+    const double neg_max = -double(std::numeric_limits<T>::max());
+    hipLaunchKernelGGL(cox_batch_max_kernel<T>, g, blk, 0, st, base, b0, off, L, scratch);
+    hipLaunchKernelGGL(cox_batch_scan1_up_kernel<T>, g, blk, 0, st, pa, pb, base, b0, off, L, scratch);
+    hipLaunchKernelGGL(cox_batch_scan1_down_kernel, g, blk, 0, st, pa, pb, L, scratch);
+    hipLaunchKernelGGL(cox_batch_loss_parts_kernel<T>, g, blk, 0, st, pa, pb, base, b0, off, L, scratch, neg_max);
+    hipLaunchKernelGGL(cox_batch_loss_final_kernel, dim3(2, static_cast<unsigned>(lc)), blk, 0, st, L, scratch, out);
+    AHIP_CHECK(hipGetLastError());
+}
+
+template void cox_loss_batch<float>(const CoxPack&, const CoxPack&, const float*, const float*, const float*, int64_t, double*,
+                                    double*, hipStream_t);
+template void cox_loss_batch<double>(const CoxPack&, const CoxPack&, const double*, const double*, const double*, int64_t,
+                                     double*, double*, hipStream_t);
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The pack, built on the host (glm_cox.ipp:214-354, 519-597 restated on stratum-segmented global arrays)

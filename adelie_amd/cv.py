@@ -82,6 +82,13 @@ def fold_ranges(n: int, n_folds: int):
     return out
 
 
+def _cox_on_device(X, glm):
+    """Whether a fold's Cox losses take ``X.cox_path_losses`` (native designs of a library that has the entry); plugin designs
+    and older libraries keep ``predict`` + ``glm.loss`` on the host."""
+    return (getattr(glm, "core_kind", None) == _abi.GLM_COX and hasattr(X, "cox_path_losses") and hasattr(X, "_backend")
+            and X._backend.has("design_cox_path_losses"))
+
+
 def _fold_loss(X, glm, fold_idx, full_lmdas, *, n_threads, early_exit, min_ratio, lmda_path_size, grpnet_params, stats=None,
                phase=None, carry=None):
     """Body of the reference's fold loop (``cv.py:247-314``).
@@ -136,6 +143,10 @@ def _fold_loss(X, glm, fold_idx, full_lmdas, *, n_threads, early_exit, min_ratio
         # multi-response fits: the (L, n, K) predictions stay on the device as well
         full_data_losses, train = X.multi_path_losses(_MULTI_KINDS[glm.name], glm.y.shape[1], full_betas,
                                                       full_intercepts, state._offsets, glm.y, glm.weights, glm_c.weights)
+        train_losses = weights_sum * train
+    elif _cox_on_device(X, glm):
+        # Cox is not elementwise: both families' risk-set sums per lambda run on the device, batched over lambda
+        full_data_losses, train = X.cox_path_losses(glm, glm_c, full_betas, full_intercepts, state._offsets)
         train_losses = weights_sum * train
     else:
         etas = predict(X=X, betas=full_betas, intercepts=full_intercepts, offsets=state._offsets, n_threads=n_threads)
@@ -212,6 +223,10 @@ def cv_grpnet(X, glm, *, n_threads: int = 1, early_exit: bool = False, min_ratio
         cons = grpnet_params.get("constraints")
         if cons is not None and any(c is not None for c in cons):
             nc = 1  # the constraint objects carry their multipliers between calls: folds sharing them run one at a time
+        if _cox_on_device(X, glm):
+            # every fold evaluates the full-data family on the design's device: its handle is made here, once, instead of by
+            # whichever fold threads reach the family's (plain dict) handle cache first
+            glm._device_handle(int(X._backend.fn("design_device")(X._handle)))
 
         def one(Xa, fold):
             b, e = ranges[fold]

@@ -483,8 +483,10 @@ def cox(start, stop, status, *, strata=None, weights=None, tie_method: str = "ef
 
     summed over strata, with ``R(u) = {k : s_k < u <= t_k}``, ``H(u)`` the events at ``u`` with non-zero weight, ``wbar`` their
     average weight and ``sigma`` the Efron scales (zero for Breslow).  The numpy members below serve the Python preamble,
-    ``diagnostic``, ``cv_grpnet``'s fold losses and the tests; inside ``grpnet`` the family is evaluated on the device
-    (``kernels_cox.hip``) from a handle the library builds on first use (``_device_handle``)."""
+    ``diagnostic``, the tests, and ``cv_grpnet``'s fold losses on plugin designs; inside ``grpnet`` the family is evaluated on
+    the device (``kernels_cox.hip``) from a handle the library builds on first use (``_device_handle``), and ``cv_grpnet`` on a
+    native design takes a fold's losses under the full-data and the training family from ``X.cox_path_losses``: every lambda
+    in one batched device evaluation from the same handles, the etas never leaving HBM."""
     status, dtype = _coerce_dtype(status, dtype)
     return _cox_make(start, stop, status, strata, weights, tie_method, dtype, None)
 

@@ -223,6 +223,32 @@ class _NativeMatrix:
             icpt.ctypes.data, off.ctypes.data, yy.ctypes.data, wa.ctypes.data, wb.ctypes.data, out.ctypes.data))
         return out[:L], out[L:]
 
+    def cox_path_losses(self, glm_a, glm_b, betas, intercepts, offsets, *, _max_batch=0):
+        """Cox losses of ``eta_l = X beta_l + intercepts[l] + offsets`` under two ``glm.cox`` families over this design's rows
+        (``cv_grpnet``: the full-data family and a fold's training family), all on the device
+        (``adelie_hip_design_cox_path_losses``).  ``betas`` is a CSR ``(L, p)`` matrix.  Returns two float64 ``(L,)`` arrays:
+        entry ``l`` is the double ``glm._device_eval(eta_l)`` returns for the loss.  ``_max_batch``: etas per batched
+        evaluation (0: as many as 1 GiB of scratch holds); the result does not depend on it."""
+        for g in (glm_a, glm_b):
+            if getattr(g, "core_kind", None) != _abi.GLM_COX or not hasattr(g, "_device_handle"):
+                raise RuntimeError("cox_path_losses: both families must be glm.cox families.")
+        dt = self.dtype
+        betas = betas.tocsr()
+        L = betas.shape[0]
+        if betas.shape[1] != self._cols or np.shape(intercepts) != (L,) or np.shape(offsets) != (self._rows,):
+            raise RuntimeError("cox_path_losses() is given inconsistent inputs!")
+        dev = int(self._backend.fn("design_device")(self._handle))
+        ha, hb = glm_a._device_handle(dev), glm_b._device_handle(dev)
+        indptr = np.ascontiguousarray(betas.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(betas.indices, dtype=np.int64)
+        values = np.ascontiguousarray(betas.data, dtype=dt)
+        icpt, off = (np.ascontiguousarray(v, dtype=dt) for v in (intercepts, offsets))
+        out = np.empty(2 * L, dtype=np.float64)
+        self._backend.check(self._backend.fn("design_cox_path_losses")(
+            self._handle, ha.h, hb.h, L, indptr.ctypes.data, indices.ctypes.data, values.ctypes.data, icpt.ctypes.data,
+            off.ctypes.data, int(_max_batch), out.ctypes.data))
+        return out[:L], out[L:]
+
     def alias(self):
         """A second handle on the same resident matrix with its own stream (``adelie_hip_design_alias``): lets independent
         solves run concurrently from different threads.  Keeps this design alive."""
@@ -711,6 +737,12 @@ class _StdView(_NativeMatrix):
         scaled = betas.tocsr().multiply(1 / self._s[None]).tocsr()
         shift = np.asarray(scaled @ self._c).reshape(-1)
         return self._base.glm_path_losses(glm_kind, scaled, np.asarray(intercepts) - shift, offsets, y, weights_a, weights_b)
+
+    def cox_path_losses(self, glm_a, glm_b, betas, intercepts, offsets, *, _max_batch=0):
+        # (the transformation of glm_path_losses above)
+        scaled = betas.tocsr().multiply(1 / self._s[None]).tocsr()
+        shift = np.asarray(scaled @ self._c).reshape(-1)
+        return self._base.cox_path_losses(glm_a, glm_b, scaled, np.asarray(intercepts) - shift, offsets, _max_batch=_max_batch)
 
     def multi_path_losses(self, glm_kind, K, betas, intercepts, offsets, y, weights_a, weights_b):
         betas = betas.tocsr()

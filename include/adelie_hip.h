@@ -418,6 +418,21 @@ int adelie_hip_glm_cox_create(int device, int dtype, int64_t n, const void* star
                               const int64_t* strata, const void* weights, int tie_method, adelie_hip_glm_cox** out);
 int adelie_hip_glm_cox_destroy(adelie_hip_glm_cox* h);
 int adelie_hip_glm_cox_eval(adelie_hip_glm_cox* h, const void* eta, void* grad, void* hess, double* loss);
+/* cv_grpnet post-processing for the Cox family on the device (what adelie_hip_design_glm_path_losses is for the elementwise
+ * families): for the L sparse coefficient rows (CSR, int64 indices) computes eta_l = X beta_l + intercepts[l] + offsets, formed
+ * in the design's dtype in that order, and returns
+ *   out[l]     = the loss of family ga at eta_l        (the double adelie_hip_glm_cox_eval(ga, eta_l) returns, bit for bit)
+ *   out[L + l] = the same under gb
+ * without moving the (L, n) linear predictors to the host.  ga and gb are two families over the design's rows that differ by
+ * their weights (the full-data family and a fold's training family); both live on the design's device, in the design's dtype.
+ * The etas of a panel are evaluated max_batch at a time, in a number of launches that does not depend on the batch; with
+ * max_batch == 0 the batch is the largest whose Cox scratch stays within 1 GiB (6 n + 17 ceil(n / 1024) doubles per lambda).
+ * The result does not depend on max_batch.  Works on every design sp_tmul works on.  values / intercepts / offsets in the
+ * design's dtype.  Errors start with "cox_path_losses:".
+ * The entry is additive and changes the layout of no existing structure: ADELIE_HIP_ABI_VERSION stays as it is. */
+int adelie_hip_design_cox_path_losses(adelie_hip_design* d, const adelie_hip_glm_cox* ga, const adelie_hip_glm_cox* gb,
+                                      int64_t L, const int64_t* indptr, const int64_t* indices, const void* values,
+                                      const void* intercepts, const void* offsets, int64_t max_batch, double* out);
 
 typedef struct adelie_hip_grpnet_args {
     /* ---- problem (static) ---- */
