@@ -258,6 +258,26 @@ class GroupPiece(C.Structure):
     )
 
 
+# adelie_hip_multi_piece_mode
+(MULTI_SWEEP, MULTI_STEP, MULTI_FUSED_STEP, MULTI_BLOCK_LISTS, MULTI_EXPAND, MULTI_EXPAND_CROSS, MULTI_AXPY, MULTI_TO_MAJOR,
+ MULTI_FROM_MAJOR, MULTI_BATCH_PICK) = range(10)
+
+
+class MultiPiece(C.Structure):
+    """adelie_hip_multi_piece (include/adelie_hip.h): every field 8 bytes wide."""
+    _fields_ = (
+        [(n, C.c_int64) for n in ("dtype", "mode", "nb", "pb", "K", "icpt")]
+        + [("X", C.c_void_p), ("X_elems", C.c_int64), ("x_off", C.c_int64), ("ld", C.c_int64), ("bits", C.c_void_p),
+           ("bits_elems", C.c_int64), ("ldb", C.c_int64), ("impute", C.c_void_p), ("v", C.c_void_p), ("v_off", C.c_int64),
+           ("out", C.c_void_p), ("w", C.c_void_p), ("r", C.c_void_p), ("dcol", C.c_void_p), ("dlt", C.c_void_p),
+           ("n_dcol", C.c_int64), ("nz", C.c_int64), ("cols", C.c_void_p), ("nb_cols", C.c_int64), ("part", C.c_void_p),
+           ("part_elems", C.c_int64), ("sign", C.c_double), ("nv", C.c_int64), ("nc", C.c_int64)]
+        + [(n, C.c_void_p) for n in ("ulist", "slot", "resp", "slot_c", "resp_c", "C")]
+        + [("C_elems", C.c_int64), ("ldc", C.c_int64), ("D", C.c_void_p), ("D_elems", C.c_int64), ("ldd", C.c_int64),
+           ("lsel_list", C.c_void_p), ("n_lsel", C.c_int64), ("lsel", C.c_int64)]
+    )
+
+
 # every symbol include/adelie_hip.h declares (checked by tests/test_abi.py)
 HIP_SYMBOLS = [
     "abi_version", "last_error", "device_count", "set_config",
@@ -273,7 +293,7 @@ HIP_SYMBOLS = [
     "design_create_cov_dense", "design_create_cov_csc", "design_create_cov_lazy", "design_cov_bmul", "design_cov_mul", "design_cov_to_dense", "gaussian_cov_solve",
     "glm_cox_create", "glm_cox_destroy", "glm_cox_eval",
     "grpnet_solve", "grpnet_solve_many", "result_destroy", "result_size", "result_copy", "result_scalar", "result_error", "result_sync",
-    "bench_sweep", "filter_sweep_test", "block_build_test", "group_piece_test", "cov_piece_test",
+    "bench_sweep", "filter_sweep_test", "block_build_test", "group_piece_test", "multi_piece_test", "cov_piece_test",
     "css_cov_solve", "css_result_destroy", "css_result_size", "css_result_copy", "css_result_scalar", "css_result_error",
     "bvls_solve", "bvls_result_destroy", "bvls_result_size", "bvls_result_copy", "bvls_result_scalar", "bvls_result_error",
     "design_create_constraint_dense", "design_adopt_constraint_dense_dev", "design_create_constraint_csc", "constraint_op",
@@ -404,6 +424,7 @@ class Backend:
         sig("filter_sweep_test", ci, [vp, vp, vp, dbl, vp, vp, i64, vp, vp, i64, vp, dbl, vp, vp, vp])
         sig("block_build_test", ci, [vp, ci, i64, vp, vp, i64, vp, i64, vp, ci, i64, ci, vp, i64, vp, i64, vp])
         sig("group_piece_test", ci, [p(GroupPiece), vp])
+        sig("multi_piece_test", ci, [p(MultiPiece), vp])
         sig("cov_piece_test", ci, [vp, ci, vp, i64, i64, i64, i64, dbl, vp, vp, vp, i64, vp])
         sig("css_cov_solve", ci, [vp, p(CssArgs), p(vp)])
         sig("css_result_destroy", ci, [vp])

@@ -492,6 +492,16 @@ struct HipMem {
 };
 template <class T> using DevArr = OwnedArr<T, HipMem>;
 
+// The column of ones of a multi-response view (MultiView::ones): nb ones, padded with zeros like a design column so that vector
+// loads past nb stay in bounds.  Enqueued on `s`; the caller synchronises.
+template <class T>
+void alloc_multi_ones(DevArr<void>& ones, int64_t nb, hipStream_t s) {
+    const int64_t len = ((nb + 31) / 32) * 32;
+    ones.alloc(size_t(len) * sizeof(T));
+    AHIP_CHECK(hipMemsetAsync(ones, 0, size_t(len) * sizeof(T), s));
+    launch_fill<T>(static_cast<T*>(ones.get()), T(1), nb, s);
+}
+
 // ---- the device arrays of a design handle, grouped by what they belong to ------------------------------------------------------
 // Every array is a DevArr: the handle that allocated it frees it when it is deleted, a handle that borrowed it (an alias, a
 // slice, a view) frees nothing.  borrow_from() under each group is all that adelie_hip_design_alias does with it, so a new

@@ -1308,14 +1308,8 @@ int adelie_hip_design_create_multi(adelie_hip_design* base, int64_t K, int inter
     d->micpt = int(icpt);
     d->nb = base->n;
     d->pb = base->p;
-    {   // the column of ones (padded like a design column so that vector loads past nb stay in bounds)
-        const size_t esz = base->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
-        const int64_t len = ((base->n + 31) / 32) * 32;
-        d->ones.alloc(size_t(len) * esz);
-        AHIP_CHECK(hipMemsetAsync(d->ones, 0, size_t(len) * esz, d->stream));
-        DTYPE_DISPATCH(d, launch_fill<T>((T*)d->ones, T(1), base->n, d->stream))
-        AHIP_CHECK(hipStreamSynchronize(d->stream));
-    }
+    DTYPE_DISPATCH(d, alloc_multi_ones<T>(d->ones, base->n, d->stream)) // the column of ones
+    AHIP_CHECK(hipStreamSynchronize(d->stream));
     *out = g.release();
     ABI_CATCH
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "gram_shape.hpp"
+#include "multi_shape.hpp"
 #include "relu_shape.hpp"
 #include "relu_sparse_shape.hpp"
 #include "shadow_kind_host.hpp"
@@ -692,16 +693,20 @@ struct MultiView {
 // out[u*K + l] = sum_i xcol(u)[i] * v[l*nb + i]  for every u in [0, pb + icpt): X is read ONCE for all K responses.
 template <class T> void launch_multi_sweep(const MultiView<T>& X, const T* v, T* out, T* work, hipStream_t s);
 template <class T> int64_t multi_sweep_work_elems(const MultiView<T>& X);
+// what launch_multi_sweep runs for this view and this v (multi_shape.hpp); rows per load of the panel steps (the type's vector
+// width, or 1 when the base does not take vector loads)
+template <class T> MSweepPlan multi_sweep_plan(const MultiView<T>& X, const T* v);
+template <class T> int multi_step_vec(const MultiView<T>& X);
 // the same over a 2-bit SNP design: out[u*K + l] = x_u . v[l*n + :]; work sized as for the view {nb = n, pb = p, icpt = 0, K}
 template <class T>
 void launch_multi_sweep_snp(const SnpView& X, const T* impute, int K, const T* v, T* out, T* work, hipStream_t s);
-// panel step on view columns (same contract as launch_panel_step; `part` holds multi_panel_part_elems(nb) elements):
+// panel step on view columns (same contract as launch_panel_step; returns the row slices = leading dimension of `part`,
+// mstep_slices(nb, multi_step_vec(X)); `part` holds nb_cols times that many elements; at most 128 changes, 256 columns):
 //   r -= sum_{m < *nz_dev} dlt[m] X'[:, dcol[m]];   part[c][slice] = X'[slice, cols[c]] . (w*r)[slice]  for c < nb_cols
 // entries that share an extended feature (the K responses of a group) are served by one load of the column slice.
 template <class T>
 int launch_multi_panel_step(const MultiView<T>& X, const T* w, T* r, const int32_t* dcol, const T* dlt,
                             const int32_t* nz_dev, const int32_t* cols, int nb_cols, T* part, hipStream_t s);
-int64_t multi_panel_part_elems(int64_t nb);
 // out[:, response] += sign * coef[m] * xcol(feature)  for m < *cnt_dev   (rollback path)
 template <class T>
 void launch_multi_axpy_cols(const MultiView<T>& X, const int32_t* cols, const T* coef, const int32_t* cnt_dev, T sign,
@@ -720,7 +725,8 @@ void launch_multi_expand(const T* C, int64_t ldc, const int32_t* slot, const int
 // ulist and its response.  nv <= 128.
 void launch_multi_block_lists(const int32_t* cols, int nv, int K, int32_t* ulist, int32_t* slot, int32_t* resp,
                               hipStream_t s);
-// fused look-ahead launch on the view: group solve of block j + multi-response step; returns the leading dimension of part
+// fused look-ahead launch on the view: group solve of block j + multi-response step (nb_cols <= 128); returns the leading
+// dimension of part, mfused_part_ld(nb, multi_step_vec(X))
 template <class T>
 int launch_multi_panel_fused(const CdGrpBlkParams<T>& sp, int j, const MultiView<T>& X, const T* w, T* r,
                              const int32_t* dcol, const T* dlt, const int32_t* nz_dev, const int32_t* cols, int nb_cols,

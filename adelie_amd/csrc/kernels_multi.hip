@@ -21,6 +21,7 @@
 #include "accessors.hpp"
 #include "wavered.hpp"
 #include "grp_solve_body.hpp"
+#include "multi_shape.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -29,12 +30,9 @@ namespace ahip {
 
 namespace {
 
-constexpr int MT = 256;  // threads of the sweep kernel
-// Features per sweep block.  The K vectors are re-read (from L2) once per block: with 4 features a K = 8 sweep pulls twice as
-// many bytes of v through L2 as it streams of X from HBM and ends up bound by L2 (1.73 ms = 4.6 TB/s at 100k x 10k f64); with
-// 8 the two are equal.
-constexpr int MCB_MAX = 8;
-constexpr int MAXB = 128; // entries of a panel block (== cd_block_size())
+constexpr int MT = kMultiSweepThreads; // threads of the sweep kernel
+constexpr int MAXB = kMultiBlock;       // entries of a panel block (== cd_block_size())
+static_assert(MT == 256 && MAXB == 128, "the kernels below are written for these");
 
 template <class T>
 __device__ __forceinline__ T wsum(T x) {
@@ -239,28 +237,6 @@ __global__ void multi_sweep_reduce_kernel(const T* __restrict__ part, T* __restr
     out[c] = s;
 }
 
-inline int msweep_mcb() {
-    return 8; // features per block (4 was the round-1 shape: the K vectors re-read from L2 twice as often)
-}
-// 0: one feature group per block; 1: four waves x 8 features; 2: four waves x 4 features (half the accumulators, twice the
-// waves per SIMD: 2.2 ms, the vectors' L2 traffic doubles); 3: four waves x 8 features with the vectors staged through LDS
-inline int msweep_wpc() {
-    return 3; // (the unstaged forms 1 / 2 measured 1.36 / 2.23 ms against 1.335 ms at K = 8)
-}
-inline void msweep_shape(int64_t nb, int64_t nfeat, int vec, int64_t& blocks_c, int& nsplit, int64_t& rows_per_split,
-                         int wpc = 0) {
-    const int MCB = wpc == 2 ? 4 * (MT / 64) : wpc ? 8 * (MT / 64) : msweep_mcb();
-    blocks_c = (nfeat + MCB - 1) / MCB;
-    const int64_t unit = int64_t(MT) * vec;
-    const int64_t max_split = std::max<int64_t>(1, (nb + unit * 4 - 1) / (unit * 4));
-    int64_t ns = std::max<int64_t>(1, (1024 + blocks_c - 1) / blocks_c);
-    ns = std::min<int64_t>(std::min<int64_t>(ns, max_split), 65535);
-    rows_per_split = (nb + ns - 1) / ns;
-    rows_per_split = ((rows_per_split + unit - 1) / unit) * unit;
-    ns = std::max<int64_t>(1, (nb + rows_per_split - 1) / rows_per_split);
-    nsplit = int(ns);
-}
-
 template <class T>
 bool multi_vecok(const MultiView<T>& X) {
     constexpr int V = VecOf<T>::N;
@@ -443,7 +419,7 @@ __global__ __launch_bounds__(64) void multi_panel_step_kernel(Acc X, int64_t nb,
 // every other workgroup of row 0.. is 16 waves = 16 row slices of the multi-response step that prepares block j+1; the slot
 // lists are built once per workgroup.  1024-thread workgroups for the same reason as panel_fused_kernel (the solve's LDS
 // request makes it one workgroup per CU for everybody).
-constexpr int MFS = 16; // waves (row slices) per fused step workgroup
+constexpr int MFS = kMultiFusedWaves; // waves (row slices) per fused step workgroup
 template <class T, class Acc, int VEC, int KT>
 __global__ __launch_bounds__(64 * MFS) void multi_fused_kernel(CdGrpBlkParams<T> sp, int j, Acc X, int64_t nb,
                                                               int K, const T* __restrict__ w, T* __restrict__ r,
@@ -572,21 +548,21 @@ __global__ void multi_from_major_kernel(const T* __restrict__ src, int64_t nb, i
     dst[q] = src[l * nb + i];
 }
 
-inline int kt_of(int K) { return K > 4 ? 8 : (K > 2 ? 4 : 2); }
-
 } // namespace
 
 template <class T>
 int64_t multi_sweep_work_elems(const MultiView<T>& X) {
-    int64_t bc, rps;
-    int ns;
-    msweep_shape(X.nb, X.pb + X.icpt, VecOf<T>::N, bc, ns, rps);
-    int64_t bc2, rps2;
-    int ns2;
-    msweep_shape(X.nb, X.pb + X.icpt, VecOf<T>::N, bc2, ns2, rps2, 1);
-    ns = std::max(ns, ns2);
-    msweep_shape(X.nb, X.pb + X.icpt, VecOf<T>::N, bc2, ns2, rps2, 2);
-    return int64_t(std::max(ns, ns2)) * (X.pb + X.icpt) * X.K + 16;
+    return msweep_work_elems(X.nb, X.pb + X.icpt, X.K, VecOf<T>::N);
+}
+template <class T>
+MSweepPlan multi_sweep_plan(const MultiView<T>& X, const T* v) {
+    constexpr int V = VecOf<T>::N;
+    const bool v_al = X.nb % V == 0 && (reinterpret_cast<uintptr_t>(v) % 16) == 0; // each of the K vectors starts 16-byte aligned
+    return msweep_plan(X.nb, X.pb + X.icpt, X.K, V, multi_vecok(X), v_al);
+}
+template <class T>
+int multi_step_vec(const MultiView<T>& X) {
+    return multi_vecok(X) ? VecOf<T>::N : 1;
 }
 
 namespace {
@@ -594,28 +570,20 @@ template <class T, class Acc>
 void multi_sweep_launch(const Acc& acc, const MultiView<T>& X, const T* v, T* out, T* work, hipStream_t s) {
     const int64_t nfeat = X.pb + X.icpt;
     constexpr int V = VecOf<T>::N;
-    int64_t bc, rps;
-    int ns;
-    const int KT = kt_of(X.K);
-    const int wpc = (KT == 8 && msweep_mcb() == 8) ? msweep_wpc() : 0;
-    msweep_shape(X.nb, nfeat, V, bc, ns, rps, wpc); // shape for the vector width (also valid for scalar loads)
-    const dim3 grid((unsigned)bc, (unsigned)ns, (unsigned)((X.K + KT - 1) / KT));
-    const bool vok = multi_vecok(X);
+    const MSweepPlan pl = multi_sweep_plan<T>(X, v); // (the row splits are cut for the vector width: also valid for scalar loads)
+    const int KT = pl.kt, ns = pl.nsplit;
+    const int64_t rps = pl.rows_per_split;
+    const dim3 grid((unsigned)pl.blocks_c, (unsigned)ns, (unsigned)pl.kchunks);
 #define AHIP_MS(VV, KK)                                                                                                 \
     do {                                                                                                                \
-        if (wpc == 2)                                                                                                   \
-            hipLaunchKernelGGL((multi_sweep_kernel<T, Acc, VV, KK, 4, true>), grid, dim3(MT), 0, s, acc, v, work, X.nb, nfeat, int(X.K), rps); \
-        else if (wpc)                                                                                                   \
+        if (pl.variant == kMSweepFourWave)                                                                              \
             hipLaunchKernelGGL((multi_sweep_kernel<T, Acc, VV, KK, 8, true>), grid, dim3(MT), 0, s, acc, v, work, X.nb, nfeat, int(X.K), rps); \
-        else if (msweep_mcb() == 8)                                                                                     \
-            hipLaunchKernelGGL((multi_sweep_kernel<T, Acc, VV, KK, 8>), grid, dim3(MT), 0, s, acc, v, work, X.nb, nfeat, int(X.K), rps); \
         else                                                                                                            \
-            hipLaunchKernelGGL((multi_sweep_kernel<T, Acc, VV, KK, 4>), grid, dim3(MT), 0, s, acc, v, work, X.nb, nfeat, int(X.K), rps); \
+            hipLaunchKernelGGL((multi_sweep_kernel<T, Acc, VV, KK, 8>), grid, dim3(MT), 0, s, acc, v, work, X.nb, nfeat, int(X.K), rps); \
     } while (0)
-    const bool v_al = X.nb % V == 0 && (reinterpret_cast<uintptr_t>(v) % 16) == 0; // each of the K vectors starts 16-byte aligned
-    if (vok && v_al && wpc == 3) {
+    if (pl.variant == kMSweepStaged) {
         hipLaunchKernelGGL((multi_sweep_lds_kernel<T, Acc, V>), grid, dim3(MT), 0, s, acc, v, work, X.nb, nfeat, int(X.K), rps);
-    } else if (vok) {
+    } else if (pl.vec == V) {
         if (KT == 8) AHIP_MS(V, 8); else if (KT == 4) AHIP_MS(V, 4); else AHIP_MS(V, 2);
     } else {
         if (KT == 8) AHIP_MS(1, 8); else if (KT == 4) AHIP_MS(1, 4); else AHIP_MS(1, 2);
@@ -641,18 +609,12 @@ void launch_multi_sweep_snp(const SnpView& X, const T* impute, int K, const T* v
     if (nfeat <= 0 || K <= 0) return;
     SnpAcc<T> acc{X.bits, X.ldb, impute};
     constexpr int V = VecOf<T>::N; // 2 or 4 calls per load: a row split starts at a multiple of MT * V, so loads stay inside a byte
-    int64_t bc, rps;
-    int ns;
-    msweep_shape(X.n, nfeat, V, bc, ns, rps);
-    const int KT = kt_of(K);
-    const dim3 grid((unsigned)bc, (unsigned)ns, (unsigned)((K + KT - 1) / KT));
+    const MSweepPlan pl = msweep_plan(X.n, nfeat, K, V, true, false, false); // the plain kernel for every K
+    const int KT = pl.kt, ns = pl.nsplit;
+    const int64_t rps = pl.rows_per_split;
+    const dim3 grid((unsigned)pl.blocks_c, (unsigned)ns, (unsigned)pl.kchunks);
 #define AHIP_MSS(KK)                                                                                                    \
-    do {                                                                                                                \
-        if (msweep_mcb() == 8)                                                                                          \
-            hipLaunchKernelGGL((multi_sweep_kernel<T, SnpAcc<T>, V, KK, 8>), grid, dim3(MT), 0, s, acc, v, work, X.n, nfeat, K, rps); \
-        else                                                                                                            \
-            hipLaunchKernelGGL((multi_sweep_kernel<T, SnpAcc<T>, V, KK, 4>), grid, dim3(MT), 0, s, acc, v, work, X.n, nfeat, K, rps); \
-    } while (0)
+    hipLaunchKernelGGL((multi_sweep_kernel<T, SnpAcc<T>, V, KK, 8>), grid, dim3(MT), 0, s, acc, v, work, X.n, nfeat, K, rps)
     if (KT == 8) AHIP_MSS(8); else if (KT == 4) AHIP_MSS(4); else AHIP_MSS(2);
 #undef AHIP_MSS
     const int64_t ncols = nfeat * K;
@@ -660,16 +622,13 @@ void launch_multi_sweep_snp(const SnpView& X, const T* impute, int K, const T* v
                        ncols, ns);
 }
 
-int64_t multi_panel_part_elems(int64_t nb) { return int64_t(MAXB) * ((nb + 63) / 64) + 16; }
-
 namespace {
 template <class T, class Acc>
 int multi_step_launch(const Acc& acc, const MultiView<T>& X, const T* w, T* r, const int32_t* dcol, const T* dlt,
                       const int32_t* nz_dev, const int32_t* cols, int nb_cols, T* part, hipStream_t s) {
     constexpr int V = VecOf<T>::N;
     const bool vok = multi_vecok(X);
-    const int RS = 64 * (vok ? V : 1);
-    const int64_t nsl = (X.nb + RS - 1) / RS;
+    const int64_t nsl = mstep_slices(X.nb, vok ? V : 1);
     const int KT = kt_of(X.K);
     const dim3 grid((unsigned)nsl, (unsigned)((X.K + KT - 1) / KT));
 #define AHIP_MP(VV, KK)                                                                                                 \
@@ -689,10 +648,8 @@ int multi_fused_launch(const Acc& acc, const CdGrpBlkParams<T>& sp, int j, const
                        hipStream_t s) {
     constexpr int V = VecOf<T>::N;
     const bool vok = multi_vecok(X);
-    const int RS = 64 * (vok ? V : 1);
-    const int64_t nsl = (X.nb + RS - 1) / RS;
-    const int64_t nwg = (nsl + MFS - 1) / MFS;
-    const int64_t part_ld = nwg * MFS;
+    const int64_t part_ld = mfused_part_ld(X.nb, vok ? V : 1);
+    const int64_t nwg = part_ld / MFS;
     const int KT = kt_of(X.K);
     const dim3 grid((unsigned)(nwg + 1), (unsigned)((X.K + KT - 1) / KT));
     const size_t lds = grp_solve_lds_total<T>();
@@ -796,6 +753,8 @@ void launch_multi_from_major(const T* src, int64_t nb, int K, T* dst, hipStream_
 
 #define INST(T)                                                                                                        \
     template int64_t multi_sweep_work_elems<T>(const MultiView<T>&);                                                   \
+    template MSweepPlan multi_sweep_plan<T>(const MultiView<T>&, const T*);                                            \
+    template int multi_step_vec<T>(const MultiView<T>&);                                                               \
     template void launch_multi_sweep<T>(const MultiView<T>&, const T*, T*, T*, hipStream_t);                           \
     template void launch_multi_sweep_snp<T>(const SnpView&, const T*, int, const T*, T*, T*, hipStream_t);             \
     template int launch_multi_panel_step<T>(const MultiView<T>&, const T*, T*, const int32_t*, const T*, const int32_t*, \

@@ -1291,6 +1291,267 @@ int adelie_hip_group_piece_test(const adelie_hip_group_piece* a, int64_t* info) 
     return 0;
 }
 
+// One launcher of kernels_multi.hip on caller-supplied inputs (tests; include/adelie_hip.h has the modes and the arrays).  Everything
+// the kernels index by is checked here against the buffers' sizes before anything is launched; the outputs are written only after
+// the last download.
+int adelie_hip_multi_piece_test(const adelie_hip_multi_piece* a, int64_t* info) {
+    try {
+        if (!a || !info) throw make_core_error("bad arguments.");
+        if (a->dtype != ADELIE_HIP_F64 && a->dtype != ADELIE_HIP_F32) throw make_core_error("bad dtype.");
+        constexpr int64_t G = 128, SLOT = G * G, BIG = int64_t(1) << 24;
+        const int mode = int(a->mode);
+        if (a->mode < ADELIE_HIP_MULTI_SWEEP || a->mode > ADELIE_HIP_MULTI_BATCH_PICK) throw make_core_error("unknown mode.");
+        const bool step = mode == ADELIE_HIP_MULTI_STEP || mode == ADELIE_HIP_MULTI_FUSED_STEP;
+        const bool view = mode == ADELIE_HIP_MULTI_SWEEP || step || mode == ADELIE_HIP_MULTI_AXPY;
+        const int64_t nb = a->nb, pb = a->pb, K = a->K, icpt = a->icpt;
+        const int64_t ncol = (pb + icpt) * K; // view columns
+        auto in_cols = [&](const int32_t* list, int64_t n, const char* what) {
+            if (n > 0 && !list) throw make_core_error(std::string(what) + ": null list.");
+            for (int64_t m = 0; m < n; ++m)
+                if (list[m] < 0 || list[m] >= ncol) throw make_core_error(std::string(what) + ": column index outside [0, (pb + icpt) K).");
+        };
+        if (view) {
+            if (nb < 1 || nb > BIG || pb < 1 || pb > (1 << 20) || K < 1 || K > 64 || (icpt != 0 && icpt != 1) || ncol > BIG)
+                throw make_core_error("view: 1 <= nb, pb, 1 <= K <= 64 and icpt in {0, 1} are required.");
+            if (a->bits) {
+                if (a->ldb < (nb + 3) / 4 || a->ldb > BIG || a->bits_elems < 1 || a->bits_elems > (int64_t(1) << 28) || pb * a->ldb > a->bits_elems || !a->impute)
+                    throw make_core_error("view: the 2-bit base needs ldb >= (nb + 3) / 4, pb ldb <= bits_elems and impute.");
+            } else {
+                if (!a->X || a->ld < nb || a->ld > BIG || a->X_elems < 1 || a->X_elems > (int64_t(1) << 28) || pb * a->ld > a->X_elems || a->x_off < 0 || a->x_off > 64)
+                    throw make_core_error("view: the dense base needs ld >= nb, pb ld <= X_elems and 0 <= x_off <= 64.");
+            }
+        }
+        int64_t n_used = 0; // entries of dcol / dlt the kernel may read
+        if (mode == ADELIE_HIP_MULTI_SWEEP) {
+            if (!a->v || !a->out || a->v_off < 0 || a->v_off > 64) throw make_core_error("SWEEP: v, out and 0 <= v_off <= 64 are required.");
+        } else if (step) {
+            const int64_t max_cols = mode == ADELIE_HIP_MULTI_STEP ? 2 * G : G;
+            if (!a->w || !a->r || !a->part || a->nz < 0 || a->nz > INT32_MAX || a->n_dcol < 0 || a->n_dcol > G || a->nb_cols < 0 ||
+                a->nb_cols > max_cols || a->part_elems < 1 || a->part_elems > (int64_t(1) << 28))
+                throw make_core_error("STEP: w, r, part, n_dcol <= 128 and nb_cols <= 256 (128 in the fused step) are required.");
+            n_used = std::min<int64_t>(a->nz, G);
+            if (n_used > a->n_dcol || (n_used > 0 && !a->dlt)) throw make_core_error("STEP: dcol / dlt hold fewer than min(nz, 128) entries.");
+            in_cols(a->dcol, a->n_dcol, "STEP dcol");
+            in_cols(a->cols, a->nb_cols, "STEP cols");
+        } else if (mode == ADELIE_HIP_MULTI_AXPY) {
+            if (!a->r || a->n_dcol < 0 || a->n_dcol > 4096 || a->nz < 0 || a->nz > a->n_dcol || (a->nz > 0 && !a->dlt))
+                throw make_core_error("AXPY: r and 0 <= nz <= n_dcol <= 4096 are required.");
+            n_used = a->nz;
+            in_cols(a->dcol, a->n_dcol, "AXPY dcol");
+        } else if (mode == ADELIE_HIP_MULTI_BLOCK_LISTS) {
+            if (a->nv < 1 || a->nv > G || K < 1 || K > (1 << 20) || !a->cols || !a->ulist || !a->slot || !a->resp)
+                throw make_core_error("BLOCK_LISTS: 1 <= nv <= 128, K >= 1, cols, ulist, slot and resp are required.");
+            for (int64_t m = 0; m < a->nv; ++m)
+                if (a->cols[m] < 0) throw make_core_error("BLOCK_LISTS: negative column index.");
+        } else if (mode == ADELIE_HIP_MULTI_EXPAND || mode == ADELIE_HIP_MULTI_EXPAND_CROSS) {
+            const bool cross = mode == ADELIE_HIP_MULTI_EXPAND_CROSS;
+            const int64_t nr = a->nv, ncc = cross ? a->nc : a->nv;
+            if (nr < 1 || nr > G || ncc < 1 || ncc > G || !a->slot || !a->resp || !a->C || !a->D || a->ldc < 1 || a->ldc > BIG ||
+                a->C_elems < 1 || a->C_elems > (int64_t(1) << 28) || a->ldd < nr || a->ldd > BIG || a->D_elems > (int64_t(1) << 28) ||
+                (ncc - 1) * a->ldd + nr > a->D_elems || (cross && (!a->slot_c || !a->resp_c)))
+                throw make_core_error("EXPAND: 1 <= nv, nc <= 128, slot, resp, C, D with ldd >= nv and (nc - 1) ldd + nv <= D_elems are required.");
+            const int32_t* sc = cross ? a->slot_c : a->slot;
+            int64_t mr = 0, mc = 0;
+            for (int64_t m = 0; m < nr; ++m) {
+                if (a->slot[m] < 0) throw make_core_error("EXPAND: negative slot.");
+                mr = std::max<int64_t>(mr, a->slot[m]);
+            }
+            for (int64_t m = 0; m < ncc; ++m) {
+                if (sc[m] < 0) throw make_core_error("EXPAND: negative slot.");
+                mc = std::max<int64_t>(mc, sc[m]);
+            }
+            if (mr >= a->ldc || mr + mc * a->ldc >= a->C_elems) throw make_core_error("EXPAND: a slot lies outside C.");
+            if (!cross) {
+                if (a->n_lsel < 1 || a->n_lsel > 64 || !a->lsel_list) throw make_core_error("EXPAND: 1 <= n_lsel <= 64 and lsel_list are required.");
+                for (int64_t q = 0; q < a->n_lsel; ++q)
+                    if (a->lsel_list[q] < -1 || a->lsel_list[q] > (1 << 20)) throw make_core_error("EXPAND: lsel out of range.");
+            }
+        } else if (mode == ADELIE_HIP_MULTI_TO_MAJOR || mode == ADELIE_HIP_MULTI_FROM_MAJOR) {
+            if (nb < 1 || K < 1 || nb > BIG || K > BIG || nb * K > (int64_t(1) << 26) || !a->v || !a->out)
+                throw make_core_error("TO_MAJOR / FROM_MAJOR: nb, K >= 1, v and out are required.");
+        } else { // BATCH_PICK
+            if (pb < 1 || K < 1 || pb > BIG || K > BIG || pb * K > (int64_t(1) << 26) || a->lsel < 0 || a->lsel >= K || !a->v || !a->out)
+                throw make_core_error("BATCH_PICK: pb, K >= 1, 0 <= lsel < K, v and out are required.");
+        }
+        AHIP_CHECK(hipSetDevice(0));
+        hipStream_t s = nullptr;
+        for (int q = 0; q < 8; ++q) info[q] = 0;
+        auto body = [&](auto tag) {
+            using T = decltype(tag);
+            auto up = [&](auto& buf, const auto* h, int64_t n) { buf.reserve(size_t(n)); buf.upload(h, size_t(n), s); };
+            auto down = [&](void* h, const void* dev, size_t bytes) { AHIP_CHECK(hipMemcpyAsync(h, dev, bytes, hipMemcpyDeviceToHost, s)); };
+            auto finish = [&](void* dst, std::vector<T>& h, const T* dev) { // download, synchronise, then write the caller's array
+                AHIP_CHECK(hipGetLastError());
+                down(h.data(), dev, h.size() * sizeof(T));
+                AHIP_CHECK(hipStreamSynchronize(s));
+                std::memcpy(dst, h.data(), h.size() * sizeof(T));
+            };
+            DevBuf<T> dX, dimp, dv, dout, dw, dr, ddlt, dpart, dwork;
+            DevBuf<uint8_t> dbits;
+            DevBuf<int32_t> ddcol, dcols, dnz;
+            DevArr<void> ones;
+            MultiView<T> mv{};
+            if (view) {
+                alloc_multi_ones<T>(ones, nb, s);
+                mv.nb = nb; mv.pb = pb; mv.K = int32_t(K); mv.icpt = int32_t(icpt);
+                mv.ones = static_cast<const T*>(ones.get());
+                if (a->bits) {
+                    up(dbits, a->bits, a->bits_elems);
+                    up(dimp, static_cast<const T*>(a->impute), pb);
+                    mv.bits = dbits.p; mv.ldb = a->ldb; mv.impute = dimp.p;
+                } else {
+                    dX.reserve(size_t(a->X_elems + a->x_off + 64));
+                    dX.upload(static_cast<const T*>(a->X), size_t(a->X_elems), s, size_t(a->x_off));
+                    mv.X = dX.p + a->x_off; mv.ld = a->ld;
+                }
+            }
+            if (mode == ADELIE_HIP_MULTI_SWEEP) {
+                dv.reserve(size_t(nb * K + a->v_off + 64));
+                dv.upload(static_cast<const T*>(a->v), size_t(nb * K), s, size_t(a->v_off));
+                up(dout, static_cast<const T*>(a->out), ncol);
+                dwork.reserve(size_t(multi_sweep_work_elems<T>(mv)));
+                const T* v = dv.p + a->v_off;
+                const MSweepPlan pl = multi_sweep_plan<T>(mv, v);
+                if (int64_t(pl.nsplit) * ncol > multi_sweep_work_elems<T>(mv)) throw make_core_error("SWEEP: the work size does not cover the plan.");
+                launch_multi_sweep<T>(mv, v, dout.p, dwork.p, s);
+                info[0] = pl.variant; info[1] = pl.vec; info[2] = pl.kt; info[3] = pl.feats; info[4] = pl.blocks_c; info[5] = pl.nsplit;
+                info[6] = pl.rows_per_split; info[7] = pl.kchunks;
+                std::vector<T> h(static_cast<size_t>(ncol));
+                finish(a->out, h, dout.p);
+                return;
+            }
+            if (step || mode == ADELIE_HIP_MULTI_AXPY) {
+                up(dr, static_cast<const T*>(a->r), nb * K);
+                ddcol.reserve(size_t(G)); ddlt.reserve(size_t(G));
+                if (a->n_dcol > 0) up(ddcol, a->dcol, a->n_dcol);
+                if (n_used > 0) up(ddlt, static_cast<const T*>(a->dlt), a->n_dcol);
+                const int32_t nz32 = int32_t(a->nz);
+                up(dnz, &nz32, 1);
+            }
+            if (mode == ADELIE_HIP_MULTI_AXPY) {
+                launch_multi_axpy_cols<T>(mv, ddcol.p, ddlt.p, dnz.p, T(a->sign), dr.p, s);
+                std::vector<T> h(static_cast<size_t>(nb * K));
+                finish(a->r, h, dr.p);
+                return;
+            }
+            if (step) {
+                const bool fused = mode == ADELIE_HIP_MULTI_FUSED_STEP;
+                const int vec = multi_step_vec<T>(mv);
+                const int64_t ld = fused ? mfused_part_ld(nb, vec) : mstep_slices(nb, vec);
+                if (a->nb_cols * ld > a->part_elems) throw make_core_error("STEP: part holds fewer than nb_cols * slices elements.");
+                up(dw, static_cast<const T*>(a->w), nb * K);
+                up(dpart, static_cast<const T*>(a->part), a->part_elems);
+                dcols.reserve(size_t(2 * G));
+                if (a->nb_cols > 0) up(dcols, a->cols, a->nb_cols);
+                int got = 0;
+                // the solve half of the fused launch: one singleton group, zero gradient, a penalty above it (set up as the
+                // PANEL_SOLVE mode of adelie_hip_group_piece_test sets up its block): it changes nothing
+                DevBuf<int32_t> dsb, dsz, dg0, ddesc, dvcol, dact, dsdcol;
+                DevBuf<int64_t> dvoff;
+                DevBuf<int8_t> disact;
+                DevBuf<T> dvars, dV, dxm, dspen, dbeta, dDb, dgb, dsdlt, dsdd;
+                DevBuf<CdBlkState<T>> dst;
+                if (fused) {
+                    const int32_t zero32 = 0, one32 = 1, g0[2] = {0, 1};
+                    const int64_t zero64 = 0;
+                    const int8_t zero8 = 0;
+                    const T one = T(1), zero = T(0);
+                    up(dsb, &zero32, 1); up(dsz, &one32, 1); up(dvoff, &zero64, 1); up(dg0, g0, 2);
+                    ddesc.reserve(size_t(GDESC_STRIDE));
+                    AHIP_CHECK(hipMemsetAsync(ddesc.p, 0, size_t(GDESC_STRIDE) * sizeof(int32_t), s));
+                    CdGrpBlkParams<T> p{};
+                    p.nv = 1;
+                    p.sbegin = dsb.p; p.ssize = dsz.p; p.voff = dvoff.p; p.blk_g0 = dg0.p; p.list = nullptr;
+                    p.nblk = 1;
+                    launch_grp_layout<T>(p, 1, ddesc.p, s);
+                    up(dvars, &one, 1); up(dV, &one, 1); up(dxm, &zero, 1); up(dspen, &one, 1); up(dbeta, &zero, 1);
+                    up(dvcol, &zero32, 1); up(disact, &zero8, 1);
+                    dact.reserve(3);
+                    AHIP_CHECK(hipMemsetAsync(dact.p, 0, 3 * sizeof(int32_t), s));
+                    CdBlkState<T> st0{};
+                    up(dst, &st0, 1);
+                    dDb.reserve(size_t(SLOT)); dgb.reserve(size_t(G)); dsdlt.reserve(size_t(G)); dsdd.reserve(size_t(G)); dsdcol.reserve(size_t(G));
+                    AHIP_CHECK(hipMemsetAsync(dDb.p, 0, size_t(SLOT) * sizeof(T), s));
+                    AHIP_CHECK(hipMemsetAsync(dgb.p, 0, size_t(G) * sizeof(T), s));
+                    AHIP_CHECK(hipMemsetAsync(dsdlt.p, 0, size_t(G) * sizeof(T), s));
+                    AHIP_CHECK(hipMemsetAsync(dsdd.p, 0, size_t(G) * sizeof(T), s));
+                    AHIP_CHECK(hipMemsetAsync(dsdcol.p, 0, size_t(G) * sizeof(int32_t), s));
+                    p.vars = dvars.p; p.xmean = dxm.p; p.beta = dbeta.p; p.is_active = disact.p; p.active_set = dact.p;
+                    p.l1 = T(1); p.l2 = T(0); p.newton_tol = T(1e-6); p.dbeta_tol = T(0);
+                    p.newton_max_iters = 10; p.max_active_size = 1; p.mark = 0;
+                    p.V = dV.p; p.spen = dspen.p; p.st = dst.p; p.vcol = dvcol.p;
+                    p.rot = 1; p.desc = ddesc.p;
+                    p.Dptr = dDb.p; p.gblk = dgb.p; p.dlt = dsdlt.p; p.dd = dsdd.p; p.dcol = dsdcol.p;
+                    got = launch_multi_panel_fused<T>(p, 0, mv, dw.p, dr.p, ddcol.p, ddlt.p, dnz.p, dcols.p, int(a->nb_cols), dpart.p, s);
+                } else {
+                    got = launch_multi_panel_step<T>(mv, dw.p, dr.p, ddcol.p, ddlt.p, dnz.p, dcols.p, int(a->nb_cols), dpart.p, s);
+                }
+                AHIP_CHECK(hipGetLastError());
+                info[0] = got; info[1] = vec;
+                std::vector<T> hr(static_cast<size_t>(nb * K)), hp(static_cast<size_t>(a->part_elems));
+                down(hr.data(), dr.p, hr.size() * sizeof(T));
+                down(hp.data(), dpart.p, hp.size() * sizeof(T));
+                AHIP_CHECK(hipStreamSynchronize(s));
+                if (got != ld) throw make_core_error("STEP: the launcher's leading dimension differs from the one part was sized for.");
+                std::memcpy(a->r, hr.data(), hr.size() * sizeof(T));
+                std::memcpy(a->part, hp.data(), hp.size() * sizeof(T));
+                return;
+            }
+            if (mode == ADELIE_HIP_MULTI_BLOCK_LISTS) {
+                DevBuf<int32_t> du, dsl, drs;
+                up(dcols, a->cols, a->nv); up(du, a->ulist, a->nv); up(dsl, a->slot, a->nv); up(drs, a->resp, a->nv);
+                launch_multi_block_lists(dcols.p, int(a->nv), int(K), du.p, dsl.p, drs.p, s);
+                AHIP_CHECK(hipGetLastError());
+                std::vector<int32_t> h(size_t(3 * a->nv));
+                down(h.data(), du.p, size_t(a->nv) * 4); down(h.data() + a->nv, dsl.p, size_t(a->nv) * 4); down(h.data() + 2 * a->nv, drs.p, size_t(a->nv) * 4);
+                AHIP_CHECK(hipStreamSynchronize(s));
+                std::memcpy(a->ulist, h.data(), size_t(a->nv) * 4);
+                std::memcpy(a->slot, h.data() + a->nv, size_t(a->nv) * 4);
+                std::memcpy(a->resp, h.data() + 2 * a->nv, size_t(a->nv) * 4);
+                return;
+            }
+            if (mode == ADELIE_HIP_MULTI_EXPAND || mode == ADELIE_HIP_MULTI_EXPAND_CROSS) {
+                DevBuf<int32_t> dsl, drs, dslc, drsc;
+                DevBuf<T> dC, dD;
+                up(dsl, a->slot, a->nv); up(drs, a->resp, a->nv);
+                up(dC, static_cast<const T*>(a->C), a->C_elems); up(dD, static_cast<const T*>(a->D), a->D_elems);
+                if (mode == ADELIE_HIP_MULTI_EXPAND) {
+                    for (int64_t q = 0; q < a->n_lsel; ++q)
+                        launch_multi_expand<T>(dC.p, a->ldc, dsl.p, drs.p, int(a->nv), int(a->lsel_list[q]), dD.p, a->ldd, s);
+                } else {
+                    up(dslc, a->slot_c, a->nc); up(drsc, a->resp_c, a->nc);
+                    launch_multi_expand_cross<T>(dC.p, a->ldc, dsl.p, drs.p, int(a->nv), dslc.p, drsc.p, int(a->nc), dD.p, a->ldd, s);
+                }
+                std::vector<T> h(static_cast<size_t>(a->D_elems));
+                finish(a->D, h, dD.p);
+                return;
+            }
+            if (mode == ADELIE_HIP_MULTI_TO_MAJOR || mode == ADELIE_HIP_MULTI_FROM_MAJOR) {
+                up(dv, static_cast<const T*>(a->v), nb * K); up(dout, static_cast<const T*>(a->out), nb * K);
+                if (mode == ADELIE_HIP_MULTI_TO_MAJOR) launch_multi_to_major<T>(dv.p, nb, int(K), dout.p, s);
+                else launch_multi_from_major<T>(dv.p, nb, int(K), dout.p, s);
+                std::vector<T> h(static_cast<size_t>(nb * K));
+                finish(a->out, h, dout.p);
+                return;
+            }
+            // BATCH_PICK
+            up(dv, static_cast<const T*>(a->v), pb * K); up(dout, static_cast<const T*>(a->out), pb);
+            const T scale = T(a->sign);
+            up(dr, &scale, 1);
+            if (a->w) up(dw, static_cast<const T*>(a->w), pb);
+            launch_batch_pick<T>(dv.p, pb, int(K), int(a->lsel), dr.p, a->w ? dw.p : nullptr, dout.p, s);
+            std::vector<T> h(static_cast<size_t>(pb));
+            finish(a->out, h, dout.p);
+        };
+        if (a->dtype == ADELIE_HIP_F64) body(double{});
+        else body(float{});
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return 1;
+    }
+    return 0;
+}
+
 // One of the two places where the path solver touches the covariance matrix A, through the dispatcher the solver calls
 // (design_ops.hpp: raw_cov_gather / raw_cov_grad), on either storage (tests; include/adelie_hip.h has the arguments).  Everything
 // the kernels index by is checked here before anything is launched.

@@ -1030,6 +1030,83 @@ typedef struct adelie_hip_group_piece {
 } adelie_hip_group_piece;
 int adelie_hip_group_piece_test(const adelie_hip_group_piece* a, int64_t* info);
 
+/* One launcher of the multi-response kernels (kernels_multi.hip) on caller-supplied inputs, exactly as the solver calls it (tests):
+ * uploads, builds the view [1 (x) I_K, X (x) I_K] itself, launches on one stream, synchronises, downloads.  No design handle.
+ * Every field is 8 bytes wide; value arrays (`void*`) are in `dtype`, scalars cross as double.  Everything a kernel indexes by is
+ * checked against the sizes given here before anything is launched: a bad table is refused with an error string, nothing runs
+ * and no output is written.
+ *
+ * The view (SWEEP, STEP, FUSED_STEP, AXPY): nb rows, pb base columns, K responses, icpt (0 / 1) a leading column of ones.  Dense
+ * base: X (X_elems values, pad rows included) is uploaded to a 256-byte aligned allocation at element x_off (0 .. 64); column j
+ * starts at element j ld, ld >= nb, (pb - 1) ld + nb <= X_elems.  An ld that is no multiple of the 16-byte vector, or an x_off
+ * that breaks 16-byte alignment, selects the scalar-load kernels.  2-bit base (bits != null; X ignored): bits (bits_elems bytes),
+ * ldb >= (nb + 3) / 4 bytes per column, (pb - 1) ldb + (nb + 3) / 4 <= bits_elems, impute (pb).  Vectors of nb K values are
+ * response-major (element (i, l) at l nb + i); column index c = u K + l is (extended feature u, response l), u < pb + icpt.
+ *
+ * mode  SWEEP: launch_multi_sweep, out (in/out, (pb + icpt) K) = x_u . v_l; v (nb K) is placed v_off (0 .. 64) elements behind a
+ *         256-byte boundary.  info = {variant (0 plain, 1 four waves, 2 staged through LDS), rows per load, responses per chunk,
+ *         features per workgroup, feature blocks, row splits, rows per split, response chunks}.
+ *       STEP: launch_multi_panel_step.  r (in/out) -= sum_{m < min(nz, 128)} dlt[m] x(dcol[m]) with nz read on the device
+ *         (dcol / dlt hold n_dcol >= min(nz, 128) entries); part (in/out, part_elems >= nb_cols * slices, pre-filled by the
+ *         caller, comes back whole): part[c * slices + s] = x(cols[c])[slice s] . (w r)[slice s], c < nb_cols <= 256.
+ *         info = {slices = leading dimension of part, rows per load}.
+ *       FUSED_STEP: launch_multi_panel_fused, the same step (nb_cols <= 128) beside a group solve of one singleton group with
+ *         zero gradient and a penalty above it, which changes nothing.  info as STEP (leading dimension = slices rounded up to
+ *         whole 16-wave workgroups).
+ *       BLOCK_LISTS: launch_multi_block_lists of cols (nv <= 128) -> ulist, slot, resp (in/out, nv each).
+ *       EXPAND: launch_multi_expand, D (in/out, D_elems, leading dimension ldd >= nv) from C (C_elems, ldc) through slot / resp
+ *         (nv, inputs) for every lsel in lsel_list (n_lsel calls in sequence on the one output).
+ *       EXPAND_CROSS: launch_multi_expand_cross, D (nr x nc, ldd >= nr) from C through slot / resp (rows, nr = nv) and slot_c /
+ *         resp_c (columns, nc).
+ *       AXPY: launch_multi_axpy_cols, r (in/out, nb K) += sign * sum_{m < nz} dlt[m] x(dcol[m]), nz <= n_dcol read on the device.
+ *       TO_MAJOR / FROM_MAJOR: launch_multi_{to,from}_major of v (nb K) into out (in/out, nb K).
+ *       BATCH_PICK: launch_batch_pick, out (in/out, pb) [u] = v[u K + lsel] - (w ? sign * w[u] : 0); v holds pb K values, w pb.
+ * The entry is additive and changes the layout of no existing structure: ADELIE_HIP_ABI_VERSION stays as it is. */
+enum adelie_hip_multi_piece_mode {
+    ADELIE_HIP_MULTI_SWEEP = 0, ADELIE_HIP_MULTI_STEP = 1, ADELIE_HIP_MULTI_FUSED_STEP = 2, ADELIE_HIP_MULTI_BLOCK_LISTS = 3,
+    ADELIE_HIP_MULTI_EXPAND = 4, ADELIE_HIP_MULTI_EXPAND_CROSS = 5, ADELIE_HIP_MULTI_AXPY = 6, ADELIE_HIP_MULTI_TO_MAJOR = 7,
+    ADELIE_HIP_MULTI_FROM_MAJOR = 8, ADELIE_HIP_MULTI_BATCH_PICK = 9
+};
+typedef struct adelie_hip_multi_piece {
+    int64_t dtype, mode;
+    /* the view */
+    int64_t nb, pb, K, icpt;
+    const void* X;
+    int64_t X_elems, x_off, ld;
+    const uint8_t* bits;
+    int64_t bits_elems, ldb;
+    const void* impute;
+    /* vectors */
+    const void* v;
+    int64_t v_off;
+    void* out;
+    const void* w;
+    void* r;
+    /* lists */
+    const int32_t* dcol;
+    const void* dlt;
+    int64_t n_dcol, nz;
+    const int32_t* cols;
+    int64_t nb_cols;
+    void* part;
+    int64_t part_elems;
+    double sign;
+    /* BLOCK_LISTS, EXPAND, EXPAND_CROSS */
+    int64_t nv, nc;
+    int32_t* ulist;
+    int32_t* slot;
+    int32_t* resp;
+    const int32_t* slot_c;
+    const int32_t* resp_c;
+    const void* C;
+    int64_t C_elems, ldc;
+    void* D;
+    int64_t D_elems, ldd;
+    const int64_t* lsel_list;
+    int64_t n_lsel, lsel;
+} adelie_hip_multi_piece;
+int adelie_hip_multi_piece_test(const adelie_hip_multi_piece* a, int64_t* info);
+
 /* One of the two places where the path solver touches the covariance matrix A (dense or kept sparse), through exactly the launcher
  * the solver calls (tests): uploads, launches on A's stream, synchronises, downloads.  Column lists must be distinct and in [0, p).
  *   ADELIE_HIP_COV_PIECE_GATHER: the copy of A[S, S] into the screen Gram matrix for the new screen values [pos0, nv) of the
