@@ -290,7 +290,7 @@ HIP_SYMBOLS = [
     "design_device", "design_stream",
     "design_cmul", "design_ctmul", "design_bmul", "design_btmul", "design_bmul_cols", "design_btmul_cols", "design_mul", "design_mul_batch", "design_cov",
     "design_sq_mul", "design_sp_tmul",
-    "design_create_cov_dense", "design_create_cov_csc", "design_create_cov_lazy", "design_cov_bmul", "design_cov_mul", "design_cov_to_dense", "gaussian_cov_solve",
+    "design_create_cov_dense", "design_create_cov_csc", "design_create_cov_lazy", "design_cov_bmul", "design_cov_mul", "design_cov_mul_batch", "design_cov_to_dense", "gaussian_cov_solve",
     "glm_cox_create", "glm_cox_destroy", "glm_cox_eval",
     "grpnet_solve", "grpnet_solve_many", "result_destroy", "result_size", "result_copy", "result_scalar", "result_error", "result_sync",
     "bench_sweep", "filter_sweep_test", "block_build_test", "group_piece_test", "multi_piece_test", "cov_piece_test",
@@ -413,6 +413,7 @@ class Backend:
         sig("design_create_cov_lazy", ci, [vp, p(vp)])
         sig("design_cov_bmul", ci, [vp, vp, i64, vp, vp, i64, vp])
         sig("design_cov_mul", ci, [vp, vp, vp, i64, vp])
+        sig("design_cov_mul_batch", ci, [vp, i64, vp, vp, vp, vp, vp])
         sig("design_cov_to_dense", ci, [vp, i64, i64, vp])
         sig("result_destroy", ci, [vp])
         sig("result_size", i64, [vp, ci])

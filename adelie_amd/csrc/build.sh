@@ -13,7 +13,7 @@ pids=()
 for f in kernels_cons kernels_append kernels_eig kernels_strip kernels_cov kernels_cov_sparse kernels_sparse kernels_sweep kernels_filter kernels_convert kernels_gram kernels_cd kernels_cd_lasso kernels_cd_block kernels_cd_block_group kernels_cd_panel kernels_multi kernels_glm kernels_cox kernels_factor kernels_relu kernels_relu_sparse kernels_phased kernels_css kernels_bvls kernels_pinball kernels_pinball_sparse kernels_qp_full design solver; do
   src="$HERE/$f.hip"; obj="$OBJ/$f.o"
   if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/kernels.hpp" -nt "$obj" ] || [ "$HERE/common.hpp" -nt "$obj" ] || [ "$HERE/dev_array_host.hpp" -nt "$obj" ] \
-     || [ "$HERE/accessors.hpp" -nt "$obj" ] || [ "$HERE/wavered.hpp" -nt "$obj" ] || { { [ "$f" = kernels_sweep ] || [ "$f" = kernels_filter ] || [ "$f" = kernels_convert ]; } && { [ "$HERE/sweep_common.hpp" -nt "$obj" ] || [ "$HERE/sweep_shape.hpp" -nt "$obj" ]; }; } || [ "$HERE/gram_common.hpp" -nt "$obj" ] || [ "$HERE/gram_shape.hpp" -nt "$obj" ] || [ "$HERE/multi_shape.hpp" -nt "$obj" ] || [ "$HERE/relu_shape.hpp" -nt "$obj" ] || [ "$HERE/relu_sparse_shape.hpp" -nt "$obj" ] || { { [ "$f" = design ] || [ "$f" = kernels_phased ]; } && { [ "$HERE/phased_decode_host.hpp" -nt "$obj" ] || [ "$HERE/snp_decode_host.hpp" -nt "$obj" ]; }; } || { [ "$f" = design ] && { [ "$HERE/csc_build_host.hpp" -nt "$obj" ] || [ "$HERE/design_csc.hpp" -nt "$obj" ] || [ "$HERE/design_snp.hpp" -nt "$obj" ]; }; } || { { [ "$f" = design ] || [ "$f" = kernels_cov_sparse ]; } && [ "$HERE/cov_csc_host.hpp" -nt "$obj" ]; } || [ "$HERE/blk_solve_body.hpp" -nt "$obj" ] || [ "$HERE/grp_solve_body.hpp" -nt "$obj" ] || [ "$HERE/cox.hpp" -nt "$obj" ] || [ "$HERE/filter_host.hpp" -nt "$obj" ] || { [ "$f" = solver ] && [ "$HERE/screen_reads_host.hpp" -nt "$obj" ]; } || [ "$HERE/shadow_kind_host.hpp" -nt "$obj" ] || [ "$HERE/pieces_host.hpp" -nt "$obj" ] || [ "$HERE/cd_fit_body.hpp" -nt "$obj" ] || { { [ "$f" = kernels_bvls ] || [ "$f" = kernels_pinball ]; } && { [ "$HERE/cd_screen_driver.hpp" -nt "$obj" ] || [ "$HERE/cd_screen_host.hpp" -nt "$obj" ]; }; } || { [ "$f" = kernels_qp_full ] && [ "$HERE/qp_full_body.hpp" -nt "$obj" ]; } || { { [ "$f" = design ] || [ "$f" = solver ]; } && [ "$HERE/design_ops.hpp" -nt "$obj" ]; } || { [ "$f" = solver ] && [ -n "$(find "$HERE" -name "solver_*.hpp" -newer "$obj" 2>/dev/null)" ]; } || [ "$HERE/../../include/adelie_hip.h" -nt "$obj" ]; then
+     || [ "$HERE/accessors.hpp" -nt "$obj" ] || [ "$HERE/wavered.hpp" -nt "$obj" ] || { { [ "$f" = kernels_sweep ] || [ "$f" = kernels_filter ] || [ "$f" = kernels_convert ]; } && { [ "$HERE/sweep_common.hpp" -nt "$obj" ] || [ "$HERE/sweep_shape.hpp" -nt "$obj" ]; }; } || [ "$HERE/gram_common.hpp" -nt "$obj" ] || [ "$HERE/gram_shape.hpp" -nt "$obj" ] || [ "$HERE/multi_shape.hpp" -nt "$obj" ] || [ "$HERE/relu_shape.hpp" -nt "$obj" ] || [ "$HERE/relu_sparse_shape.hpp" -nt "$obj" ] || { { [ "$f" = design ] || [ "$f" = kernels_phased ]; } && { [ "$HERE/phased_decode_host.hpp" -nt "$obj" ] || [ "$HERE/snp_decode_host.hpp" -nt "$obj" ]; }; } || { [ "$f" = design ] && { [ "$HERE/csc_build_host.hpp" -nt "$obj" ] || [ "$HERE/design_csc.hpp" -nt "$obj" ] || [ "$HERE/design_snp.hpp" -nt "$obj" ]; }; } || { { [ "$f" = design ] || [ "$f" = kernels_cov_sparse ]; } && [ "$HERE/cov_csc_host.hpp" -nt "$obj" ]; } || { { [ "$f" = design ] || [ "$f" = kernels_cov_sparse ] || [ "$f" = kernels_cov ]; } && [ "$HERE/cov_batch_host.hpp" -nt "$obj" ]; } || [ "$HERE/blk_solve_body.hpp" -nt "$obj" ] || [ "$HERE/grp_solve_body.hpp" -nt "$obj" ] || [ "$HERE/cox.hpp" -nt "$obj" ] || [ "$HERE/filter_host.hpp" -nt "$obj" ] || { [ "$f" = solver ] && [ "$HERE/screen_reads_host.hpp" -nt "$obj" ]; } || [ "$HERE/shadow_kind_host.hpp" -nt "$obj" ] || [ "$HERE/pieces_host.hpp" -nt "$obj" ] || [ "$HERE/cd_fit_body.hpp" -nt "$obj" ] || { { [ "$f" = kernels_bvls ] || [ "$f" = kernels_pinball ]; } && { [ "$HERE/cd_screen_driver.hpp" -nt "$obj" ] || [ "$HERE/cd_screen_host.hpp" -nt "$obj" ]; }; } || { [ "$f" = kernels_qp_full ] && [ "$HERE/qp_full_body.hpp" -nt "$obj" ]; } || { { [ "$f" = design ] || [ "$f" = solver ]; } && [ "$HERE/design_ops.hpp" -nt "$obj" ]; } || { [ "$f" = solver ] && [ -n "$(find "$HERE" -name "solver_*.hpp" -newer "$obj" 2>/dev/null)" ]; } || [ "$HERE/../../include/adelie_hip.h" -nt "$obj" ]; then
     timeout 600 $HIPCC $FLAGS -c "$src" -o "$obj" &
     pids+=($!)
   fi

@@ -10,6 +10,7 @@
 #include "design_ops.hpp"
 #include "csc_build_host.hpp"
 #include "cov_csc_host.hpp"
+#include "cov_batch_host.hpp"
 #include "phased_decode_host.hpp"
 #include "snp_decode_host.hpp"
 
@@ -749,6 +750,61 @@ void op_cov_mul(adelie_hip_design* d, const int64_t* indices, const T* values, i
     AHIP_CHECK(hipMemcpyAsync(out, dout, size_t(d->p) * sizeof(T), hipMemcpyDeviceToHost, s));
     AHIP_CHECK(hipStreamSynchronize(s));
 }
+// out[l, :] = v - A beta_l (v null: A beta_l) for the L rows of a validated CSR matrix, cov_batch_chunk_rows rows at a time: the
+// chunk's part of B (kept sparse) or its union plan (dense storage; cov_batch_host.hpp) goes up, the batches run, and the
+// finished rows come down, so the device scratch is one chunk's whatever L is.
+template <class T>
+void op_cov_mul_batch(adelie_hip_design* d, int64_t L, const int64_t* indptr, const int64_t* indices, const T* values, const T* v,
+                      T* out) {
+    set_device(d);
+    hipStream_t s = d->stream;
+    const int64_t p = d->p, chunk = cov_batch_chunk_rows(p, sizeof(T));
+    constexpr int Lb = kCovBatchLb;
+    T* dv = nullptr;
+    if (v) {
+        dv = scratch<T>(d->s_n2, size_t(p));
+        AHIP_CHECK(hipMemcpyAsync(dv, v, size_t(p) * sizeof(T), hipMemcpyHostToDevice, s));
+    }
+    T* dout = scratch<T>(d->s_p1, size_t(std::min(chunk, L)) * size_t(p));
+    CovBatchPlan<T> plan;
+    for (int64_t l0 = 0; l0 < L; l0 += chunk) {
+        const int64_t lc = std::min(chunk, L - l0);
+        if (d->cov_csc()) {
+            const int64_t e0 = indptr[l0], ne = indptr[l0 + lc] - e0;
+            int64_t* dptr = scratch<int64_t>(d->s_idx1, size_t(lc) + 1);
+            int64_t* dind = scratch<int64_t>(d->s_idx2, size_t(ne));
+            T* dval = scratch<T>(d->s_n1, size_t(ne));
+            T* dw = scratch<T>(d->s_work, size_t(p) * Lb);
+            AHIP_CHECK(hipMemcpyAsync(dptr, indptr + l0, size_t(lc + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            if (ne) {
+                AHIP_CHECK(hipMemcpyAsync(dind, indices + e0, size_t(ne) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+                AHIP_CHECK(hipMemcpyAsync(dval, values + e0, size_t(ne) * sizeof(T), hipMemcpyHostToDevice, s));
+            }
+            for (int64_t b0 = 0; b0 < lc; b0 += Lb) {
+                const int rows = int(std::min<int64_t>(Lb, lc - b0));
+                int64_t max_row = 0;
+                for (int r = 0; r < rows; ++r) max_row = std::max(max_row, indptr[l0 + b0 + r + 1] - indptr[l0 + b0 + r]);
+                launch_cov_csc_fill_w_batch<T>(dptr + b0, dind, dval, e0, rows, max_row, dw, p, s);
+                launch_cov_csc_coldot_batch<T>(d->cov_csc_view<T>(), dw, dv, rows, dout + size_t(b0) * size_t(p), s);
+            }
+        } else {
+            cov_batch_plan_unions<T>(l0, lc, indptr, indices, values, plan);
+            const size_t nu = plan.ucols.size();
+            int64_t* duptr = scratch<int64_t>(d->s_idx1, plan.uptr.size());
+            int32_t* ducols = scratch<int32_t>(d->s_idx2, nu);
+            T* dcoef = scratch<T>(d->s_n1, nu * Lb);
+            AHIP_CHECK(hipMemcpyAsync(duptr, plan.uptr.data(), plan.uptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            if (nu) {
+                AHIP_CHECK(hipMemcpyAsync(ducols, plan.ucols.data(), nu * sizeof(int32_t), hipMemcpyHostToDevice, s));
+                AHIP_CHECK(hipMemcpyAsync(dcoef, plan.coef.data(), nu * Lb * sizeof(T), hipMemcpyHostToDevice, s));
+            }
+            launch_cov_mul_batch<T>(static_cast<const T*>(d->X), d->ld, p, duptr, ducols, dcoef, dv, lc, dout, s);
+        }
+        AHIP_CHECK(hipGetLastError());
+        AHIP_CHECK(hipMemcpyAsync(out + size_t(l0) * size_t(p), dout, size_t(lc) * size_t(p) * sizeof(T), hipMemcpyDeviceToHost, s));
+        AHIP_CHECK(hipStreamSynchronize(s)); // (the next chunk overwrites the plan and the scratch)
+    }
+}
 template <class T>
 void op_cov_to_dense(adelie_hip_design* d, int64_t i, int64_t q, T* out) {
     set_device(d);
@@ -993,6 +1049,18 @@ int adelie_hip_design_cov_mul(adelie_hip_design* d, const int64_t* indices, cons
     for (int64_t k = 0; k < ni; ++k)
         if (indices[k] < 0 || indices[k] >= d->p) throw make_core_error("mul(): index out of range.");
     DTYPE_DISPATCH(d, op_cov_mul<T>(d, indices, (const T*)values, ni, (T*)out))
+    ABI_CATCH
+}
+int adelie_hip_design_cov_mul_batch(adelie_hip_design* d, int64_t L, const int64_t* indptr, const int64_t* indices, const void* values,
+                                    const void* v, void* out) {
+    ABI_TRY
+    if (!d) throw make_core_error("null argument.");
+    if (!d->cov) throw make_core_error("mul_batch: A must be a covariance matrix (matrix.dense(method=\"cov\") or kept sparse), not a design matrix.");
+    if (const char* e = cov_batch_validate(L, indptr, indices, values, d->p)) throw make_core_error(e);
+    if (L > 0) {
+        if (!out) throw make_core_error("null argument.");
+        DTYPE_DISPATCH(d, op_cov_mul_batch<T>(d, L, indptr, indices, (const T*)values, (const T*)v, (T*)out))
+    }
     ABI_CATCH
 }
 int adelie_hip_design_cov_to_dense(adelie_hip_design* d, int64_t i, int64_t q, void* out) {

@@ -793,6 +793,20 @@ void launch_cov_csc_gather(const CovCscView<T>& A, const int32_t* vcol, int32_t 
 // out (q, q) column-major on the device = A[i:i+q, i:i+q]
 template <class T>
 void launch_cov_csc_to_dense(const CovCscView<T>& A, int64_t i, int64_t q, T* out, hipStream_t s);
+
+// Lambda-batched v - A beta_l (adelie_hip_design_cov_mul_batch; cov_batch_host.hpp has the batch width, the chunking and the
+// dense plan).  Dense storage: the rows [0, rows) of a chunk in one launch, out (rows, p) with rows contiguous, v null for the
+// product alone.  Kept sparse: one batch of rows <= kCovBatchLb per launch; fill_w_batch zeroes the (p, kCovBatchLb) block w and
+// writes the batch's rows into it (indptr: the batch's rows + 1 pointers, ebase: the position of the uploaded chunk's first
+// entry; max_row: the longest of the batch's rows).
+template <class T>
+void launch_cov_mul_batch(const T* S, int64_t lda, int64_t p, const int64_t* uptr, const int32_t* ucols, const T* coef, const T* v,
+                          int64_t rows, T* out, hipStream_t s);
+template <class T>
+void launch_cov_csc_fill_w_batch(const int64_t* indptr, const int64_t* indices, const T* values, int64_t ebase, int rows,
+                                 int64_t max_row, T* w, int64_t p, hipStream_t s);
+template <class T>
+void launch_cov_csc_coldot_batch(const CovCscView<T>& A, const T* w, const T* base, int rows, T* out, hipStream_t s);
 template <class T> void launch_copy2d(const T* src, int64_t lds, T* dst, int64_t ldd, int64_t rows, int64_t cols, hipStream_t s);
 // vars[pos0 + a] = max(C[(pos0+a)*(ldc+1)], 0) for a < cnt   (gs == 1 groups)
 // Appending new screen groups to the device mirrors (solver.hip::device_append_screen): ONE packed upload + one scatter

@@ -9,6 +9,7 @@
 // A matrix kept sparse (adelie_hip_design_create_cov_csc) has the same four operations over its stored entries in
 // kernels_cov_sparse.hip; design_ops.hpp (raw_cov_gather / raw_cov_grad) and design.hip (op_cov_*) dispatch on the storage.
 #include "kernels.hpp"
+#include "cov_batch_host.hpp"
 
 namespace ahip {
 
@@ -76,7 +77,49 @@ __global__ __launch_bounds__(256) void cov_grad_kernel(const T* __restrict__ S, 
     grad[j] = v[j] - acc;
 }
 
+// Lambda-batched mul (adelie_hip_design_cov_mul_batch): out[b LB + r, j] = v[j] - sum_k coef[k, r] * S[j + ucols[k] * lda] over
+// the ascending union ucols[uptr[b] .. uptr[b + 1]) of the column indices of batch b's LB rows (cov_batch_host.hpp plans it), or
+// the sum alone when v is null.  blockIdx.y is the batch.  Row r's sum is cov_mul_kernel's expression in cov_mul_kernel's
+// order with terms of coefficient exactly zero in between, which leave a finite sum as it is: the bits of a single mul.  S[..]
+// is loaded once for the LB rows.
+// LB = 8, from the compile output for gfx950 (-Rpass-analysis=kernel-resource-usage), f64: LB 4 / 8 / 16 take 30 / 34 / 46
+// VGPRs (f32 at LB 8: 30), all at the full 8 waves per SIMD and without scratch memory, so registers do not decide here.
+// The batch width is shared with the kept-sparse kernel (kernels_cov_sparse.hip), where 16 rows fall to 5 waves per SIMD; and
+// the grid is blocks x batches, which 16 rows per batch would halve: 100 rows at p = 20 000 are 79 x 13 blocks at LB = 8.
+template <class T, int LB>
+__global__ __launch_bounds__(256) void cov_mul_batch_kernel(const T* __restrict__ S, int64_t lda, int64_t p,
+                                                            const int64_t* __restrict__ uptr, const int32_t* __restrict__ ucols,
+                                                            const T* __restrict__ coef, const T* __restrict__ v, int64_t rows,
+                                                            T* __restrict__ out) {
+    const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (j >= p) return;
+    const int64_t r0 = int64_t(blockIdx.y) * LB;
+    const int64_t k1 = uptr[blockIdx.y + 1];
+    T acc[LB];
+#pragma unroll
+    for (int r = 0; r < LB; ++r) acc[r] = T(0);
+#pragma unroll 4
+    for (int64_t k = uptr[blockIdx.y]; k < k1; ++k) {
+        const T s = S[j + int64_t(ucols[k]) * lda];
+        const T* __restrict__ c = coef + k * LB;
+#pragma unroll
+        for (int r = 0; r < LB; ++r) acc[r] = fma(c[r], s, acc[r]); // (spelled out: cov_mul_kernel's sum is contracted to this)
+    }
+#pragma unroll
+    for (int r = 0; r < LB; ++r)
+        if (r0 + r < rows) out[(r0 + r) * p + j] = v ? v[j] - acc[r] : acc[r];
+}
+
 } // namespace
+
+template <class T>
+void launch_cov_mul_batch(const T* S, int64_t lda, int64_t p, const int64_t* uptr, const int32_t* ucols, const T* coef, const T* v,
+                          int64_t rows, T* out, hipStream_t s) {
+    if (rows <= 0 || p <= 0) return;
+    const int64_t batches = (rows + kCovBatchLb - 1) / kCovBatchLb; // <= kCovBatchMaxBatches: far below grid.y's 65535
+    hipLaunchKernelGGL((cov_mul_batch_kernel<T, kCovBatchLb>), dim3(unsigned((p + 255) / 256), unsigned(batches)), dim3(256), 0, s, S,
+                       lda, p, uptr, ucols, coef, v, rows, out);
+}
 
 template <class T>
 void launch_cov_gather(const T* S, int64_t lda, int tr, const int32_t* vcol, int32_t nv, int32_t pos0, int32_t N, T* C,
@@ -110,7 +153,9 @@ void launch_cov_grad(const T* S, int64_t lda, int64_t p, const T* v, const int32
                                      T*, hipStream_t);                                                                  \
     template void launch_cov_mul<T>(const T*, int64_t, int64_t, const int64_t*, const T*, int64_t, T*, hipStream_t);    \
     template void launch_cov_grad<T>(const T*, int64_t, int64_t, const T*, const int32_t*, const T*, const int32_t*, T*, \
-                                     hipStream_t);
+                                     hipStream_t);                                                                      \
+    template void launch_cov_mul_batch<T>(const T*, int64_t, int64_t, const int64_t*, const int32_t*, const T*, const T*, int64_t, \
+                                          T*, hipStream_t);
 INST(double)
 INST(float)
 #undef INST

@@ -1,8 +1,9 @@
 """Post-fit helpers — mirrors the numeric parts of ``adelie.diagnostic``: ``predict`` (reference
 ``adelie/diagnostic.py:30-121``), ``coefficient`` (``:577-646``), ``objective`` (``:124-278``, the parity fall-back
 metric of the reference's own tests, ``tests/test_solver.py:447-466``) and the KKT diagnostics ``residuals`` /
-``gradients`` / ``gradient_norms`` / ``gradient_scores`` / ``diagnostic(state)`` (``:279-574,1248-1415``): the L
-gradient sweeps ``X^T r_l`` go through one ABI call that streams the resident design once per eight vectors.
+``gradients`` / ``gradient_norms`` / ``gradient_scores`` / ``diagnostic(state)`` (``:279-574,1126-1170,1248-1415``): the L
+gradient sweeps ``X^T r_l`` of a naive state, and the L products ``v - A beta_l`` of a covariance state, go through one ABI
+call each that streams the resident matrix once per eight vectors.
 Plotting is out of scope."""
 import logging
 
@@ -230,6 +231,52 @@ class DiagnosticNaive:
                                                penalty=penalty)
 
 
+def _cov_gradients(A, betas, v):
+    """``v - A beta_l`` for every row of ``betas``, ``(L, p)`` in the matrix's dtype: one lambda-batched product on the device
+    (``A.mul_batch``) when the library has ``adelie_hip_design_cov_mul_batch``, one ``A.mul`` per row against an older
+    library.  Both give the same bits."""
+    dtype = A.dtype
+    v = np.ascontiguousarray(v, dtype=dtype)
+    B = betas if isinstance(betas, csr_matrix) else csr_matrix(np.atleast_2d(betas))
+    backend = getattr(A, "_backend", None)
+    if hasattr(A, "mul_batch") and backend is not None and backend.has("design_cov_mul_batch"):
+        return A.mul_batch(B.astype(dtype, copy=False), v)
+    L, p = B.shape
+    grads = np.empty((L, p), dtype=dtype)
+    for l in range(L):
+        row = B[l]
+        A.mul(row.indices, row.data, grads[l])
+    return v[None] - grads
+
+
+class DiagnosticCov:
+    """The quantities ``adelie.diagnostic.DiagnosticCov`` computes for a solved covariance state (reference
+    ``diagnostic.py:1126-1170``): the gradients ``v - A beta_l`` along the path, ``(L, p)``, their group norms and the KKT
+    scores.  The reference multiplies once per lambda; here the L products are one call that reads ``A`` once per eight
+    lambdas.  A state with constraint objects reaches ``gradient_norms``' refusal.  The plotting methods of the reference class
+    are not provided."""
+
+    def __init__(self, state):
+        self.state = state
+        self.betas = state.betas
+        self.duals = getattr(state, "duals", None)
+        constraints = getattr(state, "constraints", None)
+        if constraints is not None and all(c is None for c in constraints):
+            constraints = None
+        self._args = {"constraints": constraints, "groups": state.groups, "penalty": state.penalty}
+        self.gradients = _cov_gradients(state.A, self.betas, state.v)
+        self.gradient_norms = gradient_norms(grads=self.gradients, betas=self.betas, duals=self.duals, lmdas=state.lmdas,
+                                             constraints=constraints, groups=state.groups, alpha=state.alpha,
+                                             penalty=state.penalty)
+        self.gradient_scores = gradient_scores(grad_norms=self.gradient_norms, lmdas=state.lmdas, alpha=state.alpha,
+                                               penalty=state.penalty)
+
+
 def diagnostic(state):
-    """Diagnostic object of a solved state (reference ``diagnostic.py:1393-1415``; only naive states exist here)."""
+    """Diagnostic object of a solved state (reference ``diagnostic.py:1393-1415``): :class:`DiagnosticCov` for a covariance
+    state, :class:`DiagnosticNaive` otherwise."""
+    from . import state as _state
+
+    if isinstance(state, _state.gaussian_cov_base):
+        return DiagnosticCov(state)
     return DiagnosticNaive(state)

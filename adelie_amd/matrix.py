@@ -1973,6 +1973,44 @@ class _CovMatrix:
         if buf is not out:
             out[...] = buf
 
+    def mul_batch(self, B, v=None, out=None):
+        """``out[l] = v - A B[l]`` for every row of ``B`` (``A B[l]`` without ``v``): the ``(L, p)`` array that one
+        :meth:`mul` per row and a subtraction in this matrix's dtype would give, bit for bit, from one C-ABI call
+        (``adelie_hip_design_cov_mul_batch``) that reads the matrix once per eight rows.  ``B`` is a ``csr_matrix`` or a dense
+        ``(L, p)`` array; a CSR operand is brought to canonical form first (indices sorted, duplicates summed).  ``out``: a
+        C-contiguous ``(L, p)`` array of this matrix's dtype to write into and return instead of a new one."""
+        r = self._cols
+        if not self._backend.has("design_cov_mul_batch"):
+            raise RuntimeError(f"{self._backend.path}: no adelie_hip_design_cov_mul_batch -- rebuild the library.")
+        if isinstance(B, np.ndarray):
+            self._chk(B.ndim == 2, "mul_batch() is given inconsistent inputs! B must be (L, p).")
+            B = csr_matrix(B)
+        elif isinstance(B, csr_matrix):
+            if not B.has_canonical_format:
+                B = B.copy()
+                B.sum_duplicates()
+                B.sort_indices()
+        else:
+            raise RuntimeError("B is not one of np.ndarray or scipy.sparse.csr_matrix.")
+        L, c = B.shape
+        nv = r if v is None else len(v)
+        self._chk(c == r and nv == r,
+                  "mul_batch() is given inconsistent inputs! Invoked check_mul_batch(L=%d, c=%d, v=%d, r=%d, c=%d)" % (L, c, nv, r, r))
+        if np.dtype(B.dtype).type not in (np.float32, np.float64):
+            raise RuntimeError("B must have dtype float32 or float64.")
+        indptr = np.ascontiguousarray(B.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(B.indices, dtype=np.int64)
+        values = np.ascontiguousarray(B.data, dtype=self.dtype)
+        vv = None if v is None else np.ascontiguousarray(v, dtype=self.dtype)
+        if out is None:
+            out = np.empty((L, r), dtype=self.dtype)
+        self._chk(isinstance(out, np.ndarray) and out.shape == (L, r) and out.dtype == self.dtype and out.flags.c_contiguous,
+                  "mul_batch() is given inconsistent inputs! out must be a C-contiguous (L, p) array of the matrix's dtype.")
+        self._backend.check(self._backend.fn("design_cov_mul_batch")(
+            self._handle, L, indptr.ctypes.data, indices.ctypes.data, values.ctypes.data, None if vv is None else vv.ctypes.data,
+            out.ctypes.data))
+        return out
+
     def to_dense(self, i, p, out):
         """``out = A[i:i+p, i:i+p]`` (``matrix_cov_dense.ipp:64-74``); ``out`` is ``(p, p)`` F-ordered."""
         r = self._cols

@@ -611,6 +611,19 @@ int adelie_hip_design_cov_bmul(adelie_hip_design* A, const int64_t* subset, int6
                                const void* values, int64_t n_indices, void* out);
 /* MatrixCovBase::mul (:43-62): out = sum_i values[i] * A[indices[i], :] */
 int adelie_hip_design_cov_mul(adelie_hip_design* A, const int64_t* indices, const void* values, int64_t n_indices, void* out);
+/* MatrixCovBase::mul for many sparse vectors at once (what DiagnosticCov needs, reference diagnostic.py:1126-1170): for the L
+ * rows beta_l of a CSR matrix (int64 indices; inside a row ascending and distinct) computes
+ *   out[l, :] = v - A beta_l        (v == NULL: A beta_l)
+ * into the (L, p) array `out`, rows contiguous; values, v and out in the handle's dtype.  Row l has the bits of
+ * v - adelie_hip_design_cov_mul(beta_l), the subtraction in the handle's dtype, for every finite A, whichever rows share its
+ * batch.  The rows are multiplied eight at a time: a matrix kept sparse is read once per eight rows, dense storage once per
+ * column index of the eight rows' union.  The device scratch is that of a bounded number of rows (at most 128, fewer when p is
+ * large), not of L.  Accepts covariance handles of both storages and refuses any other design; indptr / indices that are out of
+ * range or not ascending inside a row are refused on the host before anything is uploaded.  L == 0 is a no-op.  Errors other
+ * than a null argument start with "mul_batch:".
+ * The entry is additive and changes the layout of no existing structure: ADELIE_HIP_ABI_VERSION stays as it is. */
+int adelie_hip_design_cov_mul_batch(adelie_hip_design* A, int64_t L, const int64_t* indptr, const int64_t* indices,
+                                    const void* values, const void* v, void* out);
 /* MatrixCovBase::to_dense (:64-74): out = A[i:i+q, i:i+q], (q, q) column-major */
 int adelie_hip_design_cov_to_dense(adelie_hip_design* A, int64_t i, int64_t q, void* out);
 int adelie_hip_gaussian_cov_solve(adelie_hip_design* A, const adelie_hip_grpnet_args* args, adelie_hip_result** out);
