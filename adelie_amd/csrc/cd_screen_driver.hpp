@@ -21,7 +21,6 @@
 #include "cd_screen_host.hpp"
 
 namespace ahip {
-void set_last_error(const std::string& s); // design.hip
 
 // what a solve leaves behind; `n` rows and `p` coordinates (bvls: X is (n, p); pinball: A is (p, n) = (m, d))
 struct CdScreenResult {
@@ -59,27 +58,23 @@ inline int64_t cd_result_size(const CdScreenResult* r, int which) {
     return r->extra_size(which);
 }
 inline int cd_result_copy(const CdScreenResult* r, int which, void* out, int64_t cap) {
-    try {
-        const int64_t size = cd_result_size(r, which);
-        if (size < 0 || !out) throw make_core_error("unknown result vector.");
-        const size_t m = size_t(std::min(size, cap));
-        const size_t es = r->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
-        if (!m) return 0;
-        switch (which) {
-            case CDS_BETA: std::memcpy(out, r->beta.data(), m * es); break;
-            case CDS_RESID: std::memcpy(out, r->resid.data(), m * es); break;
-            case CDS_GRAD: std::memcpy(out, r->grad.data(), m * es); break;
-            case CDS_SCREEN_SET: std::memcpy(out, r->screen_set.data(), m * sizeof(int64_t)); break;
-            case CDS_ACTIVE_SET: std::memcpy(out, r->active_set.data(), m * sizeof(int64_t)); break;
-            case CDS_IS_SCREEN: std::memcpy(out, r->is_screen.data(), m); break;
-            case CDS_IS_ACTIVE: std::memcpy(out, r->is_active.data(), m); break;
-            default: r->extra_copy(which, out, m, es);
-        }
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return 1;
+    ABI_TRY
+    const int64_t size = cd_result_size(r, which);
+    if (size < 0 || !out) throw make_core_error("unknown result vector.");
+    const size_t m = size_t(std::min(size, cap));
+    const size_t es = r->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
+    if (!m) return 0;
+    switch (which) {
+        case CDS_BETA: std::memcpy(out, r->beta.data(), m * es); break;
+        case CDS_RESID: std::memcpy(out, r->resid.data(), m * es); break;
+        case CDS_GRAD: std::memcpy(out, r->grad.data(), m * es); break;
+        case CDS_SCREEN_SET: std::memcpy(out, r->screen_set.data(), m * sizeof(int64_t)); break;
+        case CDS_ACTIVE_SET: std::memcpy(out, r->active_set.data(), m * sizeof(int64_t)); break;
+        case CDS_IS_SCREEN: std::memcpy(out, r->is_screen.data(), m); break;
+        case CDS_IS_ACTIVE: std::memcpy(out, r->is_active.data(), m); break;
+        default: r->extra_copy(which, out, m, es);
     }
-    return 0;
+    ABI_CATCH
 }
 inline double cd_result_scalar(const CdScreenResult* r, int which) {
     if (!r) return 0;
@@ -398,8 +393,7 @@ int cd_screen_solve(adelie_hip_design* X, const Args* a, Result** out, Checks ch
                 throw;
             }
         };
-        if (X->dtype == ADELIE_HIP_F64) run(Solver<double>(X, a, res));
-        else run(Solver<float>(X, a, res));
+        DTYPE_DISPATCH(X, run(Solver<T>(X, a, res)))
         res->total_time = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         *out = res;
     } catch (const std::exception& e) {

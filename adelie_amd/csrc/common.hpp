@@ -147,6 +147,23 @@ inline core_error make_solver_error(const std::string& m) { return core_error("a
                                      "' at " #expr);                                                       \
     } while (0)
 
+// ---- the frame of a C-ABI entry ------------------------------------------------------------------------------------------------
+// ABI_TRY ... ABI_CATCH around an entry's body: an exception's message becomes adelie_hip_last_error() (thread-local, design.hip)
+// and the entry returns 1; otherwise it returns 0.  A handler that does more (frees a result, waits for a stream) is written out.
+void set_last_error(const std::string& s);
+#define ABI_TRY try {
+#define ABI_CATCH                         \
+    }                                     \
+    catch (const std::exception& e) {     \
+        ::ahip::set_last_error(e.what()); \
+        return 1;                         \
+    }                                     \
+    return 0;
+// runs the statement(s) once with T = the value type of `d` (a design, or an argument block with a dtype)
+#define DTYPE_DISPATCH(d, ...)                                                            \
+    if ((d)->dtype == ADELIE_HIP_F64) { using T = double; (void)sizeof(T); __VA_ARGS__; } \
+    else { using T = float; (void)sizeof(T); __VA_ARGS__; }
+
 // wall-clock spent in hipMalloc / hipFree by the DevBufs of this process (tuning aid, printed under ADELIE_HIP_TRACE_ENQ)
 struct DevAllocStats {
     static double& seconds() { static double s = 0; return s; }

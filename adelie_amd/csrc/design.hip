@@ -18,12 +18,7 @@ using namespace ahip;
 
 namespace {
 
-thread_local std::string g_last_error;
-
-inline int fail(const std::exception& e) {
-    g_last_error = e.what();
-    return 1;
-}
+thread_local std::string g_last_error; // written by ahip::set_last_error (below), read by adelie_hip_last_error
 
 template <class T>
 T* scratch(DevBuf<char>& b, size_t n) {
@@ -604,22 +599,6 @@ inline int32_t factor_basis(const int64_t* levels, int64_t j, bool& disc) {
     return disc ? int32_t(levels[j]) : 2;
 }
 
-} // namespace
-
-#define ABI_TRY try {
-#define ABI_CATCH                      \
-    }                                  \
-    catch (const std::exception& e) {  \
-        return fail(e);                \
-    }                                  \
-    return 0;
-
-// runs the statement(s) once with T = the design's value type
-#define DTYPE_DISPATCH(d, ...)                                                            \
-    if ((d)->dtype == ADELIE_HIP_F64) { using T = double; (void)sizeof(T); __VA_ARGS__; } \
-    else { using T = float; (void)sizeof(T); __VA_ARGS__; }
-
-namespace {
 template <class T>
 void derive_t(adelie_hip_design* src, adelie_hip_design* d, const int64_t* rows, int64_t nrows, const int64_t* cols,
               int64_t ncols, const double* centers, const double* scales) {

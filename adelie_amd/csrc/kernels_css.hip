@@ -25,8 +25,6 @@
 #include "wavered.hpp"
 
 namespace ahip {
-void set_last_error(const std::string& s); // design.hip
-
 namespace {
 
 enum { CSS_LS = 0, CSS_SF = 1, CSS_MD = 2 };
@@ -622,8 +620,7 @@ int adelie_hip_css_cov_solve(adelie_hip_design* A, const adelie_hip_css_args* a,
         res->p = A->p;
         res->k = a->subset_size;
         const auto t0 = std::chrono::steady_clock::now();
-        if (A->dtype == ADELIE_HIP_F64) css_run<double>(A, a, res);
-        else css_run<float>(A, a, res);
+        DTYPE_DISPATCH(A, css_run<T>(A, a, res))
         res->total_time = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         *out = res;
     } catch (const std::exception& e) {
@@ -652,26 +649,22 @@ int64_t adelie_hip_css_result_size(const adelie_hip_css_result* r, int which) {
 }
 
 int adelie_hip_css_result_copy(const adelie_hip_css_result* r, int which, void* out, int64_t cap) {
-    try {
-        const int64_t size = adelie_hip_css_result_size(r, which);
-        if (size < 0 || !out) throw make_core_error("unknown result vector.");
-        const size_t n = size_t(std::min(size, cap));
-        const size_t es = r->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
-        if (!n) return 0;
-        switch (which) {
-            case ADELIE_HIP_CSS_SUBSET: std::memcpy(out, r->subset.data(), n * sizeof(int64_t)); break;
-            case ADELIE_HIP_CSS_S_RESID:
-                AHIP_CHECK(hipSetDevice(r->device));
-                AHIP_CHECK(hipMemcpy(out, r->Sr.p, n * es, hipMemcpyDeviceToHost));
-                break;
-            case ADELIE_HIP_CSS_S_RESID_DIAG: std::memcpy(out, r->diag.data(), n * es); break;
-            case ADELIE_HIP_CSS_L_T: std::memcpy(out, r->L_T.data(), n * sizeof(double)); break;
-        }
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return 1;
+    ABI_TRY
+    const int64_t size = adelie_hip_css_result_size(r, which);
+    if (size < 0 || !out) throw make_core_error("unknown result vector.");
+    const size_t n = size_t(std::min(size, cap));
+    const size_t es = r->dtype == ADELIE_HIP_F64 ? sizeof(double) : sizeof(float);
+    if (!n) return 0;
+    switch (which) {
+        case ADELIE_HIP_CSS_SUBSET: std::memcpy(out, r->subset.data(), n * sizeof(int64_t)); break;
+        case ADELIE_HIP_CSS_S_RESID:
+            AHIP_CHECK(hipSetDevice(r->device));
+            AHIP_CHECK(hipMemcpy(out, r->Sr.p, n * es, hipMemcpyDeviceToHost));
+            break;
+        case ADELIE_HIP_CSS_S_RESID_DIAG: std::memcpy(out, r->diag.data(), n * es); break;
+        case ADELIE_HIP_CSS_L_T: std::memcpy(out, r->L_T.data(), n * sizeof(double)); break;
     }
-    return 0;
+    ABI_CATCH
 }
 
 double adelie_hip_css_result_scalar(const adelie_hip_css_result* r, int which) {

@@ -10,7 +10,6 @@
 #include "qp_full_body.hpp"
 
 namespace ahip {
-void set_last_error(const std::string& s); // design.hip
 
 int64_t g_qp_full_lds_max_d = 0; // adelie_hip_set_config("qp_full_lds_max_d", x): 0 = automatic
 
@@ -188,40 +187,35 @@ void qp_full_run(const adelie_hip_qp_full_args* a) {
 using namespace ahip;
 
 extern "C" int adelie_hip_qp_full_solve(const adelie_hip_qp_full_args* a) {
-    try {
-        const auto t0 = std::chrono::steady_clock::now();
-        if (!a) throw make_core_error("null argument.");
-        if (a->kind != ADELIE_HIP_QP_FULL_NNQP && a->kind != ADELIE_HIP_QP_FULL_LASSO && a->kind != ADELIE_HIP_QP_FULL_PINBALL)
-            throw make_core_error("qp_full: unknown kind.");
-        if (a->dtype != ADELIE_HIP_F32 && a->dtype != ADELIE_HIP_F64) throw make_core_error("qp_full: bad dtype.");
-        const int64_t n = a->n_problems;
-        if (n < 0 || n >= (int64_t(1) << 31)) throw make_core_error("qp_full: n_problems must be in [0, 2^31).");
-        if (n > 0) {
-            if (!a->d || !a->quad || !a->x || !a->grad || !a->tol || !a->max_iters || !a->iters || !a->status ||
-                (a->kind != ADELIE_HIP_QP_FULL_NNQP && !a->penalty_a) || (a->kind == ADELIE_HIP_QP_FULL_PINBALL && (!a->penalty_b || !a->y_var)))
-                throw make_core_error("null argument.");
-            int count = 0;
-            if (hipGetDeviceCount(&count) != hipSuccess) {
-                (void)hipGetLastError();
-                count = 0;
-            }
-            if (a->device < 0 || a->device >= count) throw make_core_error("qp_full: no such device (adelie_amd has no CPU fallback).");
-            for (int64_t k = 0; k < n; ++k) {
-                const int64_t d = a->d[k];
-                if (d < 0 || d > (int64_t(1) << 20)) throw make_core_error("qp_full: d must be in [0, 2^20].");
-                if (a->tol[k] < 0) throw make_solver_error("tol must be >= 0.");
-                if (a->max_iters[k] < 0) throw make_core_error("qp_full: max_iters must be >= 0.");
-                if (d > 0 && (!a->quad[k] || !a->x[k] || !a->grad[k] || (a->kind != ADELIE_HIP_QP_FULL_NNQP && !a->penalty_a[k]) ||
-                              (a->kind == ADELIE_HIP_QP_FULL_PINBALL && !a->penalty_b[k])))
-                    throw make_core_error("null argument.");
-            }
-            if (a->dtype == ADELIE_HIP_F64) qp_full_run<double>(a);
-            else qp_full_run<float>(a);
+    ABI_TRY
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!a) throw make_core_error("null argument.");
+    if (a->kind != ADELIE_HIP_QP_FULL_NNQP && a->kind != ADELIE_HIP_QP_FULL_LASSO && a->kind != ADELIE_HIP_QP_FULL_PINBALL)
+        throw make_core_error("qp_full: unknown kind.");
+    if (a->dtype != ADELIE_HIP_F32 && a->dtype != ADELIE_HIP_F64) throw make_core_error("qp_full: bad dtype.");
+    const int64_t n = a->n_problems;
+    if (n < 0 || n >= (int64_t(1) << 31)) throw make_core_error("qp_full: n_problems must be in [0, 2^31).");
+    if (n > 0) {
+        if (!a->d || !a->quad || !a->x || !a->grad || !a->tol || !a->max_iters || !a->iters || !a->status ||
+            (a->kind != ADELIE_HIP_QP_FULL_NNQP && !a->penalty_a) || (a->kind == ADELIE_HIP_QP_FULL_PINBALL && (!a->penalty_b || !a->y_var)))
+            throw make_core_error("null argument.");
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess) {
+            (void)hipGetLastError();
+            count = 0;
         }
-        if (a->time_elapsed) *a->time_elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return 1;
+        if (a->device < 0 || a->device >= count) throw make_core_error("qp_full: no such device (adelie_amd has no CPU fallback).");
+        for (int64_t k = 0; k < n; ++k) {
+            const int64_t d = a->d[k];
+            if (d < 0 || d > (int64_t(1) << 20)) throw make_core_error("qp_full: d must be in [0, 2^20].");
+            if (a->tol[k] < 0) throw make_solver_error("tol must be >= 0.");
+            if (a->max_iters[k] < 0) throw make_core_error("qp_full: max_iters must be >= 0.");
+            if (d > 0 && (!a->quad[k] || !a->x[k] || !a->grad[k] || (a->kind != ADELIE_HIP_QP_FULL_NNQP && !a->penalty_a[k]) ||
+                          (a->kind == ADELIE_HIP_QP_FULL_PINBALL && !a->penalty_b[k])))
+                throw make_core_error("null argument.");
+        }
+        DTYPE_DISPATCH(a, qp_full_run<T>(a))
     }
-    return 0;
+    if (a->time_elapsed) *a->time_elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    ABI_CATCH
 }
