@@ -3,7 +3,8 @@
 Mirrors the user-facing surface of JamesYang007/adelie for the ``grpnet`` hot path only
 (``solver.grpnet``, ``cv.cv_grpnet``, ``matrix.dense`` / ``matrix.snp_unphased`` / ``matrix.kronecker_eye``,
 ``glm.gaussian`` / ``glm.binomial`` / ``glm.multigaussian`` / ``glm.multinomial``, the naive State objects), the covariance
-method (``solver.gaussian_cov``), column subset selection on a resident covariance (``solver.css_cov``,
+method (``solver.gaussian_cov``), the pin solvers on a fixed screen set (``state.gaussian_pin_naive`` /
+``state.gaussian_pin_cov``), column subset selection on a resident covariance (``solver.css_cov``,
 ``sklearn.CSSModelSelection``), bounded-variable least squares (``solver.bvls``) and pinball least squares on a resident
 constraint matrix (``solver.pinball``, ``matrix.dense(method="constraint")``), and the full-matrix NNQP / lasso / pinball
 descents, one or a batch per call (``optimization.StateNNQPFull`` / ``StateLassoFull`` / ``StatePinballFull``,

@@ -199,12 +199,14 @@ V = dict(
     screen_X_means=9, screen_vars=10, screen_transforms=11,
     benchmark_screen=12, benchmark_fit_screen=13, benchmark_fit_active=14, benchmark_kkt=15,
     benchmark_invariance=16,
+    rsqs=17, benchmark_active=18, screen_grad=19,  # adelie_hip_gaussian_pin_solve
     betas_values=200, duals_values=201, constraint_mu=202, constraint_vmu=203,
 )
 I = dict(
     screen_set=100, screen_begins=101, screen_is_active=102, active_set=103, n_valid_solutions=104,
     active_sizes=105, screen_sizes=106, betas_indptr=107, betas_indices=108,
     duals_indptr=109, duals_indices=110, constraint_dev_groups=111,
+    active_begins=112, active_order=113,  # adelie_hip_gaussian_pin_solve
 )
 S = dict(
     lmda_max=0, lmda=1, rsq=2, resid_sum=3, active_set_size=4, beta0=5, loss_null=6, loss_full=7,
@@ -217,7 +219,9 @@ S = dict(
     t_host_screen_ms=86, t_panel_step_ms=87, n_panel_step_launches=88, t_host_screen_wait_ms=89,
     t_fsweep_ms=90, n_fsweep_launches=91, fsweep_bytes=92,
     n_screen_reads=93, n_screen_short=94, n_filter_open_cols=95, engine_panel=96,
+    pin_iters=97, n_pin_launches=98, pin_route=99,  # adelie_hip_gaussian_pin_solve
 )
+PIN_NAIVE, PIN_COV = 0, 1  # enum adelie_hip_pin_method
 
 class QpFullArgs(C.Structure):
     """``adelie_hip_qp_full_args`` (an addition to ABI 14)."""
@@ -291,6 +295,7 @@ HIP_SYMBOLS = [
     "design_cmul", "design_ctmul", "design_bmul", "design_btmul", "design_bmul_cols", "design_btmul_cols", "design_mul", "design_mul_batch", "design_cov",
     "design_sq_mul", "design_sp_tmul",
     "design_create_cov_dense", "design_create_cov_csc", "design_create_cov_lazy", "design_cov_bmul", "design_cov_mul", "design_cov_mul_batch", "design_cov_to_dense", "gaussian_cov_solve",
+    "gaussian_pin_solve",
     "glm_cox_create", "glm_cox_destroy", "glm_cox_eval",
     "grpnet_solve", "grpnet_solve_many", "result_destroy", "result_size", "result_copy", "result_scalar", "result_error", "result_sync",
     "bench_sweep", "filter_sweep_test", "block_build_test", "group_piece_test", "multi_piece_test", "cov_piece_test",
@@ -408,6 +413,7 @@ class Backend:
         sig("grpnet_solve", ci, [vp, p(GrpnetArgs), p(vp)])
         sig("grpnet_solve_many", ci, [p(vp), p(p(GrpnetArgs)), C.c_int32, p(vp), DONE_FN, vp])
         sig("gaussian_cov_solve", ci, [vp, p(GrpnetArgs), p(vp)])
+        sig("gaussian_pin_solve", ci, [vp, p(GrpnetArgs), ci, vp, p(vp)])
         sig("design_create_cov_dense", ci, [vp, i64, ci, ci, ci, p(vp)])
         sig("design_create_cov_csc", ci, [vp, vp, vp, i64, ci, ci, p(vp)])
         sig("design_create_cov_lazy", ci, [vp, p(vp)])

@@ -3,7 +3,7 @@
 # read, as paths relative to this directory, so they stay valid when the tree is copied), and those depfiles decide what is stale:
 # no list of headers is kept by hand.
 UNITS := kernels_cons kernels_append kernels_eig kernels_strip kernels_cov kernels_cov_sparse kernels_sparse kernels_sweep \
-         kernels_filter kernels_convert kernels_gram kernels_cd kernels_cd_lasso kernels_cd_block kernels_cd_block_group \
+         kernels_filter kernels_convert kernels_gram kernels_cd kernels_cd_lasso kernels_cd_pin kernels_cd_block kernels_cd_block_group \
          kernels_cd_panel kernels_multi kernels_glm kernels_cox kernels_factor kernels_relu kernels_relu_sparse kernels_phased \
          kernels_css kernels_bvls kernels_pinball kernels_pinball_sparse kernels_qp_full design solver test_entries
 OBJS := $(UNITS:%=$(OBJ)/%.o)

@@ -15,6 +15,8 @@
 #include "filter_host.hpp"
 #include "screen_reads_host.hpp"
 #include "cox.hpp"
+#include "cd_pin.hpp"
+#include "pin_rows_host.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -366,6 +368,7 @@ struct Solver {
 #include "solver_panel.hpp"
 #include "solver_fit.hpp"
 #include "solver_path.hpp"
+#include "solver_pin.hpp"
 };
 
 struct ResultBase {
@@ -428,6 +431,11 @@ struct Result : ResultBase {
             case ADELIE_HIP_V_CONSTRAINT_MU: return s.cons_on ? s.G : 0;
             case ADELIE_HIP_V_CONSTRAINT_VMU: return s.cons_dev ? s.p : 0;
             case ADELIE_HIP_I_CONSTRAINT_DEV_GROUPS: return s.cons_dev ? int64_t(s.devcons_list.size()) : 0;
+            case ADELIE_HIP_V_RSQS: return s.pin_rsqs.size();
+            case ADELIE_HIP_V_BENCHMARK_ACTIVE: return s.pin_bench_active.size();
+            case ADELIE_HIP_V_SCREEN_GRAD: return s.pin_screen_grad.size();
+            case ADELIE_HIP_I_ACTIVE_BEGINS: return s.pin_abegins.size();
+            case ADELIE_HIP_I_ACTIVE_ORDER: return s.pin_aorder.size();
         }
         return -1;
     }
@@ -457,6 +465,11 @@ struct Result : ResultBase {
             case ADELIE_HIP_V_BENCHMARK_FIT_ACTIVE: cp_d(s.benchmark_fit_active, d, cap); return 0;
             case ADELIE_HIP_V_BENCHMARK_KKT: cp_d(s.benchmark_kkt, d, cap); return 0;
             case ADELIE_HIP_V_BENCHMARK_INVARIANCE: cp_d(s.benchmark_invariance, d, cap); return 0;
+            case ADELIE_HIP_V_RSQS: cp_d(s.pin_rsqs, d, cap); return 0;
+            case ADELIE_HIP_V_BENCHMARK_ACTIVE: cp_d(s.pin_bench_active, d, cap); return 0;
+            case ADELIE_HIP_V_SCREEN_GRAD: cp_d(s.pin_screen_grad, d, cap); return 0;
+            case ADELIE_HIP_I_ACTIVE_BEGINS: cp_i(s.pin_abegins, ii, cap); return 0;
+            case ADELIE_HIP_I_ACTIVE_ORDER: cp_i(s.pin_aorder, ii, cap); return 0;
             case ADELIE_HIP_I_SCREEN_SET: cp_i(s.screen_set, ii, cap); return 0;
             case ADELIE_HIP_I_SCREEN_BEGINS: cp_i(s.screen_begins, ii, cap); return 0;
             case ADELIE_HIP_I_SCREEN_IS_ACTIVE: cp_i(s.screen_is_active, ii, cap); return 0;
@@ -574,6 +587,9 @@ struct Result : ResultBase {
             case ADELIE_HIP_S_N_SCREEN_SHORT: return double(s.n_screen_short);
             case ADELIE_HIP_S_N_FILTER_OPEN_COLS: return double(s.n_filter_open_cols);
             case ADELIE_HIP_S_ENGINE_PANEL: return s.engine_panel ? 1.0 : 0.0;
+            case ADELIE_HIP_S_PIN_ITERS: return double(s.pin_iters);
+            case ADELIE_HIP_S_N_PIN_LAUNCHES: return double(s.n_pin_launches);
+            case ADELIE_HIP_S_PIN_ROUTE: return double(s.pin_route);
             default:
                 if (which >= 900 && which < 908) return double(s.cd_dbg[which - 900]);
                 if (which >= 910 && which < 918) return 1e3 * s.t_host[which - 910];
@@ -641,6 +657,44 @@ void run(adelie_hip_design* X, const adelie_hip_grpnet_args* a, adelie_hip_resul
 
 } // namespace
 
+int g_pin_path_launch = 1; // adelie_hip_set_config("pin_path_launch", 0/1)
+
+namespace {
+
+// adelie_hip_gaussian_pin_solve: build as for a warm-started Gaussian solve, then the pin path (solver_pin.hpp)
+template <class T>
+void run_pin(adelie_hip_design* X, const adelie_hip_grpnet_args* a, const void* screen_grad, adelie_hip_result* res) {
+    auto* r = new Result<T>();
+    res->r = r;
+    r->device = X->device;
+    r->s.live = res;
+    r->s.stage.init(size_t(8) << 20, X->stream);
+    Staging::Scope stage_scope(&r->s.stage);
+    DeferredFrees::Scope deferred_scope(&r->s.deferred);
+    r->s.pin_mode = true;
+    r->s.pin_sg = static_cast<const T*>(screen_grad);
+    r->s.pin_path_launch = g_pin_path_launch;
+    r->s.build(X, a);
+    Stopwatch sw;
+    sw.start();
+    try {
+        r->s.pin_cov_setup(a->cov_v != nullptr);
+        r->s.solve_pin();
+    } catch (const std::exception& e) {
+        r->s.error = e.what();
+    }
+    try {
+        r->s.finalize();
+        r->s.pin_collect();
+    } catch (const std::exception& e) {
+        if (r->s.error.empty()) r->s.error = e.what();
+    }
+    r->s.total_time = sw.elapsed();
+    r->s.live = nullptr;
+}
+
+} // namespace
+
 void adelie_hip_internal_free_batcher(void* b) { delete static_cast<SweepBatcher*>(b); }
 void adelie_hip_internal_batch_stats(void* b, double* out) {
     out[0] = out[1] = out[2] = 0;
@@ -668,6 +722,7 @@ int adelie_hip_set_config(const char* name, double value) {
     if (nm == "hessian_min") g_hessian_min = value;
     else if (nm == "dbeta_tol") g_dbeta_tol = value;
     else if (nm == "sweep_batch") g_sweep_batch = value != 0.0 ? 1 : 0;
+    else if (nm == "pin_path_launch") g_pin_path_launch = value != 0.0 ? 1 : 0;
     else if (nm == "pool_limit_mb") {
         DevPool::limit_bytes() = value > 0 ? size_t(value) << 20 : 0;
         if (value <= 0) DevPool::trim();
@@ -717,6 +772,32 @@ static int solve_entry(adelie_hip_design* X, const adelie_hip_grpnet_args* args,
     auto* res = new adelie_hip_result();
     try {
         DTYPE_DISPATCH(X, run<T>(X, args, res))
+    } catch (...) {
+        delete res;
+        throw;
+    }
+    *out = res;
+    ABI_CATCH
+}
+int adelie_hip_gaussian_pin_solve(adelie_hip_design* X, const adelie_hip_grpnet_args* args, int method, const void* screen_grad,
+                                  adelie_hip_result** out) {
+    ABI_TRY
+    if (!X || !args || !out) throw make_core_error("null argument.");
+    const bool cov = method == ADELIE_HIP_PIN_COV;
+    if (!cov && method != ADELIE_HIP_PIN_NAIVE) throw make_core_error("pin solve: method must be ADELIE_HIP_PIN_NAIVE or ADELIE_HIP_PIN_COV.");
+    if (cov && !X->cov) throw make_core_error("A must be a covariance matrix (matrix.dense(method=\"cov\")).");
+    if (!cov && X->cov) throw make_core_error("X is a covariance matrix: use the covariance method's pin solve.");
+    if (X->constraint) throw make_core_error("X is a constraint matrix (matrix.dense(method=\"constraint\")): use pinball.");
+    if (cov && !screen_grad && args->screen_beta_size > 0) throw make_core_error("screen_grad is required by the covariance method's pin solve.");
+    if (args->constraint_kind)
+        for (int64_t g = 0; g < args->G; ++g)
+            if (args->constraint_kind[g] != 0) throw make_core_error("pin solves take no constraints: use grpnet / gaussian_cov.");
+    if (args->glm_kind != ADELIE_HIP_GLM_GAUSSIAN) throw make_core_error("pin solves are Gaussian.");
+    if (X->is_multi()) throw make_core_error("pin solves are not offered on a multi-response view (design kind: kronecker_eye).");
+    if (!args->lmda_path && args->n_lmda_path > 0) throw make_core_error("lmda_path is required.");
+    auto* res = new adelie_hip_result();
+    try {
+        DTYPE_DISPATCH(X, run_pin<T>(X, args, screen_grad, res))
     } catch (...) {
         delete res;
         throw;

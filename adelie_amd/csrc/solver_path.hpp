@@ -410,7 +410,9 @@
         active_set_size = size_t(a->active_set_size);
         active_set.assign(a->active_set, a->active_set + G);
         lmda = T(a->lmda);
-        grad.assign((const T*)a->grad, (const T*)a->grad + p);
+        if (a->grad) grad.assign((const T*)a->grad, (const T*)a->grad + p);
+        else if (pin_mode) grad.assign(size_t(p), T(0)); // (a pin state carries the residual / the screen gradient instead)
+        else throw make_core_error("grad is required.");
         abs_grad.assign(G, 0);
         for (idx g = 0; g < G; ++g) {
             max_gs = std::max(max_gs, group_sizes[g]);
@@ -429,8 +431,9 @@
         // state_base.ipp:9-116
         if (alpha < 0 || alpha > 1) throw make_core_error("alpha must be in [0,1].");
         if (tol < 0) throw make_core_error("tol must be >= 0.");
-        if (adev_tol < 0 || adev_tol > 1) throw make_core_error("adev_tol must be in [0,1].");
-        if (ddev_tol < 0 || ddev_tol > 1) throw make_core_error("ddev_tol must be in [0,1].");
+        // (the reference's pin states take adev_tol / ddev_tol as they come: state_gaussian_pin_base.hpp has no range check)
+        if (!pin_mode && (adev_tol < 0 || adev_tol > 1)) throw make_core_error("adev_tol must be in [0,1].");
+        if (!pin_mode && (ddev_tol < 0 || ddev_tol > 1)) throw make_core_error("ddev_tol must be in [0,1].");
         if (newton_tol < 0) throw make_core_error("newton_tol must be >= 0.");
         if (a->n_threads < 1) throw make_core_error("n_threads must be >= 1.");
         if (min_ratio < 0 || min_ratio > 1) throw make_core_error("min_ratio must be in [0,1].");
@@ -661,10 +664,11 @@
         dev_cons_abs_grad_host(lmda);
 
         if (cov_mode) {
-            if (!a->cov_v) throw make_core_error("v must be (p,) where A is (p, p).");
+            if (!a->cov_v && !pin_mode) throw make_core_error("v must be (p,) where A is (p, p).");
             d_covv.reserve(p); d_xm.reserve(p);
             if (D->cov_csc()) { d_cov_w.reserve(p); d_cov_pos.reserve(p); } // the scratch of kernels_cov_sparse.hip
-            d_covv.upload((const T*)a->cov_v, p, st);
+            if (a->cov_v) d_covv.upload((const T*)a->cov_v, p, st);
+            else AHIP_CHECK(hipMemsetAsync(d_covv.p, 0, size_t(p) * sizeof(T), st)); // (a pin solve: pin_cov_setup fills it)
             X_means.assign(size_t(p), T(0)); // no centring in the covariance method
             d_xm.upload(X_means.data(), p, st);
             rsq = T(a->rsq);

@@ -1829,3 +1829,432 @@ class pinball(_ScreenSetState):
         dt = self._dtype.type
         self.A.rmmul(k, self.S, self._screen_AS[k])
         self._screen_ASAT_diag[k] = max(dt(self.A.rvmul(k, self._screen_AS[k])), dt(0))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# pin states: block coordinate descent along a given lambda path on a screen set that never changes
+# ---------------------------------------------------------------------------------------------------------------------
+_PIN_ENTRY = "gaussian_pin_solve"
+
+
+def _pin_refuse_constraints(constraints, instead):
+    if constraints is not None and any(c is not None for c in constraints):
+        raise RuntimeError("adelie_amd: pin states take no constraint objects (every entry of `constraints` must be None); "
+                           f"use {instead}, which solves constrained groups.")
+
+
+def _pin_backend(M, what):
+    backend = getattr(M, "_backend", None)
+    if backend is None or not backend.has(_PIN_ENTRY):
+        raise RuntimeError(f"adelie_amd: {what} must be a design resident on the device whose library exports "
+                           f"adelie_hip_{_PIN_ENTRY} (backend.has(\"{_PIN_ENTRY}\")); build one with adelie_amd.matrix "
+                           "(dense, snp_unphased, sparse, lazy_cov, ...) -- other backends have no pin solve.")
+    return backend
+
+
+class gaussian_pin_base:
+    """What the two pin states share (reference ``state.py:179-398``): the checks, ``solve()`` and the read-back."""
+
+    _method = None
+
+    @staticmethod
+    def _check(cond, msg, method, logger):
+        cond = bool(cond)
+        logger.log(logging.INFO if cond else logging.ERROR, f"check {msg}: {'pass' if cond else 'FAIL'}")
+        if method == "assert":
+            assert cond, msg
+        return cond
+
+    def check(self, method: str = None, logger=logger):
+        """The consistency checks of reference ``state.py:179-398`` (``method="assert"`` asserts each).  Returns whether all
+        passed."""
+        ok = []
+        c = lambda cond, msg: ok.append(self._check(cond, msg, method, logger))
+        p = int(np.sum(self.group_sizes))
+        c(np.all((0 <= self.groups) & (self.groups <= p)), "groups is in [0, p)")
+        c(len(self.groups) == len(np.unique(self.groups)), "groups has unique values")
+        c(self.groups.dtype == np.dtype("int"), "groups dtype is int")
+        G = len(self.groups)
+        c(len(self.group_sizes) == G, "groups and group_sizes have same length")
+        c(np.all((0 < self.group_sizes) & (self.group_sizes <= p)), "group_sizes is in (0, p]")
+        c(self.group_sizes.dtype == np.dtype("int"), "group_sizes dtype is int")
+        c(len(self.group_sizes) == G and np.allclose(self.groups, np.cumsum(np.concatenate([[0], self.group_sizes]))[:-1]),
+          "groups and group_sizes consistency")
+        c(np.all(self.penalty >= 0), "penalty is non-negative")
+        in_range = bool(np.all((0 <= self.screen_set) & (self.screen_set < G)))
+        c(in_range, "screen_set is a subset of [0, G)")
+        c(len(self.screen_set) == len(np.unique(self.screen_set)), "screen_set has unique values")
+        c(self.screen_set.dtype == np.dtype("int"), "screen_set dtype is int")
+        S = len(self.screen_set)
+        sizes = self.group_sizes[self.screen_set] if in_range else np.zeros(0, dtype=int)
+        expected = np.cumsum(np.concatenate([[0], sizes]).astype(int))
+        WS = int(expected[-1])
+        c(len(self.screen_begins) == S and np.all(self.screen_begins == expected[:-1]),
+          "screen_begins is [0, g1, g2, ...] where gi is the group size of (i-1)th screen group.")
+        c(self.screen_begins.dtype == np.dtype("int"), "screen_begins dtype is int")
+        c(len(self.screen_vars) == WS, "screen_vars size")
+        c(np.all(0 <= self.screen_vars), "screen_vars is non-negative")
+        c(len(self.screen_transforms) == S, "screen_transforms size")
+        c(len(self.screen_beta) == WS, "screen_beta size")
+        c(np.all(0 <= self.lmda_path), "lmda_path is non-negative")
+        if np.any(self.lmda_path != np.sort(self.lmda_path)[::-1]):
+            logger.warning("lmda_path are not sorted in decreasing order")
+        active_set = self.active_set[:self.active_set_size]
+        flags = np.arange(S)[self.screen_is_active] if len(self.screen_is_active) == S else np.zeros(0, dtype=int)
+        c(len(self.screen_is_active) == S and len(flags) == len(active_set) and np.all(flags == np.sort(active_set)),
+          "screen_is_active is consistent with active_set")
+        c(self.screen_is_active.dtype == np.dtype("bool"), "screen_is_active dtype is bool")
+        act_ok = bool(np.all((0 <= active_set) & (active_set < S)))
+        c(act_ok, "active_set is in [0, S)")
+        c(len(active_set) == len(np.unique(active_set)), "active_set is unique")
+        c(active_set.dtype == np.dtype("int"), "active_set dtype is int")
+        if act_ok and in_range:
+            expected = np.cumsum(np.concatenate([[0], self.group_sizes[self.screen_set[active_set]]]).astype(int))[:-1]
+            c(len(self.active_begins) == len(expected) and np.all(self.active_begins == expected),
+              "active_begins is [0, g1, g2, ...] where gi is the group size of (i-1)th active group.")
+            c(self.active_begins.dtype == np.dtype("int"), "active_begins dtype is int")
+            order_ok = len(self.active_order) == len(active_set)
+            actual = self.groups[self.screen_set[active_set[self.active_order]]] if order_ok else np.zeros(0)
+            c(order_ok and np.all(actual == np.sort(actual)), "active_order orders active_set such that groups is ordered")
+            c(self.active_order.dtype == np.dtype("int"), "active_order dtype is int")
+        c(self.betas.shape[0] <= self.lmda_path.shape[0], "betas rows is no more than the number of lmda_path")
+        c(isinstance(self.betas, csr_matrix), "betas type")
+        c(self.betas.shape[1] == p, "betas shape")
+        c(self.rsqs.shape == (self.betas.shape[0],), "rsqs shape")
+        c(np.all(0 <= self.rsqs), "rsqs is non-negative")
+        c(self.lmdas.shape == (self.betas.shape[0],), "lmdas shape")
+        return all(ok)
+
+    # -- construction helpers ---------------------------------------------------------------------------------------
+    def _init_common(self, M, dtype, groups, alpha, penalty, screen_set, lmda_path, rsq, screen_beta, screen_is_active,
+                     active_set_size, active_set, max_active_size, max_iters, tol, newton_tol, newton_max_iters, n_threads):
+        p = M.cols()
+        self.dtype = dtype
+        self._X = M
+        self.groups = np.array(groups, copy=True, dtype=int)
+        gs = np.concatenate([self.groups, [p]]).astype(int)
+        self.group_sizes = gs[1:] - gs[:-1]
+        G = len(self.groups)
+        self.alpha = alpha
+        self.penalty = np.array(penalty, copy=True, dtype=dtype)
+        self.screen_set = np.array(screen_set, copy=True, dtype=int)
+        self.lmda_path = np.array(lmda_path, copy=True, dtype=dtype)
+        self.screen_beta = np.array(screen_beta, copy=True, dtype=dtype)
+        self.screen_is_active = np.array(screen_is_active, copy=True, dtype=bool)
+        self.active_set = np.array(active_set, copy=True, dtype=int)
+        self.active_set_size = int(active_set_size)
+        self.constraints = [None] * G
+        inside = self.screen_set[(0 <= self.screen_set) & (self.screen_set < G)]
+        if len(inside) != len(self.screen_set):
+            raise RuntimeError("adelie_core: screen_set must be a subset of [0, G) where groups is (G,).")
+        self.screen_begins = np.cumsum(np.concatenate([[0], self.group_sizes[self.screen_set]]).astype(int))[:-1]
+        self.max_active_size = G if max_active_size is None else int(np.minimum(max_active_size, G))
+        self.max_iters = max_iters
+        self.tol = tol
+        self.newton_tol = newton_tol
+        self.newton_max_iters = newton_max_iters
+        self.n_threads = n_threads
+        self.rsq = rsq
+        if len(self.penalty) != G:
+            raise RuntimeError("adelie_core: penalty must be (G,) where groups is (G,).")
+        # nothing solved yet
+        self.betas = csr_matrix((0, p), dtype=dtype)
+        self.intercepts = np.zeros(0, dtype=dtype)
+        self.rsqs = np.zeros(0, dtype=dtype)
+        self.lmdas = np.zeros(0, dtype=dtype)
+        self.iters = 0
+        self.benchmark_screen = np.zeros(0)
+        self.benchmark_active = np.zeros(0)
+        self.error = ""
+        self.counters = {}
+        act = self.active_set[:self.active_set_size]
+        ok = len(act) == 0 or bool(np.all((0 <= act) & (act < len(self.screen_set))))
+        sizes = self.group_sizes[self.screen_set[act]] if ok else np.zeros(0, dtype=int)
+        self.active_begins = np.cumsum(np.concatenate([[0], sizes]).astype(int))[:-1]
+        self.active_order = np.argsort(self.groups[self.screen_set[act]], kind="stable").astype(int) if ok else np.zeros(0, dtype=int)
+
+    def _pin_args(self, keep):
+        a = _abi.GrpnetArgs()
+        dtype = self.dtype
+
+        def val(x):
+            arr = np.ascontiguousarray(x, dtype=dtype)
+            keep.append(arr)
+            return arr.ctypes.data
+
+        def idx(x):
+            arr = np.ascontiguousarray(x, dtype=np.int64)
+            keep.append(arr)
+            return arr.ctypes.data
+
+        G = len(self.groups)
+        S = len(self.screen_set)
+        if len(self.screen_is_active) != S:
+            raise RuntimeError("adelie_core: screen_is_active must be (s,) where screen_set is (s,).")
+        if len(self.active_set) > G or self.active_set_size > len(self.active_set):
+            raise RuntimeError("adelie_core: active_set must hold active_set_size entries and at most G.")
+        if len(self.screen_beta) != int(np.sum(self.group_sizes[self.screen_set])):
+            raise RuntimeError("adelie_core: screen_beta must hold one value per screen coefficient.")
+        a.G = G
+        a.groups = idx(self.groups)
+        a.group_sizes = idx(self.group_sizes)
+        a.alpha = float(self.alpha)
+        a.penalty = val(self.penalty)
+        a.glm_kind = _abi.GLM_GAUSSIAN
+        a.rsq = float(self.rsq)
+        lp = np.ascontiguousarray(self.lmda_path, dtype=dtype)
+        keep.append(lp)
+        a.lmda_path = lp.ctypes.data if lp.size else None
+        a.n_lmda_path = lp.size
+        a.lmda_path_size = lp.size
+        a.lmda_max = -1.0
+        a.min_ratio = 1e-2
+        a.max_screen_size = G
+        a.max_active_size = int(self.max_active_size)
+        a.pivot_subset_ratio = 0.1
+        a.pivot_subset_min = 1
+        a.pivot_slack_ratio = 1.25
+        a.screen_rule = _abi.SCREEN_PIVOT
+        a.early_exit = 1
+        a.max_iters = int(self.max_iters)
+        a.tol = float(self.tol)
+        a.newton_tol = float(self.newton_tol)
+        a.newton_max_iters = int(self.newton_max_iters)
+        a.n_threads = int(self.n_threads)
+        a.screen_set_size = S
+        a.screen_set = idx(self.screen_set)
+        a.screen_beta_size = len(self.screen_beta)
+        a.screen_beta = val(self.screen_beta)
+        sa = np.ascontiguousarray(self.screen_is_active, dtype=np.int8)
+        keep.append(sa)
+        a.screen_is_active = sa.ctypes.data
+        a.active_set_size = int(self.active_set_size)
+        act = np.zeros(G, dtype=np.int64)
+        act[:len(self.active_set)] = self.active_set
+        keep.append(act)
+        a.active_set = act.ctypes.data
+        a.lmda = float(lp[0]) if lp.size else 0.0
+        return a
+
+    def solve(self):
+        """Runs the path; returns a new solved state and leaves this one untouched.  A solver error ("max coordinate
+        descents reached at lambda index: l.", "Maximum number of active groups reached.") ends the path: the rows before the
+        failing lambda are kept, the message is ``error`` and is logged."""
+        backend = _pin_backend(self._X, "the design")
+        keep = []
+        args = self._pin_args(keep)
+        sg = self._marshal_method(args, keep)
+        handle = _abi.C.c_void_p()
+        backend.check(backend.fn(_PIN_ENTRY)(self._X._handle, _abi.C.byref(args), self._method, sg, _abi.C.byref(handle)))
+        try:
+            new = self._from_result(backend, handle)
+        finally:
+            backend.fn("result_destroy")(handle)
+        if new.error != "":
+            if new.error.startswith("adelie_core solver: "):
+                logger.error(RuntimeError(new.error))
+            else:
+                logger.warning(RuntimeError(new.error))
+        return new
+
+    def _from_result(self, backend, r):
+        new = object.__new__(type(self))
+        new.__dict__.update(self.__dict__)
+        dtype = self.dtype
+        vec = lambda nm: backend.result_vec(r, _abi.V[nm])
+        ivec = lambda nm: backend.result_vec(r, _abi.I[nm], index=True).astype(int)
+        sc = lambda nm: backend.fn("result_scalar")(r, _abi.S[nm])
+        indptr, indices = ivec("betas_indptr"), ivec("betas_indices")
+        values = vec("betas_values").astype(dtype)
+        new.betas = csr_matrix((values, indices, indptr), shape=(len(indptr) - 1, self._X.cols()))
+        new.intercepts = vec("intercepts").astype(dtype)
+        new.rsqs = vec("rsqs").astype(dtype)
+        new.lmdas = vec("lmdas").astype(dtype)
+        new.benchmark_screen = vec("benchmark_screen")
+        new.benchmark_active = vec("benchmark_active")
+        new.screen_beta = vec("screen_beta").astype(dtype)
+        new.screen_is_active = ivec("screen_is_active").astype(bool)
+        new.active_set = ivec("active_set")
+        new.active_set_size = int(sc("active_set_size"))
+        new.active_begins = ivec("active_begins")
+        new.active_order = ivec("active_order")
+        new.rsq = dtype(sc("rsq"))
+        new.iters = int(sc("pin_iters"))
+        new.total_time = sc("total_time")
+        names = _COUNTERS + ["n_pin_launches", "pin_route"]
+        new.counters = {nm: int(v) if v == v else 0 for nm, v in ((nm, sc(nm)) for nm in names)}
+        new.timers = {nm: (v if v == v else 0.0) for nm, v in ((nm, sc(nm)) for nm in _TIMERS)}
+        err = backend.fn("result_error")(r)
+        new.error = err.decode() if err else ""
+        self._from_result_method(new, backend, r, sc, vec)
+        return new
+
+
+class gaussian_pin_naive_base(gaussian_pin_base):
+    """Gaussian pin state, naive method (reference ``state.py:401-720``)."""
+
+    _method = _abi.PIN_NAIVE
+
+    def check(self, method: str = None, logger=logger):
+        ok = super().check(method=method, logger=logger)
+        ok &= self._check(isinstance(self.X, (_matrix.MatrixNaiveBase64, _matrix.MatrixNaiveBase32)), "X type", method, logger)
+        ok &= self._check(self.resid.shape[0] == self.X.rows(), "resid shape", method, logger)
+        return ok
+
+    def _marshal_method(self, a, keep):
+        dtype = self.dtype
+        w = np.ascontiguousarray(self.weights, dtype=dtype)
+        xm = np.ascontiguousarray(self._X_means, dtype=dtype)
+        r = np.ascontiguousarray(self.resid, dtype=dtype)
+        keep += [w, xm, r]
+        a.weights = w.ctypes.data
+        a.X_means = xm.ctypes.data
+        a.resid = r.ctypes.data
+        a.y_mean = float(self.y_mean)
+        a.y_var = float(self.y_var)
+        a.resid_sum = float(self.resid_sum)
+        a.intercept = int(bool(self.intercept))
+        a.adev_tol = float(self.adev_tol)
+        a.ddev_tol = float(self.ddev_tol)
+        return None
+
+    def _from_result_method(self, new, backend, r, sc, vec):
+        new.resid = vec("resid").astype(self.dtype)
+        new.resid_sum = self.dtype(sc("resid_sum"))
+
+
+def gaussian_pin_naive(
+    *, X, y_mean, y_var, constraints, groups, alpha, penalty, weights, screen_set, lmda_path, rsq, resid, screen_beta,
+    screen_is_active, active_set_size, active_set, intercept=True, max_active_size=None, max_iters=int(1e5), tol=1e-7,
+    adev_tol=0.9, ddev_tol=0, newton_tol=1e-12, newton_max_iters=1000, n_threads=1,
+):
+    """Creates a Gaussian, pin, naive method state object (reference ``adelie.state.gaussian_pin_naive``, ``state.py:421-720``;
+    argument meaning, defaults and attribute names identical).  A pin solve is block coordinate descent along ``lmda_path`` on
+    a screen set that never changes: no screening, no KKT sweep, no ``lmda_max`` search.  ``tol`` is absolute and ``max_iters``
+    bounds the iterations of the whole path, as upstream.
+
+    The constructor derives ``group_sizes``, ``screen_begins``, ``max_active_size = min(., G)``, ``resid_sum`` and -- from
+    ``X.cov`` per screen group, centred with an intercept, through ``eigh`` with the eigenvalues clamped at 0 --
+    ``screen_vars``, ``screen_X_means`` and ``screen_transforms``; all are public attributes.  (The solve itself builds its own
+    copies of the last three on the device, as every warm-started Gaussian solve of this package does.)
+
+    ``X`` is a native design: ``matrix.dense`` (f64, f32), ``matrix.snp_unphased`` / ``snp_calldata``,
+    ``matrix.sparse(resident="csc")`` and every other native single-response kind (standardized views, concatenations,
+    one-hot / interaction / ReLU expansions, phased ancestry) run through the same driver; a multi-response view
+    (``kronecker_eye``) is refused by the library before anything is launched, with a message naming the kind.  Any
+    non-``None`` entry of ``constraints`` is refused: use ``grpnet``.
+
+    A screen set small enough for the single-workgroup descent (fewer than 128 values, or groups too wide for the block
+    engine) runs the whole path in ONE kernel launch; ``configs.set_configs("pin_path_launch", False)`` runs one launch per
+    lambda instead, with the same bits.  On the one-launch route ``benchmark_screen`` / ``benchmark_active`` are filled from
+    the device's ``wall_clock64()`` deltas per lambda, split by the visit counts of the two kinds of pass.  Larger screen
+    sets run the block / panel engines, one fit per lambda.  ``counters["pin_route"]`` says which route ran (1: one launch,
+    2: one launch per lambda, 3: block engine, 4: panel engine) and ``counters["n_pin_launches"]`` how many descents it
+    launched."""
+    if not isinstance(X, (_matrix.MatrixNaiveBase64, _matrix.MatrixNaiveBase32)):
+        raise ValueError("X must be an instance of MatrixNaiveBase32 or MatrixNaiveBase64.")
+    _pin_refuse_constraints(constraints, "grpnet")
+    _pin_backend(X, "X")
+    dtype = X.dtype
+    s = gaussian_pin_naive_base()
+    s._init_common(X, dtype, groups, alpha, penalty, screen_set, lmda_path, rsq, screen_beta, screen_is_active,
+                   active_set_size, active_set, max_active_size, max_iters, tol, newton_tol, newton_max_iters, n_threads)
+    s.X = X
+    s.y_mean = y_mean
+    s.y_var = y_var
+    s.weights = np.array(weights, copy=True, dtype=dtype)
+    s.resid = np.array(resid, copy=True, dtype=dtype)
+    s.intercept = intercept
+    s.adev_tol = adev_tol
+    s.ddev_tol = ddev_tol
+    n, p = X.rows(), X.cols()
+    if len(s.weights) != n:
+        raise RuntimeError("adelie_core: weights must be (n,) where X is (n, p).")
+    if len(s.resid) != n:
+        raise RuntimeError("adelie_core: resid must be (n,) where X is (n, p).")
+    sqrt_weights = np.sqrt(s.weights)
+    X_means = np.empty(p, dtype=dtype)
+    X.mul(np.ones(n, dtype=dtype), s.weights, X_means)
+    s._X_means = X_means
+    svars, smeans, strans = [], [], []
+    for i in s.screen_set:
+        g, gs = int(s.groups[i]), int(s.group_sizes[i])
+        XiTXi = np.empty((gs, gs), dtype=dtype, order="F")
+        X.cov(g, gs, sqrt_weights, XiTXi)
+        Xi_means = X_means[g:g + gs]
+        if intercept:
+            XiTXi -= Xi_means[:, None] @ Xi_means[None]
+        evars, v = np.linalg.eigh(XiTXi)
+        svars.append(np.maximum(evars, 0))
+        smeans.append(Xi_means)
+        strans.append(np.asfortranarray(v, dtype=dtype))
+    s.screen_vars = np.concatenate(svars).astype(dtype) if svars else np.zeros(0, dtype=dtype)
+    s.screen_X_means = np.concatenate(smeans).astype(dtype) if smeans else np.zeros(0, dtype=dtype)
+    s.screen_transforms = strans
+    s.resid_sum = dtype(np.sum(s.weights * s.resid))
+    return s
+
+
+class gaussian_pin_cov_base(gaussian_pin_base):
+    """Gaussian pin state, covariance method (reference ``state.py:723-1004``)."""
+
+    _method = _abi.PIN_COV
+
+    def check(self, method: str = None, logger=logger):
+        ok = super().check(method=method, logger=logger)
+        ok &= self._check(isinstance(self.A, (_matrix.MatrixCovBase64, _matrix.MatrixCovBase32)), "A type", method, logger)
+        return ok
+
+    def _marshal_method(self, a, keep):
+        dtype = self.dtype
+        sg = np.ascontiguousarray(self.screen_grad, dtype=dtype)
+        if len(sg) != len(self.screen_beta):
+            raise RuntimeError("adelie_core: screen_grad must hold one value per screen coefficient.")
+        keep.append(sg)
+        a.rdev_tol = float(self.rdev_tol)
+        a.intercept = 0
+        return sg.ctypes.data
+
+    def _from_result_method(self, new, backend, r, sc, vec):
+        new.screen_grad = vec("screen_grad").astype(self.dtype)
+
+
+def gaussian_pin_cov(
+    *, A, constraints, groups, alpha, penalty, screen_set, lmda_path, rsq, screen_beta, screen_grad, screen_is_active,
+    active_set_size, active_set, max_active_size=None, max_iters=int(1e5), tol=1e-7, rdev_tol=1e-4, newton_tol=1e-12,
+    newton_max_iters=1000, n_threads=1,
+):
+    """Creates a Gaussian, pin, covariance method state object (reference ``adelie.state.gaussian_pin_cov``,
+    ``state.py:739-1004``; argument meaning, defaults and attribute names identical).  ``screen_grad`` is
+    ``v_S - A_SS beta_S`` in screen-value order; the solved state carries the final one.  ``intercepts`` are zeros.
+
+    The constructor derives ``group_sizes``, ``screen_begins``, ``max_active_size = min(., G)`` and, from ``A.to_dense`` per
+    screen group through ``eigh`` with the eigenvalues clamped at 0, ``screen_vars`` and ``screen_transforms``.
+
+    ``A`` is a native covariance handle: ``matrix.dense(method="cov")``, ``matrix.lazy_cov`` and
+    ``matrix.sparse(method="cov", resident="csc")`` run through the same driver.  Any non-``None`` entry of ``constraints``
+    is refused: use ``gaussian_cov``.  Routes, the ``pin_path_launch`` config, the benchmark vectors and the counters are those
+    of :func:`gaussian_pin_naive`; the exit rule is ``rsqs[l] - rsqs[l-1] <= rdev_tol * rsqs[l]``."""
+    if not isinstance(A, (_matrix.MatrixCovBase64, _matrix.MatrixCovBase32)):
+        raise ValueError("A must be an instance of MatrixCovBase32 or MatrixCovBase64.")
+    _pin_refuse_constraints(constraints, "gaussian_cov")
+    _pin_backend(A, "A")
+    dtype = A.dtype
+    s = gaussian_pin_cov_base()
+    s._init_common(A, dtype, groups, alpha, penalty, screen_set, lmda_path, rsq, screen_beta, screen_is_active,
+                   active_set_size, active_set, max_active_size, max_iters, tol, newton_tol, newton_max_iters, n_threads)
+    s.A = A
+    s.rdev_tol = rdev_tol
+    s.intercept = False
+    s.screen_grad = np.array(screen_grad, copy=True, dtype=dtype)
+    svars, strans = [], []
+    for i in s.screen_set:
+        g, gs = int(s.groups[i]), int(s.group_sizes[i])
+        Aii = np.empty((gs, gs), dtype=dtype, order="F")
+        A.to_dense(g, gs, Aii)
+        dsq, v = np.linalg.eigh(Aii)
+        svars.append(np.maximum(dsq, 0))
+        strans.append(np.asfortranarray(v, dtype=dtype))
+    s.screen_vars = np.concatenate(svars).astype(dtype) if svars else np.zeros(0, dtype=dtype)
+    s.screen_transforms = strans
+    return s

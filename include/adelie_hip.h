@@ -77,7 +77,9 @@ int         adelie_hip_device_count(void);
  * "bvls_lds_max_ns" (default 0 = as many as the device's LDS holds) keeps the fit kernel's per-coordinate state in global
  * memory for screen sets larger than the value (test hook: both forms give the same bits).
  * adelie_hip_qp_full_solve: "qp_full_lds_max_d" (default 0 = as many as the device's LDS holds) keeps the per-coordinate state of
- * a problem with d > 64 in global memory from that d on (test hook: both forms give the same bits). */
+ * a problem with d > 64 in global memory from that d on (test hook: both forms give the same bits).
+ * adelie_hip_gaussian_pin_solve: "pin_path_launch" (0/1, default 1): a pin path on a screen set that the single-workgroup
+ * descent takes runs in one launch (1) or in one launch per lambda (0); both give the same bits.  Read when a solve starts. */
 int         adelie_hip_set_config(const char* name, double value);
 
 /* ------------------------------------------------------------------------------------------
@@ -627,6 +629,29 @@ int adelie_hip_design_cov_mul_batch(adelie_hip_design* A, int64_t L, const int64
 /* MatrixCovBase::to_dense (:64-74): out = A[i:i+q, i:i+q], (q, q) column-major */
 int adelie_hip_design_cov_to_dense(adelie_hip_design* A, int64_t i, int64_t q, void* out);
 int adelie_hip_gaussian_cov_solve(adelie_hip_design* A, const adelie_hip_grpnet_args* args, adelie_hip_result** out);
+/* == adelie.state.gaussian_pin_naive(...).solve() / gaussian_pin_cov(...).solve()  (solver_gaussian_pin_naive.hpp:217-401,
+ * solver_gaussian_pin_cov.hpp:530-705): block coordinate descent along args->lmda_path on a screen set that never changes.
+ * No screening, no KKT sweep, no lambda_max search.  `method` is ADELIE_HIP_PIN_NAIVE (a naive design) or ADELIE_HIP_PIN_COV
+ * (a covariance handle; `screen_grad`, in the handle's dtype, holds v_S - A_SS beta_S in screen-value order and is ignored by
+ * the naive method).  Of the args the entry reads what a pin state has: the problem (G, groups, group_sizes, alpha, penalty),
+ * the Gaussian block (weights, X_means, y_mean, y_var; naive only), resid, rsq, resid_sum, lmda_path / n_lmda_path,
+ * max_active_size, max_iters, tol, adev_tol, ddev_tol, rdev_tol, newton_tol, newton_max_iters, intercept, n_threads and the
+ * warm-start block (screen_set, screen_beta, screen_is_active, active_set_size, active_set).  tol is absolute, as in the
+ * reference's pin states; adev_tol / ddev_tol are taken as they come; max_iters bounds the iterations of the whole path.
+ * grad and cov_v may be NULL (with cov_v NULL the linear term is put back together from screen_grad).  Constraints and
+ * penalty_l2 are refused; so is a multi-response view.
+ * A screen set that the single-workgroup descent takes runs the whole path in ONE launch (kernels_cd_pin.hip), or -- with
+ * adelie_hip_set_config("pin_path_launch", 0) -- one launch per lambda; both give the same bits.  Larger screen sets run the
+ * block / panel engines, one fit per lambda.  The path stops after the first lambda that meets an exit rule (naive:
+ * rsq >= adev_tol * y_var, or rsqs[l] - rsqs[l-1] <= ddev_tol * y_var; cov: rsqs[l] - rsqs[l-1] <= rdev_tol * rsqs[l]); that
+ * row is kept.  A lambda that fails ("max coordinate descents reached at lambda index: l.", "Maximum number of active groups
+ * reached.") ends the solve: the rows before it are kept, the state is the one the last solved lambda left, the message is
+ * adelie_hip_result_error.  Results: the accessors below; ADELIE_HIP_V_RSQS, ADELIE_HIP_V_BENCHMARK_SCREEN / _ACTIVE,
+ * ADELIE_HIP_V_SCREEN_GRAD, ADELIE_HIP_I_ACTIVE_BEGINS / _ORDER and ADELIE_HIP_S_PIN_ITERS belong to this entry.
+ * The entry is additive and changes the layout of no existing structure: ADELIE_HIP_ABI_VERSION stays as it is. */
+enum adelie_hip_pin_method { ADELIE_HIP_PIN_NAIVE = 0, ADELIE_HIP_PIN_COV = 1 };
+int adelie_hip_gaussian_pin_solve(adelie_hip_design* X, const adelie_hip_grpnet_args* args, int method, const void* screen_grad,
+                                  adelie_hip_result** out);
 int adelie_hip_result_destroy(adelie_hip_result* r);
 
 /* ---- result accessors: the read-only properties of py_state.cpp:763-1040,1156-1217 ---- */
@@ -638,6 +663,9 @@ enum adelie_hip_vec {
     ADELIE_HIP_V_SCREEN_TRANSFORMS, /* concatenated column-major (q,q) blocks in screen order */
     ADELIE_HIP_V_BENCHMARK_SCREEN, ADELIE_HIP_V_BENCHMARK_FIT_SCREEN, ADELIE_HIP_V_BENCHMARK_FIT_ACTIVE,
     ADELIE_HIP_V_BENCHMARK_KKT, ADELIE_HIP_V_BENCHMARK_INVARIANCE,
+    /* adelie_hip_gaussian_pin_solve: rsq after each solved lambda; the active-pass share of each lambda's time (the screen-pass
+     * share is ADELIE_HIP_V_BENCHMARK_SCREEN); the final screen gradient of the covariance method */
+    ADELIE_HIP_V_RSQS, ADELIE_HIP_V_BENCHMARK_ACTIVE, ADELIE_HIP_V_SCREEN_GRAD,
     /* index vectors (copied out as int64) */
     ADELIE_HIP_I_SCREEN_SET = 100, ADELIE_HIP_I_SCREEN_BEGINS, ADELIE_HIP_I_SCREEN_IS_ACTIVE,
     ADELIE_HIP_I_ACTIVE_SET, ADELIE_HIP_I_N_VALID_SOLUTIONS, ADELIE_HIP_I_ACTIVE_SIZES,
@@ -649,6 +677,8 @@ enum adelie_hip_vec {
      * indices; their multipliers are the entries of ADELIE_HIP_V_CONSTRAINT_VMU) -- the binding reads this list instead of
      * re-deriving the library's rule, and the objects of every other group stayed live on the caller's side */
     ADELIE_HIP_I_CONSTRAINT_DEV_GROUPS,
+    /* adelie_hip_gaussian_pin_solve: active_begins / active_order of the reference's pin states */
+    ADELIE_HIP_I_ACTIVE_BEGINS, ADELIE_HIP_I_ACTIVE_ORDER,
     /* betas values (double), CSR (L, p) like convert_sparse_to_dense's input, py_state.cpp:9-60 */
     ADELIE_HIP_V_BETAS_VALUES = 200,
     ADELIE_HIP_V_DUALS_VALUES,
@@ -706,7 +736,11 @@ enum adelie_hip_scalar {
     /* 1 when the set-up of this solve left the panel engines open to it (they take a fit once its screen set is large enough),
      * 0 when it kept the solve on the full-Gram engines throughout: the covariance method, a design kept sparse or a
      * standardized view without their panel forms, and always a design made of pieces (adelie_hip_design_create_pieces) */
-    ADELIE_HIP_S_ENGINE_PANEL
+    ADELIE_HIP_S_ENGINE_PANEL,
+    /* adelie_hip_gaussian_pin_solve: iterations (passes) of the whole path; descent launches (one-launch route: 1; one launch
+     * per lambda: the lambdas it ran; block / panel engines: their fits); the route taken (1: one launch, 2: one launch per
+     * lambda, 3: block engine, 4: panel engine) */
+    ADELIE_HIP_S_PIN_ITERS, ADELIE_HIP_S_N_PIN_LAUNCHES, ADELIE_HIP_S_PIN_ROUTE
 };
 int64_t     adelie_hip_result_size(const adelie_hip_result* r, int which);
 /* Copies min(size, cap) elements: value vectors as double, index vectors as int64. */
