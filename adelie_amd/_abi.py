@@ -282,6 +282,23 @@ class MultiPiece(C.Structure):
     )
 
 
+# adelie_hip_glm_piece_mode
+(GLM_PIECE_PREPARE, GLM_PIECE_WEIGHTS, GLM_PIECE_FINISH, GLM_PIECE_NULL_STEP, GLM_PIECE_GRADIENT, GLM_PIECE_LOSS, GLM_PIECE_LOSS2,
+ GLM_PIECE_MULTI_LOSS2, GLM_PIECE_SET_ETA, GLM_PIECE_DOT_DIFF, GLM_PIECE_REL_CHANGE, GLM_PIECE_GATHER, GLM_PIECE_SCATTER) = range(13)
+
+
+class GlmPiece(C.Structure):
+    """adelie_hip_glm_piece (include/adelie_hip.h): every field 8 bytes wide."""
+    _fields_ = (
+        [(n, C.c_int64) for n in ("dtype", "mode", "kind", "n", "nb", "K")]
+        + [(n, C.c_double) for n in ("hmin", "hess_sum", "shift", "b0", "sentinel")]
+        + [(n, C.c_void_p) for n in ("y", "w", "wb", "eta", "resid", "off", "hess", "irls_resid", "irls_y", "wts", "cb_z", "b0v",
+                                     "resid_prev", "eta_prev", "prev", "src", "idx", "dst")]
+        + [(n, C.c_int64) for n in ("cnt", "src_elems", "dst_elems")]
+        + [("sums", C.c_void_p)]
+    )
+
+
 # every symbol include/adelie_hip.h declares (checked by tests/test_abi.py)
 HIP_SYMBOLS = [
     "abi_version", "last_error", "device_count", "set_config",
@@ -298,7 +315,7 @@ HIP_SYMBOLS = [
     "gaussian_pin_solve",
     "glm_cox_create", "glm_cox_destroy", "glm_cox_eval",
     "grpnet_solve", "grpnet_solve_many", "result_destroy", "result_size", "result_copy", "result_scalar", "result_error", "result_sync",
-    "bench_sweep", "filter_sweep_test", "block_build_test", "group_piece_test", "multi_piece_test", "cov_piece_test",
+    "bench_sweep", "filter_sweep_test", "block_build_test", "group_piece_test", "multi_piece_test", "glm_piece_test", "cov_piece_test",
     "css_cov_solve", "css_result_destroy", "css_result_size", "css_result_copy", "css_result_scalar", "css_result_error",
     "bvls_solve", "bvls_result_destroy", "bvls_result_size", "bvls_result_copy", "bvls_result_scalar", "bvls_result_error",
     "design_create_constraint_dense", "design_adopt_constraint_dense_dev", "design_create_constraint_csc", "constraint_op",
@@ -432,6 +449,7 @@ class Backend:
         sig("block_build_test", ci, [vp, ci, i64, vp, vp, i64, vp, i64, vp, ci, i64, ci, vp, i64, vp, i64, vp])
         sig("group_piece_test", ci, [p(GroupPiece), vp])
         sig("multi_piece_test", ci, [p(MultiPiece), vp])
+        sig("glm_piece_test", ci, [p(GlmPiece), vp])
         sig("cov_piece_test", ci, [vp, ci, vp, i64, i64, i64, i64, dbl, vp, vp, vp, i64, vp])
         sig("css_cov_solve", ci, [vp, p(CssArgs), p(vp)])
         sig("css_result_destroy", ci, [vp])

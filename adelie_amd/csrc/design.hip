@@ -355,17 +355,6 @@ void op_sp_tmul(adelie_hip_design* d, int64_t L, const int64_t* indptr, const in
     });
 }
 
-} // namespace
-namespace ahip {
-template <class T>
-void launch_glm_loss2(int kind, const T* y, const T* wa, const T* wb, const T* base, T b0, const T* off, int64_t n, T* sums,
-                      hipStream_t s);
-template <class T>
-void launch_multi_loss2(int kind, const T* y, const T* wa, const T* wb, const T* base, const T* b0, const T* off, int64_t nb,
-                        int K, T* sums, hipStream_t s);
-}
-namespace {
-
 // Per-row losses of eta_l = X beta_l + intercepts[l] + offsets under two weight vectors, without moving eta to the host.
 template <class T>
 void op_path_losses(adelie_hip_design* d, int kind, int64_t L, const int64_t* indptr, const int64_t* indices,

@@ -752,6 +752,13 @@ struct IrlsScalars {
 };
 // step 1: hess/irls_resid from (eta, resid); partial sums
 // (implemented in kernels_glm.hip; declared there to keep this header small)
+// the losses of eta = base + b0 + off under two weight vectors (design.hip's path losses; kernels_glm.hip)
+template <class T>
+void launch_glm_loss2(int kind, const T* y, const T* wa, const T* wb, const T* base, T b0, const T* off, int64_t n, T* sums,
+                      hipStream_t s);
+template <class T>
+void launch_multi_loss2(int kind, const T* y, const T* wa, const T* wb, const T* base, const T* b0, const T* off, int64_t nb,
+                        int K, T* sums, hipStream_t s);
 
 // ---- misc -------------------------------------------------------------------------------------
 // copy a (rows x cols) block between column-major matrices with different leading dimensions

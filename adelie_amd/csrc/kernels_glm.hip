@@ -57,15 +57,22 @@ __global__ void final_reduce_kernel(T* sums, int K) {
     }
 }
 
+// The family members below are evaluated operation by operation, as the reference's Eigen expressions are: no multiply is fused
+// into a following add or subtract.  With contraction left to the compiler, the packed two-trip body of an unrolled grid-stride
+// loop and its remainder came out with different fusions of the probit member (float32, n = 131149 against the same elements at
+// n = 131), so the last bits of an observation's gradient depended on how many trips its thread made, and irls_finish and
+// glm_gradient could disagree on the same (y, w, eta).
+#define GLM_NO_CONTRACT _Pragma("clang fp contract(off)")
 // binomial probit helpers (glm_binomial.ipp:100-120)
-template <class T> __device__ __forceinline__ T std_cdf(T x) { return T(0.5) * (T(1) + erf(x * T(0.70710678118654752440))); }
-template <class T> __device__ __forceinline__ T std_pdf(T x) { return T(0.39894228040143267794) * exp(T(-0.5) * x * x); }
+template <class T> __device__ __forceinline__ T std_cdf(T x) { GLM_NO_CONTRACT return T(0.5) * (T(1) + erf(x * T(0.70710678118654752440))); }
+template <class T> __device__ __forceinline__ T std_pdf(T x) { GLM_NO_CONTRACT return T(0.39894228040143267794) * exp(T(-0.5) * x * x); }
 template <class T> __device__ __forceinline__ T fmax_of();
 template <> __device__ __forceinline__ double fmax_of<double>() { return 1.7976931348623157e308; }
 template <> __device__ __forceinline__ float fmax_of<float>() { return 3.402823466e38f; }
 
 template <class T>
 __device__ __forceinline__ T glm_grad(int kind, T y, T w, T eta) {
+    GLM_NO_CONTRACT
     if (kind == ADELIE_HIP_GLM_BINOMIAL_LOGIT) return w * (y - T(1) / (T(1) + exp(-eta)));
     if (kind == ADELIE_HIP_GLM_POISSON) return w * (y - exp(eta));                        // glm_poisson.ipp:14-23
     if (kind == ADELIE_HIP_GLM_BINOMIAL_PROBIT) {                                         // glm_binomial.ipp:131-143
@@ -77,6 +84,7 @@ __device__ __forceinline__ T glm_grad(int kind, T y, T w, T eta) {
 // per-observation loss without the weight (glm_*.ipp loss members)
 template <class T>
 __device__ __forceinline__ T glm_loss_term(int kind, T y, T e) {
+    GLM_NO_CONTRACT
     if (kind == ADELIE_HIP_GLM_BINOMIAL_LOGIT) return (T(e > T(0)) - y) * e + log(T(1) + exp(-fabs(e)));
     if (kind == ADELIE_HIP_GLM_POISSON) return min(-e, fmax_of<T>()) * y + exp(e);        // glm_poisson.ipp:36-44
     if (kind == ADELIE_HIP_GLM_BINOMIAL_PROBIT) {                                         // glm_binomial.ipp:161-173
@@ -88,6 +96,7 @@ __device__ __forceinline__ T glm_loss_term(int kind, T y, T e) {
 // multinomial (glm_multinomial.ipp:47-66): w is the observation weight repeated for every class, K the class count
 template <class T>
 __device__ __forceinline__ T glm_hess(int kind, T y, T w, T grad, T eta, int K = 1) {
+    GLM_NO_CONTRACT
     if (kind == ADELIE_HIP_GLM_POISSON) return w * y - grad;                              // glm_poisson.ipp:25-34
     if (kind == ADELIE_HIP_GLM_BINOMIAL_PROBIT) {                                         // glm_binomial.ipp:145-159
         const T mx = fmax_of<T>(), c = std_cdf(eta), pd = std_pdf(eta), c1 = T(1) - c;

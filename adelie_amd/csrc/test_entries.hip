@@ -15,6 +15,37 @@
 #include <string>
 #include <vector>
 
+namespace ahip {
+// the IRLS launchers of kernels_glm.hip, as solver.hip declares them beside its path driver (launch_glm_loss2 and
+// launch_multi_loss2 are in kernels.hpp)
+template <class T>
+void launch_irls_prepare(int kind, const T* y, const T* w, const T* eta, const T* resid, const T* offsets, T hessian_min,
+                         int64_t n, T* hess, T* irls_resid, T* irls_y, T* sums, hipStream_t s, int K);
+template <class T>
+void launch_irls_weights(const T* hess, T hess_sum, const T* irls_y, T shift, int64_t n, T* wts, T* irls_resid, T* sums,
+                         hipStream_t s);
+template <class T>
+void launch_irls_finish(int kind, const T* y, const T* w, const T* irls_y, const T* offsets, const T* irls_resid, T shift,
+                        int64_t n, T* eta, T* resid, T* sums, hipStream_t s, int K);
+template <class T>
+void launch_glm_gradient(int kind, const T* y, const T* w, const T* eta, int64_t n, T* resid, hipStream_t s, int K);
+template <class T>
+void launch_glm_loss(int kind, const T* y, const T* w, const T* eta, int64_t n, T* sums, hipStream_t s, int K);
+template <class T>
+void launch_null_step(int kind, const T* y, const T* w, const T* eta, const T* resid, const T* offsets, T hessian_min,
+                      int64_t n, T* sums, hipStream_t s, int K, const T* cb_hess, const T* cb_z);
+template <class T>
+void launch_set_eta(const T* offsets, T beta0, int64_t n, T* eta, hipStream_t s);
+template <class T>
+void launch_dot_diff(const T* a, const T* a0, const T* b, const T* b0, int64_t n, T* sums, hipStream_t s);
+template <class T>
+void launch_rel_change(const T* a, T* prev, int64_t n, T* out, hipStream_t s);
+template <class T>
+void launch_gather(const T* src, const int32_t* idx, int64_t cnt, T* dst, hipStream_t s);
+template <class T>
+void launch_scatter(const T* src, const int32_t* idx, int64_t cnt, T* dst, hipStream_t s);
+} // namespace ahip
+
 using namespace ahip;
 
 namespace {
@@ -734,6 +765,211 @@ int adelie_hip_multi_piece_test(const adelie_hip_multi_piece* a, int64_t* info) 
         if (a->w) st.up(dw, static_cast<const T*>(a->w), pb);
         launch_batch_pick<T>(dv.p, pb, int(K), int(a->lsel), dr.p, a->w ? dw.p : nullptr, dout.p, s);
         st.finish(a->out, dout.p, size_t(pb) * sizeof(T));
+    };
+    DTYPE_DISPATCH(a, body(T{}))
+    ABI_CATCH
+}
+
+// One launcher of kernels_glm.hip on caller-supplied inputs (include/adelie_hip.h has the modes and the arrays).
+int adelie_hip_glm_piece_test(const adelie_hip_glm_piece* a, int64_t* info) {
+    ABI_TRY
+    if (!a || !info) throw make_core_error("bad arguments.");
+    if (a->dtype != ADELIE_HIP_F64 && a->dtype != ADELIE_HIP_F32) throw make_core_error("bad dtype.");
+    if (a->mode < ADELIE_HIP_GLM_PIECE_PREPARE || a->mode > ADELIE_HIP_GLM_PIECE_SCATTER) throw make_core_error("unknown mode.");
+    constexpr int64_t BIG = int64_t(1) << 24, SUMS = 16 + 4 * 256;
+    const int mode = int(a->mode);
+    const int64_t n = a->n, nb = a->nb, K = a->K, cnt = a->cnt;
+    const bool moves = mode == ADELIE_HIP_GLM_PIECE_GATHER || mode == ADELIE_HIP_GLM_PIECE_SCATTER;
+    const bool irls = mode == ADELIE_HIP_GLM_PIECE_PREPARE || mode == ADELIE_HIP_GLM_PIECE_FINISH || mode == ADELIE_HIP_GLM_PIECE_NULL_STEP;
+    const bool member = irls || mode == ADELIE_HIP_GLM_PIECE_GRADIENT || mode == ADELIE_HIP_GLM_PIECE_LOSS ||
+                        mode == ADELIE_HIP_GLM_PIECE_LOSS2 || mode == ADELIE_HIP_GLM_PIECE_MULTI_LOSS2; // takes a kind
+    const bool reduces = !(moves || mode == ADELIE_HIP_GLM_PIECE_FINISH || mode == ADELIE_HIP_GLM_PIECE_GRADIENT ||
+                           mode == ADELIE_HIP_GLM_PIECE_SET_ETA);
+    int kind = 0;
+    bool multinomial = false, cb = false, pre = false;
+    if (member) {
+        if (a->kind < ADELIE_HIP_GLM_GAUSSIAN || a->kind > ADELIE_HIP_GLM_COX) throw make_core_error("unknown kind.");
+        kind = int(a->kind);
+        multinomial = kind == ADELIE_HIP_GLM_MULTINOMIAL;
+        cb = kind == ADELIE_HIP_GLM_CALLBACK;
+        pre = cb || kind == ADELIE_HIP_GLM_COX;
+        if (pre && !irls) throw make_core_error("the CALLBACK and COX kinds are taken by PREPARE, FINISH and NULL_STEP only.");
+        if (mode == ADELIE_HIP_GLM_PIECE_MULTI_LOSS2 && kind != ADELIE_HIP_GLM_GAUSSIAN && !multinomial)
+            throw make_core_error("MULTI_LOSS2 takes the kinds GAUSSIAN and MULTINOMIAL.");
+        if (mode == ADELIE_HIP_GLM_PIECE_LOSS2 && multinomial) throw make_core_error("LOSS2 does not take MULTINOMIAL (MULTI_LOSS2 does).");
+    }
+    // the sizes the kernels index by
+    const bool row_coupled = mode == ADELIE_HIP_GLM_PIECE_MULTI_LOSS2 ||
+                             (multinomial && (mode == ADELIE_HIP_GLM_PIECE_PREPARE || mode == ADELIE_HIP_GLM_PIECE_FINISH ||
+                                              mode == ADELIE_HIP_GLM_PIECE_GRADIENT || mode == ADELIE_HIP_GLM_PIECE_LOSS));
+    if (!moves) {
+        if (n < 1 || n > BIG) throw make_core_error("1 <= n <= 2^24 is required.");
+        if (row_coupled && (K < 1 || K > 64 || nb < 1 || nb > BIG || n != nb * K))
+            throw make_core_error("a row-coupled launch needs 1 <= K <= 64, nb >= 1 and n == nb * K.");
+        if (multinomial && mode == ADELIE_HIP_GLM_PIECE_NULL_STEP && (K < 1 || K > 64)) throw make_core_error("NULL_STEP: 1 <= K <= 64 is required.");
+    } else {
+        if (cnt < 0 || cnt > BIG || !a->idx || !a->src || !a->dst) throw make_core_error("GATHER / SCATTER: 0 <= cnt <= 2^24, idx, src and dst are required.");
+        const int64_t range = mode == ADELIE_HIP_GLM_PIECE_GATHER ? a->src_elems : a->dst_elems;
+        if (range < 1 || range > BIG) throw make_core_error("GATHER / SCATTER: 1 <= src_elems (dst_elems) <= 2^24 is required.");
+        std::vector<uint8_t> seen(mode == ADELIE_HIP_GLM_PIECE_SCATTER ? size_t(range) : 0, 0);
+        for (int64_t q = 0; q < cnt; ++q) {
+            if (a->idx[q] < 0 || a->idx[q] >= range) throw make_core_error("GATHER / SCATTER: an index lies outside the array it addresses.");
+            if (mode == ADELIE_HIP_GLM_PIECE_SCATTER) {
+                if (seen[size_t(a->idx[q])]) throw make_core_error("SCATTER: the indices must be distinct.");
+                seen[size_t(a->idx[q])] = 1;
+            }
+        }
+    }
+    if (reduces && !a->sums) throw make_core_error("sums is required.");
+    // the arrays the launcher reads or writes for this mode and kind
+    auto need = [&](const void* p, const char* what) {
+        if (!p) throw make_core_error(std::string(what) + " is required for this mode and kind.");
+    };
+    switch (mode) {
+    case ADELIE_HIP_GLM_PIECE_PREPARE:
+        need(a->eta, "eta"), need(a->off, "off"), need(a->hess, "hess"), need(a->irls_resid, "irls_resid"), need(a->irls_y, "irls_y");
+        if (!pre) need(a->y, "y"), need(a->w, "w");
+        if (!cb) need(a->resid, "resid");
+        break;
+    case ADELIE_HIP_GLM_PIECE_WEIGHTS:
+        need(a->hess, "hess"), need(a->irls_y, "irls_y"), need(a->wts, "wts"), need(a->irls_resid, "irls_resid");
+        if (!(a->hess_sum == a->hess_sum) || a->hess_sum == 0) throw make_core_error("WEIGHTS: hess_sum must be a non-zero number.");
+        break;
+    case ADELIE_HIP_GLM_PIECE_FINISH:
+        need(a->irls_y, "irls_y"), need(a->off, "off"), need(a->irls_resid, "irls_resid"), need(a->eta, "eta"), need(a->resid, "resid");
+        if (!pre) need(a->y, "y"), need(a->w, "w");
+        break;
+    case ADELIE_HIP_GLM_PIECE_NULL_STEP:
+        need(a->eta, "eta"), need(a->off, "off");
+        if (!pre) need(a->y, "y"), need(a->w, "w");
+        if (!cb) need(a->resid, "resid");
+        if (pre) need(a->hess, "hess");
+        if (cb) need(a->cb_z, "cb_z");
+        break;
+    case ADELIE_HIP_GLM_PIECE_GRADIENT:
+        need(a->y, "y"), need(a->w, "w"), need(a->eta, "eta"), need(a->resid, "resid");
+        break;
+    case ADELIE_HIP_GLM_PIECE_LOSS:
+        need(a->y, "y"), need(a->w, "w"), need(a->eta, "eta");
+        break;
+    case ADELIE_HIP_GLM_PIECE_LOSS2:
+    case ADELIE_HIP_GLM_PIECE_MULTI_LOSS2:
+        need(a->y, "y"), need(a->w, "w"), need(a->wb, "wb"), need(a->eta, "eta"), need(a->off, "off");
+        if (mode == ADELIE_HIP_GLM_PIECE_MULTI_LOSS2) need(a->b0v, "b0v");
+        break;
+    case ADELIE_HIP_GLM_PIECE_SET_ETA:
+        need(a->off, "off"), need(a->eta, "eta");
+        break;
+    case ADELIE_HIP_GLM_PIECE_DOT_DIFF:
+        need(a->resid, "resid"), need(a->resid_prev, "resid_prev"), need(a->eta, "eta"), need(a->eta_prev, "eta_prev");
+        break;
+    case ADELIE_HIP_GLM_PIECE_REL_CHANGE:
+        need(a->wts, "wts"), need(a->prev, "prev");
+        break;
+    default: break;
+    }
+    AHIP_CHECK(hipSetDevice(0));
+    hipStream_t s = nullptr;
+    Stage st{s};
+    for (int q = 0; q < 8; ++q) info[q] = 0;
+    auto body = [&](auto tag) {
+        using T = decltype(tag);
+        DevBuf<T> dy, dw, dwb, deta, dresid, doff, dhess, dir, diy, dwts, dz, db0v, drp, dep, dprev, dsrc, ddst, dsums;
+        DevBuf<int32_t> didx;
+        // an array of `len` values on the device, or no array where the caller gave none
+        auto put = [&](DevBuf<T>& buf, const void* h, int64_t len) -> T* {
+            if (!h) return nullptr;
+            st.up(buf, static_cast<const T*>(h), len);
+            return buf.p;
+        };
+        if (moves) {
+            const bool gather = mode == ADELIE_HIP_GLM_PIECE_GATHER;
+            const int64_t ns = gather ? a->src_elems : std::max<int64_t>(cnt, 1), nd = gather ? std::max<int64_t>(cnt, 1) : a->dst_elems;
+            const int64_t ups = gather ? a->src_elems : cnt, upd = gather ? cnt : a->dst_elems;
+            dsrc.reserve(size_t(ns)); ddst.reserve(size_t(nd)); didx.reserve(size_t(std::max<int64_t>(cnt, 1)));
+            if (ups > 0) dsrc.upload(static_cast<const T*>(a->src), size_t(ups), s);
+            if (upd > 0) ddst.upload(static_cast<const T*>(a->dst), size_t(upd), s);
+            if (cnt > 0) didx.upload(a->idx, size_t(cnt), s);
+            if (gather) launch_gather<T>(dsrc.p, didx.p, cnt, ddst.p, s);
+            else launch_scatter<T>(dsrc.p, didx.p, cnt, ddst.p, s);
+            info[0] = 1;
+            AHIP_CHECK(hipGetLastError());
+            if (upd > 0) st.fetch(a->dst, ddst.p, size_t(upd) * sizeof(T));
+            st.land();
+            return;
+        }
+        const std::vector<T> hs(size_t(SUMS), T(a->sentinel));
+        st.up(dsums, hs.data(), SUMS);
+        T* sums = dsums.p;
+        const int64_t nw = mode == ADELIE_HIP_GLM_PIECE_MULTI_LOSS2 ? nb : n; // (MULTI_LOSS2: one weight per observation)
+        const T* y = put(dy, a->y, n);
+        const T* w = put(dw, a->w, nw);
+        const T* wb = put(dwb, a->wb, nw);
+        T* eta = put(deta, a->eta, n);
+        T* resid = put(dresid, a->resid, n);
+        const T* off = put(doff, a->off, n);
+        T* hess = put(dhess, a->hess, n);
+        T* ir = put(dir, a->irls_resid, n);
+        T* iy = put(diy, a->irls_y, n);
+        T* wts = put(dwts, a->wts, n);
+        const T* z = put(dz, a->cb_z, n);
+        const T* b0v = put(db0v, a->b0v, std::max<int64_t>(K, 1));
+        const T* rp = put(drp, a->resid_prev, n);
+        const T* ep = put(dep, a->eta_prev, n);
+        T* prev = put(dprev, a->prev, n);
+        auto back = [&](void* h, const T* dev, int64_t len) { st.fetch(h, dev, size_t(len) * sizeof(T)); };
+        const int Ki = int(std::max<int64_t>(K, 1));
+        switch (mode) {
+        case ADELIE_HIP_GLM_PIECE_PREPARE:
+            launch_irls_prepare<T>(kind, y, w, eta, resid, off, T(a->hmin), n, hess, ir, iy, sums, s, Ki);
+            AHIP_CHECK(hipGetLastError());
+            back(a->hess, hess, n), back(a->irls_resid, ir, n), back(a->irls_y, iy, n);
+            break;
+        case ADELIE_HIP_GLM_PIECE_WEIGHTS:
+            launch_irls_weights<T>(hess, T(a->hess_sum), iy, T(a->shift), n, wts, ir, sums, s);
+            AHIP_CHECK(hipGetLastError());
+            back(a->wts, wts, n), back(a->irls_resid, ir, n);
+            break;
+        case ADELIE_HIP_GLM_PIECE_FINISH:
+            launch_irls_finish<T>(kind, y, w, iy, off, ir, T(a->shift), n, eta, resid, sums, s, Ki);
+            AHIP_CHECK(hipGetLastError());
+            back(a->eta, eta, n), back(a->resid, resid, n);
+            break;
+        case ADELIE_HIP_GLM_PIECE_NULL_STEP:
+            launch_null_step<T>(kind, y, w, eta, resid, off, T(a->hmin), n, sums, s, Ki, hess, z);
+            break;
+        case ADELIE_HIP_GLM_PIECE_GRADIENT:
+            launch_glm_gradient<T>(kind, y, w, eta, n, resid, s, Ki);
+            AHIP_CHECK(hipGetLastError());
+            back(a->resid, resid, n);
+            break;
+        case ADELIE_HIP_GLM_PIECE_LOSS:
+            launch_glm_loss<T>(kind, y, w, eta, n, sums, s, Ki);
+            break;
+        case ADELIE_HIP_GLM_PIECE_LOSS2:
+            launch_glm_loss2<T>(kind, y, w, wb, eta, T(a->b0), off, n, sums, s);
+            break;
+        case ADELIE_HIP_GLM_PIECE_MULTI_LOSS2:
+            launch_multi_loss2<T>(kind, y, w, wb, eta, b0v, off, nb, Ki, sums, s);
+            break;
+        case ADELIE_HIP_GLM_PIECE_SET_ETA:
+            launch_set_eta<T>(off, T(a->b0), n, eta, s);
+            AHIP_CHECK(hipGetLastError());
+            back(a->eta, eta, n);
+            break;
+        case ADELIE_HIP_GLM_PIECE_DOT_DIFF:
+            launch_dot_diff<T>(resid, rp, eta, ep, n, sums, s);
+            break;
+        default: // REL_CHANGE
+            launch_rel_change<T>(wts, prev, n, sums + 15, s);
+            AHIP_CHECK(hipGetLastError());
+            back(a->prev, prev, n);
+            break;
+        }
+        info[0] = 1;
+        AHIP_CHECK(hipGetLastError());
+        if (reduces) back(a->sums, sums, 16);
+        st.land();
     };
     DTYPE_DISPATCH(a, body(T{}))
     ABI_CATCH

@@ -1154,6 +1154,72 @@ typedef struct adelie_hip_multi_piece {
 } adelie_hip_multi_piece;
 int adelie_hip_multi_piece_test(const adelie_hip_multi_piece* a, int64_t* info);
 
+/* One launcher of kernels_glm.hip -- the elementwise and reduction kernels every IRLS iteration runs -- on caller-supplied inputs
+ * (tests): uploads, calls exactly the launch_* the solver calls on one stream, synchronises, downloads.  No design handle is used.
+ * Every field is 8 bytes wide; value arrays are of `dtype` (adelie_hip_dtype), index arrays int32, scalars cross as double.  Arrays
+ * marked in/out are pre-filled by the caller and come back whole, so an element the launch did not write shows.  `sums` (out, 16
+ * values) receives the first 16 elements of the device's reduction scratch, which is allocated as the solver allocates it
+ * (16 + 4 * 256 elements) and filled with `sentinel` before the launch: the results of a reduction are sums[0 .. 2], the result of
+ * REL_CHANGE is sums[15], as in the solver.  kind is an adelie_hip_glm_kind; with ADELIE_HIP_GLM_MULTINOMIAL the arrays of n
+ * values are response-major (nb, K), element (i, k) at [k * nb + i], and n == nb * K is required (w: the observation weights
+ * repeated for every class).  A NULL array is accepted only where the launcher does not read it for that kind.  Everything a kernel
+ * indexes by is checked before anything is launched; a call that is refused (nonzero return, adelie_hip_last_error) writes nothing.
+ * info receives 8 values: {launcher calls made, 0, ...}.
+ *   PREPARE: launch_irls_prepare(kind, y, w, eta, resid, off, hmin, n, hess, irls_resid, irls_y, sums, K); hess, irls_resid, irls_y
+ *     in/out.  kinds CALLBACK and COX read hess, CALLBACK reads irls_resid; y, w may be NULL for those, resid for CALLBACK.
+ *   WEIGHTS: launch_irls_weights(hess, hess_sum, irls_y, shift, n, wts, irls_resid, sums); wts, irls_resid in/out.
+ *   FINISH: launch_irls_finish(kind, y, w, irls_y, off, irls_resid, shift, n, eta, resid, sums, K); eta, resid in/out; y, w may be
+ *     NULL for CALLBACK and COX.
+ *   NULL_STEP: launch_null_step(kind, y, w, eta, resid, off, hmin, n, sums, K, hess, cb_z); hess is required for CALLBACK and COX,
+ *     cb_z for CALLBACK (y, w, and for CALLBACK resid, may be NULL then).  K >= 1 for MULTINOMIAL, n is the length of the one
+ *     class handed in (the solver calls it class by class).
+ *   GRADIENT: launch_glm_gradient(kind, y, w, eta, n, resid, K); resid in/out.   LOSS: launch_glm_loss(kind, y, w, eta, n, sums, K).
+ *   LOSS2: launch_glm_loss2(kind, y, w, wb, eta, b0, off, n, sums): eta holds the base.
+ *   MULTI_LOSS2: launch_multi_loss2(kind, y, w, wb, eta, b0v, off, nb, K, sums): kind GAUSSIAN (multigaussian) or MULTINOMIAL,
+ *     y / eta / off hold n == nb * K values response-major, w / wb nb values, b0v K values.
+ *     (GRADIENT, LOSS, LOSS2 take the kinds GAUSSIAN .. BINOMIAL_PROBIT; PREPARE, FINISH, NULL_STEP also CALLBACK and COX.)
+ *   SET_ETA: launch_set_eta(off, b0, n, eta); eta in/out.
+ *   DOT_DIFF: launch_dot_diff(resid, resid_prev, eta, eta_prev, n, sums).
+ *   REL_CHANGE: launch_rel_change(wts, prev, n, sums + 15); prev in/out.
+ *   GATHER: launch_gather(src, idx, cnt, dst): dst[a] = src[idx[a]], src holds src_elems, dst (in/out) cnt values.
+ *   SCATTER: launch_scatter(src, idx, cnt, dst): dst[idx[a]] = src[a], distinct indices, src holds cnt, dst (in/out) dst_elems
+ *     values.  cnt == 0 is allowed in both and leaves dst as it was.
+ * The entry is additive and changes the layout of no existing structure: ADELIE_HIP_ABI_VERSION stays as it is. */
+enum adelie_hip_glm_piece_mode {
+    ADELIE_HIP_GLM_PIECE_PREPARE = 0, ADELIE_HIP_GLM_PIECE_WEIGHTS = 1, ADELIE_HIP_GLM_PIECE_FINISH = 2,
+    ADELIE_HIP_GLM_PIECE_NULL_STEP = 3, ADELIE_HIP_GLM_PIECE_GRADIENT = 4, ADELIE_HIP_GLM_PIECE_LOSS = 5,
+    ADELIE_HIP_GLM_PIECE_LOSS2 = 6, ADELIE_HIP_GLM_PIECE_MULTI_LOSS2 = 7, ADELIE_HIP_GLM_PIECE_SET_ETA = 8,
+    ADELIE_HIP_GLM_PIECE_DOT_DIFF = 9, ADELIE_HIP_GLM_PIECE_REL_CHANGE = 10, ADELIE_HIP_GLM_PIECE_GATHER = 11,
+    ADELIE_HIP_GLM_PIECE_SCATTER = 12
+};
+typedef struct adelie_hip_glm_piece {
+    int64_t dtype, mode, kind;
+    int64_t n, nb, K;
+    double hmin, hess_sum, shift, b0, sentinel;
+    const void* y;
+    const void* w;
+    const void* wb;
+    void* eta;
+    void* resid;
+    const void* off;
+    void* hess;
+    void* irls_resid;
+    void* irls_y;
+    void* wts;
+    const void* cb_z;
+    const void* b0v;
+    const void* resid_prev;
+    const void* eta_prev;
+    void* prev;
+    /* GATHER, SCATTER */
+    const void* src;
+    const int32_t* idx;
+    void* dst;
+    int64_t cnt, src_elems, dst_elems;
+    void* sums;
+} adelie_hip_glm_piece;
+int adelie_hip_glm_piece_test(const adelie_hip_glm_piece* a, int64_t* info);
+
 /* One of the two places where the path solver touches the covariance matrix A (dense or kept sparse), through exactly the launcher
  * the solver calls (tests): uploads, launches on A's stream, synchronises, downloads.  Column lists must be distinct and in [0, p).
  *   ADELIE_HIP_COV_PIECE_GATHER: the copy of A[S, S] into the screen Gram matrix for the new screen values [pos0, nv) of the

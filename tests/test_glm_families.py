@@ -132,3 +132,46 @@ def test_cv_device_path_losses(hip, family):
     np.testing.assert_allclose(lb, [glm.reweight(wb).loss(e) for e in eta], rtol=1e-10, atol=1e-12)
     cv = ad.cv_grpnet(Xd, glm, n_folds=3, seed=0, lmda_path_size=6, min_ratio=0.3)
     assert cv.losses.shape == (3, 6) and np.all(np.isfinite(cv.losses))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_path_losses_reach_the_tested_loss_launchers(hip, dtype):
+    """The public route into launch_glm_loss2 / launch_multi_loss2 (design.hip), against the loss references of tests/glm_checks.py:
+    glm_path_losses on an n = 65537 (a second stride trip), p = 2 dense design and multi_path_losses on nb = 2053, K = 3.  Column
+    k of X holds the (tiled) base eta of class k and the coefficient row is a single 1 per response, so X beta is that eta exactly
+    and the sums must meet the bounds the piece tests use."""
+    import scipy.sparse as sp
+
+    import glm_checks as gc
+
+    T = gc.NP_TYPE[dtype]
+    n = 65537
+    for kind in (gc.LOGIT, gc.PROBIT, gc.POISSON):
+        base = gc.base_arrays(kind, dtype, 1)
+        a = gc.call_inputs(gc.M_LOSS2, kind, dtype, n, 1, base)
+        X = np.asfortranarray(np.stack([a["eta"], np.ones(n, dtype=T)], axis=1))
+        betas = sp.csr_matrix((np.ones(2, dtype=T), np.array([0, 0]), np.array([0, 1, 2])), shape=(2, 2))
+        la, lb = ad.matrix.dense(X).glm_path_losses(kind, betas, np.full(2, gc.SCALARS["b0"], dtype=T), a["off"], a["y"], a["w"], a["wb"])
+        ref = gc.base_reference(gc.M_LOSS2, kind, dtype, 1)
+        counts = np.bincount(np.arange(n) % gc.NBASE, minlength=gc.NBASE)
+        for q, got in enumerate((la, lb)):
+            assert got[0] == got[1]
+            r = gc.sum_check(T(got[0]), ref["terms"][q], counts, n, dtype, "glm_path_losses %s" % gc.KIND_NAME[kind])
+            print("glm_path_losses %s %s sums[%d] error / bound = %.3e" % (gc.KIND_NAME[kind], dtype, q, r))
+            assert r <= 1.0
+    nb, K = 2053, 3
+    for kind in (gc.GAUSSIAN, gc.MULTINOMIAL):
+        base = gc.base_arrays(kind, dtype, K)
+        NB = base["y"].shape[1]
+        a = gc.call_inputs(gc.M_MLOSS2, kind, dtype, nb * K, K, base)
+        X = np.asfortranarray(a["eta"].reshape(K, nb).T)
+        betas = sp.csr_matrix((np.ones(K, dtype=T), np.arange(K) * K + np.arange(K), np.array([0, K])), shape=(1, K * K))
+        rowmajor = lambda v: np.ascontiguousarray(v.reshape(K, nb).T)      # noqa: E731
+        la, lb = ad.matrix.dense(X).multi_path_losses(kind, K, betas, a["b0v"][None, :], rowmajor(a["off"]), rowmajor(a["y"]), a["w"], a["wb"])
+        ref = gc.base_reference(gc.M_MLOSS2, kind, dtype, K)
+        counts = np.bincount(np.arange(nb) % NB, minlength=NB)
+        for q, got in enumerate((la, lb)):
+            r = gc.sum_check(T(got[0]), ref["terms"][q], counts, nb, dtype, "multi_path_losses %s" % gc.KIND_NAME[kind])
+            print("multi_path_losses %s %s sums[%d] error / bound = %.3e" % (gc.KIND_NAME[kind], dtype, q, r))
+            assert r <= 1.0
