@@ -8,9 +8,10 @@ method (``solver.gaussian_cov``), the pin solvers on a fixed screen set (``state
 ``sklearn.CSSModelSelection``), bounded-variable least squares (``solver.bvls``) and pinball least squares on a resident
 constraint matrix (``solver.pinball``, ``matrix.dense(method="constraint")``), and the full-matrix NNQP / lasso / pinball
 descents, one or a batch per call (``optimization.StateNNQPFull`` / ``StateLassoFull`` / ``StatePinballFull``,
-``optimization.solve_many``).  All numerics run in hand-written HIP
+``optimization.solve_many``), and the group update itself, one or a batch per call (``bcd.solve``, ``bcd.solve_many``).  All numerics run in hand-written HIP
 kernels for gfx950 behind the C ABI declared in ``include/adelie_hip.h``.
 """
+from . import bcd
 from . import configs
 from . import constraint
 from . import glm

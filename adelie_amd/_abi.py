@@ -237,6 +237,21 @@ class QpFullArgs(C.Structure):
 QP_FULL_KIND = dict(nnqp=0, lasso=1, pinball=2)
 QP_FULL_MAX_ITERS = 1
 
+
+class BcdArgs(C.Structure):
+    """``adelie_hip_bcd_args`` (an addition to ABI 14)."""
+
+    _fields_ = [("dtype", C.c_int32), ("device", C.c_int32), ("solver", C.c_int32), ("_pad0", C.c_int32),
+                ("n_problems", C.c_int64), ("offsets", C.c_void_p), ("quad", C.c_void_p), ("linear", C.c_void_p),
+                ("l1", C.c_void_p), ("l2", C.c_void_p), ("quad_is_dev", C.c_int32), ("linear_is_dev", C.c_int32),
+                ("l1_is_dev", C.c_int32), ("l2_is_dev", C.c_int32), ("tol", C.c_double), ("max_iters", C.c_int64),
+                ("beta", C.c_void_p), ("beta_is_dev", C.c_int32), ("_pad1", C.c_int32), ("iters", C.c_void_p),
+                ("status", C.c_void_p), ("time_elapsed", C.c_void_p)]
+
+
+# enum adelie_hip_bcd_solver
+BCD_SOLVER = dict(newton=0, newton_abs=1)
+
 # adelie_hip_cov_piece
 COV_PIECE_GATHER, COV_PIECE_GRAD = range(2)
 # adelie_hip_group_piece_mode
@@ -322,6 +337,7 @@ HIP_SYMBOLS = [
     "pinball_solve", "pinball_result_destroy", "pinball_result_size", "pinball_result_copy", "pinball_result_scalar",
     "pinball_result_error",
     "qp_full_solve",
+    "bcd_solve",
 ]
 
 
@@ -474,6 +490,7 @@ class Backend:
         sig("pinball_result_scalar", dbl, [vp, ci])
         sig("pinball_result_error", C.c_char_p, [vp])
         sig("qp_full_solve", ci, [p(QpFullArgs)])
+        sig("bcd_solve", ci, [p(BcdArgs)])
 
     def check(self, rc):
         if rc != 0:

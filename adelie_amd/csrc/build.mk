@@ -5,7 +5,7 @@
 UNITS := kernels_cons kernels_append kernels_eig kernels_strip kernels_cov kernels_cov_sparse kernels_sparse kernels_sweep \
          kernels_filter kernels_convert kernels_gram kernels_cd kernels_cd_lasso kernels_cd_pin kernels_cd_block kernels_cd_block_group \
          kernels_cd_panel kernels_multi kernels_glm kernels_cox kernels_factor kernels_relu kernels_relu_sparse kernels_phased \
-         kernels_css kernels_bvls kernels_pinball kernels_pinball_sparse kernels_qp_full design solver test_entries
+         kernels_css kernels_bvls kernels_pinball kernels_pinball_sparse kernels_qp_full kernels_bcd design solver test_entries
 OBJS := $(UNITS:%=$(OBJ)/%.o)
 DEPS := $(OBJS:.o=.d)
 
@@ -17,6 +17,9 @@ $(OUT): $(OBJS)
 # The depfile is written after the object, hence the touch; a failed or interrupted compile leaves no object behind.
 $(OBJ)/%.o: %.hip $(OBJ)/%.d
 	timeout 600 $(HIPCC) $(FLAGS) -MMD -MP -MF $(OBJ)/$*.d -c $< -o $@ && touch $@
+# kernels_bcd packs the float32 values of neighbouring problems side by side, which invites packed float32 instructions; their
+# results must be those of the scalar ones bit for bit, so the unit is compiled without them.
+$(OBJ)/kernels_bcd.o: FLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 $(DEPS): ;
 .DELETE_ON_ERROR:
 -include $(DEPS)

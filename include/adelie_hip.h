@@ -1285,6 +1285,57 @@ typedef struct adelie_hip_qp_full_args {
 } adelie_hip_qp_full_args;
 int adelie_hip_qp_full_solve(const adelie_hip_qp_full_args* args);
 
+/* ------------------------------------------------------------------------------------------
+ * The group update   min 1/2 sum_i q_i x_i^2 - v' x + l1 ||x||_2 + l2/2 ||x||_2^2,   a batch per call
+ *   == adelie.bcd.solve(solver="newton" | "newton_abs")   (py_bcd.cpp; bcd/unconstrained/newton.hpp:35-142, :205-272;
+ *      bcd/utils.hpp; optimization/newton.hpp:28-65)
+ * Per problem, in the value type and in the reference's order of operations (no contraction):
+ *   ||v||_2 <= l1 : x = 0, iters = 0;    else l1 <= 0 : x = v / (q + l2), iters = 0;
+ *   else Newton on h = ||x||_2 for phi(h) = sum_i v_i^2 / ((q_i + l2) h + l1)^2 - 1 (the reference's step_f, projection
+ *   max(h, 0), stopping rule |phi(h)| <= tol and count), then x = h v / ((q + l2) h + l1).  NEWTON starts at h = 0, NEWTON_ABS
+ *   from root_lower_bound / root_upper_bound and the adaptive-bisection loop (which also ends when a probe no longer moves:
+ *   the reference would spin there).  A problem that stops at max_iters is left as its last step left it, as py_bcd.cpp leaves
+ *   it: iters == max_iters, status ADELIE_HIP_BCD_MAX_ITERS, no error.
+ * Only the sums over a group are not the reference's: they run in an order fixed by the group's own length d (kernels_bcd.hip:
+ * teams of 4 .. 64 lanes sharing a wavefront for d <= 64, a wavefront per problem up to 1024, a workgroup beyond, with no upper
+ * limit), so a problem's beta and iters have the same bits in whatever batch and position it is solved.
+ *
+ * Problem k owns the entries [offsets[k], offsets[k+1]) of the flat arrays quad, linear and beta; offsets is a HOST array of
+ * n_problems + 1 non-decreasing entries starting at 0 (a rectangular batch: offsets = d * arange).  quad, linear (offsets[B]
+ * values) and l1, l2 (n_problems values) are of `dtype`, HOST pointers unless their *_is_dev flag says they are DEVICE pointers
+ * on `device`, which are read in place.  beta is written on the host, or in place on the device if beta_is_dev.  iters
+ * (n_problems, HOST) receives the Newton steps taken, status (HOST, may be NULL) an adelie_hip_bcd_status each, *time_elapsed
+ * (may be NULL) the wall-clock seconds of the call.  Returns nonzero with adelie_hip_last_error for malformed arguments.
+ * The entry is additive and changes the layout of no existing structure: ADELIE_HIP_ABI_VERSION stays as it is.
+ * ------------------------------------------------------------------------------------------ */
+enum adelie_hip_bcd_solver { ADELIE_HIP_BCD_NEWTON = 0, ADELIE_HIP_BCD_NEWTON_ABS = 1 };
+enum adelie_hip_bcd_status { ADELIE_HIP_BCD_OK = 0, ADELIE_HIP_BCD_MAX_ITERS = 1 };
+typedef struct adelie_hip_bcd_args {
+    int32_t        dtype;         /* adelie_hip_dtype */
+    int32_t        device;
+    int32_t        solver;        /* adelie_hip_bcd_solver */
+    int32_t        _pad0;
+    int64_t        n_problems;
+    const int64_t* offsets;
+    const void*    quad;
+    const void*    linear;
+    const void*    l1;
+    const void*    l2;
+    int32_t        quad_is_dev;
+    int32_t        linear_is_dev;
+    int32_t        l1_is_dev;
+    int32_t        l2_is_dev;
+    double         tol;
+    int64_t        max_iters;
+    void*          beta;          /* out */
+    int32_t        beta_is_dev;
+    int32_t        _pad1;
+    int64_t*       iters;         /* out */
+    int32_t*       status;        /* out, may be NULL */
+    double*        time_elapsed;  /* out, may be NULL */
+} adelie_hip_bcd_args;
+int adelie_hip_bcd_solve(const adelie_hip_bcd_args* args);
+
 #ifdef __cplusplus
 }
 #endif
