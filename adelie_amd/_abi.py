@@ -314,6 +314,17 @@ class GlmPiece(C.Structure):
     )
 
 
+class ConsVisit(C.Structure):
+    """adelie_hip_cons_visit (include/adelie_hip.h): every field 8 bytes wide."""
+    _fields_ = (
+        [(n, C.c_int64) for n in ("dtype", "q", "native", "gram", "mark", "first_of_pass", "is_active", "active_size",
+                                  "max_active_size", "col0", "n_updates")]
+        + [(n, C.c_double) for n in ("l1", "l2", "dbeta_tol", "rsq", "resid_sum", "cm")]
+        + [("cfg", C.c_double * 5)]
+        + [(n, C.c_void_p) for n in ("V", "grad", "beta", "vars", "va", "vb", "mu", "sxm", "dcol", "dlt", "st_f", "st_i")]
+    )
+
+
 # every symbol include/adelie_hip.h declares (checked by tests/test_abi.py)
 HIP_SYMBOLS = [
     "abi_version", "last_error", "device_count", "set_config",
@@ -331,6 +342,7 @@ HIP_SYMBOLS = [
     "glm_cox_create", "glm_cox_destroy", "glm_cox_eval",
     "grpnet_solve", "grpnet_solve_many", "result_destroy", "result_size", "result_copy", "result_scalar", "result_error", "result_sync",
     "bench_sweep", "filter_sweep_test", "block_build_test", "group_piece_test", "multi_piece_test", "glm_piece_test", "cov_piece_test",
+    "cons_visit_test",
     "css_cov_solve", "css_result_destroy", "css_result_size", "css_result_copy", "css_result_scalar", "css_result_error",
     "bvls_solve", "bvls_result_destroy", "bvls_result_size", "bvls_result_copy", "bvls_result_scalar", "bvls_result_error",
     "design_create_constraint_dense", "design_adopt_constraint_dense_dev", "design_create_constraint_csc", "constraint_op",
@@ -466,6 +478,7 @@ class Backend:
         sig("group_piece_test", ci, [p(GroupPiece), vp])
         sig("multi_piece_test", ci, [p(MultiPiece), vp])
         sig("glm_piece_test", ci, [p(GlmPiece), vp])
+        sig("cons_visit_test", ci, [p(ConsVisit)])
         sig("cov_piece_test", ci, [vp, ci, vp, i64, i64, i64, i64, dbl, vp, vp, vp, i64, vp])
         sig("css_cov_solve", ci, [vp, p(CssArgs), p(vp)])
         sig("css_result_destroy", ci, [vp])

@@ -487,9 +487,14 @@ struct ConsVisitParams {
     CdBlkState<T>* host_st; int32_t* host_seq; int32_t report_seq; // end-of-pass report (report_seq = 0: none)
     int64_t* n_visits;                    // device counter or nullptr
 };
+// q <= 64: one wavefront, Q and H in LDS; 65 .. 128: one workgroup of 256 threads, H in LDS and Q read through L2
+// (kernels_cons_wide.hip, reached through launch_grp_cons_visit)
 size_t cons_visit_lds(int q);
 template <class T>
 void launch_grp_cons_visit(const ConsVisitParams<T>& p, hipStream_t s);
+size_t cons_visit_wide_lds(int q);
+template <class T>
+void launch_grp_cons_visit_wide(const ConsVisitParams<T>& p, hipStream_t s);
 // abs_grad (and, outside the screen set, the solve_zero multipliers) of the `count` groups in `list` with device constraint objects
 template <class T>
 void launch_cons_abs_grad(const int32_t* list, int count, const int32_t* native, const int64_t* groups, const int64_t* gsizes,

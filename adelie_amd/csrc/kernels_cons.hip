@@ -365,11 +365,13 @@ __global__ void cons_abs_grad_kernel(const int32_t* __restrict__ list, int count
 
 } // namespace
 
-size_t cons_visit_lds(int q) { return (size_t(2) * size_t(q) * size_t(q | 1) + 2 * CW) * sizeof(double); }
+// the dynamic LDS of a visit: Q and H for the one-wavefront kernel, H alone for the wide one (kernels_cons_wide.hip)
+size_t cons_visit_lds(int q) { return q > CW ? cons_visit_wide_lds(q) : (size_t(2) * size_t(q) * size_t(q | 1) + 2 * CW) * sizeof(double); }
 
 template <class T>
 void launch_grp_cons_visit(const ConsVisitParams<T>& p, hipStream_t s) {
-    if (p.q < 1 || p.q > CW) throw std::runtime_error("adelie_hip: device constraint visit of a group beyond 64 coefficients.");
+    if (p.q < 1 || p.q > 2 * CW) throw std::runtime_error("adelie_hip: device constraint visit of a group beyond 128 coefficients.");
+    if (p.q > CW) return launch_grp_cons_visit_wide<T>(p, s); // 65 .. 128: one workgroup of four wavefronts
     static const bool raised = [] {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(grp_cons_visit_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   int(cons_visit_lds(CW)));

@@ -975,6 +975,96 @@ int adelie_hip_glm_piece_test(const adelie_hip_glm_piece* a, int64_t* info) {
     ABI_CATCH
 }
 
+// One visit of a group with a box / one-sided constraint object, through launch_grp_cons_visit (include/adelie_hip.h has the
+// arrays): q <= 64 reaches the one-wavefront kernel of kernels_cons.hip, 65 .. 128 the workgroup kernel of kernels_cons_wide.hip.
+int adelie_hip_cons_visit_test(const adelie_hip_cons_visit* a) {
+    ABI_TRY
+    if (!a) throw make_core_error("bad arguments.");
+    if (a->dtype != ADELIE_HIP_F64 && a->dtype != ADELIE_HIP_F32) throw make_core_error("bad dtype.");
+    const int64_t q = a->q;
+    if (q < 1 || q > 128) throw make_core_error("1 <= q <= 128 is required.");
+    if (a->native != ADELIE_HIP_NATIVE_BOX && a->native != ADELIE_HIP_NATIVE_ONE_SIDED)
+        throw make_core_error("native must be 4 (box) or 5 (one-sided).");
+    if (!a->grad || !a->beta || !a->vars || !a->va || !a->vb || !a->mu || !a->dcol || !a->dlt || !a->st_f || !a->st_i || (q > 1 && !a->V))
+        throw make_core_error("V (q > 1), grad, beta, vars, va, vb, mu, dcol, dlt, st_f and st_i are required.");
+    if ((a->gram != 0 && a->gram != 1) || (a->mark != 0 && a->mark != 1) || (a->first_of_pass != 0 && a->first_of_pass != 1) ||
+        (a->is_active != 0 && a->is_active != 1))
+        throw make_core_error("gram, mark, first_of_pass and is_active are flags.");
+    if (a->max_active_size < 0 || a->max_active_size > 4096 || a->active_size < 0 || a->active_size > a->max_active_size)
+        throw make_core_error("0 <= active_size <= max_active_size <= 4096 is required.");
+    if (a->col0 < 0 || a->col0 > (int64_t(1) << 30)) throw make_core_error("0 <= col0 <= 2^30 is required.");
+    auto number = [](double x) { return x == x && std::abs(x) <= 1e300; };
+    if (!number(a->l1) || !number(a->l2) || !number(a->dbeta_tol) || a->l1 < 0 || a->l2 < 0) throw make_core_error("l1, l2 >= 0 and dbeta_tol must be numbers.");
+    // the loops of the driver are bounded by these
+    if (!(a->cfg[0] >= 0 && a->cfg[0] <= 1e6) || !(a->cfg[1] >= 0) || !(a->cfg[2] >= 0 && a->cfg[2] <= 1e8) || !(a->cfg[3] >= 0) ||
+        !(a->cfg[4] > 0 && a->cfg[4] < 1))
+        throw make_core_error("cfg: 0 <= max_iters <= 1e6, tol >= 0, 0 <= pinball / nnqp max_iters <= 1e8, its tol >= 0, 0 < slack < 1.");
+    AHIP_CHECK(hipSetDevice(0));
+    hipStream_t s = nullptr;
+    Stage st{s};
+    auto body = [&](auto tag) {
+        using T = decltype(tag);
+        const T* va = static_cast<const T*>(a->va);
+        const T* vb = static_cast<const T*>(a->vb);
+        for (int64_t t = 0; t < q; ++t) { // the rules of the path driver (solver_path.hpp)
+            if (a->native == ADELIE_HIP_NATIVE_BOX) { // constraint_box.ipp:30-37
+                if (!(vb[t] >= 0)) throw make_core_error("upper must be >= 0.");
+                if (!(va[t] <= 0)) throw make_core_error("lower must be <= 0.");
+            } else {                                  // constraint_one_sided.ipp:74-79
+                if (std::abs(va[t]) != 1) throw make_core_error("sgn must be a vector of +/-1.");
+                if (!(vb[t] >= 0)) throw make_core_error("b must be >= 0.");
+            }
+        }
+        DevBuf<T> dV, dg, dbeta, dvars, dva, dvb, dmu, dsxm, ddlt;
+        DevBuf<int32_t> ddcol, dact;
+        DevBuf<int8_t> disact;
+        DevBuf<CdBlkState<T>> dst;
+        if (q > 1) st.up(dV, static_cast<const T*>(a->V), q * q);
+        st.up(dg, static_cast<const T*>(a->grad), q); st.up(dbeta, static_cast<const T*>(a->beta), q);
+        st.up(dvars, static_cast<const T*>(a->vars), q); st.up(dva, va, q); st.up(dvb, vb, q);
+        st.up(dmu, static_cast<const T*>(a->mu), q);
+        if (a->sxm) st.up(dsxm, static_cast<const T*>(a->sxm), q);
+        st.up(ddlt, static_cast<const T*>(a->dlt), q); st.up(ddcol, a->dcol, q);
+        const int8_t act = int8_t(a->is_active);
+        st.up(disact, &act, 1);
+        st.zeros(dact, a->max_active_size + 1);
+        CdBlkState<T> st0{};
+        st0.rsq = T(a->rsq); st0.resid_sum = T(a->resid_sum); st0.cm = T(a->cm); st0.n_updates = a->n_updates;
+        st0.active_size = int32_t(a->active_size);
+        st.up(dst, &st0, 1);
+        ConsVisitParams<T> vp{};
+        vp.q = int32_t(q); vp.ss = 0; vp.b = 0; vp.col0 = int32_t(a->col0); vp.native = int32_t(a->native);
+        vp.gsrc = dg.p; vp.beta = dbeta.p; vp.vars = dvars.p; vp.V = q > 1 ? dV.p : nullptr; vp.sxm = a->sxm ? dsxm.p : nullptr;
+        vp.is_active = disact.p; vp.active_set = dact.p; vp.st = dst.p;
+        vp.l1 = a->l1; vp.l2 = a->l2; vp.dbeta_tol = a->dbeta_tol;
+        vp.mark = int32_t(a->mark); vp.first_of_pass = int32_t(a->first_of_pass); vp.gram = int32_t(a->gram);
+        vp.max_active_size = int32_t(a->max_active_size);
+        vp.dcol = ddcol.p; vp.dlt = ddlt.p; vp.va = dva.p; vp.vb = dvb.p; vp.mu = dmu.p;
+        for (int e = 0; e < 5; ++e) vp.cfg[e] = a->cfg[e];
+        hipEvent_t e0, e1;
+        AHIP_CHECK(hipEventCreate(&e0));
+        AHIP_CHECK(hipEventCreate(&e1));
+        AHIP_CHECK(hipEventRecord(e0, s));
+        launch_grp_cons_visit<T>(vp, s);
+        AHIP_CHECK(hipEventRecord(e1, s));
+        CdBlkState<T> hst{};
+        int8_t act1 = 0;
+        st.down(&hst, dst.p, sizeof(hst));
+        st.down(&act1, disact.p, 1);
+        st.fetch(a->beta, dbeta.p, size_t(q) * sizeof(T)); st.fetch(a->mu, dmu.p, size_t(q) * sizeof(T));
+        st.fetch(a->dlt, ddlt.p, size_t(q) * sizeof(T)); st.fetch(a->dcol, ddcol.p, size_t(q) * sizeof(int32_t));
+        st.land();
+        float ms = 0;
+        AHIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        a->st_f[0] = double(hst.rsq); a->st_f[1] = double(hst.resid_sum); a->st_f[2] = double(hst.cm); a->st_f[3] = double(ms);
+        a->st_i[0] = hst.n_updates; a->st_i[1] = hst.active_size; a->st_i[2] = hst.status; a->st_i[3] = hst.nz; a->st_i[4] = act1;
+    };
+    DTYPE_DISPATCH(a, body(T{}))
+    ABI_CATCH
+}
+
 // One of the two places where the path solver touches the covariance matrix A, through the dispatcher the solver calls
 // (design_ops.hpp: raw_cov_gather / raw_cov_grad), on either storage (include/adelie_hip.h has the arguments).
 int adelie_hip_cov_piece_test(adelie_hip_design* A, int what, const int32_t* vcol, int64_t nv, int64_t pos0, int64_t N, int64_t ldc,

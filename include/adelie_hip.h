@@ -536,9 +536,9 @@ typedef struct adelie_hip_grpnet_args {
     const double*  constraint_cfg;    /* (G, 5) row-major or NULL */
     /* ABI 5: constraint_native[g] = 6 (linear): constraint_lin[g] describes the object (NULL entries elsewhere) */
     const adelie_hip_linear_constraint* const* constraint_lin; /* (G,) or NULL */
-    /* ABI 7: kind-3 groups whose constraint_native is 4 (box) or 5 (one-sided) and that hold <= 64 coefficients are solved ON
+    /* ABI 7: kind-3 groups whose constraint_native is 4 (box) or 5 (one-sided) and that hold <= 128 coefficients are solved ON
      * THE DEVICE from constraint_va / _vb / _cfg (kernels_cons.hip: the reference's proximal-Newton dual solver in one
-     * wavefront; no callback is made for them).  constraint_vmu: the multipliers those objects hold on entry, per COEFFICIENT
+     * wavefront up to 64 coefficients, kernels_cons_wide.hip: in one workgroup from 65 to 128; no callback is made for them).  constraint_vmu: the multipliers those objects hold on entry, per COEFFICIENT
      * (p,) value_t, or NULL for zeros; what they hold on return is the result vector ADELIE_HIP_V_CONSTRAINT_VMU. */
     const void*    constraint_vmu;
     /* ABI 8: separate factors for the quadratic part of the penalty, (G,) value_t or NULL (= penalty): the objective's penalty
@@ -1219,6 +1219,36 @@ typedef struct adelie_hip_glm_piece {
     void* sums;
 } adelie_hip_glm_piece;
 int adelie_hip_glm_piece_test(const adelie_hip_glm_piece* a, int64_t* info);
+
+/* ONE visit of a group of q coefficients that carries a box / one-sided constraint object (tests, micro-benchmarks), through the
+ * launcher the path solver calls: q <= 64 runs the one-wavefront kernel, 65 <= q <= 128 the workgroup kernel.  All arrays HOST,
+ * of the dtype given, q values unless said otherwise: V (q, q) column-major eigenbasis (ignored for q == 1), grad the group's
+ * gradient, beta (in/out), vars the eigenvalues, va / vb (box: lower, upper; one-sided: sgn, b; the rules of constraint_va /
+ * constraint_vb), mu (in/out) the multipliers, sxm the column means or NULL; cfg as constraint_cfg; native 4 (box) or 5 (one-sided);
+ * gram: the changes leave as (screen value, delta) instead of (design column col0 + i, delta) and resid_sum stays; mark /
+ * is_active / active_size / max_active_size: the active-set marking of a changed group; rsq, resid_sum, cm, n_updates: the pass
+ * state on entry.  Out: dcol (int32) and dlt (both in/out: left as they were when the group did not change), st_f (4 doubles:
+ * rsq, resid_sum, cm, milliseconds of the launch between two events), st_i (5 int64: n_updates, active_size, status -- CdStatus:
+ * 0 OK, 2 max_active, 4 .. 7 the constraint solver's errors --, nz, is_active afterwards).
+ * The entry is additive and changes the layout of no existing structure: ADELIE_HIP_ABI_VERSION stays as it is. */
+typedef struct adelie_hip_cons_visit {
+    int64_t dtype, q, native, gram, mark, first_of_pass, is_active, active_size, max_active_size, col0, n_updates;
+    double l1, l2, dbeta_tol, rsq, resid_sum, cm;
+    double cfg[5];
+    const void* V;
+    const void* grad;
+    void* beta;
+    const void* vars;
+    const void* va;
+    const void* vb;
+    void* mu;
+    const void* sxm;
+    int32_t* dcol;
+    void* dlt;
+    double* st_f;
+    int64_t* st_i;
+} adelie_hip_cons_visit;
+int adelie_hip_cons_visit_test(const adelie_hip_cons_visit* a);
 
 /* One of the two places where the path solver touches the covariance matrix A (dense or kept sparse), through exactly the launcher
  * the solver calls (tests): uploads, launches on A's stream, synchronises, downloads.  Column lists must be distinct and in [0, p).
