@@ -297,6 +297,20 @@ class MultiPiece(C.Structure):
     )
 
 
+# adelie_hip_multi_sparse_piece_mode
+MULTI_SPARSE_SWEEP, MULTI_SPARSE_STEP, MULTI_SPARSE_GRAM, MULTI_SPARSE_AXPY = range(4)
+
+
+class MultiSparsePiece(C.Structure):
+    """adelie_hip_multi_sparse_piece (include/adelie_hip.h): every field 8 bytes wide."""
+    _fields_ = (
+        [(n, C.c_int64) for n in ("dtype", "mode", "n", "p", "K", "icpt", "nnz", "rb", "th")]
+        + [(n, C.c_void_p) for n in ("cptr", "cidx", "cval", "rptr", "rcol", "rval", "v", "out", "w", "r", "dcol", "dlt")]
+        + [("n_dcol", C.c_int64), ("nz", C.c_int64), ("cols", C.c_void_p), ("nb_cols", C.c_int64), ("gblk", C.c_void_p),
+           ("ucols", C.c_void_p), ("M", C.c_int64), ("ldc", C.c_int64), ("C", C.c_void_p), ("sign", C.c_double)]
+    )
+
+
 # adelie_hip_glm_piece_mode
 (GLM_PIECE_PREPARE, GLM_PIECE_WEIGHTS, GLM_PIECE_FINISH, GLM_PIECE_NULL_STEP, GLM_PIECE_GRADIENT, GLM_PIECE_LOSS, GLM_PIECE_LOSS2,
  GLM_PIECE_MULTI_LOSS2, GLM_PIECE_SET_ETA, GLM_PIECE_DOT_DIFF, GLM_PIECE_REL_CHANGE, GLM_PIECE_GATHER, GLM_PIECE_SCATTER) = range(13)
@@ -350,6 +364,7 @@ HIP_SYMBOLS = [
     "pinball_result_error",
     "qp_full_solve",
     "bcd_solve",
+    "multi_sparse_piece_test",
 ]
 
 
@@ -478,6 +493,7 @@ class Backend:
         sig("group_piece_test", ci, [p(GroupPiece), vp])
         sig("multi_piece_test", ci, [p(MultiPiece), vp])
         sig("glm_piece_test", ci, [p(GlmPiece), vp])
+        sig("multi_sparse_piece_test", ci, [p(MultiSparsePiece)])
         sig("cons_visit_test", ci, [p(ConsVisit)])
         sig("cov_piece_test", ci, [vp, ci, vp, i64, i64, i64, i64, dbl, vp, vp, vp, i64, vp])
         sig("css_cov_solve", ci, [vp, p(CssArgs), p(vp)])

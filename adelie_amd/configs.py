@@ -2,7 +2,8 @@
 ``adelie_core/configs.hpp:6-21``, ``py_configs.cpp:6-49``).  Only the two constants that change
 numerics on the hot path are forwarded to the native library, and one switch of this package's own:
 ``pin_path_launch`` (default ``True``: a pin path on a small screen set is one kernel launch; ``False``: one launch per
-lambda; same bits either way, see ``state.gaussian_pin_naive``)."""
+lambda; same bits either way, see ``state.gaussian_pin_naive``) and ``multi_keep_sparse`` (default ``True``: a multi-response view
+keeps a design kept sparse as its base; ``False``: it is built over the expanded dense copy; read by ``matrix._multi_view`` only)."""
 from . import _abi
 
 
@@ -14,6 +15,7 @@ class Configs:
     max_solver_value_def = 1e100
     pb_symbol_def = "\033[1;32m█\033[0m"
     pin_path_launch_def = True
+    multi_keep_sparse_def = True
 
     hessian_min = hessian_min_def
     dbeta_tol = dbeta_tol_def
@@ -22,6 +24,7 @@ class Configs:
     max_solver_value = max_solver_value_def
     pb_symbol = pb_symbol_def
     pin_path_launch = pin_path_launch_def
+    multi_keep_sparse = multi_keep_sparse_def
 
 
 def set_configs(name: str, value=None):

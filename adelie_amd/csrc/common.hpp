@@ -640,7 +640,7 @@ struct adelie_hip_design : ahip::DenseArrs, ahip::SnpArrs, ahip::CscArrs, ahip::
     }
     int dtype = ADELIE_HIP_F64;
     int device = 0;
-    // storage kinds: dense, snp (2-bit), multi-response view of a dense or 2-bit design (adelie_hip_design_create_multi),
+    // storage kinds: dense, snp (2-bit), multi-response view of a dense, 2-bit or kept-sparse design (adelie_hip_design_create_multi),
     // sparse kept sparse (adelie_hip_design_create_csc: CSC + CSR copies of the entries, kernels_sparse.hip), column blocks of
     // dense and 2-bit designs that stay as they are (adelie_hip_design_create_pieces: PiecesArrs; X, bits and the rest are null)
     enum : int { kDense = 0, kSnp = 1, kMulti = 2, kCsc = 3, kPieces = 4 };
@@ -712,9 +712,15 @@ struct adelie_hip_design : ahip::DenseArrs, ahip::SnpArrs, ahip::CscArrs, ahip::
         return ahip::ReluCscView<T>{rz_seg, rz_idx, static_cast<const T*>(rz_val), rbits, n, r_d, r_m, r_gated, sh.tile_rows, int(sh.tiles)};
     }
     template <class T> ahip::MultiView<T> multi() const {
-        return ahip::MultiView<T>{static_cast<const T*>(X), nb, pb, ld, static_cast<const T*>(ones), int32_t(mK), int32_t(micpt),
-                                  bits, ldb, static_cast<const T*>(impute)};
+        ahip::MultiView<T> v{static_cast<const T*>(X), nb, pb, ld, static_cast<const T*>(ones), int32_t(mK), int32_t(micpt),
+                             bits, ldb, static_cast<const T*>(impute)};
+        if (cptr != nullptr) { // base kept sparse: its compressed arrays, with the base's own shape
+            v.csc = csc<T>();
+            v.csc.n = nb, v.csc.p = pb;
+        }
+        return v;
     }
+    bool multi_sparse() const { return kind == kMulti && cptr != nullptr; }
 };
 
 // The shadow of `d` (of the design its aliases were made from), built on d's stream if there is none yet: false when the

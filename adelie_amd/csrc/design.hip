@@ -1329,8 +1329,8 @@ int adelie_hip_design_create_multi(adelie_hip_design* base, int64_t K, int inter
     if (!base || !out) throw make_core_error("null argument.");
     if (base->constraint) no_view(base);
     no_pieces(*base, "kronecker_eye / a multi-response family");
-    if ((!base->is_dense() && !base->is_snp()) || base->cov || base->std_center)
-        throw make_core_error("the multi-response view needs a dense or 2-bit SNP base design.");
+    if ((!base->is_dense() && !base->is_snp() && !base->is_csc()) || base->cov || base->std_center)
+        throw make_core_error("the multi-response view needs a dense, 2-bit SNP or plain kept-sparse base design.");
     if (K < 1) throw make_core_error("K must be >= 1.");
     const int64_t icpt = intercept ? 1 : 0;
     if ((base->p + icpt) * K > int64_t(0x7fffffff) || base->n * K > (int64_t(1) << 40))
@@ -1340,6 +1340,7 @@ int adelie_hip_design_create_multi(adelie_hip_design* base, int64_t K, int inter
     d->kind = adelie_hip_design::kMulti;
     d->DenseArrs::borrow_from(*base);
     d->SnpArrs::borrow_from(*base); // (2-bit base: the K-wide kernels decode the calls themselves, MultiView::bits)
+    d->CscArrs::borrow_from(*base); // (base kept sparse: the K-wide kernels of kernels_multi_sparse.hip, MultiView::csc)
     d->mK = K;
     d->micpt = int(icpt);
     d->nb = base->n;

@@ -694,6 +694,10 @@ struct MultiView {
     const uint8_t* bits = nullptr;
     int64_t ldb = 0;
     const T* impute = nullptr;
+    // base kept sparse (matrix_naive_kronecker_eye.ipp over matrix_naive_sparse.ipp): csc.cptr != nullptr, X and bits unused; the
+    // plain (nb, pb) matrix, no standardized view.  Served by the launch_*_csc launchers below (kernels_multi_sparse.hip).
+    CscView<T> csc{};
+    bool sparse_base() const { return csc.cptr != nullptr; }
 };
 // out[u*K + l] = sum_i xcol(u)[i] * v[l*nb + i]  for every u in [0, pb + icpt): X is read ONCE for all K responses.
 template <class T> void launch_multi_sweep(const MultiView<T>& X, const T* v, T* out, T* work, hipStream_t s);
@@ -743,6 +747,25 @@ void launch_gram_multi(const MultiView<T>& X, const T* w, const int32_t* mcols, 
 template <class T>
 void launch_multi_expand_cross(const T* G, int64_t ldg, const int32_t* slot_r, const int32_t* resp_r, int nr,
                                const int32_t* slot_c, const int32_t* resp_c, int nc, T* C, int64_t ldc, hipStream_t s);
+// The same operations on a view whose base is kept sparse (X.sparse_base(); kernels_multi_sparse.hip), same contracts:
+// sweep: each stored entry's index and value are read once per chunk of responses; partial sums per tile / row block of the base,
+//   added in block order; `work` holds multi_sweep_work_elems_csc(X) elements.
+// panel step: as launch_panel_step_csc the block's gradient goes straight to gblk and 0 slices are returned; phase (A) adds with
+//   hardware atomics; `work` holds multi_step_work_elems_csc(K) elements.
+// syrk: C (M x M, both triangles) over the extended features ucols, M <= 128; `work` holds kVecSumScratch elements.
+// axpy: `delta_zeroed` holds (pb + icpt) K elements, all zero on entry and on exit.
+template <class T> int64_t multi_sweep_work_elems_csc(const MultiView<T>& X);
+template <class T> void launch_multi_sweep_csc(const MultiView<T>& X, const T* v, T* out, T* work, hipStream_t s);
+int64_t multi_step_work_elems_csc(int K);
+template <class T>
+int launch_multi_panel_step_csc(const MultiView<T>& X, const T* w, T* r, const int32_t* dcol, const T* dlt, const int32_t* nz_dev,
+                                const int32_t* cols, int nb_cols, T* gblk, T* work, hipStream_t s);
+template <class T>
+void launch_syrk_multi_csc(const MultiView<T>& X, const T* w, const int32_t* ucols, int32_t M, T* C, int64_t ldc, T* work,
+                           hipStream_t s);
+template <class T>
+void launch_multi_axpy_cols_csc(const MultiView<T>& X, const int32_t* cols, const T* coef, const int32_t* cnt_dev, T sign, T* out,
+                                T* delta_zeroed, hipStream_t s);
 template <class T>
 void launch_batch_pick(const T* src, int64_t nfeat, int K, int slot, const T* sub_scale, const T* sub_vec, T* out,
                        hipStream_t s);

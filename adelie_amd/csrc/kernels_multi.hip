@@ -1,4 +1,5 @@
-// kernels_multi.hip — the multi-response view [1 (x) I_K, X (x) I_K] of a resident dense design (gfx950 / CDNA4).
+// kernels_multi.hip — the multi-response view [1 (x) I_K, X (x) I_K] of a resident dense or 2-bit design (gfx950 / CDNA4); a base
+// kept sparse has its own K-wide kernels over compressed columns in kernels_multi_sparse.hip.
 //
 // Replaces, for StateMultiGaussianNaive (reference adelie/state.py:2027-2391, solver_multigaussian_naive.hpp:9-52), the
 // composition MatrixNaiveConcatenate([MatrixNaiveKroneckerEye(ones), MatrixNaiveKroneckerEye(X)])
@@ -22,6 +23,7 @@
 #include "wavered.hpp"
 #include "grp_solve_body.hpp"
 #include "multi_shape.hpp"
+#include "multi_slots.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -280,27 +282,6 @@ __device__ __forceinline__ Pack<T, VEC> mcol(const SnpOnesAcc<T>& X, int u, int6
 #pragma unroll
     for (int e = 0; e < VEC; ++e) r.v[e] = (full || i + e < nb) ? x.v[e] : T(0);
     return r;
-}
-
-// slots of a list of view columns: returns the number of slots; feat[slot] = extended feature; for every entry m the
-// callback gets (m, slot, response)
-template <class F>
-__device__ __forceinline__ int build_slots(const int32_t* __restrict__ list, int cnt, int K, int* feat, int lane, F f) {
-    int nslot = 0;
-    for (int base = 0; base < cnt; base += 64) {
-        const int m = base + lane;
-        const bool valid = m < cnt;
-        const int col = valid ? list[m] : 0;
-        const int u = col / K, l = col - u * K;
-        const int pu = (valid && m > 0) ? list[m - 1] / K : -1;
-        const bool head = valid && (m == 0 || u != pu);
-        const unsigned long long mask = __ballot(head);
-        const int slot = nslot + __popcll(mask & ((2ull << lane) - 1ull)) - 1;
-        if (head) feat[slot] = u;
-        if (valid) f(m, slot, l);
-        nslot += __popcll(mask);
-    }
-    return nslot;
 }
 
 // phases (A) and (B) of the multi-response panel step for one wave (64 * VEC rows starting at row i, responses l0..l0+KT)

@@ -481,6 +481,7 @@
         // multi-response view: Gram of the two blocks' distinct features, expanded to view columns (zero between different
         // responses); look-ahead only runs under uniform weights (Gaussian), so one Gram serves all responses
         const MultiView<T> mv = D->multi<T>();
+        if (mv.sparse_base()) throw make_core_error("internal: cross blocks on a multi-response view of a design kept sparse.");
         for (int j = 1; j < nblk; ++j) {
             const int nbp = nb_of(j - 1), nb = nb_of(j);
             XKey& k = tab[size_t(j)];
@@ -703,6 +704,9 @@
     DevBuf<T> d_std_tmp, d_std_coef;
     // multi-response view (adelie_hip_design_create_multi): residual / weights live response-major on the device
     bool multi() const { return D->is_multi(); }
+    // ... over a base kept sparse (kernels_multi_sparse.hip): the sequential panel form only -- no look-ahead, so neither cross
+    // blocks nor the fused launch, which streams dense column slices
+    bool multi_sparse() const { return D->multi_sparse(); }
     int mk() const { return multi() ? int(D->mK) : 1; } // class count handed to the GLM kernels
     bool multi_w_uniform = true;
     std::vector<int32_t> h_vcol, h_actcols, multi_seen; // host mirrors of d_vcol / d_actcols (block column lists)

@@ -889,7 +889,7 @@
         std::vector<idx> act_host(active_set.begin(), active_set.begin() + asz); // host mirror of the active list
         std::vector<int32_t>& acols = h_actcols;
         // look-ahead form (see run_panel_passes); not on the multi-response view, whose step is a different kernel
-        const bool la = lookahead && !is_glm() && (!multi() || multi_w_uniform) && !std_generic() && !sparse();
+        const bool la = lookahead && !is_glm() && (!multi() || multi_w_uniform) && !std_generic() && !sparse() && !multi_sparse();
         if (la) reserve_lookahead(maxblk, mode);
         // (The group solve summing the slice partials itself, as the lasso solve does, was measured slower — config 3: 722.7 ms
         // with, 654.1 ms without: a group launch is bound by its solve — and removed in round 4.)
@@ -1080,6 +1080,7 @@
                 const int32_t* nz_apply = (j == 0) ? d_zero_i32.p : d_la_nz.p + pslot; // (j = 0 of a fused opening: nothing to apply)
                 int ld;
                 if (time_panel) t_step.begin(st);
+                if (multi_sparse()) throw make_core_error("internal: the fused launch on a multi-response view of a design kept sparse.");
                 if (multi())
                     ld = launch_multi_panel_fused<T>(bp, j, D->multi<T>(), cur_w, r_dev, d_la_dcol.p + size_t(pslot) * SL,
                                                      d_la_dlt.p + size_t(pslot) * SL, d_la_nz.p + pslot, cols_n, nbn, d_part.p, st);

@@ -8,7 +8,8 @@
         if (multi()) { // only the full sweep of the Gaussian path is needed on the view (intercept off: no centring epilogue)
             if (cols || ncols != p || sub_vec || square) throw make_core_error("unsupported sweep on a multi-response view.");
             const MultiView<T> mv = D->multi<T>();
-            launch_multi_sweep<T>(mv, v, out, d_work_sweep.reserve(size_t(multi_sweep_work_elems<T>(mv))), st);
+            if (mv.sparse_base()) launch_multi_sweep_csc<T>(mv, v, out, d_work_sweep.reserve(size_t(multi_sweep_work_elems_csc<T>(mv))), st);
+            else launch_multi_sweep<T>(mv, v, out, d_work_sweep.reserve(size_t(multi_sweep_work_elems<T>(mv))), st);
             return;
         }
         if (std_generic()) { // raw sweep(s) of the base design, then the view's epilogue (kernels_sparse.hip, header)
@@ -38,11 +39,15 @@
     // `want_tail`: the step may leave the block's gradient in d_gblk itself (2-bit designs, StepTail; kernels.hpp) -- then
     // step_tailed is set and the caller skips panel_reduce; tail_xm = the by-column means of the intercept term (or nullptr)
     DevBuf<int32_t> d_tail_ctr;
+    DevBuf<T> d_msp_work; // launch_multi_panel_step_csc's scratch
     int32_t tail_base = 0;
     bool step_tailed = false;
     int panel_step(const T* w, T* r, const int32_t* dcol, const T* dlt, const int32_t* nz_dev, const int32_t* cols, int nb,
                    bool want_tail = false, const T* tail_xm = nullptr) {
         step_tailed = false;
+        if (multi_sparse()) // base kept sparse: the gradient goes straight to d_gblk (returns 0: no partials to reduce)
+            return launch_multi_panel_step_csc<T>(D->multi<T>(), w, r, dcol, dlt, nz_dev, cols, nb, d_gblk.p,
+                                                  d_msp_work.reserve(size_t(multi_step_work_elems_csc(mk()))), st);
         if (multi()) return launch_multi_panel_step<T>(D->multi<T>(), w, r, dcol, dlt, nz_dev, cols, nb, d_part.p, st);
         no_pieces(*D, "the panel step"); // (unreachable: engine_panel is off)
         const T* kappa = nullptr;
@@ -170,10 +175,11 @@
             ml.reserve(size_t(6 * B));
             mc.reserve(size_t(B) * B);
             launch_multi_block_lists(cols, nb, mv.K, ml.p, ml.p + B, ml.p + 2 * B, gs);
-            T* work = (side ? d_work_gram2 : d_work_gram).reserve(size_t(syrk_work_elems(mv.nb, 128)));
+            T* work = (side ? d_work_gram2 : d_work_gram).reserve(size_t(std::max<int64_t>(syrk_work_elems(mv.nb, 128), kVecSumScratch)));
             const int reps = multi_w_uniform ? 1 : mv.K;
             for (int l = 0; l < reps; ++l) {
-                launch_syrk_multi<T>(mv, w + size_t(l) * size_t(mv.nb), ml.p, nu, mc.p, B, work, gs);
+                if (mv.sparse_base()) launch_syrk_multi_csc<T>(mv, w + size_t(l) * size_t(mv.nb), ml.p, nu, mc.p, B, work, gs);
+                else launch_syrk_multi<T>(mv, w + size_t(l) * size_t(mv.nb), ml.p, nu, mc.p, B, work, gs);
                 launch_multi_expand<T>(mc.p, B, ml.p + B, ml.p + 2 * B, nb, multi_w_uniform ? -1 : l, Dptr, B, gs);
                 cnt.gram_flops += 2.0 * double(mv.nb) * 256.0 * (nu <= 32 ? 3.0 : (nu <= 64 ? 10.0 : 36.0));
             }
@@ -199,6 +205,14 @@
     void axpy_cols(const int32_t* cols, const T* coef, const int32_t* cnt_dev, int32_t count, T sign, T* out) {
         if (multi()) {
             if (!cnt_dev) throw make_core_error("unsupported axpy on a multi-response view.");
+            if (multi_sparse()) { // coefficients scattered into a vector that is all zero between calls, then one pass over the rows
+                if (d_sp_delta.cap < size_t(p) + 8) {
+                    d_sp_delta.reserve(size_t(p) + 8);
+                    AHIP_CHECK(hipMemsetAsync(d_sp_delta.p, 0, (size_t(p) + 8) * sizeof(T), st));
+                }
+                launch_multi_axpy_cols_csc<T>(D->multi<T>(), cols, coef, cnt_dev, sign, out, d_sp_delta.p, st);
+                return;
+            }
             launch_multi_axpy_cols<T>(D->multi<T>(), cols, coef, cnt_dev, sign, out, st);
             return;
         }

@@ -106,12 +106,20 @@ int adelie_hip_bench_sweep(adelie_hip_design* d, int64_t reps, double* ms_per_la
         v.reserve(d->n); out.reserve(d->p); xm.reserve(d->p); sc.reserve(1);
         // a one-hot / interaction or convex-relu design: the route ADELIE_HIP_FACTOR_SWEEP / ADELIE_HIP_RELU_SWEEP select (read here)
         // (a design made of pieces: raw_sweep issues the full range piece by piece, as a solve's per-lambda sweep does)
-        const bool structured = raw_sweep_structured(*d, 0, d->p, nullptr, false, SweepHooks::from_env());
-        work.reserve(size_t(raw_sweep_work_elems(*d, d->p, structured)));
+        const bool structured = !d->is_multi() && raw_sweep_structured(*d, 0, d->p, nullptr, false, SweepHooks::from_env());
+        if (!d->is_multi()) work.reserve(size_t(raw_sweep_work_elems(*d, d->p, structured)));
+        else if (d->multi_sparse()) work.reserve(size_t(multi_sweep_work_elems_csc<T>(d->multi<T>())));
+        else work.reserve(size_t(multi_sweep_work_elems<T>(d->multi<T>())));
         launch_fill<T>(v.p, T(1) / T(d->n), d->n, s);
         launch_fill<T>(xm.p, T(0.5), d->p, s);
         launch_fill<T>(sc.p, T(0.25), 1, s);
-        auto once = [&]() { raw_sweep<T>(*d, v.p, out.p, 0, d->p, nullptr, sc.p, xm.p, false, structured, work.p, s); };
+        // (a multi-response view: its K-wide sweep over all view columns, dense / 2-bit or compressed-column base)
+        const MultiView<T> mv = d->is_multi() ? d->multi<T>() : MultiView<T>{};
+        auto once = [&]() {
+            if (!d->is_multi()) raw_sweep<T>(*d, v.p, out.p, 0, d->p, nullptr, sc.p, xm.p, false, structured, work.p, s);
+            else if (mv.sparse_base()) launch_multi_sweep_csc<T>(mv, v.p, out.p, work.p, s);
+            else launch_multi_sweep<T>(mv, v.p, out.p, work.p, s);
+        };
         once();
         AHIP_CHECK(hipStreamSynchronize(s));
         hipEvent_t e0, e1;
@@ -1118,6 +1126,148 @@ int adelie_hip_cov_piece_test(adelie_hip_design* A, int what, const int32_t* vco
         }
     };
     DTYPE_DISPATCH(A, body(T{}))
+    ABI_CATCH
+}
+
+// One launcher of kernels_multi_sparse.hip on caller-supplied inputs (include/adelie_hip.h has the modes and the arrays).
+int adelie_hip_multi_sparse_piece_test(const adelie_hip_multi_sparse_piece* a) {
+    ABI_TRY
+    if (!a) throw make_core_error("bad arguments.");
+    if (a->dtype != ADELIE_HIP_F64 && a->dtype != ADELIE_HIP_F32) throw make_core_error("bad dtype.");
+    constexpr int64_t G = 128, BIG = int64_t(1) << 24;
+    const int mode = int(a->mode);
+    if (a->mode < ADELIE_HIP_MULTI_SPARSE_SWEEP || a->mode > ADELIE_HIP_MULTI_SPARSE_AXPY) throw make_core_error("unknown mode.");
+    const int64_t n = a->n, p = a->p, K = a->K, icpt = a->icpt, nnz = a->nnz;
+    if (n < 1 || n > BIG || p < 1 || p > (1 << 20) || K < 1 || K > 64 || (icpt != 0 && icpt != 1) || nnz < 0 || nnz > (int64_t(1) << 28) ||
+        a->rb < 0 || a->th < 0 || a->th > 65536 || !a->cptr || !a->rptr || (nnz > 0 && (!a->cidx || !a->cval || !a->rcol || !a->rval)))
+        throw make_core_error("view: 1 <= n, p, 1 <= K <= 64, icpt in {0, 1}, 0 <= th <= 65536 and the six compressed arrays are required.");
+    const int64_t ncol = (p + icpt) * K;
+    auto compressed = [&](const int64_t* ptr, const int32_t* idx, int64_t outer, int64_t inner, const char* what) {
+        if (ptr[0] != 0 || ptr[outer] != nnz) throw make_core_error(std::string(what) + ": pointers must run from 0 to nnz.");
+        for (int64_t j = 0; j < outer; ++j) {
+            if (ptr[j + 1] < ptr[j] || ptr[j + 1] > nnz) throw make_core_error(std::string(what) + ": pointers must not decrease.");
+            for (int64_t t = ptr[j]; t < ptr[j + 1]; ++t)
+                if (idx[t] < 0 || idx[t] >= inner || (t > ptr[j] && idx[t] <= idx[t - 1]))
+                    throw make_core_error(std::string(what) + ": indices must be in range and ascending.");
+        }
+    };
+    compressed(a->cptr, a->cidx, p, n, "columns");
+    compressed(a->rptr, a->rcol, n, p, "rows");
+    auto in_cols = [&](const int32_t* list, int64_t cnt, int64_t hi, const char* what) {
+        if (cnt > 0 && !list) throw make_core_error(std::string(what) + ": null list.");
+        for (int64_t m = 0; m < cnt; ++m)
+            if (list[m] < 0 || list[m] >= hi) throw make_core_error(std::string(what) + ": index out of range.");
+    };
+    int64_t n_used = 0;
+    if (mode == ADELIE_HIP_MULTI_SPARSE_SWEEP) {
+        if (!a->v || !a->out) throw make_core_error("SWEEP: v and out are required.");
+    } else if (mode == ADELIE_HIP_MULTI_SPARSE_STEP) {
+        if (!a->w || !a->r || a->nz < 0 || a->nz > INT32_MAX || a->n_dcol < 0 || a->n_dcol > G || a->nb_cols < 0 || a->nb_cols > 2 * G ||
+            (a->nb_cols > 0 && !a->gblk))
+            throw make_core_error("STEP: w, r, gblk, n_dcol <= 128 and nb_cols <= 256 are required.");
+        n_used = std::min<int64_t>(a->nz, G);
+        if (n_used > a->n_dcol || (n_used > 0 && !a->dlt)) throw make_core_error("STEP: dcol / dlt hold fewer than min(nz, 128) entries.");
+        in_cols(a->dcol, a->n_dcol, ncol, "STEP dcol");
+        in_cols(a->cols, a->nb_cols, ncol, "STEP cols");
+    } else if (mode == ADELIE_HIP_MULTI_SPARSE_GRAM) {
+        if (!a->w || !a->C || a->M < 1 || a->M > G || a->ldc < a->M || a->ldc > BIG) throw make_core_error("GRAM: w, C, 1 <= M <= 128 and ldc >= M are required.");
+        in_cols(a->ucols, a->M, p + icpt, "GRAM ucols");
+    } else {
+        if (!a->r || a->n_dcol < 0 || a->n_dcol > 4096 || a->nz < 0 || a->nz > a->n_dcol || (a->nz > 0 && !a->dlt))
+            throw make_core_error("AXPY: r and 0 <= nz <= n_dcol <= 4096 are required.");
+        n_used = a->nz;
+        in_cols(a->dcol, a->n_dcol, ncol, "AXPY dcol");
+    }
+    AHIP_CHECK(hipSetDevice(0));
+    hipStream_t s = nullptr;
+    Stage st{s};
+    auto body = [&](auto tag) {
+        using T = decltype(tag);
+        DevBuf<int64_t> dcptr, drptr, dbptr, dtptr, dcolptr;
+        DevBuf<int32_t> dcidx, drcol, ddcol, dcols, dnz, ducols;
+        DevBuf<uint16_t> dtrow;
+        DevBuf<T> dcval, drval, dtval, dv, dout, dw, dr, ddlt, dg, dC, dwork, ddelta;
+        const int64_t nz1 = std::max<int64_t>(nnz, 1);
+        st.up(dcptr, a->cptr, p + 1); st.up(drptr, a->rptr, n + 1);
+        dcidx.reserve(size_t(nz1)); drcol.reserve(size_t(nz1)); dcval.reserve(size_t(nz1)); drval.reserve(size_t(nz1));
+        if (nnz) {
+            dcidx.upload(a->cidx, size_t(nnz), s); drcol.upload(a->rcol, size_t(nnz), s);
+            dcval.upload(static_cast<const T*>(a->cval), size_t(nnz), s); drval.upload(static_cast<const T*>(a->rval), size_t(nnz), s);
+        }
+        MultiView<T> mv{};
+        mv.nb = n; mv.pb = p; mv.K = int32_t(K); mv.icpt = int32_t(icpt);
+        CscView<T>& B = mv.csc;
+        B = CscView<T>{dcptr.p, dcidx.p, dcval.p, drptr.p, drcol.p, drval.p, n, p, nnz, nullptr, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
+        if (a->rb > 0 && (n + a->rb - 1) / a->rb > 1) { // row blocks, as csc_finish lays them out
+            B.rb = a->rb; B.nb = int((n + a->rb - 1) / a->rb);
+            if (B.nb > 4096) throw make_core_error("rb: too many row blocks.");
+            dbptr.reserve(size_t(p) * size_t(B.nb + 1));
+            launch_csc_block_ptr(dcptr.p, dcidx.p, p, B.nb, B.rb, dbptr.p, s);
+            B.bptr = dbptr.p;
+        }
+        if (a->th > 0) { // the tile-major copy, as csc_finish builds it
+            const int64_t th = a->th, nt = (n + th - 1) / th;
+            if (nt > 4096) throw make_core_error("th: too many tiles.");
+            dcolptr.reserve(size_t(p) * size_t(nt + 1));
+            launch_csc_block_ptr(dcptr.p, dcidx.p, p, int(nt), th, dcolptr.p, s);
+            std::vector<int64_t> cp(size_t(p) * size_t(nt + 1)), tp(size_t(nt) * size_t(p + 1));
+            st.down(cp.data(), dcolptr.p, cp.size() * sizeof(int64_t));
+            st.sync();
+            int64_t run = 0;
+            for (int64_t t = 0; t < nt; ++t) {
+                int64_t* row = tp.data() + size_t(t) * size_t(p + 1);
+                for (int64_t c = 0; c < p; ++c) {
+                    row[c] = run;
+                    run += cp[size_t(c) * size_t(nt + 1) + size_t(t) + 1] - cp[size_t(c) * size_t(nt + 1) + size_t(t)];
+                }
+                row[p] = run;
+            }
+            st.up(dtptr, tp.data(), int64_t(tp.size()));
+            dtrow.reserve(size_t(nz1)); dtval.reserve(size_t(nz1));
+            launch_csc_tile_scatter<T>(dcolptr.p, dcidx.p, dcval.p, p, int(nt), th, dtptr.p, dtrow.p, dtval.p, s);
+            st.sync(); // (tp is read by the upload until here)
+            B.tptr = dtptr.p; B.trow = dtrow.p; B.tval = dtval.p; B.nt = int(nt); B.th = th;
+        }
+        if (mode == ADELIE_HIP_MULTI_SPARSE_SWEEP) {
+            st.up(dv, static_cast<const T*>(a->v), n * K);
+            st.up(dout, static_cast<const T*>(a->out), ncol);
+            dwork.reserve(size_t(multi_sweep_work_elems_csc<T>(mv)));
+            launch_multi_sweep_csc<T>(mv, dv.p, dout.p, dwork.p, s);
+            st.finish(a->out, dout.p, size_t(ncol) * sizeof(T));
+            return;
+        }
+        if (mode == ADELIE_HIP_MULTI_SPARSE_GRAM) {
+            st.up(dw, static_cast<const T*>(a->w), n);
+            st.up(ducols, a->ucols, a->M);
+            st.up(dC, static_cast<const T*>(a->C), a->M * a->ldc);
+            dwork.reserve(size_t(kVecSumScratch));
+            launch_syrk_multi_csc<T>(mv, dw.p, ducols.p, int32_t(a->M), dC.p, a->ldc, dwork.p, s);
+            st.finish(a->C, dC.p, size_t(a->M * a->ldc) * sizeof(T));
+            return;
+        }
+        st.up(dr, static_cast<const T*>(a->r), n * K);
+        ddcol.reserve(size_t(std::max<int64_t>(a->n_dcol, G))); ddlt.reserve(size_t(std::max<int64_t>(a->n_dcol, G)));
+        if (a->n_dcol > 0) ddcol.upload(a->dcol, size_t(a->n_dcol), s);
+        if (n_used > 0) ddlt.upload(static_cast<const T*>(a->dlt), size_t(a->n_dcol), s);
+        const int32_t nz32 = int32_t(a->nz);
+        st.up(dnz, &nz32, 1);
+        if (mode == ADELIE_HIP_MULTI_SPARSE_AXPY) {
+            st.zeros(ddelta, ncol + 8);
+            launch_multi_axpy_cols_csc<T>(mv, ddcol.p, ddlt.p, dnz.p, T(a->sign), dr.p, ddelta.p, s);
+            st.finish(a->r, dr.p, size_t(n * K) * sizeof(T));
+            return;
+        }
+        st.up(dw, static_cast<const T*>(a->w), n * K);
+        dcols.reserve(size_t(2 * G)); dg.reserve(size_t(2 * G));
+        if (a->nb_cols > 0) { dcols.upload(a->cols, size_t(a->nb_cols), s); dg.upload(static_cast<const T*>(a->gblk), size_t(a->nb_cols), s); }
+        dwork.reserve(size_t(multi_step_work_elems_csc(int(K))));
+        launch_multi_panel_step_csc<T>(mv, dw.p, dr.p, ddcol.p, ddlt.p, dnz.p, dcols.p, int(a->nb_cols), dg.p, dwork.p, s);
+        AHIP_CHECK(hipGetLastError());
+        if (a->nb_cols > 0) st.fetch(a->gblk, dg.p, size_t(a->nb_cols) * sizeof(T));
+        st.fetch(a->r, dr.p, size_t(n * K) * sizeof(T));
+        st.land();
+    };
+    DTYPE_DISPATCH(a, body(T{}))
     ABI_CATCH
 }
 

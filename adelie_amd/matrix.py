@@ -15,6 +15,7 @@ import numpy as np
 from scipy.sparse import csc_matrix, csr_matrix, issparse
 
 from . import _abi
+from .configs import Configs
 
 
 class MatrixNaiveBase:
@@ -781,10 +782,13 @@ def _std_view(base, centers, scales, n_threads):
 def _multi_view(base, K, intercept):
     _no_pieces(base, "a multi-response view (kronecker_eye, the multigaussian and multinomial families)")
     if not isinstance(base, _NativeMatrix) or isinstance(base, _MultiView):
-        raise RuntimeError("adelie_amd: the multi-response view needs a resident (dense or 2-bit SNP) design as its base.")
+        raise RuntimeError("adelie_amd: the multi-response view needs a resident (dense, 2-bit SNP or kept-sparse) design as its base.")
     if int(K) < 1:
         raise RuntimeError("adelie_core: K must be >= 1.")
-    if _is_kept_sparse(base):  # the K-wide kernels stream dense or 2-bit column slices
+    # A plain design kept sparse stays as it is (the K-wide kernels over compressed columns, kernels_multi_sparse.hip; reference:
+    # MatrixNaiveKroneckerEye over MatrixNaiveSparse).  Its standardized view, or any design kept sparse with
+    # set_configs("multi_keep_sparse", False), is expanded: the dense K-wide kernels stream column slices.
+    if _is_kept_sparse(base) and (getattr(base, "_std", None) is not None or not Configs.multi_keep_sparse):
         base = _expanded(base)
     if isinstance(base, _StdView):
         base = base._materialize()

@@ -337,7 +337,8 @@ def grpnet(
         panel_off = os.environ.get("ADELIE_HIP_STD_PANEL", "1") == "0" if is_view else False
         if sparse_kept and os.environ.get("ADELIE_HIP_SPARSE_PANEL", "1") == "0":
             panel_off = True
-        if (sparse_kept and gaussian) or ((is_view or sparse_kept) and panel_off):
+        # (multi-response families on a design kept sparse: constrained fits are not offered on the compressed-column view)
+        if (sparse_kept and (gaussian or getattr(glm, "is_multi", False))) or ((is_view or sparse_kept) and panel_off):
             warnings.warn(
                 "adelie_amd: constraints on a lazily standardized / sparse-resident design run on its materialised dense copy "
                 f"({X.rows()} x {X.cols()} values of device memory).", RuntimeWarning, stacklevel=2)

@@ -1366,6 +1366,51 @@ typedef struct adelie_hip_bcd_args {
 } adelie_hip_bcd_args;
 int adelie_hip_bcd_solve(const adelie_hip_bcd_args* args);
 
+/* One launcher of the multi-response kernels over a base kept sparse (kernels_multi_sparse.hip) on caller-supplied inputs, exactly
+ * as the solver calls it (tests): uploads, builds the view [1 (x) I_K, X (x) I_K] over the (n, p) matrix given column-compressed
+ * (cptr p + 1, cidx / cval nnz, row indices ascending inside a column) and row-compressed (rptr n + 1, rcol / rval nnz), launches
+ * on one stream, synchronises, downloads.  rb > 0 cuts the rows into blocks of rb rows (CscView::bptr), th > 0 (at most 65536)
+ * builds the tile-major copy with tiles of th rows, so that a small matrix spans several of either.  Every field is 8 bytes wide;
+ * value arrays (`void*`) are in `dtype`, `sign` crosses as double.  Vectors of n K values are response-major; column index
+ * c = u K + l is (extended feature u < p + icpt, response l).  Every index array is checked before anything is launched.
+ *
+ * mode  SWEEP: launch_multi_sweep_csc, out ((p + icpt) K) = x_u . v_l.
+ *       STEP:  launch_multi_panel_step_csc.  r (in/out, n K) -= sum_{m < min(nz, 128)} dlt[m] x(dcol[m]) with nz read on the device
+ *              (dcol / dlt hold n_dcol <= 128 entries); gblk (in/out, nb_cols <= 256) [c] = x(cols[c]) . (w r) of its response.
+ *       GRAM:  launch_syrk_multi_csc, C (in/out, M ldc values, M <= 128, ldc >= M) [a + b ldc] = sum_i w[i] x(ucols[a]) x(ucols[b])
+ *              with w the n weights of one response.
+ *       AXPY:  launch_multi_axpy_cols_csc, r (in/out, n K) += sign sum_{m < nz} dlt[m] x(dcol[m]), nz <= n_dcol <= 4096 read on the
+ *              device; distinct columns.
+ * The entry is additive and changes the layout of no existing structure: ADELIE_HIP_ABI_VERSION stays as it is. */
+enum adelie_hip_multi_sparse_piece_mode {
+    ADELIE_HIP_MULTI_SPARSE_SWEEP = 0, ADELIE_HIP_MULTI_SPARSE_STEP = 1, ADELIE_HIP_MULTI_SPARSE_GRAM = 2, ADELIE_HIP_MULTI_SPARSE_AXPY = 3
+};
+typedef struct adelie_hip_multi_sparse_piece {
+    int64_t dtype, mode;
+    int64_t n, p, K, icpt, nnz, rb, th;
+    const int64_t* cptr;
+    const int32_t* cidx;
+    const void* cval;
+    const int64_t* rptr;
+    const int32_t* rcol;
+    const void* rval;
+    const void* v;
+    void* out;
+    const void* w;
+    void* r;
+    const int32_t* dcol;
+    const void* dlt;
+    int64_t n_dcol, nz;
+    const int32_t* cols;
+    int64_t nb_cols;
+    void* gblk;
+    const int32_t* ucols;
+    int64_t M, ldc;
+    void* C;
+    double sign;
+} adelie_hip_multi_sparse_piece;
+int adelie_hip_multi_sparse_piece_test(const adelie_hip_multi_sparse_piece* a);
+
 #ifdef __cplusplus
 }
 #endif
