@@ -19,7 +19,7 @@
 namespace ahip {
 
 // ---- every environment hook of libadelie_hip.so, in one place ------------------------------------------------------------------
-// Fifteen variables.  They are read when a solve starts (Hooks::from_env, one call per solve): the tests force the multi-CU engines
+// Sixteen variables.  They are read when a solve starts (Hooks::from_env, one call per solve): the tests force the multi-CU engines
 // at sizes the CPU checker finishes in seconds and compare variants between two solves of ONE process, so reading them once at
 // library load would freeze the first test's setting.  None changes results beyond rounding.  (Python side: ADELIE_HIP_LIB picks
 // another build of this library, ADELIE_HIP_SWEEP_BATCH=0 keeps concurrent CV folds from sharing their sweeps.)
@@ -49,6 +49,9 @@ namespace ahip {
 //   ADELIE_HIP_SHADOW_KIND=f32|q15|auto  the encoding of that shadow copy, read when a design's copy is made: float32, int16
 //                                 with one scale per column, or (default) the rule of shadow_kind_host.hpp           [A/B, tests]
 //   ADELIE_HIP_SHADOW_MIN_BYTES=b `auto` considers q15 when the float32 copy would hold at least b bytes (default 2^30)  [test hook]
+//   ADELIE_HIP_HANDOFF=copies     a Gaussian lambda's hand-off (scores, coefficients, the snapshot before a speculative pass)
+//                                 through copies on the solver's stream instead of host-mapped memory and one launch
+//                                 (Solver::fit_handoff); same results bit for bit                                      [A/B, tests]
 //   ADELIE_HIP_TIME_PANEL=1       per-launch HIP events around the panel step (bench.py's roofline leg)
 //   ADELIE_HIP_TRACE=1|2          1: per-pass trace on stderr; 2: + enqueue / allocation / build timings
 struct Hooks {
@@ -64,6 +67,7 @@ struct Hooks {
     double filter_depth_margin = -1; // ADELIE_HIP_FILTER_DEPTH_MARGIN (< 0: unset)
     double irls_reuse = -1;
     bool time_panel = false;
+    bool handoff_copies = false; // ADELIE_HIP_HANDOFF=copies
     bool cons_host = false; // ADELIE_HIP_CONS_HOST=1: box / one-sided objects on several coefficients visited on the host (A/B, tests)
     int trace = 0;
     static Hooks from_env() {
@@ -77,6 +81,7 @@ struct Hooks {
         if (const char* e = std::getenv("ADELIE_HIP_SPECULATE")) h.speculate = std::atoi(e) != 0;
         if (const char* e = std::getenv("ADELIE_HIP_IRLS_REUSE")) h.irls_reuse = std::max(0.0, std::atof(e));
         h.time_panel = std::getenv("ADELIE_HIP_TIME_PANEL") != nullptr;
+        if (const char* e = std::getenv("ADELIE_HIP_HANDOFF")) h.handoff_copies = std::strcmp(e, "copies") == 0;
         if (const char* e = std::getenv("ADELIE_HIP_CONS_HOST")) h.cons_host = std::atoi(e) != 0;
         if (const char* e = std::getenv("ADELIE_HIP_SPARSE_PANEL")) h.sparse_panel = std::atoi(e) != 0;
         if (const char* e = std::getenv("ADELIE_HIP_STD_PANEL")) h.std_panel = std::atoi(e) != 0;
@@ -264,6 +269,7 @@ struct Staging {
     struct Pend { void* dst; const void* src; size_t bytes; };
     std::vector<Pend> pend;
     size_t n_fallback = 0; // copies on this arena's stream that did not fit and went the pageable way
+    size_t n_flush = 0;    // flush() calls so far: whoever queues on `pend` from a buffer of its own tells by it what has arrived
     Staging() = default;
     Staging(const Staging&) = delete;
     Staging& operator=(const Staging&) = delete;
@@ -295,6 +301,7 @@ struct Staging {
     void flush() {
         for (const Pend& q : pend) std::memcpy(q.dst, q.src, q.bytes);
         pend.clear();
+        ++n_flush;
     }
     // `m = mark()` taken when an event was recorded; after waiting for that event the slots handed out before it are free
     size_t mark() const { return head; }

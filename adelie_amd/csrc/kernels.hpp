@@ -335,7 +335,8 @@ void launch_syrk_snp(const SnpView& X, const T* impute, const T* w, const int32_
 // groups (slot[g] >= 0 gives the value offset into screen_beta), plain norm otherwise.
 template <class T>
 void launch_abs_grad(const T* grad, const int64_t* groups, const int64_t* group_sizes, int64_t G, const int32_t* slot,
-                     const T* screen_beta, const T* penalty, T one_minus_alpha_lmda, T* abs_grad, hipStream_t s);
+                     const T* screen_beta, const T* penalty, T one_minus_alpha_lmda, T* abs_grad, hipStream_t s,
+                     T* abs_grad_host = nullptr); // abs_grad_host: the device address of host-mapped memory that takes the same values
 // the same when some groups of one coefficient carry box constraints clo[g] <= beta <= chi[g] (+-inf: none); cmu: the
 // multipliers of the screen values, mu_out (G,): every group's multiplier afterwards
 template <class T>
@@ -402,6 +403,19 @@ struct CdBlkState { // device-resident scalars carried from block to block and r
     int64_t n_updates;
     int32_t active_size, status, nz, _pad;
 };
+// What a Gaussian panel fit hands over once its coefficients and residual are final, in one launch (kernels_convert.hip):
+// the coefficients to beta0 and to host-mapped memory, the residual to its snapshot, the newcomers of the active list and the
+// four words of a filtered sweep to host-mapped memory, and the state the next (speculative) pass starts from to `st`.
+// Parts with a count of 0 / a null pointer are skipped.
+template <class T>
+struct FitHandoff {
+    const T* beta; T* beta0; T* beta_host; int64_t nv;
+    const T* r; T* r_snap; int64_t n;
+    const int32_t* active_set; int32_t* act_host; int64_t act_from, act_count;
+    const int32_t* meta; int32_t* meta_host;
+    CdBlkState<T> st0; CdBlkState<T>* st;
+};
+template <class T> void launch_fit_handoff(const FitHandoff<T>& a, hipStream_t s);
 template <class T>
 struct CdBlkParams {
     int32_t nv;

@@ -14,7 +14,7 @@ template <class T>
 __global__ void abs_grad_kernel(const T* __restrict__ grad, const int64_t* __restrict__ groups,
                                 const int64_t* __restrict__ group_sizes, int64_t G, const int32_t* __restrict__ slot,
                                 const T* __restrict__ screen_beta, const T* __restrict__ penalty, T oma_lmda,
-                                T* __restrict__ abs_grad) {
+                                T* __restrict__ abs_grad, T* __restrict__ abs_grad_host) {
     const int64_t g = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (g >= G) return;
     const int64_t k = groups[g], sz = group_sizes[g];
@@ -29,7 +29,24 @@ __global__ void abs_grad_kernel(const T* __restrict__ grad, const int64_t* __res
     } else {
         for (int64_t t = 0; t < sz; ++t) acc += grad[k + t] * grad[k + t];
     }
-    abs_grad[g] = sqrt(acc);
+    const T a = sqrt(acc);
+    abs_grad[g] = a;
+    if (abs_grad_host) abs_grad_host[g] = a; // (host-mapped: the host reads it after the wait it has behind this launch anyway)
+}
+
+// Solver::fit_handoff: every part is a grid-stride copy bounded by its own count
+template <class T>
+__global__ void fit_handoff_kernel(FitHandoff<T> a) {
+    const int64_t i0 = int64_t(blockIdx.x) * blockDim.x + threadIdx.x, stride = int64_t(gridDim.x) * blockDim.x;
+    for (int64_t i = i0; i < a.n; i += stride) a.r_snap[i] = a.r[i];
+    for (int64_t i = i0; i < a.nv; i += stride) {
+        const T b = a.beta[i];
+        a.beta0[i] = b;
+        a.beta_host[i] = b;
+    }
+    for (int64_t i = i0; i < a.act_count; i += stride) a.act_host[i] = a.active_set[a.act_from + i];
+    if (a.meta && i0 < 4) a.meta_host[i0] = a.meta[i0];
+    if (a.st && i0 == 0) *a.st = a.st0;
 }
 
 // update_abs_grad (solver_base.hpp:20-110) when some groups of one coefficient carry a box constraint
@@ -190,10 +207,17 @@ __global__ __launch_bounds__(256) void snp_impute_kernel(const uint8_t* __restri
 
 template <class T>
 void launch_abs_grad(const T* grad, const int64_t* groups, const int64_t* group_sizes, int64_t G, const int32_t* slot,
-                     const T* screen_beta, const T* penalty, T oma_lmda, T* abs_grad, hipStream_t s) {
+                     const T* screen_beta, const T* penalty, T oma_lmda, T* abs_grad, hipStream_t s, T* abs_grad_host) {
     if (G <= 0) return;
     hipLaunchKernelGGL((abs_grad_kernel<T>), dim3(unsigned((G + 255) / 256)), dim3(256), 0, s, grad, groups,
-                       group_sizes, G, slot, screen_beta, penalty, oma_lmda, abs_grad);
+                       group_sizes, G, slot, screen_beta, penalty, oma_lmda, abs_grad, abs_grad_host);
+}
+
+template <class T>
+void launch_fit_handoff(const FitHandoff<T>& a, hipStream_t s) {
+    const int64_t most = std::max<int64_t>(std::max(a.n, a.nv), std::max<int64_t>(a.act_count, 4));
+    const unsigned grid = unsigned(std::min<int64_t>((most + 255) / 256, 1024));
+    hipLaunchKernelGGL((fit_handoff_kernel<T>), dim3(grid), dim3(256), 0, s, a);
 }
 
 template <class T>
@@ -380,7 +404,8 @@ template void launch_snp_impute<float>(const uint8_t*, int64_t, int64_t, int64_t
 
 #define INST(T)                                                                                                        \
     template void launch_abs_grad<T>(const T*, const int64_t*, const int64_t*, int64_t, const int32_t*, const T*,      \
-                                     const T*, T, T*, hipStream_t);                                                    \
+                                     const T*, T, T*, hipStream_t, T*);                                                \
+    template void launch_fit_handoff<T>(const FitHandoff<T>&, hipStream_t);                                            \
     template void launch_abs_grad_cons<T>(const T*, const int64_t*, const int64_t*, int64_t, const int32_t*, const T*, \
                                           const T*, T, const T*, const T*, const T*, T*, T*, hipStream_t);             \
     template void launch_copy2d<T>(const T*, int64_t, T*, int64_t, int64_t, int64_t, hipStream_t);                     \

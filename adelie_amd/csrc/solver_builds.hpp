@@ -365,6 +365,57 @@
     PassReport* h_report = nullptr;
     int32_t report_seq = 0;
     bool use_report = true;
+    // ---- a Gaussian lambda's hand-off through host-mapped memory (ADELIE_HIP_HANDOFF=copies: through copies on the stream) ----
+    // One fine-grained pinned block per solver, written by kernels through its device address.  Its four parts: the scores of
+    // device_abs_grad (G values), and what fit_handoff (solver_fit.hpp) moves: the coefficients (up to p values), the newcomers
+    // of the active list (up to G words) and the four words of a filtered sweep.  The host reads a part after the wait it has
+    // behind the writing launch today: hand_arrives() queues the part on the staging arena's pending list like a staged download,
+    // and the next Staging::flush() moves it to its place.  The staged downloads had a fresh slot each; the block is fixed, so
+    // a part may be written once between two flushes: hand_arrives() keeps a pending bit per part and throws on a second one.
+    enum HandPart { HAND_SCORES = 0, HAND_BETA, HAND_ACT, HAND_META, HAND_PARTS };
+    char* h_hand = nullptr;
+    char* hand_dev = nullptr;
+    size_t hand_bytes = 0;
+    int hand_state = 0; // 0: not asked yet, 1: ready, -1: off (the hook, no arena on this thread, or no mapped memory)
+    unsigned hand_pending = 0; // bit k: part k was written and has not been flushed to its place yet
+    size_t hand_flush = 0;     // stage.n_flush when hand_pending was last looked at
+    size_t hand_off(int part) const {
+        auto up = [](size_t b) { return (b + 63) & ~size_t(63); };
+        const size_t sizes[HAND_PARTS] = {size_t(G) * sizeof(T), size_t(p) * sizeof(T), size_t(G) * 4, 64};
+        size_t off = 0;
+        for (int k = 0; k < part; ++k) off += up(sizes[k]);
+        return off;
+    }
+    template <class U> U* hand_dev_at(int part) const { return reinterpret_cast<U*>(hand_dev + hand_off(part)); }
+    bool handoff_mapped() {
+        if (hand_state == 0) {
+            hand_state = -1;
+            if (!hooks.handoff_copies && Staging::current() == &stage && stage.base) {
+                hand_bytes = hand_off(HAND_PARTS);
+                void* hp = HostPool::take(hand_bytes, hipHostMallocMapped);
+                void* dp = nullptr;
+                if (hp && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
+                    h_hand = static_cast<char*>(hp);
+                    hand_dev = static_cast<char*>(dp);
+                    hand_state = 1;
+                } else {
+                    (void)hipGetLastError();
+                    HostPool::give(hp, hand_bytes, hipHostMallocMapped);
+                }
+            }
+        }
+        return hand_state == 1 && Staging::current() == &stage;
+    }
+    // the first `bytes` of `part`, written by a launch just enqueued, reach `dst` at the next flush
+    void hand_arrives(void* dst, int part, size_t bytes) {
+        if (!bytes) return;
+        if (hand_flush != stage.n_flush) hand_pending = 0; // (flushed since: every part queued before has reached its place)
+        hand_flush = stage.n_flush;
+        if (hand_pending & (1u << part))
+            throw make_core_error("internal: a part of the hand-off block was written twice before the host read it.");
+        hand_pending |= 1u << part;
+        stage.pend.push_back(Staging::Pend{dst, h_hand + hand_off(part), bytes});
+    }
     ~Solver() {
         // every DevBuf member is parked in the allocation cache by its destructor: nothing may still be running on them
         if (st) (void)hipStreamSynchronize(st);
@@ -378,6 +429,7 @@
                 StreamPool::give(st_x[k]);
             }
         HostPool::give(h_report, sizeof(PassReport), hipHostMallocMapped);
+        HostPool::give(h_hand, hand_bytes, hipHostMallocMapped);
         deferred.drain(); // blocks outgrown during the solve: every stream that may have used them is idle now
 
         if (spec_ev) (void)hipEventDestroy(spec_ev);

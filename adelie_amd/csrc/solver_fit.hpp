@@ -26,7 +26,8 @@
         sc.rsq = rsq_in;
         sc.resid_sum = rsum_io;
         sc.active_size = int32_t(active_set_size);
-        d_sc.upload(&sc, 1, st);
+        // (the Gaussian panel engines carry these in d_blk and only ever write d_sc's n_delta: nothing reads the upload there)
+        if (!(nv > 0 && panel_mode() && !is_glm() && !cov_mode && handoff_mapped())) d_sc.upload(&sc, 1, st);
         CdParams<T> cp{};
         cp.nv = int32_t(nv);
         cp.ns = int32_t(ns);
@@ -63,6 +64,7 @@
         Stopwatch sw;
         sw.start();
         bool small_fit = false; // the whole pin solve ran in the single-workgroup kernel (its scalars are in d_sc)
+        bool fs_meta_owed = false; // the sweep enqueued below was a filtered one whose four words are still to be fetched
         open_from_grad = grad_fresh && !is_glm() && !cov_mode && r_dev == d_r.p && !resume && !std_generic();
         grad_fresh = false; // (whatever engine runs, the residual moves)
         if (!(nv > 0 && panel_mode() && !all_scalar)) join_uv(); // (only the group panel passes know which of them need it)
@@ -75,7 +77,7 @@
             // Gaussian: the residual is final and current on the device -> enqueue the invariance sweep of this lambda now,
             // so that it runs while the host does the post-fit bookkeeping below (otherwise the GPU idles ~0.2 ms per lambda)
             if (!is_glm() && sc.status == CD_OK && r_dev == d_r.p && inv_wanted) {
-                invariance_sweep(lm, int(sc.active_size), &d_blk.p->resid_sum);
+                fs_meta_owed = invariance_sweep(lm, int(sc.active_size), &d_blk.p->resid_sum, handoff_mapped());
                 device_abs_grad(lm, int(sc.active_size));
                 grad_fresh = true;
                 inv_prelaunched = true;
@@ -153,13 +155,22 @@
         active_set_size = size_t(sc.active_size);
         rsum_io = sc.resid_sum;
         o.rsq = sc.rsq;
-        if (!defer_fit_output) d_beta.download(screen_beta.data(), size_t(nv), st);
         std::vector<int32_t> act(active_set_size > old_active ? active_set_size - old_active : 0);
-        if (!act.empty()) d_actset.download(act.data(), act.size(), st, old_active);
+        const bool spec_follows = spec_enabled && spec_next_lm > T(0) && inv_prelaunched && inv_prelaunched_lm == lm && !cons_on &&
+                                  nv > 0 && panel_mode() && r_dev == d_r.p;
+        // With a speculative pass to follow, one launch hands everything over (fit_handoff below) instead of two or three
+        // downloads, two device copies and an upload on the stream.
+        const bool fused = spec_follows && !defer_fit_output && handoff_mapped();
+        if (fused) {
+            fit_handoff(sc, old_active, act, fs_meta_owed);
+        } else {
+            if (fs_meta_owed) d_fs_meta.download(fs_meta, 4, st);
+            if (!defer_fit_output) d_beta.download(screen_beta.data(), size_t(nv), st);
+            if (!act.empty()) d_actset.download(act.data(), act.size(), st, old_active);
+        }
         // everything this fit hands back is enqueued; behind it, the first active pass of the next lambda (see spec_enabled)
         bool waited = false;
-        if (spec_enabled && spec_next_lm > T(0) && inv_prelaunched && inv_prelaunched_lm == lm && !cons_on && nv > 0 &&
-            panel_mode() && r_dev == d_r.p) {
+        if (spec_follows) {
             if (!spec_ev) AHIP_CHECK(hipEventCreateWithFlags(&spec_ev, hipEventDisableTiming));
             AHIP_CHECK(hipEventRecord(spec_ev, st));
             const size_t stage_mark = stage.mark();
@@ -172,9 +183,11 @@
                 }
                 act.clear();
             }
-            d_r_snap.reserve(size_t(n));
-            AHIP_CHECK(hipMemcpyAsync(d_beta0.p, d_beta.p, size_t(nv) * sizeof(T), hipMemcpyDeviceToDevice, st));
-            AHIP_CHECK(hipMemcpyAsync(d_r_snap.p, d_r.p, size_t(n) * sizeof(T), hipMemcpyDeviceToDevice, st));
+            if (!fused) {
+                d_r_snap.reserve(size_t(n));
+                AHIP_CHECK(hipMemcpyAsync(d_beta0.p, d_beta.p, size_t(nv) * sizeof(T), hipMemcpyDeviceToDevice, st));
+                AHIP_CHECK(hipMemcpyAsync(d_r_snap.p, d_r.p, size_t(n) * sizeof(T), hipMemcpyDeviceToDevice, st));
+            }
             CdParams<T> cp2 = cp;
             cp2.lmda = spec_next_lm;
             CdScalars<T> sc2{};
@@ -187,8 +200,9 @@
             grad_fresh = false;
             {
                 struct ModeGuard { int& m; ~ModeGuard() { m = 0; } } mode_guard{spec_mode};
-                if (all_scalar) run_panel_passes(cp2, sc2, r_dev);
-                else run_group_panel_passes(cp2, sc2, r_dev);
+                // (fused: fit_handoff stored the pass's initial state in d_blk, the pass driver uploads none)
+                if (all_scalar) run_panel_passes(cp2, sc2, r_dev, fused);
+                else run_group_panel_passes(cp2, sc2, r_dev, fused);
             }
             if (spec_enqueued) {
                 spec_active = true;
@@ -214,6 +228,26 @@
         o.t_screen = t_cd - o.t_active;
         if (!defer_fit_output) assemble_fit_output(o, true);
         return o;
+    }
+
+    // What a Gaussian panel fit hands over once its coefficients and residual are final and a speculative pass follows, in one
+    // launch (FitHandoff, kernels.hpp): what the host reads goes to the host-mapped block (the coefficients, the newcomers of
+    // the active list into `act`, with `meta_owed` the four words of the filtered sweep enqueued behind the fit), the snapshots
+    // the pass may be rolled back to are taken (d_beta0, d_r_snap), and the state the pass starts from is stored in d_blk.
+    void fit_handoff(const CdScalars<T>& sc, size_t old_active, std::vector<int32_t>& act, bool meta_owed) {
+        d_r_snap.reserve(size_t(n));
+        d_blk.reserve(1);
+        FitHandoff<T> h{};
+        h.beta = d_beta.p; h.beta0 = d_beta0.p; h.beta_host = hand_dev_at<T>(HAND_BETA); h.nv = int64_t(nv);
+        h.r = d_r.p; h.r_snap = d_r_snap.p; h.n = int64_t(n);
+        h.active_set = d_actset.p; h.act_host = hand_dev_at<int32_t>(HAND_ACT);
+        h.act_from = int64_t(old_active); h.act_count = int64_t(act.size());
+        if (meta_owed) { h.meta = d_fs_meta.p; h.meta_host = hand_dev_at<int32_t>(HAND_META); }
+        h.st0 = initial_pass_state(sc); h.st = d_blk.p;
+        launch_fit_handoff<T>(h, st);
+        hand_arrives(screen_beta.data(), HAND_BETA, size_t(nv) * sizeof(T));
+        hand_arrives(act.data(), HAND_ACT, act.size() * sizeof(int32_t));
+        if (meta_owed) hand_arrives(fs_meta, HAND_META, sizeof(fs_meta));
     }
 
     // The coefficient rows a fit hands back (pin_naive:359-394).  Under IRLS only the LAST pin solve of a lambda needs them: the
@@ -282,7 +316,8 @@
         // device scalar for the sweep epilogue
         CdScalars<T> sc{};
         sc.resid_sum = resid_sum;
-        d_sc.upload(&sc, 1, st);
+        // (read by load_screen_gradient's sweep only; pin_solve uploads or skips its own)
+        if (!(panel_mode() && handoff_mapped())) d_sc.upload(&sc, 1, st);
         cur_w = d_w.p;
         cur_xm = d_xm.p;
         if (!panel_mode()) load_screen_gradient(d_w.p, d_r.p, &d_sc.p->resid_sum);

@@ -238,7 +238,8 @@
     // Residual-based block passes (kernels_cd_panel.hip).  Per block: panel step (apply the previous block's changes to the
     // residual, partial gradients of this block) -> reduce -> one-workgroup solve against the cached diagonal block.
     // The residual is current when this returns (no end-of-fit update), also on failure (changes are undone).
-    void run_panel_passes(const CdParams<T>& cp, CdScalars<T>& sc, T* r_dev) {
+    // `state_stored`: d_blk already holds initial_pass_state(sc) (fit_handoff stored it on the stream): no upload here
+    void run_panel_passes(const CdParams<T>& cp, CdScalars<T>& sc, T* r_dev, bool state_stored = false) {
         no_pieces(*D, "the panel engine"); // (unreachable: engine_panel is off; the fused launches below take a dense or a 2-bit view)
         // Block size: 128 visits under fixed weights (Gaussian: a diagonal block is built once and re-used for the rest of
         // the path); 64 under IRLS, where every block is rebuilt per IRLS iteration and used about once, so the MFMA cost
@@ -251,7 +252,7 @@
         panel_setup(maxblk);
         CdBlkState<T> bs = initial_pass_state(sc);
         const int mode = spec_mode; // 1: enqueue one (speculative) active pass and return; 2: that pass is already in flight
-        if (mode != 2) d_blk.upload(&bs, 1, st);
+        if (mode != 2 && !state_stored) d_blk.upload(&bs, 1, st);
         bool first_open = open_from_grad && mode != 2 && !cons_on; // block 0 of the first pass: gradient from the sweep
         open_from_grad = false;
         CdBlkParams<T> bp{};
@@ -853,14 +854,14 @@
         sync();
     }
 
-    void run_group_panel_passes(const CdParams<T>& cp, CdScalars<T>& sc, T* r_dev) {
+    void run_group_panel_passes(const CdParams<T>& cp, CdScalars<T>& sc, T* r_dev, bool state_stored = false) { // (state_stored: see run_panel_passes)
         no_pieces(*D, "the group panel engine"); // (unreachable: engine_panel is off; the fused launches below take a dense or a 2-bit view)
         const int SL = cd_block_size();
         panel_setup(group_maxblk());
         const size_t maxblk = panel_maxblk;
         CdBlkState<T> bs = initial_pass_state(sc);
         const int mode = spec_mode; // see run_panel_passes
-        if (mode != 2) d_blk.upload(&bs, 1, st);
+        if (mode != 2 && !state_stored) d_blk.upload(&bs, 1, st);
         bool first_open = open_from_grad && mode != 2 && !cons_on && !multi(); // see run_panel_passes
         open_from_grad = false;
         CdGrpBlkParams<T> bp{};

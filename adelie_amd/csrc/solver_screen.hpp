@@ -319,6 +319,12 @@
                 launch_cons_abs_grad<T>(d_devcons_list.p, int(devcons_list.size()), d_cons_native.p, d_groups.p, d_gsizes.p, d_slot.p,
                                         d_grad.p, d_beta.p, d_penalty.p, (1 - alpha) * lm, d_cons_va.p, d_cons_vb.p, d_cons_mu.p, d_absgrad.p, st);
         } else {
+            if (handoff_mapped()) { // the scores go to host-mapped memory in the same launch: no copy behind it
+                launch_abs_grad<T>(d_grad.p, d_groups.p, d_gsizes.p, G, d_slot.p, d_beta.p, has_pen2 ? d_penalty2.p : d_penalty.p,
+                                   (1 - alpha) * lm, d_absgrad.p, st, hand_dev_at<T>(HAND_SCORES));
+                hand_arrives(abs_grad.data(), HAND_SCORES, size_t(G) * sizeof(T));
+                return;
+            }
             launch_abs_grad<T>(d_grad.p, d_groups.p, d_gsizes.p, G, d_slot.p, d_beta.p, has_pen2 ? d_penalty2.p : d_penalty.p,
                                (1 - alpha) * lm, d_absgrad.p, st);
         }
@@ -433,8 +439,10 @@
         return fs_state == 1 ? tstar : T(0);
     }
 
-    // v = W o r and the gradient of lambda lm into d_grad, behind whatever is on the stream: filtered when it may be
-    void invariance_sweep(T lm, int active_now, const T* rsum_dev) {
+    // v = W o r and the gradient of lambda lm into d_grad, behind whatever is on the stream: filtered when it may be.
+    // `defer_meta`: the caller fetches the four words of a filtered sweep (d_fs_meta -> fs_meta) itself; returns whether the
+    // sweep was a filtered one that left them to the caller.
+    bool invariance_sweep(T lm, int active_now, const T* rsum_dev, bool defer_meta = false) {
         const T tstar = filter_threshold(lm, active_now);
         if (!(tstar > 0)) {
             launch_vmul<T>(d_w.p, d_r.p, d_v.p, n, st);
@@ -442,7 +450,7 @@
             sweep(d_v.p, d_grad.p, nullptr, p, rsum_dev, intercept ? d_xm.p : nullptr);
             t_sweep.end(st);
             grad_filtered = false;
-            return;
+            return false;
         }
         if constexpr (std::is_same<T, double>::value) {
             const T* xm = intercept ? d_xm.p : nullptr;
@@ -470,12 +478,14 @@
             t_fsweep.begin(st);
             enqueue_filtered_sweep(D->dense<T>(), fs_shadow, a, st);
             t_fsweep.end(st);
-            d_fs_meta.download(fs_meta, 4, st);
+            if (!defer_meta) d_fs_meta.download(fs_meta, 4, st);
             grad_filtered = true;
             fs_lm = lm;
             fs_pending_screen_cols = int64_t(nv) + std::max<int64_t>(fs_pen0_cols, 0);
             ++n_sweeps_filtered;
+            return defer_meta;
         }
+        return false;
     }
 
     // after the host has the downloads of a filtered sweep: its counters, and the full sweep when the list overflowed or a
