@@ -46,7 +46,8 @@ class LinearConstraint(C.Structure):
     """``adelie_hip_linear_constraint`` (ABI 5)."""
 
     _fields_ = [("m", C.c_int64), ("d", C.c_int64), ("A", C.c_void_p), ("lower", C.c_void_p), ("upper", C.c_void_p),
-                ("vars", C.c_void_p), ("cfg", C.c_double * 7)]
+                ("vars", C.c_void_p), ("cfg", C.c_double * 7),
+                ("mu", C.c_void_p), ("order", C.c_void_p), ("n_order", C.c_int64)]  # what the object holds on entry
 
 
 class GlmCallbacks(C.Structure):
@@ -200,13 +201,14 @@ V = dict(
     benchmark_screen=12, benchmark_fit_screen=13, benchmark_fit_active=14, benchmark_kkt=15,
     benchmark_invariance=16,
     rsqs=17, benchmark_active=18, screen_grad=19,  # adelie_hip_gaussian_pin_solve
-    betas_values=200, duals_values=201, constraint_mu=202, constraint_vmu=203,
+    betas_values=200, duals_values=201, constraint_mu=202, constraint_vmu=203, constraint_lmu=204,
 )
 I = dict(
     screen_set=100, screen_begins=101, screen_is_active=102, active_set=103, n_valid_solutions=104,
     active_sizes=105, screen_sizes=106, betas_indptr=107, betas_indices=108,
     duals_indptr=109, duals_indices=110, constraint_dev_groups=111,
     active_begins=112, active_order=113,  # adelie_hip_gaussian_pin_solve
+    constraint_lorder=114, constraint_lnorder=115,  # linear objects solved on the device
 )
 S = dict(
     lmda_max=0, lmda=1, rsq=2, resid_sum=3, active_set_size=4, beta0=5, loss_null=6, loss_full=7,
@@ -336,6 +338,9 @@ class ConsVisit(C.Structure):
         + [(n, C.c_double) for n in ("l1", "l2", "dbeta_tol", "rsq", "resid_sum", "cm")]
         + [("cfg", C.c_double * 5)]
         + [(n, C.c_void_p) for n in ("V", "grad", "beta", "vars", "va", "vb", "mu", "sxm", "dcol", "dlt", "st_f", "st_i")]
+        + [("m", C.c_int64)]  # native 6 (linear) only, from here on
+        + [(n, C.c_void_p) for n in ("lin_A", "lin_lower", "lin_upper", "lin_vars", "lin_order", "lin_norder")]
+        + [("lin_cfg", C.c_double * 2)]
     )
 
 

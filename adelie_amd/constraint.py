@@ -13,7 +13,7 @@ Two routes into the solver (``adelie_hip_grpnet_args::constraint_kind``):
   callbacks of ``adelie_hip_constraint_callbacks`` — the role the reference's ``PyConstraintBase`` trampoline plays.
 
 After a solve every object holds the multipliers of the last fit (``dual`` / ``duals_nnz``), as the reference's objects do.
-``linear`` (a general matrix ``A``) is such a host object too.
+``linear`` (a general matrix ``A``) is such a host object beyond 64 coefficients or 64 rows; up to there it is solved on the device.
 """
 from typing import Union
 
@@ -493,7 +493,9 @@ class _Linear(_ProxNewton, ConstraintBase):
     ``A' mu`` in place of ``mu`` (``:275-470``).  The Newton step minimises the pinball-penalised quadratic model with Hessian
     ``A hess A'`` (the reference's ``m < d`` branch, ``:408-418``; for ``m >= d`` it solves the same sub-problem through a
     low-rank active-set variant), the multipliers at ``x = 0`` come from a sign-bounded least-squares fit of ``A' mu`` to
-    ``Q v`` (``:283-349``) by the reference's warm-started coordinate descent (``_bvls``).  Always a host object."""
+    ``Q v`` (``:283-349``) by the reference's warm-started coordinate descent (``_bvls``).  The solver runs a group of at most 64
+    coefficients with at most 64 rows on the device from ``_linear_descriptor`` (kernels_cons_linear.hip, the same three loops)
+    and leaves ``_mu`` / ``_order`` as the last fit had them; a larger one is visited here, through the callbacks."""
 
     kind = KIND_HOST
 
@@ -550,7 +552,11 @@ class _Linear(_ProxNewton, ConstraintBase):
         for i, v in enumerate((c["max_iters"], c["tol"], self._nnls_cfg[0], self._nnls_cfg[1], c["pinball_max_iters"],
                                c["pinball_tol"], c["slack"])):
             d.cfg[i] = float(v)
-        return d, (A, lo, up, va)
+        # what the object holds on entry: a group of <= 64 coefficients with <= 64 rows is solved on the device from these
+        mu = np.ascontiguousarray(self._mu, dtype=np.float64)
+        order = np.array(self._active_order(mu), dtype=np.int32)
+        d.mu, d.order, d.n_order = mu.ctypes.data, order.ctypes.data, len(order)
+        return d, (A, lo, up, va, mu, order)
 
     def _At(self, mu):
         return self._A.T @ mu

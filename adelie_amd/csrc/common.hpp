@@ -29,7 +29,7 @@ namespace ahip {
 //                                 constrained problems always use                                                   [test hook]
 //   ADELIE_HIP_SPECULATE=0        no speculative first active-set pass behind the invariance sweep                  [A/B, bit-identity test]
 //   ADELIE_HIP_IRLS_REUSE=theta   IRLS diagonal-block / Gram reuse threshold (default 0.1, 0 = rebuild per iteration) [documented deviation]
-//   ADELIE_HIP_CONS_HOST=1        box / one-sided constraint objects visited on the host instead of kernels_cons.hip  [A/B, tests]
+//   ADELIE_HIP_CONS_HOST=1        box / one-sided / linear constraint objects visited on the host instead of kernels_cons*.hip  [A/B, tests]
 //   ADELIE_HIP_SPARSE_PANEL=0     IRLS on a design kept sparse on the full-Gram engines instead of the panel engine    [A/B, tests]
 //   ADELIE_HIP_STD_PANEL=0        standardized dense / 2-bit views on their full-Gram engines instead of the panel engines [A/B, tests]
 //   ADELIE_HIP_FACTOR_SWEEP=0|1   full sweeps of a one-hot / interaction design read off Z (kernels_factor.hip) or off the

@@ -348,7 +348,8 @@ void launch_abs_grad_cons(const T* grad, const int64_t* groups, const int64_t* g
 enum CdStatus : int32_t {
     CD_OK = 0, CD_MAX_CDS = 1, CD_MAX_ACTIVE = 2, CD_NEWTON = 3,
     // constraint objects solved on the device (kernels_cons.hip): the errors of constraint/utils.hpp:24-243 and its sub-solvers
-    CD_CONS_PN = 4, CD_CONS_QP_BOX = 5, CD_CONS_QP_NNQP = 6, CD_CONS_UNEXPECTED = 7
+    CD_CONS_PN = 4, CD_CONS_QP_BOX = 5, CD_CONS_QP_NNQP = 6, CD_CONS_UNEXPECTED = 7,
+    CD_CONS_BVLS = 8 // (kernels_cons_linear.hip: the bounded least squares of a linear object)
 };
 // adelie_hip_grpnet_args::constraint_native
 constexpr int32_t ADELIE_HIP_NATIVE_BOX = 4, ADELIE_HIP_NATIVE_ONE_SIDED = 5, ADELIE_HIP_NATIVE_LINEAR = 6;
@@ -500,6 +501,12 @@ struct ConsVisitParams {
     double cfg[5];                        // max_iters, tol, pinball / nnqp max_iters, its tol, slack
     CdBlkState<T>* host_st; int32_t* host_seq; int32_t report_seq; // end-of-pass report (report_seq = 0: none)
     int64_t* n_visits;                    // device counter or nullptr
+    // NATIVE_LINEAR (kernels_cons_linear.hip): lower <= A x <= upper with m rows; mu then has m entries and va / vb are not read
+    int32_t m;
+    const double* lA;                     // [m * q] row-major
+    const double* llo; const double* lup; const double* lvars; // [m] lower, upper, the squared row norms of A
+    int32_t* lorder; int32_t* lnorder;    // [m] + [1] in/out: the non-zero multipliers in the order they became non-zero
+    double lcfg[2];                       // the bounded least squares' max_iters and tol
 };
 // q <= 64: one wavefront, Q and H in LDS; 65 .. 128: one workgroup of 256 threads, H in LDS and Q read through L2
 // (kernels_cons_wide.hip, reached through launch_grp_cons_visit)
@@ -509,6 +516,26 @@ void launch_grp_cons_visit(const ConsVisitParams<T>& p, hipStream_t s);
 size_t cons_visit_wide_lds(int q);
 template <class T>
 void launch_grp_cons_visit_wide(const ConsVisitParams<T>& p, hipStream_t s);
+// a linear object (q <= 64 coefficients, m <= 64 rows): one wavefront, B = A V and the dual Hessian in LDS
+size_t cons_visit_linear_lds(int m, int q);
+template <class T>
+void launch_grp_cons_visit_linear(const ConsVisitParams<T>& p, hipStream_t s);
+// what the solver keeps on the device for its linear objects: per group (G,) the offset of A, the offset of the group's rows in
+// the per-row arrays (dual_groups), m and the bounded least squares' (max_iters, tol); per row the bounds, variances, multipliers
+// and the order list; err: set to a CdStatus when a solve_zero fails
+template <class T>
+struct ConsLinearStore {
+    const int64_t* aoff; const int64_t* doff; const int32_t* m;
+    const double* A; const double* lower; const double* upper; const double* vars;
+    T* mu; int32_t* order; int32_t* norder;
+    const double* cfg;
+    int32_t* err;
+};
+// abs_grad of the groups of `list` whose object is linear (the others are skipped): one wavefront each
+template <class T>
+void launch_cons_linear_abs_grad(const int32_t* list, int count, const int32_t* native, const int64_t* groups, const int64_t* gsizes,
+                                 const int32_t* slot, const T* grad, const T* beta, const T* penalty, T regul_scale,
+                                 const ConsLinearStore<T>& ls, T* abs_grad, hipStream_t s);
 // abs_grad (and, outside the screen set, the solve_zero multipliers) of the `count` groups in `list` with device constraint objects
 template <class T>
 void launch_cons_abs_grad(const int32_t* list, int count, const int32_t* native, const int64_t* groups, const int64_t* gsizes,

@@ -23,6 +23,7 @@
 #include <string>
 #include "kernels.hpp"
 #include "wavered.hpp"
+#include "cons_common.hpp" // ConsRc, group_prox (shared with kernels_cons_linear.hip)
 
 namespace ahip {
 
@@ -63,34 +64,6 @@ __device__ __forceinline__ double matvec_t(const ConsCtx& c, const double* M, do
         for (int i = 0; i < c.d; ++i) acc += M[i + c.lane * c.LD] * c.vs[i];
     return acc;
 }
-
-// bcd/unconstrained/newton.hpp:35-142 + optimization/newton.hpp:28-65 (the unconstrained group update, started at h = 0 as the
-// reference's): x, and the buffers b1 = L + l2, b2 = 1 / (b1 h + l1) the dual Hessian reads
-__device__ __forceinline__ void group_prox(const ConsCtx& c, double L, double v, double l1, double l2, double& x, double& b1, double& b2) {
-    const bool in = c.lane < c.d;
-    const double vn = sqrt(wsum(in ? v * v : 0.0));
-    if (vn <= l1) { x = 0; return; }
-    if (l1 <= 0.0) { x = in ? v / (L + l2) : 0.0; return; }
-    b1 = L + l2;
-    double h = 0, fh, dfh;
-    auto step_f = [&](double hh) {
-        b2 = in ? 1.0 / (b1 * hh + l1) : 0.0;
-        const double z = v * b2, zz = in ? z * z : 0.0;
-        const double t = wsum(zz);
-        fh = t - 1.0;
-        const double s = wsum(zz * b1 * b2);
-        dfh = -s * (1.0 + sqrt(t)) / t;
-    };
-    step_f(h);
-    for (int it = 0; fabs(fh) > 1e-12 && it < 100000; ++it) {
-        h -= fh / dfh;
-        h = fmax(h, 0.0);
-        step_f(h);
-    }
-    x = in ? h * v * b2 : 0.0;
-}
-
-enum ConsRc { CRC_OK = 0, CRC_PN = 1, CRC_QP = 2, CRC_UNEXPECTED = 3 };
 
 // The quadratic sub-problem in mu by coordinate descent (ProxNewton's newton_step): g = gradient of the model at mu (kept
 // current), var * qp_tol the stopping threshold.  Box: pinball_full.hpp:92-104 with penalty_neg = lo, penalty_pos = up;
@@ -332,6 +305,7 @@ __global__ void cons_abs_grad_kernel(const int32_t* __restrict__ list, int count
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count) return;
     const int g = list[t];
+    if (native[g] == ADELIE_HIP_NATIVE_LINEAR) return; // (cons_linear_abs_grad_kernel)
     const int64_t k = groups[g], q = gsizes[g];
     const bool box = native[g] == ADELIE_HIP_NATIVE_BOX;
     double acc = 0;
@@ -370,6 +344,7 @@ size_t cons_visit_lds(int q) { return q > CW ? cons_visit_wide_lds(q) : (size_t(
 
 template <class T>
 void launch_grp_cons_visit(const ConsVisitParams<T>& p, hipStream_t s) {
+    if (p.native == ADELIE_HIP_NATIVE_LINEAR) return launch_grp_cons_visit_linear<T>(p, s); // kernels_cons_linear.hip
     if (p.q < 1 || p.q > 2 * CW) throw std::runtime_error("adelie_hip: device constraint visit of a group beyond 128 coefficients.");
     if (p.q > CW) return launch_grp_cons_visit_wide<T>(p, s); // 65 .. 128: one workgroup of four wavefronts
     static const bool raised = [] {

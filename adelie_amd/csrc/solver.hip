@@ -431,6 +431,9 @@ struct Result : ResultBase {
             case ADELIE_HIP_V_CONSTRAINT_MU: return s.cons_on ? s.G : 0;
             case ADELIE_HIP_V_CONSTRAINT_VMU: return s.cons_dev ? s.p : 0;
             case ADELIE_HIP_I_CONSTRAINT_DEV_GROUPS: return s.cons_dev ? int64_t(s.devcons_list.size()) : 0;
+            case ADELIE_HIP_V_CONSTRAINT_LMU: return s.cons_dev && s.any_lin_dev ? int64_t(s.lin_mu.size()) : 0;
+            case ADELIE_HIP_I_CONSTRAINT_LORDER: return s.cons_dev && s.any_lin_dev ? int64_t(s.lin_order.size()) : 0;
+            case ADELIE_HIP_I_CONSTRAINT_LNORDER: return s.cons_dev && s.any_lin_dev ? int64_t(s.lin_norder.size()) : 0;
             case ADELIE_HIP_V_RSQS: return s.pin_rsqs.size();
             case ADELIE_HIP_V_BENCHMARK_ACTIVE: return s.pin_bench_active.size();
             case ADELIE_HIP_V_SCREEN_GRAD: return s.pin_screen_grad.size();
@@ -527,6 +530,9 @@ struct Result : ResultBase {
                 cp_d(s.cons_vmu, d, cap);
                 return 0;
             }
+            case ADELIE_HIP_V_CONSTRAINT_LMU: if (s.cons_dev && s.any_lin_dev) cp_d(s.lin_mu, d, cap); return 0;
+            case ADELIE_HIP_I_CONSTRAINT_LORDER: if (s.cons_dev && s.any_lin_dev) cp_i(s.lin_order, ii, cap); return 0;
+            case ADELIE_HIP_I_CONSTRAINT_LNORDER: if (s.cons_dev && s.any_lin_dev) cp_i(s.lin_norder, ii, cap); return 0;
         }
         return 1;
     }

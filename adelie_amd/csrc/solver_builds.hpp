@@ -64,9 +64,30 @@
     DevBuf<int32_t> d_cons_native, d_devcons_list;
     DevBuf<int64_t> d_cons_nvis;
     int64_t n_host_cons_visits = 0, n_dev_cons_visits_final = 0;
+    // ... and the built-in linear class (constraint_native 6: lower <= A x <= upper, described by constraint_lin[g]) on groups of
+    // <= 64 coefficients with <= 64 rows (kernels_cons_linear.hip): A, the bounds and the row variances are uploaded once per
+    // solve, the m multipliers of a group and the order in which they became non-zero live in d_lin_mu / d_lin_order at
+    // dual_groups[g] (d_lin_norder[g] entries of the order are in use)
+    std::vector<int32_t> lin_m;                // (G,) rows of a linear object that came with its description, else 0
+    std::vector<int64_t> lin_aoff;             // (G,) offset of the group's A in d_lin_A
+    std::vector<double> lin_cfg;               // (G, 2) the bounded least squares' max_iters, tol
+    std::vector<T> lin_mu;                     // (n_duals,) host mirrors
+    std::vector<int32_t> lin_order, lin_norder; // (n_duals,), (G,)
+    DevBuf<double> d_lin_A, d_lin_lo, d_lin_up, d_lin_vars, d_lin_cfg;
+    DevBuf<int64_t> d_lin_aoff, d_lin_doff;
+    DevBuf<int32_t> d_lin_m, d_lin_order, d_lin_norder, d_lin_err;
+    DevBuf<T> d_lin_mu;
+    int32_t lin_err = 0;
+    bool any_lin_dev = false;
+    bool lin_dev(idx g) const { return cons_native[g] == ADELIE_HIP_NATIVE_LINEAR; } // (of a group with on_device())
+    ConsLinearStore<T> lin_store() {
+        return ConsLinearStore<T>{d_lin_aoff.p, d_lin_doff.p, d_lin_m.p, d_lin_A.p, d_lin_lo.p, d_lin_up.p, d_lin_vars.p,
+                                  d_lin_mu.p, d_lin_order.p, d_lin_norder.p, d_lin_cfg.p, d_lin_err.p};
+    }
     bool on_device(idx g) const {
-        return cons_dev && host_cons(g) && (cons_native[g] == ADELIE_HIP_NATIVE_BOX || cons_native[g] == ADELIE_HIP_NATIVE_ONE_SIDED) &&
-               group_sizes[g] <= 128;
+        if (!cons_dev || !host_cons(g)) return false;
+        if (cons_native[g] == ADELIE_HIP_NATIVE_LINEAR) return group_sizes[g] <= 64 && lin_m[g] >= 1 && lin_m[g] <= 64;
+        return (cons_native[g] == ADELIE_HIP_NATIVE_BOX || cons_native[g] == ADELIE_HIP_NATIVE_ONE_SIDED) && group_sizes[g] <= 128;
     }
     adelie_hip_glm_callbacks glm_cb{};       // glm_kind == CALLBACK: the user's GlmBase subclass, evaluated on the host
     std::vector<T> cb_eta, cb_grad, cb_hess, cb_z;

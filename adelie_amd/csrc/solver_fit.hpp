@@ -127,6 +127,7 @@
             if (sc.status == CD_CONS_PN) throw make_solver_error("ConstraintBase: proximal newton max iterations reached!");
             if (sc.status == CD_CONS_QP_BOX) throw make_solver_error("StatePinballFull: max iterations reached!");
             if (sc.status == CD_CONS_QP_NNQP) throw make_solver_error("StateNNQPFull: max iterations reached!");
+            if (sc.status == CD_CONS_BVLS) throw make_solver_error("bvls: max iterations reached!");
             if (sc.status == CD_CONS_UNEXPECTED)
                 throw make_core_error("Possibly an unexpected error! Previous iterate should have been properly initialized. ");
             throw make_solver_error("Newton-ABS max iterations reached! Try increasing newton_max_iters.");

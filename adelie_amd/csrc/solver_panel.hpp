@@ -768,12 +768,96 @@
         vp.host_st = rep_st_dev; vp.host_seq = rep_seq_dev;
         vp.report_seq = (report && h_report) ? ++report_seq : 0;
         vp.n_visits = d_cons_nvis.p;
+        if (lin_dev(g)) { // a linear object: m multipliers at dual_groups[g] (kernels_cons_linear.hip)
+            const idx o = dual_groups[g];
+            vp.m = lin_m[g];
+            vp.lA = d_lin_A.p + lin_aoff[g];
+            vp.llo = d_lin_lo.p + o; vp.lup = d_lin_up.p + o; vp.lvars = d_lin_vars.p + o;
+            vp.mu = d_lin_mu.p + o; vp.lorder = d_lin_order.p + o; vp.lnorder = d_lin_norder.p + g;
+            vp.lcfg[0] = lin_cfg[size_t(g) * 2]; vp.lcfg[1] = lin_cfg[size_t(g) * 2 + 1];
+        }
         launch_grp_cons_visit<T>(vp, st);
+    }
+    // The linear objects that run on the device: their description (constraint_lin) and what they hold on entry, uploaded once per
+    // solve.  n_duals: the number of multipliers of all constraints (the per-row arrays are indexed by dual_groups).
+    void upload_linear_objects(const adelie_hip_grpnet_args* a, idx n_duals) {
+        any_lin_dev = false;
+        for (int32_t g : devcons_list) any_lin_dev = any_lin_dev || lin_dev(g);
+        if (!any_lin_dev) return;
+        const size_t nd = size_t(std::max<idx>(n_duals, 1));
+        std::vector<double> A, lo(nd, 0.0), up(nd, 0.0), va(nd, 0.0);
+        lin_aoff.assign(size_t(G), 0);
+        lin_cfg.assign(size_t(G) * 2, 0.0);
+        lin_mu.assign(nd, T(0));
+        lin_order.assign(nd, -1);
+        lin_norder.assign(size_t(G), 0);
+        for (int32_t g : devcons_list) {
+            if (!lin_dev(g)) continue;
+            const adelie_hip_linear_constraint& ld = *a->constraint_lin[g];
+            const idx m = ld.m, d = ld.d, o = dual_groups[g];
+            lin_aoff[size_t(g)] = int64_t(A.size());
+            A.insert(A.end(), ld.A, ld.A + size_t(m) * size_t(d));
+            for (idx k = 0; k < m; ++k) {
+                if (ld.upper[k] < 0) throw make_core_error("upper must be >= 0.");
+                if (ld.lower[k] > 0) throw make_core_error("lower must be <= 0.");
+                lo[size_t(o + k)] = ld.lower[k]; up[size_t(o + k)] = ld.upper[k]; va[size_t(o + k)] = ld.vars[k];
+                if (ld.mu) lin_mu[size_t(o + k)] = T(ld.mu[k]);
+            }
+            // cfg: max_iters, tol, nnls_max_iters, nnls_tol, pinball_max_iters, pinball_tol, slack (the loops of the kernel are bounded by these)
+            lin_cfg[size_t(g) * 2] = std::min(std::max(ld.cfg[2], 0.0), 1e9);
+            lin_cfg[size_t(g) * 2 + 1] = ld.cfg[3];
+            std::vector<uint8_t> seen(size_t(m), 0);
+            if (ld.order)
+                for (int64_t t = 0; t < ld.n_order; ++t) {
+                    const int32_t k = ld.order[t];
+                    if (k < 0 || k >= m || seen[size_t(k)]) throw make_core_error("constraint_lin: order must list distinct rows.");
+                    seen[size_t(k)] = 1;
+                    lin_order[size_t(o + lin_norder[size_t(g)]++)] = k;
+                }
+        }
+        d_lin_A.reserve(A.size()); d_lin_lo.reserve(nd); d_lin_up.reserve(nd); d_lin_vars.reserve(nd); d_lin_cfg.reserve(size_t(G) * 2);
+        d_lin_aoff.reserve(G); d_lin_doff.reserve(G); d_lin_m.reserve(G); d_lin_order.reserve(nd); d_lin_norder.reserve(G);
+        d_lin_err.reserve(1); d_lin_mu.reserve(nd);
+        d_lin_A.upload(A.data(), A.size(), st);
+        d_lin_lo.upload(lo.data(), nd, st); d_lin_up.upload(up.data(), nd, st); d_lin_vars.upload(va.data(), nd, st);
+        d_lin_cfg.upload(lin_cfg.data(), lin_cfg.size(), st);
+        d_lin_aoff.upload(lin_aoff.data(), size_t(G), st);
+        d_lin_doff.upload(dual_groups.data(), size_t(G), st);
+        d_lin_m.upload(lin_m.data(), size_t(G), st);
+        d_lin_mu.upload(lin_mu.data(), nd, st);
+        d_lin_order.upload(lin_order.data(), nd, st);
+        d_lin_norder.upload(lin_norder.data(), size_t(G), st);
+        lin_err = 0;
+        d_lin_err.upload(&lin_err, 1, st);
+        sync(); // (A, lo, up, va are locals)
+    }
+    // abs_grad of those groups for the state that was handed in (dev_cons_abs_grad_host's job for the box / one-sided objects): the
+    // device kernel itself, on a screen layout of its own since the solver's is not built yet
+    void linear_abs_grad_at_construction(T lm) {
+        if (!cons_dev || !any_lin_dev) return;
+        std::vector<int32_t> begin_of(static_cast<size_t>(G), int32_t(-1));
+        for (size_t ss = 0; ss < screen_set.size() && ss < screen_begins.size(); ++ss) begin_of[size_t(screen_set[ss])] = int32_t(screen_begins[ss]);
+        DevBuf<int32_t> d_begin;
+        DevBuf<T> d_sbeta;
+        d_begin.reserve(G); d_sbeta.reserve(std::max<size_t>(screen_beta.size(), 1));
+        d_begin.upload(begin_of.data(), size_t(G), st);
+        if (!screen_beta.empty()) d_sbeta.upload(screen_beta.data(), screen_beta.size(), st);
+        d_absgrad.upload(abs_grad.data(), size_t(G), st);
+        launch_cons_linear_abs_grad<T>(d_devcons_list.p, int(devcons_list.size()), d_cons_native.p, d_groups.p, d_gsizes.p, d_begin.p,
+                                       d_grad.p, d_sbeta.p, d_penalty.p, (1 - alpha) * lm, lin_store(), d_absgrad.p, st);
+        d_absgrad.download(abs_grad.data(), size_t(G), st);
+        d_lin_err.download(&lin_err, 1, st);
+        sync();
+        check_linear_error();
+    }
+    void check_linear_error() {
+        if (lin_err == CD_CONS_BVLS) throw make_solver_error("bvls: max iterations reached!");
     }
     // abs_grad of the groups with host constraint objects (solver_base.hpp:62-93): the constraint's gradient for screened groups,
     // its solve_zero for the others; overrides what the device kernel wrote for them (it knows no bounds for these groups)
     void host_cons_abs_grad(T lm) {
         if (!cons_host) return;
+        check_linear_error(); // (a solve_zero of cons_linear_abs_grad_kernel that failed; device_abs_grad fetched the flag)
         if (cons_dev && devcons_list.size() == n_host_cons) return; // every object runs on the device
         d_grad.download(grad.data(), size_t(p), st);
         sync();
@@ -820,6 +904,7 @@
         d_cons_vb.download(vb.data(), size_t(p), st);
         sync();
         for (int32_t g : devcons_list) {
+            if (lin_dev(g)) continue; // (linear_abs_grad_at_construction)
             const idx q = group_sizes[g], k = groups[g];
             const bool box = cons_native[g] == ADELIE_HIP_NATIVE_BOX;
             double acc = 0;

@@ -109,6 +109,13 @@
             for (idx g = 0; g < G; ++g) {
                 if (!cons_kind[g]) continue;
                 if (on_device(g)) { // multipliers per coefficient, in the object's order (the gradient convention: box mu, one-sided mu >= 0)
+                    if (lin_dev(g)) { // (a linear object: its m multipliers)
+                        for (idx t = 0; t < lin_m[g]; ++t) {
+                            const T m = lin_mu[size_t(dual_groups[g] + t)];
+                            if (m != 0) { di.push_back(dual_groups[g] + t); dv.push_back(m); }
+                        }
+                        continue;
+                    }
                     for (idx t = 0; t < group_sizes[g]; ++t) {
                         const T m = cons_vmu[size_t(groups[g] + t)];
                         if (m != 0) { di.push_back(dual_groups[g] + t); dv.push_back(m); }
@@ -300,11 +307,19 @@
         download_invariants();
     }
 
+    // what the linear objects on the device hold -> host mirrors (on the solver's stream; the caller synchronises)
+    void download_linear_state() {
+        if (!any_lin_dev) return;
+        d_lin_mu.download(lin_mu.data(), lin_mu.size(), st);
+        d_lin_order.download(lin_order.data(), lin_order.size(), st);
+        d_lin_norder.download(lin_norder.data(), lin_norder.size(), st);
+    }
     // multipliers of the screened coordinates as their last visits left them (device) -> host mirror
     std::vector<T> cmu_stage;
     void refresh_screen_multipliers() {
         if (cons_on && cons_dev) { // the device objects' multipliers, screened or not (cons_abs_grad_kernel keeps the others)
             d_cons_mu.download(cons_vmu.data(), size_t(p), st);
+            download_linear_state();
             if (nv <= 0) sync();
         }
         if (!cons_on || nv <= 0) return;
@@ -325,6 +340,7 @@
         if (is_glm()) d_eta.download(eta.data(), size_t(n), st);
         if (cons_dev) { // what the device-side constraint objects hold, and how often they were visited
             d_cons_mu.download(cons_vmu.data(), size_t(p), st);
+            download_linear_state();
             d_cons_nvis.download(&n_dev_cons_visits_final, 1, st);
         }
         if (nv > 0) {
@@ -600,6 +616,14 @@
                     cons_native.assign(a->constraint_native, a->constraint_native + G);
                     cons_cfg.assign(a->constraint_cfg, a->constraint_cfg + size_t(G) * 5);
                     cons_dev = true; // (on_device() reads cons_native)
+                    lin_m.assign(size_t(G), 0);
+                    if (a->constraint_lin)
+                        for (idx g = 0; g < G; ++g) {
+                            const adelie_hip_linear_constraint* ld = a->constraint_lin[g];
+                            if (cons_native[g] != ADELIE_HIP_NATIVE_LINEAR || !ld || !ld->A || !ld->lower || !ld->upper || !ld->vars) continue;
+                            if (ld->d != group_sizes[g] || ld->m != cons_m[g]) throw make_core_error("constraint_lin: A must be (m, d) for a group of d coefficients with m multipliers.");
+                            if (ld->m >= 1 && ld->m <= 64) lin_m[g] = int32_t(ld->m);
+                        }
                     devcons_list.clear();
                     for (idx g = 0; g < G; ++g)
                         if (on_device(g)) devcons_list.push_back(int32_t(g));
@@ -608,7 +632,7 @@
                         const T* va = static_cast<const T*>(a->constraint_va);
                         const T* vb = static_cast<const T*>(a->constraint_vb);
                         for (int32_t g : devcons_list)
-                            for (idx t = 0; t < group_sizes[g]; ++t) {
+                            for (idx t = 0; t < group_sizes[g] && !lin_dev(g); ++t) {
                                 const idx k = groups[g] + t;
                                 if (cons_native[g] == ADELIE_HIP_NATIVE_BOX) { // constraint_box.ipp:30-37
                                     if (vb[k] < 0) throw make_core_error("upper must be >= 0.");
@@ -622,8 +646,9 @@
                         if (a->constraint_vmu) {
                             const T* vm = static_cast<const T*>(a->constraint_vmu);
                             for (int32_t g : devcons_list)
-                                for (idx t = 0; t < group_sizes[g]; ++t) cons_vmu[size_t(groups[g] + t)] = vm[groups[g] + t];
+                                for (idx t = 0; t < group_sizes[g] && !lin_dev(g); ++t) cons_vmu[size_t(groups[g] + t)] = vm[groups[g] + t];
                         }
+                        upload_linear_objects(a, nd);
                         d_cons_va.reserve(p); d_cons_vb.reserve(p); d_cons_mu.reserve(p); d_cons_native.reserve(G);
                         d_devcons_list.reserve(devcons_list.size()); d_cons_nvis.reserve(1);
                         d_cons_va.upload(va, size_t(p), st);
@@ -662,6 +687,7 @@
         update_abs_grad_host(lmda);
         host_cons_abs_grad(lmda);
         dev_cons_abs_grad_host(lmda);
+        linear_abs_grad_at_construction(lmda);
 
         if (cov_mode) {
             if (!a->cov_v && !pin_mode) throw make_core_error("v must be (p,) where A is (p, p).");

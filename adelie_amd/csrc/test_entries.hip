@@ -983,17 +983,36 @@ int adelie_hip_glm_piece_test(const adelie_hip_glm_piece* a, int64_t* info) {
     ABI_CATCH
 }
 
-// One visit of a group with a box / one-sided constraint object, through launch_grp_cons_visit (include/adelie_hip.h has the
-// arrays): q <= 64 reaches the one-wavefront kernel of kernels_cons.hip, 65 .. 128 the workgroup kernel of kernels_cons_wide.hip.
+// One visit of a group with a box / one-sided / linear constraint object, through launch_grp_cons_visit (include/adelie_hip.h has
+// the arrays): q <= 64 reaches the one-wavefront kernel of kernels_cons.hip, 65 .. 128 the workgroup kernel of kernels_cons_wide.hip,
+// a linear object (native 6, q <= 64, m <= 64) the one-wavefront kernel of kernels_cons_linear.hip.
 int adelie_hip_cons_visit_test(const adelie_hip_cons_visit* a) {
     ABI_TRY
     if (!a) throw make_core_error("bad arguments.");
     if (a->dtype != ADELIE_HIP_F64 && a->dtype != ADELIE_HIP_F32) throw make_core_error("bad dtype.");
     const int64_t q = a->q;
     if (q < 1 || q > 128) throw make_core_error("1 <= q <= 128 is required.");
-    if (a->native != ADELIE_HIP_NATIVE_BOX && a->native != ADELIE_HIP_NATIVE_ONE_SIDED)
-        throw make_core_error("native must be 4 (box) or 5 (one-sided).");
-    if (!a->grad || !a->beta || !a->vars || !a->va || !a->vb || !a->mu || !a->dcol || !a->dlt || !a->st_f || !a->st_i || (q > 1 && !a->V))
+    const bool linear = a->native == ADELIE_HIP_NATIVE_LINEAR;
+    if (a->native != ADELIE_HIP_NATIVE_BOX && a->native != ADELIE_HIP_NATIVE_ONE_SIDED && !linear)
+        throw make_core_error("native must be 4 (box), 5 (one-sided) or 6 (linear).");
+    const int64_t nm = linear ? a->m : q; // multipliers
+    if (linear) {
+        if (q > 64 || nm < 1 || nm > 64) throw make_core_error("linear: q <= 64 and 1 <= m <= 64 are required.");
+        if (!a->lin_A || !a->lin_lower || !a->lin_upper || !a->lin_vars || !a->lin_order || !a->lin_norder)
+            throw make_core_error("linear: lin_A, lin_lower, lin_upper, lin_vars, lin_order and lin_norder are required.");
+        if (!(a->lin_cfg[0] >= 0 && a->lin_cfg[0] <= 1e8) || !(a->lin_cfg[1] >= 0)) throw make_core_error("lin_cfg: 0 <= max_iters <= 1e8, tol >= 0.");
+        if (a->lin_norder[0] < 0 || a->lin_norder[0] > nm) throw make_core_error("linear: 0 <= lin_norder <= m is required.");
+        std::vector<uint8_t> seen(size_t(nm), 0);
+        for (int64_t t = 0; t < nm; ++t) {
+            if (!(a->lin_upper[t] >= 0)) throw make_core_error("upper must be >= 0.");
+            if (!(a->lin_lower[t] <= 0)) throw make_core_error("lower must be <= 0.");
+            if (t >= a->lin_norder[0]) continue;
+            const int32_t k = a->lin_order[t];
+            if (k < 0 || k >= nm || seen[size_t(k)]) throw make_core_error("linear: lin_order must list distinct rows.");
+            seen[size_t(k)] = 1;
+        }
+    }
+    if (!a->grad || !a->beta || !a->vars || (!linear && (!a->va || !a->vb)) || !a->mu || !a->dcol || !a->dlt || !a->st_f || !a->st_i || (q > 1 && !a->V))
         throw make_core_error("V (q > 1), grad, beta, vars, va, vb, mu, dcol, dlt, st_f and st_i are required.");
     if ((a->gram != 0 && a->gram != 1) || (a->mark != 0 && a->mark != 1) || (a->first_of_pass != 0 && a->first_of_pass != 1) ||
         (a->is_active != 0 && a->is_active != 1))
@@ -1014,7 +1033,7 @@ int adelie_hip_cons_visit_test(const adelie_hip_cons_visit* a) {
         using T = decltype(tag);
         const T* va = static_cast<const T*>(a->va);
         const T* vb = static_cast<const T*>(a->vb);
-        for (int64_t t = 0; t < q; ++t) { // the rules of the path driver (solver_path.hpp)
+        for (int64_t t = 0; t < q && !linear; ++t) { // the rules of the path driver (solver_path.hpp)
             if (a->native == ADELIE_HIP_NATIVE_BOX) { // constraint_box.ipp:30-37
                 if (!(vb[t] >= 0)) throw make_core_error("upper must be >= 0.");
                 if (!(va[t] <= 0)) throw make_core_error("lower must be <= 0.");
@@ -1029,8 +1048,15 @@ int adelie_hip_cons_visit_test(const adelie_hip_cons_visit* a) {
         DevBuf<CdBlkState<T>> dst;
         if (q > 1) st.up(dV, static_cast<const T*>(a->V), q * q);
         st.up(dg, static_cast<const T*>(a->grad), q); st.up(dbeta, static_cast<const T*>(a->beta), q);
-        st.up(dvars, static_cast<const T*>(a->vars), q); st.up(dva, va, q); st.up(dvb, vb, q);
-        st.up(dmu, static_cast<const T*>(a->mu), q);
+        st.up(dvars, static_cast<const T*>(a->vars), q);
+        if (!linear) { st.up(dva, va, q); st.up(dvb, vb, q); }
+        st.up(dmu, static_cast<const T*>(a->mu), nm);
+        DevBuf<double> dlA, dllo, dlup, dlva;
+        DevBuf<int32_t> dlord, dlnord;
+        if (linear) {
+            st.up(dlA, a->lin_A, nm * q); st.up(dllo, a->lin_lower, nm); st.up(dlup, a->lin_upper, nm); st.up(dlva, a->lin_vars, nm);
+            st.up(dlord, a->lin_order, nm); st.up(dlnord, a->lin_norder, 1);
+        }
         if (a->sxm) st.up(dsxm, static_cast<const T*>(a->sxm), q);
         st.up(ddlt, static_cast<const T*>(a->dlt), q); st.up(ddcol, a->dcol, q);
         const int8_t act = int8_t(a->is_active);
@@ -1049,6 +1075,10 @@ int adelie_hip_cons_visit_test(const adelie_hip_cons_visit* a) {
         vp.max_active_size = int32_t(a->max_active_size);
         vp.dcol = ddcol.p; vp.dlt = ddlt.p; vp.va = dva.p; vp.vb = dvb.p; vp.mu = dmu.p;
         for (int e = 0; e < 5; ++e) vp.cfg[e] = a->cfg[e];
+        if (linear) {
+            vp.m = int32_t(nm); vp.lA = dlA.p; vp.llo = dllo.p; vp.lup = dlup.p; vp.lvars = dlva.p;
+            vp.lorder = dlord.p; vp.lnorder = dlnord.p; vp.lcfg[0] = a->lin_cfg[0]; vp.lcfg[1] = a->lin_cfg[1];
+        }
         hipEvent_t e0, e1;
         AHIP_CHECK(hipEventCreate(&e0));
         AHIP_CHECK(hipEventCreate(&e1));
@@ -1059,7 +1089,8 @@ int adelie_hip_cons_visit_test(const adelie_hip_cons_visit* a) {
         int8_t act1 = 0;
         st.down(&hst, dst.p, sizeof(hst));
         st.down(&act1, disact.p, 1);
-        st.fetch(a->beta, dbeta.p, size_t(q) * sizeof(T)); st.fetch(a->mu, dmu.p, size_t(q) * sizeof(T));
+        st.fetch(a->beta, dbeta.p, size_t(q) * sizeof(T)); st.fetch(a->mu, dmu.p, size_t(nm) * sizeof(T));
+        if (linear) { st.fetch(a->lin_order, dlord.p, size_t(nm) * sizeof(int32_t)); st.fetch(a->lin_norder, dlnord.p, sizeof(int32_t)); }
         st.fetch(a->dlt, ddlt.p, size_t(q) * sizeof(T)); st.fetch(a->dcol, ddcol.p, size_t(q) * sizeof(int32_t));
         st.land();
         float ms = 0;

@@ -363,8 +363,18 @@ class base:
                 # box / one-sided objects on several coefficients that the DEVICE solved: the same courtesy.  Which groups those
                 # were is the library's report (ABI 9), not a rule restated here.  Such an object is not live during the solve
                 # (an exit_cond callback sees the multipliers it entered with); it holds the last fit's on return.
+                lin = None
                 for i in backend.result_vec(r, _abi.I["constraint_dev_groups"], index=True):
                     c = cons[int(i)]
+                    if isinstance(c, _constraint._Linear):  # m multipliers at dual_groups[i], and the order they entered in
+                        if lin is None:
+                            lin = (backend.result_vec(r, _abi.V["constraint_lmu"]),
+                                   backend.result_vec(r, _abi.I["constraint_lorder"], index=True),
+                                   backend.result_vec(r, _abi.I["constraint_lnorder"], index=True))
+                        o = int(new.dual_groups[int(i)])
+                        c._mu[...] = lin[0][o:o + c.dual_size]
+                        c._order = [int(k) for k in lin[1][o:o + int(lin[2][int(i)])]]
+                        continue
                     g0 = int(self.groups[int(i)])
                     c._mu[...] = vmu[g0:g0 + c.primal_size]
         sc = lambda nm: backend.fn("result_scalar")(r, _abi.S[nm])

@@ -396,8 +396,13 @@ enum adelie_hip_constraint_kind {
 
 /* ABI 5.  Description of a `linear` constraint object (reference ConstraintLinear, adelie/constraint.py:137-306,
  * constraint_linear.ipp:142-217):  lower <= A z <= upper  on the group's d coefficients, m rows, with the settings of the
- * reference's proximal-Newton solver.  Like constraint_native / _va / _vb / _cfg it is read by the CPU checker (oracle/) only,
- * which runs such a group with its own restatement of that solver; libadelie_hip.so visits the group through constraint_cb. */
+ * reference's proximal-Newton solver.  The CPU checker (oracle/) runs such a group with its own restatement of that solver;
+ * libadelie_hip.so solves it ON THE DEVICE (kernels_cons_linear.hip: one wavefront per visit) when d <= 64 and m <= 64, without a
+ * callback, and visits a larger one through constraint_cb.  mu / order / n_order: what the object holds on entry -- its m
+ * multipliers and the n_order rows whose multipliers are non-zero in the order they became non-zero (the warm start of the
+ * reference's bounded least squares) --, NULL / 0 for a fresh object; what it holds on return are the result vectors
+ * ADELIE_HIP_V_CONSTRAINT_LMU, ADELIE_HIP_I_CONSTRAINT_LORDER and ADELIE_HIP_I_CONSTRAINT_LNORDER.  These three fields are
+ * appended: the checker, which does not read them, is unchanged. */
 typedef struct adelie_hip_linear_constraint {
     int64_t        m, d;
     const double*  A;       /* (m, d) row-major */
@@ -405,6 +410,9 @@ typedef struct adelie_hip_linear_constraint {
     const double*  upper;   /* (m,) >= 0 */
     const double*  vars;    /* (m,) squared row norms of A */
     double         cfg[7];  /* max_iters, tol, nnls_max_iters, nnls_tol, pinball_max_iters, pinball_tol, slack */
+    const double*  mu;      /* (m,) or NULL */
+    const int32_t* order;   /* (n_order,) distinct rows, or NULL */
+    int64_t        n_order;
 } adelie_hip_linear_constraint;
 
 /* ABI 11.  Cox proportional-hazards family (reference GlmCox{32,64}, glm_cox.hpp / glm_cox.ipp).
@@ -534,7 +542,8 @@ typedef struct adelie_hip_grpnet_args {
     const void*    constraint_va;     /* (p,) value_t or NULL */
     const void*    constraint_vb;     /* (p,) value_t or NULL */
     const double*  constraint_cfg;    /* (G, 5) row-major or NULL */
-    /* ABI 5: constraint_native[g] = 6 (linear): constraint_lin[g] describes the object (NULL entries elsewhere) */
+    /* ABI 5: constraint_native[g] = 6 (linear): constraint_lin[g] describes the object (NULL entries elsewhere); with d <= 64 and
+     * m <= 64 it is solved on the device from that description (kernels_cons_linear.hip) */
     const adelie_hip_linear_constraint* const* constraint_lin; /* (G,) or NULL */
     /* ABI 7: kind-3 groups whose constraint_native is 4 (box) or 5 (one-sided) and that hold <= 128 coefficients are solved ON
      * THE DEVICE from constraint_va / _vb / _cfg (kernels_cons.hip: the reference's proximal-Newton dual solver in one
@@ -679,13 +688,18 @@ enum adelie_hip_vec {
     ADELIE_HIP_I_CONSTRAINT_DEV_GROUPS,
     /* adelie_hip_gaussian_pin_solve: active_begins / active_order of the reference's pin states */
     ADELIE_HIP_I_ACTIVE_BEGINS, ADELIE_HIP_I_ACTIVE_ORDER,
+    /* the linear objects among ADELIE_HIP_I_CONSTRAINT_DEV_GROUPS: (n_duals,) indexed like the columns of `duals`, the rows of
+     * each such group in the order their multipliers became non-zero (-1 beyond the count), and (G,) that count per group */
+    ADELIE_HIP_I_CONSTRAINT_LORDER, ADELIE_HIP_I_CONSTRAINT_LNORDER,
     /* betas values (double), CSR (L, p) like convert_sparse_to_dense's input, py_state.cpp:9-60 */
     ADELIE_HIP_V_BETAS_VALUES = 200,
     ADELIE_HIP_V_DUALS_VALUES,
     /* (G,) the multiplier each constraint object is left holding when the solve returns (0 for unconstrained groups) */
     ADELIE_HIP_V_CONSTRAINT_MU,
     /* ABI 7: (p,) per coefficient, the multipliers of the box / one-sided objects that were solved on the device (0 elsewhere) */
-    ADELIE_HIP_V_CONSTRAINT_VMU
+    ADELIE_HIP_V_CONSTRAINT_VMU,
+    /* (n_duals,) indexed like the columns of `duals`: the multipliers of the linear objects that were solved on the device */
+    ADELIE_HIP_V_CONSTRAINT_LMU
 };
 enum adelie_hip_scalar {
     ADELIE_HIP_S_LMDA_MAX = 0, ADELIE_HIP_S_LMDA, ADELIE_HIP_S_RSQ, ADELIE_HIP_S_RESID_SUM,
@@ -1229,7 +1243,11 @@ int adelie_hip_glm_piece_test(const adelie_hip_glm_piece* a, int64_t* info);
  * is_active / active_size / max_active_size: the active-set marking of a changed group; rsq, resid_sum, cm, n_updates: the pass
  * state on entry.  Out: dcol (int32) and dlt (both in/out: left as they were when the group did not change), st_f (4 doubles:
  * rsq, resid_sum, cm, milliseconds of the launch between two events), st_i (5 int64: n_updates, active_size, status -- CdStatus:
- * 0 OK, 2 max_active, 4 .. 7 the constraint solver's errors --, nz, is_active afterwards).
+ * 0 OK, 2 max_active, 4 .. 8 the constraint solver's errors --, nz, is_active afterwards).
+ * native 6 (linear, q <= 64): lower <= A x <= upper with m <= 64 rows; lin_A (m, q) row-major, lin_lower / lin_upper / lin_vars
+ * (m,), all double; mu then holds m values, va / vb are not read; lin_order (m,) int32 and lin_norder (1,) int32, both in/out: the
+ * rows whose multipliers are non-zero in the order they became non-zero; lin_cfg: the bounded least squares' max_iters and tol.
+ * These fields are appended and read for native 6 only.
  * The entry is additive and changes the layout of no existing structure: ADELIE_HIP_ABI_VERSION stays as it is. */
 typedef struct adelie_hip_cons_visit {
     int64_t dtype, q, native, gram, mark, first_of_pass, is_active, active_size, max_active_size, col0, n_updates;
@@ -1247,6 +1265,14 @@ typedef struct adelie_hip_cons_visit {
     void* dlt;
     double* st_f;
     int64_t* st_i;
+    int64_t m;
+    const double* lin_A;
+    const double* lin_lower;
+    const double* lin_upper;
+    const double* lin_vars;
+    int32_t* lin_order;
+    int32_t* lin_norder;
+    double lin_cfg[2];
 } adelie_hip_cons_visit;
 int adelie_hip_cons_visit_test(const adelie_hip_cons_visit* a);
 
