@@ -13,7 +13,7 @@ Two routes into the solver (``adelie_hip_grpnet_args::constraint_kind``):
   callbacks of ``adelie_hip_constraint_callbacks`` — the role the reference's ``PyConstraintBase`` trampoline plays.
 
 After a solve every object holds the multipliers of the last fit (``dual`` / ``duals_nnz``), as the reference's objects do.
-``linear`` (a general matrix ``A``) is such a host object beyond 64 coefficients or 64 rows; up to there it is solved on the device.
+``linear`` (a general matrix ``A``) is such a host object beyond 64 rows; up to there it is solved on the device.
 """
 from typing import Union
 
@@ -493,9 +493,10 @@ class _Linear(_ProxNewton, ConstraintBase):
     ``A' mu`` in place of ``mu`` (``:275-470``).  The Newton step minimises the pinball-penalised quadratic model with Hessian
     ``A hess A'`` (the reference's ``m < d`` branch, ``:408-418``; for ``m >= d`` it solves the same sub-problem through a
     low-rank active-set variant), the multipliers at ``x = 0`` come from a sign-bounded least-squares fit of ``A' mu`` to
-    ``Q v`` (``:283-349``) by the reference's warm-started coordinate descent (``_bvls``).  The solver runs a group of at most 64
-    coefficients with at most 64 rows on the device from ``_linear_descriptor`` (kernels_cons_linear.hip, the same three loops)
-    and leaves ``_mu`` / ``_order`` as the last fit had them; a larger one is visited here, through the callbacks."""
+    ``Q v`` (``:283-349``) by the reference's warm-started coordinate descent (``_bvls``).  The solver runs an object with at most 64
+    rows (a constrained group has at most 128 coefficients) on the device from ``_linear_descriptor`` (kernels_cons_linear.hip up
+    to 64 coefficients, kernels_cons_linear_wide.hip from 65; the same three loops) and leaves ``_mu`` / ``_order`` as the last fit
+    had them; one with more rows is visited here, through the callbacks."""
 
     kind = KIND_HOST
 

@@ -1,5 +1,6 @@
 // cons_common.hpp — what the one-wavefront constraint kernels share (kernels_cons.hip: box / one-sided objects;
-// kernels_cons_linear.hip: linear objects): the return codes of a visit and the unconstrained group update.
+// kernels_cons_linear.hip: linear objects): the return codes of a visit and the unconstrained group update.  The workgroup kernel
+// of kernels_cons_linear_wide.hip takes the return codes from here and restates the update on two components a lane.
 #pragma once
 #include "kernels.hpp"
 #include "wavered.hpp"

@@ -516,10 +516,15 @@ void launch_grp_cons_visit(const ConsVisitParams<T>& p, hipStream_t s);
 size_t cons_visit_wide_lds(int q);
 template <class T>
 void launch_grp_cons_visit_wide(const ConsVisitParams<T>& p, hipStream_t s);
-// a linear object (q <= 64 coefficients, m <= 64 rows): one wavefront, B = A V and the dual Hessian in LDS
+// a linear object (m <= 64 rows): B = A V and the dual Hessian in LDS; q <= 64 coefficients: one wavefront
+// (kernels_cons_linear.hip), 65 .. 128: one workgroup of 256 threads (kernels_cons_linear_wide.hip), both reached through
+// launch_grp_cons_visit_linear
 size_t cons_visit_linear_lds(int m, int q);
 template <class T>
 void launch_grp_cons_visit_linear(const ConsVisitParams<T>& p, hipStream_t s);
+size_t cons_visit_linear_wide_lds(int m, int q);
+template <class T>
+void launch_grp_cons_visit_linear_wide(const ConsVisitParams<T>& p, hipStream_t s);
 // what the solver keeps on the device for its linear objects: per group (G,) the offset of A, the offset of the group's rows in
 // the per-row arrays (dual_groups), m and the bounded least squares' (max_iters, tol); per row the bounds, variances, multipliers
 // and the order list; err: set to a CdStatus when a solve_zero fails
@@ -531,11 +536,16 @@ struct ConsLinearStore {
     const double* cfg;
     int32_t* err;
 };
-// abs_grad of the groups of `list` whose object is linear (the others are skipped): one wavefront each
+// abs_grad of the groups of `list` whose object is linear (the others are skipped): one wavefront each.  Every group of the list
+// has <= 64 coefficients; the linear objects on 65 .. 128 go to the second launcher with a list of their own, one workgroup each.
 template <class T>
 void launch_cons_linear_abs_grad(const int32_t* list, int count, const int32_t* native, const int64_t* groups, const int64_t* gsizes,
                                  const int32_t* slot, const T* grad, const T* beta, const T* penalty, T regul_scale,
                                  const ConsLinearStore<T>& ls, T* abs_grad, hipStream_t s);
+template <class T>
+void launch_cons_linear_wide_abs_grad(const int32_t* list, int count, const int32_t* native, const int64_t* groups, const int64_t* gsizes,
+                                      const int32_t* slot, const T* grad, const T* beta, const T* penalty, T regul_scale,
+                                      const ConsLinearStore<T>& ls, T* abs_grad, hipStream_t s);
 // abs_grad (and, outside the screen set, the solve_zero multipliers) of the `count` groups in `list` with device constraint objects
 template <class T>
 void launch_cons_abs_grad(const int32_t* list, int count, const int32_t* native, const int64_t* groups, const int64_t* gsizes,

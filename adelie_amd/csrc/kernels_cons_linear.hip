@@ -605,12 +605,13 @@ void raise_lds(K kernel) {
 
 } // namespace
 
-size_t cons_visit_linear_lds(int m, int q) { return linear_lds(m, q); }
+size_t cons_visit_linear_lds(int m, int q) { return q > LW ? cons_visit_linear_wide_lds(m, q) : linear_lds(m, q); }
 
 template <class T>
 void launch_grp_cons_visit_linear(const ConsVisitParams<T>& p, hipStream_t s) {
+    if (p.q > LW && p.q <= 128 && p.m >= 1 && p.m <= LW) return launch_grp_cons_visit_linear_wide<T>(p, s); // kernels_cons_linear_wide.hip
     if (p.q < 1 || p.q > LW || p.m < 1 || p.m > LW)
-        throw std::runtime_error("adelie_hip: device visit of a linear constraint beyond 64 coefficients or 64 rows.");
+        throw std::runtime_error("adelie_hip: device visit of a linear constraint beyond 128 coefficients or 64 rows.");
     if (!p.lA || !p.llo || !p.lup || !p.lvars || !p.lorder || !p.lnorder)
         throw std::runtime_error("adelie_hip: device visit of a linear constraint without its description.");
     static const bool raised = [] { raise_lds(grp_cons_linear_visit_kernel<T>); return true; }();

@@ -65,9 +65,11 @@
     DevBuf<int64_t> d_cons_nvis;
     int64_t n_host_cons_visits = 0, n_dev_cons_visits_final = 0;
     // ... and the built-in linear class (constraint_native 6: lower <= A x <= upper, described by constraint_lin[g]) on groups of
-    // <= 64 coefficients with <= 64 rows (kernels_cons_linear.hip): A, the bounds and the row variances are uploaded once per
-    // solve, the m multipliers of a group and the order in which they became non-zero live in d_lin_mu / d_lin_order at
-    // dual_groups[g] (d_lin_norder[g] entries of the order are in use)
+    // <= 128 coefficients with <= 64 rows (kernels_cons_linear.hip up to 64 coefficients, kernels_cons_linear_wide.hip from 65):
+    // A, the bounds and the row variances are uploaded once per solve, the m multipliers of a group and the order in which they
+    // became non-zero live in d_lin_mu / d_lin_order at dual_groups[g] (d_lin_norder[g] entries of the order are in use).
+    // d_lin_list: those groups, the n_lin_narrow ones of <= 64 coefficients first, then the n_lin_wide others (abs_grad runs a
+    // kernel for each kind)
     std::vector<int32_t> lin_m;                // (G,) rows of a linear object that came with its description, else 0
     std::vector<int64_t> lin_aoff;             // (G,) offset of the group's A in d_lin_A
     std::vector<double> lin_cfg;               // (G, 2) the bounded least squares' max_iters, tol
@@ -75,8 +77,9 @@
     std::vector<int32_t> lin_order, lin_norder; // (n_duals,), (G,)
     DevBuf<double> d_lin_A, d_lin_lo, d_lin_up, d_lin_vars, d_lin_cfg;
     DevBuf<int64_t> d_lin_aoff, d_lin_doff;
-    DevBuf<int32_t> d_lin_m, d_lin_order, d_lin_norder, d_lin_err;
+    DevBuf<int32_t> d_lin_m, d_lin_order, d_lin_norder, d_lin_err, d_lin_list;
     DevBuf<T> d_lin_mu;
+    int n_lin_narrow = 0, n_lin_wide = 0;
     int32_t lin_err = 0;
     bool any_lin_dev = false;
     bool lin_dev(idx g) const { return cons_native[g] == ADELIE_HIP_NATIVE_LINEAR; } // (of a group with on_device())
@@ -84,9 +87,16 @@
         return ConsLinearStore<T>{d_lin_aoff.p, d_lin_doff.p, d_lin_m.p, d_lin_A.p, d_lin_lo.p, d_lin_up.p, d_lin_vars.p,
                                   d_lin_mu.p, d_lin_order.p, d_lin_norder.p, d_lin_cfg.p, d_lin_err.p};
     }
+    // abs_grad of the linear objects on the device: A'mu for the screened groups (slot[g] >= 0), solve_zero for the others
+    void launch_linear_abs_grad(const int32_t* slot, const T* beta_dev, T regul_scale) {
+        launch_cons_linear_abs_grad<T>(d_lin_list.p, n_lin_narrow, d_cons_native.p, d_groups.p, d_gsizes.p, slot, d_grad.p, beta_dev,
+                                       d_penalty.p, regul_scale, lin_store(), d_absgrad.p, st);
+        launch_cons_linear_wide_abs_grad<T>(d_lin_list.p + n_lin_narrow, n_lin_wide, d_cons_native.p, d_groups.p, d_gsizes.p, slot, d_grad.p,
+                                            beta_dev, d_penalty.p, regul_scale, lin_store(), d_absgrad.p, st);
+    }
     bool on_device(idx g) const {
         if (!cons_dev || !host_cons(g)) return false;
-        if (cons_native[g] == ADELIE_HIP_NATIVE_LINEAR) return group_sizes[g] <= 64 && lin_m[g] >= 1 && lin_m[g] <= 64;
+        if (cons_native[g] == ADELIE_HIP_NATIVE_LINEAR) return group_sizes[g] <= 128 && lin_m[g] >= 1 && lin_m[g] <= 64;
         return (cons_native[g] == ADELIE_HIP_NATIVE_BOX || cons_native[g] == ADELIE_HIP_NATIVE_ONE_SIDED) && group_sizes[g] <= 128;
     }
     adelie_hip_glm_callbacks glm_cb{};       // glm_kind == CALLBACK: the user's GlmBase subclass, evaluated on the host

@@ -768,7 +768,7 @@
         vp.host_st = rep_st_dev; vp.host_seq = rep_seq_dev;
         vp.report_seq = (report && h_report) ? ++report_seq : 0;
         vp.n_visits = d_cons_nvis.p;
-        if (lin_dev(g)) { // a linear object: m multipliers at dual_groups[g] (kernels_cons_linear.hip)
+        if (lin_dev(g)) { // a linear object: m multipliers at dual_groups[g] (kernels_cons_linear.hip, kernels_cons_linear_wide.hip)
             const idx o = dual_groups[g];
             vp.m = lin_m[g];
             vp.lA = d_lin_A.p + lin_aoff[g];
@@ -818,6 +818,15 @@
         d_lin_A.reserve(A.size()); d_lin_lo.reserve(nd); d_lin_up.reserve(nd); d_lin_vars.reserve(nd); d_lin_cfg.reserve(size_t(G) * 2);
         d_lin_aoff.reserve(G); d_lin_doff.reserve(G); d_lin_m.reserve(G); d_lin_order.reserve(nd); d_lin_norder.reserve(G);
         d_lin_err.reserve(1); d_lin_mu.reserve(nd);
+        std::vector<int32_t> list; // the narrow groups first, then the wide ones
+        for (int32_t g : devcons_list)
+            if (lin_dev(g) && group_sizes[g] <= 64) list.push_back(g);
+        n_lin_narrow = int(list.size());
+        for (int32_t g : devcons_list)
+            if (lin_dev(g) && group_sizes[g] > 64) list.push_back(g);
+        n_lin_wide = int(list.size()) - n_lin_narrow;
+        d_lin_list.reserve(list.size());
+        d_lin_list.upload(list.data(), list.size(), st);
         d_lin_A.upload(A.data(), A.size(), st);
         d_lin_lo.upload(lo.data(), nd, st); d_lin_up.upload(up.data(), nd, st); d_lin_vars.upload(va.data(), nd, st);
         d_lin_cfg.upload(lin_cfg.data(), lin_cfg.size(), st);
@@ -843,8 +852,7 @@
         d_begin.upload(begin_of.data(), size_t(G), st);
         if (!screen_beta.empty()) d_sbeta.upload(screen_beta.data(), screen_beta.size(), st);
         d_absgrad.upload(abs_grad.data(), size_t(G), st);
-        launch_cons_linear_abs_grad<T>(d_devcons_list.p, int(devcons_list.size()), d_cons_native.p, d_groups.p, d_gsizes.p, d_begin.p,
-                                       d_grad.p, d_sbeta.p, d_penalty.p, (1 - alpha) * lm, lin_store(), d_absgrad.p, st);
+        launch_linear_abs_grad(d_begin.p, d_sbeta.p, (1 - alpha) * lm);
         d_absgrad.download(abs_grad.data(), size_t(G), st);
         d_lin_err.download(&lin_err, 1, st);
         sync();

@@ -318,9 +318,8 @@
             if (cons_dev) // box / one-sided objects on several coefficients: their gradient term / solve_zero (kernels_cons.hip)
                 launch_cons_abs_grad<T>(d_devcons_list.p, int(devcons_list.size()), d_cons_native.p, d_groups.p, d_gsizes.p, d_slot.p,
                                         d_grad.p, d_beta.p, d_penalty.p, (1 - alpha) * lm, d_cons_va.p, d_cons_vb.p, d_cons_mu.p, d_absgrad.p, st);
-            if (cons_dev && any_lin_dev) { // linear objects: A'mu / the bounded least squares of solve_zero (kernels_cons_linear.hip)
-                launch_cons_linear_abs_grad<T>(d_devcons_list.p, int(devcons_list.size()), d_cons_native.p, d_groups.p, d_gsizes.p, d_slot.p,
-                                               d_grad.p, d_beta.p, d_penalty.p, (1 - alpha) * lm, lin_store(), d_absgrad.p, st);
+            if (cons_dev && any_lin_dev) { // linear objects: A'mu / the bounded least squares of solve_zero (kernels_cons_linear*.hip)
+                launch_linear_abs_grad(d_slot.p, d_beta.p, (1 - alpha) * lm);
                 d_lin_err.download(&lin_err, 1, st);
             }
         } else {

@@ -985,7 +985,8 @@ int adelie_hip_glm_piece_test(const adelie_hip_glm_piece* a, int64_t* info) {
 
 // One visit of a group with a box / one-sided / linear constraint object, through launch_grp_cons_visit (include/adelie_hip.h has
 // the arrays): q <= 64 reaches the one-wavefront kernel of kernels_cons.hip, 65 .. 128 the workgroup kernel of kernels_cons_wide.hip,
-// a linear object (native 6, q <= 64, m <= 64) the one-wavefront kernel of kernels_cons_linear.hip.
+// a linear object (native 6, m <= 64) the one-wavefront kernel of kernels_cons_linear.hip for q <= 64 and the workgroup kernel of
+// kernels_cons_linear_wide.hip for 65 .. 128.
 int adelie_hip_cons_visit_test(const adelie_hip_cons_visit* a) {
     ABI_TRY
     if (!a) throw make_core_error("bad arguments.");
@@ -997,7 +998,7 @@ int adelie_hip_cons_visit_test(const adelie_hip_cons_visit* a) {
         throw make_core_error("native must be 4 (box), 5 (one-sided) or 6 (linear).");
     const int64_t nm = linear ? a->m : q; // multipliers
     if (linear) {
-        if (q > 64 || nm < 1 || nm > 64) throw make_core_error("linear: q <= 64 and 1 <= m <= 64 are required.");
+        if (nm < 1 || nm > 64) throw make_core_error("linear: 1 <= m <= 64 is required.");
         if (!a->lin_A || !a->lin_lower || !a->lin_upper || !a->lin_vars || !a->lin_order || !a->lin_norder)
             throw make_core_error("linear: lin_A, lin_lower, lin_upper, lin_vars, lin_order and lin_norder are required.");
         if (!(a->lin_cfg[0] >= 0 && a->lin_cfg[0] <= 1e8) || !(a->lin_cfg[1] >= 0)) throw make_core_error("lin_cfg: 0 <= max_iters <= 1e8, tol >= 0.");

@@ -397,8 +397,9 @@ enum adelie_hip_constraint_kind {
 /* ABI 5.  Description of a `linear` constraint object (reference ConstraintLinear, adelie/constraint.py:137-306,
  * constraint_linear.ipp:142-217):  lower <= A z <= upper  on the group's d coefficients, m rows, with the settings of the
  * reference's proximal-Newton solver.  The CPU checker (oracle/) runs such a group with its own restatement of that solver;
- * libadelie_hip.so solves it ON THE DEVICE (kernels_cons_linear.hip: one wavefront per visit) when d <= 64 and m <= 64, without a
- * callback, and visits a larger one through constraint_cb.  mu / order / n_order: what the object holds on entry -- its m
+ * libadelie_hip.so solves it ON THE DEVICE when d <= 128 and m <= 64 (kernels_cons_linear.hip: one wavefront per visit up to
+ * d = 64; kernels_cons_linear_wide.hip: one workgroup per visit from 65 to 128), without a callback, and visits one with more
+ * rows through constraint_cb.  mu / order / n_order: what the object holds on entry -- its m
  * multipliers and the n_order rows whose multipliers are non-zero in the order they became non-zero (the warm start of the
  * reference's bounded least squares) --, NULL / 0 for a fresh object; what it holds on return are the result vectors
  * ADELIE_HIP_V_CONSTRAINT_LMU, ADELIE_HIP_I_CONSTRAINT_LORDER and ADELIE_HIP_I_CONSTRAINT_LNORDER.  These three fields are
@@ -542,8 +543,8 @@ typedef struct adelie_hip_grpnet_args {
     const void*    constraint_va;     /* (p,) value_t or NULL */
     const void*    constraint_vb;     /* (p,) value_t or NULL */
     const double*  constraint_cfg;    /* (G, 5) row-major or NULL */
-    /* ABI 5: constraint_native[g] = 6 (linear): constraint_lin[g] describes the object (NULL entries elsewhere); with d <= 64 and
-     * m <= 64 it is solved on the device from that description (kernels_cons_linear.hip) */
+    /* ABI 5: constraint_native[g] = 6 (linear): constraint_lin[g] describes the object (NULL entries elsewhere); with d <= 128 and
+     * m <= 64 it is solved on the device from that description (kernels_cons_linear.hip, kernels_cons_linear_wide.hip) */
     const adelie_hip_linear_constraint* const* constraint_lin; /* (G,) or NULL */
     /* ABI 7: kind-3 groups whose constraint_native is 4 (box) or 5 (one-sided) and that hold <= 128 coefficients are solved ON
      * THE DEVICE from constraint_va / _vb / _cfg (kernels_cons.hip: the reference's proximal-Newton dual solver in one
@@ -1244,7 +1245,7 @@ int adelie_hip_glm_piece_test(const adelie_hip_glm_piece* a, int64_t* info);
  * state on entry.  Out: dcol (int32) and dlt (both in/out: left as they were when the group did not change), st_f (4 doubles:
  * rsq, resid_sum, cm, milliseconds of the launch between two events), st_i (5 int64: n_updates, active_size, status -- CdStatus:
  * 0 OK, 2 max_active, 4 .. 8 the constraint solver's errors --, nz, is_active afterwards).
- * native 6 (linear, q <= 64): lower <= A x <= upper with m <= 64 rows; lin_A (m, q) row-major, lin_lower / lin_upper / lin_vars
+ * native 6 (linear, q <= 128: one wavefront up to 64, one workgroup from 65): lower <= A x <= upper with m <= 64 rows; lin_A (m, q) row-major, lin_lower / lin_upper / lin_vars
  * (m,), all double; mu then holds m values, va / vb are not read; lin_order (m,) int32 and lin_norder (1,) int32, both in/out: the
  * rows whose multipliers are non-zero in the order they became non-zero; lin_cfg: the bounded least squares' max_iters and tol.
  * These fields are appended and read for native 6 only.

@@ -1,13 +1,16 @@
-"""`linear` constraint objects (lower <= A x <= upper, up to 64 rows on up to 64 coefficients): the one-wavefront kernel of
-kernels_cons_linear.hip against the route it replaces (a host visit: the numpy class through callbacks, ADELIE_HIP_CONS_HOST=1).
+"""`linear` constraint objects (lower <= A x <= upper, up to 64 rows on up to 128 coefficients): the one-wavefront kernel of
+kernels_cons_linear.hip and the workgroup kernel of kernels_cons_linear_wide.hip (65 to 128 coefficients) against the route they
+replace (a host visit: the numpy class through callbacks, ADELIE_HIP_CONS_HOST=1).
 
-    python scripts/bench_cons_linear.py [n reps]
+    python scripts/bench_cons_linear.py [n reps [wide]]
 
 1. One binding visit through adelie_hip_cons_visit_test (HIP events around the launch) at (m, d) = (4, 4), (16, 16), (64, 64) and
    (64, 8), float64, with the objects' default settings; beside it the wall time of the host object's solve() on the same inputs
    (the numpy driver alone, without the transfers and the synchronisation a host visit adds).
 2. A Gaussian path of 8 lambdas on n rows with 40 groups of 4 coefficients, every one with a linear object of 1 to 5 rows: device
    route and host route alternated in one process, `reps` runs each.
+With `wide`: the visits at (m, d) = (4, 65), (16, 96), (64, 128) and (64, 65), and a path on n rows with groups of 65 / 128 / 96 / 4 /
+1 / 1 coefficients whose three wide groups carry linear objects of 3 / 64 / 17 rows.
 """
 import ctypes as C
 import json
@@ -66,10 +69,10 @@ def one_visit(hip, m, d, reps):
             "multipliers_nnz": int(np.sum(mu != 0)), "max_abs_dx_device_vs_host": float(np.abs(beta @ Q - xh).max())}
 
 
-def path(n, reps):
-    G, gsz = 40, 4
-    p = G * gsz
-    groups = np.arange(0, p, gsz)
+def path(n, reps, wide=False):
+    sizes = np.array([65, 128, 96, 4, 1, 1] if wide else [4] * 40)
+    G, p = len(sizes), int(sizes.sum())
+    groups = np.concatenate([[0], np.cumsum(sizes)[:-1]])
     rng = np.random.RandomState(3)
     X = np.asfortranarray(rng.normal(0, 1, (n, p)))
     b = rng.normal(0, 1, p) * (rng.rand(p) < 0.5)
@@ -77,10 +80,11 @@ def path(n, reps):
     Xd = ad.matrix.dense(X)
     r = np.random.RandomState(5)
     spec = []
-    for _ in range(G):
-        m = r.randint(1, 6)
-        spec.append((r.randn(m, gsz), -r.uniform(0, 0.2, m) * (r.rand(m) < 0.7), r.uniform(0.02, 0.2, m)))
-    make = lambda: [constraint.linear(*s) for s in spec]
+    for g in range(G):
+        m = (3, 64, 17, 0, 0, 0)[g] if wide else r.randint(1, 6)
+        scale = np.sqrt(sizes[g]) if wide else 1.0
+        spec.append((r.randn(m, sizes[g]) / scale, -r.uniform(0, 0.2, m) * (r.rand(m) < 0.7), r.uniform(0.02, 0.2, m)) if m else None)
+    make = lambda: [None if s is None else constraint.linear(*s) for s in spec]
     kw = dict(groups=groups, alpha=0.7, lmda_path_size=8, min_ratio=0.05, early_exit=False, progress_bar=False)
     secs, last = {"device": [], "host": []}, {}
     for rep in range(reps + 1):  # (run 0 warms both routes up)
@@ -97,7 +101,8 @@ def path(n, reps):
             if rep:
                 secs[arm].append(el)
             last[arm] = st
-    out = {"workload": f"Gaussian group elastic net {n}x{p}, {G} groups of {gsz} with linear objects of 1 to 5 rows, alpha 0.7, 8 lambdas"}
+    what = "groups of 65 / 128 / 96 / 4 / 1 / 1, linear objects of 3 / 64 / 17 rows on the wide ones" if wide else f"{G} groups of 4 with linear objects of 1 to 5 rows"
+    out = {"workload": f"Gaussian group elastic net {n}x{p}, {what}, alpha 0.7, 8 lambdas"}
     for arm in ("device", "host"):
         c = last[arm].counters
         out[arm] = {"seconds": spread(secs[arm]), "n_dev_cons_visits": c["n_dev_cons_visits"], "n_host_cons_visits": c["n_host_cons_visits"]}
@@ -108,7 +113,8 @@ def path(n, reps):
 if __name__ == "__main__":
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 20000
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+    wide = len(sys.argv) > 3 and sys.argv[3] == "wide"
     hip = _abi.hip_backend()
-    for m, d in ((4, 4), (16, 16), (64, 64), (64, 8)):
+    for m, d in ((4, 65), (16, 96), (64, 128), (64, 65)) if wide else ((4, 4), (16, 16), (64, 64), (64, 8)):
         print(json.dumps(one_visit(hip, m, d, reps)), flush=True)
-    print(json.dumps(path(n, reps)), flush=True)
+    print(json.dumps(path(n, reps, wide)), flush=True)
