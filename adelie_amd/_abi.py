@@ -13,6 +13,7 @@ import numpy as np
 
 F32, F64 = 0, 1
 COL_MAJOR, ROW_MAJOR = 0, 1
+FMT_F16, FMT_BF16 = 0, 1  # the 16-bit formats of design_create_dense16 / design_adopt_dense16_dev
 SCREEN_STRONG, SCREEN_PIVOT = 0, 1
 GLM_GAUSSIAN, GLM_BINOMIAL_LOGIT, GLM_GAUSSIAN_IRLS, GLM_MULTINOMIAL, GLM_POISSON, GLM_BINOMIAL_PROBIT = 0, 1, 2, 3, 4, 5
 GLM_CALLBACK = 6  # a Python subclass of glm.GlmBase64/32, evaluated by host callbacks
@@ -347,7 +348,7 @@ class ConsVisit(C.Structure):
 # every symbol include/adelie_hip.h declares (checked by tests/test_abi.py)
 HIP_SYMBOLS = [
     "abi_version", "last_error", "device_count", "set_config",
-    "design_create_dense", "design_create_sparse", "design_create_csc", "design_create_standardized", "design_adopt_dense_dev", "design_create_snp_unphased",
+    "design_create_dense", "design_create_sparse", "design_create_csc", "design_create_standardized", "design_adopt_dense_dev", "design_create_dense16", "design_adopt_dense16_dev", "design_create_snp_unphased",
     "design_create_snp_calldata", "design_create_snp_bed", "design_alias", "design_drop_shadow", "design_shadow_stats", "design_shadow_info", "design_create_slice", "design_create_multi", "design_create_derived", "design_create_concat", "design_create_pieces", "design_impute", "design_destroy", "design_owned_bytes",
     "design_create_one_hot", "design_create_interaction", "design_factor_groups",
     "design_create_convex_relu", "design_create_convex_relu_csc",
@@ -425,6 +426,8 @@ class Backend:
         sig("set_config", ci, [C.c_char_p, dbl])
         sig("design_create_dense", ci, [vp, i64, i64, ci, ci, ci, p(vp)])
         sig("design_adopt_dense_dev", ci, [vp, i64, i64, ci, ci, ci, p(vp)])
+        sig("design_create_dense16", ci, [vp, i64, i64, ci, ci, ci, p(vp)])
+        sig("design_adopt_dense16_dev", ci, [vp, i64, i64, ci, ci, ci, p(vp)])
         sig("design_create_sparse", ci, [vp, vp, vp, i64, i64, ci, ci, p(vp)])
         sig("design_create_csc", ci, [vp, vp, vp, vp, vp, vp, i64, i64, ci, ci, p(vp)])
         sig("design_create_standardized", ci, [vp, vp, vp, p(vp)])

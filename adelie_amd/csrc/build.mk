@@ -2,7 +2,7 @@
 # One object per translation unit.  The compiler writes each object's depfile (-MMD: the unit's source and every project header it
 # read, as paths relative to this directory, so they stay valid when the tree is copied), and those depfiles decide what is stale:
 # no list of headers is kept by hand.
-UNITS := kernels_cons kernels_cons_wide kernels_cons_linear kernels_cons_linear_wide kernels_append kernels_eig kernels_strip kernels_cov kernels_cov_sparse kernels_sparse kernels_sweep \
+UNITS := kernels_cons kernels_cons_wide kernels_cons_linear kernels_cons_linear_wide kernels_append kernels_eig kernels_strip kernels_cov kernels_cov_sparse kernels_sparse kernels_sweep kernels_dense16 \
          kernels_filter kernels_convert kernels_gram kernels_cd kernels_cd_lasso kernels_cd_pin kernels_cd_block kernels_cd_block_group \
          kernels_cd_panel kernels_multi kernels_multi_sparse kernels_glm kernels_cox kernels_factor kernels_relu kernels_relu_sparse kernels_phased \
          kernels_css kernels_bvls kernels_pinball kernels_pinball_sparse kernels_qp_full kernels_bcd design solver test_entries

@@ -622,6 +622,14 @@ struct PiecesArrs {
         pc_k = o.pc_k;
     }
 };
+// dense design kept 16-bit (adelie_hip_design_create_dense16 / _adopt_dense16_dev; kernels_dense16.hip): the IEEE half or bfloat16
+// values as the caller laid them out, owned (an upload) or borrowed (an adopted tensor); the design's value type is float
+struct Dense16Arrs {
+    DevArr<unsigned short> X16;
+    int64_t ld16 = 0;
+    int fmt16 = 0, rm16 = 0; // kFmtF16 / kFmtBF16; 1: row-major
+    void borrow_from(const Dense16Arrs& o) { X16.borrow(o.X16), ld16 = o.ld16, fmt16 = o.fmt16, rm16 = o.rm16; }
+};
 // float32 shadow of a dense f64 design for the filtered invariance sweep (kernels_filter.hip: ShadowView), made on the first
 // eligible solve.  Like the batcher it lives with the design the aliases were made from: nobody borrows it, the aliases read
 // their owner's.  sh_kind (shadow_kind_host.hpp): float32 values, or int16 with the per-column scales in sh_scale.
@@ -639,24 +647,27 @@ struct ShadowArrs {
 
 // ---- the opaque handles of include/adelie_hip.h ------------------------------------------------------------
 struct adelie_hip_design : ahip::DenseArrs, ahip::SnpArrs, ahip::CscArrs, ahip::StdArrs, ahip::FactorArrs, ahip::ReluArrs,
-                           ahip::ReluCscArrs, ahip::PiecesArrs, ahip::ShadowArrs {
+                           ahip::ReluCscArrs, ahip::PiecesArrs, ahip::Dense16Arrs, ahip::ShadowArrs {
     // what adelie_hip_design_alias shares with `o`; o must outlive this handle
     void borrow_arrays(const adelie_hip_design& o) {
         DenseArrs::borrow_from(o), SnpArrs::borrow_from(o), CscArrs::borrow_from(o), StdArrs::borrow_from(o);
         FactorArrs::borrow_from(o), ReluArrs::borrow_from(o), ReluCscArrs::borrow_from(o), PiecesArrs::borrow_from(o);
+        Dense16Arrs::borrow_from(o);
     }
     int dtype = ADELIE_HIP_F64;
     int device = 0;
     // storage kinds: dense, snp (2-bit), multi-response view of a dense, 2-bit or kept-sparse design (adelie_hip_design_create_multi),
     // sparse kept sparse (adelie_hip_design_create_csc: CSC + CSR copies of the entries, kernels_sparse.hip), column blocks of
-    // dense and 2-bit designs that stay as they are (adelie_hip_design_create_pieces: PiecesArrs; X, bits and the rest are null)
-    enum : int { kDense = 0, kSnp = 1, kMulti = 2, kCsc = 3, kPieces = 4 };
+    // dense and 2-bit designs that stay as they are (adelie_hip_design_create_pieces: PiecesArrs; X, bits and the rest are null),
+    // dense kept 16-bit (adelie_hip_design_create_dense16: Dense16Arrs; dtype is F32, X and the rest are null)
+    enum : int { kDense = 0, kSnp = 1, kMulti = 2, kCsc = 3, kPieces = 4, kDense16 = 5 };
     int kind = kDense;
     bool is_dense() const { return kind == kDense; }
     bool is_snp() const { return kind == kSnp; }
     bool is_multi() const { return kind == kMulti; }
     bool is_csc() const { return kind == kCsc; }
     bool is_pieces() const { return kind == kPieces; }
+    bool is_dense16() const { return kind == kDense16; }
     // standardized view over a dense or 2-bit design (adelie_hip_design_create_standardized): the base kernels run on the raw
     // matrix, centring and scaling are applied around them; a view over compressed columns applies them inside its kernels
     bool is_std_view() const { return std_center != nullptr && kind != kCsc; }
@@ -689,6 +700,7 @@ struct adelie_hip_design : ahip::DenseArrs, ahip::SnpArrs, ahip::CscArrs, ahip::
 
     template <class T> ahip::DenseView<T> dense() const { return ahip::DenseView<T>{static_cast<const T*>(X), n, p, ld}; }
     ahip::SnpView snp() const { return ahip::SnpView{bits, n, p, ldb}; }
+    ahip::Dense16View dense16() const { return ahip::Dense16View{X16, n, p, ld16, fmt16, rm16}; }
     template <class T> ahip::PiecesView<T> pieces() const {
         ahip::PiecesView<T> v{};
         for (int m = 0; m < ahip::kMaxPieces; ++m)

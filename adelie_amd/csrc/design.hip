@@ -183,7 +183,7 @@ void op_mul_batch(adelie_hip_design* d, const T* V, int64_t L, T* out) {
     constexpr int64_t KB = 8;
     // sparse: one pass over the stored entries per vector (a convex-relu design: over those of Z, by the hook); a design made of
     // pieces: one sweep per vector as well, every piece at its own rate (the K-wide kernels below take one dense or 2-bit view)
-    if (d->is_csc() || d->is_pieces()) {
+    if (d->is_csc() || d->is_pieces() || d->is_dense16()) { // (a design kept 16-bit: one sweep of kernels_dense16.hip per vector)
         T* dv1 = scratch<T>(d->s_n1, size_t(n));
         T* dout1 = scratch<T>(d->s_p1, size_t(p));
         const bool structured = raw_sweep_structured(*d, 0, p, nullptr, false, SweepHooks::from_env());
@@ -1139,6 +1139,40 @@ int adelie_hip_design_adopt_dense_dev(const void* dev_ptr, int64_t n, int64_t p,
     DTYPE_DISPATCH(g, create_dense_t<T>(g.get(), dev_ptr, true, order))
     *out = g.release();
     ABI_CATCH
+}
+
+// A dense design kept 16-bit (kernels_dense16.hip): the n * p values stay as they lie, column- or row-major, uploaded once or
+// adopted in place; dtype F32.  Nothing is padded and nothing is converted, so nothing but the 2 n p bytes is resident.
+static int create_dense16(const void* src, bool on_device, int64_t n, int64_t p, int format, int order, int device,
+                          adelie_hip_design** out) {
+    ABI_TRY
+    if (!src || !out) throw make_core_error("null argument.");
+    if (format != ADELIE_HIP_FMT_F16 && format != ADELIE_HIP_FMT_BF16) throw make_core_error("format must be FMT_F16 or FMT_BF16.");
+    if (order != ADELIE_HIP_COL_MAJOR && order != ADELIE_HIP_ROW_MAJOR) throw make_core_error("order must be COL_MAJOR or ROW_MAJOR.");
+    if (reinterpret_cast<uintptr_t>(src) % 2 != 0) throw make_core_error("a 16-bit matrix must be 2-byte aligned.");
+    DesignGuard g(new_design(n, p, ADELIE_HIP_F32, device));
+    adelie_hip_design* d = g.get();
+    d->kind = adelie_hip_design::kDense16;
+    d->fmt16 = format == ADELIE_HIP_FMT_BF16 ? kFmtBF16 : kFmtF16;
+    d->rm16 = order == ADELIE_HIP_ROW_MAJOR ? 1 : 0;
+    d->ld16 = d->rm16 ? p : n;
+    if (on_device) {
+        d->X16.borrow(static_cast<unsigned short*>(const_cast<void*>(src))); // adopted in place: the caller frees it
+    } else {
+        d->X16.alloc(size_t(n) * size_t(p));
+        AHIP_CHECK(hipMemcpyAsync(d->X16, src, size_t(n) * size_t(p) * 2, hipMemcpyHostToDevice, d->stream));
+        AHIP_CHECK(hipStreamSynchronize(d->stream));
+    }
+    *out = g.release();
+    ABI_CATCH
+}
+int adelie_hip_design_create_dense16(const void* host, int64_t n, int64_t p, int format, int order, int device,
+                                     adelie_hip_design** out) {
+    return create_dense16(host, false, n, p, format, order, device, out);
+}
+int adelie_hip_design_adopt_dense16_dev(const void* dev_ptr, int64_t n, int64_t p, int format, int order, int device,
+                                        adelie_hip_design** out) {
+    return create_dense16(dev_ptr, true, n, p, format, order, device, out);
 }
 
 #include "design_snp.hpp"

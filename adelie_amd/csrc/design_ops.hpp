@@ -5,10 +5,12 @@
 // calls (solver_screen.hpp: sweep / gram / axpy_cols); one over compressed columns is handled inside the csc kernels, whose
 // CscView carries the centers and scales.  The multi-response view has K-wide kernels of its own (the solver calls them) and
 // is refused here.  A design made of pieces (kPieces) is the fourth branch of each: a sweep over a column range goes piece by
-// piece through the dense / 2-bit launches, everything else through the same kernels over PiecesAcc.  Every work buffer is the caller's: the solver and the matrix operations keep different scratch, and a
+// piece through the dense / 2-bit launches, everything else through the same kernels over PiecesAcc.  A dense design kept 16-bit
+// (kDense16) is the fifth, served by the kernels of kernels_dense16.hip, in float32 only.  Every work buffer is the caller's: the solver and the matrix operations keep different scratch, and a
 // caller may hold live data in one buffer while an operation works in another, so nothing here reserves memory.
 #pragma once
 #include "common.hpp"
+#include <type_traits>
 
 namespace ahip {
 
@@ -18,11 +20,18 @@ inline core_error multi_view_error() {
 // A design made of pieces has neither a dense nor a 2-bit view of its own.  Every two-way branch `dense ? ... : ...snp...` of
 // the solver and of the design entry points calls this in front of it, so that no launch is ever handed a null view; the
 // solver keeps such a design off the panel engines (solver_path.hpp), which is what makes those branches unreachable.
+// A dense design kept 16-bit (kDense16, kernels_dense16.hip) is in the same position and is refused by the same call: it is the
+// fifth branch of each dispatch below and has nothing else.
 inline void no_pieces(const adelie_hip_design& d, const char* where) {
     if (d.is_pieces())
         throw make_core_error(std::string(where) + " is not offered on a design made of pieces (concatenate(..., resident=\"pieces\")); "
                               "resident=\"auto\" gives one design, on which everything works.");
+    if (d.is_dense16())
+        throw make_core_error(std::string(where) + " is not offered on a dense design kept 16-bit (float16 / bfloat16 input of "
+                              "matrix.dense); build the design from mat.float() / mat.astype(np.float32), on which everything works.");
 }
+// the 16-bit kind computes in float32 only (its handle's dtype is F32 by construction)
+inline core_error dense16_f64_error() { return make_core_error("internal: a dense design kept 16-bit was given float64 operands."); }
 template <class T>
 const T* snp_impute(const adelie_hip_design& d) { return static_cast<const T*>(d.impute); }
 
@@ -43,6 +52,7 @@ inline int64_t raw_sweep_work_elems(const adelie_hip_design& d, int64_t ncols, b
     if (d.is_pieces())
         return d.dtype == ADELIE_HIP_F64 ? sweep_work_elems_pieces<double>(d.pieces<double>(), c0, ncols)
                                          : sweep_work_elems_pieces<float>(d.pieces<float>(), c0, ncols);
+    if (d.is_dense16()) return sweep_work_elems_dense16(d.dense16(), ncols);
     if (structured && d.relu_csc()) return relu_sparse_sweep_work_elems(d.n, d.r_d, d.r_m);
     if (structured && d.relu()) return relu_sweep_work_elems(d.n, d.r_d, d.r_m);
     if (structured) return factor_sweep_work_elems(d.n, d.p, d.f_nchunk);
@@ -58,7 +68,10 @@ void raw_sweep(const adelie_hip_design& d, const T* v, T* out, int64_t c0, int64
     else if (d.is_snp()) launch_sweep_snp<T>(d.snp(), snp_impute<T>(d), v, out, c0, ncols, cols, sub_scale, sub_vec, square, work, s);
     else if (d.is_csc()) launch_sweep_csc<T>(d.csc<T>(), v, out, c0, ncols, cols, sub_scale, sub_vec, square, work, s);
     else if (d.is_pieces()) launch_sweep_pieces<T>(d.pieces<T>(), v, out, c0, ncols, cols, sub_scale, sub_vec, square, work, s);
-    else throw multi_view_error();
+    else if (d.is_dense16()) {
+        if constexpr (std::is_same<T, float>::value) launch_sweep_dense16(d.dense16(), v, out, c0, ncols, cols, sub_scale, sub_vec, square, work, s);
+        else throw dense16_f64_error();
+    } else throw multi_view_error();
 }
 
 // ---- Gram: C[m_pos0 + a, n_pos0 + b] = x_mcols[a]^T W x_ncols[b] (kernels.hpp: launch_gram) -----------------------------------
@@ -72,7 +85,10 @@ void raw_gram(const adelie_hip_design& d, const T* w, const int32_t* mcols, int3
     else if (d.is_snp()) launch_gram_snp<T>(d.snp(), snp_impute<T>(d), w, mcols, M, m_pos0, ncols, N, n_pos0, xm, center, C, ldc, work, s);
     else if (d.is_csc()) launch_gram_csc<T>(d.csc<T>(), w, mcols, M, m_pos0, ncols, N, n_pos0, xm, center, C, ldc, work, s);
     else if (d.is_pieces()) launch_gram_pieces<T>(d.pieces<T>(), w, mcols, M, m_pos0, ncols, N, n_pos0, xm, center, C, ldc, work, s);
-    else throw multi_view_error();
+    else if (d.is_dense16()) {
+        if constexpr (std::is_same<T, float>::value) launch_gram_dense16(d.dense16(), w, mcols, M, m_pos0, ncols, N, n_pos0, xm, center, C, ldc, work, s);
+        else throw dense16_f64_error();
+    } else throw multi_view_error();
 }
 
 // ---- axpy: out += sign * sum_k coef[k] x_cols[k] (kernels.hpp: launch_axpy_cols) ----------------------------------------------
@@ -85,7 +101,10 @@ void raw_axpy_cols(const adelie_hip_design& d, const int32_t* cols, const T* coe
     else if (d.is_snp()) launch_axpy_cols_snp<T>(d.snp(), snp_impute<T>(d), cols, coef, count_dev, count, sign, out, s);
     else if (d.is_csc()) launch_axpy_cols_csc<T>(d.csc<T>(), cols, coef, count_dev, count, sign, out, delta_zeroed, s);
     else if (d.is_pieces()) launch_axpy_cols_pieces<T>(d.pieces<T>(), cols, coef, count_dev, count, sign, out, s);
-    else throw multi_view_error();
+    else if (d.is_dense16()) {
+        if constexpr (std::is_same<T, float>::value) launch_axpy_cols_dense16(d.dense16(), cols, coef, count_dev, count, sign, out, s);
+        else throw dense16_f64_error();
+    } else throw multi_view_error();
 }
 
 // ---- sp_tmul: out (L, n) row-major = V X^T for a CSR V of L rows (kernels.hpp: launch_sp_tmul) --------------------------------
@@ -97,7 +116,10 @@ void raw_sp_tmul(const adelie_hip_design& d, int64_t L, const int64_t* indptr, c
     else if (d.is_snp()) launch_sp_tmul_snp<T>(d.snp(), snp_impute<T>(d), L, indptr, indices, values, out, s);
     else if (d.is_csc()) launch_sp_tmul_csc<T>(d.csc<T>(), L, indptr, indices, values, out, work, s);
     else if (d.is_pieces()) launch_sp_tmul_pieces<T>(d.pieces<T>(), L, indptr, indices, values, out, s);
-    else throw multi_view_error();
+    else if (d.is_dense16()) {
+        if constexpr (std::is_same<T, float>::value) launch_sp_tmul_dense16(d.dense16(), L, indptr, indices, values, out, s);
+        else throw dense16_f64_error();
+    } else throw multi_view_error();
 }
 
 // ---- covariance method: the two places the path solver touches A, over its storage (kernels_cov.hip, kernels_cov_sparse.hip) ----

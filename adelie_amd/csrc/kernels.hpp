@@ -110,6 +110,28 @@ template <class T>
 void launch_gram_pieces(const PiecesView<T>& X, const T* w, const int32_t* mcols, int32_t M, int32_t m_pos0, const int32_t* ncols,
                         int32_t N, int32_t n_pos0, const T* xm_by_col, bool center, T* C, int64_t ldc, T* work, hipStream_t s);
 
+// ---- dense design kept 16-bit (kernels_dense16.hip) ------------------------------------------------------------------------
+// IEEE half or bfloat16 values as the caller laid them out: element (i, j) at X[i + j * ld] (column-major) or X[i * ld + j]
+// (row-major); no padding, any 2-byte-aligned base.  The design's value type is float: every value is converted in registers.
+enum : int { kFmtF16 = 0, kFmtBF16 = 1 }; // (ADELIE_HIP_FMT_F16 / _BF16)
+struct Dense16View {
+    const unsigned short* X;
+    int64_t n, p, ld;
+    int fmt, row_major;
+};
+// The four operations with the interfaces of launch_sweep / launch_gram_pieces / launch_axpy_cols / launch_sp_tmul; the sweep's
+// `work` holds sweep_work_elems_dense16(X, ncols) elements, the Gram's gram_work_elems(n, M, N).
+int64_t sweep_work_elems_dense16(const Dense16View& X, int64_t ncols);
+void launch_sweep_dense16(const Dense16View& X, const float* v, float* out, int64_t c0, int64_t ncols, const int32_t* cols,
+                          const float* sub_scale, const float* sub_vec, bool square, float* work, hipStream_t s);
+void launch_gram_dense16(const Dense16View& X, const float* w, const int32_t* mcols, int32_t M, int32_t m_pos0, const int32_t* ncols,
+                         int32_t N, int32_t n_pos0, const float* xm_by_col, bool center, float* C, int64_t ldc, float* work,
+                         hipStream_t s);
+void launch_axpy_cols_dense16(const Dense16View& X, const int32_t* cols, const float* coef, const int32_t* count_dev, int32_t count,
+                              float sign, float* out, hipStream_t s);
+void launch_sp_tmul_dense16(const Dense16View& X, int64_t L, const int64_t* indptr, const int64_t* indices, const float* values,
+                            float* out, hipStream_t s);
+
 // ---- filtered invariance sweep (kernels_filter.hip): a float32 shadow of a dense f64 design ----------------------------------
 // Xs: the columns rounded to float32 (column-major, ld a multiple of 4); err[j] = ||x_j - xs_j||_2, nrm[j] = ||xs_j||_2 (both
 // rounded up).  |x_j.v - xs_j.v| as the two sweeps compute them differ by at most (err[j] + fp_term() * nrm[j]) * ||v||_2.

@@ -783,7 +783,8 @@
     // design made of pieces (adelie_hip_design_create_pieces): dense and 2-bit column blocks that stay as they are.  Gram engines
     // only, through raw_sweep / raw_gram / raw_axpy_cols (design_ops.hpp); it has no dense and no 2-bit view of its own, so
     // every `dense() ? ... : ...snp...` branch of the panel engines and of the block builds has no_pieces() in front of it
-    bool pieces() const { return D->is_pieces(); }
+    // (a dense design kept 16-bit, kernels_dense16.hip, is in the same position: the raw operations and nothing else)
+    bool pieces() const { return D->is_pieces() || D->is_dense16(); }
     DevBuf<T> d_std_tmp, d_std_coef;
     // multi-response view (adelie_hip_design_create_multi): residual / weights live response-major on the device
     bool multi() const { return D->is_multi(); }

@@ -523,6 +523,9 @@
             bool any = false;
             for (idx g = 0; g < G; ++g) any = any || a->constraint_kind[g] != 0;
             if (any) {
+                if (D->is_dense16())
+                    throw make_core_error("constraints are not implemented on a dense design kept 16-bit (their solves live in the panel "
+                                          "engines); build the design from mat.float() / mat.astype(np.float32).");
                 if (pieces())
                     throw make_core_error("constraints are not implemented on a design made of pieces (their solves live in the panel engines); "
                                           "use concatenate(..., resident=\"auto\").");

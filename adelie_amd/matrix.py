@@ -126,6 +126,16 @@ def _no_pieces(mat, what, instead=""):
     if getattr(mat, "_kind", None) == "pieces":
         raise RuntimeError(f"adelie_amd: {what} is not offered on a design made of pieces (concatenate(..., resident=\"pieces\"))."
                            f"{instead}  resident=\"auto\" copies the pieces into one design, on which everything works.")
+    if getattr(mat, "_kind", None) == "dense16":  # (serves the same operations as a design made of pieces, and no others)
+        raise RuntimeError(f"adelie_amd: {what} is not offered on a dense design kept 16-bit (float16 / bfloat16 input of "
+                           "matrix.dense).  Build the design from mat.float() / mat.astype(np.float32), on which everything works.")
+
+
+def _format16(mat, is_torch):
+    """The 16-bit format code of ``matrix.dense``'s input (``_abi.FMT_F16`` / ``FMT_BF16``), or ``None`` for any other input."""
+    if is_torch:
+        return {"torch.float16": _abi.FMT_F16, "torch.bfloat16": _abi.FMT_BF16}.get(str(mat.dtype))
+    return _abi.FMT_F16 if isinstance(mat, np.ndarray) and mat.dtype == np.float16 else None
 
 
 class PyMatrixNaiveTranspose:
@@ -980,6 +990,15 @@ def dense(mat, *, method: str = "naive", copy: bool = False, n_threads: int = 1,
         adopted in place (no copy); it must be F- or C-contiguous and is kept alive by the handle.  An adopted tensor must
         not be modified while the handle lives: a float64 design keeps a float32 or 16-bit copy of itself (``shadow_info()``)
         for the invariance sweeps of Gaussian paths (``drop_shadow()`` after a modification has the copy made again).
+
+        A numpy ``float16`` array or a device ``torch.float16`` / ``torch.bfloat16`` tensor (F- or C-contiguous, adopted in
+        place in either order) gives a design kept 16-bit in HBM: ``2 n p`` bytes resident, no float32 or float64 copy then or
+        later, ``dtype == np.float32`` (every stored value is exactly a float32 value; all arithmetic is float32) and
+        ``_kind == "dense16"``.  It serves every matrix operation, ``grpnet`` with ``glm.gaussian(dtype=np.float32)`` and the
+        single-response families on the full-Gram engines (``counters["engine_panel"] == 0``), ``cv_grpnet`` and
+        ``diagnostic``; multi-response views, lazy ``standardize``, non-identity ``subset``, ``concatenate``, ``lazy_cov``,
+        ``bvls``, constraints and pin states are refused with an error that says the way out: ``mat.float()`` /
+        ``mat.astype(np.float32)``.  ``method="cov"`` and ``method="constraint"`` do not take 16-bit input.
     method : str
         ``"naive"`` (a design), ``"cov"`` (a covariance matrix for ``gaussian_cov`` / ``css_cov``) or ``"constraint"`` (an
         ``(m, d)`` constraint matrix for ``pinball``, kept row-major in HBM).
@@ -988,6 +1007,11 @@ def dense(mat, *, method: str = "naive", copy: bool = False, n_threads: int = 1,
     device : int
         HIP device ordinal for host inputs.
     """
+    is_torch = not isinstance(mat, np.ndarray) and type(mat).__module__.startswith("torch")
+    fmt16 = _format16(mat, is_torch)
+    if fmt16 is not None and method in ("cov", "constraint"):
+        raise RuntimeError(f"adelie_amd: dense(method=\"{method}\") does not take float16 / bfloat16 input; pass mat.float() / "
+                           "mat.astype(np.float32).")
     if method == "cov":
         return _cov_dense(_abi.hip_backend(), "design_create_cov_dense", mat, n_threads, device)
     if method == "constraint":
@@ -999,11 +1023,14 @@ def dense(mat, *, method: str = "naive", copy: bool = False, n_threads: int = 1,
     backend = _abi.hip_backend()
     handle = _abi.C.c_void_p()
 
-    if not isinstance(mat, np.ndarray) and type(mat).__module__.startswith("torch"):
+    if is_torch:
         t = mat
         if t.dim() != 2 or not t.is_cuda:
             raise RuntimeError("torch input must be a 2-D tensor in device memory.")
-        dtype = {"torch.float64": np.float64, "torch.float32": np.float32}[str(t.dtype)]
+        dtype = {"torch.float64": np.float64, "torch.float32": np.float32}.get(str(t.dtype))
+        if dtype is None and fmt16 is None:
+            raise RuntimeError(f"adelie_amd: dense() does not take a {t.dtype} tensor; the accepted dtypes are torch.float64, "
+                               "torch.float32, torch.float16 and torch.bfloat16.")
         n, p = t.shape
         if t.stride() == (1, n) or (p == 1 and t.stride(0) == 1):
             order = _abi.COL_MAJOR
@@ -1012,6 +1039,9 @@ def dense(mat, *, method: str = "naive", copy: bool = False, n_threads: int = 1,
             warnings.warn("Detected matrix to be C-contiguous. Performance may improve with F-contiguous matrix.")
         else:
             raise RuntimeError("torch input must be F- or C-contiguous.")
+        if fmt16 is not None:  # kept 16-bit, adopted in place in either order
+            backend.check(backend.fn("design_adopt_dense16_dev")(t.data_ptr(), n, p, fmt16, order, t.device.index or 0, handle))
+            return _wrap(backend, handle, np.float32, n_threads, keep=t, kind="dense16")
         backend.check(backend.fn("design_adopt_dense_dev")(
             t.data_ptr(), n, p, _abi.dtype_code(dtype), order, t.device.index or 0, handle))
         return _wrap(backend, handle, dtype, n_threads, keep=t, kind="dense")
@@ -1020,13 +1050,16 @@ def dense(mat, *, method: str = "naive", copy: bool = False, n_threads: int = 1,
     if mat.ndim != 2:
         raise RuntimeError("mat must be 2-dimensional.")
     dtype = mat.dtype
-    code = _abi.dtype_code(dtype)
+    code = fmt16 if fmt16 is not None else _abi.dtype_code(dtype)
     if mat.flags.f_contiguous:
         order = _abi.COL_MAJOR
     else:
         order = _abi.ROW_MAJOR
         mat = np.ascontiguousarray(mat)
         warnings.warn("Detected matrix to be C-contiguous. Performance may improve with F-contiguous matrix.")
+    if fmt16 is not None:  # uploaded once as 2 bytes a value, in the order it has
+        backend.check(backend.fn("design_create_dense16")(mat.ctypes.data, mat.shape[0], mat.shape[1], code, order, device, handle))
+        return _wrap(backend, handle, np.float32, n_threads, kind="dense16")
     backend.check(backend.fn("design_create_dense")(
         mat.ctypes.data, mat.shape[0], mat.shape[1], code, order, device, handle))
     return _wrap(backend, handle, dtype.type, n_threads, kind="dense")
@@ -1812,7 +1845,7 @@ def subset(mat, indices, *, axis: int = 0, n_threads: int = 1):
         indices = np.flatnonzero(indices)
     if axis not in (0, 1):
         raise RuntimeError("axis must be 0 or 1.")
-    if getattr(mat, "_kind", None) == "pieces":  # (the identity is the design itself; anything else would need a copy)
+    if getattr(mat, "_kind", None) in ("pieces", "dense16"):  # (the identity is the design itself; anything else would need a copy)
         size = mat.rows() if axis == 0 else mat.cols()
         if indices.ndim == 1 and indices.size == size and np.array_equal(indices, np.arange(size)):
             return mat

@@ -2165,6 +2165,8 @@ def gaussian_pin_naive(
         raise ValueError("X must be an instance of MatrixNaiveBase32 or MatrixNaiveBase64.")
     _pin_refuse_constraints(constraints, "grpnet")
     _pin_backend(X, "X")
+    if getattr(X, "_kind", None) == "dense16":
+        _matrix._no_pieces(X, "gaussian_pin_naive")
     dtype = X.dtype
     s = gaussian_pin_naive_base()
     s._init_common(X, dtype, groups, alpha, penalty, screen_set, lmda_path, rsq, screen_beta, screen_is_active,

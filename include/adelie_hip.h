@@ -149,6 +149,19 @@ int adelie_hip_design_create_standardized(adelie_hip_design* src, const double* 
  * not owned, must outlive the design. */
 int adelie_hip_design_adopt_dense_dev(const void* dev_ptr, int64_t n, int64_t p, int dtype, int order,
                                       int device, adelie_hip_design** out);
+/* A dense (n,p) design kept 16-bit in HBM: IEEE half or bfloat16 values (`format`), column- or row-major (`order`), uploaded once
+ * as 2 bytes a value (create) or adopted in place from device memory (adopt: not owned, must outlive the design; any 2-byte
+ * aligned pointer).  No float32 / float64 copy is made, then or later.  The design's dtype is ADELIE_HIP_F32: every value is
+ * exactly a float32 value, is converted in registers, and all arithmetic is float32 (kernels_dense16.hip).  Offered on it: the
+ * matrix operations, adelie_hip_design_alias, the loss paths and the path solvers without constraints, which stay on their
+ * full-Gram engines (ADELIE_HIP_S_ENGINE_PANEL = 0).  Refused on it with an error, as on a design made of pieces: create_multi,
+ * create_standardized, create_derived, create_slice, create_concat / create_pieces, create_cov_lazy, impute, bvls / pinball
+ * solves, constraints, adelie_hip_block_build_test.  Additive: ADELIE_HIP_ABI_VERSION stays as it is. */
+enum adelie_hip_format16 { ADELIE_HIP_FMT_F16 = 0, ADELIE_HIP_FMT_BF16 = 1 };
+int adelie_hip_design_create_dense16(const void* host, int64_t n, int64_t p, int format, int order, int device,
+                                     adelie_hip_design** out);
+int adelie_hip_design_adopt_dense16_dev(const void* dev_ptr, int64_t n, int64_t p, int format, int order, int device,
+                                        adelie_hip_design** out);
 /* == adelie.matrix.snp_unphased over an adelie.io.snp_unphased file image
  * (matrix.py:1245-1298, io_snp_unphased.ipp:10-41): `snpdat` is the whole .snpdat byte image;
  * it is decoded once into a dense 2-bit-per-call column-major device layout. */
